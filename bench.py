@@ -6,10 +6,15 @@ rank's groups and (N > 1) the all-gather of the per-group records.  Workload = B
 config: OLS, 1M groups x n = 1000 x p = 8, inputs resident in HBM before the timed region; with N ranks
 the same 1M groups are partitioned across the ranks ("strong" scaling, BASELINE config 4).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (metric / roofline / cpu_baseline), see DESIGN.md "Measurement".
+Rank 0 prints ONE JSON line, see DESIGN.md "Measurement".  A plain run sets up, warms up, times the steps and reports
+the headline (metric / value / ms_per_step).  `--full` adds everything else, as the lines of earlier rounds had it: the
+per-step spread, the parity gate against the CPU oracle, the roofline from the library's kernel timers, the multi-rank
+audit (N > 1), the end-to-end leg from host memory and the CPU baseline.  `--dump-outputs DIR` writes what the timed
+path returned in its last step as DIR/<name>.npy (float64; a fixed, seeded sample of rows when the whole is larger than
+DUMP_LIMIT_BYTES), so that two builds can be compared output for output on identical inputs.
 """
 from __future__ import annotations
 
@@ -40,6 +45,9 @@ FP64_MFMA_PEAK_TFLOPS = 78.6
 # stays achieved / peak.
 MEASURED_STREAM_READ_GBS = 6390.0
 MEASURED_MFMA_F64_TFLOPS = 72.0
+# --dump-outputs: all arrays together stay below 64 MB (npy headers included)
+DUMP_LIMIT_BYTES = 60_000_000
+DUMP_SEED = 20240607
 
 
 def algorithmic_bytes_per_fit(n: int, p: int, weighted: bool, inference: bool) -> int:
@@ -297,6 +305,25 @@ def multi_rank_audit(pkg, ctx, dmod, sharded, core_all, lo, hi, G, p, kt, steps,
             "gather_ms": gather_ms}
 
 
+def dump_outputs(directory, arrays):
+    """Write {name: device tensor [rows, ...]} as DIR/<name>.npy in float64.  When the arrays together hold more than
+    DUMP_LIMIT_BYTES, the same fraction of every array's rows is kept: a sorted sample drawn with a fixed seed, so that runs
+    with the same arguments write the same rows.  Returns {name: [rows written, rows in all]}."""
+    os.makedirs(directory, exist_ok=True)
+    total = sum(t.numel() * 8 for t in arrays.values())
+    frac = min(1.0, DUMP_LIMIT_BYTES / total) if total else 1.0
+    written = {}
+    for name, t in arrays.items():
+        rows = t.shape[0]
+        keep = rows if frac >= 1.0 else int(rows * frac)
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, size=keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(directory, f"{name}.npy"), t.to(torch.float64).cpu().numpy())
+        written[name] = [keep, rows]
+    return written
+
+
 def launch_ranks(n: int) -> int:
     """Start `n` ranks of this script (one process per GPU) through torch.distributed.run on 127.0.0.1 and wait."""
     import socket
@@ -330,13 +357,19 @@ def main():
                     help="vif_agg: variance inflation factors (p OLS fits per group from one Gram matrix)")
     ap.add_argument("--predict", action="store_true",
                     help="fit + per-row predictions (*_fit_predict_agg); every 5th row is a prediction row (NULL y)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--end-to-end-row-log", action="store_true",
-                    help="also time the end-to-end leg with the aggregate state's row log on (the DuckDB arena's default budgets)")
+                    help="with --full: also time the end-to-end leg with the aggregate state's row log on (the DuckDB arena's default budgets)")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="skip the host-memory -> aggregate state -> records leg (p <= 8 only; reported as `end_to_end`)")
-    ap.add_argument("--parity-sample", type=int, default=1024)
+                    help="with --full: skip the host-memory -> aggregate state -> records leg (p <= 8 only; reported as `end_to_end`)")
+    ap.add_argument("--parity-sample", type=int, default=1024, help="with --full: groups per rank checked against the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-step spread, parity gate, roofline, multi-rank audit, end-to-end leg and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # bare `python bench.py --gpus N`: this process becomes the launcher.  It has made no GPU call (importing
@@ -424,9 +457,10 @@ def main():
     timed = sharded.contexts() if sharded.contexts() else [ctx]
     if ctx not in timed:
         timed.append(ctx)
-    for c in timed:
-        c.enable_timing(True)
-        c.collect_timing()
+    if args.full:
+        for c in timed:
+            c.enable_timing(True)
+            c.collect_timing()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -434,9 +468,10 @@ def main():
     marks = []                # an event at the end of every step's kernels (on the stream the step ran on): per-step spread
     for _ in range(args.steps):
         core_all, inf_all = step()
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record(sharded.last_stream() or torch.cuda.current_stream(dev))
-        marks.append(ev)
+        if args.full:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record(sharded.last_stream() or torch.cuda.current_stream(dev))
+            marks.append(ev)
     sharded.finish()          # every all-gather issued inside the timed region completes inside it
     torch.cuda.synchronize()
     if world > 1:
@@ -451,7 +486,7 @@ def main():
     # (no minimum: a step's END moves with how its tail interleaves with the next step's accumulate kernel, so the smallest
     # spacing of two marks is not the duration of any step; roofline.avg_launch_ms is the kernel's own average)
     kt = None
-    for c in timed:   # the sharded driver alternates between contexts: sum their kernel times
+    for c in (timed if args.full else []):   # the sharded driver alternates between contexts: sum their kernel times
         k = c.collect_timing()
         c.enable_timing(False)
         if kt is None:
@@ -461,14 +496,29 @@ def main():
             hi_ms = max(kt["accumulate_ms_max"], k["accumulate_ms_max"])
             kt = {key: kt[key] + k[key] for key in kt}
             kt["accumulate_ms_min"], kt["accumulate_ms_max"] = lo_ms, hi_ms
-    refined = ctx.last_refine_count() if not (args.window or args.vif) else 0
+    refined = ctx.last_refine_count() if args.full and not (args.window or args.vif) else 0
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearsal else dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (the gathered records: every group of every rank)
+        if args.vif:
+            arrays = {"vif": vif_buf}
+        elif args.window:
+            arrays = {"predictions": pred_buf}
+        elif args.predict:
+            arrays = {"core": core_all, "predictions": pred_buf}
+        else:
+            arrays = {"core": core_all, **({"inference": inf_all} if inf_all is not None else {})}
+        dumped = dump_outputs(args.dump_outputs, arrays)
+
     ok, cerr, derr = True, 0.0, 0.0
-    if args.vif:
+    if not args.full:
+        args.parity_sample = 0      # the parity gates below are checks of --full, not part of the headline
+    if args.full and args.vif:
         import oracle
         S = min(512, G_local)
         nr = int(offs[S].item())
@@ -479,7 +529,7 @@ def main():
         derr = float(np.max(np.abs(got[:, :p][fin] / ref[:, :p][fin] - 1.0))) if fin.any() else 0.0
         ok = ok and derr < 1e-6
         args.parity_sample = 0
-    if args.window:
+    if args.full and args.window:
         # parity gate of the window path: a few partitions against the oracle's O(n^2) refits
         import oracle
         S = min(8, G_local)
@@ -512,6 +562,27 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         fits_per_s = G * args.steps / elapsed
+        extra = {}
+        if args.vif:
+            extra = {"equivalent_ols_fits_per_sec": G * p * args.steps / elapsed}
+        if args.window or args.predict:
+            extra = {"rows_per_sec": G * n * args.steps / elapsed}
+        if args.window:
+            extra["row_fits_per_sec"] = G * n * args.steps / elapsed
+        out = {
+            "metric": "group_fits_per_sec", "value": fits_per_s if ok else None, "unit": "fits/s", **extra,
+            "ns_per_row": (elapsed / args.steps) * 1e9 / (G * n),
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
+            "data": "synthetic",
+            "config": {"workload": (f"vif_agg: {G} groups x n={n} x p={p}, device-resident grouped columns" if args.vif else "") or f"{args.model}_fit{'_predict' if (args.predict or args.window) else ''}{(' OVER (ROWS BETWEEN ' + ('UNBOUNDED' if frame[0] is None else str(frame[0])) + ' PRECEDING AND ' + str(frame[1]) + ' PRECEDING)') if args.window else '_agg'}: {G} groups x n={n} x p={p}, device-resident grouped columns, "
+                                   f"fit_intercept=true, compute_inference={str(args.inference).lower()}",
+                       "groups_total": G, "groups_per_gpu": G_local, "rows_per_group": n, "features": p,
+                       "partition": f"contiguous key ranges over {world} rank(s); all-gather of {p + 6}-double records"},
+        }
+        if dumped is not None:
+            out["dumped_rows"] = dumped
+    if rank == 0 and args.full:
         bytes_fit = algorithmic_bytes_per_fit(n, p, weighted, args.inference)
         if args.vif:
             bytes_fit = 8 * n * p + 8 * (p + 1)     # the features once, the VIF record out
@@ -571,28 +642,14 @@ def main():
                     traffic = tj[f"{args.model}_n{n}_p{p}_bytes_per_group"] * G_local     # per step, like `achieved`
             except Exception:
                 traffic = None
-        extra = {}
-        if args.vif:
-            extra = {"equivalent_ols_fits_per_sec": G * p * args.steps / elapsed}
         if args.window:
-            extra = {"rows_per_sec": G * n * args.steps / elapsed, "row_fits_per_sec": G * n * args.steps / elapsed,
-                     "window_kernel_ms_per_step": kt["predict_ms"] / args.steps,
-                     "frames_refitted_with_refinement_last_step": ctx.last_window_refit_count()}
+            out.update({"window_kernel_ms_per_step": kt["predict_ms"] / args.steps,
+                        "frames_refitted_with_refinement_last_step": ctx.last_window_refit_count()})
         if args.predict:
-            extra = {"rows_per_sec": G * n * args.steps / elapsed, "predict_kernel_ms_per_step": kt["predict_ms"] / args.steps,
-                     "predict_GBps": G_local * n * (8 * p + 24) / (kt["predict_ms"] / args.steps * 1e-3) / 1e9
-                     if kt["predict_ms"] > 0 else 0.0}
-        out = {
-            "metric": "group_fits_per_sec", "value": fits_per_s if ok else None, "unit": "fits/s", **extra,
-            "ns_per_row": (elapsed / args.steps) * 1e9 / (G * n),
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "ms_per_step_median": step_ms_median,   # rank 0's own steps (HIP events at the end of every step)
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": (f"vif_agg: {G} groups x n={n} x p={p}, device-resident grouped columns" if args.vif else "") or f"{args.model}_fit{'_predict' if (args.predict or args.window) else ''}{(' OVER (ROWS BETWEEN ' + ('UNBOUNDED' if frame[0] is None else str(frame[0])) + ' PRECEDING AND ' + str(frame[1]) + ' PRECEDING)') if args.window else '_agg'}: {G} groups x n={n} x p={p}, device-resident grouped columns, "
-                                   f"fit_intercept=true, compute_inference={str(args.inference).lower()}",
-                       "groups_total": G, "groups_per_gpu": G_local, "rows_per_group": n, "features": p,
-                       "partition": f"contiguous key ranges over {world} rank(s); all-gather of {p + 6}-double records"},
+            out.update({"predict_kernel_ms_per_step": kt["predict_ms"] / args.steps,
+                        "predict_GBps": G_local * n * (8 * p + 24) / (kt["predict_ms"] / args.steps * 1e-3) / 1e9
+                        if kt["predict_ms"] > 0 else 0.0})
+        out.update({
             "parity": {"ok": ok, "sample_groups_per_rank": min(args.parity_sample, G_local),
                        "sample_windows": ([list(wd) for wd in sample_windows(G_local, args.parity_sample)]
                                           if args.parity_sample > 0 else None),
@@ -630,11 +687,12 @@ def main():
                          "exposed_non_accumulate_ms_per_step": exposed_ms,
                          # true only when (nearly) nothing of the solve is left outside the accumulate kernels' time
                          "solve_overlaps_next_accumulate": bool(exposed_ms <= 0.02 * ms_per_step)},
-        }
-    # ---- N > 1: what the SCALE record can be audited with (outside the timed region; the N = 1 path takes none of it).
+            "ms_per_step_median": step_ms_median,   # rank 0's own steps (HIP events at the end of every step)
+        })
+    # ---- N > 1 with --full: what the SCALE record can be audited with (outside the timed region; the N = 1 path takes none of it).
     # The audit is a sequence of collectives, one of them on a second RCCL communicator: should any of them never return,
     # a watchdog prints the line — the timing above is complete — and ends the rank instead of hanging the run.
-    if world > 1:
+    if world > 1 and args.full:
         import threading
         finished = threading.Event()
         audit_stage = ["(not started)"]      # the collective this rank entered last, for the watchdog's report
@@ -661,7 +719,7 @@ def main():
         if rank == 0 and multi is not None:
             out["multi_gpu"] = multi
     if rank == 0:
-        if world == 1 and p <= 8 and not (args.no_end_to_end or args.vif or args.window or args.predict or args.inference):
+        if args.full and world == 1 and p <= 8 and not (args.no_end_to_end or args.vif or args.window or args.predict or args.inference):
             # The pipelined driver of the timed loop (two more contexts, each with its own streams) is finished with: while its streams
             # exist the H2D copies of the leg below run at 47-48 GB/s instead of the 55 GB/s the same leg reaches in a process without
             # them (scripts/e2e_bisect.py: with the driver alive 47.6, after dropping it 55.0).  A DuckDB process holds the arena's
@@ -674,7 +732,7 @@ def main():
                     out["end_to_end_with_row_log"] = end_to_end_leg(pkg, ctx, offs, y, x_cols, w, opts, args.model, kw, G, n, p, with_row_log=True)
             except Exception as exc:      # the leg is an addition to the line, never a reason to lose it
                 out["end_to_end"] = {"error": str(exc)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(offs, y, x_cols, w, args.model, kw, n, p)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -14,7 +14,6 @@ import pytest
 
 from conftest import ROOT
 
-OUT = "/tmp/anofox_sanitize"
 TOOLS = os.path.join(ROOT, "tests", "tools")
 CSRC = os.path.join(ROOT, "anofox-statistics_amd", "csrc")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -23,31 +22,30 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 def _need_hipcc():
     if not os.path.exists(HIPCC):
         pytest.skip("needs hipcc")
-    os.makedirs(OUT, exist_ok=True)
 
 
-def test_dd_arith_host():
+def test_dd_arith_host(tmp_path):
     _need_hipcc()
-    exe = os.path.join(OUT, "dd_arith_check")
+    exe = os.path.join(tmp_path, "dd_arith_check")
     subprocess.check_call([HIPCC, "-O3", "-std=c++17", "-fno-fast-math", "-mfma", "--offload-arch=gfx950", "-I" + CSRC,
                            os.path.join(TOOLS, "dd_arith_check.hip"), "-o", exe], stderr=subprocess.DEVNULL)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
 
 
-def _fma_count(extra):
-    asm = os.path.join(OUT, "dd_probe%s.s" % ("_unguarded" if extra else ""))
+def _fma_count(out, extra):
+    asm = os.path.join(out, "dd_probe%s.s" % ("_unguarded" if extra else ""))
     subprocess.check_call([HIPCC, "-O3", "-std=c++17", "-fno-fast-math", "--offload-arch=gfx950", "-S", "--cuda-device-only",
                            "-I" + CSRC, *extra, os.path.join(TOOLS, "dd_arith_probe.hip"), "-o", asm], stderr=subprocess.DEVNULL)
     text = open(asm).read()
     return text.count("v_fma_f64"), text.count("v_mul_f64")
 
 
-def test_dd_arith_device_code():
+def test_dd_arith_device_code(tmp_path):
     _need_hipcc()
-    fma, mul = _fma_count([])
+    fma, mul = _fma_count(tmp_path, [])
     assert (fma, mul) == (1, 1), f"two_sum / two_prod of dd_arith.h: expected one v_fma_f64 and one v_mul_f64 per term, got {fma} / {mul}"
-    fma_unguarded, _ = _fma_count(["-DDD_UNGUARDED"])
+    fma_unguarded, _ = _fma_count(tmp_path, ["-DDD_UNGUARDED"])
     if fma_unguarded <= fma:
         pytest.skip("this hipcc does not contract the unguarded formulas: the probe cannot show the defect")
     assert fma_unguarded > fma

@@ -203,6 +203,53 @@ def test_bench_audit_watchdog_fails_the_run(tmp_path):
     assert "error" in rec["multi_gpu"] and rec["multi_gpu"]["rank0_pending_collective"]
 
 
+def test_bench_plain_run_dumps_the_timed_steps_records(tmp_path):
+    """A plain `python bench.py --dump-outputs DIR` (no --full): the line holds the headline figures and nothing of --full,
+    DIR/core.npy holds the records of the last timed step — bit for bit those of a plain fit_batch_device call on the same
+    synthetic inputs — and a second run writes the same file."""
+    import json
+    import multiprocessing as mp
+    import torch
+    G, n, p = 3000, 200, 8
+    mpc = mp.get_context("forkserver")
+    dumps = []
+    for k in range(2):
+        out, d = str(tmp_path / f"bench{k}.json"), str(tmp_path / f"dump{k}")
+        args = ["--groups", str(G), "--rows", str(n), "--steps", "3", "--warmup", "1", "--dump-outputs", d]
+        pr = mpc.Process(target=_run_bench_args, args=(out, args))
+        pr.start()
+        pr.join(300)
+        if pr.is_alive():
+            pr.kill()
+            pytest.fail("bench.py --dump-outputs did not finish")
+        assert pr.exitcode == 0
+        rec = json.loads([ln for ln in open(out).read().splitlines() if ln.startswith("{")][-1])
+        assert rec["metric"] == "group_fits_per_sec" and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["steps"] == 3
+        assert not {"parity", "roofline", "end_to_end", "cpu_baseline"} & set(rec)
+        assert rec["dumped_rows"] == {"core": [G, G]}
+        dumps.append(np.load(os.path.join(d, "core.npy")))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == (G, p + 6)
+    assert np.array_equal(dumps[0].view(np.int64), dumps[1].view(np.int64))
+    pkg = import_pkg()
+    synth = import_pkg("synth")
+    offs, y, x_cols, _ = synth.make_grouped(G, n, p, device="cuda:0", chunk_groups=max(1, min(32768, (1 << 25) // n)))
+    ctx = pkg.Context(0)
+    core, _ = ctx.fit_batch_device(offs, y, x_cols, None, pkg.RegressionOptions().batch_options("ols"))
+    torch.cuda.synchronize()
+    assert np.array_equal(dumps[0].view(np.int64), core.cpu().numpy().view(np.int64))
+    ctx.close()
+
+
+def _run_bench_args(out, args):
+    """Runs in a process forked from the clean fork server (no GPU state): a one-GPU bench.py with `args`."""
+    import subprocess
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    with open(out, "w") as f:
+        rc = subprocess.call([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *args], stdout=f, env=env)
+    sys.exit(rc)
+
+
 def _run_bench(out, extra_env=None):
     """Runs in a process forked from the clean fork server (no GPU state): exec is allowed here."""
     import subprocess
@@ -210,7 +257,7 @@ def _run_bench(out, extra_env=None):
     env.pop("WORLD_SIZE", None)
     with open(out, "w") as f:
         rc = subprocess.call([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--groups", "20000",
-                              "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], stdout=f, env=env)
+                              "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"], stdout=f, env=env)
     sys.exit(rc)
 
 

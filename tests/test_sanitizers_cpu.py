@@ -17,20 +17,23 @@ import pytest
 
 from conftest import ROOT
 
-OUT = "/tmp/anofox_sanitize"
-
 
 @pytest.fixture(scope="module")
-def built():
+def built(tmp_path_factory):
     if not shutil.which("g++") or not os.path.isdir("/opt/rocm/include/hip"):
         pytest.skip("needs g++ and the HIP headers")
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "tools"), f"OUT={OUT}"], stdout=subprocess.DEVNULL)
-    return OUT
+    # a directory of this run's own: a fixed path shared by every user of the machine may belong to someone else
+    out = str(tmp_path_factory.mktemp("anofox_sanitize"))
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "tools"), f"OUT={out}"], stdout=subprocess.DEVNULL)
+    return out
 
 
 @pytest.mark.parametrize("unit", ["oracle_sanitize", "host_sanitize", "arena_sanitize", "glue_sanitize"])
 def test_sanitizer_unit(built, unit):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    if unit == "host_sanitize" and os.path.exists("/dev/kfd"):
+        # its compute calls are meant to end at "no HIP device": with a GPU they reach the host build's stubbed launchers
+        pytest.skip("host_sanitize checks the library's no-device path: a GPU is present")
+    env =dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     env.pop("LD_PRELOAD", None)
     r = subprocess.run([os.path.join(built, unit)], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
