@@ -17,9 +17,9 @@ from .aggregate import (StreamingStates, FitAggResult, FitPredictAggResult, OlsF
                         ols_fit_predict_agg, ridge_fit_agg, ridge_fit_predict_agg, wls_fit_agg, wls_fit_predict_agg,
                         result_from_records, ols_fit_predict, ridge_fit_predict, wls_fit_predict, vif_agg,
                         residuals_diagnostics_agg)
-from .options import InvalidInputException, RegressionOptions, parse_options  # noqa: E402
-from .runtime import AggState, Context, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
-from .scalar import aic, bic, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
+from .options import ElasticNetOptions, InvalidInputException, RegressionOptions, parse_elasticnet_options, parse_options  # noqa: E402
+from .runtime import AggState, Context, elasticnet_fit_batch_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
+from .scalar import aic, bic, elasticnet_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
 # src/scalar_functions/{aic_bic,vif}.cpp) and the deprecated aggregate aliases
@@ -27,6 +27,7 @@ SQL_FUNCTIONS.update({
     "anofox_stats_ols_fit": ols_fit, "ols_fit": ols_fit,
     "anofox_stats_ridge_fit": ridge_fit, "ridge_fit": ridge_fit,
     "anofox_stats_wls_fit": wls_fit, "wls_fit": wls_fit,
+    "anofox_stats_elasticnet_fit": elasticnet_fit, "elasticnet_fit": elasticnet_fit,
     "anofox_stats_predict": predict,
     "anofox_stats_aic": aic, "aic": aic, "anofox_stats_bic": bic, "bic": bic,
     "anofox_stats_vif": vif, "vif": vif,
@@ -42,6 +43,7 @@ __all__ = [
     "ols_fit_predict_agg", "ridge_fit_predict_agg", "wls_fit_predict_agg", "predict", "predict_with_interval",
     "t_critical", "fit_predict_expanding_host", "fit_predict_window_host", "ols_fit_predict", "ridge_fit_predict", "wls_fit_predict",
     "vif", "vif_agg", "vif_batch_host", "residuals_diagnostics", "residuals_diagnostics_agg", "residuals_batch_host",
+    "ElasticNetOptions", "elasticnet_fit", "elasticnet_fit_batch_host", "parse_elasticnet_options",
 ]
 
 

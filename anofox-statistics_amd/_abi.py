@@ -102,6 +102,16 @@ class AnofoxResidualsResult(C.Structure):  # anofox_stats_ffi.h:527-536
                 ("has_standardized", C.c_bool), ("has_studentized", C.c_bool), ("has_leverage", C.c_bool)]
 
 
+class AnofoxElasticNetOptions(C.Structure):  # anofox_stats_ffi.h:384-397, 40 bytes
+    _fields_ = [("alpha", C.c_double), ("l1_ratio", C.c_double), ("fit_intercept", C.c_bool),
+                ("max_iterations", C.c_uint32), ("tolerance", C.c_double), ("lambda_scaling", C.c_int)]
+
+
+class AnofoxHipElasticNetBatchOptions(C.Structure):
+    _fields_ = [("fit_intercept", C.c_bool), ("alpha", C.c_double), ("l1_ratio", C.c_double),
+                ("max_iterations", C.c_uint32), ("tolerance", C.c_double), ("lambda_scaling", C.c_int)]
+
+
 # every symbol include/anofox_stats_hip.h declares: name -> (restype, argtypes)
 _ERRP = C.POINTER(AnofoxError)
 _CTX = C.c_void_p
@@ -217,6 +227,14 @@ SYMBOLS = {
     "anofox_hip_agg_state_import_slots_host": (C.c_bool, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, _ERRP]),
     "anofox_hip_agg_state_finalize_host": (C.c_bool, [C.c_void_p, C.c_int64, _DP, _DP, C.POINTER(C.c_int64), C.c_void_p, _ERRP]),
     "anofox_hip_agg_state_finalize_device": (C.c_bool, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_elasticnet_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxElasticNetOptions,
+                                         C.POINTER(AnofoxFitResultCore), _ERRP]),
+    "anofox_hip_elasticnet_fit_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                          C.POINTER(C.c_void_p), AnofoxHipElasticNetBatchOptions, C.c_void_p,
+                                                          C.c_void_p, _ERRP]),
+    "anofox_hip_elasticnet_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                        C.POINTER(_DP), AnofoxHipElasticNetBatchOptions, _DP,
+                                                        C.POINTER(C.c_int32), _ERRP]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "anofox_hip_host_free": (None, [C.c_void_p]),
 }

@@ -58,6 +58,22 @@ void agg_state_detach(struct AnofoxHipAggState *s); // agg_state.hip
 bool refit_groups_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
                          const double *d_y, const double *const *x_cols, const double *d_w, const AnofoxHipBatchOptions &opt,
                          double *d_core, double *d_inf, AnofoxError *e);
+// What follows the accumulate kernels of one launch of the batch path (host_api.hip): the regression models' solve and
+// refinement chain, or another model's solve on the same moment records (elasticnet.hip).  `narrow` runs once on the
+// narrow records (p <= 8, the context's stream), `wide` once per slab of wide records on the solve stream `st`; `slab`
+// is the call's largest slab.
+struct SolveStages {
+	bool (*narrow)(AnofoxHipContext *ctx, BatchArgs &a, hipStream_t st, void *user, AnofoxError *e);
+	bool (*wide)(AnofoxHipContext *ctx, WideArgs &a, hipStream_t st, int64_t slab, void *user, AnofoxError *e);
+	void *user;
+};
+// host_api.hip: the device batch path with the accumulate dispatch of an unweighted fit (opt.model, fit_intercept) and
+// `stages` after it; enqueued on the context's stream
+bool moment_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
+                         const double *d_y, const double *const *x_cols, const AnofoxHipBatchOptions &opt, const SolveStages &stages,
+                         double *d_core, AnofoxError *e);
+// host_api.hip: the calling thread's default context on the current device (the host entry points' ctx == NULL)
+AnofoxHipContext *thread_default_context(AnofoxError *e);
 }
 }
 

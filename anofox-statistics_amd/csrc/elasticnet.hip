@@ -1,0 +1,633 @@
+// elasticnet.hip — grouped elastic net fits: a batched covariance-mode coordinate-descent solve on the moment records of
+// the accumulate kernels, and the entry points anofox_hip_elasticnet_fit_batch_{device,host} / anofox_elasticnet_fit.
+//
+// Reference: fit_elasticnet (crates/anofox-stats-core/src/models/elasticnet.rs:29-200): alpha / l1_ratio checks, the row
+// filter (finite y and x, no weights), the constant-column test |x - x_first| < 1e-10, the intercept-only shortcut and
+// NaN coefficients at constant columns.  Per group ("Elastic net") the solve minimises
+//     1/2 sum_i (y_i - b0 - x_i'b)^2 + lam (l1 sum |b_j| + (1 - l1)/2 sum b_j^2)
+// over the non-constant columns.  With an intercept C / c are the centred X'X / X'y (the records are shifted by the first
+// valid row, so centring is exact), without one the raw moments.  Cyclic coordinate descent from b = 0 in column order:
+//     b_j <- S(c_j - sum_{k != j} C_jk b_k, lam l1) / (C_jj + lam (1 - l1))
+// until a full sweep moves no coefficient by more than tolerance sqrt(S_yy / C_jj), or max_iterations sweeps.
+//   narrow (p <= 8): one LANE per group, C, c and b in registers, the sum formed afresh at every step;
+//   wide (9 <= p <= 128): one WAVEFRONT per group, C column-major in LDS, lane k owns b_k and the gradient
+//     r_k = c_k - (C b)_k (and k + 64): a coordinate step is a broadcast of r_j, b_j and an axpy of column j into r.
+// Statistics as the ridge record (solve_narrow.hip): rss = S_yy - 2 b'c + b'C b; where that falls below 1e-7 of the
+// total sum of squares it has cancelled, and rows_rss_kernel sums the squared residuals y - b0 - x'b from the rows.
+// No atomics: every group is a lane's or a wavefront's own work, so repeated calls give bit-identical records.
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "common.h"
+
+using namespace anofox;
+
+#include "context.h"
+
+using namespace anofox::host;
+
+namespace {
+
+constexpr double kEnRefineTol = 1e-7; // rss / tss below this => rss from the rows
+
+struct EnParams {
+	double alpha, l1_ratio, tolerance;
+	int max_iterations;
+	int lambda_scaling;
+	int32_t *iterations; // [G] or nullptr: sweeps, negated when the limit stopped the group
+};
+
+__device__ __forceinline__ double en_nan() { return __builtin_nan(""); }
+__device__ __forceinline__ double soft_threshold(double z, double t) { return z > t ? z - t : (z < -t ? z + t : 0.0); }
+
+// The checks every group passes before its solve (elasticnet.rs:33-136 and the aggregate's "< 2 rows -> NULL" rule).
+// Returns the status; 0 with *shortcut = true is the intercept-only fit (en_write_shortcut).
+__device__ __forceinline__ int en_prechecks(const EnParams &en, int64_t nrows, double cnt, int p_eff, bool icpt, bool *shortcut) {
+	*shortcut = false;
+	if (nrows < 2) return ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS;                            // the aggregate's NULL rule
+	if (!(en.alpha >= 0.0)) return ANOFOX_ERROR_INVALID_ALPHA;                             // elasticnet.rs:34-36
+	if (!(en.l1_ratio >= 0.0 && en.l1_ratio <= 1.0)) return ANOFOX_ERROR_INVALID_L1_RATIO; // elasticnet.rs:39-41
+	if (!(cnt > 0.0)) return ANOFOX_ERROR_NO_VALID_DATA;                                   // elasticnet.rs:77-79
+	if (p_eff == 0) {                                                                      // elasticnet.rs:104-128
+		if (!icpt) return ANOFOX_ERROR_INSUFFICIENT_DATA;
+		*shortcut = true;
+		return 0;
+	}
+	if (cnt < (double)(p_eff + (icpt ? 1 : 0))) return ANOFOX_ERROR_INSUFFICIENT_DATA; // elasticnet.rs:131-136
+	return 0;
+}
+
+// every column constant, with an intercept: NaN coefficients, the mean, r2 = adj = 0, sd(y) with n - 1 (elasticnet.rs:110-128)
+__device__ __forceinline__ void en_write_shortcut(double *core, int p, double ymean, double cyy_c, double cnt) {
+	for (int k = 0; k < p; ++k) core[k] = en_nan();
+	core[p] = ymean;
+	core[p + 1] = 0.0;
+	core[p + 2] = 0.0;
+	core[p + 3] = sqrt(cyy_c / (cnt - 1.0));
+	core[p + 4] = cnt;
+	core[p + 5] = 0.0;
+}
+
+__device__ __forceinline__ void en_write_status(double *core, int p, int status) {
+	for (int k = 0; k < p + 5; ++k) core[k] = en_nan();
+	core[p + 5] = (double)status;
+}
+
+// penalty: raw lam = alpha; glmnet lam = n alpha / sd_y, sd_y about the mean with or without an intercept (the ridge rule,
+// solve_narrow.hip).  The L1 / L2 parts, with 0 where their share is 0 (an infinite lam times 0 is not NaN).
+__device__ __forceinline__ void en_penalty(const EnParams &en, double cnt, double cyy_c, double *pen1, double *pen2) {
+	const double lam = en.lambda_scaling == ANOFOX_LAMBDA_SCALING_GLMNET ? cnt * en.alpha / sqrt(cyy_c / cnt) : en.alpha;
+	*pen1 = en.l1_ratio > 0.0 ? lam * en.l1_ratio : 0.0;
+	*pen2 = en.l1_ratio < 1.0 ? lam * (1.0 - en.l1_ratio) : 0.0;
+}
+
+// r2 / adj / rse / n of a finished fit (the ridge record's formulas, df from the non-constant columns); queued groups get
+// their tss parked in the r2 slot and flag 1 for rows_rss_kernel
+__device__ __forceinline__ void en_write_stats(double *core, int p, double rss, double tss, double cnt, int p_eff, bool icpt,
+                                               int32_t *flag) {
+	const double df = cnt - (double)(p_eff + (icpt ? 1 : 0));
+	const bool cancels = !(rss > kEnRefineTol * tss);
+	const double r2 = 1.0 - rss / tss;
+	core[p + 1] = cancels ? tss : r2;
+	core[p + 2] = 1.0 - (1.0 - r2) * (cnt - (icpt ? 1.0 : 0.0)) / df;
+	core[p + 3] = sqrt(rss / df);
+	core[p + 4] = cnt;
+	core[p + 5] = 0.0;
+	*flag = cancels ? 1 : 0;
+}
+
+// ---- narrow: one lane per group ----
+template <int P>
+__global__ __launch_bounds__(64) void en_solve_narrow_kernel(BatchArgs a, EnParams en) {
+	using L = MomentLayout<P>;
+	const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (g >= a.n_groups) return;
+	const bool icpt = a.fit_intercept != 0;
+	const double *rec = a.moments + g * (int64_t)L::REC;
+	double *core = a.core + g * (int64_t)(P + 6);
+	a.refine_list[g] = 0;
+	const int64_t nrows = a.row_offsets[g + 1] - a.row_offsets[g];
+	const double cnt = rec[L::OFF_CNT], sw = rec[L::OFF_SW];
+	const unsigned mask = (unsigned)rec[L::OFF_MASK];
+	const int p_eff = __popc(mask);
+	const double sy = rec[L::OFF_S + P], qyy = rec[L::q_index(P, P)];
+	const double cyy_c = qyy - sy * sy / sw;
+	const double ymean = (icpt ? rec[L::OFF_FIRST + P] : 0.0) + sy / sw;
+	bool shortcut;
+	const int status = en_prechecks(en, nrows, cnt, p_eff, icpt, &shortcut);
+	if (status != 0 || shortcut) {
+		if (status != 0) en_write_status(core, P, status);
+		else en_write_shortcut(core, P, ymean, cyy_c, cnt);
+		if (en.iterations) en.iterations[g] = 0;
+		return;
+	}
+	double C[P][P], c[P], b[P], xbar[P];
+#pragma unroll
+	for (int i = 0; i < P; ++i) {
+		const double si = rec[L::OFF_S + i];
+		xbar[i] = (icpt ? rec[L::OFF_FIRST + i] : 0.0) + si / sw;
+#pragma unroll
+		for (int j = 0; j <= i; ++j) {
+			const double v = rec[L::q_index(j, i)] - (icpt ? si * rec[L::OFF_S + j] / sw : 0.0);
+			C[i][j] = v;
+			C[j][i] = v;
+		}
+		c[i] = rec[L::q_index(i, P)] - (icpt ? si * sy / sw : 0.0);
+		b[i] = 0.0;
+	}
+	const double tss = icpt ? cyy_c : qyy;
+	double pen1, pen2;
+	en_penalty(en, cnt, cyy_c, &pen1, &pen2);
+	const double thresh = en.tolerance * sqrt(tss);
+	int sweeps = 0;
+	bool converged = false;
+	while (sweeps < en.max_iterations) {
+		++sweeps;
+		double dmax = 0.0;
+#pragma unroll
+		for (int j = 0; j < P; ++j) {
+			if (!((mask >> j) & 1u)) continue;
+			double z = c[j];
+#pragma unroll
+			for (int k = 0; k < P; ++k)
+				if (k != j) z -= C[j][k] * b[k];
+			const double bn = soft_threshold(z, pen1) / (C[j][j] + pen2);
+			dmax = fmax(dmax, sqrt(C[j][j]) * fabs(bn - b[j]));
+			b[j] = bn;
+		}
+		if (dmax <= thresh) { converged = true; break; }
+	}
+	double bc = 0.0, bcb = 0.0, b0 = ymean;
+#pragma unroll
+	for (int i = 0; i < P; ++i) {
+		double cbi = 0.0;
+#pragma unroll
+		for (int k = 0; k < P; ++k) cbi += C[i][k] * b[k];
+		bc += b[i] * c[i];
+		bcb += b[i] * cbi;
+		b0 -= b[i] * xbar[i];
+	}
+#pragma unroll
+	for (int j = 0; j < P; ++j) core[j] = ((mask >> j) & 1u) ? b[j] : en_nan();
+	core[P] = icpt ? b0 : en_nan();
+	en_write_stats(core, P, tss - 2.0 * bc + bcb, tss, cnt, p_eff, icpt, &a.refine_list[g]);
+	if (en.iterations) en.iterations[g] = converged ? sweeps : -sweeps;
+}
+
+// ---- wide: one wavefront per group, C in LDS ----
+// R = rows of C per lane (1: p <= 64, 2: p <= 128)
+template <int R>
+__global__ __launch_bounds__(64) void en_solve_wide_kernel(WideArgs a, EnParams en) {
+	extern __shared__ double en_lds[]; // [p * p] column-major C, then [p] active flags (as doubles)
+	const int p = a.p;
+	const int T = wide_tiles(p), P16 = 16 * T, NT = T * (T + 1) / 2;
+	const int lane = threadIdx.x;
+	const int64_t gl = blockIdx.x;
+	const int64_t g = a.group_base + gl;
+	const bool icpt = a.fit_intercept != 0;
+	const double *rec = a.moments + gl * (int64_t)wide_record_len(T);
+	const double *vec = rec + (int64_t)NT * 256;
+	const double *sx = vec, *sxy = vec + P16, *fx = vec + 2 * P16, *nonconst = vec + 3 * P16;
+	const double *sc = vec + 4 * P16;
+	double *core = a.core + g * (int64_t)(p + 6);
+	const double sy = sc[0], syy = sc[1], sw = sc[2], cnt = sc[3], first_y = sc[4];
+	const int64_t nrows = a.row_offsets[g + 1] - a.row_offsets[g];
+	int p_eff = 0;
+	for (int j = 0; j < p; ++j) p_eff += nonconst[j] != 0.0 ? 1 : 0;
+	const double cyy_c = syy - sy * sy / sw;
+	const double ymean = (icpt ? first_y : 0.0) + sy / sw;
+	if (lane == 0) a.refine_list[gl] = 0;
+	bool shortcut;
+	const int status = en_prechecks(en, nrows, cnt, p_eff, icpt, &shortcut); // (uniform: lane 0 writes)
+	if (status != 0 || shortcut) {
+		if (lane == 0) {
+			if (status != 0) en_write_status(core, p, status);
+			else en_write_shortcut(core, p, ymean, cyy_c, cnt);
+			if (en.iterations) en.iterations[g] = 0;
+		}
+		return;
+	}
+	double *Cs = en_lds;
+	double *act = en_lds + (size_t)p * p;
+	const double inv_sw = 1.0 / sw;
+	for (int idx = lane; idx < p * p; idx += 64) {
+		const int j = idx / p, k = idx - j * p; // Cs[j * p + k] = C[k][j]
+		const int lo = j < k ? j : k, hi = j < k ? k : j;
+		const int I = lo >> 4, J = hi >> 4;
+		const int tile = I * T - I * (I - 1) / 2 + (J - I);
+		double v = rec[(int64_t)tile * 256 + (lo & 15) * 16 + (hi & 15)];
+		if (icpt) v -= sx[lo] * sx[hi] * inv_sw;
+		Cs[idx] = v;
+	}
+	for (int j = lane; j < p; j += 64) act[j] = nonconst[j] != 0.0 ? 1.0 : 0.0;
+	__syncthreads();
+
+	double r[R], b[R], cc[R];
+#pragma unroll
+	for (int h = 0; h < R; ++h) {
+		const int k = lane + 64 * h;
+		cc[h] = k < p ? (icpt ? sxy[k] - sx[k] * sy * inv_sw : sxy[k]) : 0.0;
+		r[h] = cc[h];
+		b[h] = 0.0;
+	}
+	const double tss = icpt ? cyy_c : syy;
+	double pen1, pen2;
+	en_penalty(en, cnt, cyy_c, &pen1, &pen2);
+	const double thresh = en.tolerance * sqrt(tss);
+	int sweeps = 0;
+	bool converged = false;
+	while (sweeps < en.max_iterations) {
+		++sweeps;
+		double dmax = 0.0;
+		for (int j = 0; j < p; ++j) {
+			if (act[j] == 0.0) continue;
+			const int owner = j & 63, h = j >> 6;
+			const double rsel = (R == 1 || h == 0) ? r[0] : r[R - 1];
+			const double bsel = (R == 1 || h == 0) ? b[0] : b[R - 1];
+			const double rj = __shfl(rsel, owner, 64), bj = __shfl(bsel, owner, 64);
+			const double cjj = Cs[j * p + j];
+			const double bn = soft_threshold(rj + cjj * bj, pen1) / (cjj + pen2);
+			const double d = bn - bj;
+			dmax = fmax(dmax, sqrt(cjj) * fabs(d));
+			if (d != 0.0) {
+				const double *col = Cs + j * p;
+#pragma unroll
+				for (int hh = 0; hh < R; ++hh) {
+					const int k = lane + 64 * hh;
+					if (k < p) r[hh] = fma(-col[k], d, r[hh]);
+				}
+				if (lane == owner) {
+					if (R == 1 || h == 0) b[0] = bn;
+					else b[R - 1] = bn;
+				}
+			}
+		}
+		if (dmax <= thresh) { converged = true; break; }
+	}
+	// rss = S_yy - 2 b'c + b'C b = S_yy - b'(c + r), with C b = c - r; intercept from the column means
+	double s_bcr = 0.0, s_bx = 0.0;
+#pragma unroll
+	for (int h = 0; h < R; ++h) {
+		const int k = lane + 64 * h;
+		if (k < p) {
+			s_bcr += b[h] * (cc[h] + r[h]);
+			s_bx += b[h] * (fx[k] * (icpt ? 1.0 : 0.0) + sx[k] * inv_sw);
+		}
+	}
+	for (int m = 32; m >= 1; m >>= 1) {
+		s_bcr += __shfl_xor(s_bcr, m, 64);
+		s_bx += __shfl_xor(s_bx, m, 64);
+	}
+#pragma unroll
+	for (int h = 0; h < R; ++h) {
+		const int k = lane + 64 * h;
+		if (k < p) core[k] = act[k] != 0.0 ? b[h] : en_nan();
+	}
+	if (lane == 0) {
+		core[p] = icpt ? ymean - s_bx : en_nan();
+		en_write_stats(core, p, tss - s_bcr, tss, cnt, p_eff, icpt, &a.refine_list[gl]);
+		if (en.iterations) en.iterations[g] = converged ? sweeps : -sweeps;
+	}
+}
+
+// ---- rss from the rows of the groups whose moment identity cancelled (flag[gl] == 1), one wavefront per group ----
+struct RowsArgs {
+	const int64_t *row_offsets;
+	const double *y;
+	const double *x_table[kWideMaxP];
+	double *core;
+	const int32_t *flag; // [n_groups] of this launch
+	int64_t group_base, n_groups;
+	int p;
+	int fit_intercept;
+};
+
+__global__ __launch_bounds__(64) void rows_rss_kernel(RowsArgs a) {
+	const int lane = threadIdx.x;
+	const int p = a.p;
+	for (int64_t gl = blockIdx.x; gl < a.n_groups; gl += gridDim.x) {
+		if (a.flag[gl] == 0) continue;
+		const int64_t g = a.group_base + gl;
+		double *core = a.core + g * (int64_t)(p + 6);
+		const double b0 = a.fit_intercept ? core[p] : 0.0;
+		int p_eff = 0;
+		for (int j = 0; j < p; ++j) p_eff += isnan(core[j]) ? 0 : 1;
+		double rss = 0.0;
+		for (int64_t row = a.row_offsets[g] + lane; row < a.row_offsets[g + 1]; row += 64) {
+			const double yv = a.y[row];
+			bool ok = isfinite(yv);
+			double fit = b0;
+			for (int j = 0; j < p; ++j) {
+				const double xv = a.x_table[j][row];
+				ok = ok && isfinite(xv);
+				const double bj = core[j];
+				if (!isnan(bj)) fit = fma(bj, xv, fit);
+			}
+			const double e = yv - fit;
+			if (ok) rss = fma(e, e, rss);
+		}
+		for (int m = 32; m >= 1; m >>= 1) rss += __shfl_xor(rss, m, 64);
+		if (lane == 0) {
+			const bool icpt = a.fit_intercept != 0;
+			const double tss = core[p + 1], cnt = core[p + 4]; // tss parked by the solve
+			const double df = cnt - (double)(p_eff + (icpt ? 1 : 0));
+			const double r2 = 1.0 - rss / tss;
+			core[p + 1] = r2;
+			core[p + 2] = 1.0 - (1.0 - r2) * (cnt - (icpt ? 1.0 : 0.0)) / df;
+			core[p + 3] = sqrt(rss / df);
+		}
+	}
+}
+
+template <int P>
+hipError_t launch_en_narrow_p(const BatchArgs &a, const EnParams &en, hipStream_t st) {
+	hipLaunchKernelGGL((en_solve_narrow_kernel<P>), dim3((unsigned)((a.n_groups + 63) / 64)), dim3(64), 0, st, a, en);
+	return hipGetLastError();
+}
+
+hipError_t launch_en_narrow(const BatchArgs &a, const EnParams &en, hipStream_t st) {
+	switch (a.p) {
+	case 1: return launch_en_narrow_p<1>(a, en, st);
+	case 2: return launch_en_narrow_p<2>(a, en, st);
+	case 3: return launch_en_narrow_p<3>(a, en, st);
+	case 4: return launch_en_narrow_p<4>(a, en, st);
+	case 5: return launch_en_narrow_p<5>(a, en, st);
+	case 6: return launch_en_narrow_p<6>(a, en, st);
+	case 7: return launch_en_narrow_p<7>(a, en, st);
+	case 8: return launch_en_narrow_p<8>(a, en, st);
+	default: return hipErrorInvalidValue;
+	}
+}
+
+hipError_t launch_en_wide(const WideArgs &a, const EnParams &en, hipStream_t st) {
+	const size_t lds = ((size_t)a.p * a.p + (size_t)a.p) * sizeof(double);
+	static const bool attr_set = [] {
+		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&en_solve_wide_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&en_solve_wide_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+		return true;
+	}();
+	(void)attr_set;
+	if (a.p <= 64) hipLaunchKernelGGL((en_solve_wide_kernel<1>), dim3((unsigned)a.n_groups), dim3(64), lds, st, a, en);
+	else hipLaunchKernelGGL((en_solve_wide_kernel<2>), dim3((unsigned)a.n_groups), dim3(64), lds, st, a, en);
+	return hipGetLastError();
+}
+
+hipError_t launch_rows_rss(const RowsArgs &ra, hipStream_t st) {
+	const unsigned grid = ra.n_groups < 16384 ? (unsigned)ra.n_groups : 16384u;
+	hipLaunchKernelGGL(rows_rss_kernel, dim3(grid), dim3(64), 0, st, ra);
+	return hipGetLastError();
+}
+
+// the solve stages handed to the batch path (host_api.hip: moment_batch_device)
+bool en_narrow_stage(AnofoxHipContext *, BatchArgs &a, hipStream_t st, void *user, AnofoxError *e) {
+	const EnParams &en = *static_cast<const EnParams *>(user);
+	if (hip_fail(launch_en_narrow(a, en, st), "elastic net solve kernel launch", e)) return false;
+	RowsArgs ra;
+	memset(&ra, 0, sizeof ra);
+	ra.row_offsets = a.row_offsets;
+	ra.y = a.y;
+	for (int j = 0; j < a.p; ++j) ra.x_table[j] = a.x[j];
+	ra.core = a.core;
+	ra.flag = a.refine_list;
+	ra.group_base = 0;
+	ra.n_groups = a.n_groups;
+	ra.p = a.p;
+	ra.fit_intercept = a.fit_intercept;
+	return !hip_fail(launch_rows_rss(ra, st), "elastic net rows kernel launch", e);
+}
+
+bool en_wide_stage(AnofoxHipContext *, WideArgs &a, hipStream_t st, int64_t, void *user, AnofoxError *e) {
+	const EnParams &en = *static_cast<const EnParams *>(user);
+	if (hip_fail(launch_en_wide(a, en, st), "elastic net solve kernel launch", e)) return false;
+	RowsArgs ra;
+	memset(&ra, 0, sizeof ra);
+	ra.row_offsets = a.row_offsets;
+	ra.y = a.y;
+	for (int j = 0; j < a.p; ++j) ra.x_table[j] = a.x_table[j];
+	ra.core = a.core;
+	ra.flag = a.refine_list;
+	ra.group_base = a.group_base;
+	ra.n_groups = a.n_groups;
+	ra.p = a.p;
+	ra.fit_intercept = a.fit_intercept;
+	return !hip_fail(launch_rows_rss(ra, st), "elastic net rows kernel launch", e);
+}
+
+bool validate_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols,
+                 const AnofoxHipElasticNetBatchOptions &o, const void *core, AnofoxError *e) {
+	if (!ctx) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
+	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
+	if (p > (size_t)kWideMaxP) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT,
+		          "n_features = " + std::to_string(p) + " exceeds the supported maximum of " + std::to_string(kWideMaxP));
+		return false;
+	}
+	if (G > 0 && (!off || !y || !core)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets, y or core is NULL"); return false; }
+	for (size_t j = 0; j < p; ++j)
+		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
+	if (!(o.tolerance >= 0.0)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "tolerance must be >= 0"); return false; }
+	if ((int)o.lambda_scaling != ANOFOX_LAMBDA_SCALING_RAW && (int)o.lambda_scaling != ANOFOX_LAMBDA_SCALING_GLMNET) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "unknown lambda_scaling");
+		return false;
+	}
+	return true;
+}
+
+bool run_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y, const double *const *x_cols,
+            const AnofoxHipElasticNetBatchOptions &o, double *d_core, int32_t *d_iterations, AnofoxError *e) {
+	if (G == 0) return true;
+	EnParams en;
+	en.alpha = o.alpha;
+	en.l1_ratio = o.l1_ratio;
+	en.tolerance = o.tolerance;
+	en.max_iterations = o.max_iterations > 0x7fffffffu ? 0x7fffffff : (int)o.max_iterations;
+	en.lambda_scaling = (int)o.lambda_scaling;
+	en.iterations = d_iterations;
+	AnofoxHipBatchOptions acc; // the moments of an unweighted fit
+	memset(&acc, 0, sizeof acc);
+	acc.model = ANOFOX_HIP_MODEL_OLS;
+	acc.fit_intercept = o.fit_intercept;
+	acc.confidence_level = 0.95;
+	acc.hc_type = ANOFOX_HC_NONE;
+	const SolveStages stages = {en_narrow_stage, en_wide_stage, &en};
+	// (the stages run before this call returns: `en` is captured by value into the kernel arguments at launch)
+	return moment_batch_device(ctx, G, p, n_rows, d_off, d_y, x_cols, acc, stages, d_core, e);
+}
+
+std::string fmt_g(double v) {
+	char buf[64];
+	snprintf(buf, sizeof buf, "%g", v);
+	return buf;
+}
+
+} // namespace
+
+extern "C" {
+
+bool anofox_hip_elasticnet_fit_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                            const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                            AnofoxHipElasticNetBatchOptions options, double *d_core, int32_t *d_iterations,
+                                            AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!validate_en(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, options, d_core, out_error)) return false;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	const bool ok = run_en(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, options, d_core, d_iterations, out_error);
+	ctx->gate_wait = ctx->gate_record = nullptr; // the gate never outlives the call it was set for
+	return ok;
+}
+
+bool anofox_hip_elasticnet_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                          const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                          AnofoxHipElasticNetBatchOptions options, double *core, int32_t *iterations,
+                                          AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!ctx) {
+		ctx = thread_default_context(out_error);
+		if (!ctx) return false;
+	}
+	if (!validate_en(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, options, core, out_error)) return false;
+	if (n_groups == 0) return true;
+	for (int64_t g = 0; g < n_groups; ++g) {
+		if (row_offsets[g + 1] < row_offsets[g] || row_offsets[g] < 0 || row_offsets[g + 1] > n_rows) {
+			set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing and within [0, n_rows]");
+			return false;
+		}
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	const size_t p = n_features, core_len = p + 6;
+	// the groups pass through the GPU in slabs of at most ~32M rows (as anofox_hip_fit_batch_host)
+	const int64_t slab_rows = 32ll << 20;
+	std::vector<int64_t> off;
+	int64_t g0 = 0;
+	while (g0 < n_groups) {
+		int64_t g1 = g0 + 1;
+		while (g1 < n_groups && row_offsets[g1 + 1] - row_offsets[g0] <= slab_rows) ++g1;
+		const int64_t G = g1 - g0;
+		const int64_t r0 = row_offsets[g0], R = row_offsets[g1] - r0;
+		off.resize((size_t)G + 1);
+		for (int64_t g = 0; g <= G; ++g) off[(size_t)g] = row_offsets[g0 + g] - r0;
+		const size_t b_off = align_up(((size_t)G + 1) * sizeof(int64_t), 256);
+		const size_t b_col = align_up(((size_t)R + 2) * sizeof(double), 256);
+		const size_t b_core = align_up((size_t)G * core_len * sizeof(double), 256);
+		const size_t b_it = align_up((size_t)G * sizeof(int32_t), 256);
+		if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, b_off + (p + 1) * b_col + b_core + b_it, "staging", out_error)) return false;
+		char *cur = (char *)ctx->stage;
+		int64_t *d_off = (int64_t *)cur;
+		cur += b_off;
+		hipStream_t st = ctx->stream;
+		if (hip_fail(hipMemcpyAsync(d_off, off.data(), ((size_t)G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D offsets", out_error)) return false;
+		const double *d_x[kWideMaxP];
+		for (size_t j = 0; j < p; ++j) {
+			if (R > 0 && hip_fail(hipMemcpyAsync(cur, x_cols[j] + r0, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st), "H2D x", out_error)) return false;
+			d_x[j] = (const double *)cur;
+			cur += b_col;
+		}
+		if (R > 0 && hip_fail(hipMemcpyAsync(cur, y + r0, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st), "H2D y", out_error)) return false;
+		const double *d_y = (const double *)cur;
+		cur += b_col;
+		double *d_core = (double *)cur;
+		cur += b_core;
+		int32_t *d_it = iterations ? (int32_t *)cur : nullptr;
+		if (!run_en(ctx, G, p, R, d_off, d_y, d_x, options, d_core, d_it, out_error)) return false;
+		if (hip_fail(hipMemcpyAsync(core + (size_t)g0 * core_len, d_core, (size_t)G * core_len * sizeof(double), hipMemcpyDeviceToHost, st), "D2H core", out_error)) return false;
+		if (d_it && hip_fail(hipMemcpyAsync(iterations + g0, d_it, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H iterations", out_error)) return false;
+		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
+		g0 = g1;
+	}
+	return true;
+}
+
+// A batch of one group with fit_single's conventions (host_api.hip): argument checks first, NULL entries -> NaN through the
+// validity bitmask, a one-row input padded with an all-NaN row (the batch applies the aggregate's "< 2 rows" rule), the
+// reference's error texts (crates/anofox-stats-core/src/errors.rs), the coefficients malloc'ed.
+bool anofox_elasticnet_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxElasticNetOptions options,
+                           AnofoxFitResultCore *out_core, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!out_core) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "out_core is NULL"); return false; }
+	if (!x || x_count == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
+	if (options.alpha < 0.0) { // elasticnet.rs:33-41: alpha, then l1_ratio, then the inputs
+		set_error(out_error, ANOFOX_ERROR_INVALID_ALPHA, "Invalid alpha parameter: " + fmt_g(options.alpha) + " (must be >= 0)");
+		return false;
+	}
+	if (options.l1_ratio < 0.0 || options.l1_ratio > 1.0) {
+		set_error(out_error, ANOFOX_ERROR_INVALID_L1_RATIO, "Invalid L1 ratio: " + fmt_g(options.l1_ratio) + " (must be in [0, 1])");
+		return false;
+	}
+	if (y.len == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Empty input: y cannot be empty"); return false; }
+	for (size_t j = 0; j < x_count; ++j) {
+		if (x[j].len != y.len) {
+			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH, "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(x[j].len) + " rows");
+			return false;
+		}
+	}
+	const size_t p = x_count, n = y.len;
+	if (p > (size_t)kWideMaxP) {
+		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Elastic Net fit: more than " + std::to_string(kWideMaxP) + " features are not supported by the GPU path");
+		return false;
+	}
+	const size_t n_pad = n < 2 ? 2 : n;
+	auto expand = [](const AnofoxDataArray &a, std::vector<double> &out, size_t len) {
+		out.assign(len, NAN);
+		for (size_t i = 0; i < a.len; ++i) {
+			const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
+			out[i] = valid ? a.data[i] : NAN;
+		}
+	};
+	std::vector<std::vector<double>> cols(p);
+	std::vector<double> yv;
+	expand(y, yv, n_pad);
+	std::vector<const double *> xp(p);
+	for (size_t j = 0; j < p; ++j) { expand(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
+	AnofoxHipElasticNetBatchOptions o;
+	memset(&o, 0, sizeof o);
+	o.fit_intercept = options.fit_intercept;
+	o.alpha = options.alpha;
+	o.l1_ratio = options.l1_ratio;
+	o.max_iterations = options.max_iterations;
+	o.tolerance = options.tolerance;
+	o.lambda_scaling = options.lambda_scaling;
+	const int64_t off[2] = {0, (int64_t)n_pad};
+	std::vector<double> core(p + 6);
+	if (!anofox_hip_elasticnet_fit_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), o, core.data(), nullptr, out_error))
+		return false;
+	const int status = (int)core[p + 5];
+	if (status != ANOFOX_ERROR_SUCCESS) {
+		size_t n_valid = 0;
+		for (size_t i = 0; i < n; ++i) {
+			bool ok = isfinite(yv[i]);
+			for (size_t j = 0; ok && j < p; ++j) ok = isfinite(cols[j][i]);
+			n_valid += ok;
+		}
+		std::string msg;
+		switch (status) { // crates/anofox-stats-core/src/errors.rs
+		case ANOFOX_ERROR_NO_VALID_DATA: msg = "All rows filtered due to NULL/NaN values"; break;
+		case ANOFOX_ERROR_INSUFFICIENT_DATA:
+			msg = "Insufficient data: " + std::to_string(n_valid) + " rows, " + std::to_string(p) + " features (need rows > features)";
+			break;
+		default: msg = "Elastic Net fit failed on the GPU path"; break;
+		}
+		set_error(out_error, (AnofoxErrorCode)status, msg);
+		return false;
+	}
+	double *coef = (double *)malloc(p * sizeof(double));
+	if (!coef) { set_error(out_error, ANOFOX_ERROR_ALLOCATION_FAILURE, "Failed to allocate coefficients"); return false; }
+	memcpy(coef, core.data(), p * sizeof(double));
+	out_core->coefficients = coef;
+	out_core->coefficients_len = p;
+	out_core->intercept = core[p];
+	out_core->r_squared = core[p + 1];
+	out_core->adj_r_squared = core[p + 2];
+	out_core->residual_std_error = core[p + 3];
+	out_core->n_observations = (size_t)core[p + 4];
+	out_core->n_features = p;
+	return true;
+}
+
+} // extern "C"

@@ -54,11 +54,76 @@ bool carve_workspace(AnofoxHipContext *ctx, int64_t G, int p, Workspace *out, An
 	return true;
 }
 
-// Wide designs (8 < p <= 128): the same four stages on the MFMA / LDS kernels, slab by slab.
+// The regression models' (OLS / ridge / WLS) solve stage on one slab of wide records: the primary solve, the refinement
+// passes of the queued groups, the finish and HC kernels, the double-double refit.  `slab` is the largest slab of the
+// call (it sizes the HC scratch once).
+bool regression_wide_stage(AnofoxHipContext *ctx, WideArgs &a, hipStream_t ss, int64_t slab, void *, AnofoxError *e) {
+	const int p = a.p;
+	const bool mid = solve_mid_supports(p);
+	// moderately wide designs: one lane per group (solve_mid.hip); beyond that one workgroup per group
+	auto solve = [&](int mode) { return mid ? launch_solve_mid(a, mode, ss) : launch_solve_wide(a, mode, ss); };
+	// the primary solve of every width runs with one wavefront per group and the matrix in registers (solve_tiles.hip);
+	// the lane-per-group / workgroup-per-group kernels keep the refinement modes.  ANOFOX_SOLVE_TILES=0: without it.
+	static const bool tiles_on = !(getenv("ANOFOX_SOLVE_TILES") && atoi(getenv("ANOFOX_SOLVE_TILES")) == 0);
+	// (p <= 10: a 16 x 16 tile is mostly padding and the lane-per-group solve is as fast — 200 000 x 1000 x 9: 0.58 vs 0.70 ms;
+	// from there on the tiles win: p = 16 1.74 -> 0.69 ms, 100 000 x 1000 x 32 4.24 -> 0.76 ms, x 24 with inference 3.40 -> 1.77 ms)
+	const bool tiles_mid = mid && tiles_on && p >= 11 && solve_tiles_supports(p);
+	if (hip_fail(tiles_mid ? launch_solve_tiles(a, ss) : solve(0), "wide solve kernel launch", e)) return false;
+	// (solve_mid writes complete inference records itself; after the tiles kernel t, p and the interval come from the
+	// finish kernel — before the refinement modes, whose final pass rewrites the queued groups' records in full)
+	if (tiles_mid && hip_fail(launch_inference_wide_finish(a, ss), "wide inference finish kernel launch", e)) return false;
+	// four updates on the wide path: with the residual in double-double every update gains about two digits even at
+	// cond(X) = 2e7 (an exactly determined 67 x 67 system of the deep fuzz sweep: 5.4e-7 after two, 4.3e-9 after three,
+	// 2.3e-11 after four); the launches are idle unless groups are queued.  ANOFOX_WIDE_REFINE_STEPS overrides (measurements).
+	static const int wide_steps = getenv("ANOFOX_WIDE_REFINE_STEPS") ? atoi(getenv("ANOFOX_WIDE_REFINE_STEPS")) : 2 * kRefineSteps;
+	for (int it = 0; it < wide_steps; ++it) { // queued groups only: b += (X'WX)^-1 X'Wr
+		if (hip_fail(launch_residual_grad_wide(a, ss), "wide residual kernel launch", e)) return false;
+		if (hip_fail(solve(1), "wide refine kernel launch", e)) return false;
+	}
+	if (hip_fail(launch_residual_grad_wide(a, ss), "wide residual kernel launch", e)) return false;
+	if (hip_fail(solve(2), "wide final kernel launch", e)) return false;
+	if (!mid && hip_fail(launch_inference_wide_finish(a, ss), "wide inference finish kernel launch", e)) return false;
+	if (a.hc_type != ANOFOX_HC_NONE && a.inference && a.model != ANOFOX_HIP_MODEL_RIDGE) {
+		if (!ensure_buffer(&ctx->aux, &ctx->aux_bytes, (size_t)slab * sizeof(double), "hc scratch", e)) return false;
+		a.hc_df = (double *)ctx->aux;
+		if (hip_fail(launch_hc_wide(a, ss), "wide hc kernel launch", e)) return false;
+	}
+	// (r4) LAST: the queued groups once more, from their rows in double-double — standard errors (classical and HC) that do not
+	// carry cond(X)^2 eps, and the reference's aliasing rule instead of the 1e-11 pivot test (refit_dd.hip).
+	// ANOFOX_REFIT_DD=0: without it (measurements).
+	static const bool refit_dd_on = !(getenv("ANOFOX_REFIT_DD") && atoi(getenv("ANOFOX_REFIT_DD")) == 0);
+	if (refit_dd_on && hip_fail(launch_refit_dd_wide(a, ss), "double-double refit kernel launch", e)) return false;
+	return true;
+}
+
+// The same stage on the narrow records (p <= 8).
+bool regression_narrow_stage(AnofoxHipContext *ctx, BatchArgs &a, hipStream_t st, void *, AnofoxError *e) {
+	if (hip_fail(launch_solve_narrow(a, st), "solve kernel launch", e)) return false;
+	// queued groups only: kRefineSteps x (b += (X'WX)^-1 X'Wr), then the statistics from the directly summed RSS
+	if (hip_fail(launch_refine_fused_narrow(a, kRefineSteps, st), "refine kernel launch", e)) return false;
+	// ols.rs:209-231, wls.rs:230-252: HC errors replace the classical ones; ridge has no such branch
+	if (a.hc_type != ANOFOX_HC_NONE && a.inference && a.model != ANOFOX_HIP_MODEL_RIDGE) {
+		const size_t b_tab = align_up(sizeof(PredictSegTable), 256); // overflow segments of very large groups, then the prep records
+		if (!ensure_buffer(&ctx->aux, &ctx->aux_bytes, b_tab + hc_prep_bytes(a.n_groups, a.p), "hc scratch", e)) return false;
+		if (hip_fail(hipMemsetAsync(ctx->aux, 0, 64, st), "hipMemsetAsync", e)) return false;
+		if (hip_fail(launch_hc_narrow(a, (double *)((char *)ctx->aux + b_tab), ctx->aux, st), "hc kernel launch", e)) return false;
+	}
+	// (r4) LAST: the queued groups once more, from their rows in double-double (refit_dd.hip) — the reference's aliasing rule
+	// instead of the 1e-11 pivot test (round 3's narrow sweeps: 12 "rank band" groups of 240 000 cases), standard errors without
+	// cond(X)^2 eps.  ANOFOX_REFIT_DD=0: without it.
+	static const bool refit_dd_on = !(getenv("ANOFOX_REFIT_DD") && atoi(getenv("ANOFOX_REFIT_DD")) == 0);
+	if (refit_dd_on && hip_fail(launch_refit_dd_narrow(a, st), "double-double refit kernel launch", e)) return false;
+	return true;
+}
+
+const SolveStages kRegressionStages = {regression_narrow_stage, regression_wide_stage, nullptr};
+
+// Wide designs (8 < p <= 128): the accumulate kernels on the MFMA / LDS paths, slab by slab, each slab followed by the
+// solve stage.
 bool run_wide_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off,
                     const double *d_y, const double *const *x_cols, const double *d_w,
                     const AnofoxHipBatchOptions &opt, double *d_core, double *d_inf, const int64_t *d_rule_counts,
-                    AnofoxError *e) {
+                    AnofoxError *e, const SolveStages &stages) {
 	const int T = wide_tiles((int)p);
 	const size_t rec_bytes = (size_t)wide_record_len(T) * sizeof(double);
 	// the moment scratch is reused by slabs of groups: at most ~1 GiB of it is live
@@ -68,7 +133,6 @@ bool run_wide_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
 	const size_t b_mom = align_up((size_t)slab * rec_bytes, 256);
 	const size_t b_rss = align_up((size_t)G * (size_t)refine_vec_len((int)p) * sizeof(double), 256);
 	const size_t b_lst = align_up((size_t)slab * sizeof(int32_t), 256);
-	const bool mid = solve_mid_supports((int)p);
 	static const bool mid_acc_on = !(getenv("ANOFOX_MID_ACC") && atoi(getenv("ANOFOX_MID_ACC")) == 0); // A/B switch for measurements
 	const bool mid_acc = mid_acc_on && accumulate_mid_supports((int)p);
 	// Several slabs: slab k's solve / refinement kernels run on a second stream while the main stream accumulates slab k + 1
@@ -212,39 +276,7 @@ bool run_wide_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
 				a.launch_part = 0;
 			}
 		}
-		// moderately wide designs: one lane per group (solve_mid.hip); beyond that one workgroup per group
-		auto solve = [&](int mode) { return mid ? launch_solve_mid(a, mode, ss) : launch_solve_wide(a, mode, ss); };
-		// the primary solve of every width runs with one wavefront per group and the matrix in registers (solve_tiles.hip);
-		// the lane-per-group / workgroup-per-group kernels keep the refinement modes.  ANOFOX_SOLVE_TILES=0: without it.
-		static const bool tiles_on = !(getenv("ANOFOX_SOLVE_TILES") && atoi(getenv("ANOFOX_SOLVE_TILES")) == 0);
-		// (p <= 10: a 16 x 16 tile is mostly padding and the lane-per-group solve is as fast — 200 000 x 1000 x 9: 0.58 vs 0.70 ms;
-		// from there on the tiles win: p = 16 1.74 -> 0.69 ms, 100 000 x 1000 x 32 4.24 -> 0.76 ms, x 24 with inference 3.40 -> 1.77 ms)
-		const bool tiles_mid = mid && tiles_on && p >= 11 && solve_tiles_supports((int)p);
-		if (hip_fail(tiles_mid ? launch_solve_tiles(a, ss) : solve(0), "wide solve kernel launch", e)) return false;
-		// (solve_mid writes complete inference records itself; after the tiles kernel t, p and the interval come from the
-		// finish kernel — before the refinement modes, whose final pass rewrites the queued groups' records in full)
-		if (tiles_mid && hip_fail(launch_inference_wide_finish(a, ss), "wide inference finish kernel launch", e)) return false;
-		// four updates on the wide path: with the residual in double-double every update gains about two digits even at
-		// cond(X) = 2e7 (an exactly determined 67 x 67 system of the deep fuzz sweep: 5.4e-7 after two, 4.3e-9 after three,
-		// 2.3e-11 after four); the launches are idle unless groups are queued.  ANOFOX_WIDE_REFINE_STEPS overrides (measurements).
-		static const int wide_steps = getenv("ANOFOX_WIDE_REFINE_STEPS") ? atoi(getenv("ANOFOX_WIDE_REFINE_STEPS")) : 2 * kRefineSteps;
-		for (int it = 0; it < wide_steps; ++it) { // queued groups only: b += (X'WX)^-1 X'Wr
-			if (hip_fail(launch_residual_grad_wide(a, ss), "wide residual kernel launch", e)) return false;
-			if (hip_fail(solve(1), "wide refine kernel launch", e)) return false;
-		}
-		if (hip_fail(launch_residual_grad_wide(a, ss), "wide residual kernel launch", e)) return false;
-		if (hip_fail(solve(2), "wide final kernel launch", e)) return false;
-		if (!mid && hip_fail(launch_inference_wide_finish(a, ss), "wide inference finish kernel launch", e)) return false;
-		if (a.hc_type != ANOFOX_HC_NONE && a.inference && a.model != ANOFOX_HIP_MODEL_RIDGE) {
-			if (!ensure_buffer(&ctx->aux, &ctx->aux_bytes, (size_t)slab * sizeof(double), "hc scratch", e)) return false;
-			a.hc_df = (double *)ctx->aux;
-			if (hip_fail(launch_hc_wide(a, ss), "wide hc kernel launch", e)) return false;
-		}
-		// (r4) LAST: the queued groups once more, from their rows in double-double — standard errors (classical and HC) that do not
-		// carry cond(X)^2 eps, and the reference's aliasing rule instead of the 1e-11 pivot test (refit_dd.hip).
-		// ANOFOX_REFIT_DD=0: without it (measurements).
-		static const bool refit_dd_on = !(getenv("ANOFOX_REFIT_DD") && atoi(getenv("ANOFOX_REFIT_DD")) == 0);
-		if (refit_dd_on && hip_fail(launch_refit_dd_wide(a, ss), "double-double refit kernel launch", e)) return false;
+		if (!stages.wide(ctx, a, ss, slab, stages.user, e)) return false;
 
 		if (overlap && hip_fail(hipEventRecord(ctx->slab_solve_done[buf], ss), "hipEventRecord", e)) return false;
 		if (ctx->timing) {
@@ -261,15 +293,16 @@ bool run_wide_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
 	return true;
 }
 
-// Core of the device path: accumulate -> solve -> (queued groups only) residual RSS -> solve again.
+// Core of the device path: accumulate -> solve -> (queued groups only) residual RSS -> solve again; another model's
+// solve stages may take the place of the regression stages.
 // Everything is enqueued on the context's stream; no host synchronisation.
 bool run_device_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off,
                       const double *d_y, const double *const *x_cols, const double *d_w,
                       const AnofoxHipBatchOptions &opt, double *d_core, double *d_inf, AnofoxError *e,
-                      const int64_t *d_rule_counts = nullptr) {
+                      const int64_t *d_rule_counts = nullptr, const SolveStages &stages = kRegressionStages) {
 	if (G == 0) return true;
 	if (p > (size_t)kNarrowMaxP)
-		return run_wide_batch(ctx, G, p, n_rows, d_off, d_y, x_cols, d_w, opt, d_core, d_inf, d_rule_counts, e);
+		return run_wide_batch(ctx, G, p, n_rows, d_off, d_y, x_cols, d_w, opt, d_core, d_inf, d_rule_counts, e, stages);
 	Workspace ws;
 	if (!carve_workspace(ctx, G, (int)p, &ws, e)) return false;
 
@@ -336,21 +369,7 @@ bool run_device_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows
 		ctx->gate_record = nullptr;
 		if (hip_fail(hipEventRecord(gr, st), "hipEventRecord", e)) return false;
 	}
-	if (hip_fail(launch_solve_narrow(a, st), "solve kernel launch", e)) return false;
-	// queued groups only: kRefineSteps x (b += (X'WX)^-1 X'Wr), then the statistics from the directly summed RSS
-	if (hip_fail(launch_refine_fused_narrow(a, kRefineSteps, st), "refine kernel launch", e)) return false;
-	// ols.rs:209-231, wls.rs:230-252: HC errors replace the classical ones; ridge has no such branch
-	if (a.hc_type != ANOFOX_HC_NONE && a.inference && a.model != ANOFOX_HIP_MODEL_RIDGE) {
-		const size_t b_tab = align_up(sizeof(PredictSegTable), 256); // overflow segments of very large groups, then the prep records
-		if (!ensure_buffer(&ctx->aux, &ctx->aux_bytes, b_tab + hc_prep_bytes(G, (int)p), "hc scratch", e)) return false;
-		if (hip_fail(hipMemsetAsync(ctx->aux, 0, 64, st), "hipMemsetAsync", e)) return false;
-		if (hip_fail(launch_hc_narrow(a, (double *)((char *)ctx->aux + b_tab), ctx->aux, st), "hc kernel launch", e)) return false;
-	}
-	// (r4) LAST: the queued groups once more, from their rows in double-double (refit_dd.hip) — the reference's aliasing rule
-	// instead of the 1e-11 pivot test (round 3's narrow sweeps: 12 "rank band" groups of 240 000 cases), standard errors without
-	// cond(X)^2 eps.  ANOFOX_REFIT_DD=0: without it.
-	static const bool refit_dd_on = !(getenv("ANOFOX_REFIT_DD") && atoi(getenv("ANOFOX_REFIT_DD")) == 0);
-	if (refit_dd_on && hip_fail(launch_refit_dd_narrow(a, st), "double-double refit kernel launch", e)) return false;
+	if (!stages.narrow(ctx, a, st, stages.user, e)) return false;
 	if (ctx->timing) {
 		(void)hipEventRecord(e2, st);
 		ctx->acc_events.emplace_back(e0, e1);   // owns e0 and e1
@@ -406,6 +425,12 @@ bool refit_groups_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int6
                          double *d_core, double *d_inf, AnofoxError *e) {
 	return run_device_batch(ctx, n_groups, p, n_rows, d_row_offsets, d_y, x_cols, d_w, opt, d_core, d_inf, e);
 }
+bool moment_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
+                         const double *d_y, const double *const *x_cols, const AnofoxHipBatchOptions &opt, const SolveStages &stages,
+                         double *d_core, AnofoxError *e) {
+	return run_device_batch(ctx, n_groups, p, n_rows, d_row_offsets, d_y, x_cols, nullptr, opt, d_core, nullptr, e, nullptr, stages);
+}
+AnofoxHipContext *thread_default_context(AnofoxError *e) { return default_context(e); }
 } // namespace host
 } // namespace anofox
 

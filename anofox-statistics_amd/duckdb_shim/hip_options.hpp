@@ -1,5 +1,5 @@
 // hip_options.hpp — the options argument of the regression aggregates as the reference's parser reads it, shared by the
-// DuckDB glue files of this directory (fit_agg_hip.cpp, family_agg_hip.cpp).
+// DuckDB glue files of this directory (fit_agg_hip.cpp, family_agg_hip.cpp, elasticnet_agg_hip.cpp).
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -121,6 +121,73 @@ inline AnofoxHipBatchOptions MakeHipOptions(HipModel model, const HipFitOptions 
 	b.lambda_scaling = model == HipModel::RIDGE ? o.lambda_scaling : ANOFOX_LAMBDA_SCALING_RAW;
 	b.hc_type = model == HipModel::RIDGE ? ANOFOX_HC_NONE : o.hc_type;
 	return b;
+}
+
+// ---- the elastic net's options (elasticnet_aggregate.cpp bind data; keys map_options_parser.cpp:637-750 with :651-656) ----
+struct HipElasticNetOptions {
+	double alpha = 1.0;
+	double l1_ratio = 0.5;
+	bool fit_intercept = true;
+	uint32_t max_iterations = 1000;
+	double tolerance = 1e-6;
+	AnofoxLambdaScaling lambda_scaling = ANOFOX_LAMBDA_SCALING_RAW;
+	bool operator==(const HipElasticNetOptions &o) const {
+		return alpha == o.alpha && l1_ratio == o.l1_ratio && fit_intercept == o.fit_intercept && max_iterations == o.max_iterations &&
+		       tolerance == o.tolerance && lambda_scaling == o.lambda_scaling;
+	}
+	AnofoxHipElasticNetBatchOptions Batch() const {
+		AnofoxHipElasticNetBatchOptions b;
+		memset(&b, 0, sizeof b);
+		b.fit_intercept = fit_intercept;
+		b.alpha = alpha;
+		b.l1_ratio = l1_ratio;
+		b.max_iterations = max_iterations;
+		b.tolerance = tolerance;
+		b.lambda_scaling = lambda_scaling;
+		return b;
+	}
+};
+
+inline void ApplyElasticNetOption(const string &raw_key, const Value &v, HipElasticNetOptions &o, bool &has_alpha, double &alpha, bool &has_lambda,
+                                  double &lambda) {
+	if (v.IsNull()) return;
+	const string key = Lower(raw_key);
+	if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(v);
+	else if (key == "alpha") { has_alpha = true; alpha = v.GetValue<double>(); }
+	else if (key == "lambda") { has_lambda = true; lambda = v.GetValue<double>(); }
+	else if (key == "l1_ratio") o.l1_ratio = v.GetValue<double>();
+	else if (key == "max_iterations" || key == "max_iter") {
+		const double it = v.GetValue<double>();
+		if (!(it >= 0.0 && it <= 4294967295.0)) throw InvalidInputException("Value %s is out of range for UINTEGER", v.ToString().c_str());
+		o.max_iterations = (uint32_t)it;
+	} else if (key == "tolerance" || key == "tol") o.tolerance = v.GetValue<double>();
+	else if (key == "lambda_scaling")
+		o.lambda_scaling = ExtractEnum<AnofoxLambdaScaling>(v, "lambda_scaling", "'raw', 'glmnet'",
+		                                                    {{"raw", ANOFOX_LAMBDA_SCALING_RAW}, {"glmnet", ANOFOX_LAMBDA_SCALING_GLMNET}});
+	// every other key: ignored, as upstream
+}
+
+// STRUCT or MAP literal, keys case-insensitive, alpha wins over lambda (GetRegularizationStrength)
+inline void ParseHipElasticNetOptions(const Value &v, HipElasticNetOptions &o) {
+	if (v.IsNull()) return;
+	bool has_alpha = false, has_lambda = false;
+	double alpha = 0.0, lambda = 0.0;
+	if (v.type().id() == LogicalTypeId::STRUCT) {
+		auto &kids = StructValue::GetChildren(v);
+		for (idx_t i = 0; i < kids.size(); i++)
+			ApplyElasticNetOption(StructType::GetChildName(v.type(), i), kids[i], o, has_alpha, alpha, has_lambda, lambda);
+	} else if (v.type().id() == LogicalTypeId::MAP) {
+		for (auto &entry : MapValue::GetChildren(v)) {
+			auto &kv = StructValue::GetChildren(entry);
+			if (kv.size() != 2 || kv[0].IsNull()) continue;
+			ApplyElasticNetOption(kv[0].type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(kv[0]) : kv[0].ToString(), kv[1], o, has_alpha, alpha,
+			                      has_lambda, lambda);
+		}
+	} else {
+		throw InvalidInputException("Options must be a MAP or STRUCT, got %s", v.type().ToString().c_str());
+	}
+	if (has_alpha) o.alpha = alpha;
+	else if (has_lambda) o.alpha = lambda;
 }
 
 } // namespace hip_glue

@@ -119,3 +119,74 @@ def parse_options(opts: Optional[Mapping[str, Any]]) -> RegressionOptions:
     elif lam is not None:
         out.alpha = lam
     return out
+
+
+@dataclass
+class ElasticNetOptions:
+    """Resolved options of the elastic net (defaults = the reference's ElasticNetOptions bind data)."""
+    alpha: float = 1.0
+    l1_ratio: float = 0.5
+    fit_intercept: bool = True
+    max_iterations: int = 1000
+    tolerance: float = 1e-6
+    lambda_scaling: str = "raw"
+
+    def batch_options(self) -> _abi.AnofoxHipElasticNetBatchOptions:
+        return _abi.AnofoxHipElasticNetBatchOptions(self.fit_intercept, self.alpha, self.l1_ratio, self.max_iterations,
+                                                    self.tolerance, _abi.LAMBDA_SCALING[self.lambda_scaling])
+
+    def ffi_options(self) -> _abi.AnofoxElasticNetOptions:
+        return _abi.AnofoxElasticNetOptions(self.alpha, self.l1_ratio, self.fit_intercept, self.max_iterations,
+                                            self.tolerance, _abi.LAMBDA_SCALING[self.lambda_scaling])
+
+
+def _extract_uint32(val: Any) -> Optional[int]:
+    if val is None:
+        return None
+    v = int(val)
+    if v < 0 or v > 0xFFFFFFFF:
+        raise InvalidInputException(f"Value {v} is out of range for UINTEGER")
+    return v
+
+
+def parse_elasticnet_options(opts: Optional[Mapping[str, Any]]) -> ElasticNetOptions:
+    """The elastic net's MAP options (map_options_parser.cpp:637-750 with the keys of :651-656): alpha / lambda
+    (alpha wins), l1_ratio, fit_intercept / intercept, max_iterations / max_iter, tolerance / tol, lambda_scaling.
+    Keys are case-insensitive; unknown keys are ignored."""
+    out = ElasticNetOptions()
+    if opts is None:
+        return out
+    if not isinstance(opts, Mapping):
+        raise InvalidInputException("Options parameter must be a constant expression")
+    alpha = lam = None
+    for raw_key, val in opts.items():
+        key = str(raw_key).lower()
+        if key in ("intercept", "fit_intercept"):
+            v = _extract_bool(val)
+            if v is not None:
+                out.fit_intercept = v
+        elif key == "alpha":
+            alpha = _extract_double(val)
+        elif key == "lambda":
+            lam = _extract_double(val)
+        elif key == "l1_ratio":
+            v = _extract_double(val)
+            if v is not None:
+                out.l1_ratio = v
+        elif key in ("max_iterations", "max_iter"):
+            v = _extract_uint32(val)
+            if v is not None:
+                out.max_iterations = v
+        elif key in ("tolerance", "tol"):
+            v = _extract_double(val)
+            if v is not None:
+                out.tolerance = v
+        elif key == "lambda_scaling":
+            v = _extract_enum(val, _abi.LAMBDA_SCALING, "lambda_scaling", "'raw', 'glmnet'")
+            if v is not None:
+                out.lambda_scaling = v
+    if alpha is not None:      # GetRegularizationStrength: alpha first, then lambda
+        out.alpha = alpha
+    elif lam is not None:
+        out.alpha = lam
+    return out

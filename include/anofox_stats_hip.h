@@ -230,6 +230,23 @@ ANOFOX_HIP_API bool anofox_compute_residuals(AnofoxDataArray y, AnofoxDataArray 
                               AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_residuals(AnofoxResidualsResult *result);
 
+/* replaces AnofoxElasticNetOptions, anofox_stats_ffi.h:384-397 — 40 bytes: alpha @0, l1_ratio @8, fit_intercept @16,
+ * max_iterations @20, tolerance @24, lambda_scaling @32 */
+typedef struct {
+	double alpha;        /* penalty strength, >= 0 */
+	double l1_ratio;     /* share of the L1 part in [0, 1]: 0 = ridge, 1 = lasso */
+	bool fit_intercept;
+	uint32_t max_iterations; /* coordinate-descent sweeps at most */
+	double tolerance;    /* a sweep that moves no coefficient by more than tolerance sqrt(S_yy / C_jj) ends the solve */
+	AnofoxLambdaScaling lambda_scaling;
+} AnofoxElasticNetOptions;
+
+/* replaces anofox_elasticnet_fit, anofox_stats_ffi.h:410-411 (over crates/anofox-stats-core/src/models/elasticnet.rs):
+ * one group through anofox_hip_elasticnet_fit_batch_host, with anofox_ols_fit's conventions.  The objective, the solve
+ * and the statuses: DESIGN.md §1 "Elastic net".  No inference block (the reference has none either). */
+ANOFOX_HIP_API bool anofox_elasticnet_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxElasticNetOptions options,
+                           AnofoxFitResultCore *out_core, AnofoxError *out_error);
+
 #endif /* ANOFOX_STATS_FFI_H */
 
 /* ------------------------------------------------------------------------ */
@@ -323,6 +340,33 @@ ANOFOX_HIP_API bool anofox_hip_fit_batch_host(AnofoxHipContext *ctx, int64_t n_g
                                const int64_t *row_offsets, const double *y, const double *const *x_cols,
                                const double *w, AnofoxHipBatchOptions options, double *core, double *inference,
                                AnofoxError *out_error);
+
+/*
+ * Grouped elastic net (anofox_stats_elasticnet_fit_agg): per group, over the rows with finite y and x, minimise
+ *     1/2 sum_i (y_i - b0 - x_i'b)^2 + lam (l1_ratio sum |b_j| + (1 - l1_ratio)/2 sum b_j^2)
+ * with lam = alpha (RAW) or n alpha / sd_y (GLMNET, as ridge), by cyclic coordinate descent from b = 0 on the moments
+ * of the accumulate kernels (DESIGN.md §1 "Elastic net").  Records: core[g] as above (length p + 6); statuses 4
+ * (alpha < 0), 5 (l1_ratio outside [0, 1]), 6, 10, ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS.  iterations (may be NULL):
+ * iterations[g] = sweeps run, negated when max_iterations stopped the group (its last iterate is returned, status 0).
+ */
+typedef struct {
+	bool fit_intercept;
+	double alpha;
+	double l1_ratio;
+	uint32_t max_iterations;
+	double tolerance;
+	AnofoxLambdaScaling lambda_scaling;
+} AnofoxHipElasticNetBatchOptions;
+
+ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                            const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                            AnofoxHipElasticNetBatchOptions options, double *d_core, int32_t *d_iterations,
+                                            AnofoxError *out_error);
+/* host pointers, synchronous; ctx may be NULL (per-thread default context) */
+ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                          const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                          AnofoxHipElasticNetBatchOptions options, double *core, int32_t *iterations,
+                                          AnofoxError *out_error);
 
 /*
  * Information criteria as batched outputs of the fit records: what the SQL functions
