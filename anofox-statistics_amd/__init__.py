@@ -16,9 +16,11 @@ from .aggregate import (StreamingStates, FitAggResult, FitPredictAggResult, OlsF
                         RidgeFitPredictAgg, WlsFitAgg, WlsFitPredictAgg, SQL_FUNCTIONS, ols_fit_agg,
                         ols_fit_predict_agg, ridge_fit_agg, ridge_fit_predict_agg, wls_fit_agg, wls_fit_predict_agg,
                         result_from_records, ols_fit_predict, ridge_fit_predict, wls_fit_predict, vif_agg,
-                        residuals_diagnostics_agg)
-from .options import ElasticNetOptions, InvalidInputException, RegressionOptions, parse_elasticnet_options, parse_options  # noqa: E402
-from .runtime import AggState, Context, elasticnet_fit_batch_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
+                        residuals_diagnostics_agg, ElasticNetFitPredictAgg, elasticnet_fit_predict_agg,
+                        elasticnet_fit_predict)
+from .options import (ElasticNetOptions, ElasticNetPredictOptions, InvalidInputException, RegressionOptions,  # noqa: E402
+                      parse_elasticnet_options, parse_elasticnet_predict_options, parse_options)
+from .runtime import AggState, Context, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
 from .scalar import aic, bic, elasticnet_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
@@ -44,6 +46,9 @@ __all__ = [
     "t_critical", "fit_predict_expanding_host", "fit_predict_window_host", "ols_fit_predict", "ridge_fit_predict", "wls_fit_predict",
     "vif", "vif_agg", "vif_batch_host", "residuals_diagnostics", "residuals_diagnostics_agg", "residuals_batch_host",
     "ElasticNetOptions", "elasticnet_fit", "elasticnet_fit_batch_host", "parse_elasticnet_options",
+    "ElasticNetPredictOptions", "parse_elasticnet_predict_options", "ElasticNetFitPredictAgg", "elasticnet_fit_predict_agg",
+    "elasticnet_fit_predict", "elasticnet_fit_predict_batch_host", "elasticnet_fit_predict_window_host",
+    "elasticnet_fit_predict_frames_host",
 ]
 
 

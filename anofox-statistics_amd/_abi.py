@@ -235,6 +235,24 @@ SYMBOLS = {
     "anofox_hip_elasticnet_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
                                                         C.POINTER(_DP), AnofoxHipElasticNetBatchOptions, _DP,
                                                         C.POINTER(C.c_int32), _ERRP]),
+    "anofox_hip_elasticnet_fit_predict_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                                  C.POINTER(C.c_void_p), C.c_void_p, AnofoxHipElasticNetBatchOptions,
+                                                                  C.c_double, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_elasticnet_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                                C.POINTER(_DP), C.POINTER(C.c_int64), AnofoxHipElasticNetBatchOptions,
+                                                                C.c_double, _DP, _DP, _ERRP]),
+    "anofox_hip_elasticnet_fit_predict_window_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                                   C.POINTER(C.c_void_p), AnofoxHipWindowFrame,
+                                                                   AnofoxHipElasticNetBatchOptions, C.c_double, C.c_void_p, _ERRP]),
+    "anofox_hip_elasticnet_fit_predict_window_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                                 C.POINTER(_DP), AnofoxHipWindowFrame, AnofoxHipElasticNetBatchOptions,
+                                                                 C.c_double, _DP, _ERRP]),
+    "anofox_hip_elasticnet_fit_predict_frames_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p),
+                                                                   C.c_void_p, C.c_void_p, AnofoxHipElasticNetBatchOptions, C.c_double,
+                                                                   C.c_void_p, _ERRP]),
+    "anofox_hip_elasticnet_fit_predict_frames_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, _DP, C.POINTER(_DP), C.POINTER(C.c_int64),
+                                                                 C.POINTER(C.c_int64), AnofoxHipElasticNetBatchOptions, C.c_double,
+                                                                 _DP, _ERRP]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "anofox_hip_host_free": (None, [C.c_void_p]),
 }

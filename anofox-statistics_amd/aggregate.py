@@ -22,7 +22,7 @@ from typing import Any, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .options import InvalidInputException, RegressionOptions, parse_options
+from .options import InvalidInputException, RegressionOptions, parse_elasticnet_predict_options, parse_options
 from .runtime import AggState, Context, fit_batch_host
 
 
@@ -384,7 +384,7 @@ class _FitPredictAgg:
     has_weights = False
 
     def __init__(self, options: Optional[Mapping[str, Any]] = None, context: Optional[Context] = None):
-        self.options: RegressionOptions = parse_options(options)
+        self.options = self._parse_options(options)
         self._ctx = context
         self.n_features: Optional[int] = None
         self._chunks: List[tuple] = []
@@ -439,6 +439,15 @@ class _FitPredictAgg:
                                  None if wv is None else wv[keep]))
         return self
 
+    @staticmethod
+    def _parse_options(options):
+        return parse_options(options)
+
+    def _fit_predict(self, offsets, y_fit, x_cols, w, train_counts):
+        from .runtime import fit_predict_batch_host
+        return fit_predict_batch_host(offsets, y_fit, x_cols, w, self.options.batch_options(self.model),
+                                      train_counts=train_counts, ctx=self._ctx)
+
     def combine(self, other: "_FitPredictAgg"):
         if other.n_features is not None:
             if self.n_features is None:
@@ -451,7 +460,6 @@ class _FitPredictAgg:
         return self
 
     def finalize(self) -> FitPredictAggResult:
-        from .runtime import fit_predict_batch_host
         ukeys = np.unique(np.concatenate(self._seen_keys)) if self._seen_keys else np.empty(0)
         G = len(ukeys)
         p = self.n_features or 0
@@ -474,8 +482,7 @@ class _FitPredictAgg:
         y_fit = np.where(train, y, np.nan)
         train_counts = np.bincount(gid[order], weights=train.astype(np.float64), minlength=G).astype(np.int64)
         x_cols = [np.ascontiguousarray(X[:, j]) for j in range(p)]
-        opts = self.options.batch_options(self.model)
-        core, pred = fit_predict_batch_host(offsets, y_fit, x_cols, w, opts, train_counts=train_counts, ctx=self._ctx)
+        core, pred = self._fit_predict(offsets, y_fit, x_cols, w, train_counts)
         is_null = core[:, p + 5] != 0
         return FitPredictAggResult(ukeys, offsets, np.where(ynull, np.nan, y), ynull, pred[:, 0], pred[:, 1],
                                    pred[:, 2], train, is_null, core)
@@ -708,3 +715,69 @@ def residuals_diagnostics_agg(group_keys, y, y_hat, x=None, context=None):
 
 SQL_FUNCTIONS.update({"anofox_stats_residuals_diagnostics_agg": residuals_diagnostics_agg,
                       "residuals_diagnostics_agg": residuals_diagnostics_agg})
+
+
+# ------------------------------------------------------------------------------------------------------
+# elastic net fit-predict: anofox_stats_elasticnet_fit_predict_agg (src/aggregate_functions/
+# elasticnet_predict_aggregate.cpp) and the window function anofox_stats_elasticnet_fit_predict
+# (src/window_functions/elasticnet_fit_predict.cpp)
+# ------------------------------------------------------------------------------------------------------
+class ElasticNetFitPredictAgg(_FitPredictAgg):
+    """The elastic net fit-predict aggregate: training rows as the ridge aggregate (a NULL feature goes to the fit, whose
+    row filter drops it; elasticnet_predict_aggregate.cpp:194-239), "fewer than 2 training rows -> NULL" (:309), a
+    failed fit -> NULL list.  Its bind reads `alpha` only: a `lambda` key is ignored (:405-431)."""
+    model = "elasticnet"
+    sql_name = "anofox_stats_elasticnet_fit_predict_agg"
+
+    @staticmethod
+    def _parse_options(options):
+        return parse_elasticnet_predict_options(options, use_lambda=False)
+
+    def _fit_predict(self, offsets, y_fit, x_cols, w, train_counts):
+        from .runtime import elasticnet_fit_predict_batch_host
+        return elasticnet_fit_predict_batch_host(offsets, y_fit, x_cols, self.options.batch_options(), self.options.confidence_level,
+                                                 train_counts=train_counts, ctx=self._ctx)
+
+
+def elasticnet_fit_predict_agg(group_keys, y, x, options=None, context=None, split=None) -> FitPredictAggResult:
+    return ElasticNetFitPredictAgg(options, context).update(group_keys, y, x, split=split).finalize()
+
+
+def elasticnet_fit_predict(partition_keys, order, y, x, options=None, context=None, frame_end="current row", frame=None):
+    """anofox_stats_elasticnet_fit_predict(y, x [, options]) OVER (PARTITION BY partition_keys ORDER BY order ROWS ...):
+    (yhat, yhat_lower, yhat_upper) per input row, in input order; NaN = SQL NULL.  Frames as ols_fit_predict; options as
+    the window function's bind (alpha wins over lambda)."""
+    from .runtime import elasticnet_fit_predict_window_host
+    opts = parse_elasticnet_predict_options(options, use_lambda=True)
+    start, end = _parse_frame(frame, frame_end)
+    keys = np.asarray(partition_keys)
+    yv, ynull = _null_mask_1d(y)
+    yv = np.where(ynull, np.nan, yv)
+    rows = [None if r is None else [np.nan if v is None else float(v) for v in r] for r in x]
+    p = max((len(r) for r in rows if r is not None), default=0)
+    Xd = np.full((len(yv), p), np.nan)
+    for i, r in enumerate(rows):
+        if r is None:
+            continue                                             # NULL x list: no current x, no training
+        if len(r) != p:
+            raise InvalidInputException(f"Inconsistent feature count: expected {p}, got {len(r)}")
+        Xd[i] = r
+    if opts.null_policy == "drop_y_zero_x":
+        yv = np.where(np.any(Xd == 0.0, axis=1), np.nan, yv)
+    ukeys, gid = np.unique(keys, return_inverse=True)
+    perm = np.lexsort((np.asarray(order), gid))
+    counts = np.bincount(gid, minlength=len(ukeys))
+    offsets = np.zeros(len(ukeys) + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    pred_sorted = elasticnet_fit_predict_window_host(offsets, yv[perm], [np.ascontiguousarray(Xd[perm, j]) for j in range(p)],
+                                                     opts.batch_options(), (start, end), opts.confidence_level, ctx=context)
+    out = np.empty_like(pred_sorted)
+    out[perm] = pred_sorted
+    return out[:, 0], out[:, 1], out[:, 2]
+
+
+SQL_FUNCTIONS.update({
+    "anofox_stats_elasticnet_fit_predict_agg": elasticnet_fit_predict_agg, "elasticnet_fit_predict_agg": elasticnet_fit_predict_agg,
+    "elasticnet_predict_agg": elasticnet_fit_predict_agg, "anofox_stats_elasticnet_predict_agg": elasticnet_fit_predict_agg,
+    "anofox_stats_elasticnet_fit_predict": elasticnet_fit_predict, "elasticnet_fit_predict": elasticnet_fit_predict,
+})

@@ -374,6 +374,15 @@ constexpr int kWindowTcritCap = 65536;
 constexpr int64_t kFrameUnbounded = ANOFOX_HIP_FRAME_UNBOUNDED;
 hipError_t launch_tcrit_table(double *table, int cap, double prob, hipStream_t stream);
 hipError_t launch_window_predict(const WindowArgs &a, hipStream_t stream);
+// Elastic net solve parameters (elasticnet.hip, elasticnet_solve.h)
+struct EnParams {
+	double alpha, l1_ratio, tolerance;
+	int max_iterations;
+	int lambda_scaling;
+	int32_t *iterations; // [G] or nullptr: sweeps, negated when the limit stopped the group
+};
+// the window kernels with the elastic net solve (window_narrow.hip); flagged frames: cancelled rss or ill-conditioned
+hipError_t launch_window_predict_en(const WindowArgs &a, const EnParams &en, hipStream_t stream);
 
 // residual diagnostics (residuals_narrow.hip), p <= kNarrowMaxP
 struct ResidualArgs {

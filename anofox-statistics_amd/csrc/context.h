@@ -74,6 +74,34 @@ bool moment_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int6
                          double *d_core, AnofoxError *e);
 // host_api.hip: the calling thread's default context on the current device (the host entry points' ctx == NULL)
 AnofoxHipContext *thread_default_context(AnofoxError *e);
+// The window path of another model (the elastic net): its solve stages for the frames path, and its in-register window kernels
+// for p <= 8 (launch == nullptr: every frame through the frames path)
+struct WindowSolve {
+	SolveStages stages;
+	hipError_t (*launch)(const WindowArgs &a, void *user, hipStream_t st);
+	void *user;
+};
+// host_api.hip: the fit-predict entry points (batch / ROWS window / explicit frames) with another model's solve; `opt` = the
+// accumulate options of its moments (an unweighted fit) with the interval's confidence level.  Argument checks first; the
+// host forms take ctx == NULL as the thread's default context.
+bool model_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
+                                    const double *d_y, const double *const *x_cols, const int64_t *d_train_counts,
+                                    const AnofoxHipBatchOptions &opt, const SolveStages &stages, double *d_core, double *d_pred, AnofoxError *e);
+bool model_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets,
+                                  const double *y, const double *const *x_cols, const int64_t *train_counts, const AnofoxHipBatchOptions &opt,
+                                  const SolveStages &stages, double *core, double *pred, AnofoxError *e);
+bool model_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
+                                     const double *d_y, const double *const *x_cols, const AnofoxHipWindowFrame &frame,
+                                     const AnofoxHipBatchOptions &opt, const WindowSolve &ws, double *d_pred, AnofoxError *e);
+bool model_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets,
+                                   const double *y, const double *const *x_cols, const AnofoxHipWindowFrame &frame,
+                                   const AnofoxHipBatchOptions &opt, const WindowSolve &ws, double *pred, AnofoxError *e);
+bool model_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size_t p, const double *d_y, const double *const *x_cols,
+                                     const int64_t *d_frame_lo, const int64_t *d_frame_hi, const AnofoxHipBatchOptions &opt,
+                                     const SolveStages &stages, double *d_pred, AnofoxError *e);
+bool model_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t p, const double *y, const double *const *x_cols,
+                                   const int64_t *frame_lo, const int64_t *frame_hi, const AnofoxHipBatchOptions &opt,
+                                   const SolveStages &stages, double *pred, AnofoxError *e);
 }
 }
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "common.h"
+#include "elasticnet_solve.h"
 
 using namespace anofox;
 
@@ -31,74 +32,6 @@ using namespace anofox;
 using namespace anofox::host;
 
 namespace {
-
-constexpr double kEnRefineTol = 1e-7; // rss / tss below this => rss from the rows
-
-struct EnParams {
-	double alpha, l1_ratio, tolerance;
-	int max_iterations;
-	int lambda_scaling;
-	int32_t *iterations; // [G] or nullptr: sweeps, negated when the limit stopped the group
-};
-
-__device__ __forceinline__ double en_nan() { return __builtin_nan(""); }
-__device__ __forceinline__ double soft_threshold(double z, double t) { return z > t ? z - t : (z < -t ? z + t : 0.0); }
-
-// The checks every group passes before its solve (elasticnet.rs:33-136 and the aggregate's "< 2 rows -> NULL" rule).
-// Returns the status; 0 with *shortcut = true is the intercept-only fit (en_write_shortcut).
-__device__ __forceinline__ int en_prechecks(const EnParams &en, int64_t nrows, double cnt, int p_eff, bool icpt, bool *shortcut) {
-	*shortcut = false;
-	if (nrows < 2) return ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS;                            // the aggregate's NULL rule
-	if (!(en.alpha >= 0.0)) return ANOFOX_ERROR_INVALID_ALPHA;                             // elasticnet.rs:34-36
-	if (!(en.l1_ratio >= 0.0 && en.l1_ratio <= 1.0)) return ANOFOX_ERROR_INVALID_L1_RATIO; // elasticnet.rs:39-41
-	if (!(cnt > 0.0)) return ANOFOX_ERROR_NO_VALID_DATA;                                   // elasticnet.rs:77-79
-	if (p_eff == 0) {                                                                      // elasticnet.rs:104-128
-		if (!icpt) return ANOFOX_ERROR_INSUFFICIENT_DATA;
-		*shortcut = true;
-		return 0;
-	}
-	if (cnt < (double)(p_eff + (icpt ? 1 : 0))) return ANOFOX_ERROR_INSUFFICIENT_DATA; // elasticnet.rs:131-136
-	return 0;
-}
-
-// every column constant, with an intercept: NaN coefficients, the mean, r2 = adj = 0, sd(y) with n - 1 (elasticnet.rs:110-128)
-__device__ __forceinline__ void en_write_shortcut(double *core, int p, double ymean, double cyy_c, double cnt) {
-	for (int k = 0; k < p; ++k) core[k] = en_nan();
-	core[p] = ymean;
-	core[p + 1] = 0.0;
-	core[p + 2] = 0.0;
-	core[p + 3] = sqrt(cyy_c / (cnt - 1.0));
-	core[p + 4] = cnt;
-	core[p + 5] = 0.0;
-}
-
-__device__ __forceinline__ void en_write_status(double *core, int p, int status) {
-	for (int k = 0; k < p + 5; ++k) core[k] = en_nan();
-	core[p + 5] = (double)status;
-}
-
-// penalty: raw lam = alpha; glmnet lam = n alpha / sd_y, sd_y about the mean with or without an intercept (the ridge rule,
-// solve_narrow.hip).  The L1 / L2 parts, with 0 where their share is 0 (an infinite lam times 0 is not NaN).
-__device__ __forceinline__ void en_penalty(const EnParams &en, double cnt, double cyy_c, double *pen1, double *pen2) {
-	const double lam = en.lambda_scaling == ANOFOX_LAMBDA_SCALING_GLMNET ? cnt * en.alpha / sqrt(cyy_c / cnt) : en.alpha;
-	*pen1 = en.l1_ratio > 0.0 ? lam * en.l1_ratio : 0.0;
-	*pen2 = en.l1_ratio < 1.0 ? lam * (1.0 - en.l1_ratio) : 0.0;
-}
-
-// r2 / adj / rse / n of a finished fit (the ridge record's formulas, df from the non-constant columns); queued groups get
-// their tss parked in the r2 slot and flag 1 for rows_rss_kernel
-__device__ __forceinline__ void en_write_stats(double *core, int p, double rss, double tss, double cnt, int p_eff, bool icpt,
-                                               int32_t *flag) {
-	const double df = cnt - (double)(p_eff + (icpt ? 1 : 0));
-	const bool cancels = !(rss > kEnRefineTol * tss);
-	const double r2 = 1.0 - rss / tss;
-	core[p + 1] = cancels ? tss : r2;
-	core[p + 2] = 1.0 - (1.0 - r2) * (cnt - (icpt ? 1.0 : 0.0)) / df;
-	core[p + 3] = sqrt(rss / df);
-	core[p + 4] = cnt;
-	core[p + 5] = 0.0;
-	*flag = cancels ? 1 : 0;
-}
 
 // ---- narrow: one lane per group ----
 template <int P>
@@ -109,73 +42,13 @@ __global__ __launch_bounds__(64) void en_solve_narrow_kernel(BatchArgs a, EnPara
 	const bool icpt = a.fit_intercept != 0;
 	const double *rec = a.moments + g * (int64_t)L::REC;
 	double *core = a.core + g * (int64_t)(P + 6);
-	a.refine_list[g] = 0;
-	const int64_t nrows = a.row_offsets[g + 1] - a.row_offsets[g];
-	const double cnt = rec[L::OFF_CNT], sw = rec[L::OFF_SW];
-	const unsigned mask = (unsigned)rec[L::OFF_MASK];
-	const int p_eff = __popc(mask);
-	const double sy = rec[L::OFF_S + P], qyy = rec[L::q_index(P, P)];
-	const double cyy_c = qyy - sy * sy / sw;
-	const double ymean = (icpt ? rec[L::OFF_FIRST + P] : 0.0) + sy / sw;
-	bool shortcut;
-	const int status = en_prechecks(en, nrows, cnt, p_eff, icpt, &shortcut);
-	if (status != 0 || shortcut) {
-		if (status != 0) en_write_status(core, P, status);
-		else en_write_shortcut(core, P, ymean, cyy_c, cnt);
-		if (en.iterations) en.iterations[g] = 0;
-		return;
-	}
-	double C[P][P], c[P], b[P], xbar[P];
+	const int64_t nrows = a.rule_counts ? a.rule_counts[g] : group_row_end(a, g) - a.row_offsets[g];
+	double out[P + 6];
+	const EnSolveInfo s = en_fit_from_moments<P, false>(rec, en, icpt, nrows, out);
 #pragma unroll
-	for (int i = 0; i < P; ++i) {
-		const double si = rec[L::OFF_S + i];
-		xbar[i] = (icpt ? rec[L::OFF_FIRST + i] : 0.0) + si / sw;
-#pragma unroll
-		for (int j = 0; j <= i; ++j) {
-			const double v = rec[L::q_index(j, i)] - (icpt ? si * rec[L::OFF_S + j] / sw : 0.0);
-			C[i][j] = v;
-			C[j][i] = v;
-		}
-		c[i] = rec[L::q_index(i, P)] - (icpt ? si * sy / sw : 0.0);
-		b[i] = 0.0;
-	}
-	const double tss = icpt ? cyy_c : qyy;
-	double pen1, pen2;
-	en_penalty(en, cnt, cyy_c, &pen1, &pen2);
-	const double thresh = en.tolerance * sqrt(tss);
-	int sweeps = 0;
-	bool converged = false;
-	while (sweeps < en.max_iterations) {
-		++sweeps;
-		double dmax = 0.0;
-#pragma unroll
-		for (int j = 0; j < P; ++j) {
-			if (!((mask >> j) & 1u)) continue;
-			double z = c[j];
-#pragma unroll
-			for (int k = 0; k < P; ++k)
-				if (k != j) z -= C[j][k] * b[k];
-			const double bn = soft_threshold(z, pen1) / (C[j][j] + pen2);
-			dmax = fmax(dmax, sqrt(C[j][j]) * fabs(bn - b[j]));
-			b[j] = bn;
-		}
-		if (dmax <= thresh) { converged = true; break; }
-	}
-	double bc = 0.0, bcb = 0.0, b0 = ymean;
-#pragma unroll
-	for (int i = 0; i < P; ++i) {
-		double cbi = 0.0;
-#pragma unroll
-		for (int k = 0; k < P; ++k) cbi += C[i][k] * b[k];
-		bc += b[i] * c[i];
-		bcb += b[i] * cbi;
-		b0 -= b[i] * xbar[i];
-	}
-#pragma unroll
-	for (int j = 0; j < P; ++j) core[j] = ((mask >> j) & 1u) ? b[j] : en_nan();
-	core[P] = icpt ? b0 : en_nan();
-	en_write_stats(core, P, tss - 2.0 * bc + bcb, tss, cnt, p_eff, icpt, &a.refine_list[g]);
-	if (en.iterations) en.iterations[g] = converged ? sweeps : -sweeps;
+	for (int k = 0; k < P + 6; ++k) core[k] = out[k];
+	a.refine_list[g] = s.cancels ? 1 : 0;
+	if (en.iterations) en.iterations[g] = s.converged ? s.sweeps : -s.sweeps;
 }
 
 // ---- wide: one wavefront per group, C in LDS ----
@@ -195,7 +68,7 @@ __global__ __launch_bounds__(64) void en_solve_wide_kernel(WideArgs a, EnParams 
 	const double *sc = vec + 4 * P16;
 	double *core = a.core + g * (int64_t)(p + 6);
 	const double sy = sc[0], syy = sc[1], sw = sc[2], cnt = sc[3], first_y = sc[4];
-	const int64_t nrows = a.row_offsets[g + 1] - a.row_offsets[g];
+	const int64_t nrows = a.rule_counts ? a.rule_counts[g] : group_row_end(a, g) - a.row_offsets[g];
 	int p_eff = 0;
 	for (int j = 0; j < p; ++j) p_eff += nonconst[j] != 0.0 ? 1 : 0;
 	const double cyy_c = syy - sy * sy / sw;
@@ -297,6 +170,7 @@ __global__ __launch_bounds__(64) void en_solve_wide_kernel(WideArgs a, EnParams 
 // ---- rss from the rows of the groups whose moment identity cancelled (flag[gl] == 1), one wavefront per group ----
 struct RowsArgs {
 	const int64_t *row_offsets;
+	const int64_t *row_ends; // optional: group g owns rows [row_offsets[g], row_ends[g]) (BatchArgs::row_ends)
 	const double *y;
 	const double *x_table[kWideMaxP];
 	double *core;
@@ -317,7 +191,8 @@ __global__ __launch_bounds__(64) void rows_rss_kernel(RowsArgs a) {
 		int p_eff = 0;
 		for (int j = 0; j < p; ++j) p_eff += isnan(core[j]) ? 0 : 1;
 		double rss = 0.0;
-		for (int64_t row = a.row_offsets[g] + lane; row < a.row_offsets[g + 1]; row += 64) {
+		const int64_t hi = a.row_ends ? a.row_ends[g] : a.row_offsets[g + 1];
+		for (int64_t row = a.row_offsets[g] + lane; row < hi; row += 64) {
 			const double yv = a.y[row];
 			bool ok = isfinite(yv);
 			double fit = b0;
@@ -389,6 +264,7 @@ bool en_narrow_stage(AnofoxHipContext *, BatchArgs &a, hipStream_t st, void *use
 	RowsArgs ra;
 	memset(&ra, 0, sizeof ra);
 	ra.row_offsets = a.row_offsets;
+	ra.row_ends = a.row_ends;
 	ra.y = a.y;
 	for (int j = 0; j < a.p; ++j) ra.x_table[j] = a.x[j];
 	ra.core = a.core;
@@ -406,6 +282,7 @@ bool en_wide_stage(AnofoxHipContext *, WideArgs &a, hipStream_t st, int64_t, voi
 	RowsArgs ra;
 	memset(&ra, 0, sizeof ra);
 	ra.row_offsets = a.row_offsets;
+	ra.row_ends = a.row_ends;
 	ra.y = a.y;
 	for (int j = 0; j < a.p; ++j) ra.x_table[j] = a.x_table[j];
 	ra.core = a.core;
@@ -416,6 +293,11 @@ bool en_wide_stage(AnofoxHipContext *, WideArgs &a, hipStream_t st, int64_t, voi
 	ra.fit_intercept = a.fit_intercept;
 	return !hip_fail(launch_rows_rss(ra, st), "elastic net rows kernel launch", e);
 }
+
+bool validate_elasticnet_options(const AnofoxHipElasticNetBatchOptions &o, AnofoxError *e);
+EnParams elasticnet_params(const AnofoxHipElasticNetBatchOptions &o, int32_t *d_iterations);
+AnofoxHipBatchOptions elasticnet_moment_options(const AnofoxHipElasticNetBatchOptions &o, double confidence_level);
+SolveStages elasticnet_stages(EnParams *en);
 
 bool validate_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols,
                  const AnofoxHipElasticNetBatchOptions &o, const void *core, AnofoxError *e) {
@@ -430,6 +312,20 @@ bool validate_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, con
 	if (G > 0 && (!off || !y || !core)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets, y or core is NULL"); return false; }
 	for (size_t j = 0; j < p; ++j)
 		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
+	return validate_elasticnet_options(o, e);
+}
+
+bool run_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y, const double *const *x_cols,
+            const AnofoxHipElasticNetBatchOptions &o, double *d_core, int32_t *d_iterations, AnofoxError *e) {
+	if (G == 0) return true;
+	EnParams en = elasticnet_params(o, d_iterations);
+	const AnofoxHipBatchOptions acc = elasticnet_moment_options(o, 0.95);
+	const SolveStages stages = elasticnet_stages(&en);
+	// (the stages run before this call returns: `en` is captured by value into the kernel arguments at launch)
+	return moment_batch_device(ctx, G, p, n_rows, d_off, d_y, x_cols, acc, stages, d_core, e);
+}
+
+bool validate_elasticnet_options(const AnofoxHipElasticNetBatchOptions &o, AnofoxError *e) {
 	if (!(o.tolerance >= 0.0)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "tolerance must be >= 0"); return false; }
 	if ((int)o.lambda_scaling != ANOFOX_LAMBDA_SCALING_RAW && (int)o.lambda_scaling != ANOFOX_LAMBDA_SCALING_GLMNET) {
 		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "unknown lambda_scaling");
@@ -438,9 +334,7 @@ bool validate_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, con
 	return true;
 }
 
-bool run_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y, const double *const *x_cols,
-            const AnofoxHipElasticNetBatchOptions &o, double *d_core, int32_t *d_iterations, AnofoxError *e) {
-	if (G == 0) return true;
+EnParams elasticnet_params(const AnofoxHipElasticNetBatchOptions &o, int32_t *d_iterations) {
 	EnParams en;
 	en.alpha = o.alpha;
 	en.l1_ratio = o.l1_ratio;
@@ -448,15 +342,30 @@ bool run_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const in
 	en.max_iterations = o.max_iterations > 0x7fffffffu ? 0x7fffffff : (int)o.max_iterations;
 	en.lambda_scaling = (int)o.lambda_scaling;
 	en.iterations = d_iterations;
+	return en;
+}
+
+AnofoxHipBatchOptions elasticnet_moment_options(const AnofoxHipElasticNetBatchOptions &o, double confidence_level) {
 	AnofoxHipBatchOptions acc; // the moments of an unweighted fit
 	memset(&acc, 0, sizeof acc);
 	acc.model = ANOFOX_HIP_MODEL_OLS;
 	acc.fit_intercept = o.fit_intercept;
-	acc.confidence_level = 0.95;
+	acc.confidence_level = confidence_level;
 	acc.hc_type = ANOFOX_HC_NONE;
-	const SolveStages stages = {en_narrow_stage, en_wide_stage, &en};
-	// (the stages run before this call returns: `en` is captured by value into the kernel arguments at launch)
-	return moment_batch_device(ctx, G, p, n_rows, d_off, d_y, x_cols, acc, stages, d_core, e);
+	return acc;
+}
+
+SolveStages elasticnet_stages(EnParams *en) { return SolveStages{en_narrow_stage, en_wide_stage, en}; }
+
+// the in-register window kernels (window_narrow.hip, ElasticNetFit); ANOFOX_EN_WINDOW_NARROW=0 sends p <= 8 to the frames path
+// as well (A/B switch for measurements)
+hipError_t en_window_launch(const WindowArgs &a, void *user, hipStream_t st) {
+	return launch_window_predict_en(a, *static_cast<const EnParams *>(user), st);
+}
+
+WindowSolve elasticnet_window(EnParams *en) {
+	static const bool narrow_on = !(getenv("ANOFOX_EN_WINDOW_NARROW") && atoi(getenv("ANOFOX_EN_WINDOW_NARROW")) == 0);
+	return WindowSolve{elasticnet_stages(en), narrow_on ? en_window_launch : nullptr, en};
 }
 
 std::string fmt_g(double v) {
@@ -628,6 +537,75 @@ bool anofox_elasticnet_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x
 	out_core->n_observations = (size_t)core[p + 4];
 	out_core->n_features = p;
 	return true;
+}
+
+// ---- elastic net fit-predict (anofox_stats_elasticnet_fit_predict_agg, anofox_stats_elasticnet_fit_predict): the elastic net
+// record has the regression layout (p + 6), so the predict kernels and the frames path's predict apply unchanged ----
+
+bool anofox_hip_elasticnet_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                    const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                    const int64_t *d_train_counts, AnofoxHipElasticNetBatchOptions options,
+                                                    double confidence_level, double *d_core, double *d_pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!validate_elasticnet_options(options, out_error)) return false;
+	EnParams en = elasticnet_params(options, nullptr);
+	return model_fit_predict_batch_device(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_train_counts,
+	                                      elasticnet_moment_options(options, confidence_level), elasticnet_stages(&en), d_core, d_pred, out_error);
+}
+
+bool anofox_hip_elasticnet_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                  const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                  const int64_t *train_counts, AnofoxHipElasticNetBatchOptions options,
+                                                  double confidence_level, double *core, double *pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!validate_elasticnet_options(options, out_error)) return false;
+	EnParams en = elasticnet_params(options, nullptr);
+	return model_fit_predict_batch_host(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, train_counts,
+	                                    elasticnet_moment_options(options, confidence_level), elasticnet_stages(&en), core, pred, out_error);
+}
+
+bool anofox_hip_elasticnet_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                     const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                     AnofoxHipWindowFrame frame, AnofoxHipElasticNetBatchOptions options,
+                                                     double confidence_level, double *d_pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!validate_elasticnet_options(options, out_error)) return false;
+	EnParams en = elasticnet_params(options, nullptr);
+	return model_fit_predict_window_device(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, frame,
+	                                       elasticnet_moment_options(options, confidence_level), elasticnet_window(&en), d_pred, out_error);
+}
+
+bool anofox_hip_elasticnet_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                   const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                   AnofoxHipWindowFrame frame, AnofoxHipElasticNetBatchOptions options,
+                                                   double confidence_level, double *pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!validate_elasticnet_options(options, out_error)) return false;
+	EnParams en = elasticnet_params(options, nullptr);
+	return model_fit_predict_window_host(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, frame,
+	                                     elasticnet_moment_options(options, confidence_level), elasticnet_window(&en), pred, out_error);
+}
+
+bool anofox_hip_elasticnet_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *d_y,
+                                                     const double *const *x_cols, const int64_t *d_frame_lo, const int64_t *d_frame_hi,
+                                                     AnofoxHipElasticNetBatchOptions options, double confidence_level, double *d_pred,
+                                                     AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!validate_elasticnet_options(options, out_error)) return false;
+	EnParams en = elasticnet_params(options, nullptr);
+	return model_fit_predict_frames_device(ctx, n_rows, n_features, d_y, x_cols, d_frame_lo, d_frame_hi,
+	                                       elasticnet_moment_options(options, confidence_level), elasticnet_stages(&en), d_pred, out_error);
+}
+
+bool anofox_hip_elasticnet_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y,
+                                                   const double *const *x_cols, const int64_t *frame_lo, const int64_t *frame_hi,
+                                                   AnofoxHipElasticNetBatchOptions options, double confidence_level, double *pred,
+                                                   AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!validate_elasticnet_options(options, out_error)) return false;
+	EnParams en = elasticnet_params(options, nullptr);
+	return model_fit_predict_frames_host(ctx, n_rows, n_features, y, x_cols, frame_lo, frame_hi,
+	                                     elasticnet_moment_options(options, confidence_level), elasticnet_stages(&en), pred, out_error);
 }
 
 } // extern "C"

@@ -738,18 +738,12 @@ bool anofox_hip_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups
 	                   out_error);
 }
 
-bool anofox_hip_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
-                                       const int64_t *row_offsets, const double *y, const double *const *x_cols,
-                                       const double *w, const int64_t *train_counts, AnofoxHipBatchOptions options,
-                                       double *core, double *pred, AnofoxError *out_error) {
-	reset_error(out_error);
-	options.compute_inference = false;
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
-	if (!validate_batch(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, w, options, core, nullptr, out_error))
-		return false;
+namespace {
+
+// the host form of the fit-predict batch after the argument checks, with the solve stages of the model
+bool fit_predict_batch_host_run(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows, const int64_t *row_offsets,
+                                const double *y, const double *const *x_cols, const double *w, const int64_t *train_counts,
+                                const AnofoxHipBatchOptions &options, const SolveStages &stages, double *core, double *pred, AnofoxError *out_error) {
 	if (n_groups == 0) return true;
 	if (!pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
 	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) {
@@ -804,12 +798,31 @@ bool anofox_hip_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, 
 	double *d_core = (double *)cur;
 	cur += b_core;
 	double *d_pred = (double *)cur;
-	if (!run_device_batch(ctx, n_groups, p, n_rows, d_off, d_y, d_x, d_w, options, d_core, nullptr, out_error, d_cnt)) return false;
+	if (!run_device_batch(ctx, n_groups, p, n_rows, d_off, d_y, d_x, d_w, options, d_core, nullptr, out_error, d_cnt, stages)) return false;
 	if (!run_predict(ctx, n_groups, p, n_rows, d_off, d_x, d_core, options.confidence_level, d_pred, out_error)) return false;
 	if (hip_fail(hipMemcpyAsync(core, d_core, G * core_len * sizeof(double), hipMemcpyDeviceToHost, st), "D2H core", out_error)) return false;
 	if (R > 0 && hip_fail(hipMemcpyAsync(pred, d_pred, R * 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H pred", out_error)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
+
+} // namespace
+
+bool anofox_hip_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                       const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                       const double *w, const int64_t *train_counts, AnofoxHipBatchOptions options,
+                                       double *core, double *pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	options.compute_inference = false;
+	if (!ctx) {
+		ctx = default_context(out_error);
+		if (!ctx) return false;
+	}
+	if (!validate_batch(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, w, options, core, nullptr, out_error))
+		return false;
+	return fit_predict_batch_host_run(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, w, train_counts, options, kRegressionStages,
+	                                  core, pred, out_error);
+}
+
 
 
 namespace {
@@ -848,7 +861,7 @@ bool carve_frames(AnofoxHipContext *ctx, int64_t n_rows, int64_t n_frames, size_
 // Fit every frame [d_lo[e], d_hi[e]) as a group and predict its last row into d_pred[(d_list ? d_list[e] : e)].
 bool run_frames(AnofoxHipContext *ctx, const FrameScratch &fs, int64_t n_frames, size_t p, int64_t n_rows, const double *d_y,
                 const double *const *x_cols, const double *d_w, const int64_t *d_lo, const int64_t *d_hi, AnofoxHipBatchOptions opt,
-                double *d_pred, const int32_t *d_list, AnofoxError *e) {
+                double *d_pred, const int32_t *d_list, AnofoxError *e, const SolveStages &stages = kRegressionStages) {
 	if (n_frames == 0) return true;
 	opt.compute_inference = false; // the window functions fit without inference (ols_fit_predict.cpp:296)
 	opt.hc_type = ANOFOX_HC_NONE;
@@ -888,7 +901,7 @@ bool run_frames(AnofoxHipContext *ctx, const FrameScratch &fs, int64_t n_frames,
 		a.list = d_list ? d_list + s0 : nullptr;
 		ok = !hip_fail(launch_frames_rule(a, st), "frame rule kernel launch", e);
 		ctx->frame_ends = a.hi;
-		ok = ok && run_device_batch(ctx, S, p, n_rows, a.lo, d_y, x_cols, d_w, opt, fs.core, nullptr, e, fs.rule);
+		ok = ok && run_device_batch(ctx, S, p, n_rows, a.lo, d_y, x_cols, d_w, opt, fs.core, nullptr, e, fs.rule, stages);
 		ctx->frame_ends = nullptr;
 		ok = ok && !hip_fail(launch_frames_predict(a, st), "frame predict kernel launch", e);
 	}
@@ -900,11 +913,18 @@ bool run_frames(AnofoxHipContext *ctx, const FrameScratch &fs, int64_t n_frames,
 	return ok;
 }
 
+// ws != nullptr: another model's solve (the elastic net, elasticnet.hip) — its in-register kernels and its stages for the frames path
 bool run_window(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y,
                 const double *const *x_cols, const double *d_w, const AnofoxHipWindowFrame &frame,
-                const AnofoxHipBatchOptions &opt, double *d_pred, AnofoxError *e) {
+                const AnofoxHipBatchOptions &opt, double *d_pred, AnofoxError *e, const WindowSolve *ws = nullptr) {
 	if (G == 0) return true;
-	if (p > (size_t)kNarrowMaxP) {
+	const SolveStages stages = ws ? ws->stages : kRegressionStages;
+	// ill-conditioned frames are flagged by the kernel and refitted with the fit path's refinement passes.  Another model's
+	// kernels rely on that refit for frames whose moment RSS cancels (the elastic net does not clamp it): without flagging,
+	// every frame of such a model goes through the frames path.
+	static const bool flag_on = !(getenv("ANOFOX_WIN_FLAG") && atoi(getenv("ANOFOX_WIN_FLAG")) == 0); // A/B switch for measurements
+	const bool flagging = flag_on && n_rows > 0 && n_rows < (int64_t)0x7fffffff;
+	if (p > (size_t)kNarrowMaxP || (ws && (!ws->launch || !flagging))) {
 		// wider than the in-register window kernels: every frame becomes a virtual group of the batch fit (frames.hip)
 		if (n_rows == 0) return true;
 		FrameScratch fs;
@@ -915,7 +935,7 @@ bool run_window(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, cons
 		             "frame bounds kernel launch", e))
 			return false;
 		ctx->frame_prefix = frame.start_preceding == ANOFOX_HIP_FRAME_UNBOUNDED; // (every frame starts at its partition's first row)
-		const bool ok = run_frames(ctx, fs, n_rows, p, n_rows, d_y, x_cols, d_w, fs.lo, fs.hi, opt, d_pred, nullptr, e);
+		const bool ok = run_frames(ctx, fs, n_rows, p, n_rows, d_y, x_cols, d_w, fs.lo, fs.hi, opt, d_pred, nullptr, e, stages);
 		ctx->frame_prefix = false;
 		return ok;
 	}
@@ -943,9 +963,6 @@ bool run_window(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, cons
 	a.frame_start = frame.start_preceding;
 	a.frame_end = frame.end_preceding;
 	a.avg_rows = (n_rows > 0 && G > 0) ? (double)n_rows / (double)G : 0.0;
-	// ill-conditioned frames are flagged by the kernel and refitted below with the fit path's refinement passes
-	static const bool flag_on = !(getenv("ANOFOX_WIN_FLAG") && atoi(getenv("ANOFOX_WIN_FLAG")) == 0); // A/B switch for measurements
-	const bool flagging = flag_on && n_rows > 0 && n_rows < (int64_t)0x7fffffff;
 	if (flagging) {
 		if (!ensure_buffer(&ctx->aux, &ctx->aux_bytes, 256 + (size_t)n_rows * sizeof(int32_t), "window flag list", e)) return false;
 		a.flag_count = (int32_t *)ctx->aux;
@@ -959,7 +976,7 @@ bool run_window(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, cons
 		e1 = get_event(ctx);
 		(void)hipEventRecord(e0, st);
 	}
-	if (hip_fail(launch_window_predict(a, st), "window kernel launch", e)) return false;
+	if (hip_fail(ws ? ws->launch(a, ws->user, st) : launch_window_predict(a, st), "window kernel launch", e)) return false;
 	if (ctx->timing) {
 		(void)hipEventRecord(e1, st);
 		ctx->predict_events.emplace_back(e0, e1);
@@ -979,7 +996,7 @@ bool run_window(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, cons
 	if (hip_fail(launch_frames_from_rows_spec(d_off, G, n_rows, frame.start_preceding, frame.end_preceding, fs.lo, fs.hi, st, a.flag_list, n_flag),
 	             "frame bounds kernel launch", e))
 		return false;
-	return run_frames(ctx, fs, n_flag, p, n_rows, d_y, x_cols, d_w, fs.lo, fs.hi, opt, d_pred, a.flag_list, e);
+	return run_frames(ctx, fs, n_flag, p, n_rows, d_y, x_cols, d_w, fs.lo, fs.hi, opt, d_pred, a.flag_list, e, stages);
 }
 
 bool validate_window(AnofoxHipContext *ctx, int64_t G, size_t p, const void *off, const void *y, const double *const *x_cols,
@@ -1049,15 +1066,11 @@ bool anofox_hip_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows,
 	return run_frames(ctx, fs, n_rows, n_features, n_rows, d_y, x_cols, d_w, d_frame_lo, d_frame_hi, options, d_pred, nullptr, out_error);
 }
 
-bool anofox_hip_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y,
-                                        const double *const *x_cols, const double *w, const int64_t *frame_lo,
-                                        const int64_t *frame_hi, AnofoxHipBatchOptions options, double *pred, AnofoxError *out_error) {
-	reset_error(out_error);
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
-	if (!validate_frames(ctx, n_rows, n_features, y, x_cols, w, frame_lo, frame_hi, options, pred, out_error)) return false;
+namespace {
+
+bool frames_host_run(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y, const double *const *x_cols, const double *w,
+                     const int64_t *frame_lo, const int64_t *frame_hi, const AnofoxHipBatchOptions &options, const SolveStages &stages,
+                     double *pred, AnofoxError *out_error) {
 	if (n_rows == 0) return true;
 	for (int64_t e = 0; e < n_rows; ++e)
 		if (frame_lo[e] < 0 || frame_hi[e] > n_rows || (frame_hi[e] > frame_lo[e] && frame_lo[e] >= n_rows)) {
@@ -1099,10 +1112,25 @@ bool anofox_hip_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, s
 	FrameScratch fs;
 	if (!carve_frames(ctx, n_rows, n_rows, p, false, &fs, out_error)) return false;
 	if (hip_fail(launch_frames_ynn(d_y, n_rows, fs.ynn, fs.scan_tmp, fs.scan_tmp_bytes, st), "frame scan launch", out_error)) return false;
-	if (!run_frames(ctx, fs, n_rows, p, n_rows, d_y, d_x, d_w, d_lo, d_hi, options, d_pred, nullptr, out_error)) return false;
+	if (!run_frames(ctx, fs, n_rows, p, n_rows, d_y, d_x, d_w, d_lo, d_hi, options, d_pred, nullptr, out_error, stages)) return false;
 	if (hip_fail(hipMemcpyAsync(pred, d_pred, R * 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H pred", out_error)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
+
+} // namespace
+
+bool anofox_hip_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y,
+                                        const double *const *x_cols, const double *w, const int64_t *frame_lo,
+                                        const int64_t *frame_hi, AnofoxHipBatchOptions options, double *pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!ctx) {
+		ctx = default_context(out_error);
+		if (!ctx) return false;
+	}
+	if (!validate_frames(ctx, n_rows, n_features, y, x_cols, w, frame_lo, frame_hi, options, pred, out_error)) return false;
+	return frames_host_run(ctx, n_rows, n_features, y, x_cols, w, frame_lo, frame_hi, options, kRegressionStages, pred, out_error);
+}
+
 
 bool anofox_hip_fit_predict_expanding_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
                                              const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
@@ -1122,16 +1150,11 @@ bool anofox_hip_fit_predict_expanding_host(AnofoxHipContext *ctx, int64_t n_grou
 	                                          out_error);
 }
 
-bool anofox_hip_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
-                                        const int64_t *row_offsets, const double *y, const double *const *x_cols,
-                                        const double *w, AnofoxHipWindowFrame frame, AnofoxHipBatchOptions options,
-                                        double *pred, AnofoxError *out_error) {
-	reset_error(out_error);
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
-	if (!validate_window(ctx, n_groups, n_features, row_offsets, y, x_cols, w, frame, options, pred, out_error)) return false;
+namespace {
+
+bool window_host_run(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows, const int64_t *row_offsets, const double *y,
+                     const double *const *x_cols, const double *w, const AnofoxHipWindowFrame &frame, const AnofoxHipBatchOptions &options,
+                     const WindowSolve *ws, double *pred, AnofoxError *out_error) {
 	if (n_groups == 0) return true;
 	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) {
 		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
@@ -1172,10 +1195,26 @@ bool anofox_hip_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups,
 		cur += b_col;
 	}
 	double *d_pred = (double *)cur;
-	if (!run_window(ctx, n_groups, p, n_rows, d_off, d_y, d_x, d_w, frame, options, d_pred, out_error)) return false;
+	if (!run_window(ctx, n_groups, p, n_rows, d_off, d_y, d_x, d_w, frame, options, d_pred, out_error, ws)) return false;
 	if (R > 0 && hip_fail(hipMemcpyAsync(pred, d_pred, R * 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H pred", out_error)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
+
+} // namespace
+
+bool anofox_hip_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                        const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                        const double *w, AnofoxHipWindowFrame frame, AnofoxHipBatchOptions options,
+                                        double *pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!ctx) {
+		ctx = default_context(out_error);
+		if (!ctx) return false;
+	}
+	if (!validate_window(ctx, n_groups, n_features, row_offsets, y, x_cols, w, frame, options, pred, out_error)) return false;
+	return window_host_run(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, w, frame, options, nullptr, pred, out_error);
+}
+
 
 bool anofox_hip_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
                                const int64_t *row_offsets, const double *y, const double *const *x_cols,
@@ -1253,6 +1292,7 @@ bool anofox_hip_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n
 	}
 	return true;
 }
+
 
 } // extern "C"
 
@@ -1985,3 +2025,82 @@ void anofox_free_residuals(AnofoxResidualsResult *result) {
 }
 
 } // extern "C"
+
+/* ------------------------------------------------------------------------------------------------ */
+/* Fit-predict of another model's solve (the elastic net, elasticnet.hip): the regression entry      */
+/* points' argument checks, staging and paths with the model's solve stages and window kernels        */
+/* ------------------------------------------------------------------------------------------------ */
+
+namespace anofox {
+namespace host {
+
+bool model_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
+                                    const double *d_y, const double *const *x_cols, const int64_t *d_train_counts,
+                                    const AnofoxHipBatchOptions &opt, const SolveStages &stages, double *d_core, double *d_pred, AnofoxError *e) {
+	if (!validate_batch(ctx, n_groups, p, n_rows, d_row_offsets, d_y, x_cols, nullptr, opt, d_core, nullptr, e)) return false;
+	if (n_groups > 0 && !d_pred) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", e)) return false;
+	const bool ok = run_device_batch(ctx, n_groups, p, n_rows, d_row_offsets, d_y, x_cols, nullptr, opt, d_core, nullptr, e, d_train_counts, stages) &&
+	                run_predict(ctx, n_groups, p, n_rows, d_row_offsets, x_cols, d_core, opt.confidence_level, d_pred, e);
+	ctx->gate_wait = ctx->gate_record = nullptr; // the gate never outlives the call it was set for
+	return ok;
+}
+
+bool model_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets,
+                                  const double *y, const double *const *x_cols, const int64_t *train_counts, const AnofoxHipBatchOptions &opt,
+                                  const SolveStages &stages, double *core, double *pred, AnofoxError *e) {
+	if (!ctx) {
+		ctx = default_context(e);
+		if (!ctx) return false;
+	}
+	if (!validate_batch(ctx, n_groups, p, n_rows, row_offsets, y, x_cols, nullptr, opt, core, nullptr, e)) return false;
+	return fit_predict_batch_host_run(ctx, n_groups, p, n_rows, row_offsets, y, x_cols, nullptr, train_counts, opt, stages, core, pred, e);
+}
+
+bool model_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
+                                     const double *d_y, const double *const *x_cols, const AnofoxHipWindowFrame &frame,
+                                     const AnofoxHipBatchOptions &opt, const WindowSolve &ws, double *d_pred, AnofoxError *e) {
+	if (!validate_window(ctx, n_groups, p, d_row_offsets, d_y, x_cols, nullptr, frame, opt, d_pred, e)) return false;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", e)) return false;
+	return run_window(ctx, n_groups, p, n_rows, d_row_offsets, d_y, x_cols, nullptr, frame, opt, d_pred, e, &ws);
+}
+
+bool model_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets,
+                                   const double *y, const double *const *x_cols, const AnofoxHipWindowFrame &frame,
+                                   const AnofoxHipBatchOptions &opt, const WindowSolve &ws, double *pred, AnofoxError *e) {
+	if (!ctx) {
+		ctx = default_context(e);
+		if (!ctx) return false;
+	}
+	if (!validate_window(ctx, n_groups, p, row_offsets, y, x_cols, nullptr, frame, opt, pred, e)) return false;
+	return window_host_run(ctx, n_groups, p, n_rows, row_offsets, y, x_cols, nullptr, frame, opt, &ws, pred, e);
+}
+
+bool model_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size_t p, const double *d_y, const double *const *x_cols,
+                                     const int64_t *d_frame_lo, const int64_t *d_frame_hi, const AnofoxHipBatchOptions &opt,
+                                     const SolveStages &stages, double *d_pred, AnofoxError *e) {
+	if (!validate_frames(ctx, n_rows, p, d_y, x_cols, nullptr, d_frame_lo, d_frame_hi, opt, d_pred, e)) return false;
+	if (n_rows == 0) return true;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", e)) return false;
+	FrameScratch fs;
+	if (!carve_frames(ctx, n_rows, n_rows, p, false, &fs, e)) return false;
+	if (hip_fail(launch_frames_ynn(d_y, n_rows, fs.ynn, fs.scan_tmp, fs.scan_tmp_bytes, ctx->stream), "frame scan launch", e)) return false;
+	return run_frames(ctx, fs, n_rows, p, n_rows, d_y, x_cols, nullptr, d_frame_lo, d_frame_hi, opt, d_pred, nullptr, e, stages);
+}
+
+bool model_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t p, const double *y, const double *const *x_cols,
+                                   const int64_t *frame_lo, const int64_t *frame_hi, const AnofoxHipBatchOptions &opt,
+                                   const SolveStages &stages, double *pred, AnofoxError *e) {
+	if (!ctx) {
+		ctx = default_context(e);
+		if (!ctx) return false;
+	}
+	if (!validate_frames(ctx, n_rows, p, y, x_cols, nullptr, frame_lo, frame_hi, opt, pred, e)) return false;
+	return frames_host_run(ctx, n_rows, p, y, x_cols, nullptr, frame_lo, frame_hi, opt, stages, pred, e);
+}
+
+} // namespace host
+} // namespace anofox

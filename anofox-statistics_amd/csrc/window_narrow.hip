@@ -24,7 +24,9 @@
 // consecutive rows and hit L1/L2 after the first touch, so the direct sum costs O(frame) cached loads per row.
 #include "common.h"
 #include "device_math.h"
+#include "elasticnet_solve.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace anofox {
 
@@ -193,6 +195,30 @@ __device__ __forceinline__ void fit_from_moments(const double (&rec)[MomentLayou
 	out.nobs = cnt;
 }
 
+// The fit the window kernels run on each frame's moments (template parameter FIT): RegressionFit = the regression models'
+// Cholesky solve above (fit_from_moments, called directly so that those instantiations compile exactly as before), or
+// ElasticNetFit = the elastic net's coordinate descent (elasticnet_solve.h).  `suspect` sends the frame to the frames path.
+struct RegressionFit {};
+
+// Elastic net: the batch path's solve (en_fit_from_moments) on the frame's record; n_y = the frame's training rows (more than
+// p + [intercept] here, so the "< 2 rows" rule never fires).  Suspect: the moment rss cancelled (the batch path sums it from
+// the rows instead, rows_rss_kernel) or C + pen2 I fails the Cholesky pivot test of fit_from_moments.
+struct ElasticNetFit {
+	EnParams en;
+	template <int P>
+	__device__ __forceinline__ void fit(const double (&rec)[MomentLayout<P>::REC], bool icpt, double n_y, PrefixFit<P> &out) const {
+		double core[P + 6];
+		const EnSolveInfo s = en_fit_from_moments<P, true>(rec, en, icpt, (int64_t)n_y, core);
+		out.ok = core[P + 5] == 0.0;
+#pragma unroll
+		for (int j = 0; j < P; ++j) out.coef[j] = core[j];
+		out.intercept = core[P];
+		out.rse = core[P + 3];
+		out.nobs = core[P + 4];
+		out.suspect = s.cancels || s.small_pivot;
+	}
+};
+
 // inclusive prefix within segments of SEGW consecutive lanes (sl = lane % SEGW)
 template <int SEGW>
 __device__ __forceinline__ double scan_incl(double v, int sl) {
@@ -243,8 +269,9 @@ struct SegMap {
 	}
 };
 
-template <int P, bool WEIGHTED, bool CENTER, int SEGW>
-__global__ __launch_bounds__(256) void expanding_predict_kernel(WindowArgs args) {
+template <int P, bool WEIGHTED, bool CENTER, int SEGW, class FIT, class... FitArgs>
+__global__ __launch_bounds__(256) void expanding_predict_kernel(WindowArgs args, FitArgs... fit_args) {
+	const FIT fitter{fit_args...};
 	using L = MomentLayout<P>;
 	constexpr int Z = L::Z;
 	constexpr int ZZ = L::ZZ;
@@ -346,7 +373,8 @@ __global__ __launch_bounds__(256) void expanding_predict_kernel(WindowArgs args)
 		// when IT is not finite — lib.rs:2264-2349; an intercept-only fit predicts whatever x holds)
 		if (in && n_y > (double)(P + (icpt ? 1 : 0))) {       // ols_fit_predict.cpp:257-262 (strictly more)
 			PrefixFit<P> f;
-			fit_from_moments<P>(rec, args.model, icpt, args.alpha, args.lambda_scaling, f);
+			if constexpr (std::is_same<FIT, RegressionFit>::value) fit_from_moments<P>(rec, args.model, icpt, args.alpha, args.lambda_scaling, f);
+			else fitter.template fit<P>(rec, icpt, n_y, f);
 			suspect = f.ok && f.suspect;
 			if (f.ok) {
 				double v = isnan(f.intercept) ? 0.0 : f.intercept;
@@ -409,11 +437,12 @@ __global__ __launch_bounds__(256) void expanding_predict_kernel(WindowArgs args)
 }
 
 // Shared tail of both kernels: Finalize of the window aggregate for one frame (moments in rec), predicting z.
-template <int P>
-__device__ __forceinline__ void predict_from_moments(const WindowArgs &args, const double (&rec)[MomentLayout<P>::REC], bool icpt,
-                                                     const double (&z)[P + 1], double &yhat, double &ylo, double &yhi, bool &suspect) {
+template <int P, class FIT>
+__device__ __forceinline__ void predict_from_moments(const WindowArgs &args, const FIT &fitter, const double (&rec)[MomentLayout<P>::REC], bool icpt,
+                                                     double n_y, const double (&z)[P + 1], double &yhat, double &ylo, double &yhi, bool &suspect) {
 	PrefixFit<P> f;
-	fit_from_moments<P>(rec, args.model, icpt, args.alpha, args.lambda_scaling, f);
+	if constexpr (std::is_same<FIT, RegressionFit>::value) fit_from_moments<P>(rec, args.model, icpt, args.alpha, args.lambda_scaling, f);
+	else fitter.template fit<P>(rec, icpt, n_y, f);
 	if (!f.ok) return;
 	suspect = f.suspect;
 	double v = isnan(f.intercept) ? 0.0 : f.intercept;
@@ -432,8 +461,9 @@ __device__ __forceinline__ void predict_from_moments(const WindowArgs &args, con
 	yhi = v + margin;
 }
 
-template <int P, bool WEIGHTED, bool CENTER, int SEGW>
-__global__ __launch_bounds__(256) void rolling_predict_kernel(WindowArgs args) {
+template <int P, bool WEIGHTED, bool CENTER, int SEGW, class FIT, class... FitArgs>
+__global__ __launch_bounds__(256) void rolling_predict_kernel(WindowArgs args, FitArgs... fit_args) {
+	const FIT fitter{fit_args...};
 	using L = MomentLayout<P>;
 	constexpr int Z = L::Z;
 	constexpr int ZZ = L::ZZ;
@@ -531,7 +561,7 @@ __global__ __launch_bounds__(256) void rolling_predict_kernel(WindowArgs args) {
 			rec[L::OFF_SW] = sw;
 			rec[L::OFF_CNT] = cnt;
 			rec[L::OFF_MASK] = (double)mask;
-			predict_from_moments<P>(args, rec, icpt, z, yhat, ylo, yhi, suspect);
+			predict_from_moments<P>(args, fitter, rec, icpt, n_y, z, yhat, ylo, yhi, suspect);
 		}
 		if (in) {
 			double *out = args.pred + e * 3;
@@ -550,15 +580,15 @@ hipError_t launch_window_ps(const WindowArgs &a, hipStream_t stream) {
 	const bool weighted = a.model == ANOFOX_HIP_MODEL_WLS;
 	const bool center = a.fit_intercept != 0;
 	const bool rolling = a.frame_start != kFrameUnbounded;
-#define ANOFOX_WINDOW_LAUNCH(KERNEL)                                                                             \
-	do {                                                                                                         \
-		if (weighted) {                                                                                          \
-			if (center) hipLaunchKernelGGL((KERNEL<P, true, true, SEGW>), grid, block, 0, stream, a);            \
-			else hipLaunchKernelGGL((KERNEL<P, true, false, SEGW>), grid, block, 0, stream, a);                  \
-		} else {                                                                                                 \
-			if (center) hipLaunchKernelGGL((KERNEL<P, false, true, SEGW>), grid, block, 0, stream, a);           \
-			else hipLaunchKernelGGL((KERNEL<P, false, false, SEGW>), grid, block, 0, stream, a);                 \
-		}                                                                                                        \
+#define ANOFOX_WINDOW_LAUNCH(KERNEL)                                                                                          \
+	do {                                                                                                                      \
+		if (weighted) {                                                                                                       \
+			if (center) hipLaunchKernelGGL((KERNEL<P, true, true, SEGW, RegressionFit>), grid, block, 0, stream, a);     \
+			else hipLaunchKernelGGL((KERNEL<P, true, false, SEGW, RegressionFit>), grid, block, 0, stream, a);           \
+		} else {                                                                                                              \
+			if (center) hipLaunchKernelGGL((KERNEL<P, false, true, SEGW, RegressionFit>), grid, block, 0, stream, a);    \
+			else hipLaunchKernelGGL((KERNEL<P, false, false, SEGW, RegressionFit>), grid, block, 0, stream, a);          \
+		}                                                                                                                     \
 	} while (0)
 	if (rolling) ANOFOX_WINDOW_LAUNCH(rolling_predict_kernel);
 	else ANOFOX_WINDOW_LAUNCH(expanding_predict_kernel);
@@ -566,12 +596,11 @@ hipError_t launch_window_ps(const WindowArgs &a, hipStream_t stream) {
 	return hipGetLastError();
 }
 
-template <int P>
-hipError_t launch_window_p(const WindowArgs &a, hipStream_t stream) {
-	// Narrow segments waste fewer lanes on a partition's last tile and scan in fewer steps (3 instead of 6), so the
-	// expanding kernel prefers 8 lanes per partition whenever there are enough partitions to fill the machine that way
-	// (1M x 100 x 3: 3.5 ms vs 4.7 ms with a wavefront each; 4M x 20 x 3: 3.3 ms vs 9.1 ms); few long partitions keep
-	// whole wavefronts.  The rolling kernel has no scans: narrow segments only for short partitions.
+// Narrow segments waste fewer lanes on a partition's last tile and scan in fewer steps (3 instead of 6), so the
+// expanding kernel prefers 8 lanes per partition whenever there are enough partitions to fill the machine that way
+// (1M x 100 x 3: 3.5 ms vs 4.7 ms with a wavefront each; 4M x 20 x 3: 3.3 ms vs 9.1 ms); few long partitions keep
+// whole wavefronts.  The rolling kernel has no scans: narrow segments only for short partitions.
+inline int window_segw(const WindowArgs &a) {
 	int segw = 64;
 	if (a.avg_rows > 0.0) {
 		if (a.frame_start == kFrameUnbounded) {
@@ -583,9 +612,39 @@ hipError_t launch_window_p(const WindowArgs &a, hipStream_t stream) {
 		}
 	}
 	if (const char *e = getenv("ANOFOX_WIN_SEGW")) segw = atoi(e);
+	return segw;
+}
+
+template <int P>
+hipError_t launch_window_p(const WindowArgs &a, hipStream_t stream) {
+	const int segw = window_segw(a);
 	if (segw == 8) return launch_window_ps<P, 8>(a, stream);
 	if (segw == 16) return launch_window_ps<P, 16>(a, stream);
 	return launch_window_ps<P, 64>(a, stream);
+}
+
+// elastic net (unweighted): the same kernels with ElasticNetFit
+template <int P, int SEGW>
+hipError_t launch_window_en_ps(const WindowArgs &a, const EnParams &en, hipStream_t stream) {
+	const int64_t waves = (a.n_groups + (64 / SEGW) - 1) / (64 / SEGW);
+	const dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+	const bool center = a.fit_intercept != 0;
+	if (a.frame_start != kFrameUnbounded) {
+		if (center) hipLaunchKernelGGL((rolling_predict_kernel<P, false, true, SEGW, ElasticNetFit>), grid, block, 0, stream, a, en);
+		else hipLaunchKernelGGL((rolling_predict_kernel<P, false, false, SEGW, ElasticNetFit>), grid, block, 0, stream, a, en);
+	} else {
+		if (center) hipLaunchKernelGGL((expanding_predict_kernel<P, false, true, SEGW, ElasticNetFit>), grid, block, 0, stream, a, en);
+		else hipLaunchKernelGGL((expanding_predict_kernel<P, false, false, SEGW, ElasticNetFit>), grid, block, 0, stream, a, en);
+	}
+	return hipGetLastError();
+}
+
+template <int P>
+hipError_t launch_window_en_p(const WindowArgs &a, const EnParams &en, hipStream_t stream) {
+	const int segw = window_segw(a);
+	if (segw == 8) return launch_window_en_ps<P, 8>(a, en, stream);
+	if (segw == 16) return launch_window_en_ps<P, 16>(a, en, stream);
+	return launch_window_en_ps<P, 64>(a, en, stream);
 }
 
 } // namespace
@@ -607,6 +666,22 @@ hipError_t launch_window_predict(const WindowArgs &a, hipStream_t stream) {
 	case 6: return launch_window_p<6>(a, stream);
 	case 7: return launch_window_p<7>(a, stream);
 	case 8: return launch_window_p<8>(a, stream);
+	default: return hipErrorInvalidValue;
+	}
+}
+
+hipError_t launch_window_predict_en(const WindowArgs &a, const EnParams &en, hipStream_t stream) {
+	if (a.n_groups <= 0) return hipSuccess;
+	if (a.frame_start < a.frame_end || a.frame_start == -kFrameUnbounded || a.frame_end == kFrameUnbounded) return hipErrorInvalidValue;
+	switch (a.p) {
+	case 1: return launch_window_en_p<1>(a, en, stream);
+	case 2: return launch_window_en_p<2>(a, en, stream);
+	case 3: return launch_window_en_p<3>(a, en, stream);
+	case 4: return launch_window_en_p<4>(a, en, stream);
+	case 5: return launch_window_en_p<5>(a, en, stream);
+	case 6: return launch_window_en_p<6>(a, en, stream);
+	case 7: return launch_window_en_p<7>(a, en, stream);
+	case 8: return launch_window_en_p<8>(a, en, stream);
 	default: return hipErrorInvalidValue;
 	}
 }

@@ -140,6 +140,15 @@ class ElasticNetOptions:
                                             self.tolerance, _abi.LAMBDA_SCALING[self.lambda_scaling])
 
 
+@dataclass
+class ElasticNetPredictOptions(ElasticNetOptions):
+    """Options of the elastic net fit-predict family (anofox_stats_elasticnet_fit_predict_agg and
+    anofox_stats_elasticnet_fit_predict): the elastic net options plus the interval's confidence level and the null policy
+    (defaults of elasticnet_predict_aggregate.cpp:40-44)."""
+    confidence_level: float = 0.95
+    null_policy: str = "drop"
+
+
 def _extract_uint32(val: Any) -> Optional[int]:
     if val is None:
         return None
@@ -189,4 +198,34 @@ def parse_elasticnet_options(opts: Optional[Mapping[str, Any]]) -> ElasticNetOpt
         out.alpha = alpha
     elif lam is not None:
         out.alpha = lam
+    return out
+
+
+def parse_elasticnet_predict_options(opts: Optional[Mapping[str, Any]], use_lambda: bool = True) -> ElasticNetPredictOptions:
+    """Options of the elastic net fit-predict family: parse_elasticnet_options plus confidence_level / confidence and
+    null_policy ('drop', 'drop_y_zero_x').  use_lambda=False is the fit-predict aggregate's bind, which reads opts.alpha
+    only (elasticnet_predict_aggregate.cpp:405-431): a `lambda` key is ignored there, while the window function's bind
+    uses GetRegularizationStrength (alpha wins over lambda)."""
+    base = parse_elasticnet_options(opts)
+    out = ElasticNetPredictOptions(**vars(base))
+    if opts is None:
+        return out
+    has_alpha = False
+    for raw_key, val in opts.items():
+        key = str(raw_key).lower()
+        if key == "alpha" and val is not None:
+            has_alpha = True
+        elif key in ("confidence_level", "confidence"):
+            v = _extract_double(val)
+            if v is not None:
+                out.confidence_level = v
+        elif key == "null_policy":
+            if val is not None:
+                v = str(val).lower()
+                if v not in ("drop", "drop_y_zero_x"):
+                    raise InvalidInputException(
+                        f"Invalid null_policy: '{v}'. Valid values are 'drop', 'drop_y_zero_x'")
+                out.null_policy = v
+    if not use_lambda and not has_alpha:
+        out.alpha = ElasticNetPredictOptions.alpha
     return out

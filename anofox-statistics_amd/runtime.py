@@ -259,12 +259,91 @@ class Context:
         self._check(ok, err)
         return core, iterations
 
+    def elasticnet_fit_predict_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipElasticNetBatchOptions,
+                                            confidence_level: float = 0.95, train_counts=None, core=None, pred=None,
+                                            use_current_torch_stream: bool = True):
+        """Elastic net fit + per-row predictions, device resident.  Returns (core[G, p+6], pred[N, 3]) CUDA tensors."""
+        import torch
+
+        p = len(x_cols)
+        G = int(row_offsets.numel()) - 1
+        N = int(y.numel())
+        if core is None:
+            core = torch.empty((G, p + 6), dtype=torch.float64, device=y.device)
+        if pred is None:
+            pred = torch.empty((N, 3), dtype=torch.float64, device=y.device)
+        if use_current_torch_stream:
+            self.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
+        cols = (C.c_void_p * p)(*[c.data_ptr() for c in x_cols])
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_elasticnet_fit_predict_batch_device(
+            self._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols,
+            C.c_void_p(train_counts.data_ptr() if train_counts is not None else 0), options, float(confidence_level),
+            C.c_void_p(core.data_ptr()), C.c_void_p(pred.data_ptr()), C.byref(err))
+        self._gate_events = None
+        self._check(ok, err)
+        return core, pred
+
+    def elasticnet_fit_predict_window_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipElasticNetBatchOptions,
+                                             frame=(None, 0), confidence_level: float = 0.95, pred=None,
+                                             use_current_torch_stream: bool = True):
+        """Elastic net window fit + predict over ROWS BETWEEN frame[0] PRECEDING AND frame[1] PRECEDING, device resident.
+        Returns pred[N, 3] (CUDA tensor)."""
+        import torch
+
+        p = len(x_cols)
+        G = int(row_offsets.numel()) - 1
+        N = int(y.numel())
+        if pred is None:
+            pred = torch.empty((N, 3), dtype=torch.float64, device=y.device)
+        if use_current_torch_stream:
+            self.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
+        cols = (C.c_void_p * p)(*[c.data_ptr() for c in x_cols])
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_elasticnet_fit_predict_window_device(
+            self._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols, _frame(frame), options,
+            float(confidence_level), C.c_void_p(pred.data_ptr()), C.byref(err))
+        self._check(ok, err)
+        return pred
+
+    def elasticnet_fit_predict_frames_device(self, y, x_cols: Sequence, frame_lo, frame_hi,
+                                             options: _abi.AnofoxHipElasticNetBatchOptions, confidence_level: float = 0.95,
+                                             pred=None, use_current_torch_stream: bool = True):
+        """Elastic net fit + predict over explicit frames [frame_lo[e], frame_hi[e]), device resident.  Returns pred[N, 3]."""
+        import torch
+
+        p = len(x_cols)
+        N = int(y.numel())
+        if pred is None:
+            pred = torch.empty((N, 3), dtype=torch.float64, device=y.device)
+        if use_current_torch_stream:
+            self.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
+        cols = (C.c_void_p * p)(*[c.data_ptr() for c in x_cols])
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_elasticnet_fit_predict_frames_device(
+            self._h, N, p, C.c_void_p(y.data_ptr()), cols, C.c_void_p(frame_lo.data_ptr()), C.c_void_p(frame_hi.data_ptr()),
+            options, float(confidence_level), C.c_void_p(pred.data_ptr()), C.byref(err))
+        self._check(ok, err)
+        return pred
+
     # ---- host-resident batch (numpy) ----------------------------------------------------------
     def fit_batch_host(self, row_offsets, y, x_cols: Sequence, w, options: _abi.AnofoxHipBatchOptions):
         return fit_batch_host(row_offsets, y, x_cols, w, options, ctx=self)
 
     def elasticnet_fit_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipElasticNetBatchOptions):
         return elasticnet_fit_batch_host(row_offsets, y, x_cols, options, ctx=self)
+
+    def elasticnet_fit_predict_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipElasticNetBatchOptions,
+                                          confidence_level: float = 0.95, train_counts=None):
+        return elasticnet_fit_predict_batch_host(row_offsets, y, x_cols, options, confidence_level, train_counts, ctx=self)
+
+    def elasticnet_fit_predict_window_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipElasticNetBatchOptions,
+                                           frame=(None, 0), confidence_level: float = 0.95):
+        return elasticnet_fit_predict_window_host(row_offsets, y, x_cols, options, frame, confidence_level, ctx=self)
+
+    def elasticnet_fit_predict_frames_host(self, y, x_cols: Sequence, frame_lo, frame_hi,
+                                           options: _abi.AnofoxHipElasticNetBatchOptions, confidence_level: float = 0.95):
+        return elasticnet_fit_predict_frames_host(y, x_cols, frame_lo, frame_hi, options, confidence_level, ctx=self)
 
 
 _DP = C.POINTER(C.c_double)
@@ -565,6 +644,73 @@ def fit_predict_frames_host(y, x_cols: Sequence, w, frame_lo, frame_hi, options:
         ctx._h if ctx is not None else None, N, p, yv.ctypes.data_as(_DP), colp, None if wv is None else wv.ctypes.data_as(_DP),
         lo.ctypes.data_as(C.POINTER(C.c_int64)), hi.ctypes.data_as(C.POINTER(C.c_int64)), options, pred.ctypes.data_as(_DP),
         C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return pred
+
+
+def elasticnet_fit_predict_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipElasticNetBatchOptions,
+                                      confidence_level: float = 0.95, train_counts=None, ctx: Optional[Context] = None):
+    """Elastic net fit + predict, numpy in / out: (core[G, p+6], pred[N, 3] = yhat / yhat_lower / yhat_upper, NaN = NULL)."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    tc = None if train_counts is None else np.ascontiguousarray(train_counts, dtype=np.int64)
+    p, G, N = len(cols), len(off) - 1, len(yv)
+    if any(len(c) != N for c in cols):
+        raise ValueError("every column must have y's length")
+    core = np.empty((G, p + 6), dtype=np.float64)
+    pred = np.empty((N, 3), dtype=np.float64)
+    colp = (_DP * max(p, 1))(*[c.ctypes.data_as(_DP) for c in cols])
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_elasticnet_fit_predict_batch_host(
+        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP), colp,
+        None if tc is None else tc.ctypes.data_as(C.POINTER(C.c_int64)), options, float(confidence_level),
+        core.ctypes.data_as(_DP), pred.ctypes.data_as(_DP), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return core, pred
+
+
+def elasticnet_fit_predict_window_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipElasticNetBatchOptions,
+                                       frame=(None, 0), confidence_level: float = 0.95, ctx: Optional[Context] = None):
+    """Elastic net window fit + predict over ROWS frames (as fit_predict_window_host), numpy in / out: pred[N, 3]."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    p, G, N = len(cols), len(off) - 1, len(yv)
+    if any(len(c) != N for c in cols):
+        raise ValueError("every column must have y's length")
+    pred = np.empty((N, 3), dtype=np.float64)
+    colp = (_DP * max(p, 1))(*[c.ctypes.data_as(_DP) for c in cols])
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_elasticnet_fit_predict_window_host(
+        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP), colp,
+        _frame(frame), options, float(confidence_level), pred.ctypes.data_as(_DP), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return pred
+
+
+def elasticnet_fit_predict_frames_host(y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipElasticNetBatchOptions,
+                                       confidence_level: float = 0.95, ctx: Optional[Context] = None):
+    """Elastic net fit + predict over explicit frames [frame_lo[e], frame_hi[e]), numpy in / out: pred[N, 3]."""
+    lib = _abi.load()
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    lo = np.ascontiguousarray(frame_lo, dtype=np.int64)
+    hi = np.ascontiguousarray(frame_hi, dtype=np.int64)
+    p, N = len(cols), len(yv)
+    if any(len(c) != N for c in cols) or len(lo) != N or len(hi) != N:
+        raise ValueError("every column and both frame bounds must have y's length")
+    pred = np.empty((N, 3), dtype=np.float64)
+    colp = (_DP * max(p, 1))(*[c.ctypes.data_as(_DP) for c in cols])
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_elasticnet_fit_predict_frames_host(
+        ctx._h if ctx is not None else None, N, p, yv.ctypes.data_as(_DP), colp, lo.ctypes.data_as(C.POINTER(C.c_int64)),
+        hi.ctypes.data_as(C.POINTER(C.c_int64)), options, float(confidence_level), pred.ctypes.data_as(_DP), C.byref(err))
     if not ok:
         raise AnofoxStatsError(err.code, err.text())
     return pred

@@ -369,6 +369,25 @@ ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_batch_host(AnofoxHipContext *ctx, 
                                           AnofoxError *out_error);
 
 /*
+ * Elastic net fit + predict (anofox_stats_elasticnet_fit_predict_agg, src/aggregate_functions/
+ * elasticnet_predict_aggregate.cpp:300-395): the fit of anofox_hip_elasticnet_fit_batch_* on each group's training rows
+ * (finite y and x), then every row gets {yhat, yhat_lower, yhat_upper} (pred, [n_rows x 3], NaN = SQL NULL) with the
+ * simplified interval of anofox_predict_with_interval (the record's sigma and n) at confidence_level, as
+ * anofox_hip_fit_predict_batch_*.  train_counts (optional) is what the "fewer than 2 training rows -> NULL" rule looks at
+ * (:309); core receives the records (p + 6).  A group whose status is not 0 predicts NaN everywhere.
+ */
+ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                    const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                    const int64_t *d_train_counts, AnofoxHipElasticNetBatchOptions options,
+                                                    double confidence_level, double *d_core, double *d_pred, AnofoxError *out_error);
+/* host pointers, synchronous; ctx may be NULL (per-thread default context) */
+ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                  const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                  const int64_t *train_counts, AnofoxHipElasticNetBatchOptions options,
+                                                  double confidence_level, double *core, double *pred, AnofoxError *out_error);
+
+
+/*
  * Information criteria as batched outputs of the fit records: what the SQL functions
  * aic(rss, n, k) / bic(rss, n, k) (src/scalar_functions/aic_bic.cpp:12-110 over
  * crates/anofox-stats-core/src/diagnostics/information_criteria.rs:15-33,67-85) give when they are applied to every
@@ -464,6 +483,33 @@ ANOFOX_HIP_API bool anofox_hip_fit_predict_frames_host(AnofoxHipContext *ctx, in
                                         const double *const *x_cols, const double *w, const int64_t *frame_lo,
                                         const int64_t *frame_hi, AnofoxHipBatchOptions options, double *pred,
                                         AnofoxError *out_error);
+
+/*
+ * The elastic net window function anofox_stats_elasticnet_fit_predict(y, x [, options]) OVER (... ROWS ...)
+ * (src/window_functions/elasticnet_fit_predict.cpp:150-330): per output row, the elastic net fit of the frame's rows with
+ * non-NULL y, NULL unless MORE than p + [intercept] such rows exist, predicting the x of the frame's LAST row; frames as
+ * anofox_hip_fit_predict_window_* (the expanding window is frame = {ANOFOX_HIP_FRAME_UNBOUNDED, 0}).  For p <= 8 the
+ * in-register window kernels solve every frame from its moments; frames whose moment rss cancels or that fail the
+ * Cholesky pivot test are refitted through the frames path, which serves p > 8 entirely.
+ */
+ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                     const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                     AnofoxHipWindowFrame frame, AnofoxHipElasticNetBatchOptions options,
+                                                     double confidence_level, double *d_pred, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                   const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                   AnofoxHipWindowFrame frame, AnofoxHipElasticNetBatchOptions options,
+                                                   double confidence_level, double *pred, AnofoxError *out_error);
+/* the same over explicit frames [frame_lo[e], frame_hi[e]) (as anofox_hip_fit_predict_frames_*): every frame a group of the
+ * elastic net batch fit */
+ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *d_y,
+                                                     const double *const *x_cols, const int64_t *d_frame_lo, const int64_t *d_frame_hi,
+                                                     AnofoxHipElasticNetBatchOptions options, double confidence_level, double *d_pred,
+                                                     AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y,
+                                                   const double *const *x_cols, const int64_t *frame_lo, const int64_t *frame_hi,
+                                                   AnofoxHipElasticNetBatchOptions options, double confidence_level, double *pred,
+                                                   AnofoxError *out_error);
 
 /*
  * Grouped variance inflation factors: the Finalize loop of vif_agg (src/aggregate_functions/vif_aggregate.cpp:
