@@ -17,11 +17,13 @@ from .aggregate import (StreamingStates, FitAggResult, FitPredictAggResult, OlsF
                         ols_fit_predict_agg, ridge_fit_agg, ridge_fit_predict_agg, wls_fit_agg, wls_fit_predict_agg,
                         result_from_records, ols_fit_predict, ridge_fit_predict, wls_fit_predict, vif_agg,
                         residuals_diagnostics_agg, ElasticNetFitPredictAgg, elasticnet_fit_predict_agg,
-                        elasticnet_fit_predict)
+                        elasticnet_fit_predict, RlsFitAgg, rls_fit_agg, RlsFitPredictAgg, rls_fit_predict_agg,
+                        rls_fit_predict)
 from .options import (ElasticNetOptions, ElasticNetPredictOptions, InvalidInputException, RegressionOptions,  # noqa: E402
-                      parse_elasticnet_options, parse_elasticnet_predict_options, parse_options)
-from .runtime import AggState, Context, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
-from .scalar import aic, bic, elasticnet_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
+                      parse_elasticnet_options, parse_elasticnet_predict_options, parse_options, RlsOptions,
+                      parse_rls_options)
+from .runtime import AggState, Context, rls_fit_batch_host, rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
+from .scalar import aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
 # src/scalar_functions/{aic_bic,vif}.cpp) and the deprecated aggregate aliases
@@ -30,6 +32,7 @@ SQL_FUNCTIONS.update({
     "anofox_stats_ridge_fit": ridge_fit, "ridge_fit": ridge_fit,
     "anofox_stats_wls_fit": wls_fit, "wls_fit": wls_fit,
     "anofox_stats_elasticnet_fit": elasticnet_fit, "elasticnet_fit": elasticnet_fit,
+    "anofox_stats_rls_fit": rls_fit, "rls_fit": rls_fit,
     "anofox_stats_predict": predict,
     "anofox_stats_aic": aic, "aic": aic, "anofox_stats_bic": bic, "bic": bic,
     "anofox_stats_vif": vif, "vif": vif,
@@ -49,6 +52,9 @@ __all__ = [
     "ElasticNetPredictOptions", "parse_elasticnet_predict_options", "ElasticNetFitPredictAgg", "elasticnet_fit_predict_agg",
     "elasticnet_fit_predict", "elasticnet_fit_predict_batch_host", "elasticnet_fit_predict_window_host",
     "elasticnet_fit_predict_frames_host",
+    "RlsOptions", "parse_rls_options", "rls_fit", "RlsFitAgg", "rls_fit_agg", "RlsFitPredictAgg", "rls_fit_predict_agg",
+    "rls_fit_predict", "rls_fit_batch_host", "rls_fit_predict_batch_host", "rls_fit_predict_window_host",
+    "rls_fit_predict_frames_host",
 ]
 
 

@@ -112,6 +112,14 @@ class AnofoxHipElasticNetBatchOptions(C.Structure):
                 ("max_iterations", C.c_uint32), ("tolerance", C.c_double), ("lambda_scaling", C.c_int)]
 
 
+class AnofoxRlsOptions(C.Structure):  # anofox_stats_ffi.h:593-600, 24 bytes
+    _fields_ = [("forgetting_factor", C.c_double), ("fit_intercept", C.c_bool), ("initial_p_diagonal", C.c_double)]
+
+
+class AnofoxHipRlsBatchOptions(C.Structure):
+    _fields_ = [("fit_intercept", C.c_bool), ("forgetting_factor", C.c_double), ("initial_p_diagonal", C.c_double)]
+
+
 # every symbol include/anofox_stats_hip.h declares: name -> (restype, argtypes)
 _ERRP = C.POINTER(AnofoxError)
 _CTX = C.c_void_p
@@ -253,6 +261,30 @@ SYMBOLS = {
     "anofox_hip_elasticnet_fit_predict_frames_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, _DP, C.POINTER(_DP), C.POINTER(C.c_int64),
                                                                  C.POINTER(C.c_int64), AnofoxHipElasticNetBatchOptions, C.c_double,
                                                                  _DP, _ERRP]),
+    "anofox_rls_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxRlsOptions,
+                                  C.POINTER(AnofoxFitResultCore), _ERRP]),
+    "anofox_hip_rls_fit_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_void_p), AnofoxHipRlsBatchOptions, C.c_void_p, _ERRP]),
+    "anofox_hip_rls_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                 C.POINTER(_DP), AnofoxHipRlsBatchOptions, _DP, _ERRP]),
+    "anofox_hip_rls_fit_predict_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                           C.POINTER(C.c_void_p), C.c_void_p, AnofoxHipRlsBatchOptions,
+                                                           C.c_double, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_rls_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                         C.POINTER(_DP), C.POINTER(C.c_int64), AnofoxHipRlsBatchOptions,
+                                                         C.c_double, _DP, _DP, _ERRP]),
+    "anofox_hip_rls_fit_predict_window_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                            C.POINTER(C.c_void_p), AnofoxHipWindowFrame,
+                                                            AnofoxHipRlsBatchOptions, C.c_double, C.c_void_p, _ERRP]),
+    "anofox_hip_rls_fit_predict_window_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                          C.POINTER(_DP), AnofoxHipWindowFrame, AnofoxHipRlsBatchOptions,
+                                                          C.c_double, _DP, _ERRP]),
+    "anofox_hip_rls_fit_predict_frames_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p),
+                                                            C.c_void_p, C.c_void_p, AnofoxHipRlsBatchOptions, C.c_double,
+                                                            C.c_void_p, _ERRP]),
+    "anofox_hip_rls_fit_predict_frames_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, _DP, C.POINTER(_DP), C.POINTER(C.c_int64),
+                                                          C.POINTER(C.c_int64), AnofoxHipRlsBatchOptions, C.c_double,
+                                                          _DP, _ERRP]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "anofox_hip_host_free": (None, [C.c_void_p]),
 }

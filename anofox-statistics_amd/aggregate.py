@@ -22,7 +22,7 @@ from typing import Any, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .options import InvalidInputException, RegressionOptions, parse_elasticnet_predict_options, parse_options
+from .options import InvalidInputException, RegressionOptions, parse_elasticnet_predict_options, parse_options, parse_rls_options
 from .runtime import AggState, Context, fit_batch_host
 
 
@@ -780,4 +780,97 @@ SQL_FUNCTIONS.update({
     "anofox_stats_elasticnet_fit_predict_agg": elasticnet_fit_predict_agg, "elasticnet_fit_predict_agg": elasticnet_fit_predict_agg,
     "elasticnet_predict_agg": elasticnet_fit_predict_agg, "anofox_stats_elasticnet_predict_agg": elasticnet_fit_predict_agg,
     "anofox_stats_elasticnet_fit_predict": elasticnet_fit_predict, "elasticnet_fit_predict": elasticnet_fit_predict,
+})
+
+
+# ------------------------------------------------------------------------------------------------------
+# recursive least squares: anofox_stats_rls_fit_agg (src/aggregate_functions/rls_aggregate.cpp),
+# anofox_stats_rls_fit_predict_agg (rls_predict_aggregate.cpp) and the window function anofox_stats_rls_fit_predict
+# (src/window_functions/rls_fit_predict.cpp).  RLS depends on row order, so the rows are buffered in arrival order
+# (Combine appends the source's rows after the target's) and there is no streaming moment state.
+# ------------------------------------------------------------------------------------------------------
+class RlsFitAgg(_FitAgg):
+    """anofox_stats_rls_fit_agg(y, x [, options]): the reference's filter per group over its rows in arrival order."""
+    model = "rls"
+    sql_name = "anofox_stats_rls_fit_agg"
+
+    def __init__(self, options: Optional[Mapping[str, Any]] = None, context: Optional[Context] = None):
+        super().__init__(None, context)
+        self.options = parse_rls_options(options)
+
+    def finalize(self) -> FitAggResult:
+        from .runtime import rls_fit_batch_host
+        ukeys, offsets, y, x_cols, _ = self.grouped_columns()
+        G = len(ukeys)
+        if self.n_features is None:       # no row was ever accumulated: every group is NULL
+            core = np.full((G, 6), np.nan)
+            core[:, 5] = _abi.STATUS_NULL_TOO_FEW_ROWS
+            return result_from_records(ukeys, core, None, 0)
+        core = rls_fit_batch_host(offsets, y, x_cols, self.options.batch_options(), ctx=self._ctx)
+        return result_from_records(ukeys, core, None, self.n_features)
+
+
+def rls_fit_agg(group_keys, y, x, options=None, context=None) -> FitAggResult:
+    return RlsFitAgg(options, context).update(group_keys, y, x).finalize()
+
+
+class RlsFitPredictAgg(_FitPredictAgg):
+    """anofox_stats_rls_fit_predict_agg: training rows as the other fit-predict aggregates, "fewer than 2 training rows
+    -> NULL", a failed fit -> NULL; yhat = yhat_lower = yhat_upper (the RLS record has no sigma)."""
+    model = "rls"
+    sql_name = "anofox_stats_rls_fit_predict_agg"
+
+    @staticmethod
+    def _parse_options(options):
+        return parse_rls_options(options)
+
+    def _fit_predict(self, offsets, y_fit, x_cols, w, train_counts):
+        from .runtime import rls_fit_predict_batch_host
+        return rls_fit_predict_batch_host(offsets, y_fit, x_cols, self.options.batch_options(), self.options.confidence_level,
+                                          train_counts=train_counts, ctx=self._ctx)
+
+
+def rls_fit_predict_agg(group_keys, y, x, options=None, context=None, split=None) -> FitPredictAggResult:
+    return RlsFitPredictAgg(options, context).update(group_keys, y, x, split=split).finalize()
+
+
+def rls_fit_predict(partition_keys, order, y, x, options=None, context=None, frame_end="current row", frame=None):
+    """anofox_stats_rls_fit_predict(y, x [, options]) OVER (PARTITION BY partition_keys ORDER BY order ROWS ...):
+    (yhat, yhat_lower, yhat_upper) per input row, in input order; NaN = SQL NULL.  Frames as ols_fit_predict."""
+    from .runtime import rls_fit_predict_window_host
+    opts = parse_rls_options(options)
+    start, end = _parse_frame(frame, frame_end)
+    keys = np.asarray(partition_keys)
+    yv, ynull = _null_mask_1d(y)
+    yv = np.where(ynull, np.nan, yv)
+    rows = [None if r is None else [np.nan if v is None else float(v) for v in r] for r in x]
+    p = max((len(r) for r in rows if r is not None), default=0)
+    Xd = np.full((len(yv), p), np.nan)
+    for i, r in enumerate(rows):
+        if r is None:
+            continue                                             # NULL x list: no current x, no training
+        if len(r) != p:
+            raise InvalidInputException(f"Inconsistent feature count: expected {p}, got {len(r)}")
+        Xd[i] = r
+    xnull = np.array([r is None for r in rows], dtype=bool)
+    yv = np.where(xnull, np.nan, yv)                             # a NULL x list is never buffered (rls_fit_predict.cpp:119-122)
+    if opts.null_policy == "drop_y_zero_x":                      # rls_fit_predict.cpp:147-154
+        yv = np.where(np.any(Xd == 0.0, axis=1), np.nan, yv)
+    ukeys, gid = np.unique(keys, return_inverse=True)
+    perm = np.lexsort((np.asarray(order), gid))
+    counts = np.bincount(gid, minlength=len(ukeys))
+    offsets = np.zeros(len(ukeys) + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    pred_sorted = rls_fit_predict_window_host(offsets, yv[perm], [np.ascontiguousarray(Xd[perm, j]) for j in range(p)],
+                                              opts.batch_options(), (start, end), opts.confidence_level, ctx=context)
+    out = np.empty_like(pred_sorted)
+    out[perm] = pred_sorted
+    return out[:, 0], out[:, 1], out[:, 2]
+
+
+SQL_FUNCTIONS.update({
+    "anofox_stats_rls_fit_agg": rls_fit_agg, "rls_fit_agg": rls_fit_agg,
+    "anofox_stats_rls_fit_predict_agg": rls_fit_predict_agg, "rls_fit_predict_agg": rls_fit_predict_agg,
+    "rls_predict_agg": rls_fit_predict_agg, "anofox_stats_rls_predict_agg": rls_fit_predict_agg,
+    "anofox_stats_rls_fit_predict": rls_fit_predict, "rls_fit_predict": rls_fit_predict,
 })

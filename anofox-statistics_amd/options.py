@@ -229,3 +229,67 @@ def parse_elasticnet_predict_options(opts: Optional[Mapping[str, Any]], use_lamb
     if not use_lambda and not has_alpha:
         out.alpha = ElasticNetPredictOptions.alpha
     return out
+
+
+@dataclass
+class RlsOptions:
+    """Resolved options of recursive least squares (defaults = the reference's RlsOptions and the bind data of
+    rls_aggregate.cpp / rls_predict_aggregate.cpp / rls_fit_predict.cpp)."""
+    forgetting_factor: float = 1.0
+    initial_p_diagonal: float = 100.0
+    fit_intercept: bool = True
+    confidence_level: float = 0.95
+    null_policy: str = "drop"
+
+    def batch_options(self) -> _abi.AnofoxHipRlsBatchOptions:
+        return _abi.AnofoxHipRlsBatchOptions(self.fit_intercept, self.forgetting_factor, self.initial_p_diagonal)
+
+    def ffi_options(self) -> _abi.AnofoxRlsOptions:
+        return _abi.AnofoxRlsOptions(self.forgetting_factor, self.fit_intercept, self.initial_p_diagonal)
+
+
+def parse_rls_options(opts: Optional[Mapping[str, Any]]) -> RlsOptions:
+    """The RLS functions' MAP options through the shared parser (map_options_parser.cpp:637-681): forgetting_factor,
+    initial_p_diagonal / p_diagonal, fit_intercept / intercept, confidence_level / confidence and null_policy are read.
+    Every other key is ignored — `lambda` included: the reference's own tests pass {'lambda': 0.99}, which the parser
+    stores as a regularisation strength that RLS never reads, so the forgetting factor stays 1.0.  A value the shared
+    parser cannot convert is still an error, whichever key it sits under."""
+    out = RlsOptions()
+    if opts is None:
+        return out
+    if not isinstance(opts, Mapping):
+        raise InvalidInputException("Options parameter must be a constant expression")
+    for raw_key, val in opts.items():
+        key = str(raw_key).lower()
+        if key in ("intercept", "fit_intercept"):
+            v = _extract_bool(val)
+            if v is not None:
+                out.fit_intercept = v
+        elif key in ("compute_inference", "inference"):
+            _extract_bool(val)
+        elif key in ("confidence_level", "confidence"):
+            v = _extract_double(val)
+            if v is not None:
+                out.confidence_level = v
+        elif key == "forgetting_factor":
+            v = _extract_double(val)
+            if v is not None:
+                out.forgetting_factor = v
+        elif key in ("initial_p_diagonal", "p_diagonal"):
+            v = _extract_double(val)
+            if v is not None:
+                out.initial_p_diagonal = v
+        elif key == "null_policy":
+            if val is not None:
+                v = str(val).lower()
+                if v not in ("drop", "drop_y_zero_x"):
+                    raise InvalidInputException(
+                        f"Invalid null_policy: '{v}'. Valid values are 'drop', 'drop_y_zero_x'")
+                out.null_policy = v
+        elif key in ("alpha", "lambda", "l1_ratio", "tolerance", "tol", "epsilon"):
+            _extract_double(val)                     # parsed by the shared parser, not read by RLS
+        elif key in ("max_iterations", "max_iter"):
+            _extract_uint32(val)
+        elif key == "lambda_scaling":
+            _extract_enum(val, _abi.LAMBDA_SCALING, "lambda_scaling", "'raw', 'glmnet'")
+    return out

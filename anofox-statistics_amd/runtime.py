@@ -326,6 +326,102 @@ class Context:
         self._check(ok, err)
         return pred
 
+    # ---- recursive least squares (device resident) ---------------------------------------------
+    def _rls_cols(self, y, x_cols, use_current_torch_stream):
+        import torch
+
+        for t in (y, *x_cols):
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float64:
+                raise ValueError("device calls need contiguous float64 CUDA tensors")
+        if any(int(c.numel()) != int(y.numel()) for c in x_cols):
+            raise ValueError("every column must have y's length")
+        if use_current_torch_stream:
+            self.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
+        return (C.c_void_p * len(x_cols))(*[c.data_ptr() for c in x_cols])
+
+    def rls_fit_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipRlsBatchOptions, core=None,
+                             use_current_torch_stream: bool = True):
+        """Grouped RLS on CUDA tensors (row_offsets int64[G+1], y / x_cols[j] float64[N]).  Asynchronous.  Returns core[G, p+6]."""
+        import torch
+
+        p, G, N = len(x_cols), int(row_offsets.numel()) - 1, int(y.numel())
+        cols = self._rls_cols(y, x_cols, use_current_torch_stream)
+        if core is None:
+            core = torch.empty((G, p + 6), dtype=torch.float64, device=y.device)
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_rls_fit_batch_device(self._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                       cols, options, C.c_void_p(core.data_ptr()), C.byref(err))
+        self._check(ok, err)
+        return core
+
+    def rls_fit_predict_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipRlsBatchOptions,
+                                     confidence_level: float = 0.95, train_counts=None, core=None, pred=None,
+                                     use_current_torch_stream: bool = True):
+        """RLS fit + per-row predictions, device resident.  Returns (core[G, p+6], pred[N, 3]) CUDA tensors."""
+        import torch
+
+        p, G, N = len(x_cols), int(row_offsets.numel()) - 1, int(y.numel())
+        cols = self._rls_cols(y, x_cols, use_current_torch_stream)
+        if core is None:
+            core = torch.empty((G, p + 6), dtype=torch.float64, device=y.device)
+        if pred is None:
+            pred = torch.empty((N, 3), dtype=torch.float64, device=y.device)
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_rls_fit_predict_batch_device(
+            self._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols,
+            C.c_void_p(train_counts.data_ptr() if train_counts is not None else 0), options, float(confidence_level),
+            C.c_void_p(core.data_ptr()), C.c_void_p(pred.data_ptr()), C.byref(err))
+        self._check(ok, err)
+        return core, pred
+
+    def rls_fit_predict_window_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipRlsBatchOptions,
+                                      frame=(None, 0), confidence_level: float = 0.95, pred=None,
+                                      use_current_torch_stream: bool = True):
+        """RLS window fit + predict over ROWS BETWEEN frame[0] PRECEDING AND frame[1] PRECEDING.  Returns pred[N, 3]."""
+        import torch
+
+        p, G, N = len(x_cols), int(row_offsets.numel()) - 1, int(y.numel())
+        cols = self._rls_cols(y, x_cols, use_current_torch_stream)
+        if pred is None:
+            pred = torch.empty((N, 3), dtype=torch.float64, device=y.device)
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_rls_fit_predict_window_device(
+            self._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols, _frame(frame), options,
+            float(confidence_level), C.c_void_p(pred.data_ptr()), C.byref(err))
+        self._check(ok, err)
+        return pred
+
+    def rls_fit_predict_frames_device(self, y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipRlsBatchOptions,
+                                      confidence_level: float = 0.95, pred=None, use_current_torch_stream: bool = True):
+        """RLS fit + predict over explicit frames [frame_lo[e], frame_hi[e]), device resident.  Returns pred[N, 3]."""
+        import torch
+
+        p, N = len(x_cols), int(y.numel())
+        cols = self._rls_cols(y, x_cols, use_current_torch_stream)
+        if pred is None:
+            pred = torch.empty((N, 3), dtype=torch.float64, device=y.device)
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_rls_fit_predict_frames_device(
+            self._h, N, p, C.c_void_p(y.data_ptr()), cols, C.c_void_p(frame_lo.data_ptr()), C.c_void_p(frame_hi.data_ptr()),
+            options, float(confidence_level), C.c_void_p(pred.data_ptr()), C.byref(err))
+        self._check(ok, err)
+        return pred
+
+    def rls_fit_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipRlsBatchOptions):
+        return rls_fit_batch_host(row_offsets, y, x_cols, options, ctx=self)
+
+    def rls_fit_predict_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipRlsBatchOptions,
+                                   confidence_level: float = 0.95, train_counts=None):
+        return rls_fit_predict_batch_host(row_offsets, y, x_cols, options, confidence_level, train_counts, ctx=self)
+
+    def rls_fit_predict_window_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipRlsBatchOptions,
+                                    frame=(None, 0), confidence_level: float = 0.95):
+        return rls_fit_predict_window_host(row_offsets, y, x_cols, options, frame, confidence_level, ctx=self)
+
+    def rls_fit_predict_frames_host(self, y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipRlsBatchOptions,
+                                    confidence_level: float = 0.95):
+        return rls_fit_predict_frames_host(y, x_cols, frame_lo, frame_hi, options, confidence_level, ctx=self)
+
     # ---- host-resident batch (numpy) ----------------------------------------------------------
     def fit_batch_host(self, row_offsets, y, x_cols: Sequence, w, options: _abi.AnofoxHipBatchOptions):
         return fit_batch_host(row_offsets, y, x_cols, w, options, ctx=self)
@@ -754,3 +850,83 @@ def residuals_batch_host(row_offsets, y, y_hat, x_cols: Sequence = (), rse=None,
     if not ok:
         raise AnofoxStatsError(err.code, err.text())
     return out, group
+
+
+def _host_cols(y, x_cols):
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    if any(len(c) != len(yv) for c in cols):
+        raise ValueError("every column must have y's length")
+    return yv, cols, (_DP * max(len(cols), 1))(*[c.ctypes.data_as(_DP) for c in cols])
+
+
+def rls_fit_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipRlsBatchOptions, ctx: Optional[Context] = None):
+    """Grouped RLS, numpy in / out: core[G, p+6] (DESIGN.md §1 "Recursive least squares")."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv, cols, colp = _host_cols(y, x_cols)
+    p, G, N = len(cols), len(off) - 1, len(yv)
+    core = np.empty((max(G, 0), p + 6), dtype=np.float64)
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_rls_fit_batch_host(ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)),
+                                           yv.ctypes.data_as(_DP), colp, options, core.ctypes.data_as(_DP), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return core
+
+
+def rls_fit_predict_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipRlsBatchOptions,
+                               confidence_level: float = 0.95, train_counts=None, ctx: Optional[Context] = None):
+    """RLS fit + predict, numpy in / out: (core[G, p+6], pred[N, 3] = yhat / yhat_lower / yhat_upper, NaN = NULL)."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv, cols, colp = _host_cols(y, x_cols)
+    tc = None if train_counts is None else np.ascontiguousarray(train_counts, dtype=np.int64)
+    p, G, N = len(cols), len(off) - 1, len(yv)
+    core = np.empty((max(G, 0), p + 6), dtype=np.float64)
+    pred = np.empty((N, 3), dtype=np.float64)
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_rls_fit_predict_batch_host(
+        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP), colp,
+        None if tc is None else tc.ctypes.data_as(C.POINTER(C.c_int64)), options, float(confidence_level),
+        core.ctypes.data_as(_DP), pred.ctypes.data_as(_DP), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return core, pred
+
+
+def rls_fit_predict_window_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipRlsBatchOptions, frame=(None, 0),
+                                confidence_level: float = 0.95, ctx: Optional[Context] = None):
+    """RLS window fit + predict over ROWS frames (as fit_predict_window_host), numpy in / out: pred[N, 3]."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv, cols, colp = _host_cols(y, x_cols)
+    p, G, N = len(cols), len(off) - 1, len(yv)
+    pred = np.empty((N, 3), dtype=np.float64)
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_rls_fit_predict_window_host(
+        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP), colp,
+        _frame(frame), options, float(confidence_level), pred.ctypes.data_as(_DP), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return pred
+
+
+def rls_fit_predict_frames_host(y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipRlsBatchOptions,
+                                confidence_level: float = 0.95, ctx: Optional[Context] = None):
+    """RLS fit + predict over explicit frames [frame_lo[e], frame_hi[e]), numpy in / out: pred[N, 3]."""
+    lib = _abi.load()
+    yv, cols, colp = _host_cols(y, x_cols)
+    lo = np.ascontiguousarray(frame_lo, dtype=np.int64)
+    hi = np.ascontiguousarray(frame_hi, dtype=np.int64)
+    p, N = len(cols), len(yv)
+    if len(lo) != N or len(hi) != N:
+        raise ValueError("both frame bounds must have y's length")
+    pred = np.empty((N, 3), dtype=np.float64)
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_rls_fit_predict_frames_host(
+        ctx._h if ctx is not None else None, N, p, yv.ctypes.data_as(_DP), colp, lo.ctypes.data_as(C.POINTER(C.c_int64)),
+        hi.ctypes.data_as(C.POINTER(C.c_int64)), options, float(confidence_level), pred.ctypes.data_as(_DP), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return pred

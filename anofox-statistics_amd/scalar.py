@@ -132,6 +132,35 @@ def elasticnet_fit(y, x, options=None) -> dict:
         lib.anofox_free_result_core(C.byref(core))
 
 
+def rls_fit(y, x, options=None) -> dict:
+    """anofox_stats_rls_fit([y...], [[x1...], ...], {...}) through anofox_rls_fit: the core fields only
+    (r_squared, adj_r_squared and residual_std_error are NaN, as the reference's)."""
+    from .options import parse_rls_options
+    lib = _abi.load()
+    o = parse_rls_options(options)
+    ya, k0 = _data_array(y)
+    xs = (_abi.AnofoxDataArray * max(len(x), 1))()
+    keep = [k0]
+    for j, col in enumerate(x):
+        a, k = _data_array(col)
+        xs[j] = a
+        keep.append(k)
+    core = _abi.AnofoxFitResultCore()
+    err = _abi.AnofoxError()
+    if not lib.anofox_rls_fit(ya, xs, len(x), o.ffi_options(), C.byref(core), C.byref(err)):
+        e = InvalidInputException(f"RLS fit failed: {err.text()}")
+        e.code = err.code
+        raise e
+    try:
+        p = core.coefficients_len
+        return {"coefficients": [core.coefficients[i] for i in range(p)], "intercept": core.intercept,
+                "r_squared": core.r_squared, "adj_r_squared": core.adj_r_squared,
+                "residual_std_error": core.residual_std_error, "n_observations": core.n_observations,
+                "n_features": core.n_features}
+    finally:
+        lib.anofox_free_result_core(C.byref(core))
+
+
 def aic(rss: float, n: int, k: int) -> Optional[float]:
     """aic(rss, n, k) scalar function (src/scalar_functions/aic_bic.cpp:12-60): NULL (None) on error."""
     lib = _abi.load()

@@ -247,6 +247,20 @@ typedef struct {
 ANOFOX_HIP_API bool anofox_elasticnet_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxElasticNetOptions options,
                            AnofoxFitResultCore *out_core, AnofoxError *out_error);
 
+/* replaces AnofoxRlsOptions, anofox_stats_ffi.h:593-600 — 24 bytes: forgetting_factor @0, fit_intercept @8,
+ * initial_p_diagonal @16 */
+typedef struct {
+	double forgetting_factor;  /* lambda in (0, 1]; 1 = no forgetting */
+	bool fit_intercept;
+	double initial_p_diagonal; /* P = initial_p_diagonal I before the first row, > 0 */
+} AnofoxRlsOptions;
+
+/* replaces anofox_rls_fit, anofox_stats_ffi.h:611-612 (over crates/anofox-stats-core/src/models/rls.rs): one group through
+ * anofox_hip_rls_fit_batch_host, with anofox_elasticnet_fit's conventions.  The filter and the statuses: DESIGN.md §1
+ * "Recursive least squares".  r_squared, adj_r_squared and residual_std_error are NaN, as the reference's. */
+ANOFOX_HIP_API bool anofox_rls_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxRlsOptions options,
+                    AnofoxFitResultCore *out_core, AnofoxError *out_error);
+
 #endif /* ANOFOX_STATS_FFI_H */
 
 /* ------------------------------------------------------------------------ */
@@ -510,6 +524,67 @@ ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_predict_frames_host(AnofoxHipConte
                                                    const double *const *x_cols, const int64_t *frame_lo, const int64_t *frame_hi,
                                                    AnofoxHipElasticNetBatchOptions options, double confidence_level, double *pred,
                                                    AnofoxError *out_error);
+
+/*
+ * Grouped recursive least squares (anofox_stats_rls_fit_agg): per group, the reference's sequential filter over the rows
+ * with finite y and x, in row order and in its exact operation order (DESIGN.md §1 "Recursive least squares"), so the
+ * coefficients are bit-identical to fit_rls.  Records: core[g] as above (length p + 6) with r_squared, adj_r_squared and
+ * residual_std_error NaN; statuses 1 (forgetting_factor outside (0, 1] or initial_p_diagonal <= 0, checked only when some
+ * column is not constant), 6, 10, ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS.
+ */
+typedef struct {
+	bool fit_intercept;
+	double forgetting_factor;
+	double initial_p_diagonal;
+} AnofoxHipRlsBatchOptions;
+
+ANOFOX_HIP_API bool anofox_hip_rls_fit_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                     const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                     AnofoxHipRlsBatchOptions options, double *d_core, AnofoxError *out_error);
+/* host pointers, synchronous; ctx may be NULL (per-thread default context) */
+ANOFOX_HIP_API bool anofox_hip_rls_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                   const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                   AnofoxHipRlsBatchOptions options, double *core, AnofoxError *out_error);
+
+/*
+ * RLS fit + predict (anofox_stats_rls_fit_predict_agg, src/aggregate_functions/rls_predict_aggregate.cpp): the fit of
+ * anofox_hip_rls_fit_batch_* on each group, then every row gets {yhat, yhat, yhat} (pred, [n_rows x 3], NaN = SQL NULL):
+ * anofox_predict_with_interval with sigma = NaN, so the interval is the point and confidence_level has no effect.
+ * train_counts (optional) is what the "fewer than 2 training rows -> NULL" rule looks at.  A group whose status is not 0
+ * predicts NaN everywhere.
+ */
+ANOFOX_HIP_API bool anofox_hip_rls_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                             const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                             const int64_t *d_train_counts, AnofoxHipRlsBatchOptions options,
+                                             double confidence_level, double *d_core, double *d_pred, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_rls_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                           const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                           const int64_t *train_counts, AnofoxHipRlsBatchOptions options,
+                                           double confidence_level, double *core, double *pred, AnofoxError *out_error);
+
+/*
+ * The RLS window function anofox_stats_rls_fit_predict(y, x [, options]) OVER (... ROWS ...) (src/window_functions/
+ * rls_fit_predict.cpp): per output row, the RLS fit of the frame's rows, NULL unless MORE than p + [intercept] rows with
+ * non-NULL y exist (:228), predicting the x of the frame's LAST row; frames as anofox_hip_fit_predict_window_*.  Every frame
+ * runs the batch filter over its own rows (one lane per frame for p <= 8, one wavefront above).
+ */
+ANOFOX_HIP_API bool anofox_hip_rls_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                              const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                              AnofoxHipWindowFrame frame, AnofoxHipRlsBatchOptions options,
+                                              double confidence_level, double *d_pred, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_rls_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                            const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                            AnofoxHipWindowFrame frame, AnofoxHipRlsBatchOptions options,
+                                            double confidence_level, double *pred, AnofoxError *out_error);
+/* the same over explicit frames [frame_lo[e], frame_hi[e]) (as anofox_hip_fit_predict_frames_*) */
+ANOFOX_HIP_API bool anofox_hip_rls_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *d_y,
+                                              const double *const *x_cols, const int64_t *d_frame_lo, const int64_t *d_frame_hi,
+                                              AnofoxHipRlsBatchOptions options, double confidence_level, double *d_pred,
+                                              AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_rls_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y,
+                                            const double *const *x_cols, const int64_t *frame_lo, const int64_t *frame_hi,
+                                            AnofoxHipRlsBatchOptions options, double confidence_level, double *pred,
+                                            AnofoxError *out_error);
 
 /*
  * Grouped variance inflation factors: the Finalize loop of vif_agg (src/aggregate_functions/vif_aggregate.cpp:
