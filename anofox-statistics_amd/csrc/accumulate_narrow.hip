@@ -30,16 +30,14 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "solve_narrow_impl.h"
 #include "wave_reduce.h"
 
 namespace anofox {
 
 typedef double dbl2u __attribute__((ext_vector_type(2), aligned(8)));
 
-#ifndef ANOFOX_NARROW_NT
-#define ANOFOX_NARROW_NT false
-#endif
-// 16-byte streaming load; NT = non-temporal (measured: no gain over the default policy, kept for experiments)
+// 16-byte streaming load; NT = non-temporal (ANOFOX_NARROW_NT=1, fused kernel only: an A/B switch for measurements)
 template <bool NT>
 __device__ __forceinline__ dbl2u load2(const double *p) {
 	if (NT) return __builtin_nontemporal_load(reinterpret_cast<const dbl2u *>(p));
@@ -52,7 +50,7 @@ struct NarrowTile {
 	double n0[Z], n1[Z], nw0, nw1;
 };
 
-template <int P, bool WEIGHTED>
+template <int P, bool WEIGHTED, bool NT>
 __device__ __forceinline__ void narrow_load_tile(const BatchArgs &args, int64_t base, int64_t hi, int lane, NarrowTile<P + 1> &t) {
 	const int64_t r0 = base + 2 * lane;
 	// (measured in round 3 and taken back: loading a group's partial last tile like a full one wherever the arrays reach that
@@ -60,17 +58,17 @@ __device__ __forceinline__ void narrow_load_tile(const BatchArgs &args, int64_t 
 	if (base + 128 <= hi) { // full tile: one 16-byte load per column
 #pragma unroll
 		for (int j = 0; j < P; ++j) {
-			const dbl2u v = load2<ANOFOX_NARROW_NT>(args.x[j] + r0);
+			const dbl2u v = load2<NT>(args.x[j] + r0);
 			t.n0[j] = v.x;
 			t.n1[j] = v.y;
 		}
 		{
-			const dbl2u v = load2<ANOFOX_NARROW_NT>(args.y + r0);
+			const dbl2u v = load2<NT>(args.y + r0);
 			t.n0[P] = v.x;
 			t.n1[P] = v.y;
 		}
 		if (WEIGHTED) {
-			const dbl2u v = load2<ANOFOX_NARROW_NT>(args.w + r0);
+			const dbl2u v = load2<NT>(args.w + r0);
 			t.nw0 = v.x;
 			t.nw1 = v.y;
 		}
@@ -227,7 +225,7 @@ __device__ __forceinline__ void narrow_acc_finish(NarrowAcc<P> &c, double *rec, 
 }
 
 // The rows [lo, hi) of one group (or of one segment of a very large group) -> one moment record at `rec`.
-template <int P, bool WEIGHTED, bool CENTER, bool PREFETCH>
+template <int P, bool WEIGHTED, bool CENTER, bool PREFETCH, bool NT = false>
 __device__ __forceinline__ void accumulate_rows(const BatchArgs &args, int64_t lo, int64_t hi, double *rec, int lane) {
 	constexpr int Z = P + 1;
 	NarrowAcc<P> c;
@@ -235,9 +233,9 @@ __device__ __forceinline__ void accumulate_rows(const BatchArgs &args, int64_t l
 	NarrowTile<Z> t;
 	// the loads of tile t + 1 are issued before the arithmetic of tile t (PREFETCH), so that a wave always has
 	// one tile of loads in flight; all loads of a tile sit in one arm of the (wave-uniform) full / ragged branch
-	if (PREFETCH && lo < hi) narrow_load_tile<P, WEIGHTED>(args, lo, hi, lane, t);
+	if (PREFETCH && lo < hi) narrow_load_tile<P, WEIGHTED, NT>(args, lo, hi, lane, t);
 	for (int64_t base = lo; base < hi; base += 128) {
-		if (!PREFETCH) narrow_load_tile<P, WEIGHTED>(args, base, hi, lane, t);
+		if (!PREFETCH) narrow_load_tile<P, WEIGHTED, NT>(args, base, hi, lane, t);
 		double z0[Z], z1[Z];
 		double w0 = 1.0, w1 = 1.0;
 #pragma unroll
@@ -249,7 +247,7 @@ __device__ __forceinline__ void accumulate_rows(const BatchArgs &args, int64_t l
 			w0 = t.nw0;
 			w1 = t.nw1;
 		}
-		if (PREFETCH && base + 128 < hi) narrow_load_tile<P, WEIGHTED>(args, base + 128, hi, lane, t);
+		if (PREFETCH && base + 128 < hi) narrow_load_tile<P, WEIGHTED, NT>(args, base + 128, hi, lane, t);
 		narrow_tile_compute<P, WEIGHTED, CENTER>(c, z0, z1, w0, w1, base + 2 * lane, hi);
 	}
 	narrow_acc_finish<P, CENTER>(c, rec, lane);
@@ -305,10 +303,64 @@ __device__ __forceinline__ void accumulate_group(const BatchArgs &args, int64_t 
 	accumulate_rows<P, WEIGHTED, CENTER, PF>(args, lo, hi, args.moments + g * (int64_t)L::REC, lane);
 }
 
-template <int P, bool WEIGHTED, bool CENTER, bool PF>
-__global__ __launch_bounds__(256) void accumulate_narrow_kernel(BatchArgs args) {
+// Fused variant (regression solve stages without inference records, host_api.hip decides): each wavefront takes kFusedGroups consecutive groups,
+// keeps their moment records in its own LDS slice instead of writing them to HBM, then solves them one lane per group
+// (solve_one, solve_narrow_impl.h) and writes their core records as one contiguous block.  Only a group the solve queues
+// for refinement has its moment record written to args.moments (the refinement and refit passes read it there); a group
+// registered for accumulate_segments_kernel is left out and solved by solve_big_narrow_kernel after the merge.
+#ifndef ANOFOX_NARROW_FUSED_K
+#define ANOFOX_NARROW_FUSED_K 16
+#endif
+constexpr int kFusedGroups = ANOFOX_NARROW_FUSED_K;
+static_assert(kFusedGroups >= 1 && kFusedGroups <= 32, "groups per wavefront: one lane each, a 32-bit skip mask");
+
+template <int P, bool WEIGHTED, bool CENTER, bool PF, bool NT>
+__device__ __forceinline__ void accumulate_solve_groups(const BatchArgs &args, int64_t g0, int lane, double *lrec, double *lcore) {
+	using L = MomentLayout<P>;
+	constexpr int CL = P + 6; // core record
+	const int n = (int)(args.n_groups - g0 < kFusedGroups ? args.n_groups - g0 : kFusedGroups); // wave-uniform
+	unsigned skip = 0;
+	for (int i = 0; i < n; ++i) {
+		const int64_t g = g0 + i;
+		const int64_t lo = args.row_offsets[g];
+		const int64_t hi = group_row_end(args, g);
+		if (args.seg_table && hi - lo > args.seg_rows && narrow_register_big_group(args, g, lo, hi, lane)) {
+			skip |= 1u << i;
+			continue;
+		}
+		accumulate_rows<P, WEIGHTED, CENTER, PF, NT>(args, lo, hi, lrec + i * L::REC, lane);
+	}
+	// the slice is this wavefront's alone: a fence orders its LDS stores before the loads of other lanes, no barrier
+	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+	bool queued = false;
+	if (lane < n && !((skip >> lane) & 1u)) queued = solve_one<P, MODE_PRIMARY, false>(args, g0 + lane, lrec + lane * L::REC, lcore + lane * CL);
+	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+	double *core = args.core + g0 * CL;
+	for (int k = lane; k < n * CL; k += 64)
+		if (!((skip >> (k / CL)) & 1u)) core[k] = lcore[k];
+	// queued groups: the refinement passes read the moment record from HBM
+	for (unsigned long long q = __ballot(queued); q != 0ull; q &= q - 1ull) {
+		const int i = __ffsll((long long)q) - 1;
+		for (int k = lane; k < L::REC; k += 64) args.moments[(g0 + i) * L::REC + k] = lrec[i * L::REC + k];
+	}
+}
+
+// (FUSED: at most 256 registers, VGPRs and AGPRs together, so that two waves stay resident per SIMD; the inlined solve is
+// the one without inference statistics)
+template <int P, bool WEIGHTED, bool CENTER, bool PF, bool FUSED = false, bool NT = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FUSED ? 2 : 1))) void accumulate_narrow_kernel(BatchArgs args) {
 	const int lane = threadIdx.x & 63;
-	const int64_t g = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) + (int64_t)blockIdx.x * 4;
+	const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+	if (FUSED) {
+		using L = MomentLayout<P>;
+		__shared__ double lrec[4][kFusedGroups * L::REC];
+		__shared__ double lcore[4][kFusedGroups * (P + 6)];
+		const int64_t g0 = ((int64_t)blockIdx.x * 4 + wave) * kFusedGroups;
+		if (g0 >= args.n_groups) return;
+		accumulate_solve_groups<P, WEIGHTED, CENTER, PF, NT>(args, g0, lane, lrec[wave], lcore[wave]);
+		return;
+	}
+	const int64_t g = wave + (int64_t)blockIdx.x * 4;
 	if (g >= args.n_groups) return;
 	accumulate_group<P, WEIGHTED, CENTER, PF>(args, g, lane);
 }
@@ -400,16 +452,30 @@ __global__ __launch_bounds__(256) void accumulate_segments_kernel(BatchArgs args
 	merge_segments<P, CENTER>(recs + (int64_t)b->base * L::REC, b->nseg, args.moments + b->g * (int64_t)L::REC, lane);
 }
 
-template <int P, bool PF>
+// The fused variant's groups that went to accumulate_segments_kernel: one lane each, from the merged record in HBM — the
+// same solve the separate solve kernel runs on it.
+template <int P>
+__global__ __launch_bounds__(64) void solve_big_narrow_kernel(BatchArgs args) {
+	const int slot = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+	const int total = seg_header(args.seg_table)->big_total; // reservations never exceed the capacity
+	if (slot >= total) return;
+	const int64_t g = seg_big(args.seg_table)[slot].g;
+	solve_one<P, MODE_PRIMARY>(args, g, args.moments + g * (int64_t)MomentLayout<P>::REC, args.core + g * (int64_t)(P + 6));
+}
+
+template <int P, bool PF, bool FUSED, bool NT>
 static hipError_t launch_pn(const BatchArgs &a, hipStream_t stream) {
 	const dim3 block(256);
-	const dim3 grid((unsigned)((a.n_groups + 3) / 4));
+	const int64_t per_block = FUSED ? 4 * kFusedGroups : 4;
+	const dim3 grid((unsigned)((a.n_groups + per_block - 1) / per_block));
 	const dim3 seg_grid((unsigned)((kSegMaxSegments + 3) / 4)); // idle unless some group exceeded seg_rows
 	const bool weighted = a.model == ANOFOX_HIP_MODEL_WLS;
 	const bool center = a.fit_intercept != 0;
 #define ANOFOX_ACC_LAUNCH(W, C)                                                                               \
 	do {                                                                                                      \
-		hipLaunchKernelGGL((accumulate_narrow_kernel<P, W, C, PF>), grid, block, 0, stream, a);               \
+		constexpr bool F = FUSED && narrow_fused_fits(P, W, C);                                                      \
+		if (FUSED && !F) return hipErrorNotSupported;                                                         \
+		hipLaunchKernelGGL((accumulate_narrow_kernel<P, W, C, PF, F, F && NT>), grid, block, 0, stream, a);   \
 		if (a.seg_table) hipLaunchKernelGGL((accumulate_segments_kernel<P, W, C, PF>), seg_grid, block, 0, stream, a); \
 	} while (0)
 	if (weighted) {
@@ -420,6 +486,8 @@ static hipError_t launch_pn(const BatchArgs &a, hipStream_t stream) {
 		else ANOFOX_ACC_LAUNCH(false, false);
 	}
 #undef ANOFOX_ACC_LAUNCH
+	if (FUSED && a.seg_table) // idle unless some group exceeded seg_rows
+		hipLaunchKernelGGL((solve_big_narrow_kernel<P>), dim3((unsigned)((kSegMaxBig + 63) / 64)), dim3(64), 0, stream, a);
 	return hipGetLastError();
 }
 
@@ -446,33 +514,41 @@ static hipError_t launch_list_pn(const BatchArgs &a, const int32_t *list, const 
 }
 
 template <int P>
-static hipError_t launch_p(const BatchArgs &a, const int32_t *list, const int32_t *count, hipStream_t stream) {
+static hipError_t launch_p(const BatchArgs &a, const int32_t *list, const int32_t *count, bool fused, hipStream_t stream) {
 	// ANOFOX_ACC_PF=0 issues a tile's loads at the top of its own iteration instead of one tile ahead (A/B measurements)
 	static const int pf = [] { const char *e = getenv("ANOFOX_ACC_PF"); return e ? atoi(e) : 1; }();
+	// ANOFOX_NARROW_NT=1: non-temporal loads in the fused kernel (with the prefetch on; A/B measurements)
+	static const int nt = [] { const char *e = getenv("ANOFOX_NARROW_NT"); return e ? atoi(e) : 0; }();
 	if (list) return pf ? launch_list_pn<P, true>(a, list, count, stream) : launch_list_pn<P, false>(a, list, count, stream);
-	return pf ? launch_pn<P, true>(a, stream) : launch_pn<P, false>(a, stream);
+	if (fused) {
+		if (!pf) return launch_pn<P, false, true, false>(a, stream);
+		return nt ? launch_pn<P, true, true, true>(a, stream) : launch_pn<P, true, true, false>(a, stream);
+	}
+	return pf ? launch_pn<P, true, false, false>(a, stream) : launch_pn<P, false, false, false>(a, stream);
 }
 
-static hipError_t launch_any(const BatchArgs &a, const int32_t *list, const int32_t *count, hipStream_t stream) {
+static hipError_t launch_any(const BatchArgs &a, const int32_t *list, const int32_t *count, bool fused, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
 	switch (a.p) {
-	case 1: return launch_p<1>(a, list, count, stream);
-	case 2: return launch_p<2>(a, list, count, stream);
-	case 3: return launch_p<3>(a, list, count, stream);
-	case 4: return launch_p<4>(a, list, count, stream);
-	case 5: return launch_p<5>(a, list, count, stream);
-	case 6: return launch_p<6>(a, list, count, stream);
-	case 7: return launch_p<7>(a, list, count, stream);
-	case 8: return launch_p<8>(a, list, count, stream);
+	case 1: return launch_p<1>(a, list, count, fused, stream);
+	case 2: return launch_p<2>(a, list, count, fused, stream);
+	case 3: return launch_p<3>(a, list, count, fused, stream);
+	case 4: return launch_p<4>(a, list, count, fused, stream);
+	case 5: return launch_p<5>(a, list, count, fused, stream);
+	case 6: return launch_p<6>(a, list, count, fused, stream);
+	case 7: return launch_p<7>(a, list, count, fused, stream);
+	case 8: return launch_p<8>(a, list, count, fused, stream);
 	default: return hipErrorInvalidValue;
 	}
 }
 
-hipError_t launch_accumulate_narrow(const BatchArgs &a, hipStream_t stream) { return launch_any(a, nullptr, nullptr, stream); }
+// a.primary_solved: accumulate and primary solve in one kernel — core records and the refinement queue as the solve kernel
+// leaves them, moment records only for the queued groups (the caller skips launch_solve_narrow)
+hipError_t launch_accumulate_narrow(const BatchArgs &a, hipStream_t stream) { return launch_any(a, nullptr, nullptr, a.primary_solved != 0, stream); }
 
 // only the groups in list[0 .. *count) (device memory), e.g. the ones accumulate_small.hip left out
 hipError_t launch_accumulate_narrow_list(const BatchArgs &a, const int32_t *list, const int32_t *count, hipStream_t stream) {
-	return launch_any(a, list, count, stream);
+	return launch_any(a, list, count, false, stream);
 }
 
 } // namespace anofox

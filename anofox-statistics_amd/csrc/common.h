@@ -99,7 +99,15 @@ struct BatchArgs {
 	// optional [G]: group g owns rows [row_offsets[g], row_ends[g]) instead of [row_offsets[g], row_offsets[g+1]) —
 	// row ranges may then overlap (window frames fitted as a batch of "virtual groups", frames.hip)
 	const int64_t *row_ends;
+	// set by the host: launch_accumulate_narrow runs the primary solve inside the accumulate kernel (the fused variant) —
+	// the solve stage skips launch_solve_narrow, and only the groups it queued have a moment record
+	int primary_solved;
 };
+// Every fused instantiation keeps two waves per SIMD without spilling but the weighted fit with an intercept at p = 8
+// (256 VGPRs and 9 spilled): that one keeps the separate solve kernel.
+inline constexpr __host__ __device__ bool narrow_fused_fits(int p, bool weighted, bool center) {
+	return p >= 1 && p <= kNarrowMaxP && !(p == 8 && weighted && center);
+}
 inline __host__ __device__ int64_t group_row_end(const BatchArgs &a, int64_t g) { return a.row_ends ? a.row_ends[g] : a.row_offsets[g + 1]; }
 
 // Segment bookkeeping of the narrow accumulate kernel.  seg_rows >= ceil(n_rows / kSegTargetWaves), so fewer than

@@ -98,7 +98,7 @@ bool regression_wide_stage(AnofoxHipContext *ctx, WideArgs &a, hipStream_t ss, i
 
 // The same stage on the narrow records (p <= 8).
 bool regression_narrow_stage(AnofoxHipContext *ctx, BatchArgs &a, hipStream_t st, void *, AnofoxError *e) {
-	if (hip_fail(launch_solve_narrow(a, st), "solve kernel launch", e)) return false;
+	if (!a.primary_solved && hip_fail(launch_solve_narrow(a, st), "solve kernel launch", e)) return false;
 	// queued groups only: kRefineSteps x (b += (X'WX)^-1 X'Wr), then the statistics from the directly summed RSS
 	if (hip_fail(launch_refine_fused_narrow(a, kRefineSteps, st), "refine kernel launch", e)) return false;
 	// ols.rs:209-231, wls.rs:230-252: HC errors replace the classical ones; ridge has no such branch
@@ -356,6 +356,14 @@ bool run_device_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows
 	static const bool small_on = !(getenv("ANOFOX_ACC_SMALL") && atoi(getenv("ANOFOX_ACC_SMALL")) == 0); // A/B switch
 	// (window frames: overlapping row ranges given by row_ends — the packed kernel reads row_offsets[g + 1])
 	const int segw = (small_on && !a.row_ends && n_rows > 0 && G < (int64_t)0x7fffffff) ? accumulate_small_segment_width((double)n_rows / (double)G) : 0;
+	// The regression models' primary solve inside the accumulate kernel (accumulate_narrow.hip): the moment records stay in
+	// LDS, only the groups queued for refinement get theirs in HBM.  Not where a later stage reads every group's record —
+	// other models' stages, HC errors (hc_narrow) — nor for window frames or the packed small-group kernel, and not with
+	// inference records: their special functions need more registers than the fused kernel has.
+	// ANOFOX_NARROW_FUSED=0: the separate solve kernel (A/B measurements, parity tests).
+	static const bool fused_on = !(getenv("ANOFOX_NARROW_FUSED") && atoi(getenv("ANOFOX_NARROW_FUSED")) == 0);
+	a.primary_solved = (fused_on && stages.narrow == regression_narrow_stage && !a.row_ends && !segw && !a.inference &&
+	                    narrow_fused_fits(a.p, a.model == ANOFOX_HIP_MODEL_WLS, a.fit_intercept != 0)) ? 1 : 0;
 	if (segw) {
 		int32_t *big_count = ws.refine_count + 4; // zeroed with the other counters; the list borrows the (still unused) refine queue
 		if (hip_fail(launch_accumulate_small(a, segw, ws.refine_list, big_count, st), "accumulate kernel launch", e)) return false;
