@@ -18,11 +18,12 @@ from .aggregate import (StreamingStates, FitAggResult, FitPredictAggResult, OlsF
                         result_from_records, ols_fit_predict, ridge_fit_predict, wls_fit_predict, vif_agg,
                         residuals_diagnostics_agg, ElasticNetFitPredictAgg, elasticnet_fit_predict_agg,
                         elasticnet_fit_predict, RlsFitAgg, rls_fit_agg, RlsFitPredictAgg, rls_fit_predict_agg,
-                        rls_fit_predict)
+                        rls_fit_predict, BlsFitAggResult, BlsFitAgg, NnlsFitAgg, BlsFitPredictAgg, bls_fit_agg, nnls_fit_agg,
+                        bls_fit_predict_agg, bls_result_from_records)
 from .options import (ElasticNetOptions, ElasticNetPredictOptions, InvalidInputException, RegressionOptions,  # noqa: E402
                       parse_elasticnet_options, parse_elasticnet_predict_options, parse_options, RlsOptions,
-                      parse_rls_options)
-from .runtime import AggState, Context, rls_fit_batch_host, rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
+                      parse_rls_options, BlsOptions, parse_bls_options, parse_nnls_options, parse_bls_predict_options)
+from .runtime import AggState, Context, bls_fit_batch_host, bls_fit_predict_batch_host, rls_fit_batch_host, rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
 from .scalar import aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
@@ -55,6 +56,9 @@ __all__ = [
     "RlsOptions", "parse_rls_options", "rls_fit", "RlsFitAgg", "rls_fit_agg", "RlsFitPredictAgg", "rls_fit_predict_agg",
     "rls_fit_predict", "rls_fit_batch_host", "rls_fit_predict_batch_host", "rls_fit_predict_window_host",
     "rls_fit_predict_frames_host",
+    "BlsOptions", "parse_bls_options", "parse_nnls_options", "parse_bls_predict_options", "BlsFitAggResult", "BlsFitAgg",
+    "NnlsFitAgg", "BlsFitPredictAgg", "bls_fit_agg", "nnls_fit_agg", "bls_fit_predict_agg", "bls_result_from_records",
+    "bls_fit_batch_host", "bls_fit_predict_batch_host",
 ]
 
 

@@ -120,6 +120,23 @@ class AnofoxHipRlsBatchOptions(C.Structure):
     _fields_ = [("fit_intercept", C.c_bool), ("forgetting_factor", C.c_double), ("initial_p_diagonal", C.c_double)]
 
 
+class AnofoxBlsOptions(C.Structure):  # anofox_stats_ffi.h:1186-1201, 56 bytes
+    _fields_ = [("fit_intercept", C.c_bool), ("lower_bounds", _DP), ("lower_bounds_len", C.c_size_t),
+                ("upper_bounds", _DP), ("upper_bounds_len", C.c_size_t), ("max_iterations", C.c_uint32),
+                ("tolerance", C.c_double)]
+
+
+class AnofoxBlsFitResultCore(C.Structure):  # anofox_stats_ffi.h:1206-1227, 80 bytes
+    _fields_ = [("coefficients", _DP), ("coefficients_len", C.c_size_t), ("intercept", C.c_double), ("ssr", C.c_double),
+                ("r_squared", C.c_double), ("n_observations", C.c_size_t), ("n_features", C.c_size_t),
+                ("n_active_constraints", C.c_size_t), ("at_lower_bound", C.POINTER(C.c_bool)),
+                ("at_upper_bound", C.POINTER(C.c_bool))]
+
+
+class AnofoxHipBlsBatchOptions(C.Structure):
+    _fields_ = AnofoxBlsOptions._fields_
+
+
 # every symbol include/anofox_stats_hip.h declares: name -> (restype, argtypes)
 _ERRP = C.POINTER(AnofoxError)
 _CTX = C.c_void_p
@@ -285,6 +302,22 @@ SYMBOLS = {
     "anofox_hip_rls_fit_predict_frames_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, _DP, C.POINTER(_DP), C.POINTER(C.c_int64),
                                                           C.POINTER(C.c_int64), AnofoxHipRlsBatchOptions, C.c_double,
                                                           _DP, _ERRP]),
+    "anofox_bls_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxBlsOptions,
+                                  C.POINTER(AnofoxBlsFitResultCore), _ERRP]),
+    "anofox_nnls_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t,
+                                   C.POINTER(AnofoxBlsFitResultCore), _ERRP]),
+    "anofox_free_bls_result": (None, [C.POINTER(AnofoxBlsFitResultCore)]),
+    "anofox_hip_bls_record_len": (C.c_size_t, [C.c_size_t]),
+    "anofox_hip_bls_fit_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_void_p), AnofoxHipBlsBatchOptions, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_bls_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                 C.POINTER(_DP), AnofoxHipBlsBatchOptions, _DP, C.POINTER(C.c_int32), _ERRP]),
+    "anofox_hip_bls_fit_predict_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                           C.POINTER(C.c_void_p), C.c_void_p, AnofoxHipBlsBatchOptions,
+                                                           C.c_double, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_bls_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                         C.POINTER(_DP), C.POINTER(C.c_int64), AnofoxHipBlsBatchOptions,
+                                                         C.c_double, _DP, _DP, _ERRP]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "anofox_hip_host_free": (None, [C.c_void_p]),
 }

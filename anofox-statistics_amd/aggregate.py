@@ -22,7 +22,8 @@ from typing import Any, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .options import InvalidInputException, RegressionOptions, parse_elasticnet_predict_options, parse_options, parse_rls_options
+from .options import (InvalidInputException, RegressionOptions, parse_bls_options, parse_bls_predict_options, parse_elasticnet_predict_options,
+                      parse_nnls_options, parse_options, parse_rls_options)
 from .runtime import AggState, Context, fit_batch_host
 
 
@@ -873,4 +874,117 @@ SQL_FUNCTIONS.update({
     "anofox_stats_rls_fit_predict_agg": rls_fit_predict_agg, "rls_fit_predict_agg": rls_fit_predict_agg,
     "rls_predict_agg": rls_fit_predict_agg, "anofox_stats_rls_predict_agg": rls_fit_predict_agg,
     "anofox_stats_rls_fit_predict": rls_fit_predict, "rls_fit_predict": rls_fit_predict,
+})
+
+
+# ------------------------------------------------------------------------------------------------------
+# bounded least squares: anofox_stats_bls_fit_agg / anofox_stats_nnls_fit_agg (src/aggregate_functions/bls_aggregate.cpp)
+# and anofox_stats_bls_fit_predict_agg (bls_fit_predict_aggregate.cpp).  The reference has no window function for it.
+# ------------------------------------------------------------------------------------------------------
+@dataclass
+class BlsFitAggResult:
+    """Per group the 9-field STRUCT of bls_aggregate.cpp:83-96; NULL groups have status != 0 and NaN fields."""
+    keys: np.ndarray
+    coefficients: np.ndarray          # [G, p]
+    intercept: np.ndarray             # NaN = NULL (no intercept)
+    ssr: np.ndarray
+    r_squared: np.ndarray
+    n_observations: np.ndarray
+    n_features: int
+    n_active_constraints: np.ndarray
+    at_lower_bound: np.ndarray        # [G, p] bool
+    at_upper_bound: np.ndarray
+    status: np.ndarray
+    iterations: np.ndarray            # outer active-set iterations, negated when max_iterations stopped the group
+
+    def __len__(self):
+        return len(self.keys)
+
+    @property
+    def is_null(self):
+        return self.status != 0
+
+    def row(self, i: int) -> Optional[dict]:
+        if self.status[i] != 0:
+            return None
+        nn = lambda v: None if np.isnan(v) else float(v)  # noqa: E731
+        return {"coefficients": [nn(v) for v in self.coefficients[i]], "intercept": nn(self.intercept[i]),
+                "ssr": nn(self.ssr[i]), "r_squared": nn(self.r_squared[i]), "n_observations": int(self.n_observations[i]),
+                "n_features": self.n_features, "n_active_constraints": int(self.n_active_constraints[i]),
+                "at_lower_bound": [bool(v) for v in self.at_lower_bound[i]],
+                "at_upper_bound": [bool(v) for v in self.at_upper_bound[i]]}
+
+
+def bls_result_from_records(keys, rec: np.ndarray, its: np.ndarray, p: int) -> BlsFitAggResult:
+    return BlsFitAggResult(np.asarray(keys), rec[:, :p], rec[:, p], rec[:, p + 1], rec[:, p + 2], rec[:, p + 3], p, rec[:, p + 4],
+                           rec[:, p + 6:2 * p + 6] != 0, rec[:, 2 * p + 6:3 * p + 6] != 0, rec[:, p + 5].astype(np.int64), its)
+
+
+class BlsFitAgg(_FitAgg):
+    """anofox_stats_bls_fit_agg(y, x [, options]) — alias bls_fit_agg: rows buffered per group, one batched call at Finalize."""
+    model = "bls"
+    sql_name = "anofox_stats_bls_fit_agg"
+
+    def __init__(self, options: Optional[Mapping[str, Any]] = None, context: Optional[Context] = None):
+        super().__init__(None, context)
+        self.options = self._parse(options)
+
+    @staticmethod
+    def _parse(options):
+        return parse_bls_options(options)
+
+    def finalize(self) -> BlsFitAggResult:
+        from .runtime import bls_fit_batch_host
+        ukeys, offsets, y, x_cols, _ = self.grouped_columns()
+        G = len(ukeys)
+        if self.n_features is None:       # no row was ever accumulated: every group is NULL
+            rec = np.full((G, 6), np.nan)
+            rec[:, 5] = _abi.STATUS_NULL_TOO_FEW_ROWS
+            return bls_result_from_records(ukeys, rec, np.zeros(G, dtype=np.int32), 0)
+        rec, its = bls_fit_batch_host(offsets, y, x_cols, self.options.batch_options(), ctx=self._ctx)
+        return bls_result_from_records(ukeys, rec, its, self.n_features)
+
+
+class NnlsFitAgg(BlsFitAgg):
+    """anofox_stats_nnls_fit_agg(y, x [, options]) — alias nnls_fit_agg: lower bound 0, bound keys ignored."""
+    sql_name = "anofox_stats_nnls_fit_agg"
+
+    @staticmethod
+    def _parse(options):
+        return parse_nnls_options(options)
+
+
+def bls_fit_agg(group_keys, y, x, options=None, context=None) -> BlsFitAggResult:
+    return BlsFitAgg(options, context).update(group_keys, y, x).finalize()
+
+
+def nnls_fit_agg(group_keys, y, x, options=None, context=None) -> BlsFitAggResult:
+    return NnlsFitAgg(options, context).update(group_keys, y, x).finalize()
+
+
+class BlsFitPredictAgg(_FitPredictAgg):
+    """anofox_stats_bls_fit_predict_agg: training rows as the other fit-predict aggregates (a NULL feature stays a training
+    row and is dropped by the fit's filter), "fewer than 2 training rows -> NULL", a failed fit -> NULL; the interval uses the
+    reference's sigma = sqrt(ssr / df) with its unsigned df over all columns (bls_fit_predict_aggregate.cpp:391-395)."""
+    model = "bls"
+    sql_name = "anofox_stats_bls_fit_predict_agg"
+
+    @staticmethod
+    def _parse_options(options):
+        return parse_bls_predict_options(options)
+
+    def _fit_predict(self, offsets, y_fit, x_cols, w, train_counts):
+        from .runtime import bls_fit_predict_batch_host
+        return bls_fit_predict_batch_host(offsets, y_fit, x_cols, self.options.batch_options(), self.options.confidence_level,
+                                          train_counts=train_counts, ctx=self._ctx)
+
+
+def bls_fit_predict_agg(group_keys, y, x, options=None, context=None, split=None) -> FitPredictAggResult:
+    return BlsFitPredictAgg(options, context).update(group_keys, y, x, split=split).finalize()
+
+
+SQL_FUNCTIONS.update({
+    "anofox_stats_bls_fit_agg": bls_fit_agg, "bls_fit_agg": bls_fit_agg,
+    "anofox_stats_nnls_fit_agg": nnls_fit_agg, "nnls_fit_agg": nnls_fit_agg,
+    "anofox_stats_bls_fit_predict_agg": bls_fit_predict_agg, "bls_fit_predict_agg": bls_fit_predict_agg,
 })

@@ -392,6 +392,17 @@ struct EnParams {
 // the window kernels with the elastic net solve (window_narrow.hip); flagged frames: cancelled rss or ill-conditioned
 hipError_t launch_window_predict_en(const WindowArgs &a, const EnParams &en, hipStream_t stream);
 
+// Bounded least squares solve parameters (bls.hip, bls_solve.h).  B = number of bound slots carried in the kernel arguments
+// (kNarrowMaxP for the lane kernels, kWideMaxP for the wavefront kernels).
+template <int B>
+struct BlsParamsT {
+	double lo[B], hi[B]; // per ORIGINAL column; -inf / +inf = unbounded
+	double tolerance;
+	int max_iterations;
+	int invalid;         // the call's bounds are unusable: every group gets ANOFOX_ERROR_INVALID_INPUT
+	int predict_layout;  // 0: the 3p + 6 record; 1: the regression layout (p + 6) with sigma, for the predict kernels
+	int32_t *iterations; // [G] or nullptr: outer iterations, negated when the limit stopped the group
+};
 // residual diagnostics (residuals_narrow.hip), p <= kNarrowMaxP
 struct ResidualArgs {
 	const int64_t *row_offsets;

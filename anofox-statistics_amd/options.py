@@ -232,6 +232,108 @@ def parse_elasticnet_predict_options(opts: Optional[Mapping[str, Any]], use_lamb
 
 
 @dataclass
+class BlsOptions:
+    """Resolved options of bounded least squares (defaults = the bind data of bls_aggregate.cpp:49-55 and
+    bls_fit_predict_aggregate.cpp:67-76).  lower_bound / upper_bound: None = that side absent, a number = every column, a
+    sequence = per column (the SQL MAP only carries a number); both absent = NNLS."""
+    fit_intercept: bool = False
+    lower_bound: Any = None
+    upper_bound: Any = None
+    max_iterations: int = 1000
+    tolerance: float = 1e-10
+    confidence_level: float = 0.95
+    null_policy: str = "drop"
+
+    def _bounds(self):
+        import numpy as np
+        out = []
+        for b in (self.lower_bound, self.upper_bound):
+            out.append(None if b is None else np.ascontiguousarray(np.atleast_1d(np.asarray(b, dtype=np.float64))))
+        return out
+
+    def batch_options(self) -> _abi.AnofoxHipBlsBatchOptions:
+        return self._fill(_abi.AnofoxHipBlsBatchOptions())
+
+    def ffi_options(self) -> _abi.AnofoxBlsOptions:
+        return self._fill(_abi.AnofoxBlsOptions())
+
+    def _fill(self, o):
+        import ctypes as C
+        lo, hi = self._bounds()
+        o.fit_intercept = self.fit_intercept
+        o.lower_bounds = None if lo is None else lo.ctypes.data_as(C.POINTER(C.c_double))
+        o.lower_bounds_len = 0 if lo is None else len(lo)
+        o.upper_bounds = None if hi is None else hi.ctypes.data_as(C.POINTER(C.c_double))
+        o.upper_bounds_len = 0 if hi is None else len(hi)
+        o.max_iterations = self.max_iterations
+        o.tolerance = self.tolerance
+        o._keepalive = (lo, hi)          # the struct points into these arrays
+        return o
+
+
+def _parse_bls(opts: Optional[Mapping[str, Any]], bounds: bool, predict: bool) -> BlsOptions:
+    out = BlsOptions()
+    if opts is None:
+        return out
+    if not isinstance(opts, Mapping):
+        raise InvalidInputException("Options parameter must be a constant expression")
+    for raw_key, val in opts.items():
+        key = str(raw_key).lower()
+        if key in ("intercept", "fit_intercept"):
+            v = _extract_bool(val)
+            if v is not None:
+                out.fit_intercept = v
+        elif key in ("max_iterations", "max_iter"):
+            v = _extract_uint32(val)
+            if v is not None:
+                out.max_iterations = v
+        elif key in ("tolerance", "tol"):
+            v = _extract_double(val)
+            if v is not None:
+                out.tolerance = v
+        elif key in ("lower_bound", "lower", "upper_bound", "upper"):
+            if val is None:
+                continue
+            v = [_extract_double(e) for e in val] if isinstance(val, (list, tuple)) or hasattr(val, "__array__") else _extract_double(val)
+            if bounds:                                   # (nnls: parsed by the shared parser, never read)
+                if key.startswith("lower"):
+                    out.lower_bound = v
+                else:
+                    out.upper_bound = v
+        elif key in ("confidence_level", "confidence"):
+            v = _extract_double(val)
+            if v is not None and predict:
+                out.confidence_level = v
+        elif key == "null_policy":
+            if val is not None:
+                v = str(val).lower()
+                if v not in ("drop", "drop_y_zero_x"):
+                    raise InvalidInputException(
+                        f"Invalid null_policy: '{v}'. Valid values are 'drop', 'drop_y_zero_x'")
+                if predict:
+                    out.null_policy = v
+    return out
+
+
+def parse_bls_options(opts: Optional[Mapping[str, Any]]) -> BlsOptions:
+    """anofox_stats_bls_fit_agg's MAP options (bls_aggregate.cpp:340-366): fit_intercept / intercept, lower_bound / lower,
+    upper_bound / upper, max_iterations / max_iter, tolerance / tol.  Keys are case-insensitive; other keys are ignored."""
+    return _parse_bls(opts, bounds=True, predict=False)
+
+
+def parse_nnls_options(opts: Optional[Mapping[str, Any]]) -> BlsOptions:
+    """anofox_stats_nnls_fit_agg's MAP options (bls_aggregate.cpp:370-396): fit_intercept, max_iterations and tolerance
+    only — bound keys are silently ignored, the fit is always the non-negative one."""
+    return _parse_bls(opts, bounds=False, predict=False)
+
+
+def parse_bls_predict_options(opts: Optional[Mapping[str, Any]]) -> BlsOptions:
+    """anofox_stats_bls_fit_predict_agg's MAP options: parse_bls_options plus confidence_level / confidence (default 0.95)
+    and null_policy ('drop', 'drop_y_zero_x')."""
+    return _parse_bls(opts, bounds=True, predict=True)
+
+
+@dataclass
 class RlsOptions:
     """Resolved options of recursive least squares (defaults = the reference's RlsOptions and the bind data of
     rls_aggregate.cpp / rls_predict_aggregate.cpp / rls_fit_predict.cpp)."""

@@ -261,6 +261,45 @@ typedef struct {
 ANOFOX_HIP_API bool anofox_rls_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxRlsOptions options,
                     AnofoxFitResultCore *out_core, AnofoxError *out_error);
 
+/* replaces AnofoxBlsOptions, anofox_stats_ffi.h:1186-1201 — 56 bytes: fit_intercept @0, lower_bounds @8, lower_bounds_len @16,
+ * upper_bounds @24, upper_bounds_len @32, max_iterations @40, tolerance @48 */
+typedef struct {
+	bool fit_intercept;
+	const double *lower_bounds; /* NULL = no lower bounds, one value = every column */
+	size_t lower_bounds_len;    /* 0, 1 or the number of features */
+	const double *upper_bounds;
+	size_t upper_bounds_len;
+	uint32_t max_iterations;    /* outer active-set iterations at most */
+	double tolerance;           /* |b_j - bound_j| < tolerance sets the bound flags */
+} AnofoxBlsOptions;
+
+/* replaces AnofoxBlsFitResultCore, anofox_stats_ffi.h:1206-1227 — 80 bytes: coefficients @0, coefficients_len @8,
+ * intercept @16, ssr @24, r_squared @32, n_observations @40, n_features @48, n_active_constraints @56,
+ * at_lower_bound @64, at_upper_bound @72 */
+typedef struct {
+	double *coefficients;
+	size_t coefficients_len;
+	double intercept; /* NaN without an intercept */
+	double ssr;
+	double r_squared;
+	size_t n_observations;
+	size_t n_features;
+	size_t n_active_constraints;
+	bool *at_lower_bound;
+	bool *at_upper_bound;
+} AnofoxBlsFitResultCore;
+
+/* replace anofox_bls_fit / anofox_nnls_fit / anofox_free_bls_result, anofox_stats_ffi.h:1242-1263 (over
+ * crates/anofox-stats-core/src/models/bls.rs): one group through anofox_hip_bls_fit_batch_host, with anofox_elasticnet_fit's
+ * conventions.  Both bound arrays absent = NNLS; anofox_nnls_fit is that without an intercept, 1000 iterations, tolerance
+ * 1e-10.  The minimiser, the flags and the statuses: DESIGN.md §1 "Bounded least squares".  The three arrays are malloc'ed;
+ * anofox_free_bls_result frees and nulls them (NULL-safe). */
+ANOFOX_HIP_API bool anofox_bls_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxBlsOptions options,
+                    AnofoxBlsFitResultCore *out_core, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_nnls_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxBlsFitResultCore *out_core,
+                     AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_bls_result(AnofoxBlsFitResultCore *result);
+
 #endif /* ANOFOX_STATS_FFI_H */
 
 /* ------------------------------------------------------------------------ */
@@ -399,6 +438,57 @@ ANOFOX_HIP_API bool anofox_hip_elasticnet_fit_predict_batch_host(AnofoxHipContex
                                                   const int64_t *row_offsets, const double *y, const double *const *x_cols,
                                                   const int64_t *train_counts, AnofoxHipElasticNetBatchOptions options,
                                                   double confidence_level, double *core, double *pred, AnofoxError *out_error);
+
+/*
+ * Grouped bounded least squares (anofox_stats_bls_fit_agg, anofox_stats_nnls_fit_agg): per group, over the rows with finite
+ * y and x, the minimiser of 1/2 sum_i (y_i - b0 - x_i'b)^2 subject to lower_j <= b_j <= upper_j over the non-constant
+ * columns, b0 free (absent without an intercept), by an active-set method with a Cholesky solve on the free set, on the
+ * moments of the accumulate kernels (DESIGN.md §1 "Bounded least squares").  The bounds are HOST arrays shared by all groups
+ * of the call (also in the device form; they travel in the kernel arguments): length 0 = that side unbounded, 1 = every
+ * column, n_features = per column; both absent = NNLS (lower 0).  Any other length, a NaN bound or lower_j > upper_j gives
+ * every group status 1.  Records (anofox_hip_bls_record_len(p) = 3p + 6 doubles):
+ *   bls[g] = { coefficients[0..p), intercept, ssr, r_squared, n_observations, n_active_constraints, status,
+ *              at_lower_bound[p], at_upper_bound[p] (0.0 / 1.0) }
+ * status != 0 => every other field is NaN; statuses 1, 6, 10, ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS.  A coefficient the solve
+ * holds on a bound is stored as exactly that bound.  iterations (may be NULL): iterations[g] = outer iterations run, negated
+ * when max_iterations stopped the group (its last feasible iterate is returned, status 0).
+ */
+typedef struct {
+	bool fit_intercept;
+	const double *lower_bounds;
+	size_t lower_bounds_len;
+	const double *upper_bounds;
+	size_t upper_bounds_len;
+	uint32_t max_iterations;
+	double tolerance;
+} AnofoxHipBlsBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_bls_record_len(size_t n_features);
+ANOFOX_HIP_API bool anofox_hip_bls_fit_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                     const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                     AnofoxHipBlsBatchOptions options, double *d_bls, int32_t *d_iterations,
+                                     AnofoxError *out_error);
+/* host pointers, synchronous; ctx may be NULL (per-thread default context) */
+ANOFOX_HIP_API bool anofox_hip_bls_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                   const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                   AnofoxHipBlsBatchOptions options, double *bls, int32_t *iterations, AnofoxError *out_error);
+
+/*
+ * Bounded least squares fit + predict (anofox_stats_bls_fit_predict_agg, src/aggregate_functions/
+ * bls_fit_predict_aggregate.cpp:330-452): the fit above on each group's training rows, then every row gets {yhat, yhat_lower,
+ * yhat_upper} as anofox_hip_elasticnet_fit_predict_batch_*.  core receives records in the REGRESSION layout (p + 6), which
+ * the predict kernels read: { coefficients[p], intercept, r_squared, ssr, sigma, n_observations, status } with the
+ * reference's sigma = sqrt(ssr / df), df = n_observations - n_features - [intercept] over ALL columns in unsigned 64-bit
+ * arithmetic (it wraps when constant columns make it negative: sigma ~ 0), NaN when df = 0 or ssr is NaN.
+ */
+ANOFOX_HIP_API bool anofox_hip_bls_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                             const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                             const int64_t *d_train_counts, AnofoxHipBlsBatchOptions options,
+                                             double confidence_level, double *d_core, double *d_pred, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_bls_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                           const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                           const int64_t *train_counts, AnofoxHipBlsBatchOptions options,
+                                           double confidence_level, double *core, double *pred, AnofoxError *out_error);
 
 
 /*
