@@ -116,7 +116,8 @@ def fit_bls(y, X, fit_intercept=False, lower=None, upper=None, max_iterations=10
     intercept (NaN without one), ssr, r_squared, n_observations, n_active_constraints, at_lower_bound[p], at_upper_bound[p];
     plus held_lower / held_upper (columns the solve holds on a bound), multipliers g = x_j'r, iterations and the valid rows."""
     y = np.asarray(y, dtype=np.float64)
-    X = np.asarray(X, dtype=np.float64).reshape(len(y), -1)
+    X = np.asarray(X, dtype=np.float64)
+    X = X if X.ndim == 2 else X.reshape(len(y), -1)
     n, p = X.shape
     out = {"status": 0, "p": p}
     if (n if rule_count is None else rule_count) < 2:
@@ -223,6 +224,25 @@ def input_conditions(res, y, X, fit_intercept, tolerance=1e-10):
     sv = np.linalg.svd(D / np.linalg.norm(D, axis=0), compute_uv=False)
     if sv[0] > 1e6 * sv[-1]:
         bad.append("column-scaled design condition number above 1e6")
+    return bad
+
+
+def moment_conditions(res, y, X, fit_intercept, tolerance=1e-10):
+    """input_conditions with the bound on the design that a solver of MOMENTS can be held to: it loses about
+    p kappa^2 2^-53, so 1e-9 on the coefficients needs  p kappa^2 2^-53 <= 1e-10  (kappa <= 335 at p = 8, 84 at p = 128) of the
+    column-scaled design of the non-constant columns (with the ones column when there is an intercept) — far inside
+    input_conditions' 1e6.  The randomised family sweeps assert this variant."""
+    bad = input_conditions(res, y, X, fit_intercept, tolerance)
+    if res["status"] != 0 or np.isnan(res.get("ssr", np.nan)):
+        return bad
+    ok, const = res["valid"], res["const"]
+    Xv = np.asarray(X)[ok][:, ~const]
+    D = np.concatenate([np.ones((len(Xv), 1)), Xv], axis=1) if fit_intercept else Xv
+    sv = np.linalg.svd(D / np.linalg.norm(D, axis=0), compute_uv=False)
+    kappa = sv[0] / sv[-1] if sv[-1] > 0 else np.inf
+    res["kappa"] = float(kappa)
+    if not res["p"] * kappa * kappa * 2.0 ** -53 <= 1e-10:
+        bad.append(f"p kappa^2 2^-53 above 1e-10 (kappa {kappa:.3g})")
     return bad
 
 
