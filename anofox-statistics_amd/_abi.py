@@ -26,6 +26,7 @@ ERROR_DIMENSION_MISMATCH = 9
 ERROR_NO_VALID_DATA = 10
 ERROR_INTERNAL = 99
 STATUS_NULL_TOO_FEW_ROWS = 100
+STATUS_UNREFINED = 101   # a streaming state could neither resolve nor refit the group: NaN record, SQL NULL
 
 SOLVER = {"qr": 0, "svd": 1, "cholesky": 2}
 LAMBDA_SCALING = {"raw": 0, "glmnet": 1}
@@ -252,6 +253,18 @@ SYMBOLS = {
     "anofox_hip_agg_state_import_slots_host": (C.c_bool, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, _ERRP]),
     "anofox_hip_agg_state_finalize_host": (C.c_bool, [C.c_void_p, C.c_int64, _DP, _DP, C.POINTER(C.c_int64), C.c_void_p, _ERRP]),
     "anofox_hip_agg_state_finalize_device": (C.c_bool, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_agg_state_finalize_elasticnet_host": (C.c_bool, [C.c_void_p, C.c_int64, AnofoxHipElasticNetBatchOptions, _DP,
+                                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.c_void_p, _ERRP]),
+    "anofox_hip_agg_state_finalize_elasticnet_device": (C.c_bool, [C.c_void_p, C.c_int64, AnofoxHipElasticNetBatchOptions, C.c_void_p,
+                                                                   C.c_void_p, _ERRP]),
+    "anofox_hip_agg_state_finalize_elasticnet_slots_host": (C.c_bool, [C.c_void_p, C.c_int64, C.c_void_p, AnofoxHipElasticNetBatchOptions,
+                                                                       _DP, C.POINTER(C.c_int32), C.POINTER(C.c_int64), _ERRP]),
+    "anofox_hip_agg_state_finalize_bls_host": (C.c_bool, [C.c_void_p, C.c_int64, AnofoxHipBlsBatchOptions, _DP, C.POINTER(C.c_int32),
+                                                          C.POINTER(C.c_int64), C.c_void_p, _ERRP]),
+    "anofox_hip_agg_state_finalize_bls_device": (C.c_bool, [C.c_void_p, C.c_int64, AnofoxHipBlsBatchOptions, C.c_void_p, C.c_void_p,
+                                                            _ERRP]),
+    "anofox_hip_agg_state_finalize_bls_slots_host": (C.c_bool, [C.c_void_p, C.c_int64, C.c_void_p, AnofoxHipBlsBatchOptions, _DP,
+                                                                C.POINTER(C.c_int32), C.POINTER(C.c_int64), _ERRP]),
     "anofox_elasticnet_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxElasticNetOptions,
                                          C.POINTER(AnofoxFitResultCore), _ERRP]),
     "anofox_hip_elasticnet_fit_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,

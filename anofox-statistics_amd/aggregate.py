@@ -22,8 +22,8 @@ from typing import Any, List, Mapping, Optional, Sequence
 import numpy as np
 
 from . import _abi
-from .options import (InvalidInputException, RegressionOptions, parse_bls_options, parse_bls_predict_options, parse_elasticnet_predict_options,
-                      parse_nnls_options, parse_options, parse_rls_options)
+from .options import (BlsOptions, ElasticNetOptions, InvalidInputException, RegressionOptions, parse_bls_options, parse_bls_predict_options,
+                      parse_elasticnet_options, parse_elasticnet_predict_options, parse_nnls_options, parse_options, parse_rls_options)
 from .runtime import AggState, Context, fit_batch_host
 
 
@@ -47,6 +47,7 @@ class FitAggResult:
     ci_upper: Optional[np.ndarray] = None
     f_statistic: Optional[np.ndarray] = None
     f_pvalue: Optional[np.ndarray] = None
+    iterations: Optional[np.ndarray] = None   # elastic net from a streaming state: sweeps, negated when max_iterations stopped the group
 
     def __len__(self):
         return len(self.keys)
@@ -130,6 +131,39 @@ class StreamingStates:
             core, inf, self.unrefined = self.state.finalize(self.n_slots)
             self._solved = (core, inf)
         return self._solved
+
+    # ---- other families from the same state: it does not depend on lambda, l1_ratio or the bounds, so one pass over the rows
+    # serves the regression Finalize above, any number of elastic net fits along a lambda grid and a BLS / NNLS fit ----
+    def _family_slots(self, slots, family, fit_intercept):
+        if self.state is None:
+            raise InvalidInputException("no row has reached the streaming state yet")
+        self.state.check_family(family, fit_intercept)      # before anything reaches the library
+        self.state.reserve(self.n_slots)          # slots whose rows were all skipped never reached the GPU
+        return np.arange(self.n_slots, dtype=np.uint32) if slots is None else np.ascontiguousarray(slots, dtype=np.uint32)
+
+    def finalize_elasticnet(self, options=None, slots=None):
+        """anofox_stats_elasticnet_fit_agg's fit of every slot (or of the listed ones) from the streaming state.  options: the
+        MAP of parse_elasticnet_options (or an ElasticNetOptions).  -> (FitAggResult keyed by slot number, with the sweep counts
+        in its `iterations` field; the slot numbers that came back unrefined: status 101, NULL)."""
+        opts = options if isinstance(options, ElasticNetOptions) else parse_elasticnet_options(options)
+        keys = self._family_slots(slots, "elastic net", opts.fit_intercept)
+        core, its, unrefined = self.state.finalize_elasticnet(opts.batch_options(), slots=None if slots is None else keys,
+                                                               n_slots=self.n_slots)
+        res = result_from_records(keys, core, None, self.state.p)
+        res.iterations = its
+        return res, unrefined
+
+    def finalize_bls(self, options=None, slots=None):
+        """anofox_stats_bls_fit_agg's fit from the streaming state (options: parse_bls_options' MAP or a BlsOptions).
+        -> (BlsFitAggResult keyed by slot number, the unrefined slot numbers)."""
+        opts = options if isinstance(options, BlsOptions) else parse_bls_options(options)
+        keys = self._family_slots(slots, "bounded least squares", opts.fit_intercept)
+        rec, its, unrefined = self.state.finalize_bls(opts.batch_options(), slots=None if slots is None else keys, n_slots=self.n_slots)
+        return bls_result_from_records(keys, rec, its, self.state.p), unrefined
+
+    def finalize_nnls(self, options=None, slots=None):
+        """anofox_stats_nnls_fit_agg from the streaming state: finalize_bls with the bound keys ignored (lower bound 0)."""
+        return self.finalize_bls(options if isinstance(options, BlsOptions) else parse_nnls_options(options), slots)
 
 
 class _FitAgg:

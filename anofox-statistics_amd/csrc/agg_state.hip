@@ -12,6 +12,8 @@
 // Designs wider than 8 features and heteroskedasticity-consistent errors have no moment record to stream into: such a
 // state keeps ONLY the row log ("log-only": the reference's row buffers, in HBM) and Finalize runs the batch path on
 // all of it — same entry points, any p <= 128, any hc_type.
+// The state does not depend on the options of the elastic net or of bounded least squares: agg_state_models.hip finalizes those
+// two families from the same records / the same log (read-only; the state object and the helpers they share are in agg_state.h).
 // Host chunks are staged through two device buffers on a copy stream, so the H2D copy of chunk k + 1 overlaps
 // the kernels of chunk k; update() returns once its inputs have been copied (the caller may reuse them).
 #include <stdlib.h>
@@ -22,51 +24,10 @@
 
 #include <algorithm>
 
-#include "context.h"
+#include "agg_state.h"
 
 using namespace anofox;
 using namespace anofox::host;
-
-struct AnofoxHipAggState {
-	AnofoxHipContext *ctx = nullptr;
-	size_t p = 0;
-	AnofoxHipBatchOptions opt{};
-	std::mutex mu;
-	// per-slot state
-	double *moments = nullptr;
-	int64_t *n_accum = nullptr;
-	int32_t *run_start = nullptr, *run_end = nullptr;
-	int64_t capacity = 0; // slots allocated
-	int64_t n_slots = 0;  // slots in use (largest count announced by the caller)
-	int64_t rows = 0;     // rows passed to update so far
-	// per-pass scratch (one set: the passes of one state are serialised on the context's stream)
-	void *scratch = nullptr;
-	size_t scratch_bytes = 0;
-	size_t sort_temp_bytes = 0;
-	int32_t *counters = nullptr; // [0] runs of the current pass, [1] sticky out-of-range flag (own small allocation)
-	// staging of host chunks
-	struct Stage {
-		void *buf = nullptr;
-		size_t bytes = 0;
-		hipEvent_t copied = nullptr, done = nullptr;
-	} stage[2];
-	int next_stage = 0;
-	hipStream_t copy_stream = nullptr;
-	void *pair_buf = nullptr; // combine: src | dst
-	size_t pair_bytes = 0;
-	// optional row log (anofox_hip_agg_state_retain_rows): slabs in arrival order
-	bool log_only = false;     // p > 8 or HC errors: no moments, the row log IS the state
-	bool retain = false;       // asked for
-	bool log_dropped = false;  // ... and given up because the budget was exceeded
-	size_t log_budget = 0, log_bytes = 0;            // HBM part of the log
-	size_t log_host_budget = 0, log_host_bytes = 0;  // page-locked host part (the spill beyond the HBM budget)
-	int64_t log_rows = 0;
-	std::vector<RowLogSlab> slabs;
-	void *refit_idx = nullptr, *refit_rows = nullptr; // Finalize's refit scratch
-	size_t refit_idx_bytes = 0, refit_rows_bytes = 0;
-	void *remap_buf = nullptr;
-	size_t remap_bytes = 0;
-};
 
 namespace {
 void slab_release(RowLogSlab &sl) {
@@ -753,8 +714,10 @@ bool run_solve(AnofoxHipAggState *s, int64_t n, double *d_moments, const int64_t
 // every slot 0 .. n - 1 when d_list is nullptr (K == n) — rowlog.hip's header has the steps.  Records go to rows
 // d_list[k] of d_core / d_inf (scatter) or, for all slots, straight to rows 0 .. n - 1.  Synchronises the stream once
 // (the number of selected rows has to reach the host).
+// With `model` (agg_state_models.hip) the accumulate kernels are followed by that family's solve stages instead: records of
+// model->rec_len doubles, no inference records, its iteration counts scattered with them.
 bool refit_from_log(AnofoxHipAggState *s, int64_t n, int64_t K, const int32_t *d_list, bool keep_hc, double *d_core, double *d_inf,
-                    AnofoxError *e, const int32_t *d_pos = nullptr) {
+                    AnofoxError *e, const int32_t *d_pos = nullptr, const ModelRefit *model = nullptr) {
 	AnofoxHipContext *ctx = s->ctx;
 	hipStream_t st = ctx->stream;
 	const size_t p = s->p;
@@ -794,14 +757,19 @@ bool refit_from_log(AnofoxHipAggState *s, int64_t n, int64_t K, const int32_t *d
 		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "update: a row named a slot index >= n_slots (the row was dropped)");
 		return false;
 	}
-	if (!all && counts[0] == 0) return true; // nothing logged for them (cannot happen for a fitted group): leave them as they are
+	// nothing logged for them (cannot happen for a fitted group): leave them as they are.  (Another family's log-only Finalize of
+	// listed slots has no earlier records: it goes on and gets the empty groups' status 100.)
+	if (!all && counts[0] == 0 && !(model && s->log_only)) return true;
 	const size_t M = (size_t)counts[0];
 	const size_t Mb = M ? M : 1;
 	// row scratch: keys a | keys b | y | w | x columns | offsets | core | inference | sort temp for M keys
 	const size_t b_k = align_up(Mb * sizeof(uint64_t), 256), b_c = align_up(Mb * sizeof(double), 256);
 	const size_t b_off = align_up((size_t)(K + 1) * sizeof(int64_t), 256);
-	const size_t b_core = all ? 0 : align_up((size_t)K * (p + 6) * sizeof(double), 256);
-	const size_t b_inf = (!all && s->opt.compute_inference) ? align_up((size_t)K * (5 * p + 2) * sizeof(double), 256) : 0;
+	const size_t rec_len = model ? (size_t)model->rec_len : p + 6;
+	const size_t b_core = all ? 0 : align_up((size_t)K * rec_len * sizeof(double), 256);
+	// (the inference records' place holds the other families' iteration counts)
+	const size_t b_inf = all ? 0 : (model ? (model->d_iterations ? align_up((size_t)K * sizeof(int32_t), 256) : 0)
+	                                      : (s->opt.compute_inference ? align_up((size_t)K * (5 * p + 2) * sizeof(double), 256) : 0));
 	const size_t b_t2 = align_up(rowlog_sort_temp_bytes((int64_t)Mb), 256);
 	if (!ensure_buffer(&s->refit_rows, &s->refit_rows_bytes, 2 * b_k + (2 + p) * b_c + b_off + b_core + b_inf + b_t2, "refit scratch", e)) return false;
 	char *rb = (char *)s->refit_rows;
@@ -827,6 +795,21 @@ bool refit_from_log(AnofoxHipAggState *s, int64_t n, int64_t K, const int32_t *d
 	for (size_t j = 0; j < p; ++j) x_cols[j] = d_x + j * col_stride;
 	AnofoxHipBatchOptions opt = s->opt;
 	if (!keep_hc) opt.hc_type = ANOFOX_HC_NONE;
+	if (model) {
+		int32_t *d_it2 = all ? model->d_iterations : (int32_t *)d_inf2;
+		*model->iterations_field = d_it2;
+		AnofoxHipBatchOptions acc; // the moments of an unweighted fit
+		memset(&acc, 0, sizeof acc);
+		acc.model = ANOFOX_HIP_MODEL_OLS;
+		acc.fit_intercept = s->opt.fit_intercept;
+		acc.confidence_level = 0.95;
+		acc.hc_type = ANOFOX_HC_NONE;
+		if (!moment_batch_device(ctx, K, p, (int64_t)M, d_off, d_y, x_cols, acc, model->stages, d_core2, e)) return false;
+		if (all) return true;
+		return !hip_fail(model->scatter(d_core2, d_it2, d_sorted, K, (int)rec_len, d_core, model->d_iterations, d_pos,
+		                                              model->n_records, st),
+		                 "refit scatter", e);
+	}
 	if (!refit_groups_device(ctx, K, p, (int64_t)M, d_off, d_y, x_cols, weighted ? d_w : nullptr, opt, d_core2, d_inf2, e)) return false;
 	if (all) return true;
 	bad = hip_fail(launch_rowlog_scatter(d_core2, d_sorted, K, (int)(p + 6), d_core, d_pos, st), "refit scatter", e);
@@ -883,6 +866,19 @@ bool check_slot_flag(AnofoxHipAggState *s, AnofoxError *e) {
 }
 
 } // namespace
+
+namespace anofox {
+namespace host {
+// what agg_state_models.hip shares with the Finalize above (agg_state.h)
+bool agg_state_attached(AnofoxHipAggState *s, AnofoxError *e) { return attached(s, e); }
+bool agg_state_reserve_slots(AnofoxHipAggState *s, int64_t n_slots, AnofoxError *e) { return state_reserve(s, n_slots, e); }
+bool agg_state_check_slot_flag(AnofoxHipAggState *s, AnofoxError *e) { return check_slot_flag(s, e); }
+bool agg_state_refit_from_log(AnofoxHipAggState *s, int64_t n, int64_t K, const int32_t *d_list, double *d_records, const int32_t *d_pos,
+                              const ModelRefit &model, AnofoxError *e) {
+	return refit_from_log(s, n, K, d_list, false, d_records, nullptr, e, d_pos, &model);
+}
+} // namespace host
+} // namespace anofox
 
 extern "C" {
 

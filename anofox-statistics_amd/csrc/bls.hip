@@ -474,6 +474,7 @@ bool bls_narrow_stage(AnofoxHipContext *, BatchArgs &a, hipStream_t st, void *us
 	bp.predict_layout = bw.predict_layout;
 	bp.iterations = bw.iterations;
 	if (hip_fail(launch_bls_narrow(a, bp, st), "bounded least squares solve kernel launch", e)) return false;
+	if (!a.row_offsets) return true; // the records of a streaming state: no rows here, its Finalize answers the flagged groups
 	BlsRowsArgs ra;
 	memset(&ra, 0, sizeof ra);
 	ra.row_offsets = a.row_offsets;
@@ -572,6 +573,18 @@ bool run_bls(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const i
 }
 
 } // namespace
+
+namespace anofox {
+namespace host {
+// the solve as a streaming state's Finalize runs it (agg_state_models.hip)
+bool bls_state_options(const AnofoxHipBlsBatchOptions &o, AnofoxError *e) {
+	if (!(o.tolerance >= 0.0)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "tolerance must be >= 0"); return false; }
+	return true;
+}
+BlsParamsT<kWideMaxP> bls_state_params(const AnofoxHipBlsBatchOptions &o, size_t p) { return bls_params(o, p, 0, nullptr); }
+SolveStages bls_state_stages(BlsParamsT<kWideMaxP> *bp) { return bls_stages(bp); }
+} // namespace host
+} // namespace anofox
 
 extern "C" {
 

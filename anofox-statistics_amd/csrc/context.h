@@ -72,6 +72,15 @@ struct SolveStages {
 bool moment_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
                          const double *d_y, const double *const *x_cols, const AnofoxHipBatchOptions &opt, const SolveStages &stages,
                          double *d_core, AnofoxError *e);
+// elasticnet.hip / bls.hip: the two families' option checks, solve parameters (iterations unset) and stages, for the Finalize of
+// a streaming state (agg_state_models.hip).  Their narrow stage takes records without rows (BatchArgs::row_offsets == nullptr):
+// it then leaves the groups it flags in refine_list[g] to the caller.
+bool elasticnet_state_options(const AnofoxHipElasticNetBatchOptions &o, AnofoxError *e);
+EnParams elasticnet_state_params(const AnofoxHipElasticNetBatchOptions &o);
+SolveStages elasticnet_state_stages(EnParams *en);
+bool bls_state_options(const AnofoxHipBlsBatchOptions &o, AnofoxError *e);
+BlsParamsT<kWideMaxP> bls_state_params(const AnofoxHipBlsBatchOptions &o, size_t p);
+SolveStages bls_state_stages(BlsParamsT<kWideMaxP> *bp);
 // host_api.hip: the calling thread's default context on the current device (the host entry points' ctx == NULL)
 AnofoxHipContext *thread_default_context(AnofoxError *e);
 // The window path of another model (the elastic net): its solve stages for the frames path, and its in-register window kernels

@@ -261,6 +261,7 @@ hipError_t launch_rows_rss(const RowsArgs &ra, hipStream_t st) {
 bool en_narrow_stage(AnofoxHipContext *, BatchArgs &a, hipStream_t st, void *user, AnofoxError *e) {
 	const EnParams &en = *static_cast<const EnParams *>(user);
 	if (hip_fail(launch_en_narrow(a, en, st), "elastic net solve kernel launch", e)) return false;
+	if (!a.row_offsets) return true; // the records of a streaming state: no rows here, its Finalize answers the flagged groups
 	RowsArgs ra;
 	memset(&ra, 0, sizeof ra);
 	ra.row_offsets = a.row_offsets;
@@ -375,6 +376,15 @@ std::string fmt_g(double v) {
 }
 
 } // namespace
+
+namespace anofox {
+namespace host {
+// the solve as a streaming state's Finalize runs it (agg_state_models.hip)
+bool elasticnet_state_options(const AnofoxHipElasticNetBatchOptions &o, AnofoxError *e) { return validate_elasticnet_options(o, e); }
+EnParams elasticnet_state_params(const AnofoxHipElasticNetBatchOptions &o) { return elasticnet_params(o, nullptr); }
+SolveStages elasticnet_state_stages(EnParams *en) { return elasticnet_stages(en); }
+} // namespace host
+} // namespace anofox
 
 extern "C" {
 

@@ -631,6 +631,84 @@ class AggState:
             raise AnofoxStatsError(err.code, err.text())
         return core, inference
 
+    # ---- the elastic net and bounded least squares from the same state (anofox_hip_agg_state_finalize_{elasticnet,bls}_*) ----
+    def check_family(self, family: str, fit_intercept: bool):
+        """The state has to hold the moments of the unweighted fit the family's batch call accumulates: model OLS (no
+        weights), hc_type none, the family's fit_intercept.  Raises before any library call."""
+        o = self.options
+        if int(o.model) != _abi.MODEL["ols"]:
+            what = "WLS (weights)" if int(o.model) == _abi.MODEL["wls"] else "ridge"
+            raise AnofoxStatsError(_abi.ERROR_INVALID_INPUT,
+                                   f"{family} finalize: the state was created with model {what}, it needs the unweighted OLS moments")
+        if int(o.hc_type) != 0:
+            raise AnofoxStatsError(_abi.ERROR_INVALID_INPUT,
+                                   f"{family} finalize: the state was created with an hc_type other than none")
+        if bool(o.fit_intercept) != bool(fit_intercept):
+            raise AnofoxStatsError(_abi.ERROR_INVALID_INPUT,
+                                   f"{family} finalize: fit_intercept of the options differs from the fit_intercept the state was created with")
+
+    def _finalize_family(self, family, fn_host, fn_slots, rec_len, options, slots, n_slots):
+        self.check_family(family, options.fit_intercept)
+        fn_host, fn_slots = getattr(self._lib, fn_host), getattr(self._lib, fn_slots)
+        err = _abi.AnofoxError()
+        unref = C.c_int64()
+        if slots is None:
+            G = self.n_slots if n_slots is None else int(n_slots)
+            rec = np.empty((G, rec_len), dtype=np.float64)
+            its = np.empty(G, dtype=np.int32)
+            listed = np.empty(max(G, 1), dtype=np.int32)
+            ok = fn_host(self._h, G, options, rec.ctypes.data_as(_DP), its.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(unref),
+                         listed.ctypes.data, C.byref(err))
+            if not ok:
+                raise AnofoxStatsError(err.code, err.text())
+            return rec, its, listed[:int(unref.value)].copy()
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        rec = np.empty((len(sl), rec_len), dtype=np.float64)
+        its = np.empty(len(sl), dtype=np.int32)
+        ok = fn_slots(self._h, len(sl), sl.ctypes.data, options, rec.ctypes.data_as(_DP), its.ctypes.data_as(C.POINTER(C.c_int32)),
+                      C.byref(unref), C.byref(err))
+        if not ok:
+            raise AnofoxStatsError(err.code, err.text())
+        unrefined = sl[rec[:, self.p + 5] == _abi.STATUS_UNREFINED].astype(np.int32)
+        if len(unrefined) != int(unref.value):
+            raise AnofoxStatsError(_abi.ERROR_INTERNAL, f"{family} finalize: {int(unref.value)} slots counted as unrefined, {len(unrefined)} marked")
+        return rec, its, unrefined
+
+    def finalize_elasticnet(self, options: _abi.AnofoxHipElasticNetBatchOptions, slots=None, n_slots: Optional[int] = None):
+        """The elastic net of every slot (or of the listed ones) from this state, which stays as it is:
+        -> (core[G, p+6], iterations int32[G], the slot numbers that came back unrefined: status 101, NaN record)."""
+        return self._finalize_family("elastic net", "anofox_hip_agg_state_finalize_elasticnet_host",
+                                     "anofox_hip_agg_state_finalize_elasticnet_slots_host", self.p + 6, options, slots, n_slots)
+
+    def finalize_bls(self, options: _abi.AnofoxHipBlsBatchOptions, slots=None, n_slots: Optional[int] = None):
+        """Bounded / non-negative least squares of every slot (or of the listed ones) from this state:
+        -> (bls[G, 3p+6], iterations int32[G], the unrefined slot numbers)."""
+        return self._finalize_family("bounded least squares", "anofox_hip_agg_state_finalize_bls_host",
+                                     "anofox_hip_agg_state_finalize_bls_slots_host", 3 * self.p + 6, options, slots, n_slots)
+
+    def _finalize_family_device(self, family, fn, options, records, iterations, n_slots, use_current_torch_stream):
+        import torch
+        self.check_family(family, options.fit_intercept)
+        fn = getattr(self._lib, fn)
+        G = self.n_slots if n_slots is None else int(n_slots)
+        if use_current_torch_stream:
+            self._ctx.set_stream(torch.cuda.current_stream(records.device).cuda_stream)
+        err = _abi.AnofoxError()
+        if not fn(self._h, G, options, C.c_void_p(records.data_ptr()), C.c_void_p(iterations.data_ptr() if iterations is not None else 0),
+                  C.byref(err)):
+            raise AnofoxStatsError(err.code, err.text())
+        return records, iterations
+
+    def finalize_elasticnet_device(self, options, core, iterations=None, n_slots: Optional[int] = None, use_current_torch_stream: bool = True):
+        """core: float64 CUDA tensor [G, p+6]; iterations: int32 CUDA tensor [G] or None."""
+        return self._finalize_family_device("elastic net", "anofox_hip_agg_state_finalize_elasticnet_device", options, core,
+                                            iterations, n_slots, use_current_torch_stream)
+
+    def finalize_bls_device(self, options, bls, iterations=None, n_slots: Optional[int] = None, use_current_torch_stream: bool = True):
+        """bls: float64 CUDA tensor [G, 3p+6]; iterations: int32 CUDA tensor [G] or None."""
+        return self._finalize_family_device("bounded least squares", "anofox_hip_agg_state_finalize_bls_device", options, bls,
+                                            iterations, n_slots, use_current_torch_stream)
+
 
 def fit_batch_host(row_offsets, y, x_cols: Sequence, w, options: _abi.AnofoxHipBatchOptions,
                    ctx: Optional[Context] = None):

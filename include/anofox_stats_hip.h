@@ -760,6 +760,9 @@ ANOFOX_HIP_API bool anofox_hip_residuals_batch_host(AnofoxHipContext *ctx, int64
  *             log (0 = no cap), retain_rows_host its host part, and an Update that exceeds both (or the memory itself)
  *             FAILS with ANOFOX_ERROR_ALLOCATION_FAILURE.
  *
+ *   other families  the elastic net and the bounded / non-negative least squares are finalized from the same state
+ *             (anofox_hip_agg_state_finalize_elasticnet_* / _bls_*, below): the state does not depend on their options.
+ *
  * A state belongs to one context (device + stream); calls on one state are serialised.  n_features <=
  * anofox_hip_agg_state_max_features() = 128.
  */
@@ -816,6 +819,39 @@ ANOFOX_HIP_API bool anofox_hip_agg_state_finalize_host(AnofoxHipAggState *state,
                                         int64_t *out_unrefined, int32_t *out_unrefined_slots, AnofoxError *out_error);
 ANOFOX_HIP_API bool anofox_hip_agg_state_finalize_device(AnofoxHipAggState *state, int64_t n_slots, double *d_core, double *d_inference,
                                           AnofoxError *out_error);
+/*
+ * Elastic net and bounded / non-negative least squares from a streaming state.  A state is independent of lambda, l1_ratio and
+ * the bounds, so one pass over the rows serves the regression Finalize above and any number of these; each of them is READ-ONLY
+ * (moments, row log and slots stay as they are) and two calls with the same options return identical bits.  The state must have
+ * been created with model = OLS (no weights), hc_type = none and the fit_intercept of the family's options; anything else is
+ * ANOFOX_ERROR_INVALID_INPUT naming the mismatch, and nothing is launched.  Records and iteration counts (iterations may be
+ * NULL) as anofox_hip_elasticnet_fit_batch_* (p + 6) / anofox_hip_bls_fit_batch_* (anofox_hip_bls_record_len(p)); status 100
+ * for fewer than 2 accumulated rows; unusable BLS bounds give status 1 to every other slot.
+ *   n_features <= 8   the family's solve on the moment records.  It flags the slots whose moment-form ssr has cancelled (the
+ *                     batch path sums those residuals from the rows): with a row log exactly their logged rows go through the
+ *                     batch path and *out_unrefined is 0; without one (or once it was dropped) their records are NaN with status
+ *                     ANOFOX_HIP_STATUS_UNREFINED, counted in *out_unrefined and listed (ascending) in out_unrefined_slots
+ *                     (optional, room for n_slots entries).
+ *   9 .. 128          log-only states: the batch path with the family's solve over the whole log; *out_unrefined is 0.
+ * _device: device buffers, asynchronous on the context's stream except that a kept row log synchronises it once.
+ * _slots_host: the listed (distinct) slots only, record k belongs to slots[k]; the same bits as those rows of the full call,
+ *              except slots refitted from the row log, which agree to rounding (the refit's batch of rows is another one).
+ */
+ANOFOX_HIP_API bool anofox_hip_agg_state_finalize_elasticnet_host(AnofoxHipAggState *state, int64_t n_slots, AnofoxHipElasticNetBatchOptions options,
+                                                   double *core, int32_t *iterations, int64_t *out_unrefined, int32_t *out_unrefined_slots,
+                                                   AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_agg_state_finalize_elasticnet_device(AnofoxHipAggState *state, int64_t n_slots, AnofoxHipElasticNetBatchOptions options,
+                                                     double *d_core, int32_t *d_iterations, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_agg_state_finalize_elasticnet_slots_host(AnofoxHipAggState *state, int64_t n_list, const uint32_t *slots,
+                                                         AnofoxHipElasticNetBatchOptions options, double *core, int32_t *iterations,
+                                                         int64_t *out_unrefined, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_agg_state_finalize_bls_host(AnofoxHipAggState *state, int64_t n_slots, AnofoxHipBlsBatchOptions options, double *bls,
+                                            int32_t *iterations, int64_t *out_unrefined, int32_t *out_unrefined_slots, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_agg_state_finalize_bls_device(AnofoxHipAggState *state, int64_t n_slots, AnofoxHipBlsBatchOptions options, double *d_bls,
+                                              int32_t *d_iterations, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_agg_state_finalize_bls_slots_host(AnofoxHipAggState *state, int64_t n_list, const uint32_t *slots,
+                                                  AnofoxHipBlsBatchOptions options, double *bls, int32_t *iterations, int64_t *out_unrefined,
+                                                  AnofoxError *out_error);
 /* Page-locked host memory for the shim's row arenas (copies from it run at the full PCIe rate and asynchronously). */
 ANOFOX_HIP_API void *anofox_hip_host_alloc(size_t bytes);
 ANOFOX_HIP_API void anofox_hip_host_free(void *ptr);
