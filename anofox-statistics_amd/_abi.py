@@ -138,6 +138,19 @@ class AnofoxHipBlsBatchOptions(C.Structure):
     _fields_ = AnofoxBlsOptions._fields_
 
 
+class AnofoxQuantileOptions(C.Structure):  # anofox_stats_ffi.h:1371-1380, 24 bytes
+    _fields_ = [("tau", C.c_double), ("fit_intercept", C.c_bool), ("max_iterations", C.c_uint32), ("tolerance", C.c_double)]
+
+
+class AnofoxQuantileFitResultCore(C.Structure):  # anofox_stats_ffi.h:1385-1398, 48 bytes
+    _fields_ = [("coefficients", _DP), ("coefficients_len", C.c_size_t), ("intercept", C.c_double), ("tau", C.c_double),
+                ("n_observations", C.c_size_t), ("n_features", C.c_size_t)]
+
+
+class AnofoxHipQuantileBatchOptions(C.Structure):
+    _fields_ = AnofoxQuantileOptions._fields_
+
+
 # every symbol include/anofox_stats_hip.h declares: name -> (restype, argtypes)
 _ERRP = C.POINTER(AnofoxError)
 _CTX = C.c_void_p
@@ -331,6 +344,21 @@ SYMBOLS = {
     "anofox_hip_bls_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
                                                          C.POINTER(_DP), C.POINTER(C.c_int64), AnofoxHipBlsBatchOptions,
                                                          C.c_double, _DP, _DP, _ERRP]),
+    "anofox_quantile_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxQuantileOptions,
+                                       C.POINTER(AnofoxQuantileFitResultCore), _ERRP]),
+    "anofox_free_quantile_result": (None, [C.POINTER(AnofoxQuantileFitResultCore)]),
+    "anofox_hip_quantile_record_len": (C.c_size_t, [C.c_size_t]),
+    "anofox_hip_quantile_fit_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                        C.POINTER(C.c_void_p), AnofoxHipQuantileBatchOptions, C.c_void_p, C.c_void_p,
+                                                        _ERRP]),
+    "anofox_hip_quantile_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                      C.POINTER(_DP), AnofoxHipQuantileBatchOptions, _DP, C.POINTER(C.c_int32), _ERRP]),
+    "anofox_hip_quantile_fit_predict_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                                C.POINTER(C.c_void_p), C.c_void_p, AnofoxHipQuantileBatchOptions,
+                                                                C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_quantile_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                              C.POINTER(_DP), C.POINTER(C.c_int64), AnofoxHipQuantileBatchOptions,
+                                                              _DP, _DP, _ERRP]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "anofox_hip_host_free": (None, [C.c_void_p]),
 }

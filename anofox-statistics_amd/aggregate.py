@@ -1022,3 +1022,33 @@ SQL_FUNCTIONS.update({
     "anofox_stats_nnls_fit_agg": nnls_fit_agg, "nnls_fit_agg": nnls_fit_agg,
     "anofox_stats_bls_fit_predict_agg": bls_fit_predict_agg, "bls_fit_predict_agg": bls_fit_predict_agg,
 })
+
+
+# quantile regression: anofox_stats_quantile_fit_predict_agg (src/aggregate_functions/quantile_fit_predict_aggregate.cpp).
+# The reference has no fit aggregate and no window function for it.
+
+class QuantileFitPredictAgg(_FitPredictAgg):
+    """anofox_stats_quantile_fit_predict_agg — alias quantile_fit_predict_agg: training rows as the other fit-predict
+    aggregates (a NULL feature stays a training row and is dropped by the fit's filter), "fewer than 2 training rows ->
+    NULL", a failed fit -> NULL.  The SQL result keeps y, yhat and is_training; there is no interval (the bounds are NaN)."""
+    model = "quantile"
+    sql_name = "anofox_stats_quantile_fit_predict_agg"
+
+    @staticmethod
+    def _parse_options(options):
+        from .options import parse_quantile_options
+        return parse_quantile_options(options)
+
+    def _fit_predict(self, offsets, y_fit, x_cols, w, train_counts):
+        from .runtime import quantile_fit_predict_batch_host
+        return quantile_fit_predict_batch_host(offsets, y_fit, x_cols, self.options.batch_options(), train_counts=train_counts,
+                                               ctx=self._ctx)
+
+
+def quantile_fit_predict_agg(group_keys, y, x, options=None, context=None, split=None) -> FitPredictAggResult:
+    return QuantileFitPredictAgg(options, context).update(group_keys, y, x, split=split).finalize()
+
+
+SQL_FUNCTIONS.update({
+    "anofox_stats_quantile_fit_predict_agg": quantile_fit_predict_agg, "quantile_fit_predict_agg": quantile_fit_predict_agg,
+})

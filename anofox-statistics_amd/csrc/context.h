@@ -81,6 +81,10 @@ SolveStages elasticnet_state_stages(EnParams *en);
 bool bls_state_options(const AnofoxHipBlsBatchOptions &o, AnofoxError *e);
 BlsParamsT<kWideMaxP> bls_state_params(const AnofoxHipBlsBatchOptions &o, size_t p);
 SolveStages bls_state_stages(BlsParamsT<kWideMaxP> *bp);
+// host_api.hip: the predict kernels on fit records in the regression layout, enqueued on the context's stream; the caller
+// holds ctx->mu (a family that fits outside the moment path — quantile.hip — keeps one lock over fit and predict)
+bool predict_records_locked(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
+                            const double *const *x_cols, const double *d_core, double confidence_level, double *d_pred, AnofoxError *e);
 // host_api.hip: the calling thread's default context on the current device (the host entry points' ctx == NULL)
 AnofoxHipContext *thread_default_context(AnofoxError *e);
 // The window path of another model (the elastic net): its solve stages for the frames path, and its in-register window kernels

@@ -2042,6 +2042,11 @@ void anofox_free_residuals(AnofoxResidualsResult *result) {
 namespace anofox {
 namespace host {
 
+bool predict_records_locked(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
+                            const double *const *x_cols, const double *d_core, double confidence_level, double *d_pred, AnofoxError *e) {
+	return run_predict(ctx, n_groups, p, n_rows, d_row_offsets, x_cols, d_core, confidence_level, d_pred, e);
+}
+
 bool model_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
                                     const double *d_y, const double *const *x_cols, const int64_t *d_train_counts,
                                     const AnofoxHipBatchOptions &opt, const SolveStages &stages, double *d_core, double *d_pred, AnofoxError *e) {

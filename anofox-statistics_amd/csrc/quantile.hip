@@ -1,0 +1,364 @@
+// quantile.hip — grouped quantile regression: one wavefront per group runs the exact simplex of quantile_solve.h over the
+// group's rows, and the entry points anofox_hip_quantile_fit_batch_{device,host}, anofox_hip_quantile_fit_predict_batch_*,
+// anofox_quantile_fit / anofox_free_quantile_result.
+//
+// The contract and the method: quantile_solve.h and DESIGN.md §1, "Quantile regression".
+//   quantile_fit_kernel: 64 lanes per workgroup = one wavefront per group (grid-stride over the groups).  LDS holds B^-1 and
+//     the LU workspace (k x k doubles each, k = p + [intercept] <= 33) and the per-edge vectors: qs_work_doubles(k) * 8 bytes,
+//     20.6 KB at k = 33.  Rows are strided over the lanes; residual, z and breakpoint of a row sit in a per-call device
+//     scratch (3 doubles per row, the context's workspace) that only the row's own lane touches.
+//   quantile_nan_bounds_kernel: the fit-predict entry points hand the records (regression layout, sigma = NaN) to the
+//     existing predict kernels, which give yhat = lower = upper for a NaN sigma; quantile regression has no interval, so
+//     the two bounds are then overwritten with NaN.
+// No atomics: a group is one wavefront's own work in a fixed order, so repeated calls give identical bytes.
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "quantile_solve.h"
+
+using namespace anofox;
+
+#include "context.h"
+
+using namespace anofox::host;
+using namespace anofox::quantile;
+
+namespace {
+
+struct QuantileArgs {
+	const int64_t *row_offsets;  // [G + 1]
+	const int64_t *train_counts; // [G] or nullptr: what the "fewer than 2 rows -> NULL" rule looks at
+	const double *y;
+	const double *x[kQsMaxP];
+	double *scratch; // [3 x n_rows]
+	int64_t n_rows;
+	int64_t n_groups;
+	int p;
+	int fit_intercept;
+	double tau;
+	int max_iterations;
+	int invalid;        // tau outside (0, 1): every group gets ANOFOX_ERROR_INVALID_INPUT
+	int predict_layout; // 1: the regression layout for the predict kernels
+	double *core;       // [G x (p + 6)]
+	int32_t *iterations; // [G] or nullptr
+};
+
+__global__ __launch_bounds__(64) void quantile_fit_kernel(QuantileArgs a) {
+	extern __shared__ double quantile_lds[];
+	for (int64_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
+		QsProblem P;
+		P.y = a.y;
+		P.x = a.x;
+		P.p = a.p;
+		P.fit_intercept = a.fit_intercept;
+		P.lo = a.row_offsets[g];
+		P.hi = a.row_offsets[g + 1];
+		P.rule_count = a.train_counts ? a.train_counts[g] : P.hi - P.lo;
+		P.tau = a.tau;
+		P.max_iterations = a.max_iterations;
+		P.predict_layout = a.predict_layout;
+		P.r = a.scratch;
+		P.z = a.scratch + a.n_rows;
+		P.t = a.scratch + 2 * a.n_rows;
+		qs_fit(P, a.invalid != 0, quantile_lds, a.core + g * (int64_t)(a.p + 6), a.iterations ? a.iterations + g : nullptr);
+		__syncthreads(); // the next group reuses the LDS
+	}
+}
+
+__global__ __launch_bounds__(256) void quantile_nan_bounds_kernel(double *pred, int64_t n_rows) {
+	const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= n_rows) return;
+	pred[3 * r + 1] = NAN;
+	pred[3 * r + 2] = NAN;
+}
+
+bool tau_invalid(double tau) { return !(tau > 0.0 && tau < 1.0); } // (NaN fails both)
+
+bool check_quantile(int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols, const void *out,
+                    AnofoxError *e) {
+	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
+	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
+	if (p > (size_t)kQsMaxP) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "quantile regression: n_features > 32 is not built"); return false; }
+	if (G > 0 && (!off || !y || !out)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets, y or an output is NULL"); return false; }
+	for (size_t j = 0; j < p; ++j)
+		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
+	return true;
+}
+
+bool check_host_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
+	for (int64_t g = 0; g < G; ++g) {
+		if (off[g + 1] < off[g] || off[g] < 0 || off[g + 1] > n_rows) {
+			set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing and within [0, n_rows]");
+			return false;
+		}
+	}
+	return true;
+}
+
+// the fit of G groups on device-resident inputs, enqueued on the context's stream (ctx->mu held by the caller)
+bool launch_quantile(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y,
+                     const double *const *x_cols, const int64_t *d_tc, const AnofoxHipQuantileBatchOptions &o, int predict_layout,
+                     double *d_core, int32_t *d_iterations, AnofoxError *e) {
+	if (G == 0) return true;
+	const size_t rows = n_rows > 0 ? (size_t)n_rows : 1;
+	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, 3 * rows * sizeof(double), "quantile scratch", e)) return false;
+	QuantileArgs a;
+	memset(&a, 0, sizeof a);
+	a.row_offsets = d_off;
+	a.train_counts = d_tc;
+	a.y = d_y;
+	for (size_t j = 0; j < p; ++j) a.x[j] = x_cols[j];
+	a.scratch = (double *)ctx->ws;
+	a.n_rows = (int64_t)rows;
+	a.n_groups = G;
+	a.p = (int)p;
+	a.fit_intercept = o.fit_intercept ? 1 : 0;
+	a.tau = o.tau;
+	a.max_iterations = o.max_iterations > 0x7fffffffu ? 0x7fffffff : (int)o.max_iterations;
+	a.invalid = tau_invalid(o.tau) ? 1 : 0;
+	a.predict_layout = predict_layout;
+	a.core = d_core;
+	a.iterations = d_iterations;
+	const int k = (int)p + a.fit_intercept;
+	const size_t lds = qs_work_doubles(k) * sizeof(double);
+	const int64_t max_blocks = 1 << 20;
+	hipLaunchKernelGGL(quantile_fit_kernel, dim3((unsigned)(G < max_blocks ? G : max_blocks)), dim3(64), lds, ctx->stream, a);
+	return !hip_fail(hipGetLastError(), "quantile_fit_kernel", e);
+}
+
+bool launch_nan_bounds(AnofoxHipContext *ctx, int64_t n_rows, double *d_pred, AnofoxError *e) {
+	if (n_rows == 0) return true;
+	hipLaunchKernelGGL(quantile_nan_bounds_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream, d_pred, n_rows);
+	return !hip_fail(hipGetLastError(), "quantile_nan_bounds_kernel", e);
+}
+
+struct Stage {
+	char *cur;
+	template <class T>
+	T *take(size_t n) {
+		T *p = (T *)cur;
+		cur += align_up(n * sizeof(T) + 16, 256);
+		return p;
+	}
+	static size_t bytes(size_t n, size_t elem) { return align_up(n * elem + 16, 256); }
+};
+
+bool h2d(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *e) {
+	return bytes == 0 || !hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "H2D", e);
+}
+
+bool d2h(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *e) {
+	return bytes == 0 || !hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "D2H", e);
+}
+
+} // namespace
+
+extern "C" {
+
+size_t anofox_hip_quantile_record_len(size_t p) { return p + 6; }
+
+bool anofox_hip_quantile_fit_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                          const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                          AnofoxHipQuantileBatchOptions options, double *d_quantile, int32_t *d_iterations,
+                                          AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_quantile(n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_quantile, out_error)) return false;
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	return launch_quantile(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, nullptr, options, 0, d_quantile, d_iterations,
+	                       out_error);
+}
+
+bool anofox_hip_quantile_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                        const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                        AnofoxHipQuantileBatchOptions options, double *quantile, int32_t *iterations,
+                                        AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_quantile(n_groups, n_features, n_rows, row_offsets, y, x_cols, quantile, out_error)) return false;
+	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (n_groups == 0) return true;
+	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	const size_t p = n_features, rec_len = p + 6;
+	const int64_t slab_rows = 32ll << 20; // the groups pass through the GPU in slabs of at most ~32M rows
+	std::vector<int64_t> off;
+	hipStream_t st = ctx->stream;
+	for (int64_t g0 = 0; g0 < n_groups;) {
+		int64_t g1 = g0 + 1;
+		while (g1 < n_groups && row_offsets[g1 + 1] - row_offsets[g0] <= slab_rows) ++g1;
+		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = row_offsets[g1] - r0;
+		off.resize((size_t)G + 1);
+		for (int64_t g = 0; g <= G; ++g) off[(size_t)g] = row_offsets[g0 + g] - r0;
+		const size_t need = Stage::bytes((size_t)G + 1, 8) + (p + 1) * Stage::bytes((size_t)R, 8) + Stage::bytes((size_t)G * rec_len, 8) +
+		                    Stage::bytes((size_t)G, 4);
+		if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
+		Stage s{(char *)ctx->stage};
+		int64_t *d_off = s.take<int64_t>((size_t)G + 1);
+		if (!h2d(d_off, off.data(), ((size_t)G + 1) * sizeof(int64_t), st, out_error)) return false;
+		const double *d_x[kQsMaxP];
+		for (size_t j = 0; j < p; ++j) {
+			double *c = s.take<double>((size_t)R);
+			if (!h2d(c, x_cols[j] + r0, (size_t)R * sizeof(double), st, out_error)) return false;
+			d_x[j] = c;
+		}
+		double *d_y = s.take<double>((size_t)R);
+		if (!h2d(d_y, y + r0, (size_t)R * sizeof(double), st, out_error)) return false;
+		double *d_rec = s.take<double>((size_t)G * rec_len);
+		int32_t *d_it = iterations ? s.take<int32_t>((size_t)G) : nullptr;
+		if (!launch_quantile(ctx, G, p, R, d_off, d_y, d_x, nullptr, options, 0, d_rec, d_it, out_error)) return false;
+		if (!d2h(quantile + (size_t)g0 * rec_len, d_rec, (size_t)G * rec_len * sizeof(double), st, out_error)) return false;
+		if (d_it && !d2h(iterations + g0, d_it, (size_t)G * sizeof(int32_t), st, out_error)) return false;
+		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
+		g0 = g1;
+	}
+	return true;
+}
+
+bool anofox_hip_quantile_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                  const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                  const int64_t *d_train_counts, AnofoxHipQuantileBatchOptions options, double *d_core,
+                                                  double *d_pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_quantile(n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_core, out_error)) return false;
+	if (n_groups > 0 && !d_pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	if (n_groups == 0) return true;
+	std::lock_guard<std::mutex> lk(ctx->mu); // one lock over fit, predict and the bounds: calls on a context are serialised
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	return launch_quantile(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_train_counts, options, 1, d_core, nullptr, out_error) &&
+	       // the regression predict kernels on the records (sigma = NaN: no interval)
+	       predict_records_locked(ctx, n_groups, n_features, n_rows, d_row_offsets, x_cols, d_core, 0.95, d_pred, out_error) &&
+	       launch_nan_bounds(ctx, n_rows, d_pred, out_error);
+}
+
+bool anofox_hip_quantile_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                const int64_t *train_counts, AnofoxHipQuantileBatchOptions options, double *core,
+                                                double *pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_quantile(n_groups, n_features, n_rows, row_offsets, y, x_cols, core, out_error)) return false;
+	if (n_groups > 0 && !pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
+	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (n_groups == 0) return true;
+	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) {
+		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
+		return false;
+	}
+	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	const size_t p = n_features, core_len = p + 6, G = (size_t)n_groups, N = (size_t)n_rows;
+	std::lock_guard<std::mutex> lk(ctx->mu); // one lock over staging, fit, predict and the copies back
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	const size_t need = Stage::bytes(G + 1, 8) + Stage::bytes(G, 8) + (p + 1) * Stage::bytes(N + 2, 8) + Stage::bytes(G * core_len, 8) +
+	                    Stage::bytes(3 * N, 8);
+	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
+	hipStream_t st = ctx->stream;
+	Stage s{(char *)ctx->stage};
+	int64_t *d_off = s.take<int64_t>(G + 1);
+	int64_t *d_tc = s.take<int64_t>(G);
+	if (!h2d(d_off, row_offsets, (G + 1) * sizeof(int64_t), st, out_error)) return false;
+	if (train_counts && !h2d(d_tc, train_counts, G * sizeof(int64_t), st, out_error)) return false;
+	const double *d_x[kQsMaxP];
+	for (size_t j = 0; j < p; ++j) { // (two doubles of slack: the narrow predict kernel loads rows in pairs)
+		double *c = s.take<double>(N + 2);
+		if (!h2d(c, x_cols[j], N * sizeof(double), st, out_error)) return false;
+		d_x[j] = c;
+	}
+	double *d_y = s.take<double>(N + 2);
+	if (!h2d(d_y, y, N * sizeof(double), st, out_error)) return false;
+	double *d_core = s.take<double>(G * core_len);
+	double *d_pred = s.take<double>(3 * N);
+	if (!launch_quantile(ctx, n_groups, p, n_rows, d_off, d_y, d_x, train_counts ? d_tc : nullptr, options, 1, d_core, nullptr, out_error)) return false;
+	if (!predict_records_locked(ctx, n_groups, p, n_rows, d_off, d_x, d_core, 0.95, d_pred, out_error)) return false;
+	if (!launch_nan_bounds(ctx, n_rows, d_pred, out_error)) return false;
+	if (!d2h(core, d_core, G * core_len * sizeof(double), st, out_error)) return false;
+	if (!d2h(pred, d_pred, 3 * N * sizeof(double), st, out_error)) return false;
+	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
+}
+
+// A batch of one group with anofox_elasticnet_fit's conventions: argument checks first, tau as fit_quantile checks it
+// (quantile.rs:35-40, InvalidValue -> InvalidInput), NULL entries -> NaN through the validity bitmask, a one-row input padded
+// with an all-NaN row, the reference's error texts (crates/anofox-stats-core/src/errors.rs), the coefficients malloc'ed.
+bool anofox_quantile_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxQuantileOptions options,
+                         AnofoxQuantileFitResultCore *out_core, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!out_core) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "out_core is NULL"); return false; }
+	if (!x || x_count == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
+	if (y.len == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Empty input: y cannot be empty"); return false; }
+	if (tau_invalid(options.tau)) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Invalid value for tau: tau must be in (0, 1)"); return false; }
+	for (size_t j = 0; j < x_count; ++j) {
+		if (x[j].len != y.len) {
+			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH,
+			          "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(x[j].len) + " rows");
+			return false;
+		}
+	}
+	const size_t p = x_count, n = y.len;
+	if (p > (size_t)kQsMaxP) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "quantile regression: n_features > 32 is not built"); return false; }
+	const size_t n_pad = n < 2 ? 2 : n;
+	auto expand = [](const AnofoxDataArray &a, std::vector<double> &out, size_t len) {
+		out.assign(len, NAN);
+		for (size_t i = 0; i < a.len; ++i) {
+			const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
+			out[i] = valid ? a.data[i] : NAN;
+		}
+	};
+	std::vector<std::vector<double>> cols(p);
+	std::vector<double> yv;
+	expand(y, yv, n_pad);
+	std::vector<const double *> xp(p);
+	for (size_t j = 0; j < p; ++j) { expand(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
+	AnofoxHipQuantileBatchOptions o;
+	memset(&o, 0, sizeof o);
+	o.tau = options.tau;
+	o.fit_intercept = options.fit_intercept;
+	o.max_iterations = options.max_iterations;
+	o.tolerance = options.tolerance;
+	const int64_t off[2] = {0, (int64_t)n_pad};
+	std::vector<double> rec(p + 6);
+	if (!anofox_hip_quantile_fit_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), o, rec.data(), nullptr, out_error)) return false;
+	const int status = (int)rec[p + 5];
+	if (status != ANOFOX_ERROR_SUCCESS) {
+		size_t n_valid = 0;
+		for (size_t i = 0; i < n; ++i) {
+			bool ok = isfinite(yv[i]);
+			for (size_t j = 0; ok && j < p; ++j) ok = isfinite(cols[j][i]);
+			n_valid += ok;
+		}
+		std::string msg;
+		switch (status) { // crates/anofox-stats-core/src/errors.rs
+		case ANOFOX_ERROR_NO_VALID_DATA: msg = "All rows filtered due to NULL/NaN values"; break;
+		case ANOFOX_ERROR_INSUFFICIENT_DATA:
+			msg = "Insufficient data: " + std::to_string(n_valid) + " rows, " + std::to_string(p) + " features (need rows > features)";
+			break;
+		default: msg = "Quantile fit failed on the GPU path"; break;
+		}
+		set_error(out_error, status == ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS ? ANOFOX_ERROR_INSUFFICIENT_DATA : (AnofoxErrorCode)status, msg);
+		return false;
+	}
+	double *coef = (double *)malloc(p * sizeof(double));
+	if (!coef) { set_error(out_error, ANOFOX_ERROR_ALLOCATION_FAILURE, "Failed to allocate coefficients"); return false; }
+	memcpy(coef, rec.data(), p * sizeof(double));
+	out_core->coefficients = coef;
+	out_core->coefficients_len = p;
+	out_core->intercept = rec[p];
+	out_core->tau = rec[p + 1];
+	out_core->n_observations = (size_t)rec[p + 4];
+	out_core->n_features = p;
+	return true;
+}
+
+void anofox_free_quantile_result(AnofoxQuantileFitResultCore *result) {
+	if (!result) return;
+	free(result->coefficients);
+	result->coefficients = nullptr;
+	result->coefficients_len = 0;
+}
+
+} // extern "C"

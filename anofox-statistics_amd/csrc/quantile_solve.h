@@ -1,0 +1,492 @@
+// quantile_solve.h — the quantile regression fit of one group of rows: the exact vertex of the linear program
+//     minimise  sum_i rho_tau(y_i - a_i'beta),   rho_tau(r) = r (tau - [r < 0]),   a_i = (1, x_i) or x_i,  k = p + [intercept]
+// by the Barrodale-Roberts / Koenker-d'Orey simplex over the rows.  DESIGN.md §1, "Quantile regression".
+//
+// One source for both builds: under hipcc the functions are device code run by ONE WAVEFRONT (64 lanes, rows strided over
+// the lanes, one lane per basis direction, the small matrices in LDS); under a plain C++ compiler the same text runs with
+// one "lane" (tests/tools/quantile_solve_host.cpp), which is where the algorithm is debugged.
+//
+// Basis: k elements, element j either a row whose residual is held at zero or the artificial "beta_j = 0".  It starts
+// with all k artificials (B^-1 = I, beta = 0).  Column j of B^-1 is the edge d_j: moving along it changes only element j.
+//   optimality  s = sum over the non-basis rows with r != 0 of psi(r_i) a_i (psi = tau for r > 0, tau - 1 for r < 0),
+//               u = B^-T s.  The one-sided derivatives along +d_j / -d_j are
+//                   g+_j = -u_j + (1 - tau) [row]  + sum over non-basis rows with r = 0 of (z > 0 ? (1 - tau) z : tau |z|)
+//                   g-_j = +u_j + tau [row]        + sum over non-basis rows with r = 0 of (z > 0 ? tau z : (1 - tau) |z|)
+//               (z = a_i'd_j), i.e. a row element needs -tau <= u_j <= 1 - tau, an artificial u_j = 0.  An edge is violated
+//               when g < -kQsDualTol * sum_c (sum_i |a_ic|) |d_jc| (the size u_j could have).
+//   pivot       leave along the most violated edge (the lowest violated one once a step has stalled: Bland); z_i = a_i'd;
+//               breakpoints t_i = r_i / z_i > 0 with weights |z_i|; the entering row is the weighted quantile where the
+//               derivative turns non-negative: the smallest t with sum_{t_i <= t} |z_i| >= -g, found by bisection over the
+//               bit pattern of the positive double t (one reduction per bit), ties to the lowest row.  B^-1 by the rank-one
+//               formula, r_i -= t z_i, the entering row's residual exactly 0; |r| <= kQsSnapTol max|y| is snapped to 0.
+//   finish      when no edge is violated: B is rebuilt from the basis rows, factorised by LU with partial pivoting, beta and a
+//               fresh B^-1 come from that factorisation, the residuals from the rows, and the optimality test runs again;
+//               if it fails the pivots go on (at most kQsMaxRestarts times).
+// Pivots are bounded by min(max_iterations, qs_iteration_ceiling(k)); when the bound stops a fit the last vertex is
+// returned (status 0) and the pivot count is reported negated.  No atomics, a fixed order of every sum: two calls give the
+// same bytes.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define QS_DEV __device__ inline
+#define QS_LANES 64
+#else
+#define QS_DEV inline
+#define QS_LANES 1
+#endif
+
+namespace anofox {
+namespace quantile {
+
+constexpr int kQsMaxP = 32;           // features at most (k <= 33)
+constexpr double kQsDualTol = 1e-10;  // a derivative below this share of its scale counts as zero
+constexpr double kQsPivotTol = 1e-11; // |z_i| below this share of sum_c max_i|a_ic| |d_c| is no breakpoint
+constexpr double kQsSnapTol = 1e-12;  // |r_i| <= this share of max|y| is a zero residual
+constexpr double kQsStallTol = 1e-14; // a step that lowers the loss by less than this share of max|y|: Bland's rule from here on
+constexpr int kQsMaxRestarts = 3;     // failed optimality tests after a refactorisation that may resume the pivots
+
+constexpr int kQsStatusInvalidInput = 1;
+constexpr int kQsStatusInsufficientData = 6;
+constexpr int kQsStatusNoValidData = 10;
+constexpr int kQsStatusTooFewRows = 100;
+
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int qs_iteration_ceiling(int k) { return 1000 + 50 * k; }
+
+// doubles of work memory (LDS on the device) for k basis elements
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline size_t qs_work_doubles(int k) { return 2 * (size_t)k * (size_t)(k | 1) + 12 * (size_t)k; }
+
+struct QsProblem {
+	const double *y;
+	const double *const *x; // p column pointers
+	int p;
+	int fit_intercept;
+	int64_t lo, hi;     // rows [lo, hi) of the columns
+	int64_t rule_count; // what the "fewer than 2 rows" rule looks at
+	double tau;
+	int max_iterations;
+	int predict_layout; // 0: {b, intercept, tau, loss, n_basis_rows, n, status}; 1: {b, intercept, NaN, NaN, NaN, n, status}
+	double *r, *z, *t;  // scratch, one double per row each, indexed by the row number
+};
+
+// ---- the lanes of the wavefront (one lane in the host build) ----
+#if defined(__HIPCC__)
+QS_DEV int qs_lane() { return (int)(threadIdx.x & 63u); }
+QS_DEV void qs_sync() { __syncthreads(); } // one wavefront per workgroup: orders its LDS traffic
+QS_DEV double qs_sum(double v) {
+	for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+	return v;
+}
+QS_DEV double qs_max(double v) {
+	for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
+	return v;
+}
+QS_DEV int64_t qs_sum_i(int64_t v) {
+	for (int m = 32; m >= 1; m >>= 1) v += (int64_t)__shfl_xor((long long)v, m, 64);
+	return v;
+}
+QS_DEV int64_t qs_min_i(int64_t v) {
+	for (int m = 32; m >= 1; m >>= 1) {
+		const int64_t o = (int64_t)__shfl_xor((long long)v, m, 64);
+		v = o < v ? o : v;
+	}
+	return v;
+}
+QS_DEV uint64_t qs_min_u(uint64_t v) {
+	for (int m = 32; m >= 1; m >>= 1) {
+		const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, m, 64);
+		v = o < v ? o : v;
+	}
+	return v;
+}
+QS_DEV uint64_t qs_max_u(uint64_t v) {
+	for (int m = 32; m >= 1; m >>= 1) {
+		const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, m, 64);
+		v = o > v ? o : v;
+	}
+	return v;
+}
+// the largest v and its index, the lowest index on ties; j < 0 = no candidate on this lane
+QS_DEV void qs_argmax(double &v, int &j) {
+	for (int m = 32; m >= 1; m >>= 1) {
+		const double ov = __shfl_xor(v, m, 64);
+		const int oj = __shfl_xor(j, m, 64);
+		if (oj >= 0 && (j < 0 || ov > v || (ov == v && oj < j))) { v = ov; j = oj; }
+	}
+}
+QS_DEV uint64_t qs_ballot(bool b) { return (uint64_t)__ballot(b); }
+#else
+QS_DEV int qs_lane() { return 0; }
+QS_DEV void qs_sync() {}
+QS_DEV double qs_sum(double v) { return v; }
+QS_DEV double qs_max(double v) { return v; }
+QS_DEV int64_t qs_sum_i(int64_t v) { return v; }
+QS_DEV int64_t qs_min_i(int64_t v) { return v; }
+QS_DEV uint64_t qs_min_u(uint64_t v) { return v; }
+QS_DEV uint64_t qs_max_u(uint64_t v) { return v; }
+QS_DEV void qs_argmax(double &, int &) {}
+QS_DEV uint64_t qs_ballot(bool b) { return b ? 1ull : 0ull; }
+#endif
+
+QS_DEV uint64_t qs_bits(double v) {
+	uint64_t b;
+	memcpy(&b, &v, sizeof b);
+	return b;
+}
+QS_DEV double qs_from_bits(uint64_t b) {
+	double v;
+	memcpy(&v, &b, sizeof v);
+	return v;
+}
+
+// element c of a_i
+QS_DEV double qs_elem(const QsProblem &P, int c, int64_t i) {
+	if (P.fit_intercept) return c == 0 ? 1.0 : P.x[c - 1][i];
+	return P.x[c][i];
+}
+
+QS_DEV bool qs_in_basis(const int64_t *basis, int k, int64_t i) {
+	for (int j = 0; j < k; ++j)
+		if (basis[j] == i) return true;
+	return false;
+}
+
+QS_DEV void qs_fail_record(double *rec, int p, int status, int32_t *iterations) {
+	if (qs_lane() != 0) return;
+	for (int j = 0; j < p + 5; ++j) rec[j] = NAN;
+	rec[p + 5] = (double)status;
+	if (iterations) *iterations = 0;
+}
+
+// B from the basis, P B = L U with partial pivoting, beta = B^-1 v and a fresh B^-1 from the factors, the residuals of all
+// rows from beta.  false: B is singular to working precision (a zero pivot).
+QS_DEV bool qs_refactor(const QsProblem &P, int k, int ld, double *M, double *Binv, double *beta, double *v, const int64_t *basis,
+                        int64_t *perm, double snap) {
+	const int lane = qs_lane();
+	for (int r = lane; r < k; r += QS_LANES) {
+		const int64_t b = basis[r];
+		for (int c = 0; c < k; ++c) M[r * ld + c] = b >= 0 ? qs_elem(P, c, b) : (c == r ? 1.0 : 0.0);
+		v[r] = b >= 0 ? P.y[b] : 0.0;
+		perm[r] = r;
+	}
+	qs_sync();
+	for (int c = 0; c < k; ++c) {
+		double best = -1.0;
+		int br = -1;
+		for (int r = c + lane; r < k; r += QS_LANES) {
+			const double a = fabs(M[r * ld + c]);
+			if (a > best) { best = a; br = r; }
+		}
+		qs_argmax(best, br);
+		if (br < 0 || !(best > 0.0)) return false; // (the same on every lane)
+		qs_sync();
+		if (br != c) {
+			for (int cc = lane; cc < k; cc += QS_LANES) {
+				const double tmp = M[c * ld + cc];
+				M[c * ld + cc] = M[br * ld + cc];
+				M[br * ld + cc] = tmp;
+			}
+			if (lane == 0) {
+				const double tv = v[c];
+				v[c] = v[br];
+				v[br] = tv;
+				const int64_t tp = perm[c];
+				perm[c] = perm[br];
+				perm[br] = tp;
+			}
+		}
+		qs_sync();
+		const double piv = M[c * ld + c];
+		for (int r = c + 1 + lane; r < k; r += QS_LANES) {
+			const double f = M[r * ld + c] / piv;
+			M[r * ld + c] = f;
+			for (int cc = c + 1; cc < k; ++cc) M[r * ld + cc] -= f * M[c * ld + cc];
+		}
+		qs_sync();
+	}
+	// lane j solves for column j of B^-1 (right-hand side P e_j); j == k: beta (right-hand side P v)
+	for (int j = lane; j <= k; j += QS_LANES) {
+		double *out = j < k ? Binv + j * ld : beta;
+		for (int r = 0; r < k; ++r) {
+			double acc = j < k ? (perm[r] == j ? 1.0 : 0.0) : v[r];
+			for (int c = 0; c < r; ++c) acc -= M[r * ld + c] * out[c];
+			out[r] = acc;
+		}
+		for (int r = k - 1; r >= 0; --r) {
+			double acc = out[r];
+			for (int c = r + 1; c < k; ++c) acc -= M[r * ld + c] * out[c];
+			out[r] = acc / M[r * ld + r];
+		}
+	}
+	qs_sync();
+	for (int j = lane; j < k; j += QS_LANES)
+		if (basis[j] < 0) beta[j] = 0.0; // an artificial pins its coefficient: exactly 0
+	qs_sync();
+	for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+		if (!(P.r[i] == P.r[i])) continue; // masked at the first pass
+		double fit = 0.0;
+		for (int c = 0; c < k; ++c) fit += qs_elem(P, c, i) * beta[c];
+		double rr = P.y[i] - fit;
+		if (fabs(rr) <= snap || qs_in_basis(basis, k, i)) rr = 0.0;
+		P.r[i] = rr;
+	}
+	return true;
+}
+
+// The fit of one group.  `work`: qs_work_doubles(k) doubles (LDS); rec: p + 6 doubles, written by lane 0; *iterations
+// (optional): the pivots, negated when the bound stopped the fit.  `invalid`: tau is unusable (status 1).
+QS_DEV void qs_fit(const QsProblem &P, bool invalid, double *work, double *rec, int32_t *iterations) {
+	const int lane = qs_lane();
+	const int p = P.p, k = p + (P.fit_intercept ? 1 : 0), ld = k | 1;
+	const double tau = P.tau;
+	if (invalid) { qs_fail_record(rec, p, kQsStatusInvalidInput, iterations); return; }
+	if (P.rule_count < 2) { qs_fail_record(rec, p, kQsStatusTooFewRows, iterations); return; }
+	// ---- first pass: the row mask, r = y (beta = 0), max|y| ----
+	int64_t n_valid = 0;
+	double ymax = 0.0;
+	for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+		const double yv = P.y[i];
+		bool ok = isfinite(yv);
+		for (int j = 0; j < p; ++j) ok = ok && isfinite(P.x[j][i]);
+		P.r[i] = ok ? yv : NAN;
+		P.z[i] = 0.0;      // a masked row is never a breakpoint: the line search reads these slots of EVERY row, and the
+		P.t[i] = INFINITY; // scratch arrives with whatever an earlier call left in it
+		if (ok) {
+			++n_valid;
+			ymax = fmax(ymax, fabs(yv));
+		}
+	}
+	n_valid = qs_sum_i(n_valid);
+	ymax = qs_max(ymax);
+	if (n_valid == 0) { qs_fail_record(rec, p, kQsStatusNoValidData, iterations); return; }
+	if (n_valid < k) { qs_fail_record(rec, p, kQsStatusInsufficientData, iterations); return; }
+	const double snap = kQsSnapTol * ymax;
+
+	double *Binv = work, *M = Binv + (size_t)k * ld;
+	double *s = M + (size_t)k * ld, *dvec = s + k, *beta = dvec + k, *v = beta + k, *amax = v + k, *asum = amax + k;
+	double *wrow = asum + k, *gp = wrow + k, *gm = gp + k, *thr = gm + k;
+	int64_t *basis = reinterpret_cast<int64_t *>(thr + k), *perm = basis + k;
+
+	// column sizes: max_i |a_ic| and sum_i |a_ic| over the valid rows
+	for (int c = 0; c < k; ++c) {
+		double mx = 0.0, sm = 0.0;
+		for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+			if (!(P.r[i] == P.r[i])) continue;
+			const double a = fabs(qs_elem(P, c, i));
+			mx = fmax(mx, a);
+			sm += a;
+		}
+		mx = qs_max(mx);
+		sm = qs_sum(sm);
+		if (lane == 0) { amax[c] = mx; asum[c] = sm; }
+	}
+	for (int j = lane; j < k; j += QS_LANES) {
+		for (int c = 0; c < k; ++c) Binv[j * ld + c] = c == j ? 1.0 : 0.0;
+		basis[j] = -1 - (int64_t)j;
+		beta[j] = 0.0;
+	}
+	qs_sync();
+	// rows that are zero from the start (y_i = 0) are snapped like every later residual
+	for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES)
+		if (fabs(P.r[i]) <= snap) P.r[i] = 0.0;
+
+	const int ceiling = qs_iteration_ceiling(k);
+	const int max_it = P.max_iterations < ceiling ? P.max_iterations : ceiling;
+	int pivots = 0, restarts = 0;
+	bool fresh = false, converged = false, bland = false, singular = false;
+	uint64_t blocked = 0; // edges whose line search found no breakpoint since the last pivot
+
+	for (;;) {
+		// ---- s over the non-basis rows off their kink (basis rows have r = 0) ----
+		for (int c = 0; c < k; ++c) {
+			double acc = 0.0;
+			for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+				const double ri = P.r[i];
+				if (ri > 0.0) acc += tau * qs_elem(P, c, i);
+				else if (ri < 0.0) acc += (tau - 1.0) * qs_elem(P, c, i);
+			}
+			acc = qs_sum(acc);
+			if (lane == 0) s[c] = acc;
+		}
+		qs_sync();
+		// ---- the one-sided derivatives of every edge ----
+		for (int j = lane; j < k; j += QS_LANES) {
+			double u = 0.0, sc = 0.0;
+			for (int c = 0; c < k; ++c) {
+				const double d = Binv[j * ld + c];
+				u += s[c] * d;
+				sc += asum[c] * fabs(d);
+			}
+			const bool row = basis[j] >= 0;
+			gp[j] = -u + (row ? 1.0 - tau : 0.0);
+			gm[j] = u + (row ? tau : 0.0);
+			thr[j] = kQsDualTol * sc;
+		}
+		for (int64_t c0 = P.lo; c0 < P.hi; c0 += QS_LANES) { // non-basis rows on their kink: each side pays its own slope
+			const int64_t i = c0 + lane;
+			uint64_t m = qs_ballot(i < P.hi && P.r[i] == 0.0 && !qs_in_basis(basis, k, i));
+			while (m) {
+				const int bit = __builtin_ctzll(m);
+				m &= m - 1;
+				const int64_t ii = c0 + bit;
+				for (int j = lane; j < k; j += QS_LANES) {
+					double zz = 0.0;
+					for (int c = 0; c < k; ++c) zz += qs_elem(P, c, ii) * Binv[j * ld + c];
+					if (zz > 0.0) { gp[j] += (1.0 - tau) * zz; gm[j] += tau * zz; }
+					else { gp[j] -= tau * zz; gm[j] -= (1.0 - tau) * zz; }
+				}
+			}
+		}
+		// ---- the leaving edge ----
+		double bestv = -1.0;
+		int bj = -1;
+		for (int j = lane; j < k; j += QS_LANES) {
+			if ((blocked >> j) & 1ull) continue;
+			const double g = gp[j] < gm[j] ? gp[j] : gm[j];
+			if (g < -thr[j]) {
+				const double val = bland ? (double)(k - j) : -g;
+				if (bj < 0 || val > bestv) { bestv = val; bj = j; }
+			}
+		}
+		qs_argmax(bestv, bj);
+		qs_sync(); // (gp / gm / thr are read below by every lane)
+		if (bj < 0) {
+			if (fresh) { converged = true; break; }
+			if (!qs_refactor(P, k, ld, M, Binv, beta, v, basis, perm, snap)) { singular = true; break; }
+			fresh = true;
+			blocked = 0;
+			continue;
+		}
+		if (pivots >= max_it || (fresh && restarts >= kQsMaxRestarts)) {
+			if (!fresh && !qs_refactor(P, k, ld, M, Binv, beta, v, basis, perm, snap)) singular = true;
+			break;
+		}
+		if (fresh) ++restarts;
+		const double sigma = gp[bj] < gm[bj] ? 1.0 : -1.0;
+		const double need = -(gp[bj] < gm[bj] ? gp[bj] : gm[bj]);
+		const int64_t leaving = basis[bj];
+		for (int c = lane; c < k; c += QS_LANES) dvec[c] = sigma * Binv[bj * ld + c];
+		qs_sync();
+		double zscale = 0.0;
+		for (int c = 0; c < k; ++c) zscale += amax[c] * fabs(dvec[c]);
+		const double ztol = kQsPivotTol * zscale;
+		// ---- z, the breakpoints, their range ----
+		uint64_t tmin = ~0ull, tmax = 0ull;
+		double wall = 0.0;
+		for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+			const double ri = P.r[i];
+			if (!(ri == ri)) continue;
+			double zi = 0.0;
+			for (int c = 0; c < k; ++c) zi += qs_elem(P, c, i) * dvec[c];
+			if (ri == 0.0 && i != leaving && qs_in_basis(basis, k, i)) zi = 0.0; // the other basis rows stay on their kink
+			double ti = INFINITY;
+			if (ri != 0.0 && fabs(zi) > ztol && (ri > 0.0) == (zi > 0.0)) ti = ri / zi;
+			if (!(ti > 0.0)) ti = INFINITY;
+			P.z[i] = zi;
+			P.t[i] = ti;
+			if (ti < INFINITY) {
+				const uint64_t tb = qs_bits(ti);
+				tmin = tb < tmin ? tb : tmin;
+				tmax = tb > tmax ? tb : tmax;
+				wall += fabs(zi);
+			}
+		}
+		tmin = qs_min_u(tmin);
+		tmax = qs_max_u(tmax);
+		wall = qs_sum(wall);
+		if (tmax == 0ull || !(wall >= need)) { // no breakpoint turns the derivative: rounding in g; the edge rests until a pivot
+			blocked |= 1ull << bj;
+			continue;
+		}
+		// ---- the weighted quantile of the breakpoints, by bisection over the bits of t ----
+		uint64_t blo = tmin - 1, bhi = tmax; // W(blo) = 0 < need <= W(bhi)
+		while (bhi - blo > 1) {
+			const uint64_t mid = blo + (bhi - blo) / 2;
+			double wsum = 0.0;
+			for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+				const double ti = P.t[i]; // (+inf for masked rows, set at the first pass)
+				if (ti < INFINITY && qs_bits(ti) <= mid) wsum += fabs(P.z[i]);
+			}
+			wsum = qs_sum(wsum);
+			if (wsum >= need) bhi = mid;
+			else blo = mid;
+		}
+		int64_t enter = INT64_MAX;
+		for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+			const double ti = P.t[i];
+			if (ti < INFINITY && qs_bits(ti) == bhi && i < enter) enter = i;
+		}
+		enter = qs_min_i(enter);
+		if (enter == INT64_MAX) { // (cannot happen: bhi is a breakpoint) — rest the edge rather than loop
+			blocked |= 1ull << bj;
+			continue;
+		}
+		const double tstar = qs_from_bits(bhi);
+		if (tstar * need <= kQsStallTol * ymax) bland = true;
+		// ---- the step ----
+		for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+			const double ri = P.r[i];
+			if (!(ri == ri)) continue;
+			const double zi = P.z[i];
+			double rn = zi != 0.0 ? ri - tstar * zi : ri;
+			if (fabs(rn) <= snap) rn = 0.0;
+			if (i == enter) rn = 0.0;
+			P.r[i] = rn;
+		}
+		// ---- B^-1: row `enter` replaces element bj ----
+		for (int l = lane; l < k; l += QS_LANES) {
+			double acc = 0.0;
+			for (int c = 0; c < k; ++c) acc += qs_elem(P, c, enter) * Binv[l * ld + c];
+			wrow[l] = acc;
+		}
+		qs_sync();
+		const double wj = wrow[bj];
+		qs_sync();
+		for (int c = lane; c < k; c += QS_LANES) Binv[bj * ld + c] /= wj;
+		qs_sync();
+		for (int l = lane; l < k; l += QS_LANES) {
+			if (l == bj) continue;
+			const double wl = wrow[l];
+			for (int c = 0; c < k; ++c) Binv[l * ld + c] -= wl * Binv[bj * ld + c];
+		}
+		if (lane == 0) basis[bj] = enter;
+		qs_sync();
+		++pivots;
+		fresh = false;
+		blocked = 0;
+	}
+	if (singular) { qs_fail_record(rec, p, 2 /* ANOFOX_ERROR_SINGULAR_MATRIX */, iterations); return; }
+	// ---- the record: coefficients of the refactorised basis, the loss from the rows ----
+	double loss = 0.0;
+	for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+		const double ri = P.r[i];
+		if (ri > 0.0) loss += tau * ri;
+		else if (ri < 0.0) loss += (tau - 1.0) * ri;
+	}
+	loss = qs_sum(loss);
+	if (lane == 0) {
+		const int ic = P.fit_intercept ? 1 : 0;
+		int n_rows_in = 0;
+		for (int j = 0; j < k; ++j) n_rows_in += basis[j] >= 0 ? 1 : 0;
+		for (int j = 0; j < p; ++j) rec[j] = beta[ic + j];
+		rec[p] = ic ? beta[0] : NAN;
+		rec[p + 1] = P.predict_layout ? NAN : tau;
+		rec[p + 2] = P.predict_layout ? NAN : loss;
+		rec[p + 3] = P.predict_layout ? NAN : (double)n_rows_in;
+		rec[p + 4] = (double)n_valid;
+		rec[p + 5] = 0.0;
+		if (iterations) *iterations = converged ? pivots : -pivots;
+	}
+}
+
+} // namespace quantile
+} // namespace anofox

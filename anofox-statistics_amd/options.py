@@ -334,6 +334,54 @@ def parse_bls_predict_options(opts: Optional[Mapping[str, Any]]) -> BlsOptions:
 
 
 @dataclass
+class QuantileOptions:
+    """Resolved options of quantile regression (defaults = the bind data of quantile_fit_predict_aggregate.cpp:54-57 and the
+    reference's QuantileOptions: tau 0.5, an intercept, 1000 iterations, tolerance 1e-6 — accepted and unused, the fit is the
+    exact vertex)."""
+    tau: float = 0.5
+    fit_intercept: bool = True
+    max_iterations: int = 1000
+    tolerance: float = 1e-6
+    null_policy: str = "drop"
+
+    def batch_options(self) -> _abi.AnofoxHipQuantileBatchOptions:
+        return _abi.AnofoxHipQuantileBatchOptions(self.tau, self.fit_intercept, self.max_iterations, self.tolerance)
+
+    def ffi_options(self) -> _abi.AnofoxQuantileOptions:
+        return _abi.AnofoxQuantileOptions(self.tau, self.fit_intercept, self.max_iterations, self.tolerance)
+
+
+def parse_quantile_options(opts: Optional[Mapping[str, Any]]) -> QuantileOptions:
+    """anofox_stats_quantile_fit_predict_agg's MAP options (quantile_fit_predict_aggregate.cpp): tau, fit_intercept /
+    intercept; max_iterations / max_iter and tolerance / tol as the scalar function's.  Keys are case-insensitive; other keys
+    are ignored.  tau is not range-checked here: the fit reports it (status 1 / InvalidInput)."""
+    out = QuantileOptions()
+    if opts is None:
+        return out
+    if not isinstance(opts, Mapping):
+        raise InvalidInputException("Options parameter must be a constant expression")
+    for raw_key, val in opts.items():
+        key = str(raw_key).lower()
+        if key == "tau":
+            v = _extract_double(val)
+            if v is not None:
+                out.tau = v
+        elif key in ("intercept", "fit_intercept"):
+            v = _extract_bool(val)
+            if v is not None:
+                out.fit_intercept = v
+        elif key in ("max_iterations", "max_iter"):
+            v = _extract_uint32(val)
+            if v is not None:
+                out.max_iterations = v
+        elif key in ("tolerance", "tol"):
+            v = _extract_double(val)
+            if v is not None:
+                out.tolerance = v
+    return out
+
+
+@dataclass
 class RlsOptions:
     """Resolved options of recursive least squares (defaults = the reference's RlsOptions and the bind data of
     rls_aggregate.cpp / rls_predict_aggregate.cpp / rls_fit_predict.cpp)."""

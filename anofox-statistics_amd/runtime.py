@@ -293,6 +293,43 @@ class Context:
     def bls_fit_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipBlsBatchOptions):
         return bls_fit_batch_host(row_offsets, y, x_cols, options, ctx=self)
 
+    def quantile_fit_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions,
+                                  records=None, iterations=None, use_current_torch_stream: bool = True):
+        """Grouped quantile regression on CUDA tensors (row_offsets int64[G+1], y / x_cols[j] float64[N]).  Asynchronous.
+        Returns (quantile[G, p+6], iterations int32[G]) CUDA tensors."""
+        import torch
+
+        p = len(x_cols)
+        G = int(row_offsets.numel()) - 1
+        N = int(y.numel())
+        for t in (row_offsets, y, *x_cols):
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("device batch needs contiguous CUDA tensors")
+        if row_offsets.dtype != torch.int64 or y.dtype != torch.float64 or any(c.dtype != torch.float64 for c in x_cols):
+            raise ValueError("row_offsets must be int64 and data float64")
+        if any(int(c.numel()) != N for c in x_cols):
+            raise ValueError("every column must have y's length")
+        if records is None:
+            records = torch.empty((G, p + 6), dtype=torch.float64, device=y.device)
+        if iterations is None:
+            iterations = torch.empty((G,), dtype=torch.int32, device=y.device)
+        if use_current_torch_stream:
+            self.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
+        cols = (C.c_void_p * max(p, 1))(*[c.data_ptr() for c in x_cols])
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_quantile_fit_batch_device(
+            self._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols, options,
+            C.c_void_p(records.data_ptr()), C.c_void_p(iterations.data_ptr()), C.byref(err))
+        self._check(ok, err)
+        return records, iterations
+
+    def quantile_fit_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions):
+        return quantile_fit_batch_host(row_offsets, y, x_cols, options, ctx=self)
+
+    def quantile_fit_predict_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions,
+                                        train_counts=None):
+        return quantile_fit_predict_batch_host(row_offsets, y, x_cols, options, train_counts, ctx=self)
+
     def bls_fit_predict_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipBlsBatchOptions,
                                    confidence_level: float = 0.95, train_counts=None):
         return bls_fit_predict_batch_host(row_offsets, y, x_cols, options, confidence_level, train_counts, ctx=self)
@@ -802,6 +839,53 @@ def bls_fit_predict_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.A
         ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP), colp,
         None if tc is None else tc.ctypes.data_as(C.POINTER(C.c_int64)), options, float(confidence_level),
         core.ctypes.data_as(_DP), pred.ctypes.data_as(_DP), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return core, pred
+
+
+def quantile_fit_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions, ctx: Optional[Context] = None):
+    """Grouped quantile regression, numpy in / out: (quantile[G, p+6], iterations int32[G]); the record layout is
+    anofox_hip_quantile_fit_batch_host's (include/anofox_stats_hip.h)."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    p, G, N = len(cols), len(off) - 1, len(yv)
+    if any(len(c) != N for c in cols):
+        raise ValueError("every column must have y's length")
+    rec = np.empty((G, p + 6), dtype=np.float64)
+    its = np.empty((max(G, 0),), dtype=np.int32)
+    colp = (_DP * max(p, 1))(*[c.ctypes.data_as(_DP) for c in cols])
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_quantile_fit_batch_host(
+        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP),
+        colp, options, rec.ctypes.data_as(_DP), its.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return rec, its
+
+
+def quantile_fit_predict_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions,
+                                    train_counts=None, ctx: Optional[Context] = None):
+    """Quantile regression fit + predict, numpy in / out: (core[G, p+6] = coefficients, intercept, NaN, NaN, NaN, n, status;
+    pred[N, 3] = yhat, NaN, NaN; a NaN yhat = NULL)."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    tc = None if train_counts is None else np.ascontiguousarray(train_counts, dtype=np.int64)
+    p, G, N = len(cols), len(off) - 1, len(yv)
+    if any(len(c) != N for c in cols):
+        raise ValueError("every column must have y's length")
+    core = np.empty((G, p + 6), dtype=np.float64)
+    pred = np.empty((N, 3), dtype=np.float64)
+    colp = (_DP * max(p, 1))(*[c.ctypes.data_as(_DP) for c in cols])
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_quantile_fit_predict_batch_host(
+        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP), colp,
+        None if tc is None else tc.ctypes.data_as(C.POINTER(C.c_int64)), options, core.ctypes.data_as(_DP),
+        pred.ctypes.data_as(_DP), C.byref(err))
     if not ok:
         raise AnofoxStatsError(err.code, err.text())
     return core, pred

@@ -161,6 +161,33 @@ def rls_fit(y, x, options=None) -> dict:
         lib.anofox_free_result_core(C.byref(core))
 
 
+def quantile_fit(y, x, options=None) -> dict:
+    """anofox_stats_quantile_fit([y...], [[x1...], ...], {...}) through anofox_quantile_fit: coefficients, intercept, tau,
+    n_observations, n_features."""
+    from .options import parse_quantile_options
+    lib = _abi.load()
+    o = parse_quantile_options(options)
+    ya, k0 = _data_array(y)
+    xs = (_abi.AnofoxDataArray * max(len(x), 1))()
+    keep = [k0]
+    for j, col in enumerate(x):
+        a, k = _data_array(col)
+        xs[j] = a
+        keep.append(k)
+    core = _abi.AnofoxQuantileFitResultCore()
+    err = _abi.AnofoxError()
+    if not lib.anofox_quantile_fit(ya, xs, len(x), o.ffi_options(), C.byref(core), C.byref(err)):
+        e = InvalidInputException(f"Quantile fit failed: {err.text()}")
+        e.code = err.code
+        raise e
+    try:
+        p = core.coefficients_len
+        return {"coefficients": [core.coefficients[i] for i in range(p)], "intercept": core.intercept, "tau": core.tau,
+                "n_observations": core.n_observations, "n_features": core.n_features}
+    finally:
+        lib.anofox_free_quantile_result(C.byref(core))
+
+
 def aic(rss: float, n: int, k: int) -> Optional[float]:
     """aic(rss, n, k) scalar function (src/scalar_functions/aic_bic.cpp:12-60): NULL (None) on error."""
     lib = _abi.load()

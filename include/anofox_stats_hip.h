@@ -300,6 +300,35 @@ ANOFOX_HIP_API bool anofox_nnls_fit(AnofoxDataArray y, const AnofoxDataArray *x,
                      AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_bls_result(AnofoxBlsFitResultCore *result);
 
+/* replaces AnofoxQuantileOptions, anofox_stats_ffi.h:1371-1380 — 24 bytes: tau @0, fit_intercept @8, max_iterations @12,
+ * tolerance @16 */
+typedef struct {
+	double tau;              /* the quantile, in (0, 1) */
+	bool fit_intercept;
+	uint32_t max_iterations; /* simplex pivots at most */
+	double tolerance;        /* accepted and unused: the result is the exact vertex */
+} AnofoxQuantileOptions;
+
+/* replaces AnofoxQuantileFitResultCore, anofox_stats_ffi.h:1385-1398 — 48 bytes: coefficients @0, coefficients_len @8,
+ * intercept @16, tau @24, n_observations @32, n_features @40 */
+typedef struct {
+	double *coefficients;
+	size_t coefficients_len;
+	double intercept; /* NaN without an intercept */
+	double tau;
+	size_t n_observations;
+	size_t n_features;
+} AnofoxQuantileFitResultCore;
+
+/* replace anofox_quantile_fit / anofox_free_quantile_result, anofox_stats_ffi.h:1411-1417 (over
+ * crates/anofox-stats-core/src/models/quantile.rs): one group through anofox_hip_quantile_fit_batch_host, with
+ * anofox_elasticnet_fit's conventions.  tau outside (0, 1) or NaN: false with ANOFOX_ERROR_INVALID_INPUT.  The minimiser and
+ * the statuses: DESIGN.md §1 "Quantile regression" (fit_intercept = false really fits without an intercept).  The
+ * coefficients are malloc'ed; anofox_free_quantile_result frees and nulls them (NULL-safe). */
+ANOFOX_HIP_API bool anofox_quantile_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxQuantileOptions options,
+                         AnofoxQuantileFitResultCore *out_core, AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_quantile_result(AnofoxQuantileFitResultCore *result);
+
 #endif /* ANOFOX_STATS_FFI_H */
 
 /* ------------------------------------------------------------------------ */
@@ -489,6 +518,55 @@ ANOFOX_HIP_API bool anofox_hip_bls_fit_predict_batch_host(AnofoxHipContext *ctx,
                                            const int64_t *row_offsets, const double *y, const double *const *x_cols,
                                            const int64_t *train_counts, AnofoxHipBlsBatchOptions options,
                                            double confidence_level, double *core, double *pred, AnofoxError *out_error);
+
+/*
+ * Grouped quantile regression (anofox_quantile_fit, anofox_stats_quantile_fit_predict_agg): per group, over the rows with
+ * finite y and x, THE minimiser of the pinball loss sum_i rho_tau(y_i - b0 - x_i'b), rho_tau(r) = r (tau - [r < 0]) — the
+ * exact vertex of the linear program, by a simplex over the rows, one wavefront per group (DESIGN.md §1 "Quantile
+ * regression").  1 <= n_features <= 32; more fails the call with ANOFOX_ERROR_INVALID_INPUT.  tolerance is accepted and
+ * unused.  Records (anofox_hip_quantile_record_len(p) = p + 6 doubles):
+ *   quantile[g] = { coefficients[0..p), intercept (NaN without one), tau, loss (the pinball sum over the valid rows),
+ *                   n_basis_rows (k minus the artificials left: the rank of the design), n_observations, status }
+ * status != 0 => every other field is NaN; statuses 1 (tau not in (0, 1) or NaN: every group of the call), 6 (fewer valid
+ * rows than p + [intercept]; equality is allowed and interpolates), 10, ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS.  2 (the final
+ * basis factorised with an exactly zero pivot: a guard, not expected).  An aliased
+ * column's coefficient is exactly 0.0.  iterations (may be NULL): iterations[g] = simplex pivots, negated when
+ * max_iterations (or the ceiling 1000 + 50 k) stopped the group (its last vertex is returned, status 0; with max_iterations = 0
+ * that is beta = 0 with count 0 and n_basis_rows = 0).
+ */
+typedef struct {
+	double tau;
+	bool fit_intercept;
+	uint32_t max_iterations;
+	double tolerance;
+} AnofoxHipQuantileBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_quantile_record_len(size_t n_features);
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                          const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                          AnofoxHipQuantileBatchOptions options, double *d_quantile, int32_t *d_iterations,
+                                          AnofoxError *out_error);
+/* host pointers, synchronous; ctx may be NULL (per-thread default context) */
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                        const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                        AnofoxHipQuantileBatchOptions options, double *quantile, int32_t *iterations,
+                                        AnofoxError *out_error);
+
+/*
+ * Quantile regression fit + predict (anofox_stats_quantile_fit_predict_agg, src/aggregate_functions/
+ * quantile_fit_predict_aggregate.cpp:269-345): the fit above on each group's training rows, then every row gets
+ * pred = {yhat, NaN, NaN} ([n_rows x 3]; there is no interval; a non-finite yhat is NaN = SQL NULL).  core receives records in
+ * the REGRESSION layout (p + 6): { coefficients[p], intercept, NaN, NaN, NaN, n_observations, status }.  Fewer than 2
+ * training rows (train_counts, optional) or a failed fit: status != 0 and NaN for every row of the group.
+ */
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                  const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                  const int64_t *d_train_counts, AnofoxHipQuantileBatchOptions options,
+                                                  double *d_core, double *d_pred, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                const int64_t *train_counts, AnofoxHipQuantileBatchOptions options,
+                                                double *core, double *pred, AnofoxError *out_error);
 
 
 /*
