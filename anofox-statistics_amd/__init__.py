@@ -19,13 +19,14 @@ from .aggregate import (StreamingStates, FitAggResult, FitPredictAggResult, OlsF
                         residuals_diagnostics_agg, ElasticNetFitPredictAgg, elasticnet_fit_predict_agg,
                         elasticnet_fit_predict, RlsFitAgg, rls_fit_agg, RlsFitPredictAgg, rls_fit_predict_agg,
                         rls_fit_predict, BlsFitAggResult, BlsFitAgg, NnlsFitAgg, BlsFitPredictAgg, bls_fit_agg, nnls_fit_agg,
-                        bls_fit_predict_agg, bls_result_from_records, QuantileFitPredictAgg, quantile_fit_predict_agg)
+                        bls_fit_predict_agg, bls_result_from_records, QuantileFitPredictAgg, quantile_fit_predict_agg,
+                        QuantilePathFitPredictAgg, QuantilePathFitPredictAggResult, quantile_path_fit_predict_agg)
 from .options import (ElasticNetOptions, ElasticNetPredictOptions, InvalidInputException, RegressionOptions,  # noqa: E402
                       parse_elasticnet_options, parse_elasticnet_predict_options, parse_options, RlsOptions,
                       parse_rls_options, BlsOptions, parse_bls_options, parse_nnls_options, parse_bls_predict_options,
-                      QuantileOptions, parse_quantile_options)
-from .runtime import AggState, Context, quantile_fit_batch_host, quantile_fit_predict_batch_host, bls_fit_batch_host, bls_fit_predict_batch_host, rls_fit_batch_host, rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
-from .scalar import quantile_fit, aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
+                      QuantileOptions, parse_quantile_options, QuantilePathOptions, parse_quantile_path_options)
+from .runtime import AggState, Context, quantile_fit_path_batch_host, quantile_fit_path_batch_device, quantile_fit_predict_path_batch_host, quantile_fit_batch_host, quantile_fit_predict_batch_host, bls_fit_batch_host, bls_fit_predict_batch_host, rls_fit_batch_host, rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
+from .scalar import quantile_fit, quantile_fit_path, aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
 # src/scalar_functions/{aic_bic,vif}.cpp) and the deprecated aggregate aliases
@@ -36,6 +37,7 @@ SQL_FUNCTIONS.update({
     "anofox_stats_elasticnet_fit": elasticnet_fit, "elasticnet_fit": elasticnet_fit,
     "anofox_stats_rls_fit": rls_fit, "rls_fit": rls_fit,
     "anofox_stats_quantile_fit": quantile_fit, "quantile_fit": quantile_fit,
+    "anofox_stats_quantile_fit_path": quantile_fit_path, "quantile_fit_path": quantile_fit_path,
     "anofox_stats_predict": predict,
     "anofox_stats_aic": aic, "aic": aic, "anofox_stats_bic": bic, "bic": bic,
     "anofox_stats_vif": vif, "vif": vif,
@@ -63,6 +65,9 @@ __all__ = [
     "bls_fit_batch_host", "bls_fit_predict_batch_host",
     "QuantileOptions", "parse_quantile_options", "quantile_fit", "QuantileFitPredictAgg", "quantile_fit_predict_agg",
     "quantile_fit_batch_host", "quantile_fit_predict_batch_host",
+    "QuantilePathOptions", "parse_quantile_path_options", "quantile_fit_path", "QuantilePathFitPredictAgg",
+    "QuantilePathFitPredictAggResult", "quantile_path_fit_predict_agg", "quantile_fit_path_batch_host",
+    "quantile_fit_path_batch_device", "quantile_fit_predict_path_batch_host",
 ]
 
 

@@ -359,6 +359,20 @@ SYMBOLS = {
     "anofox_hip_quantile_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
                                                               C.POINTER(_DP), C.POINTER(C.c_int64), AnofoxHipQuantileBatchOptions,
                                                               _DP, _DP, _ERRP]),
+    "anofox_quantile_fit_path": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxQuantileOptions, _DP,
+                                            C.c_size_t, C.POINTER(AnofoxQuantileFitResultCore), _ERRP]),
+    "anofox_hip_quantile_fit_path_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                             C.POINTER(C.c_void_p), AnofoxHipQuantileBatchOptions, _DP, C.c_size_t,
+                                                             C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_quantile_fit_path_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                           C.POINTER(_DP), AnofoxHipQuantileBatchOptions, _DP, C.c_size_t, _DP,
+                                                           C.POINTER(C.c_int32), _ERRP]),
+    "anofox_hip_quantile_fit_predict_path_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                                     C.POINTER(C.c_void_p), C.c_void_p, AnofoxHipQuantileBatchOptions,
+                                                                     _DP, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_quantile_fit_predict_path_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                                   C.POINTER(_DP), C.POINTER(C.c_int64), AnofoxHipQuantileBatchOptions,
+                                                                   _DP, C.c_size_t, _DP, C.POINTER(C.c_int32), _DP, _ERRP]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "anofox_hip_host_free": (None, [C.c_void_p]),
 }

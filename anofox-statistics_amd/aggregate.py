@@ -1049,6 +1049,67 @@ def quantile_fit_predict_agg(group_keys, y, x, options=None, context=None, split
     return QuantileFitPredictAgg(options, context).update(group_keys, y, x, split=split).finalize()
 
 
+@dataclass
+class QuantilePathFitPredictAggResult:
+    """Per group: the rows with yhat[n, T], one column per quantile of taus (NaN = NULL)."""
+    keys: np.ndarray
+    row_offsets: np.ndarray           # rows of group i = [row_offsets[i], row_offsets[i+1])
+    taus: tuple
+    y: np.ndarray                     # NaN where y was NULL
+    y_is_null: np.ndarray
+    yhat: np.ndarray                  # [N, T]; NaN = SQL NULL
+    is_training: np.ndarray
+    is_null: np.ndarray               # [G, T]: the column of that quantile is NULL for the whole group
+    records: np.ndarray               # fit records [G, T, p+6]
+    iterations: np.ndarray            # [G, T]
+
+    def yhat_of(self, i: int) -> np.ndarray:
+        """yhat[n, T] of group i."""
+        return self.yhat[int(self.row_offsets[i]):int(self.row_offsets[i + 1])]
+
+
+class QuantilePathFitPredictAgg(QuantileFitPredictAgg):
+    """quantile_fit_predict_agg over a grid of quantiles from one fit per group (the tau path): the row rules of
+    QuantileFitPredictAgg; a non-finite yhat is NULL, fewer than 2 training rows or a failed fit make that quantile's column
+    NULL."""
+    sql_name = "anofox_stats_quantile_path_fit_predict_agg"
+
+    @staticmethod
+    def _parse_options(options):
+        from .options import parse_quantile_path_options
+        return parse_quantile_path_options(options)
+
+    def _fit_predict(self, offsets, y_fit, x_cols, w, train_counts):
+        from .runtime import quantile_fit_predict_path_batch_host
+        self._path = quantile_fit_predict_path_batch_host(offsets, y_fit, x_cols, self.options.batch_options(), self.options.taus,
+                                                          train_counts=train_counts, ctx=self._ctx)
+        rec, _, pred = self._path
+        p = rec.shape[2] - 6
+        core = np.full((rec.shape[0], p + 6), np.nan)       # the base class reads only the status: NULL when every quantile failed
+        core[:, p + 5] = np.where((rec[:, :, p + 5] == 0).any(axis=1), 0.0, rec[:, 0, p + 5])
+        return core, np.full((pred.shape[0], 3), np.nan)
+
+    def finalize(self) -> QuantilePathFitPredictAggResult:
+        self._path = None
+        base = super().finalize()
+        T = len(self.options.taus)
+        p = self.n_features or 0
+        G = len(base.keys)
+        if self._path is None:                               # no rows at all
+            return QuantilePathFitPredictAggResult(base.keys, base.row_offsets, self.options.taus, base.y, base.y_is_null,
+                                                   np.empty((0, T)), base.is_training, np.ones((G, T), dtype=bool),
+                                                   np.full((G, T, p + 6), np.nan), np.zeros((G, T), dtype=np.int32))
+        rec, its, pred = self._path
+        return QuantilePathFitPredictAggResult(base.keys, base.row_offsets, self.options.taus, base.y, base.y_is_null, pred,
+                                               base.is_training, rec[:, :, p + 5] != 0, rec, its)
+
+
+def quantile_path_fit_predict_agg(group_keys, y, x, options, context=None, split=None) -> QuantilePathFitPredictAggResult:
+    return QuantilePathFitPredictAgg(options, context).update(group_keys, y, x, split=split).finalize()
+
+
 SQL_FUNCTIONS.update({
     "anofox_stats_quantile_fit_predict_agg": quantile_fit_predict_agg, "quantile_fit_predict_agg": quantile_fit_predict_agg,
+    "anofox_stats_quantile_path_fit_predict_agg": quantile_path_fit_predict_agg,
+    "quantile_path_fit_predict_agg": quantile_path_fit_predict_agg,
 })

@@ -1,12 +1,16 @@
 // quantile.hip — grouped quantile regression: one wavefront per group runs the exact simplex of quantile_solve.h over the
 // group's rows, and the entry points anofox_hip_quantile_fit_batch_{device,host}, anofox_hip_quantile_fit_predict_batch_*,
-// anofox_quantile_fit / anofox_free_quantile_result.
+// anofox_quantile_fit / anofox_free_quantile_result, and their tau-path siblings (*_path_*).
 //
 // The contract and the method: quantile_solve.h and DESIGN.md §1, "Quantile regression".
 //   quantile_fit_kernel: 64 lanes per workgroup = one wavefront per group (grid-stride over the groups).  LDS holds B^-1 and
 //     the LU workspace (k x k doubles each, k = p + [intercept] <= 33) and the per-edge vectors: qs_work_doubles(k) * 8 bytes,
 //     20.6 KB at k = 33.  Rows are strided over the lanes; residual, z and breakpoint of a row sit in a per-call device
 //     scratch (3 doubles per row, the context's workspace) that only the row's own lane touches.
+//   quantile_path_kernel: the same wavefront, LDS and scratch for a whole grid of tau (anofox_hip_quantile_fit_path_batch_*,
+//     anofox_hip_quantile_fit_predict_path_batch_*, anofox_quantile_fit_path): qs_fit_path begins once and pivots from each
+//     tau's vertex to the next; the grid (sorted by the host, at most kQsMaxTaus) travels in the kernel arguments.  With a
+//     prediction buffer the wavefront writes pred[i T + t] = a_i'beta_t of its group's rows right after tau_t's record.
 //   quantile_nan_bounds_kernel: the fit-predict entry points hand the records (regression layout, sigma = NaN) to the
 //     existing predict kernels, which give yhat = lower = upper for a NaN sigma; quantile regression has no interval, so
 //     the two bounds are then overwritten with NaN.
@@ -70,6 +74,38 @@ __global__ __launch_bounds__(64) void quantile_fit_kernel(QuantileArgs a) {
 	}
 }
 
+struct QuantilePathArgs {
+	QuantileArgs q;           // tau, invalid and predict_layout unused; core [G x T x (p + 6)], iterations [G x T] or nullptr
+	double *pred;             // [n_rows x T] or nullptr
+	int n_taus, n_ok;         // T; the valid tau among them
+	double taus[kQsMaxTaus];  // the valid tau ascending (qs_order_taus)
+	uint8_t slot[kQsMaxTaus]; // the caller's position of taus[t]; [n_ok, T): the invalid positions
+};
+
+__global__ __launch_bounds__(64) void quantile_path_kernel(QuantilePathArgs a) {
+	extern __shared__ double quantile_lds[];
+	const int64_t T = a.n_taus;
+	for (int64_t g = blockIdx.x; g < a.q.n_groups; g += gridDim.x) {
+		QsProblem P;
+		P.y = a.q.y;
+		P.x = a.q.x;
+		P.p = a.q.p;
+		P.fit_intercept = a.q.fit_intercept;
+		P.lo = a.q.row_offsets[g];
+		P.hi = a.q.row_offsets[g + 1];
+		P.rule_count = a.q.train_counts ? a.q.train_counts[g] : P.hi - P.lo;
+		P.tau = NAN;
+		P.max_iterations = a.q.max_iterations;
+		P.predict_layout = 0;
+		P.r = a.q.scratch;
+		P.z = a.q.scratch + a.q.n_rows;
+		P.t = a.q.scratch + 2 * a.q.n_rows;
+		qs_fit_path(P, a.taus, a.slot, a.n_ok, a.n_taus, quantile_lds, a.q.core + g * T * (int64_t)(a.q.p + 6),
+		            a.q.iterations ? a.q.iterations + g * T : nullptr, a.pred);
+		__syncthreads(); // the next group reuses the LDS
+	}
+}
+
 __global__ __launch_bounds__(256) void quantile_nan_bounds_kernel(double *pred, int64_t n_rows) {
 	const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (r >= n_rows) return;
@@ -100,14 +136,9 @@ bool check_host_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxErr
 	return true;
 }
 
-// the fit of G groups on device-resident inputs, enqueued on the context's stream (ctx->mu held by the caller)
-bool launch_quantile(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y,
-                     const double *const *x_cols, const int64_t *d_tc, const AnofoxHipQuantileBatchOptions &o, int predict_layout,
-                     double *d_core, int32_t *d_iterations, AnofoxError *e) {
-	if (G == 0) return true;
-	const size_t rows = n_rows > 0 ? (size_t)n_rows : 1;
-	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, 3 * rows * sizeof(double), "quantile scratch", e)) return false;
-	QuantileArgs a;
+void fill_args(QuantileArgs &a, AnofoxHipContext *ctx, int64_t G, size_t p, size_t rows, const int64_t *d_off, const double *d_y,
+               const double *const *x_cols, const int64_t *d_tc, const AnofoxHipQuantileBatchOptions &o, int predict_layout, double *d_core,
+               int32_t *d_iterations) {
 	memset(&a, 0, sizeof a);
 	a.row_offsets = d_off;
 	a.train_counts = d_tc;
@@ -124,11 +155,49 @@ bool launch_quantile(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows,
 	a.predict_layout = predict_layout;
 	a.core = d_core;
 	a.iterations = d_iterations;
+}
+
+// the fit of G groups on device-resident inputs, enqueued on the context's stream (ctx->mu held by the caller)
+bool launch_quantile(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y,
+                     const double *const *x_cols, const int64_t *d_tc, const AnofoxHipQuantileBatchOptions &o, int predict_layout,
+                     double *d_core, int32_t *d_iterations, AnofoxError *e) {
+	if (G == 0) return true;
+	const size_t rows = n_rows > 0 ? (size_t)n_rows : 1;
+	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, 3 * rows * sizeof(double), "quantile scratch", e)) return false;
+	QuantileArgs a;
+	fill_args(a, ctx, G, p, rows, d_off, d_y, x_cols, d_tc, o, predict_layout, d_core, d_iterations);
 	const int k = (int)p + a.fit_intercept;
 	const size_t lds = qs_work_doubles(k) * sizeof(double);
 	const int64_t max_blocks = 1 << 20;
 	hipLaunchKernelGGL(quantile_fit_kernel, dim3((unsigned)(G < max_blocks ? G : max_blocks)), dim3(64), lds, ctx->stream, a);
 	return !hip_fail(hipGetLastError(), "quantile_fit_kernel", e);
+}
+
+bool check_taus(const double *taus, size_t n_taus, AnofoxError *e) {
+	if (!taus || n_taus == 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "taus is NULL or empty"); return false; }
+	if (n_taus > (size_t)kQsMaxTaus) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "quantile path: n_taus > 64 is not built"); return false; }
+	return true;
+}
+
+// the tau path of G groups on device-resident inputs (ctx->mu held by the caller); taus: host memory, checked by check_taus;
+// d_pred: [n_rows x T] or nullptr.  options.tau is not read.
+bool launch_quantile_path(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y,
+                          const double *const *x_cols, const int64_t *d_tc, const AnofoxHipQuantileBatchOptions &o, const double *taus,
+                          size_t n_taus, double *d_rec, int32_t *d_iterations, double *d_pred, AnofoxError *e) {
+	if (G == 0) return true;
+	const size_t rows = n_rows > 0 ? (size_t)n_rows : 1;
+	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, 3 * rows * sizeof(double), "quantile scratch", e)) return false;
+	QuantilePathArgs a;
+	memset(&a, 0, sizeof a);
+	fill_args(a.q, ctx, G, p, rows, d_off, d_y, x_cols, d_tc, o, 0, d_rec, d_iterations);
+	a.pred = d_pred;
+	a.n_taus = (int)n_taus;
+	a.n_ok = qs_order_taus(taus, (int)n_taus, a.taus, a.slot);
+	const int k = (int)p + a.q.fit_intercept;
+	const size_t lds = qs_work_doubles(k) * sizeof(double);
+	const int64_t max_blocks = 1 << 20;
+	hipLaunchKernelGGL(quantile_path_kernel, dim3((unsigned)(G < max_blocks ? G : max_blocks)), dim3(64), lds, ctx->stream, a);
+	return !hip_fail(hipGetLastError(), "quantile_path_kernel", e);
 }
 
 bool launch_nan_bounds(AnofoxHipContext *ctx, int64_t n_rows, double *d_pred, AnofoxError *e) {
@@ -154,6 +223,50 @@ bool h2d(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *
 
 bool d2h(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *e) {
 	return bytes == 0 || !hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "D2H", e);
+}
+
+// ---- the one-group entry points (anofox_quantile_fit, anofox_quantile_fit_path) ----
+// NULL entries -> NaN through the validity bitmask; a one-row input is padded with an all-NaN row
+void expand_data_array(const AnofoxDataArray &a, std::vector<double> &out, size_t len) {
+	out.assign(len, NAN);
+	for (size_t i = 0; i < a.len; ++i) {
+		const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
+		out[i] = valid ? a.data[i] : NAN;
+	}
+}
+
+// a record's status != 0 as the reference's error (crates/anofox-stats-core/src/errors.rs)
+void set_scalar_fit_error(int status, size_t n, size_t p, const std::vector<double> &yv, const std::vector<std::vector<double>> &cols,
+                          AnofoxError *out_error) {
+	size_t n_valid = 0;
+	for (size_t i = 0; i < n; ++i) {
+		bool ok = isfinite(yv[i]);
+		for (size_t j = 0; ok && j < p; ++j) ok = isfinite(cols[j][i]);
+		n_valid += ok;
+	}
+	std::string msg;
+	switch (status) {
+	case ANOFOX_ERROR_NO_VALID_DATA: msg = "All rows filtered due to NULL/NaN values"; break;
+	case ANOFOX_ERROR_INSUFFICIENT_DATA:
+		msg = "Insufficient data: " + std::to_string(n_valid) + " rows, " + std::to_string(p) + " features (need rows > features)";
+		break;
+	default: msg = "Quantile fit failed on the GPU path"; break;
+	}
+	set_error(out_error, status == ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS ? ANOFOX_ERROR_INSUFFICIENT_DATA : (AnofoxErrorCode)status, msg);
+}
+
+// the malloc'ed result of one record
+bool fill_scalar_result(const double *rec, size_t p, AnofoxQuantileFitResultCore *out_core, AnofoxError *out_error) {
+	double *coef = (double *)malloc(p * sizeof(double));
+	if (!coef) { set_error(out_error, ANOFOX_ERROR_ALLOCATION_FAILURE, "Failed to allocate coefficients"); return false; }
+	memcpy(coef, rec, p * sizeof(double));
+	out_core->coefficients = coef;
+	out_core->coefficients_len = p;
+	out_core->intercept = rec[p];
+	out_core->tau = rec[p + 1];
+	out_core->n_observations = (size_t)rec[p + 4];
+	out_core->n_features = p;
+	return true;
 }
 
 } // namespace
@@ -282,6 +395,132 @@ bool anofox_hip_quantile_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
 
+bool anofox_hip_quantile_fit_path_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                               const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                               AnofoxHipQuantileBatchOptions options, const double *taus, size_t n_taus,
+                                               double *d_quantile, int32_t *d_iterations, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_quantile(n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_quantile, out_error)) return false;
+	if (!check_taus(taus, n_taus, out_error)) return false;
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	return launch_quantile_path(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, nullptr, options, taus, n_taus, d_quantile,
+	                            d_iterations, nullptr, out_error);
+}
+
+bool anofox_hip_quantile_fit_path_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                             const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                             AnofoxHipQuantileBatchOptions options, const double *taus, size_t n_taus, double *quantile,
+                                             int32_t *iterations, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_quantile(n_groups, n_features, n_rows, row_offsets, y, x_cols, quantile, out_error)) return false;
+	if (!check_taus(taus, n_taus, out_error)) return false;
+	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (n_groups == 0) return true;
+	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	const size_t p = n_features, T = n_taus, rec_len = T * (p + 6);
+	const int64_t slab_rows = 32ll << 20; // the groups pass through the GPU in slabs of at most ~32M rows
+	std::vector<int64_t> off;
+	hipStream_t st = ctx->stream;
+	for (int64_t g0 = 0; g0 < n_groups;) {
+		int64_t g1 = g0 + 1;
+		while (g1 < n_groups && row_offsets[g1 + 1] - row_offsets[g0] <= slab_rows) ++g1;
+		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = row_offsets[g1] - r0;
+		off.resize((size_t)G + 1);
+		for (int64_t g = 0; g <= G; ++g) off[(size_t)g] = row_offsets[g0 + g] - r0;
+		const size_t need = Stage::bytes((size_t)G + 1, 8) + (p + 1) * Stage::bytes((size_t)R, 8) + Stage::bytes((size_t)G * rec_len, 8) +
+		                    Stage::bytes((size_t)G * T, 4);
+		if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
+		Stage s{(char *)ctx->stage};
+		int64_t *d_off = s.take<int64_t>((size_t)G + 1);
+		if (!h2d(d_off, off.data(), ((size_t)G + 1) * sizeof(int64_t), st, out_error)) return false;
+		const double *d_x[kQsMaxP];
+		for (size_t j = 0; j < p; ++j) {
+			double *c = s.take<double>((size_t)R);
+			if (!h2d(c, x_cols[j] + r0, (size_t)R * sizeof(double), st, out_error)) return false;
+			d_x[j] = c;
+		}
+		double *d_y = s.take<double>((size_t)R);
+		if (!h2d(d_y, y + r0, (size_t)R * sizeof(double), st, out_error)) return false;
+		double *d_rec = s.take<double>((size_t)G * rec_len);
+		int32_t *d_it = iterations ? s.take<int32_t>((size_t)G * T) : nullptr;
+		if (!launch_quantile_path(ctx, G, p, R, d_off, d_y, d_x, nullptr, options, taus, T, d_rec, d_it, nullptr, out_error)) return false;
+		if (!d2h(quantile + (size_t)g0 * rec_len, d_rec, (size_t)G * rec_len * sizeof(double), st, out_error)) return false;
+		if (d_it && !d2h(iterations + (size_t)g0 * T, d_it, (size_t)G * T * sizeof(int32_t), st, out_error)) return false;
+		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
+		g0 = g1;
+	}
+	return true;
+}
+
+bool anofox_hip_quantile_fit_predict_path_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                       const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                       const int64_t *d_train_counts, AnofoxHipQuantileBatchOptions options,
+                                                       const double *taus, size_t n_taus, double *d_quantile, int32_t *d_iterations,
+                                                       double *d_pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_quantile(n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_quantile, out_error)) return false;
+	if (!check_taus(taus, n_taus, out_error)) return false;
+	if (n_groups > 0 && !d_pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	if (n_groups == 0) return true;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	return launch_quantile_path(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_train_counts, options, taus, n_taus,
+	                            d_quantile, d_iterations, d_pred, out_error);
+}
+
+bool anofox_hip_quantile_fit_predict_path_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                     const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                     const int64_t *train_counts, AnofoxHipQuantileBatchOptions options, const double *taus,
+                                                     size_t n_taus, double *quantile, int32_t *iterations, double *pred,
+                                                     AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_quantile(n_groups, n_features, n_rows, row_offsets, y, x_cols, quantile, out_error)) return false;
+	if (!check_taus(taus, n_taus, out_error)) return false;
+	if (n_groups > 0 && !pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
+	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (n_groups == 0) return true;
+	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) { // every row of pred belongs to a group's wavefront
+		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
+		return false;
+	}
+	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	const size_t p = n_features, T = n_taus, rec_len = T * (p + 6), G = (size_t)n_groups, N = (size_t)n_rows;
+	std::lock_guard<std::mutex> lk(ctx->mu); // one lock over staging, the kernel and the copies back
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	const size_t need = Stage::bytes(G + 1, 8) + Stage::bytes(G, 8) + (p + 1) * Stage::bytes(N, 8) + Stage::bytes(G * rec_len, 8) +
+	                    Stage::bytes(G * T, 4) + Stage::bytes(N * T, 8);
+	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
+	hipStream_t st = ctx->stream;
+	Stage s{(char *)ctx->stage};
+	int64_t *d_off = s.take<int64_t>(G + 1);
+	int64_t *d_tc = s.take<int64_t>(G);
+	if (!h2d(d_off, row_offsets, (G + 1) * sizeof(int64_t), st, out_error)) return false;
+	if (train_counts && !h2d(d_tc, train_counts, G * sizeof(int64_t), st, out_error)) return false;
+	const double *d_x[kQsMaxP];
+	for (size_t j = 0; j < p; ++j) {
+		double *c = s.take<double>(N);
+		if (!h2d(c, x_cols[j], N * sizeof(double), st, out_error)) return false;
+		d_x[j] = c;
+	}
+	double *d_y = s.take<double>(N);
+	if (!h2d(d_y, y, N * sizeof(double), st, out_error)) return false;
+	double *d_rec = s.take<double>(G * rec_len);
+	int32_t *d_it = s.take<int32_t>(G * T);
+	double *d_pred = s.take<double>(N * T);
+	if (!launch_quantile_path(ctx, n_groups, p, n_rows, d_off, d_y, d_x, train_counts ? d_tc : nullptr, options, taus, T, d_rec,
+	                          iterations ? d_it : nullptr, d_pred, out_error))
+		return false;
+	if (!d2h(quantile, d_rec, G * rec_len * sizeof(double), st, out_error)) return false;
+	if (iterations && !d2h(iterations, d_it, G * T * sizeof(int32_t), st, out_error)) return false;
+	if (!d2h(pred, d_pred, N * T * sizeof(double), st, out_error)) return false;
+	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
+}
+
 // A batch of one group with anofox_elasticnet_fit's conventions: argument checks first, tau as fit_quantile checks it
 // (quantile.rs:35-40, InvalidValue -> InvalidInput), NULL entries -> NaN through the validity bitmask, a one-row input padded
 // with an all-NaN row, the reference's error texts (crates/anofox-stats-core/src/errors.rs), the coefficients malloc'ed.
@@ -302,18 +541,11 @@ bool anofox_quantile_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_c
 	const size_t p = x_count, n = y.len;
 	if (p > (size_t)kQsMaxP) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "quantile regression: n_features > 32 is not built"); return false; }
 	const size_t n_pad = n < 2 ? 2 : n;
-	auto expand = [](const AnofoxDataArray &a, std::vector<double> &out, size_t len) {
-		out.assign(len, NAN);
-		for (size_t i = 0; i < a.len; ++i) {
-			const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
-			out[i] = valid ? a.data[i] : NAN;
-		}
-	};
 	std::vector<std::vector<double>> cols(p);
 	std::vector<double> yv;
-	expand(y, yv, n_pad);
+	expand_data_array(y, yv, n_pad);
 	std::vector<const double *> xp(p);
-	for (size_t j = 0; j < p; ++j) { expand(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
+	for (size_t j = 0; j < p; ++j) { expand_data_array(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
 	AnofoxHipQuantileBatchOptions o;
 	memset(&o, 0, sizeof o);
 	o.tau = options.tau;
@@ -325,32 +557,58 @@ bool anofox_quantile_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_c
 	if (!anofox_hip_quantile_fit_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), o, rec.data(), nullptr, out_error)) return false;
 	const int status = (int)rec[p + 5];
 	if (status != ANOFOX_ERROR_SUCCESS) {
-		size_t n_valid = 0;
-		for (size_t i = 0; i < n; ++i) {
-			bool ok = isfinite(yv[i]);
-			for (size_t j = 0; ok && j < p; ++j) ok = isfinite(cols[j][i]);
-			n_valid += ok;
-		}
-		std::string msg;
-		switch (status) { // crates/anofox-stats-core/src/errors.rs
-		case ANOFOX_ERROR_NO_VALID_DATA: msg = "All rows filtered due to NULL/NaN values"; break;
-		case ANOFOX_ERROR_INSUFFICIENT_DATA:
-			msg = "Insufficient data: " + std::to_string(n_valid) + " rows, " + std::to_string(p) + " features (need rows > features)";
-			break;
-		default: msg = "Quantile fit failed on the GPU path"; break;
-		}
-		set_error(out_error, status == ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS ? ANOFOX_ERROR_INSUFFICIENT_DATA : (AnofoxErrorCode)status, msg);
+		set_scalar_fit_error(status, n, p, yv, cols, out_error);
 		return false;
 	}
-	double *coef = (double *)malloc(p * sizeof(double));
-	if (!coef) { set_error(out_error, ANOFOX_ERROR_ALLOCATION_FAILURE, "Failed to allocate coefficients"); return false; }
-	memcpy(coef, rec.data(), p * sizeof(double));
-	out_core->coefficients = coef;
-	out_core->coefficients_len = p;
-	out_core->intercept = rec[p];
-	out_core->tau = rec[p + 1];
-	out_core->n_observations = (size_t)rec[p + 4];
-	out_core->n_features = p;
+	return fill_scalar_result(rec.data(), p, out_core, out_error);
+}
+
+// anofox_quantile_fit at every tau of a grid, through one anofox_hip_quantile_fit_path_batch_host call of one group.  The
+// checks, their order and the error texts are anofox_quantile_fit's; any tau outside (0, 1) fails the call.  On failure no
+// result holds memory.
+bool anofox_quantile_fit_path(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxQuantileOptions options,
+                              const double *taus, size_t n_taus, AnofoxQuantileFitResultCore *out_results, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!out_results) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "out_results is NULL"); return false; }
+	if (!x || x_count == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
+	if (y.len == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Empty input: y cannot be empty"); return false; }
+	if (!check_taus(taus, n_taus, out_error)) return false;
+	for (size_t t = 0; t < n_taus; ++t)
+		if (tau_invalid(taus[t])) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Invalid value for tau: tau must be in (0, 1)"); return false; }
+	for (size_t j = 0; j < x_count; ++j) {
+		if (x[j].len != y.len) {
+			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH,
+			          "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(x[j].len) + " rows");
+			return false;
+		}
+	}
+	const size_t p = x_count, n = y.len;
+	if (p > (size_t)kQsMaxP) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "quantile regression: n_features > 32 is not built"); return false; }
+	const size_t n_pad = n < 2 ? 2 : n;
+	std::vector<std::vector<double>> cols(p);
+	std::vector<double> yv;
+	expand_data_array(y, yv, n_pad);
+	std::vector<const double *> xp(p);
+	for (size_t j = 0; j < p; ++j) { expand_data_array(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
+	AnofoxHipQuantileBatchOptions o;
+	memset(&o, 0, sizeof o);
+	o.fit_intercept = options.fit_intercept;
+	o.max_iterations = options.max_iterations;
+	o.tolerance = options.tolerance;
+	const int64_t off[2] = {0, (int64_t)n_pad};
+	std::vector<double> rec(n_taus * (p + 6));
+	if (!anofox_hip_quantile_fit_path_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), o, taus, n_taus, rec.data(), nullptr,
+	                                             out_error))
+		return false;
+	for (size_t t = 0; t < n_taus; ++t) {
+		const double *r = rec.data() + t * (p + 6);
+		const int status = (int)r[p + 5];
+		if (status != ANOFOX_ERROR_SUCCESS) set_scalar_fit_error(status, n, p, yv, cols, out_error);
+		if (status != ANOFOX_ERROR_SUCCESS || !fill_scalar_result(r, p, &out_results[t], out_error)) {
+			for (size_t u = 0; u < t; ++u) anofox_free_quantile_result(&out_results[u]);
+			return false;
+		}
+	}
 	return true;
 }
 

@@ -22,6 +22,11 @@
 //   finish      when no edge is violated: B is rebuilt from the basis rows, factorised by LU with partial pivoting, beta and a
 //               fresh B^-1 come from that factorisation, the residuals from the rows, and the optimality test runs again;
 //               if it fails the pivots go on (at most kQsMaxRestarts times).
+//   degeneracy  when no edge is violated but rows sit on their kink off the basis, another basis of the same vertex may still
+//               have a descending edge: one such row is exchanged for one basis element (a step of length zero), the test
+//               repeated, the element put back if nothing descends; at most kQsMaxExchanges trials per tau.
+//   tau path    a vertex is feasible for every tau (only the optimality test and the line search read it): qs_fit_path begins once
+//               and pivots from the vertex each tau's finish rebuilt to the optimum of the next (qs_fit = begin, pivot, record).
 // Pivots are bounded by min(max_iterations, qs_iteration_ceiling(k)); when the bound stops a fit the last vertex is
 // returned (status 0) and the pivot count is reported negated.  No atomics, a fixed order of every sum: two calls give the
 // same bytes.
@@ -48,6 +53,7 @@ constexpr double kQsPivotTol = 1e-11; // |z_i| below this share of sum_c max_i|a
 constexpr double kQsSnapTol = 1e-12;  // |r_i| <= this share of max|y| is a zero residual
 constexpr double kQsStallTol = 1e-14; // a step that lowers the loss by less than this share of max|y|: Bland's rule from here on
 constexpr int kQsMaxRestarts = 3;     // failed optimality tests after a refactorisation that may resume the pivots
+constexpr int kQsMaxExchanges = 256;  // zero-length exchanges tried at degenerate vertices, per tau
 
 constexpr int kQsStatusInvalidInput = 1;
 constexpr int kQsStatusInsufficientData = 6;
@@ -242,14 +248,21 @@ QS_DEV bool qs_refactor(const QsProblem &P, int k, int ld, double *M, double *Bi
 	return true;
 }
 
-// The fit of one group.  `work`: qs_work_doubles(k) doubles (LDS); rec: p + 6 doubles, written by lane 0; *iterations
-// (optional): the pivots, negated when the bound stopped the fit.  `invalid`: tau is unusable (status 1).
-QS_DEV void qs_fit(const QsProblem &P, bool invalid, double *work, double *rec, int32_t *iterations) {
+// What begin leaves for the pivots and the record of every tau of the group: the sizes, the scales and the slices of `work`.
+struct QsState {
+	int k, ld, max_it;
+	int64_t n_valid;
+	double ymax, snap;
+	double *Binv, *M, *s, *dvec, *beta, *v, *amax, *asum, *wrow, *gp, *gm, *thr;
+	int64_t *basis, *perm;
+};
+
+// Begin: the row rules, the first pass, the column sizes and the all-artificial basis (B^-1 = I, beta = 0, r = y).  Nothing
+// here reads tau.  -> 0, or the status that fails the group (100, 10, 6) at every tau.
+QS_DEV int qs_begin(const QsProblem &P, double *work, QsState &S) {
 	const int lane = qs_lane();
 	const int p = P.p, k = p + (P.fit_intercept ? 1 : 0), ld = k | 1;
-	const double tau = P.tau;
-	if (invalid) { qs_fail_record(rec, p, kQsStatusInvalidInput, iterations); return; }
-	if (P.rule_count < 2) { qs_fail_record(rec, p, kQsStatusTooFewRows, iterations); return; }
+	if (P.rule_count < 2) return kQsStatusTooFewRows;
 	// ---- first pass: the row mask, r = y (beta = 0), max|y| ----
 	int64_t n_valid = 0;
 	double ymax = 0.0;
@@ -267,8 +280,8 @@ QS_DEV void qs_fit(const QsProblem &P, bool invalid, double *work, double *rec, 
 	}
 	n_valid = qs_sum_i(n_valid);
 	ymax = qs_max(ymax);
-	if (n_valid == 0) { qs_fail_record(rec, p, kQsStatusNoValidData, iterations); return; }
-	if (n_valid < k) { qs_fail_record(rec, p, kQsStatusInsufficientData, iterations); return; }
+	if (n_valid == 0) return kQsStatusNoValidData;
+	if (n_valid < k) return kQsStatusInsufficientData;
 	const double snap = kQsSnapTol * ymax;
 
 	double *Binv = work, *M = Binv + (size_t)k * ld;
@@ -300,10 +313,36 @@ QS_DEV void qs_fit(const QsProblem &P, bool invalid, double *work, double *rec, 
 		if (fabs(P.r[i]) <= snap) P.r[i] = 0.0;
 
 	const int ceiling = qs_iteration_ceiling(k);
-	const int max_it = P.max_iterations < ceiling ? P.max_iterations : ceiling;
+	S.k = k;
+	S.ld = ld;
+	S.max_it = P.max_iterations < ceiling ? P.max_iterations : ceiling;
+	S.n_valid = n_valid;
+	S.ymax = ymax;
+	S.snap = snap;
+	S.Binv = Binv; S.M = M; S.s = s; S.dvec = dvec; S.beta = beta; S.v = v; S.amax = amax; S.asum = asum;
+	S.wrow = wrow; S.gp = gp; S.gm = gm; S.thr = thr;
+	S.basis = basis; S.perm = perm;
+	return 0;
+}
+
+// Pivot to the optimum of one tau from the vertex the state holds (begin's, or the one an earlier tau's finish rebuilt: a
+// vertex is feasible for every tau), through the finish and the re-test.  The pivot budget, the restarts, Bland's rule and
+// the rested edges start afresh.  -> false: the finish met a singular basis; else beta, B^-1 and r are those of the
+// refactorised last basis.  *pivots: the count; *converged: the optimality test passed after a finish.
+QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const double tau, int *pivots_out, bool *converged_out) {
+	const int lane = qs_lane();
+	const int k = S.k, ld = S.ld, max_it = S.max_it;
+	const double ymax = S.ymax, snap = S.snap;
+	double *Binv = S.Binv, *M = S.M, *s = S.s, *dvec = S.dvec, *beta = S.beta, *v = S.v, *amax = S.amax, *asum = S.asum;
+	double *wrow = S.wrow, *gp = S.gp, *gm = S.gm, *thr = S.thr;
+	int64_t *basis = S.basis, *perm = S.perm;
 	int pivots = 0, restarts = 0;
 	bool fresh = false, converged = false, bland = false, singular = false;
 	uint64_t blocked = 0; // edges whose line search found no breakpoint since the last pivot
+	// the exchange at a degenerate vertex under trial: element esc_j gave way to row esc_i; the search resumes behind it
+	bool esc_active = false;
+	int esc_j = 0, esc_tries = 0;
+	int64_t esc_i = P.lo - 1, esc_old = 0;
 
 	for (;;) {
 		// ---- s over the non-basis rows off their kink (basis rows have r = 0) ----
@@ -360,17 +399,65 @@ QS_DEV void qs_fit(const QsProblem &P, bool invalid, double *work, double *rec, 
 		qs_argmax(bestv, bj);
 		qs_sync(); // (gp / gm / thr are read below by every lane)
 		if (bj < 0) {
-			if (fresh) { converged = true; break; }
+			if (!fresh) {
+				if (!qs_refactor(P, k, ld, M, Binv, beta, v, basis, perm, snap)) { singular = true; break; }
+				fresh = true;
+				blocked = 0;
+				continue;
+			}
+			// ---- no edge of this basis descends.  With rows on their kink off the basis the vertex is degenerate: another
+			// basis of the same vertex may have an edge that does.  Exchange one element for one such row (a step of length
+			// zero: beta and the residuals stay), test again, and put the element back when nothing descends there either.
+			// Without such rows (or candidates) nothing here runs and the test above stands. ----
+			if (esc_active) { // the exchange tried last found nothing: back to the stalled basis, its B^-1 exactly as it was
+				if (lane == 0) basis[esc_j] = esc_old;
+				qs_sync();
+				if (!qs_refactor(P, k, ld, M, Binv, beta, v, basis, perm, snap)) { singular = true; break; }
+				esc_active = false;
+			}
+			bool found = false;
+			int fj = 0;
+			int64_t fi = 0;
+			for (int j = esc_j; j < k && !found && esc_tries < kQsMaxExchanges; ++j) {
+				double wscale = 0.0;
+				for (int c = 0; c < k; ++c) wscale += amax[c] * fabs(Binv[j * ld + c]);
+				const double wtol = kQsPivotTol * wscale;
+				for (int64_t c0 = j == esc_j ? esc_i + 1 : P.lo; c0 < P.hi && !found; c0 += QS_LANES) {
+					const int64_t i = c0 + lane;
+					bool cand = i < P.hi && P.r[i] == 0.0 && !qs_in_basis(basis, k, i);
+					if (cand) {
+						double w = 0.0;
+						for (int c = 0; c < k; ++c) w += qs_elem(P, c, i) * Binv[j * ld + c];
+						cand = fabs(w) > wtol; // the row can take element j's place
+					}
+					const uint64_t m = qs_ballot(cand);
+					if (m) { found = true; fj = j; fi = c0 + __builtin_ctzll(m); }
+				}
+			}
+			if (!found) { converged = true; break; }
+			++esc_tries;
+			esc_j = fj;
+			esc_i = fi;
+			esc_old = basis[fj];
+			qs_sync();
+			if (lane == 0) basis[fj] = fi;
+			qs_sync();
 			if (!qs_refactor(P, k, ld, M, Binv, beta, v, basis, perm, snap)) { singular = true; break; }
-			fresh = true;
+			esc_active = true;
 			blocked = 0;
 			continue;
 		}
-		if (pivots >= max_it || (fresh && restarts >= kQsMaxRestarts)) {
+		const bool esc_hit = esc_active; // an exchanged basis has a descending edge: the pivots go on from it
+		if (esc_active) {
+			esc_active = false;
+			esc_j = 0;
+			esc_i = P.lo - 1;
+		}
+		if (pivots >= max_it || (fresh && !esc_hit && restarts >= kQsMaxRestarts)) {
 			if (!fresh && !qs_refactor(P, k, ld, M, Binv, beta, v, basis, perm, snap)) singular = true;
 			break;
 		}
-		if (fresh) ++restarts;
+		if (fresh && !esc_hit) ++restarts;
 		const double sigma = gp[bj] < gm[bj] ? 1.0 : -1.0;
 		const double need = -(gp[bj] < gm[bj] ? gp[bj] : gm[bj]);
 		const int64_t leaving = basis[bj];
@@ -464,8 +551,18 @@ QS_DEV void qs_fit(const QsProblem &P, bool invalid, double *work, double *rec, 
 		fresh = false;
 		blocked = 0;
 	}
-	if (singular) { qs_fail_record(rec, p, 2 /* ANOFOX_ERROR_SINGULAR_MATRIX */, iterations); return; }
-	// ---- the record: coefficients of the refactorised basis, the loss from the rows ----
+	*pivots_out = pivots;
+	*converged_out = converged;
+	return !singular;
+}
+
+// Record: the coefficients of the refactorised basis, the loss of tau from the rows, the pivot count.
+QS_DEV void qs_record(const QsProblem &P, const QsState &S, const double tau, int pivots, bool converged, double *rec,
+                      int32_t *iterations) {
+	const int lane = qs_lane();
+	const int p = P.p, k = S.k;
+	const double *beta = S.beta;
+	const int64_t *basis = S.basis;
 	double loss = 0.0;
 	for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
 		const double ri = P.r[i];
@@ -482,9 +579,98 @@ QS_DEV void qs_fit(const QsProblem &P, bool invalid, double *work, double *rec, 
 		rec[p + 1] = P.predict_layout ? NAN : tau;
 		rec[p + 2] = P.predict_layout ? NAN : loss;
 		rec[p + 3] = P.predict_layout ? NAN : (double)n_rows_in;
-		rec[p + 4] = (double)n_valid;
+		rec[p + 4] = (double)S.n_valid;
 		rec[p + 5] = 0.0;
 		if (iterations) *iterations = converged ? pivots : -pivots;
+	}
+}
+
+// The fit of one group at P.tau.  `work`: qs_work_doubles(k) doubles (LDS); rec: p + 6 doubles, written by lane 0;
+// *iterations (optional): the pivots, negated when the bound stopped the fit.  `invalid`: tau is unusable (status 1).
+QS_DEV void qs_fit(const QsProblem &P, bool invalid, double *work, double *rec, int32_t *iterations) {
+	if (invalid) { qs_fail_record(rec, P.p, kQsStatusInvalidInput, iterations); return; }
+	QsState S;
+	const int status = qs_begin(P, work, S);
+	if (status != 0) { qs_fail_record(rec, P.p, status, iterations); return; }
+	int pivots;
+	bool converged;
+	if (!qs_pivot_to_optimum(P, S, P.tau, &pivots, &converged)) {
+		qs_fail_record(rec, P.p, 2 /* ANOFOX_ERROR_SINGULAR_MATRIX */, iterations);
+		return;
+	}
+	qs_record(P, S, P.tau, pivots, converged, rec, iterations);
+}
+
+// ---- the tau path ----
+constexpr int kQsMaxTaus = 64; // quantiles of one call at most (the grid travels in the kernel arguments)
+
+// The order the path walks a caller's grid in: the valid tau (inside (0, 1)) ascending, ties in the caller's order, so that
+// neighbouring vertices are close and the result does not depend on the caller's order.  sorted[0 .. n_ok) and their
+// positions slot[0 .. n_ok); slot[n_ok .. n_taus) are the positions of the invalid ones.  -> n_ok.
+inline int qs_order_taus(const double *taus, int n_taus, double *sorted, uint8_t *slot) {
+	int n_ok = 0;
+	for (int t = 0; t < n_taus; ++t) {
+		if (!(taus[t] > 0.0 && taus[t] < 1.0)) continue; // (NaN fails both)
+		int at = n_ok++;
+		for (; at > 0 && sorted[at - 1] > taus[t]; --at) { // insertion: stable
+			sorted[at] = sorted[at - 1];
+			slot[at] = slot[at - 1];
+		}
+		sorted[at] = taus[t];
+		slot[at] = (uint8_t)t;
+	}
+	int n_bad = 0;
+	for (int t = 0; t < n_taus; ++t)
+		if (!(taus[t] > 0.0 && taus[t] < 1.0)) slot[n_ok + n_bad++] = (uint8_t)t;
+	return n_ok;
+}
+
+// The predictions of one tau: pred[i * n_taus + slot] = a_i'beta for EVERY row of the group, the prediction rows (y NaN)
+// included; NaN where an x of the row is not finite, or on all rows when beta is nullptr (a failed fit).  Rows strided over
+// the lanes, each element written once by its row's lane.
+QS_DEV void qs_predict_rows(const QsProblem &P, int k, const double *beta, double *pred, int n_taus, int slot) {
+	for (int64_t i = P.lo + qs_lane(); i < P.hi; i += QS_LANES) {
+		double fit = NAN;
+		if (beta) {
+			bool ok = true;
+			for (int j = 0; j < P.p; ++j) ok = ok && isfinite(P.x[j][i]);
+			if (ok) {
+				fit = 0.0;
+				for (int c = 0; c < k; ++c) fit += qs_elem(P, c, i) * beta[c];
+			}
+		}
+		pred[i * (int64_t)n_taus + slot] = fit;
+	}
+}
+
+// The fits of one group at every tau of a grid: begin once, then per tau (taus[0 .. n_ok), as qs_order_taus sorts them)
+// pivot from the vertex the tau before left and record.  rec: n_taus records of p + 6 doubles, iterations (optional): n_taus
+// counts, pred (optional): the call's [n_rows x n_taus] predictions — all indexed by the caller's position slot[t].  A
+// status of begin fails every valid tau alike; a singular finish fails its tau and every later one (there is no
+// trustworthy vertex to go on from); the invalid positions slot[n_ok .. n_taus) get status 1.  P.tau is not read.
+QS_DEV void qs_fit_path(const QsProblem &P, const double *taus, const uint8_t *slot, int n_ok, int n_taus, double *work, double *rec,
+                        int32_t *iterations, double *pred) {
+	const int p = P.p;
+	for (int t = n_ok; t < n_taus; ++t) {
+		qs_fail_record(rec + (size_t)slot[t] * (p + 6), p, kQsStatusInvalidInput, iterations ? iterations + slot[t] : nullptr);
+		if (pred) qs_predict_rows(P, 0, nullptr, pred, n_taus, slot[t]);
+	}
+	if (n_ok == 0) return;
+	QsState S;
+	int status = qs_begin(P, work, S);
+	for (int t = 0; t < n_ok; ++t) {
+		double *rec_t = rec + (size_t)slot[t] * (p + 6);
+		int32_t *it_t = iterations ? iterations + slot[t] : nullptr;
+		int pivots = 0;
+		bool converged = false;
+		if (status == 0 && !qs_pivot_to_optimum(P, S, taus[t], &pivots, &converged)) status = 2; // ANOFOX_ERROR_SINGULAR_MATRIX
+		if (status != 0) {
+			qs_fail_record(rec_t, p, status, it_t);
+			if (pred) qs_predict_rows(P, 0, nullptr, pred, n_taus, slot[t]);
+			continue;
+		}
+		qs_record(P, S, taus[t], pivots, converged, rec_t, it_t);
+		if (pred) qs_predict_rows(P, S.k, S.beta, pred, n_taus, slot[t]);
 	}
 }
 

@@ -382,6 +382,37 @@ def parse_quantile_options(opts: Optional[Mapping[str, Any]]) -> QuantileOptions
 
 
 @dataclass
+class QuantilePathOptions(QuantileOptions):
+    """QuantileOptions with a grid: taus, in the caller's order; the inherited tau is unused."""
+    taus: tuple = ()
+
+
+def parse_quantile_path_options(opts: Optional[Mapping[str, Any]]) -> QuantilePathOptions:
+    """The MAP options of the tau-path functions: taus (a non-empty list of numbers) and parse_quantile_options' other keys.
+    The key tau is rejected: a path takes its quantiles from taus.  The values are not range-checked here: the fit reports
+    them (status 1 / InvalidInput)."""
+    if opts is None or not isinstance(opts, Mapping):
+        if opts is not None:
+            raise InvalidInputException("Options parameter must be a constant expression")
+        raise InvalidInputException("the quantile path needs the option 'taus': a non-empty list of quantiles")
+    keys = {str(k).lower(): k for k in opts}
+    if "tau" in keys:
+        raise InvalidInputException("the quantile path takes a list of quantiles in 'taus', not 'tau'")
+    raw = opts[keys["taus"]] if "taus" in keys else None
+    if raw is None or isinstance(raw, (str, bytes)) or not (isinstance(raw, (list, tuple)) or hasattr(raw, "__array__")):
+        raise InvalidInputException("the quantile path needs the option 'taus': a non-empty list of quantiles")
+    taus = []
+    for e in list(raw):
+        v = _extract_double(e)
+        taus.append(float("nan") if v is None else v)        # a NULL element is an invalid quantile, reported by the fit
+    if not taus:
+        raise InvalidInputException("the quantile path needs the option 'taus': a non-empty list of quantiles")
+    base = parse_quantile_options({k: v for k, v in opts.items() if str(k).lower() != "taus"})
+    return QuantilePathOptions(tau=base.tau, fit_intercept=base.fit_intercept, max_iterations=base.max_iterations,
+                               tolerance=base.tolerance, null_policy=base.null_policy, taus=tuple(taus))
+
+
+@dataclass
 class RlsOptions:
     """Resolved options of recursive least squares (defaults = the reference's RlsOptions and the bind data of
     rls_aggregate.cpp / rls_predict_aggregate.cpp / rls_fit_predict.cpp)."""

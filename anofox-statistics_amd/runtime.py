@@ -326,6 +326,45 @@ class Context:
     def quantile_fit_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions):
         return quantile_fit_batch_host(row_offsets, y, x_cols, options, ctx=self)
 
+    def quantile_fit_path_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions, taus,
+                                       records=None, iterations=None, use_current_torch_stream: bool = True):
+        """The tau path on CUDA tensors (inputs as quantile_fit_batch_device; taus: a host sequence of 1 .. 64 floats).
+        Asynchronous.  Returns (quantile[G, T, p+6], iterations int32[G, T]) CUDA tensors, indexed by the position in taus."""
+        import torch
+
+        p = len(x_cols)
+        G = int(row_offsets.numel()) - 1
+        N = int(y.numel())
+        tv = np.ascontiguousarray(taus, dtype=np.float64).ravel()
+        T = len(tv)
+        for t in (row_offsets, y, *x_cols):
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("device batch needs contiguous CUDA tensors")
+        if row_offsets.dtype != torch.int64 or y.dtype != torch.float64 or any(c.dtype != torch.float64 for c in x_cols):
+            raise ValueError("row_offsets must be int64 and data float64")
+        if any(int(c.numel()) != N for c in x_cols):
+            raise ValueError("every column must have y's length")
+        if records is None:
+            records = torch.empty((G, T, p + 6), dtype=torch.float64, device=y.device)
+        if iterations is None:
+            iterations = torch.empty((G, T), dtype=torch.int32, device=y.device)
+        if use_current_torch_stream:
+            self.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
+        cols = (C.c_void_p * max(p, 1))(*[c.data_ptr() for c in x_cols])
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_quantile_fit_path_batch_device(
+            self._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols, options,
+            tv.ctypes.data_as(_DP), T, C.c_void_p(records.data_ptr()), C.c_void_p(iterations.data_ptr()), C.byref(err))
+        self._check(ok, err)
+        return records, iterations
+
+    def quantile_fit_path_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions, taus):
+        return quantile_fit_path_batch_host(row_offsets, y, x_cols, options, taus, ctx=self)
+
+    def quantile_fit_predict_path_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions,
+                                             taus, train_counts=None):
+        return quantile_fit_predict_path_batch_host(row_offsets, y, x_cols, options, taus, train_counts, ctx=self)
+
     def quantile_fit_predict_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions,
                                         train_counts=None):
         return quantile_fit_predict_batch_host(row_offsets, y, x_cols, options, train_counts, ctx=self)
@@ -889,6 +928,63 @@ def quantile_fit_predict_batch_host(row_offsets, y, x_cols: Sequence, options: _
     if not ok:
         raise AnofoxStatsError(err.code, err.text())
     return core, pred
+
+
+def quantile_fit_path_batch_device(ctx: Context, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions, taus,
+                                   **kwargs):
+    """Context.quantile_fit_path_batch_device as a function (the device path needs an explicit context)."""
+    return ctx.quantile_fit_path_batch_device(row_offsets, y, x_cols, options, taus, **kwargs)
+
+
+def quantile_fit_path_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions, taus,
+                                 ctx: Optional[Context] = None):
+    """The tau path, numpy in / out: (quantile[G, T, p+6], iterations int32[G, T]), indexed by the position in taus; the
+    contract is anofox_hip_quantile_fit_path_batch_host's (include/anofox_stats_hip.h).  options.tau is ignored."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    tv = np.ascontiguousarray(taus, dtype=np.float64).ravel()
+    p, G, N, T = len(cols), len(off) - 1, len(yv), len(tv)
+    if any(len(c) != N for c in cols):
+        raise ValueError("every column must have y's length")
+    rec = np.empty((G, T, p + 6), dtype=np.float64)
+    its = np.empty((max(G, 0), T), dtype=np.int32)
+    colp = (_DP * max(p, 1))(*[c.ctypes.data_as(_DP) for c in cols])
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_quantile_fit_path_batch_host(
+        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP),
+        colp, options, tv.ctypes.data_as(_DP), T, rec.ctypes.data_as(_DP), its.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return rec, its
+
+
+def quantile_fit_predict_path_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions, taus,
+                                         train_counts=None, ctx: Optional[Context] = None):
+    """The tau path with its fused prediction, numpy in / out: (quantile[G, T, p+6], iterations int32[G, T], pred[N, T]);
+    pred[i, t] is the prediction of row i at taus[t], NaN = NULL."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    tv = np.ascontiguousarray(taus, dtype=np.float64).ravel()
+    tc = None if train_counts is None else np.ascontiguousarray(train_counts, dtype=np.int64)
+    p, G, N, T = len(cols), len(off) - 1, len(yv), len(tv)
+    if any(len(c) != N for c in cols):
+        raise ValueError("every column must have y's length")
+    rec = np.empty((G, T, p + 6), dtype=np.float64)
+    its = np.empty((max(G, 0), T), dtype=np.int32)
+    pred = np.empty((N, T), dtype=np.float64)
+    colp = (_DP * max(p, 1))(*[c.ctypes.data_as(_DP) for c in cols])
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_quantile_fit_predict_path_batch_host(
+        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP), colp,
+        None if tc is None else tc.ctypes.data_as(C.POINTER(C.c_int64)), options, tv.ctypes.data_as(_DP), T,
+        rec.ctypes.data_as(_DP), its.ctypes.data_as(C.POINTER(C.c_int32)), pred.ctypes.data_as(_DP), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return rec, its, pred
 
 
 def fit_predict_batch_host(row_offsets, y, x_cols: Sequence, w, options: _abi.AnofoxHipBatchOptions, train_counts=None,

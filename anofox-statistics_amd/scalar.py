@@ -188,6 +188,35 @@ def quantile_fit(y, x, options=None) -> dict:
         lib.anofox_free_quantile_result(C.byref(core))
 
 
+def quantile_fit_path(y, x, options) -> list:
+    """quantile_fit at every quantile of options['taus'] from one fit (anofox_quantile_fit_path): a list of quantile_fit's
+    dicts, in the order of taus."""
+    from .options import parse_quantile_path_options
+    lib = _abi.load()
+    o = parse_quantile_path_options(options)
+    ya, k0 = _data_array(y)
+    xs = (_abi.AnofoxDataArray * max(len(x), 1))()
+    keep = [k0]
+    for j, col in enumerate(x):
+        a, k = _data_array(col)
+        xs[j] = a
+        keep.append(k)
+    T = len(o.taus)
+    taus = (C.c_double * T)(*o.taus)
+    cores = (_abi.AnofoxQuantileFitResultCore * T)()
+    err = _abi.AnofoxError()
+    if not lib.anofox_quantile_fit_path(ya, xs, len(x), o.ffi_options(), taus, T, cores, C.byref(err)):
+        e = InvalidInputException(f"Quantile fit failed: {err.text()}")
+        e.code = err.code
+        raise e
+    try:
+        return [{"coefficients": [c.coefficients[i] for i in range(c.coefficients_len)], "intercept": c.intercept, "tau": c.tau,
+                 "n_observations": c.n_observations, "n_features": c.n_features} for c in cores]
+    finally:
+        for c in cores:
+            lib.anofox_free_quantile_result(C.byref(c))
+
+
 def aic(rss: float, n: int, k: int) -> Optional[float]:
     """aic(rss, n, k) scalar function (src/scalar_functions/aic_bic.cpp:12-60): NULL (None) on error."""
     lib = _abi.load()

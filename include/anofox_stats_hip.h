@@ -328,6 +328,11 @@ typedef struct {
 ANOFOX_HIP_API bool anofox_quantile_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxQuantileOptions options,
                          AnofoxQuantileFitResultCore *out_core, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_quantile_result(AnofoxQuantileFitResultCore *result);
+/* anofox_quantile_fit at every tau of a grid from one fit (the tau path below): out_results[t] (n_taus of them, the caller's
+ * array) is the result at taus[t], each freed by anofox_free_quantile_result.  options.tau is ignored.  1 <= n_taus <= 64; a
+ * tau outside (0, 1) or NaN fails the call with ANOFOX_ERROR_INVALID_INPUT; after a failure no result holds memory. */
+ANOFOX_HIP_API bool anofox_quantile_fit_path(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxQuantileOptions options,
+                              const double *taus, size_t n_taus, AnofoxQuantileFitResultCore *out_results, AnofoxError *out_error);
 
 #endif /* ANOFOX_STATS_FFI_H */
 
@@ -567,6 +572,42 @@ ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_batch_host(AnofoxHipContext 
                                                 const int64_t *row_offsets, const double *y, const double *const *x_cols,
                                                 const int64_t *train_counts, AnofoxHipQuantileBatchOptions options,
                                                 double *core, double *pred, AnofoxError *out_error);
+
+/*
+ * The tau path: the fit above at every tau of a grid in ONE call (DESIGN.md §1 "Quantile regression", "tau path").  A group's
+ * wavefront stages its rows once and walks the valid tau in ascending order (ties in the caller's order), pivoting from each
+ * tau's optimal vertex to the next, so the result does not depend on the caller's order and equal tau give identical records.
+ * taus is HOST memory in every variant (the grid travels in the kernel arguments), 1 <= n_taus <= 64: NULL, 0 or more fails
+ * the call.  options.tau is ignored.  quantile[(g n_taus + t)] is the record (layout above) of group g at taus[t], iterations
+ * [n_groups x n_taus] (may be NULL) its pivots from the vertex the tau before left, with max_iterations and the sign
+ * convention per tau.  A tau outside (0, 1) or NaN: status 1, iteration count 0 (and a NaN pred column) at that position for
+ * every group; the other positions are fitted normally.  The row rules fail a group at every tau alike; status 2 at one tau
+ * fails every later tau (ascending) of that group too.  Each record is an optimal vertex of its tau: when the optimum is not
+ * unique it may be another vertex than the single-tau call returns, with the same loss.
+ * The fit-predict variants also write pred[n_rows x n_taus]: pred[i n_taus + t] = b0 + x_i'b at taus[t] for EVERY row of the
+ * groups (rows with a NaN y: prediction rows), written by the group's wavefront right after the record; NaN where an x of the
+ * row is not finite or the fit at that tau failed.  train_counts as anofox_hip_quantile_fit_predict_batch_*.  The records
+ * keep the quantile layout.  The device variant does not write rows outside [row_offsets[0], row_offsets[n_groups]).
+ */
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_path_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                               const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                               AnofoxHipQuantileBatchOptions options, const double *taus, size_t n_taus,
+                                               double *d_quantile, int32_t *d_iterations, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_path_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                             const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                             AnofoxHipQuantileBatchOptions options, const double *taus, size_t n_taus,
+                                             double *quantile, int32_t *iterations, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_path_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features,
+                                                       int64_t n_rows, const int64_t *d_row_offsets, const double *d_y,
+                                                       const double *const *x_cols, const int64_t *d_train_counts,
+                                                       AnofoxHipQuantileBatchOptions options, const double *taus, size_t n_taus,
+                                                       double *d_quantile, int32_t *d_iterations, double *d_pred,
+                                                       AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_path_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features,
+                                                     int64_t n_rows, const int64_t *row_offsets, const double *y,
+                                                     const double *const *x_cols, const int64_t *train_counts,
+                                                     AnofoxHipQuantileBatchOptions options, const double *taus, size_t n_taus,
+                                                     double *quantile, int32_t *iterations, double *pred, AnofoxError *out_error);
 
 
 /*
