@@ -22,9 +22,15 @@
 //   finish      when no edge is violated: B is rebuilt from the basis rows, factorised by LU with partial pivoting, beta and a
 //               fresh B^-1 come from that factorisation, the residuals from the rows, and the optimality test runs again;
 //               if it fails the pivots go on (at most kQsMaxRestarts times).
-//   degeneracy  when no edge is violated but rows sit on their kink off the basis, another basis of the same vertex may still
-//               have a descending edge: one such row is exchanged for one basis element (a step of length zero), the test
-//               repeated, the element put back if nothing descends; at most kQsMaxExchanges trials per tau.
+//   degeneracy  when no edge descends but rows sit on their kink off the basis, the vertex is degenerate and another basis of it
+//               may still have a descending edge.  Each such row carries a side (the sign of its zero: the multiplier bound it
+//               is counted at); with the sides fixed the test is the plain simplex one, u within its bounds.  No violation: the
+//               multipliers are a certificate, the vertex is optimal.  Else a pivot of length zero: the most violated element
+//               leaves; the kink rows the move would push across their side block it at t = 0, in index order those whose
+//               weights |z_i| stay below -g change side and the next one enters (the line search's rule at t = 0); the leaving
+//               row takes the side it leaves towards; the test above runs on the new basis.  After kQsBlandAfter such pivots
+//               at one tau: Bland's rule (the violated element and the first blocking row of lowest index, no side changes),
+//               which cannot cycle; at most kQsMaxExchanges in all.
 //   tau path    a vertex is feasible for every tau (only the optimality test and the line search read it): qs_fit_path begins once
 //               and pivots from the vertex each tau's finish rebuilt to the optimum of the next (qs_fit = begin, pivot, record).
 // Pivots are bounded by min(max_iterations, qs_iteration_ceiling(k)); when the bound stops a fit the last vertex is
@@ -53,7 +59,11 @@ constexpr double kQsPivotTol = 1e-11; // |z_i| below this share of sum_c max_i|a
 constexpr double kQsSnapTol = 1e-12;  // |r_i| <= this share of max|y| is a zero residual
 constexpr double kQsStallTol = 1e-14; // a step that lowers the loss by less than this share of max|y|: Bland's rule from here on
 constexpr int kQsMaxRestarts = 3;     // failed optimality tests after a refactorisation that may resume the pivots
-constexpr int kQsMaxExchanges = 256;  // zero-length exchanges tried at degenerate vertices, per tau
+#ifndef QS_MAX_EXCHANGES // (a test builds the host program with 256 to show that a fit needs the pivots under Bland's rule)
+#define QS_MAX_EXCHANGES 1024
+#endif
+constexpr int kQsMaxExchanges = QS_MAX_EXCHANGES; // zero-length pivots at degenerate vertices, per tau (then the count is reported negated)
+constexpr int kQsBlandAfter = 256;    // of them before Bland's rule takes over
 
 constexpr int kQsStatusInvalidInput = 1;
 constexpr int kQsStatusInsufficientData = 6;
@@ -241,11 +251,34 @@ QS_DEV bool qs_refactor(const QsProblem &P, int k, int ld, double *M, double *Bi
 		if (!(P.r[i] == P.r[i])) continue; // masked at the first pass
 		double fit = 0.0;
 		for (int c = 0; c < k; ++c) fit += qs_elem(P, c, i) * beta[c];
+		const double old = P.r[i];
 		double rr = P.y[i] - fit;
-		if (fabs(rr) <= snap || qs_in_basis(basis, k, i)) rr = 0.0;
+		if (fabs(rr) <= snap || qs_in_basis(basis, k, i)) rr = old == 0.0 ? old : copysign(0.0, rr); // a kink row keeps its side
 		P.r[i] = rr;
 	}
 	return true;
+}
+
+// B^-1 when row `enter` takes the place of element bj (the rank-one formula), and the basis entry.
+QS_DEV void qs_replace(const QsProblem &P, int k, int ld, double *Binv, double *wrow, int64_t *basis, int bj, int64_t enter) {
+	const int lane = qs_lane();
+	for (int l = lane; l < k; l += QS_LANES) {
+		double acc = 0.0;
+		for (int c = 0; c < k; ++c) acc += qs_elem(P, c, enter) * Binv[l * ld + c];
+		wrow[l] = acc;
+	}
+	qs_sync();
+	const double wj = wrow[bj];
+	qs_sync();
+	for (int c = lane; c < k; c += QS_LANES) Binv[bj * ld + c] /= wj;
+	qs_sync();
+	for (int l = lane; l < k; l += QS_LANES) {
+		if (l == bj) continue;
+		const double wl = wrow[l];
+		for (int c = 0; c < k; ++c) Binv[l * ld + c] -= wl * Binv[bj * ld + c];
+	}
+	if (lane == 0) basis[bj] = enter;
+	qs_sync();
 }
 
 // What begin leaves for the pivots and the record of every tau of the group: the sizes, the scales and the slices of `work`.
@@ -339,10 +372,7 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 	int pivots = 0, restarts = 0;
 	bool fresh = false, converged = false, bland = false, singular = false;
 	uint64_t blocked = 0; // edges whose line search found no breakpoint since the last pivot
-	// the exchange at a degenerate vertex under trial: element esc_j gave way to row esc_i; the search resumes behind it
-	bool esc_active = false;
-	int esc_j = 0, esc_tries = 0;
-	int64_t esc_i = P.lo - 1, esc_old = 0;
+	int zero_pivots = 0;  // pivots of length zero at degenerate vertices (not part of the pivot count)
 
 	for (;;) {
 		// ---- s over the non-basis rows off their kink (basis rows have r = 0) ----
@@ -406,58 +436,112 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 				continue;
 			}
 			// ---- no edge of this basis descends.  With rows on their kink off the basis the vertex is degenerate: another
-			// basis of the same vertex may have an edge that does.  Exchange one element for one such row (a step of length
-			// zero: beta and the residuals stay), test again, and put the element back when nothing descends there either.
-			// Without such rows (or candidates) nothing here runs and the test above stands. ----
-			if (esc_active) { // the exchange tried last found nothing: back to the stalled basis, its B^-1 exactly as it was
-				if (lane == 0) basis[esc_j] = esc_old;
-				qs_sync();
-				if (!qs_refactor(P, k, ld, M, Binv, beta, v, basis, perm, snap)) { singular = true; break; }
-				esc_active = false;
+			// basis of it may have an edge that does.  Count every such row at the multiplier bound of its side (the sign of
+			// its zero): u of the plain simplex test.  Without such rows this is the test above over again. ----
+			for (int j = lane; j < k; j += QS_LANES) {
+				double u = 0.0;
+				for (int c = 0; c < k; ++c) u += s[c] * Binv[j * ld + c];
+				const bool row = basis[j] >= 0;
+				gp[j] = -u + (row ? 1.0 - tau : 0.0);
+				gm[j] = u + (row ? tau : 0.0);
 			}
-			bool found = false;
-			int fj = 0;
-			int64_t fi = 0;
-			for (int j = esc_j; j < k && !found && esc_tries < kQsMaxExchanges; ++j) {
-				double wscale = 0.0;
-				for (int c = 0; c < k; ++c) wscale += amax[c] * fabs(Binv[j * ld + c]);
-				const double wtol = kQsPivotTol * wscale;
-				for (int64_t c0 = j == esc_j ? esc_i + 1 : P.lo; c0 < P.hi && !found; c0 += QS_LANES) {
-					const int64_t i = c0 + lane;
-					bool cand = i < P.hi && P.r[i] == 0.0 && !qs_in_basis(basis, k, i);
-					if (cand) {
-						double w = 0.0;
-						for (int c = 0; c < k; ++c) w += qs_elem(P, c, i) * Binv[j * ld + c];
-						cand = fabs(w) > wtol; // the row can take element j's place
+			for (int64_t c0 = P.lo; c0 < P.hi; c0 += QS_LANES) {
+				const int64_t i = c0 + lane;
+				uint64_t m = qs_ballot(i < P.hi && P.r[i] == 0.0 && !qs_in_basis(basis, k, i));
+				while (m) {
+					const int bit = __builtin_ctzll(m);
+					m &= m - 1;
+					const int64_t ii = c0 + bit;
+					const double psi = __builtin_signbit(P.r[ii]) ? tau - 1.0 : tau;
+					for (int j = lane; j < k; j += QS_LANES) {
+						double zz = 0.0;
+						for (int c = 0; c < k; ++c) zz += qs_elem(P, c, ii) * Binv[j * ld + c];
+						gp[j] -= psi * zz;
+						gm[j] += psi * zz;
 					}
-					const uint64_t m = qs_ballot(cand);
-					if (m) { found = true; fj = j; fi = c0 + __builtin_ctzll(m); }
 				}
 			}
-			if (!found) { converged = true; break; }
-			++esc_tries;
-			esc_j = fj;
-			esc_i = fi;
-			esc_old = basis[fj];
+			// the most violated element; under Bland's rule the one of lowest index, artificials before rows
+			const bool zbland = zero_pivots >= kQsBlandAfter;
+			bestv = -1.0;
+			bj = -1;
+			for (int j = lane; j < k; j += QS_LANES) {
+				if ((blocked >> j) & 1ull) continue;
+				const double g = gp[j] < gm[j] ? gp[j] : gm[j];
+				if (g < -thr[j]) {
+					const double val = !zbland ? -g : -(basis[j] >= 0 ? (double)k + (double)(basis[j] - P.lo) : (double)(-1 - basis[j]));
+					if (bj < 0 || val > bestv) { bestv = val; bj = j; }
+				}
+			}
+			qs_argmax(bestv, bj);
 			qs_sync();
-			if (lane == 0) basis[fj] = fi;
+			if (bj < 0) { converged = true; break; } // the multipliers lie within their bounds: a certificate
+			if (zero_pivots >= kQsMaxExchanges) break;
+			const double sg = gp[bj] < gm[bj] ? 1.0 : -1.0;
+			for (int c = lane; c < k; c += QS_LANES) dvec[c] = sg * Binv[bj * ld + c];
 			qs_sync();
-			if (!qs_refactor(P, k, ld, M, Binv, beta, v, basis, perm, snap)) { singular = true; break; }
-			esc_active = true;
+			double zs = 0.0;
+			for (int c = 0; c < k; ++c) zs += amax[c] * fabs(dvec[c]);
+			const double zt = kQsPivotTol * zs;
+			// the kink rows that the move would push across their side block it at length zero, with weight |z_i|
+			const double need0 = -(gp[bj] < gm[bj] ? gp[bj] : gm[bj]);
+			double w0 = 0.0;
+			int64_t first0 = INT64_MAX;
+			for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+				const double ri = P.r[i];
+				double wz = 0.0;
+				if (ri == 0.0 && !qs_in_basis(basis, k, i)) {
+					double zi = 0.0;
+					for (int c = 0; c < k; ++c) zi += qs_elem(P, c, i) * dvec[c];
+					if (fabs(zi) > zt && (__builtin_signbit(ri) ? zi < 0.0 : zi > 0.0)) wz = fabs(zi);
+				}
+				P.z[i] = wz;
+				if (wz > 0.0) {
+					w0 += wz;
+					if (i < first0) first0 = i;
+				}
+			}
+			w0 = qs_sum(w0);
+			first0 = qs_min_i(first0);
+			if (first0 == INT64_MAX) { // nothing blocks: rounding in g; the edge rests until a pivot
+				blocked |= 1ull << bj;
+				continue;
+			}
+			int64_t enter0 = first0;
+			if (!zbland) {
+				// the first row, in index order, at which the weights sum to -g (all of them when rounding leaves less): by
+				// bisection over the row index, one reduction per bit
+				const double target = need0 < w0 ? need0 : w0;
+				int64_t ilo = P.lo - 1, ihi = P.hi - 1; // prefix(ilo) = 0 < target <= prefix(ihi)
+				while (ihi - ilo > 1) {
+					const int64_t mid = ilo + (ihi - ilo) / 2;
+					double pre = 0.0;
+					for (int64_t i = P.lo + lane; i <= mid; i += QS_LANES) pre += P.z[i];
+					pre = qs_sum(pre);
+					if (pre >= target) ihi = mid;
+					else ilo = mid;
+				}
+				int64_t last = -1; // the last blocking row at or below ihi enters, those before it change side
+				for (int64_t i = P.lo + lane; i <= ihi; i += QS_LANES)
+					if (P.z[i] > 0.0 && i > last) last = i;
+				enter0 = -qs_min_i(-last);
+				if (enter0 < first0) enter0 = first0;
+				for (int64_t i = P.lo + lane; i < enter0; i += QS_LANES)
+					if (P.z[i] > 0.0) P.r[i] = -P.r[i];
+			}
+			const int64_t out = basis[bj];
+			if (out >= 0 && (out - P.lo) % QS_LANES == lane) P.r[out] = sg > 0.0 ? -0.0 : 0.0; // r = -t sg along the move
+			qs_replace(P, k, ld, Binv, wrow, basis, bj, enter0);
+			++zero_pivots;
+			fresh = false;
 			blocked = 0;
 			continue;
 		}
-		const bool esc_hit = esc_active; // an exchanged basis has a descending edge: the pivots go on from it
-		if (esc_active) {
-			esc_active = false;
-			esc_j = 0;
-			esc_i = P.lo - 1;
-		}
-		if (pivots >= max_it || (fresh && !esc_hit && restarts >= kQsMaxRestarts)) {
+		if (pivots >= max_it || (fresh && restarts >= kQsMaxRestarts)) {
 			if (!fresh && !qs_refactor(P, k, ld, M, Binv, beta, v, basis, perm, snap)) singular = true;
 			break;
 		}
-		if (fresh && !esc_hit) ++restarts;
+		if (fresh) ++restarts;
 		const double sigma = gp[bj] < gm[bj] ? 1.0 : -1.0;
 		const double need = -(gp[bj] < gm[bj] ? gp[bj] : gm[bj]);
 		const int64_t leaving = basis[bj];
@@ -529,24 +613,7 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 			if (i == enter) rn = 0.0;
 			P.r[i] = rn;
 		}
-		// ---- B^-1: row `enter` replaces element bj ----
-		for (int l = lane; l < k; l += QS_LANES) {
-			double acc = 0.0;
-			for (int c = 0; c < k; ++c) acc += qs_elem(P, c, enter) * Binv[l * ld + c];
-			wrow[l] = acc;
-		}
-		qs_sync();
-		const double wj = wrow[bj];
-		qs_sync();
-		for (int c = lane; c < k; c += QS_LANES) Binv[bj * ld + c] /= wj;
-		qs_sync();
-		for (int l = lane; l < k; l += QS_LANES) {
-			if (l == bj) continue;
-			const double wl = wrow[l];
-			for (int c = 0; c < k; ++c) Binv[l * ld + c] -= wl * Binv[bj * ld + c];
-		}
-		if (lane == 0) basis[bj] = enter;
-		qs_sync();
+		qs_replace(P, k, ld, Binv, wrow, basis, bj, enter);
 		++pivots;
 		fresh = false;
 		blocked = 0;

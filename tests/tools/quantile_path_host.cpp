@@ -76,7 +76,7 @@ int main() {
 		for (double &w : work) w = 3.25;
 		qs_fit_path(P, sorted, slot, n_ok, n_taus, work.data(), rec2.data(), its2.data(), pred2.data());
 		if (memcmp(its.data(), its2.data(), T * sizeof(int32_t)) != 0 || memcmp(rec.data(), rec2.data(), rec.size() * sizeof(double)) != 0 ||
-		    memcmp(pred.data(), pred2.data(), pred.size() * sizeof(double)) != 0) {
+		    (!pred.empty() && memcmp(pred.data(), pred2.data(), pred.size() * sizeof(double)) != 0)) { // (a group of no rows: no bytes)
 			fprintf(stderr, "ERROR: the path depends on the contents of its scratch\n");
 			return 3;
 		}
