@@ -20,12 +20,13 @@ from .aggregate import (StreamingStates, FitAggResult, FitPredictAggResult, OlsF
                         elasticnet_fit_predict, RlsFitAgg, rls_fit_agg, RlsFitPredictAgg, rls_fit_predict_agg,
                         rls_fit_predict, BlsFitAggResult, BlsFitAgg, NnlsFitAgg, BlsFitPredictAgg, bls_fit_agg, nnls_fit_agg,
                         bls_fit_predict_agg, bls_result_from_records, QuantileFitPredictAgg, quantile_fit_predict_agg,
-                        QuantilePathFitPredictAgg, QuantilePathFitPredictAggResult, quantile_path_fit_predict_agg)
+                        QuantilePathFitPredictAgg, QuantilePathFitPredictAggResult, quantile_path_fit_predict_agg,
+                        quantile_fit_predict)
 from .options import (ElasticNetOptions, ElasticNetPredictOptions, InvalidInputException, RegressionOptions,  # noqa: E402
                       parse_elasticnet_options, parse_elasticnet_predict_options, parse_options, RlsOptions,
                       parse_rls_options, BlsOptions, parse_bls_options, parse_nnls_options, parse_bls_predict_options,
                       QuantileOptions, parse_quantile_options, QuantilePathOptions, parse_quantile_path_options)
-from .runtime import AggState, Context, quantile_fit_path_batch_host, quantile_fit_path_batch_device, quantile_fit_predict_path_batch_host, quantile_fit_batch_host, quantile_fit_predict_batch_host, bls_fit_batch_host, bls_fit_predict_batch_host, rls_fit_batch_host, rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
+from .runtime import AggState, Context, quantile_fit_predict_window_host, quantile_fit_predict_frames_host, quantile_window_plan, quantile_window_test_hooks, quantile_window_stats, quantile_fit_path_batch_host, quantile_fit_path_batch_device, quantile_fit_predict_path_batch_host, quantile_fit_batch_host, quantile_fit_predict_batch_host, bls_fit_batch_host, bls_fit_predict_batch_host, rls_fit_batch_host, rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
 from .scalar import quantile_fit, quantile_fit_path, aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
@@ -68,6 +69,8 @@ __all__ = [
     "QuantilePathOptions", "parse_quantile_path_options", "quantile_fit_path", "QuantilePathFitPredictAgg",
     "QuantilePathFitPredictAggResult", "quantile_path_fit_predict_agg", "quantile_fit_path_batch_host",
     "quantile_fit_path_batch_device", "quantile_fit_predict_path_batch_host",
+    "quantile_fit_predict", "quantile_fit_predict_window_host", "quantile_fit_predict_frames_host", "quantile_window_plan",
+    "quantile_window_test_hooks", "quantile_window_stats",
 ]
 
 

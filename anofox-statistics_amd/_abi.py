@@ -373,6 +373,23 @@ SYMBOLS = {
     "anofox_hip_quantile_fit_predict_path_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
                                                                    C.POINTER(_DP), C.POINTER(C.c_int64), AnofoxHipQuantileBatchOptions,
                                                                    _DP, C.c_size_t, _DP, C.POINTER(C.c_int32), _DP, _ERRP]),
+    "anofox_hip_quantile_fit_predict_window_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                                 C.POINTER(C.c_void_p), AnofoxHipWindowFrame,
+                                                                 AnofoxHipQuantileBatchOptions, C.c_void_p, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_quantile_fit_predict_window_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                               C.POINTER(_DP), AnofoxHipWindowFrame, AnofoxHipQuantileBatchOptions,
+                                                               _DP, _DP, C.POINTER(C.c_int32), _ERRP]),
+    "anofox_hip_quantile_fit_predict_frames_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p),
+                                                                 C.c_void_p, C.c_void_p, AnofoxHipQuantileBatchOptions, C.c_void_p,
+                                                                 C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_quantile_fit_predict_frames_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, _DP, C.POINTER(_DP), C.POINTER(C.c_int64),
+                                                               C.POINTER(C.c_int64), AnofoxHipQuantileBatchOptions, _DP, _DP,
+                                                               C.POINTER(C.c_int32), _ERRP]),
+    "anofox_hip_quantile_window_plan": (C.c_bool, [C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64),
+                                                   C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_int64,
+                                                   C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ERRP]),
+    "anofox_hip_quantile_window_test_hooks": (None, [C.c_int64, C.c_int64]),
+    "anofox_hip_quantile_window_stats": (C.c_bool, [_CTX, C.POINTER(C.c_int64), _ERRP]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "anofox_hip_host_free": (None, [C.c_void_p]),
 }

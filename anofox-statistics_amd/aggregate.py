@@ -1108,8 +1108,44 @@ def quantile_path_fit_predict_agg(group_keys, y, x, options, context=None, split
     return QuantilePathFitPredictAgg(options, context).update(group_keys, y, x, split=split).finalize()
 
 
+def quantile_fit_predict(partition_keys, order, y, x, options=None, context=None, frame_end="current row", frame=None):
+    """quantile_fit_predict(y, x [, options]) OVER (PARTITION BY partition_keys ORDER BY order ROWS ...): the quantile
+    regression of every row's frame (rolling medians, rolling quantile bands), predicting the x of the frame's last row.
+    Returns (yhat, yhat_lower, yhat_upper) per input row, in input order, as elasticnet_fit_predict does; there is no interval,
+    so both bounds are NaN, and NaN = SQL NULL.  Frames as ols_fit_predict; options as quantile_fit_predict_agg (tau,
+    fit_intercept, max_iterations, tolerance).  The row rules are the aggregate's, per frame: fewer than 2 rows with a
+    non-NULL y, or fewer valid rows than p + [intercept], give NULL."""
+    from .options import parse_quantile_options
+    from .runtime import quantile_fit_predict_window_host
+    opts = parse_quantile_options(options)
+    start, end = _parse_frame(frame, frame_end)
+    keys = np.asarray(partition_keys)
+    yv, ynull = _null_mask_1d(y)
+    yv = np.where(ynull, np.nan, yv)
+    rows = [None if r is None else [np.nan if v is None else float(v) for v in r] for r in x]
+    p = max((len(r) for r in rows if r is not None), default=0)
+    Xd = np.full((len(yv), p), np.nan)
+    for i, r in enumerate(rows):
+        if r is None:
+            continue                                             # NULL x list: no current x, no training
+        if len(r) != p:
+            raise InvalidInputException(f"Inconsistent feature count: expected {p}, got {len(r)}")
+        Xd[i] = r
+    ukeys, gid = np.unique(keys, return_inverse=True)
+    perm = np.lexsort((np.asarray(order), gid))
+    counts = np.bincount(gid, minlength=len(ukeys))
+    offsets = np.zeros(len(ukeys) + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    pred_sorted = quantile_fit_predict_window_host(offsets, yv[perm], [np.ascontiguousarray(Xd[perm, j]) for j in range(p)],
+                                                   opts.batch_options(), (start, end), ctx=context)
+    out = np.empty_like(pred_sorted)
+    out[perm] = pred_sorted
+    return out[:, 0], out[:, 1], out[:, 2]
+
+
 SQL_FUNCTIONS.update({
     "anofox_stats_quantile_fit_predict_agg": quantile_fit_predict_agg, "quantile_fit_predict_agg": quantile_fit_predict_agg,
+    "anofox_stats_quantile_fit_predict": quantile_fit_predict, "quantile_fit_predict": quantile_fit_predict,
     "anofox_stats_quantile_path_fit_predict_agg": quantile_path_fit_predict_agg,
     "quantile_path_fit_predict_agg": quantile_path_fit_predict_agg,
 })

@@ -41,6 +41,12 @@ struct AnofoxHipContext {
 	void *wtab = nullptr;
 	size_t wtab_bytes = 0;
 	double wtab_conf = -1.0;
+	// the quantile window function's last launch on this context (quantile.hip): per walker {frames begun afresh, of them after
+	// a fitted frame} in a buffer of its own, so that no other call overwrites it; reset by every window call
+	void *qw_counts = nullptr;
+	size_t qw_counts_bytes = 0;
+	int64_t qw_frames = 0, qw_walkers = 0, qw_waves = 0, qw_span = 0;
+	bool qw_valid = false;
 	// timing
 	bool timing = false;
 	std::vector<hipEvent_t> free_events;

@@ -1,6 +1,7 @@
 // quantile.hip — grouped quantile regression: one wavefront per group runs the exact simplex of quantile_solve.h over the
 // group's rows, and the entry points anofox_hip_quantile_fit_batch_{device,host}, anofox_hip_quantile_fit_predict_batch_*,
-// anofox_quantile_fit / anofox_free_quantile_result, and their tau-path siblings (*_path_*).
+// anofox_quantile_fit / anofox_free_quantile_result, their tau-path siblings (*_path_*) and the window function
+// anofox_hip_quantile_fit_predict_{window,frames}_*.
 //
 // The contract and the method: quantile_solve.h and DESIGN.md §1, "Quantile regression".
 //   quantile_fit_kernel: 64 lanes per workgroup = one wavefront per group (grid-stride over the groups).  LDS holds B^-1 and
@@ -11,6 +12,11 @@
 //     anofox_hip_quantile_fit_predict_path_batch_*, anofox_quantile_fit_path): qs_fit_path begins once and pivots from each
 //     tau's vertex to the next; the grid (sorted by the host, at most kQsMaxTaus) travels in the kernel arguments.  With a
 //     prediction buffer the wavefront writes pred[i T + t] = a_i'beta_t of its group's rows right after tau_t's record.
+//   quantile_window_kernel: the window function (anofox_hip_quantile_fit_predict_{window,frames}_*).  One wavefront per WALKER,
+//     grid-stride over the walkers: a walker is a run of consecutive output rows of one partition, and qs_fit_window carries the
+//     optimal vertex from each row's frame to the next.  The same LDS; the scratch is a slab of 3 doubles per row of the longest
+//     span of any run (last frame's end - first frame's start) that belongs to the LAUNCHED wavefront (blockIdx), indexed by
+//     row - origin, so overlapping frames of neighbouring walkers never share a slot.  plan_window below cuts the runs.
 //   quantile_nan_bounds_kernel: the fit-predict entry points hand the records (regression layout, sigma = NaN) to the
 //     existing predict kernels, which give yhat = lower = upper for a NaN sigma; quantile regression has no interval, so
 //     the two bounds are then overwritten with NaN.
@@ -19,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -103,6 +110,53 @@ __global__ __launch_bounds__(64) void quantile_path_kernel(QuantilePathArgs a) {
 		qs_fit_path(P, a.taus, a.slot, a.n_ok, a.n_taus, quantile_lds, a.q.core + g * T * (int64_t)(a.q.p + 6),
 		            a.q.iterations ? a.q.iterations + g * T : nullptr, a.pred);
 		__syncthreads(); // the next group reuses the LDS
+	}
+}
+
+struct QuantileWindowArgs {
+	const int64_t *lo, *hi;   // [n_rows]: the frame of output row e is rows [lo[e], hi[e])
+	const int64_t *run_begin; // [n_runs + 1]: walker w owns the output rows [run_begin[w], run_begin[w + 1])
+	const double *y;
+	const double *x[kQsMaxP];
+	double *scratch; // [gridDim.x x 3 x slab_rows]
+	int32_t *cold;   // [n_runs x 2]: the frames of walker w that began afresh, and those of them that followed a fitted frame
+	int64_t n_runs;
+	int64_t slab_rows;
+	int p;
+	int fit_intercept;
+	double tau;
+	int max_iterations;
+	int invalid;
+	double *pred;        // [n_rows x 3]
+	double *rec;         // [n_rows x (p + 6)] or nullptr
+	int32_t *iterations; // [n_rows] or nullptr
+};
+
+__global__ __launch_bounds__(64) void quantile_window_kernel(QuantileWindowArgs a) {
+	extern __shared__ double quantile_lds[];
+	double *slab = a.scratch + (int64_t)blockIdx.x * 3 * a.slab_rows; // this wavefront's, whichever walker it runs
+	for (int64_t w = blockIdx.x; w < a.n_runs; w += gridDim.x) {
+		QsProblem P;
+		P.y = a.y;
+		P.x = a.x;
+		P.p = a.p;
+		P.fit_intercept = a.fit_intercept;
+		P.lo = P.hi = 0;
+		P.rule_count = 0;
+		P.tau = a.tau;
+		P.max_iterations = a.max_iterations;
+		P.predict_layout = 0;
+		P.r = slab;
+		P.z = slab + a.slab_rows;
+		P.t = slab + 2 * a.slab_rows;
+		int64_t n_restart = 0;
+		const int64_t n_cold = qs_fit_window(P, a.invalid != 0, a.lo, a.hi, a.run_begin[w], a.run_begin[w + 1], a.slab_rows, quantile_lds,
+		                                     a.pred, a.rec, a.iterations, nullptr, &n_restart);
+		if (threadIdx.x == 0) {
+			a.cold[2 * w] = (int32_t)n_cold;
+			a.cold[2 * w + 1] = (int32_t)n_restart;
+		}
+		__syncthreads(); // the next walker reuses the LDS and the slab
 	}
 }
 
@@ -267,6 +321,196 @@ bool fill_scalar_result(const double *rec, size_t p, AnofoxQuantileFitResultCore
 	out_core->n_observations = (size_t)rec[p + 4];
 	out_core->n_features = p;
 	return true;
+}
+
+// ---- the window function ----
+// The planner.  Walkers: every partition is cut into runs of consecutive output rows, min(ceil(n_g / L), n_g / kQwMinRun) of
+// them (at least one) of equal length (the last one shorter), L = ceil(n_rows / kQwTargetWalkers): with many partitions a run
+// is a whole partition, with few long ones there are about kQwTargetWalkers walkers, and no run is shorter than kQwMinRun
+// rows unless its partition is (every run begins with a cold fit, which the rows after it have to pay for).  A partition all of whose frames start at the same
+// row (UNBOUNDED PRECEDING) is one run: every run of it would span the partition anyway.  span = the longest
+// chain of a run (last hi - first lo of consecutive monotone, overlapping frames); a launched wavefront owns 3 span doubles, and
+// waves = min(runs, kQwMaxWaves, cap / (24 span)): the scratch never exceeds the cap (kQwScratchCap unless a test sets
+// another), and a span that does not fit once fails the call.
+constexpr int64_t kQwMinRun = 64;
+constexpr int64_t kQwTargetWalkers = 8192;
+constexpr int64_t kQwMaxWaves = 8192;
+constexpr int64_t kQwScratchCap = 1ll << 30;
+
+std::mutex g_qw_mu;
+int64_t g_qw_run_length = 0, g_qw_scratch_cap = 0; // anofox_hip_quantile_window_test_hooks (0: the rule above)
+
+struct WindowPlan {
+	std::vector<int64_t> run_begin; // walkers + 1
+	int64_t span = 0, waves = 0;
+};
+
+bool plan_window(int64_t n_parts, const int64_t *off, const int64_t *lo, const int64_t *hi, int64_t run_length, int64_t cap_bytes,
+                 WindowPlan &plan, AnofoxError *e) {
+	plan.run_begin.clear();
+	plan.span = plan.waves = 0;
+	const int64_t N = n_parts > 0 ? off[n_parts] - off[0] : 0;
+	if (cap_bytes <= 0) cap_bytes = kQwScratchCap;
+	int64_t L = run_length;
+	if (L <= 0) {
+		L = (N + kQwTargetWalkers - 1) / kQwTargetWalkers;
+		if (L < 1) L = 1;
+	}
+	for (int64_t g = 0; g < n_parts; ++g) {
+		const int64_t b = off[g], n = off[g + 1] - b;
+		if (n <= 0) continue;
+		int64_t pieces = (n + L - 1) / L;
+		if (run_length <= 0 && pieces > n / kQwMinRun) pieces = n / kQwMinRun > 0 ? n / kQwMinRun : 1; // no run below kQwMinRun rows
+		if (run_length <= 0 && pieces > 1) { // frames that all start at one row: one walker
+			int64_t first = -1;
+			bool same = true;
+			for (int64_t r = b; r < b + n && same; ++r) {
+				if (hi[r] <= lo[r]) continue;
+				if (first < 0) first = lo[r];
+				same = lo[r] == first;
+			}
+			if (same) pieces = 1;
+		}
+		const int64_t len = (n + pieces - 1) / pieces;
+		for (int64_t r = b; r < b + n; r += len) plan.run_begin.push_back(r);
+	}
+	const int64_t runs = (int64_t)plan.run_begin.size();
+	plan.run_begin.push_back(n_parts > 0 ? off[n_parts] : 0);
+	if (runs == 0) return true;
+	// (a run ends where the next begins or at its partition's end: the runs are contiguous over the partitions' rows, and an
+	// empty partition owns none)
+	// the walk sets its scratch origin wherever it begins afresh, so a slab has to hold the longest CHAIN of a run: consecutive
+	// non-empty frames whose bounds are both non-decreasing and that overlap (qs_fit_window's rule; a basis row that leaves or
+	// a failed frame only cuts a chain shorter).  Unsorted or far-apart explicit frames therefore cost no scratch.
+	for (int64_t w = 0; w < runs; ++w) {
+		bool have = false;
+		int64_t origin = 0, plo = 0, phi = 0;
+		for (int64_t r = plan.run_begin[(size_t)w]; r < plan.run_begin[(size_t)w + 1]; ++r) {
+			if (hi[r] <= lo[r]) { have = false; continue; }
+			if (!(have && lo[r] >= plo && hi[r] >= phi && lo[r] < phi)) origin = lo[r];
+			have = true;
+			plo = lo[r];
+			phi = hi[r];
+			if (phi - origin > plan.span) plan.span = phi - origin;
+		}
+	}
+	if (plan.span < 1) plan.span = 1;
+	const int64_t fit = cap_bytes / (3 * (int64_t)sizeof(double)) / plan.span;
+	if (fit < 1) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT,
+		          "quantile window: frame span " + std::to_string(plan.span) + " exceeds the scratch budget (" + std::to_string(cap_bytes) +
+		              " bytes, 24 per row)");
+		return false;
+	}
+	plan.waves = runs < kQwMaxWaves ? runs : kQwMaxWaves;
+	if (fit < plan.waves) plan.waves = fit;
+	return true;
+}
+
+// the frames of ROWS BETWEEN start PRECEDING AND end PRECEDING, clipped to the partition: frames_spec_kernel's arithmetic
+void rows_frames(int64_t G, const int64_t *off, const AnofoxHipWindowFrame &f, int64_t *lo, int64_t *hi) {
+	for (int64_t g = 0; g < G; ++g) {
+		const int64_t plo = off[g], phi = off[g + 1];
+		for (int64_t r = plo; r < phi; ++r) {
+			int64_t first = f.start_preceding == ANOFOX_HIP_FRAME_UNBOUNDED ? plo : r - f.start_preceding;
+			int64_t last = f.end_preceding == -ANOFOX_HIP_FRAME_UNBOUNDED ? phi - 1 : r - f.end_preceding;
+			if (first < plo) first = plo;
+			if (last > phi - 1) last = phi - 1;
+			const bool empty = last < first;
+			lo[r] = empty ? r : first;
+			hi[r] = empty ? r : last + 1;
+		}
+	}
+}
+
+bool check_window_frame(const AnofoxHipWindowFrame &f, AnofoxError *e) {
+	if (f.start_preceding < f.end_preceding || f.start_preceding == -ANOFOX_HIP_FRAME_UNBOUNDED || f.end_preceding == ANOFOX_HIP_FRAME_UNBOUNDED) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "window frame must start at or before its end");
+		return false;
+	}
+	return true;
+}
+
+bool check_window_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
+	if (!check_host_offsets(G, n_rows, off, e)) return false;
+	if (G > 0 && (off[0] != 0 || off[G] != n_rows)) { // every output row belongs to a partition's walker
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
+		return false;
+	}
+	return true;
+}
+
+bool check_host_frames(int64_t n_rows, const int64_t *lo, const int64_t *hi, AnofoxError *e) {
+	for (int64_t r = 0; r < n_rows; ++r) {
+		if (hi[r] > lo[r] && (lo[r] < 0 || hi[r] > n_rows)) {
+			set_error(e, ANOFOX_ERROR_INVALID_INPUT, "frame bounds must lie within [0, n_rows]");
+			return false;
+		}
+	}
+	return true;
+}
+
+bool check_window_args(int64_t n_rows, size_t p, const void *y, const double *const *x_cols, const void *pred, AnofoxError *e) {
+	if (n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
+	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
+	if (p > (size_t)kQsMaxP) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "quantile regression: n_features > 32 is not built"); return false; }
+	if (n_rows > 0 && (!y || !pred)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "y or pred is NULL"); return false; }
+	for (size_t j = 0; j < p; ++j)
+		if (n_rows > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
+	return true;
+}
+
+// The walk of a planned call on device-resident rows and frames (ctx->mu held by the caller).  The workspace holds the slabs,
+// then the run table, which is copied before the launch (the stream is synchronised: the plan is the caller's local).  The
+// walkers' cold-start counts go to a buffer of the context that nothing else uses (anofox_hip_quantile_window_stats).
+bool launch_quantile_window(AnofoxHipContext *ctx, size_t p, int64_t n_rows, const double *d_y, const double *const *x_cols,
+                            const int64_t *d_lo, const int64_t *d_hi, const WindowPlan &plan, const AnofoxHipQuantileBatchOptions &o,
+                            double *d_pred, double *d_rec, int32_t *d_iterations, AnofoxError *e) {
+	const int64_t runs = (int64_t)plan.run_begin.size() - 1;
+	ctx->qw_valid = false;
+	if (runs <= 0 || n_rows == 0) return true;
+	const size_t slabs = align_up((size_t)plan.waves * 3 * (size_t)plan.span * sizeof(double), 256);
+	const size_t table = align_up(((size_t)runs + 1) * sizeof(int64_t), 256);
+	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, slabs + table, "quantile window scratch", e)) return false;
+	if (!ensure_buffer(&ctx->qw_counts, &ctx->qw_counts_bytes, 2 * (size_t)runs * sizeof(int32_t), "quantile window counts", e)) return false;
+	QuantileWindowArgs a;
+	memset(&a, 0, sizeof a);
+	a.lo = d_lo;
+	a.hi = d_hi;
+	a.run_begin = (const int64_t *)((char *)ctx->ws + slabs);
+	a.y = d_y;
+	for (size_t j = 0; j < p; ++j) a.x[j] = x_cols[j];
+	a.scratch = (double *)ctx->ws;
+	a.cold = (int32_t *)ctx->qw_counts;
+	a.n_runs = runs;
+	a.slab_rows = plan.span;
+	a.p = (int)p;
+	a.fit_intercept = o.fit_intercept ? 1 : 0;
+	a.tau = o.tau;
+	a.max_iterations = o.max_iterations > 0x7fffffffu ? 0x7fffffff : (int)o.max_iterations;
+	a.invalid = tau_invalid(o.tau) ? 1 : 0;
+	a.pred = d_pred;
+	a.rec = d_rec;
+	a.iterations = d_iterations;
+	if (hip_fail(hipMemcpyAsync((void *)a.run_begin, plan.run_begin.data(), ((size_t)runs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream),
+	             "H2D", e) ||
+	    hip_fail(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize", e))
+		return false;
+	const int k = (int)p + a.fit_intercept;
+	hipLaunchKernelGGL(quantile_window_kernel, dim3((unsigned)plan.waves), dim3(64), qs_work_doubles(k) * sizeof(double), ctx->stream, a);
+	if (hip_fail(hipGetLastError(), "quantile_window_kernel", e)) return false;
+	ctx->qw_frames = n_rows;
+	ctx->qw_walkers = runs;
+	ctx->qw_waves = plan.waves;
+	ctx->qw_span = plan.span;
+	ctx->qw_valid = true;
+	return true;
+}
+
+void window_hooks(int64_t *run_length, int64_t *cap) {
+	std::lock_guard<std::mutex> lk(g_qw_mu);
+	*run_length = g_qw_run_length;
+	*cap = g_qw_scratch_cap;
 }
 
 } // namespace
@@ -609,6 +853,199 @@ bool anofox_quantile_fit_path(AnofoxDataArray y, const AnofoxDataArray *x, size_
 			return false;
 		}
 	}
+	return true;
+}
+
+// ---- the window function: anofox_hip_quantile_fit_predict_{window,frames}_{device,host} ----
+// The device variants read the partition offsets / the frame bounds back to the host for the planner (one synchronising copy).
+
+bool anofox_hip_quantile_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                   const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                   AnofoxHipWindowFrame frame, AnofoxHipQuantileBatchOptions options, double *d_pred,
+                                                   double *d_quantile, int32_t *d_iterations, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (n_groups < 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
+	if (!check_window_args(n_rows, n_features, d_y, x_cols, d_pred, out_error)) return false;
+	if (!check_window_frame(frame, out_error)) return false;
+	if (n_groups > 0 && !d_row_offsets) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets is NULL"); return false; }
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	if (n_groups == 0 || n_rows == 0) return true;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	hipStream_t st = ctx->stream;
+	const size_t G = (size_t)n_groups, N = (size_t)n_rows;
+	std::vector<int64_t> off(G + 1), lo(N), hi(N);
+	if (!d2h(off.data(), d_row_offsets, (G + 1) * sizeof(int64_t), st, out_error)) return false;
+	if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
+	if (!check_window_offsets(n_groups, n_rows, off.data(), out_error)) return false;
+	rows_frames(n_groups, off.data(), frame, lo.data(), hi.data());
+	int64_t run_length, cap;
+	window_hooks(&run_length, &cap);
+	WindowPlan plan;
+	if (!plan_window(n_groups, off.data(), lo.data(), hi.data(), run_length, cap, plan, out_error)) return false;
+	const size_t b = Stage::bytes(N, sizeof(int64_t));
+	if (!ensure_buffer(&ctx->frames_buf, &ctx->frames_bytes, 2 * b, "window frames", out_error)) return false;
+	int64_t *d_lo = (int64_t *)ctx->frames_buf, *d_hi = (int64_t *)((char *)ctx->frames_buf + b);
+	if (!h2d(d_lo, lo.data(), N * sizeof(int64_t), st, out_error) || !h2d(d_hi, hi.data(), N * sizeof(int64_t), st, out_error)) return false;
+	return launch_quantile_window(ctx, n_features, n_rows, d_y, x_cols, d_lo, d_hi, plan, options, d_pred, d_quantile, d_iterations, out_error);
+}
+
+bool anofox_hip_quantile_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *d_y,
+                                                   const double *const *x_cols, const int64_t *d_frame_lo, const int64_t *d_frame_hi,
+                                                   AnofoxHipQuantileBatchOptions options, double *d_pred, double *d_quantile,
+                                                   int32_t *d_iterations, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_window_args(n_rows, n_features, d_y, x_cols, d_pred, out_error)) return false;
+	if (n_rows > 0 && (!d_frame_lo || !d_frame_hi)) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "frame_lo or frame_hi is NULL"); return false; }
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	if (n_rows == 0) return true;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	hipStream_t st = ctx->stream;
+	const size_t N = (size_t)n_rows;
+	std::vector<int64_t> lo(N), hi(N);
+	if (!d2h(lo.data(), d_frame_lo, N * sizeof(int64_t), st, out_error) || !d2h(hi.data(), d_frame_hi, N * sizeof(int64_t), st, out_error)) return false;
+	if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
+	if (!check_host_frames(n_rows, lo.data(), hi.data(), out_error)) return false;
+	const int64_t off[2] = {0, n_rows};
+	int64_t run_length, cap;
+	window_hooks(&run_length, &cap);
+	WindowPlan plan;
+	if (!plan_window(1, off, lo.data(), hi.data(), run_length, cap, plan, out_error)) return false;
+	return launch_quantile_window(ctx, n_features, n_rows, d_y, x_cols, d_frame_lo, d_frame_hi, plan, options, d_pred, d_quantile, d_iterations,
+	                              out_error);
+}
+
+namespace {
+// both host entry points: the frames are the caller's (frames) or come from the ROWS spec (window); one lock over staging,
+// the kernel and the copies back
+bool quantile_window_host(AnofoxHipContext *ctx, int64_t n_parts, const int64_t *off, size_t p, int64_t n_rows, const double *y,
+                          const double *const *x_cols, const int64_t *lo, const int64_t *hi, const AnofoxHipQuantileBatchOptions &options,
+                          double *pred, double *quantile, int32_t *iterations, AnofoxError *out_error) {
+	int64_t run_length, cap;
+	window_hooks(&run_length, &cap);
+	WindowPlan plan;
+	if (!plan_window(n_parts, off, lo, hi, run_length, cap, plan, out_error)) return false;
+	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	const size_t N = (size_t)n_rows, rec_len = p + 6;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	const size_t need = 2 * Stage::bytes(N, 8) + (p + 1) * Stage::bytes(N, 8) + Stage::bytes(3 * N, 8) + Stage::bytes(N * rec_len, 8) +
+	                    Stage::bytes(N, 4);
+	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
+	hipStream_t st = ctx->stream;
+	Stage s{(char *)ctx->stage};
+	int64_t *d_lo = s.take<int64_t>(N), *d_hi = s.take<int64_t>(N);
+	if (!h2d(d_lo, lo, N * sizeof(int64_t), st, out_error) || !h2d(d_hi, hi, N * sizeof(int64_t), st, out_error)) return false;
+	const double *d_x[kQsMaxP];
+	for (size_t j = 0; j < p; ++j) {
+		double *c = s.take<double>(N);
+		if (!h2d(c, x_cols[j], N * sizeof(double), st, out_error)) return false;
+		d_x[j] = c;
+	}
+	double *d_y = s.take<double>(N);
+	if (!h2d(d_y, y, N * sizeof(double), st, out_error)) return false;
+	double *d_pred = s.take<double>(3 * N);
+	double *d_rec = s.take<double>(N * rec_len);
+	int32_t *d_it = s.take<int32_t>(N);
+	if (!launch_quantile_window(ctx, p, n_rows, d_y, d_x, d_lo, d_hi, plan, options, d_pred, quantile ? d_rec : nullptr,
+	                            iterations ? d_it : nullptr, out_error))
+		return false;
+	if (!d2h(pred, d_pred, 3 * N * sizeof(double), st, out_error)) return false;
+	if (quantile && !d2h(quantile, d_rec, N * rec_len * sizeof(double), st, out_error)) return false;
+	if (iterations && !d2h(iterations, d_it, N * sizeof(int32_t), st, out_error)) return false;
+	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
+}
+} // namespace
+
+bool anofox_hip_quantile_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                 const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                 AnofoxHipWindowFrame frame, AnofoxHipQuantileBatchOptions options, double *pred,
+                                                 double *quantile, int32_t *iterations, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (n_groups < 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
+	if (!check_window_args(n_rows, n_features, y, x_cols, pred, out_error)) return false;
+	if (!check_window_frame(frame, out_error)) return false;
+	if (n_groups > 0 && !row_offsets) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets is NULL"); return false; }
+	if (n_groups > 0 && !check_window_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (n_groups == 0 || n_rows == 0) return true;
+	std::vector<int64_t> lo((size_t)n_rows), hi((size_t)n_rows);
+	rows_frames(n_groups, row_offsets, frame, lo.data(), hi.data());
+	return quantile_window_host(ctx, n_groups, row_offsets, n_features, n_rows, y, x_cols, lo.data(), hi.data(), options, pred, quantile,
+	                            iterations, out_error);
+}
+
+bool anofox_hip_quantile_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y,
+                                                 const double *const *x_cols, const int64_t *frame_lo, const int64_t *frame_hi,
+                                                 AnofoxHipQuantileBatchOptions options, double *pred, double *quantile, int32_t *iterations,
+                                                 AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_window_args(n_rows, n_features, y, x_cols, pred, out_error)) return false;
+	if (n_rows > 0 && (!frame_lo || !frame_hi)) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "frame_lo or frame_hi is NULL"); return false; }
+	if (!check_host_frames(n_rows, frame_lo, frame_hi, out_error)) return false;
+	if (n_rows == 0) return true;
+	const int64_t off[2] = {0, n_rows};
+	return quantile_window_host(ctx, 1, off, n_features, n_rows, y, x_cols, frame_lo, frame_hi, options, pred, quantile, iterations, out_error);
+}
+
+// The planner alone, on host arrays: run_begin (capacity entries, may be NULL with capacity 0) receives the first output row of
+// every walker and one entry past them, *n_runs their number, *span_rows the scratch rows of one wavefront, *n_waves the
+// wavefronts a launch would use.  run_length / scratch_cap_bytes 0: the rule of the library.
+bool anofox_hip_quantile_window_plan(int64_t n_groups, const int64_t *row_offsets, int64_t n_rows, const int64_t *frame_lo,
+                                     const int64_t *frame_hi, int64_t run_length, int64_t scratch_cap_bytes, int64_t *run_begin,
+                                     int64_t capacity, int64_t *n_runs, int64_t *span_rows, int64_t *n_waves, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (n_groups < 0 || n_rows < 0 || !n_runs || !span_rows || !n_waves || (n_groups > 0 && !row_offsets) || (n_rows > 0 && (!frame_lo || !frame_hi))) {
+		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "quantile window plan: a NULL or negative argument");
+		return false;
+	}
+	if (n_groups > 0 && !check_window_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (!check_host_frames(n_rows, frame_lo, frame_hi, out_error)) return false;
+	WindowPlan plan;
+	if (!plan_window(n_groups, row_offsets, frame_lo, frame_hi, run_length, scratch_cap_bytes, plan, out_error)) return false;
+	*n_runs = (int64_t)plan.run_begin.size() - 1;
+	*span_rows = plan.span;
+	*n_waves = plan.waves;
+	if (run_begin) {
+		if (capacity < (int64_t)plan.run_begin.size()) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "quantile window plan: run_begin is too short"); return false; }
+		memcpy(run_begin, plan.run_begin.data(), plan.run_begin.size() * sizeof(int64_t));
+	}
+	return true;
+}
+
+// A test's hook: the run length and the scratch cap of every later window call of the process (0: the library's rule).
+void anofox_hip_quantile_window_test_hooks(int64_t run_length, int64_t scratch_cap_bytes) {
+	std::lock_guard<std::mutex> lk(g_qw_mu);
+	g_qw_run_length = run_length > 0 ? run_length : 0;
+	g_qw_scratch_cap = scratch_cap_bytes > 0 ? scratch_cap_bytes : 0;
+}
+
+// What the most recent window call on `ctx` (NULL: the thread's default context) did: out[6] = {output rows, frames that began
+// afresh, walkers, launched wavefronts, scratch rows per wavefront, restarts = the frames begun afresh right after a fitted
+// frame}.  Waits for the context's stream.  The record lives in the context and is reset by every window call on it; without one
+// (or after one that launched nothing) the call fails.
+bool anofox_hip_quantile_window_stats(AnofoxHipContext *ctx, int64_t *out, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!out) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "out is NULL"); return false; }
+	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (!ctx->qw_valid) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "quantile window stats: no window call on this context"); return false; }
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	const int64_t walkers = ctx->qw_walkers;
+	std::vector<int32_t> cold(2 * (size_t)walkers);
+	if (!d2h(cold.data(), ctx->qw_counts, cold.size() * sizeof(int32_t), ctx->stream, out_error)) return false;
+	if (hip_fail(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize", out_error)) return false;
+	int64_t begun = 0, restarts = 0;
+	for (int64_t w = 0; w < walkers; ++w) {
+		begun += cold[2 * (size_t)w];
+		restarts += cold[2 * (size_t)w + 1];
+	}
+	out[0] = ctx->qw_frames;
+	out[1] = begun;
+	out[2] = walkers;
+	out[3] = ctx->qw_waves;
+	out[4] = ctx->qw_span;
+	out[5] = restarts;
 	return true;
 }
 

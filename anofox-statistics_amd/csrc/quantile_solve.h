@@ -33,6 +33,8 @@
 //               which cannot cycle; at most kQsMaxExchanges in all.
 //   tau path    a vertex is feasible for every tau (only the optimality test and the line search read it): qs_fit_path begins once
 //               and pivots from the vertex each tau's finish rebuilt to the optimum of the next (qs_fit = begin, pivot, record).
+//   window      a vertex also stays feasible when rows join or leave the data set as long as its k basis rows remain: qs_fit_window
+//               walks consecutive frames of a partition and pivots from each frame's optimum to the next's.
 // Pivots are bounded by min(max_iterations, qs_iteration_ceiling(k)); when the bound stops a fit the last vertex is
 // returned (status 0) and the pivot count is reported negated.  No atomics, a fixed order of every sum: two calls give the
 // same bytes.
@@ -91,7 +93,8 @@ struct QsProblem {
 	double tau;
 	int max_iterations;
 	int predict_layout; // 0: {b, intercept, tau, loss, n_basis_rows, n, status}; 1: {b, intercept, NaN, NaN, NaN, n, status}
-	double *r, *z, *t;  // scratch, one double per row each, indexed by the row number
+	double *r, *z, *t;  // scratch, one double per row each: row i sits in slot i - origin
+	int64_t origin = 0; // 0: indexed by the row number (the fit and the tau path); the window walk keeps a slab of its own
 };
 
 // ---- the lanes of the wavefront (one lane in the host build) ----
@@ -248,13 +251,13 @@ QS_DEV bool qs_refactor(const QsProblem &P, int k, int ld, double *M, double *Bi
 		if (basis[j] < 0) beta[j] = 0.0; // an artificial pins its coefficient: exactly 0
 	qs_sync();
 	for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
-		if (!(P.r[i] == P.r[i])) continue; // masked at the first pass
+		if (!(P.r[i - P.origin] == P.r[i - P.origin])) continue; // masked at the first pass
 		double fit = 0.0;
 		for (int c = 0; c < k; ++c) fit += qs_elem(P, c, i) * beta[c];
-		const double old = P.r[i];
+		const double old = P.r[i - P.origin];
 		double rr = P.y[i] - fit;
 		if (fabs(rr) <= snap || qs_in_basis(basis, k, i)) rr = old == 0.0 ? old : copysign(0.0, rr); // a kink row keeps its side
-		P.r[i] = rr;
+		P.r[i - P.origin] = rr;
 	}
 	return true;
 }
@@ -290,6 +293,24 @@ struct QsState {
 	int64_t *basis, *perm;
 };
 
+// The column sizes max_i |a_ic| and sum_i |a_ic| over the valid rows of [P.lo, P.hi) (the rows whose r is not NaN): the scales
+// of the thresholds.  Begin computes them once per group, the window walk once per frame.
+QS_DEV void qs_column_sizes(const QsProblem &P, int k, double *amax, double *asum) {
+	const int lane = qs_lane();
+	for (int c = 0; c < k; ++c) {
+		double mx = 0.0, sm = 0.0;
+		for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
+			if (!(P.r[i - P.origin] == P.r[i - P.origin])) continue;
+			const double a = fabs(qs_elem(P, c, i));
+			mx = fmax(mx, a);
+			sm += a;
+		}
+		mx = qs_max(mx);
+		sm = qs_sum(sm);
+		if (lane == 0) { amax[c] = mx; asum[c] = sm; }
+	}
+}
+
 // Begin: the row rules, the first pass, the column sizes and the all-artificial basis (B^-1 = I, beta = 0, r = y).  Nothing
 // here reads tau.  -> 0, or the status that fails the group (100, 10, 6) at every tau.
 QS_DEV int qs_begin(const QsProblem &P, double *work, QsState &S) {
@@ -303,9 +324,9 @@ QS_DEV int qs_begin(const QsProblem &P, double *work, QsState &S) {
 		const double yv = P.y[i];
 		bool ok = isfinite(yv);
 		for (int j = 0; j < p; ++j) ok = ok && isfinite(P.x[j][i]);
-		P.r[i] = ok ? yv : NAN;
-		P.z[i] = 0.0;      // a masked row is never a breakpoint: the line search reads these slots of EVERY row, and the
-		P.t[i] = INFINITY; // scratch arrives with whatever an earlier call left in it
+		P.r[i - P.origin] = ok ? yv : NAN;
+		P.z[i - P.origin] = 0.0;      // a masked row is never a breakpoint: the line search reads these slots of EVERY row, and the
+		P.t[i - P.origin] = INFINITY; // scratch arrives with whatever an earlier call left in it
 		if (ok) {
 			++n_valid;
 			ymax = fmax(ymax, fabs(yv));
@@ -322,19 +343,7 @@ QS_DEV int qs_begin(const QsProblem &P, double *work, QsState &S) {
 	double *wrow = asum + k, *gp = wrow + k, *gm = gp + k, *thr = gm + k;
 	int64_t *basis = reinterpret_cast<int64_t *>(thr + k), *perm = basis + k;
 
-	// column sizes: max_i |a_ic| and sum_i |a_ic| over the valid rows
-	for (int c = 0; c < k; ++c) {
-		double mx = 0.0, sm = 0.0;
-		for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
-			if (!(P.r[i] == P.r[i])) continue;
-			const double a = fabs(qs_elem(P, c, i));
-			mx = fmax(mx, a);
-			sm += a;
-		}
-		mx = qs_max(mx);
-		sm = qs_sum(sm);
-		if (lane == 0) { amax[c] = mx; asum[c] = sm; }
-	}
+	qs_column_sizes(P, k, amax, asum);
 	for (int j = lane; j < k; j += QS_LANES) {
 		for (int c = 0; c < k; ++c) Binv[j * ld + c] = c == j ? 1.0 : 0.0;
 		basis[j] = -1 - (int64_t)j;
@@ -343,7 +352,7 @@ QS_DEV int qs_begin(const QsProblem &P, double *work, QsState &S) {
 	qs_sync();
 	// rows that are zero from the start (y_i = 0) are snapped like every later residual
 	for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES)
-		if (fabs(P.r[i]) <= snap) P.r[i] = 0.0;
+		if (fabs(P.r[i - P.origin]) <= snap) P.r[i - P.origin] = 0.0;
 
 	const int ceiling = qs_iteration_ceiling(k);
 	S.k = k;
@@ -379,7 +388,7 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 		for (int c = 0; c < k; ++c) {
 			double acc = 0.0;
 			for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
-				const double ri = P.r[i];
+				const double ri = P.r[i - P.origin];
 				if (ri > 0.0) acc += tau * qs_elem(P, c, i);
 				else if (ri < 0.0) acc += (tau - 1.0) * qs_elem(P, c, i);
 			}
@@ -402,7 +411,7 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 		}
 		for (int64_t c0 = P.lo; c0 < P.hi; c0 += QS_LANES) { // non-basis rows on their kink: each side pays its own slope
 			const int64_t i = c0 + lane;
-			uint64_t m = qs_ballot(i < P.hi && P.r[i] == 0.0 && !qs_in_basis(basis, k, i));
+			uint64_t m = qs_ballot(i < P.hi && P.r[i - P.origin] == 0.0 && !qs_in_basis(basis, k, i));
 			while (m) {
 				const int bit = __builtin_ctzll(m);
 				m &= m - 1;
@@ -447,12 +456,12 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 			}
 			for (int64_t c0 = P.lo; c0 < P.hi; c0 += QS_LANES) {
 				const int64_t i = c0 + lane;
-				uint64_t m = qs_ballot(i < P.hi && P.r[i] == 0.0 && !qs_in_basis(basis, k, i));
+				uint64_t m = qs_ballot(i < P.hi && P.r[i - P.origin] == 0.0 && !qs_in_basis(basis, k, i));
 				while (m) {
 					const int bit = __builtin_ctzll(m);
 					m &= m - 1;
 					const int64_t ii = c0 + bit;
-					const double psi = __builtin_signbit(P.r[ii]) ? tau - 1.0 : tau;
+					const double psi = __builtin_signbit(P.r[ii - P.origin]) ? tau - 1.0 : tau;
 					for (int j = lane; j < k; j += QS_LANES) {
 						double zz = 0.0;
 						for (int c = 0; c < k; ++c) zz += qs_elem(P, c, ii) * Binv[j * ld + c];
@@ -488,14 +497,14 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 			double w0 = 0.0;
 			int64_t first0 = INT64_MAX;
 			for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
-				const double ri = P.r[i];
+				const double ri = P.r[i - P.origin];
 				double wz = 0.0;
 				if (ri == 0.0 && !qs_in_basis(basis, k, i)) {
 					double zi = 0.0;
 					for (int c = 0; c < k; ++c) zi += qs_elem(P, c, i) * dvec[c];
 					if (fabs(zi) > zt && (__builtin_signbit(ri) ? zi < 0.0 : zi > 0.0)) wz = fabs(zi);
 				}
-				P.z[i] = wz;
+				P.z[i - P.origin] = wz;
 				if (wz > 0.0) {
 					w0 += wz;
 					if (i < first0) first0 = i;
@@ -516,21 +525,21 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 				while (ihi - ilo > 1) {
 					const int64_t mid = ilo + (ihi - ilo) / 2;
 					double pre = 0.0;
-					for (int64_t i = P.lo + lane; i <= mid; i += QS_LANES) pre += P.z[i];
+					for (int64_t i = P.lo + lane; i <= mid; i += QS_LANES) pre += P.z[i - P.origin];
 					pre = qs_sum(pre);
 					if (pre >= target) ihi = mid;
 					else ilo = mid;
 				}
 				int64_t last = -1; // the last blocking row at or below ihi enters, those before it change side
 				for (int64_t i = P.lo + lane; i <= ihi; i += QS_LANES)
-					if (P.z[i] > 0.0 && i > last) last = i;
+					if (P.z[i - P.origin] > 0.0 && i > last) last = i;
 				enter0 = -qs_min_i(-last);
 				if (enter0 < first0) enter0 = first0;
 				for (int64_t i = P.lo + lane; i < enter0; i += QS_LANES)
-					if (P.z[i] > 0.0) P.r[i] = -P.r[i];
+					if (P.z[i - P.origin] > 0.0) P.r[i - P.origin] = -P.r[i - P.origin];
 			}
 			const int64_t out = basis[bj];
-			if (out >= 0 && (out - P.lo) % QS_LANES == lane) P.r[out] = sg > 0.0 ? -0.0 : 0.0; // r = -t sg along the move
+			if (out >= 0 && (out - P.lo) % QS_LANES == lane) P.r[out - P.origin] = sg > 0.0 ? -0.0 : 0.0; // r = -t sg along the move
 			qs_replace(P, k, ld, Binv, wrow, basis, bj, enter0);
 			++zero_pivots;
 			fresh = false;
@@ -554,7 +563,7 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 		uint64_t tmin = ~0ull, tmax = 0ull;
 		double wall = 0.0;
 		for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
-			const double ri = P.r[i];
+			const double ri = P.r[i - P.origin];
 			if (!(ri == ri)) continue;
 			double zi = 0.0;
 			for (int c = 0; c < k; ++c) zi += qs_elem(P, c, i) * dvec[c];
@@ -562,8 +571,8 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 			double ti = INFINITY;
 			if (ri != 0.0 && fabs(zi) > ztol && (ri > 0.0) == (zi > 0.0)) ti = ri / zi;
 			if (!(ti > 0.0)) ti = INFINITY;
-			P.z[i] = zi;
-			P.t[i] = ti;
+			P.z[i - P.origin] = zi;
+			P.t[i - P.origin] = ti;
 			if (ti < INFINITY) {
 				const uint64_t tb = qs_bits(ti);
 				tmin = tb < tmin ? tb : tmin;
@@ -584,8 +593,8 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 			const uint64_t mid = blo + (bhi - blo) / 2;
 			double wsum = 0.0;
 			for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
-				const double ti = P.t[i]; // (+inf for masked rows, set at the first pass)
-				if (ti < INFINITY && qs_bits(ti) <= mid) wsum += fabs(P.z[i]);
+				const double ti = P.t[i - P.origin]; // (+inf for masked rows, set at the first pass)
+				if (ti < INFINITY && qs_bits(ti) <= mid) wsum += fabs(P.z[i - P.origin]);
 			}
 			wsum = qs_sum(wsum);
 			if (wsum >= need) bhi = mid;
@@ -593,7 +602,7 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 		}
 		int64_t enter = INT64_MAX;
 		for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
-			const double ti = P.t[i];
+			const double ti = P.t[i - P.origin];
 			if (ti < INFINITY && qs_bits(ti) == bhi && i < enter) enter = i;
 		}
 		enter = qs_min_i(enter);
@@ -605,13 +614,13 @@ QS_DEV bool qs_pivot_to_optimum(const QsProblem &P, const QsState &S, const doub
 		if (tstar * need <= kQsStallTol * ymax) bland = true;
 		// ---- the step ----
 		for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
-			const double ri = P.r[i];
+			const double ri = P.r[i - P.origin];
 			if (!(ri == ri)) continue;
-			const double zi = P.z[i];
+			const double zi = P.z[i - P.origin];
 			double rn = zi != 0.0 ? ri - tstar * zi : ri;
 			if (fabs(rn) <= snap) rn = 0.0;
 			if (i == enter) rn = 0.0;
-			P.r[i] = rn;
+			P.r[i - P.origin] = rn;
 		}
 		qs_replace(P, k, ld, Binv, wrow, basis, bj, enter);
 		++pivots;
@@ -632,7 +641,7 @@ QS_DEV void qs_record(const QsProblem &P, const QsState &S, const double tau, in
 	const int64_t *basis = S.basis;
 	double loss = 0.0;
 	for (int64_t i = P.lo + lane; i < P.hi; i += QS_LANES) {
-		const double ri = P.r[i];
+		const double ri = P.r[i - P.origin];
 		if (ri > 0.0) loss += tau * ri;
 		else if (ri < 0.0) loss += (tau - 1.0) * ri;
 	}
@@ -739,6 +748,147 @@ QS_DEV void qs_fit_path(const QsProblem &P, const double *taus, const uint8_t *s
 		qs_record(P, S, taus[t], pivots, converged, rec_t, it_t);
 		if (pred) qs_predict_rows(P, S.k, S.beta, pred, n_taus, slot[t]);
 	}
+}
+
+// ---- the window walk ----
+// One row of the window function's output: pred[3 e] = {yhat, NaN, NaN}, yhat = a_q'beta with qs_predict_rows' arithmetic
+// for the prediction row q (NaN where an x of q is not finite, beta is nullptr or the sum is not finite).  Lane 0 writes.
+QS_DEV void qs_window_predict(const QsProblem &P, int k, const double *beta, int64_t q, double *pred_e) {
+	if (qs_lane() != 0) return;
+	double fit = NAN;
+	if (beta) {
+		bool ok = true;
+		for (int j = 0; j < P.p; ++j) ok = ok && isfinite(P.x[j][q]);
+		if (ok) {
+			fit = 0.0;
+			for (int c = 0; c < k; ++c) fit += qs_elem(P, c, q) * beta[c];
+			if (!isfinite(fit)) fit = NAN;
+		}
+	}
+	pred_e[0] = fit;
+	pred_e[1] = NAN;
+	pred_e[2] = NAN;
+}
+
+// The fits of the consecutive output rows [e0, e1) of ONE partition, each over its frame [flo[e], fhi[e]) and predicting the
+// x of the frame's last row.  The first frame is a cold fit (begin, pivot: qs_fit).  A later frame whose bounds are both
+// non-decreasing, that overlaps the frame before it and loses none of the basis rows keeps the vertex: the rows that left
+// are masked, the rows that entered get r = y - a'beta of the carried beta (on their kink: the side of the rounding, as the
+// refactorisation assigns it), n_valid, max|y|, the snap and the column sizes are those a begin on this frame computes, and
+// the pivots go on from the carried basis with a fresh budget (as the tau path does per tau).  Every other transition, a frame
+// after one that failed, and a frame from which a basis row left begin afresh.
+//   P        y, x, p, fit_intercept, tau, max_iterations; r / z / t: a slab of slab_rows slots each that belongs to the caller
+//            (lo, hi, rule_count and origin are set here per frame: rule_count = the frame's rows whose y is not NaN)
+//   pred     [.. x 3], rec [.. x (p + 6)] (optional, the quantile layout), iterations (optional), cold (optional: 1 where
+//            the frame ran begin) — all indexed by the output row e
+// A frame longer than the slab gets status 2 (the planner never launches one).  -> the frames that ran begin; *restarts
+// (optional): those of them that followed a fitted frame (a basis row left, or the bounds were not monotone and overlapping)
+// — the first frame of the run and the frames after a failed one are not restarts.
+QS_DEV int64_t qs_fit_window(QsProblem &P, bool invalid, const int64_t *flo, const int64_t *fhi, int64_t e0, int64_t e1,
+                             int64_t slab_rows, double *work, double *pred, double *rec, int32_t *iterations, uint8_t *cold,
+                             int64_t *restarts) {
+	const int lane = qs_lane();
+	const int p = P.p, k = p + (P.fit_intercept ? 1 : 0);
+	QsState S;
+	bool have = false; // S holds the optimal vertex of the frame [plo, phi)
+	int64_t plo = 0, phi = 0, n_cold = 0, n_restart = 0;
+	P.predict_layout = 0;
+	for (int64_t e = e0; e < e1; ++e) {
+		const int64_t lo = flo[e], hi = fhi[e];
+		double *rec_e = rec ? rec + e * (int64_t)(p + 6) : nullptr;
+		int32_t *it_e = iterations ? iterations + e : nullptr;
+		if (cold && lane == 0) cold[e] = 0;
+		int status = 0;
+		bool began = false;
+		if (invalid) status = kQsStatusInvalidInput;
+		else if (hi <= lo) status = kQsStatusTooFewRows; // an empty frame
+		else if (hi - lo > slab_rows) status = 2;
+		if (status == 0) {
+			bool warm = have && lo >= plo && hi >= phi && lo < phi && hi - P.origin <= slab_rows;
+			if (warm) // a basis row among the rows that leave: this vertex does not exist on the new frame
+				for (int j = 0; j < k; ++j) warm = warm && !(S.basis[j] >= plo && S.basis[j] < lo);
+			int64_t rule = 0;
+			for (int64_t i = lo + lane; i < hi; i += QS_LANES) rule += P.y[i] == P.y[i] ? 1 : 0;
+			P.rule_count = qs_sum_i(rule);
+			P.lo = lo;
+			P.hi = hi;
+			qs_sync(); // (the basis was read above; begin writes it)
+			if (!warm) {
+				P.origin = lo;
+				began = true;
+				status = qs_begin(P, work, S);
+			} else if (P.rule_count < 2) {
+				status = kQsStatusTooFewRows;
+			} else {
+				for (int64_t i = plo + lane; i < lo; i += QS_LANES) { // the rows that left: as begin masks an invalid row
+					P.r[i - P.origin] = NAN;
+					P.z[i - P.origin] = 0.0;
+					P.t[i - P.origin] = INFINITY;
+				}
+				int64_t n_valid = 0;
+				double ymax = 0.0;
+				for (int64_t i = lo + lane; i < hi; i += QS_LANES) {
+					const double yv = P.y[i];
+					bool ok = isfinite(yv);
+					for (int j = 0; j < p; ++j) ok = ok && isfinite(P.x[j][i]);
+					if (ok) {
+						++n_valid;
+						ymax = fmax(ymax, fabs(yv));
+					}
+				}
+				n_valid = qs_sum_i(n_valid);
+				ymax = qs_max(ymax);
+				const double snap = kQsSnapTol * ymax;
+				if (n_valid == 0) status = kQsStatusNoValidData;
+				else if (n_valid < k) status = kQsStatusInsufficientData;
+				else {
+					for (int64_t i = phi + lane; i < hi; i += QS_LANES) { // the rows that entered
+						const double yv = P.y[i];
+						bool ok = isfinite(yv);
+						for (int j = 0; j < p; ++j) ok = ok && isfinite(P.x[j][i]);
+						double rr = NAN;
+						if (ok) {
+							double fit = 0.0;
+							for (int c = 0; c < k; ++c) fit += qs_elem(P, c, i) * S.beta[c];
+							rr = yv - fit;
+							if (fabs(rr) <= snap) rr = copysign(0.0, rr);
+						}
+						P.r[i - P.origin] = rr;
+						P.z[i - P.origin] = 0.0;
+						P.t[i - P.origin] = INFINITY;
+					}
+					qs_column_sizes(P, k, S.amax, S.asum);
+					S.n_valid = n_valid;
+					S.ymax = ymax;
+					S.snap = snap;
+					qs_sync();
+				}
+			}
+		}
+		int pivots = 0;
+		bool converged = false;
+		if (status == 0 && !qs_pivot_to_optimum(P, S, P.tau, &pivots, &converged)) status = 2; // ANOFOX_ERROR_SINGULAR_MATRIX
+		if (began) {
+			++n_cold;
+			n_restart += have ? 1 : 0;
+			if (cold && lane == 0) cold[e] = 1;
+		}
+		if (status != 0) {
+			if (rec_e) qs_fail_record(rec_e, p, status, it_e);
+			else if (it_e && lane == 0) *it_e = 0;
+			qs_window_predict(P, 0, nullptr, 0, pred + 3 * e);
+			have = false;
+			continue;
+		}
+		if (rec) qs_record(P, S, P.tau, pivots, converged, rec_e, it_e);
+		else if (it_e && lane == 0) *it_e = converged ? pivots : -pivots;
+		qs_window_predict(P, k, S.beta, hi - 1, pred + 3 * e);
+		have = true;
+		plo = lo;
+		phi = hi;
+	}
+	if (restarts) *restarts = n_restart;
+	return n_cold;
 }
 
 } // namespace quantile

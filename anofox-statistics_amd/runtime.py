@@ -369,6 +369,73 @@ class Context:
                                         train_counts=None):
         return quantile_fit_predict_batch_host(row_offsets, y, x_cols, options, train_counts, ctx=self)
 
+    def quantile_fit_predict_window_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions,
+                                           frame=(None, 0), want_records: bool = False, use_current_torch_stream: bool = True):
+        """The quantile window function on CUDA tensors over ROWS BETWEEN frame[0] PRECEDING AND frame[1] PRECEDING (as
+        fit_predict_window_device).  The planner reads row_offsets back to the host (one synchronising copy); the kernel is
+        enqueued.  Returns pred[N, 3], or (pred, quantile[N, p+6], iterations int32[N]) with want_records."""
+        import torch
+
+        p, G, N = len(x_cols), int(row_offsets.numel()) - 1, int(y.numel())
+        for t in (row_offsets, y, *x_cols):
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("device batch needs contiguous CUDA tensors")
+        if row_offsets.dtype != torch.int64 or y.dtype != torch.float64 or any(c.dtype != torch.float64 for c in x_cols):
+            raise ValueError("row_offsets must be int64 and data float64")
+        if any(int(c.numel()) != N for c in x_cols):
+            raise ValueError("every column must have y's length")
+        pred = torch.empty((N, 3), dtype=torch.float64, device=y.device)
+        rec = torch.empty((N, p + 6), dtype=torch.float64, device=y.device) if want_records else None
+        its = torch.empty((N,), dtype=torch.int32, device=y.device) if want_records else None
+        if use_current_torch_stream:
+            self.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
+        cols = (C.c_void_p * max(p, 1))(*[c.data_ptr() for c in x_cols])
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_quantile_fit_predict_window_device(
+            self._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols, _frame(frame), options,
+            C.c_void_p(pred.data_ptr()), C.c_void_p(rec.data_ptr()) if want_records else None,
+            C.c_void_p(its.data_ptr()) if want_records else None, C.byref(err))
+        self._check(ok, err)
+        return (pred, rec, its) if want_records else pred
+
+    def quantile_fit_predict_frames_device(self, y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipQuantileBatchOptions,
+                                           want_records: bool = False, use_current_torch_stream: bool = True):
+        """The same over explicit frames [frame_lo[e], frame_hi[e]) (int64 CUDA tensors of y's length)."""
+        import torch
+
+        p, N = len(x_cols), int(y.numel())
+        for t in (y, frame_lo, frame_hi, *x_cols):
+            if not t.is_cuda or not t.is_contiguous():
+                raise ValueError("device batch needs contiguous CUDA tensors")
+        if frame_lo.dtype != torch.int64 or frame_hi.dtype != torch.int64 or y.dtype != torch.float64 or any(c.dtype != torch.float64 for c in x_cols):
+            raise ValueError("frame bounds must be int64 and data float64")
+        if any(int(c.numel()) != N for c in (frame_lo, frame_hi, *x_cols)):
+            raise ValueError("every column and both frame bounds must have y's length")
+        pred = torch.empty((N, 3), dtype=torch.float64, device=y.device)
+        rec = torch.empty((N, p + 6), dtype=torch.float64, device=y.device) if want_records else None
+        its = torch.empty((N,), dtype=torch.int32, device=y.device) if want_records else None
+        if use_current_torch_stream:
+            self.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
+        cols = (C.c_void_p * max(p, 1))(*[c.data_ptr() for c in x_cols])
+        err = _abi.AnofoxError()
+        ok = self._lib.anofox_hip_quantile_fit_predict_frames_device(
+            self._h, N, p, C.c_void_p(y.data_ptr()), cols, C.c_void_p(frame_lo.data_ptr()), C.c_void_p(frame_hi.data_ptr()), options,
+            C.c_void_p(pred.data_ptr()), C.c_void_p(rec.data_ptr()) if want_records else None,
+            C.c_void_p(its.data_ptr()) if want_records else None, C.byref(err))
+        self._check(ok, err)
+        return (pred, rec, its) if want_records else pred
+
+    def quantile_fit_predict_window_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions,
+                                         frame=(None, 0), want_records: bool = False):
+        return quantile_fit_predict_window_host(row_offsets, y, x_cols, options, frame, want_records, ctx=self)
+
+    def quantile_fit_predict_frames_host(self, y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipQuantileBatchOptions,
+                                         want_records: bool = False):
+        return quantile_fit_predict_frames_host(y, x_cols, frame_lo, frame_hi, options, want_records, ctx=self)
+
+    def quantile_window_stats(self):
+        return quantile_window_stats(ctx=self)
+
     def bls_fit_predict_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipBlsBatchOptions,
                                    confidence_level: float = 0.95, train_counts=None):
         return bls_fit_predict_batch_host(row_offsets, y, x_cols, options, confidence_level, train_counts, ctx=self)
@@ -1153,6 +1220,96 @@ def elasticnet_fit_predict_frames_host(y, x_cols: Sequence, frame_lo, frame_hi, 
     if not ok:
         raise AnofoxStatsError(err.code, err.text())
     return pred
+
+
+def quantile_fit_predict_window_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions, frame=(None, 0),
+                                     want_records: bool = False, ctx: Optional[Context] = None):
+    """The quantile regression window function over ROWS frames (as fit_predict_window_host), numpy in / out: pred[N, 3] =
+    {yhat, NaN, NaN}; with want_records (pred, quantile[N, p+6], iterations int32[N]) — the record of every frame in
+    anofox_hip_quantile_fit_batch_host's layout and its pivots."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    p, G, N = len(cols), len(off) - 1, len(yv)
+    if any(len(c) != N for c in cols):
+        raise ValueError("every column must have y's length")
+    pred = np.empty((N, 3), dtype=np.float64)
+    rec = np.empty((N, p + 6), dtype=np.float64) if want_records else None
+    its = np.empty(N, dtype=np.int32) if want_records else None
+    colp = (_DP * max(p, 1))(*[c.ctypes.data_as(_DP) for c in cols])
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_quantile_fit_predict_window_host(
+        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(C.POINTER(C.c_int64)), yv.ctypes.data_as(_DP), colp,
+        _frame(frame), options, pred.ctypes.data_as(_DP), rec.ctypes.data_as(_DP) if want_records else None,
+        its.ctypes.data_as(C.POINTER(C.c_int32)) if want_records else None, C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return (pred, rec, its) if want_records else pred
+
+
+def quantile_fit_predict_frames_host(y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipQuantileBatchOptions,
+                                     want_records: bool = False, ctx: Optional[Context] = None):
+    """The quantile regression window function over explicit frames [frame_lo[e], frame_hi[e]), numpy in / out (as
+    quantile_fit_predict_window_host)."""
+    lib = _abi.load()
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
+    lo = np.ascontiguousarray(frame_lo, dtype=np.int64)
+    hi = np.ascontiguousarray(frame_hi, dtype=np.int64)
+    p, N = len(cols), len(yv)
+    if any(len(c) != N for c in cols) or len(lo) != N or len(hi) != N:
+        raise ValueError("every column and both frame bounds must have y's length")
+    pred = np.empty((N, 3), dtype=np.float64)
+    rec = np.empty((N, p + 6), dtype=np.float64) if want_records else None
+    its = np.empty(N, dtype=np.int32) if want_records else None
+    colp = (_DP * max(p, 1))(*[c.ctypes.data_as(_DP) for c in cols])
+    err = _abi.AnofoxError()
+    ok = lib.anofox_hip_quantile_fit_predict_frames_host(
+        ctx._h if ctx is not None else None, N, p, yv.ctypes.data_as(_DP), colp, lo.ctypes.data_as(C.POINTER(C.c_int64)),
+        hi.ctypes.data_as(C.POINTER(C.c_int64)), options, pred.ctypes.data_as(_DP), rec.ctypes.data_as(_DP) if want_records else None,
+        its.ctypes.data_as(C.POINTER(C.c_int32)) if want_records else None, C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return (pred, rec, its) if want_records else pred
+
+
+def quantile_window_plan(row_offsets, frame_lo, frame_hi, run_length: int = 0, scratch_cap_bytes: int = 0):
+    """The planner of the quantile window function alone (host arrays, no device): -> (run_begin int64[walkers + 1], scratch
+    rows per wavefront, launched wavefronts).  run_length / scratch_cap_bytes 0: the library's rule."""
+    lib = _abi.load()
+    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
+    lo = np.ascontiguousarray(frame_lo, dtype=np.int64)
+    hi = np.ascontiguousarray(frame_hi, dtype=np.int64)
+    if len(lo) != len(hi):
+        raise ValueError("both frame bounds must have the same length")
+    N = len(lo)
+    runs = np.empty(N + 2, dtype=np.int64)
+    n_runs, span, waves = C.c_int64(), C.c_int64(), C.c_int64()
+    err = _abi.AnofoxError()
+    I64 = C.POINTER(C.c_int64)
+    ok = lib.anofox_hip_quantile_window_plan(len(off) - 1, off.ctypes.data_as(I64), N, lo.ctypes.data_as(I64), hi.ctypes.data_as(I64),
+                                             int(run_length), int(scratch_cap_bytes), runs.ctypes.data_as(I64), len(runs),
+                                             C.byref(n_runs), C.byref(span), C.byref(waves), C.byref(err))
+    if not ok:
+        raise AnofoxStatsError(err.code, err.text())
+    return runs[:n_runs.value + 1].copy(), int(span.value), int(waves.value)
+
+
+def quantile_window_test_hooks(run_length: int = 0, scratch_cap_bytes: int = 0):
+    """For tests and measurements: the run length and the scratch cap of every later window call (0: the library's rule)."""
+    _abi.load().anofox_hip_quantile_window_test_hooks(int(run_length), int(scratch_cap_bytes))
+
+
+def quantile_window_stats(ctx: Optional[Context] = None):
+    """The most recent quantile window call on the context: dict(frames, cold_starts, walkers, waves, span_rows, restarts);
+    cold_starts counts every frame that began afresh, restarts those of them that followed a fitted frame."""
+    out = (C.c_int64 * 6)()
+    err = _abi.AnofoxError()
+    if not _abi.load().anofox_hip_quantile_window_stats(ctx._h if ctx is not None else None, out, C.byref(err)):
+        raise AnofoxStatsError(err.code, err.text())
+    return dict(frames=int(out[0]), cold_starts=int(out[1]), walkers=int(out[2]), waves=int(out[3]), span_rows=int(out[4]),
+                restarts=int(out[5]))
 
 
 def vif_batch_host(row_offsets, x_cols: Sequence, ctx: Optional[Context] = None):

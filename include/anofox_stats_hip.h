@@ -796,6 +796,61 @@ ANOFOX_HIP_API bool anofox_hip_rls_fit_predict_frames_host(AnofoxHipContext *ctx
                                             AnofoxError *out_error);
 
 /*
+ * The quantile regression window function: quantile_fit_predict(y, x [, options]) OVER (PARTITION BY .. ORDER BY .. ROWS ..)
+ * — rolling medians and rolling quantile bands.  Per output row e the fit above over the frame's rows with finite y and x,
+ * predicting the x of the frame's LAST row: pred[3 e] = {yhat, NaN, NaN} (there is no interval).  The row rules are the
+ * fit-predict aggregate's, per frame: fewer than 2 rows with a non-NaN y -> ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS, no valid row
+ * -> 10, fewer valid rows than p + [intercept] -> 6 (equality interpolates).  pred is NaN (SQL NULL) for an empty frame, a
+ * failed rule, a failed fit and a non-finite yhat; tau outside (0, 1) gives status 1 on every row; n_features > 32 fails the
+ * call.  quantile (may be NULL) receives [n_rows x (p + 6)] records in the layout of anofox_hip_quantile_fit_batch_*,
+ * iterations (may be NULL) the pivots of each frame, negated when max_iterations (per frame) stopped it.
+ * Frames: ROWS BETWEEN start_preceding PRECEDING AND end_preceding PRECEDING, clipped to the partition as
+ * anofox_hip_fit_predict_window_* clips them; row_offsets must start at 0 and end at n_rows.  The frames entry points take
+ * explicit bounds [frame_lo[e], frame_hi[e]) of any shape (hi <= lo: empty).
+ * Method (DESIGN.md §1 "Quantile regression", "Window function"): a wavefront walks a run of consecutive output rows of one
+ * partition and carries the optimal vertex from frame to frame — rows that leave are masked, rows that enter get their
+ * residual from the carried coefficients, and the simplex pivots on from there.  A frame begins afresh when it is the first
+ * of its run, when its bounds are not both non-decreasing or it does not overlap the frame before it, when a row of the
+ * carried basis left, and after a frame that failed.  Each frame's result is an LP-optimal vertex of that frame's rows with
+ * aliased coefficients exactly 0.0; where the optimum is not unique it may be another vertex than a fit of the frame alone
+ * returns, with the same loss.  A host-side planner cuts the partitions into runs (about 8192 walkers when partitions are few
+ * and long, a whole partition per walker when they are many or the frames start UNBOUNDED PRECEDING); each launched wavefront
+ * owns 24 bytes of scratch per row of the longest chain of a run (consecutive frames with non-decreasing, overlapping bounds:
+ * last frame's end - first frame's start; unsorted or far-apart explicit frames begin afresh and cost none), 1 GiB in all at
+ * most: fewer wavefronts are launched to stay below it, and a single span above it fails the call ("quantile window: frame
+ * span .. exceeds the scratch budget").  The device variants copy the offsets / the frame bounds to the host for the planner.
+ */
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                   const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                   AnofoxHipWindowFrame frame, AnofoxHipQuantileBatchOptions options, double *d_pred,
+                                                   double *d_quantile, int32_t *d_iterations, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                 const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                 AnofoxHipWindowFrame frame, AnofoxHipQuantileBatchOptions options, double *pred,
+                                                 double *quantile, int32_t *iterations, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *d_y,
+                                                   const double *const *x_cols, const int64_t *d_frame_lo, const int64_t *d_frame_hi,
+                                                   AnofoxHipQuantileBatchOptions options, double *d_pred, double *d_quantile,
+                                                   int32_t *d_iterations, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y,
+                                                 const double *const *x_cols, const int64_t *frame_lo, const int64_t *frame_hi,
+                                                 AnofoxHipQuantileBatchOptions options, double *pred, double *quantile,
+                                                 int32_t *iterations, AnofoxError *out_error);
+/* The planner alone, on host arrays (no device is touched): run_begin ([capacity], may be NULL) receives the first output row
+ * of every walker and one entry past the last, *n_runs their number, *span_rows the scratch rows of one wavefront, *n_waves
+ * the wavefronts a launch would use.  run_length / scratch_cap_bytes 0: the library's rule. */
+ANOFOX_HIP_API bool anofox_hip_quantile_window_plan(int64_t n_groups, const int64_t *row_offsets, int64_t n_rows, const int64_t *frame_lo,
+                                     const int64_t *frame_hi, int64_t run_length, int64_t scratch_cap_bytes, int64_t *run_begin,
+                                     int64_t capacity, int64_t *n_runs, int64_t *span_rows, int64_t *n_waves, AnofoxError *out_error);
+/* For tests and measurements: the run length and the scratch cap of every later window call of the process (0: the rule). */
+ANOFOX_HIP_API void anofox_hip_quantile_window_test_hooks(int64_t run_length, int64_t scratch_cap_bytes);
+/* out[6] = {output rows, frames that began afresh, walkers, launched wavefronts, scratch rows per wavefront, restarts = the
+ * frames begun afresh right after a fitted frame (a basis row left, or explicit bounds that are not monotone and overlapping)}
+ * of the most recent window call on ctx (NULL: the thread's default context); waits for the context's stream.  The record is
+ * the context's own: every window call on it resets it, no other call touches it, closing the context frees it. */
+ANOFOX_HIP_API bool anofox_hip_quantile_window_stats(AnofoxHipContext *ctx, int64_t *out, AnofoxError *out_error);
+
+/*
  * Grouped variance inflation factors: the Finalize loop of vif_agg (src/aggregate_functions/vif_aggregate.cpp:
  * 144-185) in one call.  x_cols as in the fit entry points (rows of a group contiguous; the aggregate's Update
  * has already dropped NULL rows and NaN values, :67-93).  d_vif[g] = { vif[n_features], status }
