@@ -1,0 +1,634 @@
+// quantile_family_hip.cpp — DuckDB glue of quantile regression over the batched C ABI:
+//
+//   anofox_stats_quantile_fit_predict_agg        src/aggregate_functions/quantile_fit_predict_aggregate.cpp (state :19-49, bind
+//                                                data :54-72, result type :77-85, Update :115-211, Combine :213-257, Finalize
+//                                                :259-354, binds :359-398, registration :403-484)
+//   anofox_stats_quantile_path_fit_predict_agg   no counterpart in the reference: the SQL face of aggregate.py's
+//                                                quantile_path_fit_predict_agg (the tau path, one fit per group for a grid of tau)
+//   anofox_stats_quantile_fit_predict            no counterpart in the reference: the SQL face of aggregate.py's
+//                                                quantile_fit_predict (window aggregate; mechanics of rls_family_hip.cpp's,
+//                                                src/window_functions/rls_fit_predict.cpp)
+//
+// As the other glue files: the DuckDB state buffers the group's rows on the host in arrival order, Combine appends the
+// source's rows after the target's, and Finalize turns the whole vector of states into ONE batched call per feature count
+// (anofox_hip_quantile_fit_predict_batch_host / anofox_hip_quantile_fit_predict_path_batch_host) where the reference makes one
+// anofox_quantile_fit call per group (:298): states = groups, columns concatenated, NaN y = "does not train".  LIST children
+// are reserved before they are written.  The glue adds no arithmetic: every yhat is the library's.
+//
+// Options (the keys options.parse_quantile_options reads; the reference's bind reads tau and fit_intercept, :363-371):
+// tau, fit_intercept / intercept, max_iterations / max_iter, tolerance / tol; the path reads taus (a LIST of numbers) in
+// place of tau.  Every other key is ignored — `quantile` included, which the reference's own example passes (:449) and
+// its aggregate never reads.  tau is not range-checked at bind: the fit reports it (status 1) and every group is NULL.
+//
+// The window aggregate fits every frame cold.  DuckDB hands an aggregate without a window callback a materialised frame per
+// output row — Update calls for the frame's rows (the naive aggregator) or a Combine of segment-tree states — and never the
+// consecutive frame bounds of a partition, which is what the sliding simplex needs to pivot from one frame's vertex to the
+// next's.  anofox_hip_quantile_fit_predict_window_* / _frames_* therefore stay reachable from the C ABI and Python only; an
+// aggregate_window_t callback over the partition is the follow-up that would reach them.
+//
+// Compiled and driven in this repository against the stand-in of DuckDB's headers (tests/tools/duckdb_stub), on the GPU
+// with the real library (tests/test_gpu_quantile_glue.py through tests/tools/quantile_family_capi.cpp).
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <map>
+#include <memory>
+
+#include "duckdb.hpp"
+#include "duckdb/common/types/data_chunk.hpp"
+#include "duckdb/execution/expression_executor.hpp"
+#include "duckdb/function/aggregate_function.hpp"
+#include "duckdb/main/extension/extension_loader.hpp"
+#include "duckdb/parser/parsed_data/create_aggregate_function_info.hpp"
+
+#include "anofox_stats_hip.h"
+#include "quantile_family_hip.hpp"
+#include "hip_options.hpp"
+
+namespace duckdb {
+
+namespace {
+using namespace hip_glue;
+
+// ---- options ----
+constexpr idx_t kMaxTaus = 64; // the library's grid limit (anofox_hip_quantile_fit_predict_path_batch_host)
+const char *const kTausMissing = "the quantile path needs the option 'taus': a non-empty list of quantiles";
+const char *const kTauGiven = "the quantile path takes a list of quantiles in 'taus', not 'tau'";
+const char *const kNotConstant = "Options parameter must be a constant expression";
+
+struct HipQuantileOptions {
+	double tau = 0.5;                // quantile_fit_predict_aggregate.cpp:55
+	bool fit_intercept = true;       // :56
+	uint32_t max_iterations = 1000;  // :292
+	double tolerance = 1e-6;         // :293
+	vector<double> taus;             // the path only, in the caller's order; NaN = a NULL element
+	bool operator==(const HipQuantileOptions &o) const {
+		return memcmp(&tau, &o.tau, sizeof tau) == 0 && fit_intercept == o.fit_intercept && max_iterations == o.max_iterations &&
+		       tolerance == o.tolerance && taus.size() == o.taus.size() &&
+		       (taus.empty() || memcmp(taus.data(), o.taus.data(), taus.size() * sizeof(double)) == 0);
+	}
+	AnofoxHipQuantileBatchOptions Batch() const {
+		AnofoxHipQuantileBatchOptions b;
+		memset(&b, 0, sizeof b);
+		b.tau = tau;
+		b.fit_intercept = fit_intercept;
+		b.max_iterations = max_iterations;
+		b.tolerance = tolerance;
+		return b;
+	}
+};
+
+void ApplyQuantileOption(const string &raw_key, const Value &v, HipQuantileOptions &o) {
+	if (v.IsNull()) return;
+	const string key = Lower(raw_key);
+	if (key == "tau") o.tau = v.GetValue<double>();
+	else if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(v);
+	else if (key == "max_iterations" || key == "max_iter") {
+		const double it = v.GetValue<double>();
+		if (!(it >= 0.0 && it <= 4294967295.0)) throw InvalidInputException("Value %s is out of range for UINTEGER", v.ToString().c_str());
+		o.max_iterations = (uint32_t)it;
+	} else if (key == "tolerance" || key == "tol") o.tolerance = v.GetValue<double>();
+	// every other key: ignored, as in the reference ({'quantile': 0.5} of its example binds and changes nothing)
+}
+
+// a STRUCT or MAP literal as (key, value) pairs
+template <class F>
+void VisitHipQuantileOptions(const Value &v, F &&visit) {
+	if (v.type().id() == LogicalTypeId::STRUCT) {
+		auto &kids = StructValue::GetChildren(v);
+		for (idx_t i = 0; i < kids.size(); i++) visit(StructType::GetChildName(v.type(), i), kids[i]);
+	} else if (v.type().id() == LogicalTypeId::MAP) {
+		for (auto &entry : MapValue::GetChildren(v)) {
+			auto &kv = StructValue::GetChildren(entry);
+			if (kv.size() != 2 || kv[0].IsNull()) continue;
+			visit(kv[0].type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(kv[0]) : kv[0].ToString(), kv[1]);
+		}
+	} else {
+		throw InvalidInputException("Options must be a MAP or STRUCT, got %s", v.type().ToString().c_str());
+	}
+}
+
+void ParseHipQuantileOptions(const Value &v, HipQuantileOptions &o) {
+	if (v.IsNull()) return;
+	VisitHipQuantileOptions(v, [&](const string &key, const Value &val) { ApplyQuantileOption(key, val, o); });
+}
+
+// options.parse_quantile_path_options: `tau` is rejected whatever its value, `taus` must be a non-empty LIST; a NULL element
+// is kept as NaN and an out-of-range one as it is (the fit reports both at their position: status 1, NULL predictions)
+void ParseHipQuantilePathOptions(const Value &v, HipQuantileOptions &o) {
+	if (v.IsNull()) throw InvalidInputException("%s", kTausMissing);
+	VisitHipQuantileOptions(v, [&](const string &key, const Value &) {
+		if (Lower(key) == "tau") throw InvalidInputException("%s", kTauGiven);
+	});
+	VisitHipQuantileOptions(v, [&](const string &key, const Value &val) {
+		if (Lower(key) != "taus") {
+			ApplyQuantileOption(key, val, o);
+			return;
+		}
+		o.taus.clear();
+		if (val.IsNull() || val.type().id() != LogicalTypeId::LIST) return;
+		for (auto &e : ListValue::GetChildren(val)) o.taus.push_back(e.IsNull() ? NAN : e.GetValue<double>());
+	});
+	if (o.taus.empty()) throw InvalidInputException("%s", kTausMissing);
+	if (o.taus.size() > kMaxTaus) throw InvalidInputException("quantile path: n_taus > 64 is not built");
+}
+
+struct HipQuantileBindData : public FunctionData {
+	HipQuantileBindData(const HipQuantileOptions &opts_p, bool use_split_col_p) : opts(opts_p), use_split_col(use_split_col_p) {}
+	HipQuantileOptions opts;
+	bool use_split_col;
+	unique_ptr<FunctionData> Copy() const override { return make_uniq<HipQuantileBindData>(opts, use_split_col); }
+	bool Equals(const FunctionData &other_p) const override {
+		auto &other = other_p.Cast<HipQuantileBindData>();
+		return opts == other.opts && use_split_col == other.use_split_col;
+	}
+};
+
+// ---- the row buffer behind a DuckDB state (the layout of rls_family_hip.cpp's) ----
+constexpr uint8_t kYNull = 1, kTraining = 2;
+struct QuantileRowBuffer {
+	idx_t n_features = 0;
+	vector<double> y;      // NaN where y was NULL
+	vector<double> x;      // row-major; a NULL list element is NaN
+	vector<uint8_t> flags; // kYNull | kTraining
+	idx_t n_training = 0;
+	vector<double> current_x; // the window aggregate: x of the last row Update saw
+	bool has_current_x = false;
+	idx_t Rows() const { return y.size(); }
+};
+struct HipQuantileRowsState {
+	QuantileRowBuffer *rows; // nullptr: never initialised (:37)
+};
+
+void HipQuantileRowsInitialize(const AggregateFunction &, data_ptr_t state_p) { reinterpret_cast<HipQuantileRowsState *>(state_p)->rows = nullptr; }
+
+void HipQuantileRowsDestroy(Vector &state_vector, AggregateInputData &, idx_t count) {
+	UnifiedVectorFormat sdata;
+	state_vector.ToUnifiedFormat(count, sdata);
+	auto states = (HipQuantileRowsState **)sdata.data;
+	for (idx_t i = 0; i < count; i++) {
+		auto &state = *states[sdata.sel->get_index(i)];
+		delete state.rows;
+		state.rows = nullptr;
+	}
+}
+
+QuantileRowBuffer &QuantileRows(HipQuantileRowsState &state, idx_t n_features) {
+	if (!state.rows) {
+		state.rows = new QuantileRowBuffer();
+		state.rows->n_features = n_features;
+	}
+	if (state.rows->n_features != n_features) // :162-164
+		throw InvalidInputException("Inconsistent feature count: expected %llu, got %llu", (unsigned long long)state.rows->n_features,
+		                            (unsigned long long)n_features);
+	return *state.rows;
+}
+
+bool IsQuantileSplitTraining(const string_t &split) { // QuantileIsSplitTraining :88-94: 'train' / 'training', any case
+	string v = split.GetString();
+	for (auto &c : v) c = (char)std::tolower((unsigned char)c);
+	return v == "train" || v == "training";
+}
+
+// Update (:115-211): a row with a NULL x list is skipped; every other row is kept for the output, a NULL list element as NaN.
+// It trains iff its y is not NULL — and, with a split column, its split value is not NULL and says train.  A NaN y that is
+// not NULL counts as a training row (:204-209); the fit's row filter drops it.  WINDOW: the last row Update saw is the row to
+// predict (a NULL x list there: nothing to predict).
+template <bool WINDOW>
+void HipQuantileRowsUpdate(Vector inputs[], AggregateInputData &aggr_input_data, idx_t input_count, Vector &state_vector, idx_t count) {
+	auto &bind = aggr_input_data.bind_data->Cast<HipQuantileBindData>();
+	if (input_count < 2) throw InvalidInputException("anofox_stats quantile_fit_predict (HIP): too few arguments");
+	UnifiedVectorFormat y_data, x_data, split_data, sdata;
+	inputs[0].ToUnifiedFormat(count, y_data);
+	inputs[1].ToUnifiedFormat(count, x_data);
+	auto y_values = UnifiedVectorFormat::GetData<double>(y_data);
+	auto x_list = UnifiedVectorFormat::GetData<list_entry_t>(x_data);
+	auto &x_child = ListVector::GetEntry(inputs[1]);
+	auto x_child_data = FlatVector::GetData<double>(x_child);
+	auto &x_child_validity = FlatVector::Validity(x_child);
+	const string_t *split_values = nullptr;
+	if (bind.use_split_col && input_count > 2) {
+		inputs[2].ToUnifiedFormat(count, split_data);
+		split_values = UnifiedVectorFormat::GetData<string_t>(split_data);
+	}
+	state_vector.ToUnifiedFormat(count, sdata);
+	auto states = (HipQuantileRowsState **)sdata.data;
+	for (idx_t i = 0; i < count; i++) {
+		auto &state = *states[sdata.sel->get_index(i)];
+		auto x_idx = x_data.sel->get_index(i);
+		if (!x_data.validity.RowIsValid(x_idx)) {
+			if (WINDOW && state.rows) state.rows->has_current_x = false;
+			continue;
+		}
+		const auto entry = x_list[x_idx];
+		auto &rows = QuantileRows(state, entry.length);
+		const size_t at = rows.x.size();
+		rows.x.resize(at + entry.length);
+		for (idx_t j = 0; j < entry.length; j++) {
+			const idx_t pos = entry.offset + j;
+			rows.x[at + j] = x_child_validity.RowIsValid(pos) ? x_child_data[pos] : NAN; // never read the slot of a NULL (:169-173)
+		}
+		if (WINDOW) {
+			rows.current_x.assign(rows.x.begin() + (ptrdiff_t)at, rows.x.end());
+			rows.has_current_x = true;
+		}
+		auto y_idx = y_data.sel->get_index(i);
+		const bool y_valid = y_data.validity.RowIsValid(y_idx);
+		bool training = y_valid;
+		if (bind.use_split_col && split_values) {
+			auto s_idx = split_data.sel->get_index(i);
+			training = split_data.validity.RowIsValid(s_idx) && IsQuantileSplitTraining(split_values[s_idx]) && y_valid;
+		}
+		rows.y.push_back(y_valid ? y_values[y_idx] : NAN);
+		rows.flags.push_back((uint8_t)((y_valid ? 0 : kYNull) | (training ? kTraining : 0)));
+		rows.n_training += training ? 1 : 0;
+	}
+}
+
+// Combine (:213-257): the source's rows after the target's; ALLOW_DESTRUCTIVE moves, PRESERVE_INPUT copies
+template <bool WINDOW>
+void HipQuantileRowsCombine(Vector &source_vector, Vector &target_vector, AggregateInputData &aggr_input_data, idx_t count) {
+	UnifiedVectorFormat source_data, target_data;
+	source_vector.ToUnifiedFormat(count, source_data);
+	target_vector.ToUnifiedFormat(count, target_data);
+	auto sources = (HipQuantileRowsState **)source_data.data;
+	auto targets = (HipQuantileRowsState **)target_data.data;
+	const bool preserve = aggr_input_data.combine_type == AggregateCombineType::PRESERVE_INPUT;
+	for (idx_t i = 0; i < count; i++) {
+		auto &source = *sources[source_data.sel->get_index(i)];
+		auto &target = *targets[target_data.sel->get_index(i)];
+		if (!source.rows || &source == &target) continue;
+		if (!target.rows) {
+			if (preserve) {
+				target.rows = new QuantileRowBuffer(*source.rows);
+			} else {
+				target.rows = source.rows;
+				source.rows = nullptr;
+			}
+			continue;
+		}
+		if (source.rows->n_features != target.rows->n_features) throw InvalidInputException("Cannot combine states with different feature counts");
+		auto &t = *target.rows;
+		const auto &s = *source.rows;
+		t.y.insert(t.y.end(), s.y.begin(), s.y.end());
+		t.x.insert(t.x.end(), s.x.begin(), s.x.end());
+		t.flags.insert(t.flags.end(), s.flags.begin(), s.flags.end());
+		t.n_training += s.n_training;
+		if (WINDOW && s.has_current_x) { // the later state's row is the frame's last
+			t.current_x = s.current_x;
+			t.has_current_x = true;
+		}
+	}
+}
+
+// the states of one Finalize vector as one batch per feature count
+struct QuantileBatch {
+	idx_t p = 0;
+	vector<idx_t> result_rows;
+	vector<QuantileRowBuffer *> buffers;
+	vector<int64_t> offsets {0};
+	vector<int64_t> train_counts;
+	vector<double> y, cols, records, pred;
+	vector<const double *> col_ptrs;
+	// rows that do not train reach the ABI with y = NaN; extra_row: the window aggregate's current x as a last such row
+	int64_t Stage(bool extra_row) {
+		int64_t n = 0;
+		for (auto *b : buffers) {
+			n += (int64_t)b->Rows() + (extra_row ? 1 : 0);
+			offsets.push_back(n);
+			train_counts.push_back((int64_t)b->n_training);
+		}
+		y.resize((size_t)n);
+		cols.resize((size_t)n * p);
+		int64_t at = 0;
+		for (auto *b : buffers) {
+			const idx_t rows = b->Rows();
+			for (idx_t r = 0; r < rows; r++) {
+				y[at + r] = (b->flags[r] & kTraining) ? b->y[r] : NAN;
+				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at + r] = b->x[r * p + j];
+			}
+			at += (int64_t)rows;
+			if (extra_row) {
+				y[at] = NAN;
+				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at] = b->current_x[j];
+				at++;
+			}
+		}
+		col_ptrs.resize(p);
+		for (idx_t j = 0; j < p; j++) col_ptrs[j] = cols.data() + j * (size_t)n;
+		return n;
+	}
+	// records [G x (p + 6)] in the regression layout, pred [n x 3] = {yhat, NaN, NaN}: the two NaN bounds are dropped by the callers
+	void Run(const HipQuantileOptions &opts, bool extra_row) {
+		const int64_t n = Stage(extra_row);
+		records.resize(buffers.size() * (p + 6));
+		pred.resize((size_t)n * 3);
+		AnofoxError err;
+		memset(&err, 0, sizeof err);
+		if (!anofox_hip_quantile_fit_predict_batch_host(nullptr, (int64_t)buffers.size(), p, n, offsets.data(), y.data(), col_ptrs.data(),
+		                                                train_counts.data(), opts.Batch(), records.data(), pred.data(), &err))
+			throw InvalidInputException("anofox_stats (HIP): %s", err.message[0] ? err.message : "the batched call failed");
+	}
+	// records [G x T x (p + 6)] in the quantile layout, pred [n x T]
+	void RunPath(const HipQuantileOptions &opts) {
+		const int64_t n = Stage(false);
+		const size_t T = opts.taus.size();
+		records.resize(buffers.size() * T * (p + 6));
+		pred.resize((size_t)n * T);
+		AnofoxError err;
+		memset(&err, 0, sizeof err);
+		if (!anofox_hip_quantile_fit_predict_path_batch_host(nullptr, (int64_t)buffers.size(), p, n, offsets.data(), y.data(), col_ptrs.data(),
+		                                                     train_counts.data(), opts.Batch(), opts.taus.data(), T, records.data(), nullptr,
+		                                                     pred.data(), &err))
+			throw InvalidInputException("anofox_stats (HIP): %s", err.message[0] ? err.message : "the batched call failed");
+	}
+	bool Failed(idx_t g, idx_t T = 1, idx_t t = 0) const { return records[(g * T + t) * (p + 6) + p + 5] != 0.0; }
+};
+
+// the states of a Finalize vector that are fitted, by feature count; the others are NULL (:269: never initialised or fewer
+// than 2 training rows; WINDOW: no current row either)
+template <bool WINDOW>
+std::map<idx_t, QuantileBatch> CollectQuantileBatches(Vector &state_vector, Vector &result, idx_t count, idx_t offset) {
+	UnifiedVectorFormat sdata;
+	state_vector.ToUnifiedFormat(count, sdata);
+	auto states = (HipQuantileRowsState **)sdata.data;
+	std::map<idx_t, QuantileBatch> batches;
+	for (idx_t i = 0; i < count; i++) {
+		auto &state = *states[sdata.sel->get_index(i)];
+		if (!state.rows || state.rows->n_training < 2 || state.rows->n_features == 0 || (WINDOW && !state.rows->has_current_x)) {
+			FlatVector::SetNull(result, i + offset, true);
+			continue;
+		}
+		auto &b = batches[state.rows->n_features];
+		b.p = state.rows->n_features;
+		b.result_rows.push_back(i + offset);
+		b.buffers.push_back(state.rows);
+	}
+	return batches;
+}
+
+// a LIST entry of `length` STRUCT rows at the end of the result's child, reserved before it is written
+idx_t AppendQuantileListEntry(Vector &result, idx_t row, idx_t length) {
+	const idx_t list_offset = ListVector::GetListSize(result);
+	ListVector::Reserve(result, list_offset + length);
+	ListVector::SetListSize(result, list_offset + length);
+	auto list_data = ListVector::GetData(result);
+	list_data[row].offset = list_offset;
+	list_data[row].length = length;
+	return list_offset;
+}
+
+void SetDoubleOrNull(Vector &field, idx_t at, double v, bool is_null) {
+	if (is_null) FlatVector::SetNull(field, at, true);
+	else FlatVector::GetData<double>(field)[at] = v;
+}
+
+// =====================================================================================================================
+// anofox_stats_quantile_fit_predict_agg(y, x[, split_col][, options]) -> LIST(STRUCT(y, yhat, is_training))
+// =====================================================================================================================
+LogicalType GetHipQuantilePredictAggResultType() { // :77-85
+	child_list_t<LogicalType> row_children;
+	row_children.push_back(make_pair("y", LogicalType::DOUBLE));
+	row_children.push_back(make_pair("yhat", LogicalType::DOUBLE));
+	row_children.push_back(make_pair("is_training", LogicalType::BOOLEAN));
+	return LogicalType::LIST(LogicalType::STRUCT(std::move(row_children)));
+}
+
+// Finalize (:259-354): NULL with fewer than 2 training rows or a failed fit; otherwise every buffered row with its prediction
+// (a non-finite yhat is NULL :341-346, y is NULL where the input was :326-330)
+void HipQuantilePredictAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
+	auto &bind = aggr_input_data.bind_data->Cast<HipQuantileBindData>();
+	auto batches = CollectQuantileBatches<false>(state_vector, result, count, offset);
+	for (auto &kv : batches) kv.second.Run(bind.opts, false);
+	for (auto &kv : batches) {
+		auto &b = kv.second;
+		for (idx_t g = 0; g < b.buffers.size(); g++) {
+			const idx_t r = b.result_rows[g];
+			if (b.Failed(g)) {
+				FlatVector::SetNull(result, r, true);
+				continue;
+			}
+			const QuantileRowBuffer &rows = *b.buffers[g];
+			const idx_t n_rows = rows.Rows();
+			const idx_t list_offset = AppendQuantileListEntry(result, r, n_rows);
+			auto &fields = StructVector::GetEntries(ListVector::GetEntry(result));
+			const double *pred = &b.pred[(size_t)b.offsets[g] * 3];
+			for (idx_t row = 0; row < n_rows; row++) {
+				const idx_t at = list_offset + row;
+				SetDoubleOrNull(*fields[0], at, rows.y[row], (rows.flags[row] & kYNull) != 0);
+				SetDoubleOrNull(*fields[1], at, pred[row * 3], !isfinite(pred[row * 3]));
+				FlatVector::GetData<bool>(*fields[2])[at] = (rows.flags[row] & kTraining) != 0;
+			}
+		}
+	}
+}
+
+template <bool SPLIT>
+unique_ptr<FunctionData> HipQuantilePredictAggBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
+	HipQuantileOptions opts;
+	const idx_t opt_idx = SPLIT ? 3 : 2;
+	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable())
+		ParseHipQuantileOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts);
+	function.return_type = GetHipQuantilePredictAggResultType();
+	return make_uniq<HipQuantileBindData>(opts, SPLIT);
+}
+
+// =====================================================================================================================
+// anofox_stats_quantile_path_fit_predict_agg(y, x[, split_col], options) -> LIST(STRUCT(y, tau, yhat, is_training))
+// long format: for each buffered row in arrival order one entry per tau in the caller's order (row-major)
+// =====================================================================================================================
+LogicalType GetHipQuantilePathAggResultType() {
+	child_list_t<LogicalType> row_children;
+	row_children.push_back(make_pair("y", LogicalType::DOUBLE));
+	row_children.push_back(make_pair("tau", LogicalType::DOUBLE));
+	row_children.push_back(make_pair("yhat", LogicalType::DOUBLE));
+	row_children.push_back(make_pair("is_training", LogicalType::BOOLEAN));
+	return LogicalType::LIST(LogicalType::STRUCT(std::move(row_children)));
+}
+
+// Finalize: the group is NULL by the row rules or when every tau failed; a single failed or invalid tau NULLs its own yhat
+// entries only (the library writes NaN there)
+void HipQuantilePathAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
+	auto &bind = aggr_input_data.bind_data->Cast<HipQuantileBindData>();
+	const auto &taus = bind.opts.taus;
+	const idx_t T = taus.size();
+	auto batches = CollectQuantileBatches<false>(state_vector, result, count, offset);
+	for (auto &kv : batches) kv.second.RunPath(bind.opts);
+	for (auto &kv : batches) {
+		auto &b = kv.second;
+		for (idx_t g = 0; g < b.buffers.size(); g++) {
+			const idx_t r = b.result_rows[g];
+			bool any_fitted = false;
+			for (idx_t t = 0; t < T; t++) any_fitted = any_fitted || !b.Failed(g, T, t);
+			if (!any_fitted) {
+				FlatVector::SetNull(result, r, true);
+				continue;
+			}
+			const QuantileRowBuffer &rows = *b.buffers[g];
+			const idx_t n_rows = rows.Rows();
+			const idx_t list_offset = AppendQuantileListEntry(result, r, n_rows * T);
+			auto &fields = StructVector::GetEntries(ListVector::GetEntry(result));
+			const double *pred = &b.pred[(size_t)b.offsets[g] * T];
+			for (idx_t row = 0; row < n_rows; row++) {
+				for (idx_t t = 0; t < T; t++) {
+					const idx_t at = list_offset + row * T + t;
+					const double yhat = pred[row * T + t];
+					SetDoubleOrNull(*fields[0], at, rows.y[row], (rows.flags[row] & kYNull) != 0);
+					SetDoubleOrNull(*fields[1], at, taus[t], isnan(taus[t]));
+					SetDoubleOrNull(*fields[2], at, yhat, b.Failed(g, T, t) || !isfinite(yhat));
+					FlatVector::GetData<bool>(*fields[3])[at] = (rows.flags[row] & kTraining) != 0;
+				}
+			}
+		}
+	}
+}
+
+template <bool SPLIT>
+unique_ptr<FunctionData> HipQuantilePathAggBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
+	HipQuantileOptions opts;
+	const idx_t opt_idx = SPLIT ? 3 : 2;
+	if (arguments.size() <= opt_idx) throw InvalidInputException("%s", kTausMissing);
+	if (!arguments[opt_idx]->IsFoldable()) throw InvalidInputException("%s", kNotConstant);
+	ParseHipQuantilePathOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts);
+	function.return_type = GetHipQuantilePathAggResultType();
+	return make_uniq<HipQuantileBindData>(opts, SPLIT);
+}
+
+// =====================================================================================================================
+// anofox_stats_quantile_fit_predict(y, x[, options]) OVER (...) -> STRUCT(yhat, yhat_lower, yhat_upper)
+// the result type of the *_fit_predict family, so the name can be swapped into an ols_fit_predict query; there is no interval:
+// both bounds are always NULL
+// =====================================================================================================================
+LogicalType GetHipQuantileFitPredictResultType() {
+	child_list_t<LogicalType> children;
+	children.push_back(make_pair("yhat", LogicalType::DOUBLE));
+	children.push_back(make_pair("yhat_lower", LogicalType::DOUBLE));
+	children.push_back(make_pair("yhat_upper", LogicalType::DOUBLE));
+	return LogicalType::STRUCT(std::move(children));
+}
+
+// Finalize: the frame's rows plus the current x as a last row that does not train, whose yhat is the result.  NULL: a state
+// never initialised, no current row, fewer than 2 training rows in the frame, a failed fit, a non-finite yhat.
+void HipQuantileFitPredictFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
+	auto &bind = aggr_input_data.bind_data->Cast<HipQuantileBindData>();
+	auto batches = CollectQuantileBatches<true>(state_vector, result, count, offset);
+	for (auto &kv : batches) kv.second.Run(bind.opts, true);
+	auto &fields = StructVector::GetEntries(result);
+	for (auto &kv : batches) {
+		auto &b = kv.second;
+		for (idx_t g = 0; g < b.buffers.size(); g++) {
+			const idx_t r = b.result_rows[g];
+			const double yhat = b.pred[((size_t)b.offsets[g + 1] - 1) * 3];
+			if (b.Failed(g) || !isfinite(yhat)) {
+				FlatVector::SetNull(result, r, true);
+				continue;
+			}
+			FlatVector::GetData<double>(*fields[0])[r] = yhat;
+			FlatVector::SetNull(*fields[1], r, true);
+			FlatVector::SetNull(*fields[2], r, true);
+		}
+	}
+}
+
+unique_ptr<FunctionData> HipQuantileFitPredictBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
+	HipQuantileOptions opts;
+	if (arguments.size() > 2 && arguments[2]->IsFoldable()) ParseHipQuantileOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[2]), opts);
+	function.return_type = GetHipQuantileFitPredictResultType();
+	return make_uniq<HipQuantileBindData>(opts, false);
+}
+
+FunctionDescription Describe(const char *what, const string &example, vector<string> names, const vector<LogicalType> &types) {
+	FunctionDescription d;
+	d.description = what;
+	d.examples = {example};
+	d.categories = {"regression", "quantile"};
+	d.parameter_names = std::move(names);
+	d.parameter_types = types;
+	return d;
+}
+
+void RegisterWithAlias(ExtensionLoader &loader, CreateAggregateFunctionInfo info, AggregateFunctionSet alias_set) {
+	const string name = info.functions.name;
+	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
+	loader.RegisterFunction(std::move(info));
+	CreateAggregateFunctionInfo alias_info(std::move(alias_set));
+	alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
+	alias_info.alias_of = name;
+	loader.RegisterFunction(std::move(alias_info));
+}
+
+} // namespace
+
+void RegisterHipQuantileFitPredictAggregateFunction(ExtensionLoader &loader) {
+	const char *name = "anofox_stats_quantile_fit_predict_agg";
+	const char *what = "Fits a quantile regression model over a partition and returns per-row predictions.";
+	const vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
+	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
+	const vector<LogicalType> split_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR};
+	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
+	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
+		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<HipQuantileRowsState>,
+		                         HipQuantileRowsInitialize, HipQuantileRowsUpdate<false>, HipQuantileRowsCombine<false>, HipQuantilePredictAggFinalize,
+		                         nullptr, split ? HipQuantilePredictAggBind<true> : HipQuantilePredictAggBind<false>, HipQuantileRowsDestroy);
+	};
+	auto fill = [&](const string &fname) {
+		AggregateFunctionSet set(fname);
+		set.AddFunction(make(fname, basic, false));          // (y, x)
+		set.AddFunction(make(fname, map_args, false));       // (y, x, options)
+		set.AddFunction(make(fname, split_args, true));      // (y, x, split_col)
+		set.AddFunction(make(fname, split_map_args, true));  // (y, x, split_col, options)
+		return set;
+	};
+	CreateAggregateFunctionInfo info(fill(name));
+	const string head = string(name) + "(y, x";
+	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic));
+	info.descriptions.push_back(Describe(what, head + ", {'tau': 0.5})", {"y", "x", "options"}, map_args));
+	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args));
+	info.descriptions.push_back(Describe(what, head + ", split_col, {'tau': 0.5})", {"y", "x", "split_col", "options"}, split_map_args));
+	RegisterWithAlias(loader, std::move(info), fill("quantile_fit_predict_agg"));
+}
+
+void RegisterHipQuantilePathFitPredictAggregateFunction(ExtensionLoader &loader) {
+	const char *name = "anofox_stats_quantile_path_fit_predict_agg";
+	const char *what = "Fits quantile regression at every quantile of a grid from one fit per partition and returns per-row, per-quantile predictions.";
+	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
+	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
+	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
+		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<HipQuantileRowsState>,
+		                         HipQuantileRowsInitialize, HipQuantileRowsUpdate<false>, HipQuantileRowsCombine<false>, HipQuantilePathAggFinalize,
+		                         nullptr, split ? HipQuantilePathAggBind<true> : HipQuantilePathAggBind<false>, HipQuantileRowsDestroy);
+	};
+	auto fill = [&](const string &fname) {
+		AggregateFunctionSet set(fname);
+		set.AddFunction(make(fname, map_args, false));       // (y, x, options)
+		set.AddFunction(make(fname, split_map_args, true));  // (y, x, split_col, options)
+		return set;
+	};
+	CreateAggregateFunctionInfo info(fill(name));
+	const string head = string(name) + "(y, x";
+	info.descriptions.push_back(Describe(what, head + ", {'taus': [0.1, 0.5, 0.9]})", {"y", "x", "options"}, map_args));
+	info.descriptions.push_back(Describe(what, head + ", split_col, {'taus': [0.1, 0.5, 0.9]})", {"y", "x", "split_col", "options"}, split_map_args));
+	RegisterWithAlias(loader, std::move(info), fill("quantile_path_fit_predict_agg"));
+}
+
+void RegisterHipQuantileFitPredictFunction(ExtensionLoader &loader) {
+	const char *name = "anofox_stats_quantile_fit_predict";
+	const char *what = "Fits a quantile regression model over a window frame and returns the prediction of the current row.";
+	const vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
+	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
+	auto fill = [&](const string &fname) {
+		AggregateFunctionSet set(fname);
+		for (auto *args : {&basic, &map_args})
+			set.AddFunction(AggregateFunction(fname, *args, GetHipQuantileFitPredictResultType(), AggregateFunction::StateSize<HipQuantileRowsState>,
+			                                  HipQuantileRowsInitialize, HipQuantileRowsUpdate<true>, HipQuantileRowsCombine<true>,
+			                                  HipQuantileFitPredictFinalize, nullptr, HipQuantileFitPredictBind, HipQuantileRowsDestroy));
+		return set;
+	};
+	CreateAggregateFunctionInfo info(fill(name));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'tau': 0.9})", {"y", "x", "options"}, map_args));
+	RegisterWithAlias(loader, std::move(info), fill("quantile_fit_predict"));
+}
+
+} // namespace duckdb
