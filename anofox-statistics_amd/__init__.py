@@ -27,6 +27,9 @@ from .options import (ElasticNetOptions, ElasticNetPredictOptions, InvalidInputE
                       parse_rls_options, BlsOptions, parse_bls_options, parse_nnls_options, parse_bls_predict_options,
                       QuantileOptions, parse_quantile_options, QuantilePathOptions, parse_quantile_path_options)
 from .runtime import AggState, Context, quantile_fit_predict_window_host, quantile_fit_predict_frames_host, quantile_window_plan, quantile_window_test_hooks, quantile_window_stats, quantile_fit_path_batch_host, quantile_fit_path_batch_device, quantile_fit_predict_path_batch_host, quantile_fit_batch_host, quantile_fit_predict_batch_host, bls_fit_batch_host, bls_fit_predict_batch_host, rls_fit_batch_host, rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
+from .glm import (GlmFitAggResult, binomial_fit_agg, glm_fit_batch_device, glm_fit_batch_host, glm_fit_predict_batch_device, glm_fit_predict_batch_host,  # noqa: E402
+                  logistic_fit, logistic_fit_agg, poisson_fit, poisson_fit_agg, poisson_fit_predict_agg)
+from .options import GlmOptions, parse_binomial_options, parse_poisson_options  # noqa: E402
 from .scalar import quantile_fit, quantile_fit_path, aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
@@ -39,6 +42,8 @@ SQL_FUNCTIONS.update({
     "anofox_stats_rls_fit": rls_fit, "rls_fit": rls_fit,
     "anofox_stats_quantile_fit": quantile_fit, "quantile_fit": quantile_fit,
     "anofox_stats_quantile_fit_path": quantile_fit_path, "quantile_fit_path": quantile_fit_path,
+    "anofox_stats_poisson_fit": poisson_fit, "poisson_fit": poisson_fit,
+    "anofox_stats_logistic_fit": logistic_fit, "logistic_fit": logistic_fit,
     "anofox_stats_predict": predict,
     "anofox_stats_aic": aic, "aic": aic, "anofox_stats_bic": bic, "bic": bic,
     "anofox_stats_vif": vif, "vif": vif,
@@ -71,6 +76,9 @@ __all__ = [
     "quantile_fit_path_batch_device", "quantile_fit_predict_path_batch_host",
     "quantile_fit_predict", "quantile_fit_predict_window_host", "quantile_fit_predict_frames_host", "quantile_window_plan",
     "quantile_window_test_hooks", "quantile_window_stats",
+    "GlmOptions", "parse_poisson_options", "parse_binomial_options", "GlmFitAggResult", "poisson_fit_agg", "binomial_fit_agg",
+    "logistic_fit_agg", "poisson_fit_predict_agg", "poisson_fit", "logistic_fit", "glm_fit_batch_host",
+    "glm_fit_predict_batch_host", "glm_fit_batch_device", "glm_fit_predict_batch_device",
 ]
 
 

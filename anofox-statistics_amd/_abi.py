@@ -151,6 +151,44 @@ class AnofoxHipQuantileBatchOptions(C.Structure):
     _fields_ = AnofoxQuantileOptions._fields_
 
 
+class AnofoxGlmFitResultCore(C.Structure):  # anofox_stats_ffi.h:715-741, 88 bytes
+    _fields_ = [("coefficients", _DP), ("coefficients_len", C.c_size_t), ("intercept", C.c_double), ("deviance", C.c_double),
+                ("null_deviance", C.c_double), ("pseudo_r_squared", C.c_double), ("aic", C.c_double), ("dispersion", C.c_double),
+                ("n_observations", C.c_size_t), ("n_features", C.c_size_t), ("iterations", C.c_uint32), ("converged", C.c_bool)]
+
+
+class AnofoxPriorSpec(C.Structure):  # anofox_stats_ffi.h:775-779, 24 bytes
+    _fields_ = [("kind", C.c_int), ("loc", C.c_double), ("scale", C.c_double)]
+
+
+class AnofoxPoissonOptions(C.Structure):  # anofox_stats_ffi.h:796-819, 80 bytes
+    _fields_ = [("fit_intercept", C.c_bool), ("link", C.c_int), ("max_iterations", C.c_uint32), ("tolerance", C.c_double),
+                ("compute_inference", C.c_bool), ("confidence_level", C.c_double), ("lambda_", C.c_double),
+                ("priors", C.POINTER(AnofoxPriorSpec)), ("priors_len", C.c_size_t), ("vcov", C.c_int), ("offset_column", C.c_size_t)]
+
+
+class AnofoxBinomialOptions(C.Structure):  # anofox_stats_ffi.h:824-847, 80 bytes
+    _fields_ = AnofoxPoissonOptions._fields_
+
+
+class AnofoxLogisticOptions(C.Structure):  # anofox_stats_ffi.h:1008-1026, 80 bytes
+    _fields_ = [("fit_intercept", C.c_bool), ("compute_inference", C.c_bool), ("confidence_level", C.c_double),
+                ("lambda_", C.c_double), ("threshold", C.c_double), ("max_iterations", C.c_uint32), ("tolerance", C.c_double),
+                ("priors", C.POINTER(AnofoxPriorSpec)), ("priors_len", C.c_size_t), ("vcov", C.c_int), ("offset_column", C.c_size_t)]
+
+
+class AnofoxLogisticFitExtras(C.Structure):  # anofox_stats_ffi.h:1032-1037
+    _fields_ = [("accuracy", C.c_double), ("threshold", C.c_double)]
+
+
+GLM_FAMILY = {"poisson": 0, "binomial": 1, "logistic": 1}
+
+
+class AnofoxHipGlmBatchOptions(C.Structure):
+    _fields_ = [("family", C.c_int32), ("fit_intercept", C.c_bool), ("max_iterations", C.c_uint32), ("tolerance", C.c_double),
+                ("lambda_", C.c_double), ("compute_inference", C.c_bool), ("confidence_level", C.c_double)]
+
+
 # every symbol include/anofox_stats_hip.h declares: name -> (restype, argtypes)
 _ERRP = C.POINTER(AnofoxError)
 _CTX = C.c_void_p
@@ -390,6 +428,25 @@ SYMBOLS = {
                                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ERRP]),
     "anofox_hip_quantile_window_test_hooks": (None, [C.c_int64, C.c_int64]),
     "anofox_hip_quantile_window_stats": (C.c_bool, [_CTX, C.POINTER(C.c_int64), _ERRP]),
+    "anofox_hip_glm_record_len": (C.c_size_t, [C.c_size_t]),
+    "anofox_hip_glm_fit_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                                   C.c_void_p, AnofoxHipGlmBatchOptions, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_glm_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP, C.POINTER(_DP), _DP,
+                                                 AnofoxHipGlmBatchOptions, _DP, _DP, _ERRP]),
+    "anofox_hip_glm_fit_predict_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                           C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, AnofoxHipGlmBatchOptions,
+                                                           C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_glm_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                         C.POINTER(_DP), _DP, C.POINTER(C.c_int64), AnofoxHipGlmBatchOptions, _DP, _DP,
+                                                         _ERRP]),
+    "anofox_poisson_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxPoissonOptions,
+                                      C.POINTER(AnofoxGlmFitResultCore), C.POINTER(AnofoxFitResultInference), _ERRP]),
+    "anofox_binomial_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxBinomialOptions,
+                                       C.POINTER(AnofoxGlmFitResultCore), C.POINTER(AnofoxFitResultInference), _ERRP]),
+    "anofox_logistic_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxLogisticOptions,
+                                       C.POINTER(AnofoxGlmFitResultCore), C.POINTER(AnofoxFitResultInference),
+                                       C.POINTER(AnofoxLogisticFitExtras), _ERRP]),
+    "anofox_free_glm_result": (None, [C.POINTER(AnofoxGlmFitResultCore)]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "anofox_hip_host_free": (None, [C.c_void_p]),
 }

@@ -1149,3 +1149,14 @@ SQL_FUNCTIONS.update({
     "anofox_stats_quantile_path_fit_predict_agg": quantile_path_fit_predict_agg,
     "quantile_path_fit_predict_agg": quantile_path_fit_predict_agg,
 })
+
+
+# generalised linear models (glm.py): poisson_fit_agg, binomial_fit_agg, logistic_fit_agg, poisson_fit_predict_agg
+from .glm import (GlmFitAggResult, binomial_fit_agg, logistic_fit_agg, poisson_fit_agg, poisson_fit_predict_agg)  # noqa: E402
+
+SQL_FUNCTIONS.update({
+    "anofox_stats_poisson_fit_agg": poisson_fit_agg, "poisson_fit_agg": poisson_fit_agg,
+    "anofox_stats_binomial_fit_agg": binomial_fit_agg, "binomial_fit_agg": binomial_fit_agg,
+    "anofox_stats_logistic_fit_agg": logistic_fit_agg, "logistic_fit_agg": logistic_fit_agg,
+    "anofox_stats_poisson_fit_predict_agg": poisson_fit_predict_agg, "poisson_fit_predict_agg": poisson_fit_predict_agg,
+})

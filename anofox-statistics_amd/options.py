@@ -474,3 +474,86 @@ def parse_rls_options(opts: Optional[Mapping[str, Any]]) -> RlsOptions:
         elif key == "lambda_scaling":
             _extract_enum(val, _abi.LAMBDA_SCALING, "lambda_scaling", "'raw', 'glmnet'")
     return out
+
+
+@dataclass
+class GlmOptions:
+    """Resolved options of the GLM family (the reference's PoissonOptions / BinomialOptions defaults: an intercept, 100 IRLS
+    iterations, tolerance 1e-8, lambda 0, no inference, confidence 0.95).  offset: the 1-based index into x of the offset column
+    (0 = none), as the reference's offset_column."""
+    family: str = "poisson"
+    fit_intercept: bool = True
+    max_iterations: int = 100
+    tolerance: float = 1e-8
+    lambda_: float = 0.0
+    link: str = ""
+    compute_inference: bool = False
+    confidence_level: float = 0.95
+    offset: int = 0
+
+    def batch_options(self) -> "_abi.AnofoxHipGlmBatchOptions":
+        return _abi.AnofoxHipGlmBatchOptions(_abi.GLM_FAMILY[self.family], self.fit_intercept, self.max_iterations, self.tolerance,
+                                             self.lambda_, self.compute_inference, self.confidence_level)
+
+
+_GLM_LINKS = {"poisson": ("log", ("identity", "sqrt")), "binomial": ("logit", ("probit", "cloglog"))}
+
+
+def _parse_glm(opts: Optional[Mapping[str, Any]], family: str) -> GlmOptions:
+    out = GlmOptions(family=family, link=_GLM_LINKS[family][0])
+    if opts is None:
+        return out
+    if not isinstance(opts, Mapping):
+        raise InvalidInputException("Options parameter must be a constant expression")
+    for raw_key, val in opts.items():
+        key = str(raw_key).lower()
+        if key in ("intercept", "fit_intercept"):
+            v = _extract_bool(val)
+            if v is not None:
+                out.fit_intercept = v
+        elif key in ("max_iterations", "max_iter"):
+            v = _extract_uint32(val)
+            if v is not None:
+                out.max_iterations = v
+        elif key in ("tolerance", "tol"):
+            v = _extract_double(val)
+            if v is not None:
+                out.tolerance = v
+        elif key == "lambda":
+            v = _extract_double(val)
+            if v is not None:
+                out.lambda_ = v
+        elif key == "compute_inference":
+            v = _extract_bool(val)
+            if v is not None:
+                out.compute_inference = v
+        elif key == "confidence_level":
+            v = _extract_double(val)
+            if v is not None:
+                out.confidence_level = v
+        elif key == "offset":
+            v = _extract_uint32(val)
+            if v is not None:
+                out.offset = v
+        elif key == "link" and val is not None:
+            out.link = str(val).lower()
+        elif key == "vcov" and val is not None and str(val).lower() != "laplace":
+            raise InvalidInputException("glm: vcov %s is not built" % str(val).lower())
+        elif key in ("priors", "prior") and val is not None:
+            raise InvalidInputException("glm: priors are not built")
+    if out.link != _GLM_LINKS[family][0]:
+        raise InvalidInputException("glm: link %s is not built" % out.link)
+    return out
+
+
+def parse_poisson_options(opts: Optional[Mapping[str, Any]]) -> GlmOptions:
+    """poisson_fit_agg's MAP options: fit_intercept / intercept, max_iterations / max_iter, tolerance / tol, lambda, link (only
+    'log' is built), compute_inference, confidence_level, offset.  Keys are case-insensitive; other keys are ignored, except that
+    vcov other than 'laplace' and priors fail with "not built" (the contract: they fail the call, they are not dropped).  The
+    values are not range-checked here: the fit reports them (status 1 / InvalidInput)."""
+    return _parse_glm(opts, "poisson")
+
+
+def parse_binomial_options(opts: Optional[Mapping[str, Any]]) -> GlmOptions:
+    """binomial_fit_agg's / logistic_fit_agg's MAP options: parse_poisson_options' keys; only the 'logit' link is built."""
+    return _parse_glm(opts, "binomial")

@@ -326,6 +326,23 @@ class Context:
     def quantile_fit_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions):
         return quantile_fit_batch_host(row_offsets, y, x_cols, options, ctx=self)
 
+    def glm_fit_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, offset=None,
+                             inference: bool = False, use_current_torch_stream: bool = True):
+        """Grouped Poisson / binomial fits on CUDA tensors through the fused IRLS kernel (glm.glm_fit_batch_device)."""
+        from .glm import glm_fit_batch_device
+        return glm_fit_batch_device(self, row_offsets, y, x_cols, options, offset, inference, use_current_torch_stream)
+
+    def glm_fit_predict_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, offset=None,
+                                     train_counts=None, use_current_torch_stream: bool = True):
+        """GLM fit + predict on CUDA tensors: (core[G, p + 11], pred[N, 3]) (glm.glm_fit_predict_batch_device)."""
+        from .glm import glm_fit_predict_batch_device
+        return glm_fit_predict_batch_device(self, row_offsets, y, x_cols, options, offset, train_counts, use_current_torch_stream)
+
+    def glm_fit_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, offset=None,
+                           inference: bool = False):
+        from .glm import glm_fit_batch_host
+        return glm_fit_batch_host(row_offsets, y, x_cols, options, offset, inference, ctx=self)
+
     def quantile_fit_path_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions, taus,
                                        records=None, iterations=None, use_current_torch_stream: bool = True):
         """The tau path on CUDA tensors (inputs as quantile_fit_batch_device; taus: a host sequence of 1 .. 64 floats).

@@ -330,3 +330,7 @@ def residuals_diagnostics(y, y_hat, x=None, residual_std_error=None, include_stu
                     studentized=take(res.studentized, res.has_studentized), leverage=take(res.leverage, res.has_leverage))
     finally:
         lib.anofox_free_residuals(C.byref(res))
+
+
+# generalised linear models (glm.py)
+from .glm import logistic_fit, poisson_fit  # noqa: E402,F401

@@ -334,6 +334,110 @@ ANOFOX_HIP_API void anofox_free_quantile_result(AnofoxQuantileFitResultCore *res
 ANOFOX_HIP_API bool anofox_quantile_fit_path(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxQuantileOptions options,
                               const double *taus, size_t n_taus, AnofoxQuantileFitResultCore *out_results, AnofoxError *out_error);
 
+/* replace AnofoxPoissonLink / AnofoxBinomialLink, anofox_stats_ffi.h:697-710.  Only the canonical links (0) are built. */
+typedef enum { ANOFOX_POISSON_LINK_LOG = 0, ANOFOX_POISSON_LINK_IDENTITY = 1, ANOFOX_POISSON_LINK_SQRT = 2 } AnofoxPoissonLink;
+typedef enum { ANOFOX_BINOMIAL_LINK_LOGIT = 0, ANOFOX_BINOMIAL_LINK_PROBIT = 1, ANOFOX_BINOMIAL_LINK_CLOGLOG = 2 } AnofoxBinomialLink;
+
+/* replaces AnofoxGlmFitResultCore, anofox_stats_ffi.h:715-741 — 88 bytes: coefficients @0, coefficients_len @8, intercept @16,
+ * deviance @24, null_deviance @32, pseudo_r_squared @40, aic @48, dispersion @56, n_observations @64, n_features @72,
+ * iterations @80, converged @84 */
+typedef struct {
+	double *coefficients; /* malloc'ed by the callee, released by anofox_free_glm_result */
+	size_t coefficients_len;
+	double intercept; /* NaN without an intercept */
+	double deviance;
+	double null_deviance;
+	double pseudo_r_squared;
+	double aic;
+	double dispersion;
+	size_t n_observations;
+	size_t n_features;
+	uint32_t iterations;
+	bool converged;
+} AnofoxGlmFitResultCore;
+
+/* replace AnofoxPriorKind / AnofoxPriorSpec / AnofoxVcovType, anofox_stats_ffi.h:759-791.  Priors are not built: a non-NULL
+ * priors pointer fails the call; only ANOFOX_VCOV_LAPLACE is built. */
+typedef enum { ANOFOX_PRIOR_FLAT = 0, ANOFOX_PRIOR_NORMAL = 1, ANOFOX_PRIOR_LAPLACE = 2 } AnofoxPriorKind;
+typedef struct {
+	AnofoxPriorKind kind;
+	double loc;
+	double scale;
+} AnofoxPriorSpec;
+typedef enum { ANOFOX_VCOV_LAPLACE = 0, ANOFOX_VCOV_SANDWICH = 1, ANOFOX_VCOV_NAIVE = 2 } AnofoxVcovType;
+
+/* replaces AnofoxPoissonOptions, anofox_stats_ffi.h:796-819 — 80 bytes: fit_intercept @0, link @4, max_iterations @8,
+ * tolerance @16, compute_inference @24, confidence_level @32, lambda @40, priors @48, priors_len @56, vcov @64,
+ * offset_column @72 (1-based index into x of the offset column, 0 = none) */
+typedef struct {
+	bool fit_intercept;
+	AnofoxPoissonLink link;
+	uint32_t max_iterations;
+	double tolerance;
+	bool compute_inference;
+	double confidence_level;
+	double lambda;
+	const AnofoxPriorSpec *priors;
+	size_t priors_len;
+	AnofoxVcovType vcov;
+	size_t offset_column;
+} AnofoxPoissonOptions;
+
+/* replaces AnofoxBinomialOptions, anofox_stats_ffi.h:824-847 — the layout of AnofoxPoissonOptions with the binomial link */
+typedef struct {
+	bool fit_intercept;
+	AnofoxBinomialLink link;
+	uint32_t max_iterations;
+	double tolerance;
+	bool compute_inference;
+	double confidence_level;
+	double lambda;
+	const AnofoxPriorSpec *priors;
+	size_t priors_len;
+	AnofoxVcovType vcov;
+	size_t offset_column;
+} AnofoxBinomialOptions;
+
+/* replaces AnofoxLogisticOptions, anofox_stats_ffi.h:1008-1026 — 80 bytes: fit_intercept @0, compute_inference @1,
+ * confidence_level @8, lambda @16, threshold @24, max_iterations @32, tolerance @40, priors @48, priors_len @56, vcov @64,
+ * offset_column @72 */
+typedef struct {
+	bool fit_intercept;
+	bool compute_inference;
+	double confidence_level;
+	double lambda;
+	double threshold; /* the classification threshold on P(y = 1), in [0, 1] */
+	uint32_t max_iterations;
+	double tolerance;
+	const AnofoxPriorSpec *priors;
+	size_t priors_len;
+	AnofoxVcovType vcov;
+	size_t offset_column;
+} AnofoxLogisticOptions;
+
+/* replaces AnofoxLogisticFitExtras, anofox_stats_ffi.h:1032-1037: the share of the fitted rows with [mu >= threshold] == y,
+ * and the threshold echoed */
+typedef struct {
+	double accuracy;
+	double threshold;
+} AnofoxLogisticFitExtras;
+
+/* replace anofox_poisson_fit / anofox_binomial_fit / anofox_logistic_fit / anofox_free_glm_result, anofox_stats_ffi.h:953-1059
+ * (over crates/anofox-stats-core/src/models/glm.rs and glm_engine/): one group through anofox_hip_glm_fit_batch_host below,
+ * with anofox_ols_fit's conventions.  offset_column is split out of x on the host (design.rs:186-202).  A link other than
+ * log / logit, non-NULL priors or a vcov other than Laplace: false with ANOFOX_ERROR_INVALID_INPUT and "glm: ... is not
+ * built".  anofox_logistic_fit wants y in {0, 1} and threshold in [0, 1].  The contract: DESIGN.md §1 "Generalised linear
+ * models".  out_inference (may be NULL) gets z values in t_values and NaN in f_statistic / f_pvalue.  A call that fails leaves
+ * out_core zeroed (NaN in its doubles), out_inference reset to {NULLs, len 0, NaNs} and out_extras NaN: nothing to free. */
+ANOFOX_HIP_API bool anofox_poisson_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxPoissonOptions options,
+                        AnofoxGlmFitResultCore *out_core, AnofoxFitResultInference *out_inference, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_binomial_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxBinomialOptions options,
+                         AnofoxGlmFitResultCore *out_core, AnofoxFitResultInference *out_inference, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_logistic_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxLogisticOptions options,
+                         AnofoxGlmFitResultCore *out_result, AnofoxFitResultInference *out_inference,
+                         AnofoxLogisticFitExtras *out_extras, AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_glm_result(AnofoxGlmFitResultCore *result);
+
 #endif /* ANOFOX_STATS_FFI_H */
 
 /* ------------------------------------------------------------------------ */
@@ -609,6 +713,60 @@ ANOFOX_HIP_API bool anofox_hip_quantile_fit_predict_path_batch_host(AnofoxHipCon
                                                      AnofoxHipQuantileBatchOptions options, const double *taus, size_t n_taus,
                                                      double *quantile, int32_t *iterations, double *pred, AnofoxError *out_error);
 
+
+/*
+ * Grouped generalised linear models (anofox_poisson_fit / anofox_binomial_fit / anofox_logistic_fit and the aggregates
+ * poisson_fit_agg, binomial_fit_agg, logistic_fit_agg, poisson_fit_predict_agg): per group, over the rows whose y, x and offset
+ * are all finite, THE minimiser of deviance(beta) + lambda sum_j beta_j^2 (the intercept not penalised) for Poisson / log or
+ * binomial / logit, by the reference's IRLS loop fused into one kernel, one wavefront per group (DESIGN.md §1 "Generalised
+ * linear models").  1 <= n_features <= 32; more fails the call.  offset (may be NULL): one double per row, added to eta.
+ * Records (anofox_hip_glm_record_len(p) = p + 11 doubles):
+ *   glm[g] = { coefficients[0..p), intercept (NaN without one), deviance, null_deviance (at mu = mean y of the valid rows),
+ *              pseudo_r_squared, aic, dispersion, n_observations, n_params, iterations, converged, status }
+ * status != 0 => every other field is NaN; statuses 1 (invalid options: every group of the call; or a finite y outside the
+ * support: y < 0 for Poisson, y outside [0, 1] for binomial), 3 (no convergence in max_iterations), 6 (fewer valid rows than
+ * max(k, 1), k = the fitted columns + [intercept]), 10 (no valid row), ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS (fit-predict only).
+ * A column that is constant over the valid rows (with an intercept) or aliased has a NaN coefficient.
+ * inference (may be NULL): [n_groups x 5 p] = { se[p], z[p], p[p], ci_lower[p], ci_upper[p] } per group, the intercept
+ * stripped; NaN when compute_inference is false, for a failed group and for a dropped or aliased column.
+ * Invalid options: tolerance not finite and positive, lambda < 0 or NaN, an unknown family, max_iterations = 0, and a
+ * confidence_level outside (0, 1) while compute_inference is set.
+ */
+#define ANOFOX_HIP_GLM_POISSON 0  /* log link */
+#define ANOFOX_HIP_GLM_BINOMIAL 1 /* logit link; logistic is the same fit */
+typedef struct {
+	int32_t family;
+	bool fit_intercept;
+	uint32_t max_iterations;
+	double tolerance;
+	double lambda;
+	bool compute_inference;
+	double confidence_level;
+} AnofoxHipGlmBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_glm_record_len(size_t n_features);
+ANOFOX_HIP_API bool anofox_hip_glm_fit_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                     const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                     const double *d_offset, AnofoxHipGlmBatchOptions options, double *d_records,
+                                     double *d_inference, AnofoxError *out_error);
+/* host pointers, synchronous; ctx may be NULL (per-thread default context) */
+ANOFOX_HIP_API bool anofox_hip_glm_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                   const int64_t *row_offsets, const double *y, const double *const *x_cols, const double *offset,
+                                   AnofoxHipGlmBatchOptions options, double *records, double *inference, AnofoxError *out_error);
+/*
+ * Fit + predict (poisson_fit_predict_agg): the fit above on each group's rows with a finite y, then pred = {mu, NaN, NaN}
+ * ([n_rows x 3], the response scale, no interval) for every row of the group, training or not; a row with a non-finite x or
+ * offset gets NaN.  core: the records above.  Fewer than 2 training rows (train_counts, optional; the group's rows without
+ * it) or a failed fit: status != 0 and NaN for every row of the group.  The same kernel writes records and predictions.
+ */
+ANOFOX_HIP_API bool anofox_hip_glm_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                             const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                             const double *d_offset, const int64_t *d_train_counts,
+                                             AnofoxHipGlmBatchOptions options, double *d_core, double *d_pred, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_glm_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                           const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                           const double *offset, const int64_t *train_counts, AnofoxHipGlmBatchOptions options,
+                                           double *core, double *pred, AnofoxError *out_error);
 
 /*
  * Information criteria as batched outputs of the fit records: what the SQL functions
