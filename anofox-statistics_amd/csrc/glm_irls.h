@@ -14,8 +14,10 @@
 //   start      R's mustart: mu = y + 0.1 (Poisson), (y + 0.5) / 2 (binomial); eta = link(mu); beta = 0.
 //   iteration  w = mu (Poisson), mu (1 - mu) (binomial);  z = eta - offset + (y - mu) / w;  solve (X'WX + lambda I') beta = X'Wz;
 //              eta, mu and the objective at the new beta;  converged when |obj - obj_old| / (0.1 + |obj|) < tolerance or
-//              max|delta beta| < tolerance (tested before step halving and again after it);  up to 10 halvings of the step
-//              while obj > obj_old + 1e-7 |obj_old| + eps max(scale, 1), scale = |null deviance|.
+//              max|delta beta| < tolerance (tested before step halving and again after it);  from the second iteration on, up
+//              to 10 halvings of the step while obj > obj_old + 1e-7 |obj_old| + eps (max(scale, 1) + 8 (n + sum y)),
+//              scale = |null deviance|, the last term the rounding of the deviance's own sum (the first iteration's obj_old
+//              is the deviance at mustart, which no beta attains: nothing to halve against).
 //   Gram       the augmented matrix [X z]'W[X z], (k + 1)(k + 2) / 2 sums (595 at k = 33), by LANES OVER MATRIX ENTRIES ON A
 //              ROW TILE STAGED IN LDS: the 64 lanes stage 64 rows {a_i, z_i, w_i} (each lane its own row), then every lane
 //              adds the tile's rows, in row order, into the entries it owns, which stay in registers (ceil(595 / 64) = 10 at
@@ -422,7 +424,7 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 	}
 	// ---- first pass: the row mask, the start values, sum y, the first valid row ----
 	int64_t n_valid, first;
-	double ybar;
+	double ybar, sum_y;
 	{
 		GiPL<int64_t> cnt, bad, fst;
 		GiPL<double> sy;
@@ -456,7 +458,8 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 		n_valid = gi_sum_i(cnt);
 		const int64_t n_bad = gi_sum_i(bad);
 		first = gi_min_i(fst);
-		ybar = gi_sum(sy) / (double)(n_valid > 0 ? n_valid : 1);
+		sum_y = gi_sum(sy);
+		ybar = sum_y / (double)(n_valid > 0 ? n_valid : 1);
 		if (n_bad > 0) status = kGiStatusInvalidInput;
 		else if (n_valid == 0) status = kGiStatusNoValidData;
 	}
@@ -548,7 +551,9 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 	GI_LANES_END
 	gi_sync();
 	// ---- the loop ----
-	const double scale = fabs(null_dev), floor_ = DBL_EPSILON * (scale > 1.0 ? scale : 1.0);
+	// (a unit deviance is rounded to a few eps (y + mu), mostly exp's ulp: an increase below 8 eps (n + sum y) is not one.  It
+	// decides only where the deviance itself is that small: a saturated fit of large counts, whose step it otherwise halves on noise)
+	const double scale = fabs(null_dev), floor_ = DBL_EPSILON * ((scale > 1.0 ? scale : 1.0) + 8.0 * ((double)n_valid + sum_y));
 	bool converged = false;
 	int iterations = 0;
 	uint64_t alias = dropped;
@@ -572,7 +577,9 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 			converged = true;
 			break;
 		}
-		if (gi_finite(obj) && gi_finite(obj_old)) {
+		// (not on the first iteration: its obj_old is the deviance at mustart, nearly the saturated fit, which no beta attains;
+		// every first step is "worse" than it, and ten halvings towards beta = 0 strand a fit with large counts)
+		if (it > 0 && gi_finite(obj) && gi_finite(obj_old)) {
 			int halvings = 0;
 			while (obj > obj_old + 1e-7 * fabs(obj_old) + floor_ && halvings < kGiMaxHalvings) {
 				++halvings;

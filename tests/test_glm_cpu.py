@@ -112,9 +112,11 @@ def test_no_convergence_status(host_glm):
 GOLDEN = os.path.join(ROOT, "tests", "golden", "glm")
 
 
-@pytest.mark.parametrize("name", ["poisson_offset", "binomial_ridge", "poisson_constant_column"])
+@pytest.mark.parametrize("name", ["poisson_offset", "binomial_ridge", "poisson_constant_column", "poisson_large_counts"])
 def test_golden_fixture(host_glm, name):
-    """Reduced cases committed as data: inputs and the restatement's outputs."""
+    """Reduced cases committed as data: inputs and the restatement's outputs.  poisson_large_counts (n = 30, p = 1, an
+    intercept, mean count 54286) is the defect of halving the first step against the deviance at mustart: ten halvings took
+    beta from the near-optimal first solve to beta / 1024, the restart from mu = 1 overflowed, and the fit ended with status 3."""
     with open(os.path.join(GOLDEN, name + ".json")) as f:
         fx = json.load(f)
     y, x = np.array(fx["y"], float), np.array(fx["x"], float)
