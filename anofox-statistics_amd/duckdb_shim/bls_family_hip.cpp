@@ -34,11 +34,14 @@
 #include "anofox_stats_hip.h"
 #include "bls_family_hip.hpp"
 #include "hip_options.hpp"
+#include "row_glue.hpp"
 
 namespace duckdb {
 
 namespace {
 using namespace hip_glue;
+
+const vector<string> kCategories = {"regression"};
 
 struct HipBlsOptions {
 	bool fit_intercept = false; // bls_aggregate.cpp:49
@@ -68,47 +71,30 @@ struct HipBlsOptions {
 	}
 };
 
-// bounds = false: nnls_fit_agg's bind; predict = true: the fit-predict aggregate's
-void ApplyBlsOption(const string &raw_key, const Value &v, HipBlsOptions &o, bool bounds, bool predict) {
-	if (v.IsNull()) return;
-	const string key = Lower(raw_key);
-	if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(v);
-	else if (key == "max_iterations" || key == "max_iter") {
-		const double it = v.GetValue<double>();
-		if (!(it >= 0.0 && it <= 4294967295.0)) throw InvalidInputException("Value %s is out of range for UINTEGER", v.ToString().c_str());
-		o.max_iterations = (uint32_t)it;
-	} else if (key == "tolerance" || key == "tol") o.tolerance = v.GetValue<double>();
-	else if (key == "lower_bound" || key == "lower") {
-		const double b = v.GetValue<double>(); // (parsed by the shared parser whoever reads it)
-		if (bounds) { o.lower = b; o.has_lower = true; }
-	} else if (key == "upper_bound" || key == "upper") {
-		const double b = v.GetValue<double>();
-		if (bounds) { o.upper = b; o.has_upper = true; }
-	} else if (key == "confidence_level" || key == "confidence") {
-		const double c = v.GetValue<double>();
-		if (predict) o.confidence_level = c;
-	} else if (key == "null_policy") {
-		const string s = Lower(v.type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(v) : v.ToString());
-		if (s != "drop" && s != "drop_y_zero_x") throw InvalidInputException("Invalid null_policy: '%s'. Valid values are 'drop', 'drop_y_zero_x'", s.c_str());
-		if (predict) o.drop_y_zero_x = s == "drop_y_zero_x";
-	}
-	// every other key: ignored, as in the reference
-}
-
+// bounds = false: nnls_fit_agg's bind; predict = true: the fit-predict aggregate's.  A key this bind does not read is still
+// converted (parsed by the shared parser whoever reads it).
 void ParseHipBlsOptions(const Value &v, HipBlsOptions &o, bool bounds, bool predict) {
 	if (v.IsNull()) return;
-	if (v.type().id() == LogicalTypeId::STRUCT) {
-		auto &kids = StructValue::GetChildren(v);
-		for (idx_t i = 0; i < kids.size(); i++) ApplyBlsOption(StructType::GetChildName(v.type(), i), kids[i], o, bounds, predict);
-	} else if (v.type().id() == LogicalTypeId::MAP) {
-		for (auto &entry : MapValue::GetChildren(v)) {
-			auto &kv = StructValue::GetChildren(entry);
-			if (kv.size() != 2 || kv[0].IsNull()) continue;
-			ApplyBlsOption(kv[0].type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(kv[0]) : kv[0].ToString(), kv[1], o, bounds, predict);
+	VisitOptionEntries(v, [&](const string &key, const Value &val) {
+		if (val.IsNull()) return;
+		if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(val);
+		else if (key == "max_iterations" || key == "max_iter") o.max_iterations = ExtractUInteger(val);
+		else if (key == "tolerance" || key == "tol") o.tolerance = val.GetValue<double>();
+		else if (key == "lower_bound" || key == "lower") {
+			const double b = val.GetValue<double>();
+			if (bounds) { o.lower = b; o.has_lower = true; }
+		} else if (key == "upper_bound" || key == "upper") {
+			const double b = val.GetValue<double>();
+			if (bounds) { o.upper = b; o.has_upper = true; }
+		} else if (key == "confidence_level" || key == "confidence") {
+			const double c = val.GetValue<double>();
+			if (predict) o.confidence_level = c;
+		} else if (key == "null_policy") {
+			const bool drop_y_zero_x = ExtractNullPolicy(val);
+			if (predict) o.drop_y_zero_x = drop_y_zero_x;
 		}
-	} else {
-		throw InvalidInputException("Options must be a MAP or STRUCT, got %s", v.type().ToString().c_str());
-	}
+		// every other key: ignored, as in the reference
+	});
 }
 
 struct HipBlsBindData : public FunctionData {
@@ -122,113 +108,18 @@ struct HipBlsBindData : public FunctionData {
 	}
 };
 
-// ---- the row buffer behind a DuckDB state (the layout of family_agg_hip.cpp's) ----
-constexpr uint8_t kYNull = 1, kTraining = 2;
-struct BlsRowBuffer {
-	idx_t n_features = 0;
-	vector<double> y;      // NaN where y was NULL
-	vector<double> x;      // row-major; a NULL list element is NaN
-	vector<uint8_t> flags; // kYNull | kTraining
-	idx_t n_training = 0;
-	idx_t Rows() const { return y.size(); }
-};
-struct HipBlsRowsState {
-	BlsRowBuffer *rows;
-};
-
-void HipBlsRowsInitialize(const AggregateFunction &, data_ptr_t state_p) { reinterpret_cast<HipBlsRowsState *>(state_p)->rows = nullptr; }
-
-void HipBlsRowsDestroy(Vector &state_vector, AggregateInputData &, idx_t count) {
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipBlsRowsState **)sdata.data;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		delete state.rows;
-		state.rows = nullptr;
-	}
-}
-
-BlsRowBuffer &BlsRows(HipBlsRowsState &state, idx_t n_features) {
-	if (!state.rows) {
-		state.rows = new BlsRowBuffer();
-		state.rows->n_features = n_features;
-	}
-	if (state.rows->n_features != n_features) throw InvalidInputException("Inconsistent feature count"); // bls_fit_predict_aggregate.cpp:204-207
-	return *state.rows;
-}
-
-bool IsBlsSplitTraining(const string_t &split) { // BlsIsSplitTraining: 'train' / 'training', any case
-	string v = split.GetString();
-	for (auto &c : v) c = (char)std::tolower((unsigned char)c);
-	return v == "train" || v == "training";
-}
-
-void HipBlsRowsCombine(Vector &source_vector, Vector &target_vector, AggregateInputData &aggr_input_data, idx_t count) {
-	UnifiedVectorFormat source_data, target_data;
-	source_vector.ToUnifiedFormat(count, source_data);
-	target_vector.ToUnifiedFormat(count, target_data);
-	auto sources = (HipBlsRowsState **)source_data.data;
-	auto targets = (HipBlsRowsState **)target_data.data;
-	const bool preserve = aggr_input_data.combine_type == AggregateCombineType::PRESERVE_INPUT;
-	for (idx_t i = 0; i < count; i++) {
-		auto &source = *sources[source_data.sel->get_index(i)];
-		auto &target = *targets[target_data.sel->get_index(i)];
-		if (!source.rows || &source == &target) continue;
-		if (!target.rows) {
-			if (preserve) {
-				target.rows = new BlsRowBuffer(*source.rows);
-			} else {
-				target.rows = source.rows;
-				source.rows = nullptr;
-			}
-			continue;
-		}
-		if (source.rows->n_features != target.rows->n_features) throw InvalidInputException("Cannot combine states with different feature counts");
-		auto &t = *target.rows;
-		const auto &s = *source.rows;
-		t.y.insert(t.y.end(), s.y.begin(), s.y.end());
-		t.x.insert(t.x.end(), s.x.begin(), s.x.end());
-		t.flags.insert(t.flags.end(), s.flags.begin(), s.flags.end());
-		t.n_training += s.n_training;
-	}
-}
-
-// the states of one Finalize vector as one batch per feature count
-struct BlsPredictBatch {
-	idx_t p = 0;
-	vector<idx_t> result_rows;
-	vector<BlsRowBuffer *> buffers;
-	vector<int64_t> offsets {0};
-	vector<int64_t> train_counts;
-	vector<double> y, cols, core, pred;
+// the states of one Finalize vector as one batch per feature count (RowBatch) through the fit-predict call
+struct BlsPredictBatch : RowBatch {
+	vector<double> core, pred;
 	void Run(const HipBlsOptions &opts) {
-		int64_t n = 0;
-		for (auto *b : buffers) {
-			n += (int64_t)b->Rows();
-			offsets.push_back(n);
-			train_counts.push_back((int64_t)b->n_training);
-		}
-		y.resize((size_t)n);
-		cols.resize((size_t)n * p);
-		int64_t at = 0;
-		for (auto *b : buffers) {
-			const idx_t rows = b->Rows();
-			for (idx_t r = 0; r < rows; r++) {
-				y[at + r] = (b->flags[r] & kTraining) ? b->y[r] : NAN;
-				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at + r] = b->x[r * p + j];
-			}
-			at += (int64_t)rows;
-		}
-		vector<const double *> col_ptrs(p);
-		for (idx_t j = 0; j < p; j++) col_ptrs[j] = cols.data() + j * (size_t)n;
-		core.resize(buffers.size() * (p + 6));
+		const int64_t n = Stage(false, false);
+		core.resize(Groups() * (p + 6));
 		pred.resize((size_t)n * 3);
 		AnofoxError err;
 		memset(&err, 0, sizeof err);
-		if (!anofox_hip_bls_fit_predict_batch_host(nullptr, (int64_t)buffers.size(), p, n, offsets.data(), y.data(), col_ptrs.data(),
-		                                           train_counts.data(), opts.Batch(), opts.confidence_level, core.data(), pred.data(), &err))
-			throw InvalidInputException("anofox_stats (HIP): %s", err.message[0] ? err.message : "the batched call failed");
+		if (!anofox_hip_bls_fit_predict_batch_host(nullptr, (int64_t)Groups(), p, n, offsets.data(), y.data(), col_ptrs.data(), train_counts.data(),
+		                                           opts.Batch(), opts.confidence_level, core.data(), pred.data(), &err))
+			ThrowAbi(err);
 	}
 	bool Failed(idx_t g) const { return core[g * (p + 6) + p + 5] != 0.0; }
 };
@@ -236,16 +127,6 @@ struct BlsPredictBatch {
 // =====================================================================================================================
 // anofox_stats_bls_fit_predict_agg(y, x[, split_col][, options]) -> LIST(STRUCT(y, yhat, yhat_lower, yhat_upper, is_training))
 // =====================================================================================================================
-LogicalType GetHipBlsPredictAggResultType() { // bls_fit_predict_aggregate.cpp:106-116
-	child_list_t<LogicalType> row_children;
-	row_children.push_back(make_pair("y", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("yhat", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("yhat_lower", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("yhat_upper", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("is_training", LogicalType::BOOLEAN));
-	return LogicalType::LIST(LogicalType::STRUCT(std::move(row_children)));
-}
-
 // Update (bls_fit_predict_aggregate.cpp:146-265): every row with a non-NULL x list is kept for the output; it trains iff y is not NULL (and the split column
 // says train), and under null_policy = 'drop_y_zero_x' no feature is exactly 0.  A NULL list element is NaN: the row is handed
 // to the fit, whose row filter drops it.
@@ -266,31 +147,24 @@ void HipBlsPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data
 		split_values = UnifiedVectorFormat::GetData<string_t>(split_data);
 	}
 	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipBlsRowsState **)sdata.data;
+	auto states = (RowsState **)sdata.data;
 	const idx_t max_features = anofox_hip_max_features();
 	for (idx_t i = 0; i < count; i++) {
 		auto &state = *states[sdata.sel->get_index(i)];
 		auto x_idx = x_data.sel->get_index(i);
 		if (!x_data.validity.RowIsValid(x_idx)) continue;
 		const auto entry = x_list[x_idx];
-		if (entry.length > max_features)
-			throw InvalidInputException("anofox_stats bls_fit_predict_agg (HIP): at most %llu features are supported, got %llu",
-			                            (unsigned long long)max_features, (unsigned long long)entry.length);
-		auto &rows = BlsRows(state, entry.length);
-		bool has_zero = false;
+		CheckMaxFeatures("bls_fit_predict_agg", entry.length, max_features);
+		auto &rows = RowsOf(state, entry.length, false);
 		const size_t at = rows.x.size();
 		rows.x.resize(at + entry.length);
-		for (idx_t j = 0; j < entry.length; j++) {
-			const idx_t pos = entry.offset + j;
-			rows.x[at + j] = x_child_validity.RowIsValid(pos) ? x_child_data[pos] : NAN; // never read the slot of a NULL
-			has_zero = has_zero || rows.x[at + j] == 0.0;
-		}
+		const bool has_zero = ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at).has_zero;
 		auto y_idx = y_data.sel->get_index(i);
 		const bool y_valid = y_data.validity.RowIsValid(y_idx);
 		bool training = y_valid;
 		if (bind.use_split_col && split_values) {
 			auto s_idx = split_data.sel->get_index(i);
-			training = split_data.validity.RowIsValid(s_idx) && IsBlsSplitTraining(split_values[s_idx]) && y_valid;
+			training = split_data.validity.RowIsValid(s_idx) && IsSplitTraining(split_values[s_idx]) && y_valid;
 		}
 		if (training && bind.opts.drop_y_zero_x && has_zero) training = false;
 		rows.y.push_back(y_valid ? y_values[y_idx] : NAN);
@@ -302,51 +176,13 @@ void HipBlsPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data
 // Finalize (bls_fit_predict_aggregate.cpp:326-452): NULL with fewer than 2 training rows or a failed fit; otherwise every buffered row with its prediction
 void HipBlsPredictAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipBlsBindData>();
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipBlsRowsState **)sdata.data;
-	std::map<idx_t, BlsPredictBatch> batches;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		if (!state.rows || state.rows->n_training < 2 || state.rows->n_features == 0) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		auto &b = batches[state.rows->n_features];
-		b.p = state.rows->n_features;
-		b.result_rows.push_back(i + offset);
-		b.buffers.push_back(state.rows);
-	}
+	auto batches = CollectBatches<BlsPredictBatch>(state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.n_training >= 2; });
 	for (auto &kv : batches) kv.second.Run(bind.opts);
-	auto list_data = ListVector::GetData(result);
 	for (auto &kv : batches) {
 		auto &b = kv.second;
-		for (idx_t g = 0; g < b.buffers.size(); g++) {
-			const idx_t r = b.result_rows[g];
-			if (b.Failed(g)) {
-				FlatVector::SetNull(result, r, true);
-				continue;
-			}
-			const BlsRowBuffer &rows = *b.buffers[g];
-			const idx_t n_rows = rows.Rows();
-			const idx_t list_offset = ListVector::GetListSize(result);
-			ListVector::Reserve(result, list_offset + n_rows);
-			ListVector::SetListSize(result, list_offset + n_rows);
-			list_data[r].offset = list_offset;
-			list_data[r].length = n_rows;
-			auto &fields = StructVector::GetEntries(ListVector::GetEntry(result));
-			const double *pred = &b.pred[(size_t)b.offsets[g] * 3];
-			for (idx_t row = 0; row < n_rows; row++) {
-				const idx_t at = list_offset + row;
-				if (rows.flags[row] & kYNull) FlatVector::SetNull(*fields[0], at, true);
-				else FlatVector::GetData<double>(*fields[0])[at] = rows.y[row];
-				if (isfinite(pred[row * 3])) {
-					for (idx_t k = 0; k < 3; k++) FlatVector::GetData<double>(*fields[1 + k])[at] = pred[row * 3 + k];
-				} else {
-					for (idx_t k = 0; k < 3; k++) FlatVector::SetNull(*fields[1 + k], at, true);
-				}
-				FlatVector::GetData<bool>(*fields[4])[at] = (rows.flags[row] & kTraining) != 0;
-			}
+		for (idx_t g = 0; g < b.Groups(); g++) {
+			if (b.Failed(g)) FlatVector::SetNull(result, b.result_rows[g], true);
+			else AppendPredictRows(result, b.result_rows[g], *b.buffers[g], &b.pred[(size_t)b.offsets[g] * 3]);
 		}
 	}
 }
@@ -357,7 +193,7 @@ unique_ptr<FunctionData> HipBlsPredictAggBind(ClientContext &context, AggregateF
 	const idx_t opt_idx = SPLIT ? 3 : 2;
 	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable())
 		ParseHipBlsOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts, true, true);
-	function.return_type = GetHipBlsPredictAggResultType();
+	function.return_type = PredictAggResultType();
 	return make_uniq<HipBlsBindData>(opts, SPLIT);
 }
 
@@ -392,7 +228,7 @@ void HipBlsAggUpdate(Vector inputs[], AggregateInputData &, idx_t input_count, V
 	auto x_child_data = FlatVector::GetData<double>(x_child);
 	auto &x_child_validity = FlatVector::Validity(x_child);
 	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipBlsRowsState **)sdata.data;
+	auto states = (RowsState **)sdata.data;
 	const idx_t max_features = anofox_hip_max_features();
 	for (idx_t i = 0; i < count; i++) {
 		auto &state = *states[sdata.sel->get_index(i)];
@@ -401,16 +237,11 @@ void HipBlsAggUpdate(Vector inputs[], AggregateInputData &, idx_t input_count, V
 		auto x_idx = x_data.sel->get_index(i);
 		if (!x_data.validity.RowIsValid(x_idx)) continue;
 		const auto entry = x_list[x_idx];
-		if (entry.length > max_features)
-			throw InvalidInputException("anofox_stats bls_fit_agg (HIP): at most %llu features are supported, got %llu",
-			                            (unsigned long long)max_features, (unsigned long long)entry.length);
-		auto &rows = BlsRows(state, entry.length);
+		CheckMaxFeatures("bls_fit_agg", entry.length, max_features);
+		auto &rows = RowsOf(state, entry.length, false);
 		const size_t at = rows.x.size();
 		rows.x.resize(at + entry.length);
-		for (idx_t j = 0; j < entry.length; j++) {
-			const idx_t pos = entry.offset + j;
-			rows.x[at + j] = x_child_validity.RowIsValid(pos) ? x_child_data[pos] : NAN; // never read the slot of a NULL
-		}
+		ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at);
 		rows.y.push_back(y_values[y_idx]);
 		rows.flags.push_back(kTraining);
 		rows.n_training++;
@@ -420,52 +251,18 @@ void HipBlsAggUpdate(Vector inputs[], AggregateInputData &, idx_t input_count, V
 // Finalize (bls_aggregate.cpp:249-330): NULL with fewer than 2 buffered rows or a failed fit; ONE batched call per feature count
 void HipBlsAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipBlsBindData>();
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipBlsRowsState **)sdata.data;
-	struct FitBatch {
-		idx_t p = 0;
-		vector<idx_t> result_rows;
-		vector<BlsRowBuffer *> buffers;
-	};
-	std::map<idx_t, FitBatch> batches;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		if (!state.rows || state.rows->Rows() < 2 || state.rows->n_features == 0) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		auto &b = batches[state.rows->n_features];
-		b.p = state.rows->n_features;
-		b.result_rows.push_back(i + offset);
-		b.buffers.push_back(state.rows);
-	}
+	auto batches = CollectBatches<RowBatch>(state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.Rows() >= 2; });
 	auto &fields = StructVector::GetEntries(result);
 	for (auto &kv : batches) {
 		auto &b = kv.second;
-		const idx_t p = b.p, G = b.buffers.size(), rec_len = 3 * p + 6;
-		vector<int64_t> offsets {0};
-		int64_t n = 0;
-		for (auto *buf : b.buffers) {
-			n += (int64_t)buf->Rows();
-			offsets.push_back(n);
-		}
-		vector<double> y((size_t)n), cols((size_t)n * p), rec(G * rec_len);
-		int64_t at = 0;
-		for (auto *buf : b.buffers) {
-			const idx_t rows = buf->Rows();
-			for (idx_t r = 0; r < rows; r++) {
-				y[at + r] = buf->y[r];
-				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at + r] = buf->x[r * p + j];
-			}
-			at += (int64_t)rows;
-		}
-		vector<const double *> col_ptrs(p);
-		for (idx_t j = 0; j < p; j++) col_ptrs[j] = cols.data() + j * (size_t)n;
+		const idx_t p = b.p, G = b.Groups(), rec_len = 3 * p + 6;
+		const int64_t n = b.Stage(false, false); // (every buffered row trains)
+		vector<double> rec(G * rec_len);
 		AnofoxError err;
 		memset(&err, 0, sizeof err);
-		if (!anofox_hip_bls_fit_batch_host(nullptr, (int64_t)G, p, n, offsets.data(), y.data(), col_ptrs.data(), bind.opts.Batch(), rec.data(), nullptr, &err))
-			throw InvalidInputException("anofox_stats (HIP): %s", err.message[0] ? err.message : "the batched call failed");
+		if (!anofox_hip_bls_fit_batch_host(nullptr, (int64_t)G, p, n, b.offsets.data(), b.y.data(), b.col_ptrs.data(), bind.opts.Batch(), rec.data(), nullptr,
+		                                   &err))
+			ThrowAbi(err);
 		for (idx_t g = 0; g < G; g++) {
 			const idx_t r = b.result_rows[g];
 			const double *rc = &rec[g * rec_len];
@@ -477,11 +274,7 @@ void HipBlsAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data
 			Vector *lists[3] = {fields[0].get(), fields[7].get(), fields[8].get()};
 			for (int l = 0; l < 3; l++) {
 				Vector &lv = *lists[l];
-				const idx_t lo = ListVector::GetListSize(lv);
-				ListVector::Reserve(lv, lo + p);
-				ListVector::SetListSize(lv, lo + p);
-				ListVector::GetData(lv)[r].offset = lo;
-				ListVector::GetData(lv)[r].length = p;
+				const idx_t lo = AppendListEntry(lv, r, p);
 				Vector &child = ListVector::GetEntry(lv);
 				for (idx_t j = 0; j < p; j++) {
 					if (l == 0) {
@@ -511,16 +304,6 @@ unique_ptr<FunctionData> HipBlsAggBind(ClientContext &context, AggregateFunction
 	return make_uniq<HipBlsBindData>(opts, false);
 }
 
-FunctionDescription Describe(const char *what, const string &example, vector<string> names, const vector<LogicalType> &types) {
-	FunctionDescription d;
-	d.description = what;
-	d.examples = {example};
-	d.categories = {"regression"};
-	d.parameter_names = std::move(names);
-	d.parameter_types = types;
-	return d;
-}
-
 template <bool NNLS>
 void RegisterFit(ExtensionLoader &loader, const char *name, const char *alias, const char *what) {
 	const vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
@@ -528,19 +311,14 @@ void RegisterFit(ExtensionLoader &loader, const char *name, const char *alias, c
 	auto fill = [&](const string &fname) {
 		AggregateFunctionSet set(fname);
 		for (auto *args : {&basic, &map_args})
-			set.AddFunction(AggregateFunction(fname, *args, GetHipBlsAggResultType(), AggregateFunction::StateSize<HipBlsRowsState>, HipBlsRowsInitialize,
-			                                  HipBlsAggUpdate, HipBlsRowsCombine, HipBlsAggFinalize, nullptr, HipBlsAggBind<NNLS>, HipBlsRowsDestroy));
+			set.AddFunction(AggregateFunction(fname, *args, GetHipBlsAggResultType(), AggregateFunction::StateSize<RowsState>, RowsInitialize,
+			                                  HipBlsAggUpdate, RowsCombine<false>, HipBlsAggFinalize, nullptr, HipBlsAggBind<NNLS>, RowsDestroy));
 		return set;
 	};
 	CreateAggregateFunctionInfo info(fill(name));
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'fit_intercept': true})", {"y", "x", "options"}, map_args));
-	loader.RegisterFunction(std::move(info));
-	CreateAggregateFunctionInfo alias_info(fill(alias));
-	alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	alias_info.alias_of = name;
-	loader.RegisterFunction(std::move(alias_info));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic, kCategories));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'fit_intercept': true})", {"y", "x", "options"}, map_args, kCategories));
+	RegisterWithAlias(loader, std::move(info), fill(alias));
 }
 
 } // namespace
@@ -561,9 +339,9 @@ void RegisterHipBlsFitPredictAggregateFunction(ExtensionLoader &loader) {
 	const vector<LogicalType> split_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR};
 	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
 	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<HipBlsRowsState>, HipBlsRowsInitialize,
-		                         HipBlsPredictAggUpdate, HipBlsRowsCombine, HipBlsPredictAggFinalize, nullptr,
-		                         split ? HipBlsPredictAggBind<true> : HipBlsPredictAggBind<false>, HipBlsRowsDestroy);
+		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>, RowsInitialize,
+		                         HipBlsPredictAggUpdate, RowsCombine<false>, HipBlsPredictAggFinalize, nullptr,
+		                         split ? HipBlsPredictAggBind<true> : HipBlsPredictAggBind<false>, RowsDestroy);
 	};
 	auto fill = [&](const string &fname) {
 		AggregateFunctionSet set(fname);
@@ -574,17 +352,12 @@ void RegisterHipBlsFitPredictAggregateFunction(ExtensionLoader &loader) {
 		return set;
 	};
 	CreateAggregateFunctionInfo info(fill(name));
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
 	const string head = string(name) + "(y, x";
-	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic));
-	info.descriptions.push_back(Describe(what, head + ", {'lower_bound': 0.0})", {"y", "x", "options"}, map_args));
-	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args));
-	info.descriptions.push_back(Describe(what, head + ", split_col, {'upper_bound': 1.0})", {"y", "x", "split_col", "options"}, split_map_args));
-	loader.RegisterFunction(std::move(info));
-	CreateAggregateFunctionInfo alias_info(fill("bls_fit_predict_agg"));
-	alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	alias_info.alias_of = name;
-	loader.RegisterFunction(std::move(alias_info));
+	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", {'lower_bound': 0.0})", {"y", "x", "options"}, map_args, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", split_col, {'upper_bound': 1.0})", {"y", "x", "split_col", "options"}, split_map_args, kCategories));
+	RegisterWithAlias(loader, std::move(info), fill("bls_fit_predict_agg"));
 }
 
 } // namespace duckdb

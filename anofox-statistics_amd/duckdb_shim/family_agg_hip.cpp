@@ -36,15 +36,14 @@
 #include "anofox_stats_hip.h"
 #include "family_agg_hip.hpp"
 #include "hip_options.hpp"
+#include "row_glue.hpp"
 
 namespace duckdb {
 
 namespace {
 using namespace hip_glue;
 
-[[noreturn]] void ThrowAbi(const AnofoxError &err) {
-	throw InvalidInputException("anofox_stats (HIP): %s", err.message[0] ? err.message : "the batched call failed");
-}
+const vector<string> kCategories = {"regression", "prediction"};
 
 // ---- bind data of the predict aggregate and the window aggregate: the parsed options ----
 struct HipFamilyBindData : public FunctionData {
@@ -64,148 +63,18 @@ struct HipFamilyBindData : public FunctionData {
 	}
 };
 
-// the row buffer behind a DuckDB state: everything Update accepted, in arrival order
-struct RowBuffer {
-	idx_t n_features = 0;
-	vector<double> y;        // NaN where y was NULL
-	vector<double> x;        // row-major, n_features per row; a NULL list element is NaN
-	vector<double> w;        // weighted models only
-	vector<uint8_t> flags;   // per row: kYNull | kTraining
-	idx_t n_training = 0;
-	// the window aggregate: x of the last row Update saw (ols_fit_predict.cpp:29-31)
-	vector<double> current_x;
-	bool has_current_x = false;
-	idx_t Rows() const { return y.size(); }
-	void Append(const RowBuffer &o) {
-		y.insert(y.end(), o.y.begin(), o.y.end());
-		x.insert(x.end(), o.x.begin(), o.x.end());
-		w.insert(w.end(), o.w.begin(), o.w.end());
-		flags.insert(flags.end(), o.flags.begin(), o.flags.end());
-		n_training += o.n_training;
-	}
-};
-constexpr uint8_t kYNull = 1, kTraining = 2;
-
-// The DuckDB-side state is one pointer: Initialize has nothing to construct and an untouched state costs no allocation
-// (a window query makes a state per output row).
-struct HipRowsState {
-	RowBuffer *rows;
-};
-
-void HipRowsInitialize(const AggregateFunction &, data_ptr_t state_p) { reinterpret_cast<HipRowsState *>(state_p)->rows = nullptr; }
-
-void HipRowsDestroy(Vector &state_vector, AggregateInputData &, idx_t count) {
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRowsState **)sdata.data;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		delete state.rows;
-		state.rows = nullptr;
-	}
-}
-
-RowBuffer &Rows(HipRowsState &state, idx_t n_features, bool message_with_counts) {
-	if (!state.rows) {
-		state.rows = new RowBuffer();
-		state.rows->n_features = n_features; // the first row with a non-NULL x list fixes it (ols_predict_aggregate.cpp:182-187)
-	}
-	if (state.rows->n_features != n_features) {
-		if (message_with_counts)
-			throw InvalidInputException("Inconsistent feature count: expected %llu, got %llu", (unsigned long long)state.rows->n_features,
-			                            (unsigned long long)n_features);
-		throw InvalidInputException("Inconsistent feature count"); // the text of the ridge / wls files
-	}
-	return *state.rows;
-}
-
-bool IsSplitTraining(const string_t &split) { // 'train' / 'training', any case (ols_predict_aggregate.cpp:125-132)
-	string v = split.GetString();
-	for (auto &c : v) c = (char)std::tolower((unsigned char)c);
-	return v == "train" || v == "training";
-}
-
-// Combine of both row-buffering aggregates: an initialised source is appended to the target; an uninitialised target takes the
-// source's buffer (moved when the source may be consumed, copied under PRESERVE_INPUT — the window segment tree)
-template <bool WINDOW>
-void HipRowsCombine(Vector &source_vector, Vector &target_vector, AggregateInputData &aggr_input_data, idx_t count) {
-	UnifiedVectorFormat source_data, target_data;
-	source_vector.ToUnifiedFormat(count, source_data);
-	target_vector.ToUnifiedFormat(count, target_data);
-	auto sources = (HipRowsState **)source_data.data;
-	auto targets = (HipRowsState **)target_data.data;
-	const bool preserve = aggr_input_data.combine_type == AggregateCombineType::PRESERVE_INPUT;
-	for (idx_t i = 0; i < count; i++) {
-		auto &source = *sources[source_data.sel->get_index(i)];
-		auto &target = *targets[target_data.sel->get_index(i)];
-		if (!source.rows || &source == &target) continue;
-		if (!target.rows) {
-			if (preserve) {
-				target.rows = new RowBuffer(*source.rows);
-			} else {
-				target.rows = source.rows;
-				source.rows = nullptr;
-			}
-			continue;
-		}
-		if (source.rows->n_features != target.rows->n_features) {
-			if (WINDOW) throw InvalidInputException("Cannot combine states with different feature counts");
-			throw InvalidInputException("Cannot combine states with different feature counts: %llu vs %llu", (unsigned long long)source.rows->n_features,
-			                            (unsigned long long)target.rows->n_features);
-		}
-		target.rows->Append(*source.rows);
-		if (WINDOW && source.rows->has_current_x) { // the later state's row is the frame's last (ols_fit_predict.cpp:238-241)
-			target.rows->current_x = source.rows->current_x;
-			target.rows->has_current_x = true;
-		}
-	}
-}
-
-// ---- the states of one Finalize vector as one batch per feature count ----
-struct FamilyBatch {
-	idx_t p = 0;
-	vector<idx_t> result_rows;     // where each group of the batch goes
-	vector<RowBuffer *> buffers;
-	vector<int64_t> offsets {0};
-	vector<int64_t> train_counts;
-	vector<double> y, w, cols;     // cols: p columns of n rows, one after the other
+// ---- the states of one Finalize vector as one batch per feature count (RowBatch) through the family's ABI call ----
+struct FamilyBatch : RowBatch {
 	vector<double> core, pred;
 	// extra_row: the window aggregate appends its current x as a row that does not train
 	void Run(const AnofoxHipBatchOptions &options, bool weighted, bool extra_row) {
-		int64_t n = 0;
-		for (auto *b : buffers) {
-			n += (int64_t)b->Rows() + (extra_row ? 1 : 0);
-			offsets.push_back(n);
-			train_counts.push_back((int64_t)b->n_training);
-		}
-		y.resize((size_t)n);
-		cols.resize((size_t)n * p);
-		if (weighted) w.resize((size_t)n);
-		int64_t at = 0;
-		for (auto *b : buffers) {
-			const idx_t rows = b->Rows();
-			for (idx_t r = 0; r < rows; r++) {
-				const bool train = b->flags[r] & kTraining;
-				y[at + r] = train ? b->y[r] : NAN; // the batch ABI's "does not train"
-				if (weighted) w[at + r] = train ? b->w[r] : 1.0;
-				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at + r] = b->x[r * p + j];
-			}
-			at += (int64_t)rows;
-			if (extra_row) {
-				y[at] = NAN;
-				if (weighted) w[at] = 1.0;
-				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at] = b->current_x[j];
-				at++;
-			}
-		}
-		vector<const double *> col_ptrs(p);
-		for (idx_t j = 0; j < p; j++) col_ptrs[j] = cols.data() + j * (size_t)n;
-		core.resize(buffers.size() * (p + 6));
+		const int64_t n = Stage(weighted, extra_row);
+		core.resize(Groups() * (p + 6));
 		pred.resize((size_t)n * 3);
 		AnofoxError err;
 		memset(&err, 0, sizeof err);
-		if (!anofox_hip_fit_predict_batch_host(nullptr, (int64_t)buffers.size(), p, n, offsets.data(), y.data(), col_ptrs.data(),
-		                                       weighted ? w.data() : nullptr, train_counts.data(), options, core.data(), pred.data(), &err))
+		if (!anofox_hip_fit_predict_batch_host(nullptr, (int64_t)Groups(), p, n, offsets.data(), y.data(), col_ptrs.data(), weighted ? w.data() : nullptr,
+		                                       train_counts.data(), options, core.data(), pred.data(), &err))
 			ThrowAbi(err);
 	}
 	bool Failed(idx_t g) const { return core[g * (p + 6) + p + 5] != 0.0; }
@@ -214,16 +83,6 @@ struct FamilyBatch {
 // =====================================================================================================================
 // *_fit_predict_agg(y, x[, weights][, split_col][, options]) -> LIST(STRUCT(y, yhat, yhat_lower, yhat_upper, is_training))
 // =====================================================================================================================
-LogicalType GetHipPredictAggResultType() { // ols_predict_aggregate.cpp:93-104
-	child_list_t<LogicalType> row_children;
-	row_children.push_back(make_pair("y", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("yhat", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("yhat_lower", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("yhat_upper", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("is_training", LogicalType::BOOLEAN));
-	return LogicalType::LIST(LogicalType::STRUCT(std::move(row_children)));
-}
-
 // Update: every row with a non-NULL x list (and, weighted, a non-NULL weight) is kept for the output; it trains iff y is not
 // NULL (or the split column says so AND y is not NULL), no list element is NULL, the weight is positive, and — under
 // null_policy = 'drop_y_zero_x' — no feature is exactly 0 (ols_predict_aggregate.cpp:134-268, wls_predict_aggregate.cpp:160-240)
@@ -249,7 +108,7 @@ void HipPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data, i
 		split_values = UnifiedVectorFormat::GetData<string_t>(split_data);
 	}
 	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRowsState **)sdata.data;
+	auto states = (RowsState **)sdata.data;
 	const idx_t max_features = anofox_hip_max_features();
 	for (idx_t i = 0; i < count; i++) {
 		auto &state = *states[sdata.sel->get_index(i)];
@@ -262,23 +121,11 @@ void HipPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data, i
 			weight = w_values[w_idx];
 		}
 		const auto entry = x_list[x_idx];
-		if (entry.length > max_features)
-			throw InvalidInputException("anofox_stats fit_predict_agg (HIP): at most %llu features are supported, got %llu",
-			                            (unsigned long long)max_features, (unsigned long long)entry.length);
-		auto &rows = Rows(state, entry.length, MODEL == HipModel::OLS);
-		bool has_null_feature = false, has_zero = false;
+		CheckMaxFeatures("fit_predict_agg", entry.length, max_features);
+		auto &rows = RowsOf(state, entry.length, MODEL == HipModel::OLS); // bare: the text of the ridge / wls files
 		const size_t at = rows.x.size();
 		rows.x.resize(at + entry.length);
-		for (idx_t j = 0; j < entry.length; j++) {
-			const idx_t pos = entry.offset + j;
-			if (x_child_validity.RowIsValid(pos)) {
-				rows.x[at + j] = x_child_data[pos];
-				has_zero = has_zero || x_child_data[pos] == 0.0;
-			} else {
-				rows.x[at + j] = NAN; // never read the slot of a NULL (upstream issue #95)
-				has_null_feature = true;
-			}
-		}
+		const ListRowFlags x_flags = ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at);
 		auto y_idx = y_data.sel->get_index(i);
 		const bool y_valid = y_data.validity.RowIsValid(y_idx);
 		bool training = y_valid;
@@ -290,8 +137,8 @@ void HipPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data, i
 		                                                    // fails the fit there — here it does not train)
 		// a NULL feature: the OLS file clears the flag (ols_predict_aggregate.cpp:236-239); the ridge / wls files keep it — the row
 		// is handed to the fit, whose row filter drops it — and so does the is_training column of their output
-		if (has_null_feature && MODEL == HipModel::OLS) training = false;
-		if (training && bind.opts.drop_y_zero_x && has_zero) training = false;
+		if (x_flags.has_null && MODEL == HipModel::OLS) training = false;
+		if (training && bind.opts.drop_y_zero_x && x_flags.has_zero) training = false;
 		rows.y.push_back(y_valid ? y_values[y_idx] : NAN);
 		if (kWeighted) rows.w.push_back(weight);
 		rows.flags.push_back((uint8_t)((y_valid ? 0 : kYNull) | (training ? kTraining : 0)));
@@ -302,54 +149,15 @@ void HipPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data, i
 void HipPredictAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipFamilyBindData>();
 	const bool weighted = bind.model == HipModel::WLS;
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRowsState **)sdata.data;
-	std::map<idx_t, FamilyBatch> batches;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		// fewer than 2 training rows -> NULL (ols_predict_aggregate.cpp:343-346); an empty x list cannot be fitted (the FFI refuses it)
-		if (!state.rows || state.rows->n_training < 2 || state.rows->n_features == 0) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		auto &b = batches[state.rows->n_features];
-		b.p = state.rows->n_features;
-		b.result_rows.push_back(i + offset);
-		b.buffers.push_back(state.rows);
-	}
+	// fewer than 2 training rows -> NULL (ols_predict_aggregate.cpp:343-346)
+	auto batches = CollectBatches<FamilyBatch>(state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.n_training >= 2; });
 	const auto options = bind.Batch();
 	for (auto &kv : batches) kv.second.Run(options, weighted, false);
-
-	auto list_data = ListVector::GetData(result);
 	for (auto &kv : batches) {
 		auto &b = kv.second;
-		for (idx_t g = 0; g < b.buffers.size(); g++) {
-			const idx_t r = b.result_rows[g];
-			if (b.Failed(g)) { // the fit failed -> NULL (ols_predict_aggregate.cpp:366-369)
-				FlatVector::SetNull(result, r, true);
-				continue;
-			}
-			const RowBuffer &rows = *b.buffers[g];
-			const idx_t n_rows = rows.Rows();
-			const idx_t list_offset = ListVector::GetListSize(result);
-			ListVector::Reserve(result, list_offset + n_rows);
-			ListVector::SetListSize(result, list_offset + n_rows);
-			list_data[r].offset = list_offset;
-			list_data[r].length = n_rows;
-			auto &fields = StructVector::GetEntries(ListVector::GetEntry(result)); // [y, yhat, yhat_lower, yhat_upper, is_training]
-			const double *pred = &b.pred[(size_t)b.offsets[g] * 3];
-			for (idx_t row = 0; row < n_rows; row++) {
-				const idx_t at = list_offset + row;
-				if (rows.flags[row] & kYNull) FlatVector::SetNull(*fields[0], at, true);
-				else FlatVector::GetData<double>(*fields[0])[at] = rows.y[row];
-				if (isfinite(pred[row * 3])) { // :404-413: a non-finite prediction is three NULLs
-					for (idx_t k = 0; k < 3; k++) FlatVector::GetData<double>(*fields[1 + k])[at] = pred[row * 3 + k];
-				} else {
-					for (idx_t k = 0; k < 3; k++) FlatVector::SetNull(*fields[1 + k], at, true);
-				}
-				FlatVector::GetData<bool>(*fields[4])[at] = (rows.flags[row] & kTraining) != 0;
-			}
+		for (idx_t g = 0; g < b.Groups(); g++) {
+			if (b.Failed(g)) FlatVector::SetNull(result, b.result_rows[g], true); // the fit failed -> NULL (ols_predict_aggregate.cpp:366-369)
+			else AppendPredictRows(result, b.result_rows[g], *b.buffers[g], &b.pred[(size_t)b.offsets[g] * 3]);
 		}
 	}
 	// (the reference's state.Reset() after a successful fit: Destroy frees the buffers here)
@@ -360,7 +168,7 @@ unique_ptr<FunctionData> HipPredictAggBind(ClientContext &context, AggregateFunc
 	HipFitOptions opts;
 	const idx_t opt_idx = (MODEL == HipModel::WLS ? 3 : 2) + (SPLIT ? 1 : 0); // ols_predict_aggregate.cpp:435 / :466
 	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable()) ParseHipFitOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts);
-	function.return_type = GetHipPredictAggResultType();
+	function.return_type = PredictAggResultType();
 	return make_uniq<HipFamilyBindData>(MODEL, opts, SPLIT);
 }
 
@@ -379,9 +187,9 @@ void RegisterHipPredictAggregate(ExtensionLoader &loader, const string &model_na
 		return v;
 	};
 	auto make = [&](const string &fname, const vector<LogicalType> &args, bool split) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<HipRowsState>, HipRowsInitialize,
-		                         HipPredictAggUpdate<MODEL>, HipRowsCombine<false>, HipPredictAggFinalize, nullptr,
-		                         split ? HipPredictAggBind<MODEL, true> : HipPredictAggBind<MODEL, false>, HipRowsDestroy);
+		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>, RowsInitialize,
+		                         HipPredictAggUpdate<MODEL>, RowsCombine<false, true>, HipPredictAggFinalize, nullptr,
+		                         split ? HipPredictAggBind<MODEL, true> : HipPredictAggBind<MODEL, false>, RowsDestroy);
 	};
 	const vector<LogicalType> map_args = with(basic, {LogicalType::ANY}), split_args = with(basic, {LogicalType::VARCHAR}),
 	                          split_map_args = with(basic, {LogicalType::VARCHAR, LogicalType::ANY});
@@ -394,16 +202,9 @@ void RegisterHipPredictAggregate(ExtensionLoader &loader, const string &model_na
 		return set;
 	};
 	CreateAggregateFunctionInfo info(fill(name));
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
 	const string head = name + "(y, x" + (kWeighted ? ", weights" : "");
 	auto describe = [&](const string &example, vector<string> names, const vector<LogicalType> &types) {
-		FunctionDescription d;
-		d.description = what;
-		d.examples = {example};
-		d.categories = {"regression", "prediction"};
-		d.parameter_names = std::move(names);
-		d.parameter_types = types;
-		info.descriptions.push_back(std::move(d));
+		info.descriptions.push_back(Describe(what, example, std::move(names), types, kCategories));
 	};
 	auto names_with = [&](std::initializer_list<const char *> more) {
 		vector<string> v = basic_names;
@@ -414,27 +215,14 @@ void RegisterHipPredictAggregate(ExtensionLoader &loader, const string &model_na
 	describe(head + ", {'null_policy': 'drop'})", names_with({"options"}), map_args);
 	describe(head + ", split_col)", names_with({"split_col"}), split_args);
 	describe(head + ", split_col, {'null_policy': 'drop'})", names_with({"split_col", "options"}), split_map_args);
-	loader.RegisterFunction(std::move(info));
 	// the short alias and the two deprecated names (ols_predict_aggregate.cpp:563-602)
-	for (const string &alias : {model_name + "_fit_predict_agg", model_name + "_predict_agg", "anofox_stats_" + model_name + "_predict_agg"}) {
-		CreateAggregateFunctionInfo alias_info(fill(alias));
-		alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-		alias_info.alias_of = name;
-		loader.RegisterFunction(std::move(alias_info));
-	}
+	RegisterWithAlias(loader, std::move(info), fill(model_name + "_fit_predict_agg"));
+	for (const string &alias : {model_name + "_predict_agg", "anofox_stats_" + model_name + "_predict_agg"}) RegisterAlias(loader, name, fill(alias));
 }
 
 // =====================================================================================================================
 // *_fit_predict(y, x[, weight][, options]) OVER (...) -> STRUCT(yhat, yhat_lower, yhat_upper)
 // =====================================================================================================================
-LogicalType GetHipFitPredictResultType() { // ols_fit_predict.cpp:84-90
-	child_list_t<LogicalType> children;
-	children.push_back(make_pair("yhat", LogicalType::DOUBLE));
-	children.push_back(make_pair("yhat_lower", LogicalType::DOUBLE));
-	children.push_back(make_pair("yhat_upper", LogicalType::DOUBLE));
-	return LogicalType::STRUCT(std::move(children));
-}
-
 // Update (ols_fit_predict.cpp:110-193): the frame's rows arrive one by one; the last one with a non-NULL x list is the row to
 // predict, every one with a non-NULL y (and weight) trains.  Only training rows are buffered.
 template <HipModel MODEL>
@@ -453,7 +241,7 @@ void HipFitPredictUpdate(Vector inputs[], AggregateInputData &aggr_input_data, i
 	auto x_child_data = FlatVector::GetData<double>(x_child);
 	auto &x_child_validity = FlatVector::Validity(x_child);
 	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRowsState **)sdata.data;
+	auto states = (RowsState **)sdata.data;
 	const idx_t max_features = anofox_hip_max_features();
 	for (idx_t i = 0; i < count; i++) {
 		auto &state = *states[sdata.sel->get_index(i)];
@@ -463,17 +251,11 @@ void HipFitPredictUpdate(Vector inputs[], AggregateInputData &aggr_input_data, i
 			continue;
 		}
 		const auto entry = x_list[x_idx];
-		if (entry.length > max_features)
-			throw InvalidInputException("anofox_stats fit_predict (HIP): at most %llu features are supported, got %llu", (unsigned long long)max_features,
-			                            (unsigned long long)entry.length);
-		auto &rows = Rows(state, entry.length, MODEL == HipModel::OLS);
+		CheckMaxFeatures("fit_predict", entry.length, max_features);
+		auto &rows = RowsOf(state, entry.length, MODEL == HipModel::OLS);
 		rows.current_x.resize(entry.length);
-		bool has_zero = false;
-		for (idx_t j = 0; j < entry.length; j++) { // (a NULL list element: NaN — the reference reads the slot as it is)
-			const idx_t pos = entry.offset + j;
-			rows.current_x[j] = x_child_validity.RowIsValid(pos) ? x_child_data[pos] : NAN;
-			has_zero = has_zero || rows.current_x[j] == 0.0;
-		}
+		// (a NULL list element: NaN — the reference reads the slot as it is)
+		const bool has_zero = ReadListRow(entry, x_child_data, x_child_validity, rows.current_x.data()).has_zero;
 		rows.has_current_x = true;
 		auto y_idx = y_data.sel->get_index(i);
 		bool training = y_data.validity.RowIsValid(y_idx);
@@ -498,32 +280,16 @@ void HipFitPredictUpdate(Vector inputs[], AggregateInputData &aggr_input_data, i
 void HipFitPredictFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipFamilyBindData>();
 	const bool weighted = bind.model == HipModel::WLS;
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRowsState **)sdata.data;
-	std::map<idx_t, FamilyBatch> batches;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		if (!state.rows || !state.rows->has_current_x || state.rows->n_features == 0) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		const idx_t min_obs = state.rows->n_features + (bind.opts.fit_intercept ? 1 : 0);
-		if (state.rows->n_training <= min_obs) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		auto &b = batches[state.rows->n_features];
-		b.p = state.rows->n_features;
-		b.result_rows.push_back(i + offset);
-		b.buffers.push_back(state.rows);
-	}
+	const idx_t intercept = bind.opts.fit_intercept ? 1 : 0;
+	auto batches = CollectBatches<FamilyBatch>(state_vector, result, count, offset, [&](const RowBuffer &rows) {
+		return rows.has_current_x && rows.n_training > rows.n_features + intercept;
+	});
 	const auto options = bind.Batch();
 	for (auto &kv : batches) kv.second.Run(options, weighted, true);
 	auto &fields = StructVector::GetEntries(result);
 	for (auto &kv : batches) {
 		auto &b = kv.second;
-		for (idx_t g = 0; g < b.buffers.size(); g++) {
+		for (idx_t g = 0; g < b.Groups(); g++) {
 			const idx_t r = b.result_rows[g];
 			if (b.Failed(g)) {
 				FlatVector::SetNull(result, r, true);
@@ -542,7 +308,7 @@ unique_ptr<FunctionData> HipFitPredictBind(ClientContext &context, AggregateFunc
 	HipFitOptions opts;
 	const idx_t opt_idx = MODEL == HipModel::WLS ? 3 : 2; // ols_fit_predict.cpp:333
 	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable()) ParseHipFitOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts);
-	function.return_type = GetHipFitPredictResultType();
+	function.return_type = FitPredictResultType();
 	return make_uniq<HipFamilyBindData>(MODEL, opts, false);
 }
 
@@ -563,33 +329,16 @@ void RegisterHipFitPredict(ExtensionLoader &loader, const string &model_name, co
 	auto fill = [&](const string &fname) {
 		AggregateFunctionSet set(fname);
 		for (auto *args : {&basic, &map_args})
-			set.AddFunction(AggregateFunction(fname, *args, GetHipFitPredictResultType(), AggregateFunction::StateSize<HipRowsState>, HipRowsInitialize,
-			                                  HipFitPredictUpdate<MODEL>, HipRowsCombine<true>, HipFitPredictFinalize, nullptr, HipFitPredictBind<MODEL>,
-			                                  HipRowsDestroy));
+			set.AddFunction(AggregateFunction(fname, *args, FitPredictResultType(), AggregateFunction::StateSize<RowsState>, RowsInitialize,
+			                                  HipFitPredictUpdate<MODEL>, RowsCombine<true>, HipFitPredictFinalize, nullptr, HipFitPredictBind<MODEL>,
+			                                  RowsDestroy));
 		return set;
 	};
 	CreateAggregateFunctionInfo info(fill(name));
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
 	const string head = name + "(y, x" + (kWeighted ? ", weight" : "");
-	FunctionDescription d1;
-	d1.description = what;
-	d1.examples = {head + ")"};
-	d1.categories = {"regression", "prediction"};
-	d1.parameter_names = basic_names;
-	d1.parameter_types = basic;
-	info.descriptions.push_back(std::move(d1));
-	FunctionDescription d2;
-	d2.description = what;
-	d2.examples = {head + ", {'null_policy': 'drop'})"};
-	d2.categories = {"regression", "prediction"};
-	d2.parameter_names = map_names;
-	d2.parameter_types = map_args;
-	info.descriptions.push_back(std::move(d2));
-	loader.RegisterFunction(std::move(info));
-	CreateAggregateFunctionInfo alias_info(fill(model_name + "_fit_predict"));
-	alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	alias_info.alias_of = name;
-	loader.RegisterFunction(std::move(alias_info));
+	info.descriptions.push_back(Describe(what, head + ")", basic_names, basic, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", {'null_policy': 'drop'})", map_names, map_args, kCategories));
+	RegisterWithAlias(loader, std::move(info), fill(model_name + "_fit_predict"));
 }
 
 // =====================================================================================================================
@@ -698,14 +447,11 @@ void HipVifFinalize(Vector &state_vector, AggregateInputData &, Vector &result, 
 			FlatVector::SetNull(result, i + offset, true);
 			continue;
 		}
-		if (state.cols->columns.size() > max_features)
-			throw InvalidInputException("anofox_stats vif_agg (HIP): at most %llu features are supported, got %llu", (unsigned long long)max_features,
-			                            (unsigned long long)state.cols->columns.size());
+		CheckMaxFeatures("vif_agg", state.cols->columns.size(), max_features);
 		auto &b = batches[state.cols->columns.size()];
 		b.result_rows.push_back(i + offset);
 		b.cols.push_back(state.cols);
 	}
-	auto list_data = ListVector::GetData(result);
 	for (auto &kv : batches) {
 		const idx_t p = kv.first;
 		auto &b = kv.second;
@@ -728,13 +474,7 @@ void HipVifFinalize(Vector &state_vector, AggregateInputData &, Vector &result, 
 				FlatVector::SetNull(result, r, true);
 				continue;
 			}
-			const idx_t list_offset = ListVector::GetListSize(result);
-			ListVector::Reserve(result, list_offset + p); // (the reference's SetListInResult omits this, vif_aggregate.cpp:132-141)
-			auto child = FlatVector::GetData<double>(ListVector::GetEntry(result));
-			for (idx_t j = 0; j < p; j++) child[list_offset + j] = vif[g * rec + j];
-			list_data[r].offset = list_offset;
-			list_data[r].length = p;
-			ListVector::SetListSize(result, list_offset + p);
+			AppendList(result, r, &vif[g * rec], p); // (reserved first: the reference's SetListInResult omits that, vif_aggregate.cpp:132-141)
 		}
 	}
 }
@@ -772,21 +512,11 @@ void RegisterHipVifAggregateFunction(ExtensionLoader &loader) {
 	AggregateFunctionSet func_set("anofox_stats_vif_agg");
 	func_set.AddFunction(make("anofox_stats_vif_agg"));
 	CreateAggregateFunctionInfo info(std::move(func_set));
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	FunctionDescription d1;
-	d1.description = "Aggregate version of VIF: computes Variance Inflation Factor for each feature from a column of feature vectors.";
-	d1.examples = {"anofox_stats_vif_agg(x)"};
-	d1.categories = {"regression-diagnostics"};
-	d1.parameter_names = {"x"};
-	d1.parameter_types = {LogicalType::LIST(LogicalType::DOUBLE)};
-	info.descriptions.push_back(std::move(d1));
-	loader.RegisterFunction(std::move(info));
+	info.descriptions.push_back(Describe("Aggregate version of VIF: computes Variance Inflation Factor for each feature from a column of feature vectors.",
+	                                     "anofox_stats_vif_agg(x)", {"x"}, {LogicalType::LIST(LogicalType::DOUBLE)}, {"regression-diagnostics"}));
 	AggregateFunctionSet alias_set("vif_agg");
 	alias_set.AddFunction(make("vif_agg"));
-	CreateAggregateFunctionInfo alias_info(std::move(alias_set));
-	alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	alias_info.alias_of = "anofox_stats_vif_agg";
-	loader.RegisterFunction(std::move(alias_info));
+	RegisterWithAlias(loader, std::move(info), std::move(alias_set));
 }
 
 } // namespace duckdb

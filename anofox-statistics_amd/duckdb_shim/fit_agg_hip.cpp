@@ -41,6 +41,7 @@
 #include "sharded_arena.hpp" // hash64: the routing hash of SURVEY.md 8(e)
 #include "fit_agg_hip.hpp"
 #include "hip_options.hpp"
+#include "row_glue.hpp" // AppendList, Describe, RegisterWithAlias, ReadListRow: this file's state is the arena's, not a row buffer
 
 #include <thread>
 
@@ -237,9 +238,7 @@ void HipAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data, idx_t in
 			throw InvalidInputException("Inconsistent feature count: expected %llu, got %llu", (unsigned long long)state.n_features,
 			                            (unsigned long long)entry.length);
 		if (entry.length == 0) continue; // an empty x list: the reference buffers the row and its fit then fails -> NULL
-		if (entry.length > max_features)
-			throw InvalidInputException("anofox_stats fit_agg (HIP): at most %llu features are supported, got %llu", (unsigned long long)max_features,
-			                            (unsigned long long)entry.length);
+		CheckMaxFeatures("fit_agg", entry.length, max_features);
 		if (state.shard < 0) state.shard = (int64_t)arenas.ShardOf(&state, entry.length); // routed once, at the first accepted row
 		if (!writer || cur_p != entry.length || cur_shard != (uint32_t)state.shard) {
 			cur_p = entry.length;
@@ -251,8 +250,7 @@ void HipAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data, idx_t in
 		}
 		if (state.slot < 0) state.slot = writer->NewSlot();
 		double *row = writer->Begin((uint32_t)state.slot, y_values[y_idx], entry.length, w);
-		for (idx_t j = 0; j < entry.length; j++) // a NULL list element becomes NaN: the fit's row filter drops the row (ols.rs:59-66)
-			row[j] = x_child_validity.RowIsValid(entry.offset + j) ? x_child_data[entry.offset + j] : NAN;
+		ReadListRow(entry, x_child_data, x_child_validity, row); // a NULL list element becomes NaN: the fit's row filter drops the row (ols.rs:59-66)
 	}
 }
 
@@ -322,17 +320,6 @@ void HipAggCombine(Vector &source_vector, Vector &target_vector, AggregateInputD
 	} catch (const std::runtime_error &e) {
 		throw InvalidInputException(string(e.what()));
 	}
-}
-
-void AppendList(Vector &list_vec, idx_t row, const double *src, idx_t n) {
-	auto entries = ListVector::GetData(list_vec);
-	auto offset = ListVector::GetListSize(list_vec);
-	ListVector::Reserve(list_vec, offset + n); // the reference's SetListInResult omits this (ols_aggregate.cpp:237-246)
-	auto child = FlatVector::GetData<double>(ListVector::GetEntry(list_vec));
-	for (idx_t k = 0; k < n; k++) child[offset + k] = src[k];
-	entries[row].offset = offset;
-	entries[row].length = n;
-	ListVector::SetListSize(list_vec, offset + n);
 }
 
 // Finalize: ols_aggregate.cpp:249-338.  One arena call per feature count of the vector (one, normally): it fits what
@@ -450,30 +437,14 @@ void RegisterHipAggregate(ExtensionLoader &loader, const char *name, const char 
 	func_set.AddFunction(make(name, basic_args)); // (y, x[, weight]) — defaults
 	func_set.AddFunction(make(name, map_args));   // (y, x[, weight], {'intercept': true, ...})
 	CreateAggregateFunctionInfo info(std::move(func_set));
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	FunctionDescription d1;
-	d1.description = what;
-	d1.examples = {string(name) + "(y, x" + (kWeighted ? ", w" : "") + ", " + example_opts + ")"};
-	d1.categories = {"regression"};
-	d1.parameter_names = map_names;
-	d1.parameter_types = map_args;
-	info.descriptions.push_back(std::move(d1));
-	FunctionDescription d2;
-	d2.description = what;
-	d2.examples = {string(name) + "(y, x" + (kWeighted ? ", w" : "") + ")"};
-	d2.categories = {"regression"};
-	d2.parameter_names = basic_names;
-	d2.parameter_types = basic_args;
-	info.descriptions.push_back(std::move(d2));
-	loader.RegisterFunction(std::move(info));
+	const string head = string(name) + "(y, x" + (kWeighted ? ", w" : "");
+	info.descriptions.push_back(Describe(what, head + ", " + example_opts + ")", map_names, map_args, {"regression"}));
+	info.descriptions.push_back(Describe(what, head + ")", basic_names, basic_args, {"regression"}));
 
 	AggregateFunctionSet alias_set(alias); // the short alias (ols_aggregate.cpp:415-425)
 	alias_set.AddFunction(make(alias, basic_args));
 	alias_set.AddFunction(make(alias, map_args));
-	CreateAggregateFunctionInfo alias_info(std::move(alias_set));
-	alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	alias_info.alias_of = name;
-	loader.RegisterFunction(std::move(alias_info));
+	RegisterWithAlias(loader, std::move(info), std::move(alias_set));
 }
 
 } // namespace

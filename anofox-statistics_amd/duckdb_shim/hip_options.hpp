@@ -1,5 +1,8 @@
-// hip_options.hpp — the options argument of the regression aggregates as the reference's parser reads it, shared by the
-// DuckDB glue files of this directory (fit_agg_hip.cpp, family_agg_hip.cpp, elasticnet_agg_hip.cpp).
+// hip_options.hpp — the options argument of the regression aggregates as the reference's parser reads it, shared by every
+// DuckDB glue file of this directory: the STRUCT / MAP walk, the value converters with the reference's error texts, and the
+// option sets more than one file reads (ols / ridge / wls: fit_agg_hip.cpp, family_agg_hip.cpp; the elastic net:
+// elasticnet_agg_hip.cpp, elasticnet_family_hip.cpp, and rls_family_hip.cpp for the keys it converts and ignores).
+// bls_family_hip.cpp and quantile_family_hip.cpp keep their own option sets and parse them with the same pieces.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -53,59 +56,88 @@ inline bool ExtractBool(const Value &v) {
 	}
 }
 
+inline string OptionString(const Value &v) { return Lower(v.type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(v) : v.ToString()); }
+
 template <class ENUM>
 ENUM ExtractEnum(const Value &v, const char *what, const char *valid, std::initializer_list<std::pair<const char *, ENUM>> table) {
-	const string s = Lower(v.type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(v) : v.ToString());
+	const string s = OptionString(v);
 	for (auto &e : table)
 		if (s == e.first) return e.second;
 	throw InvalidInputException("Invalid %s: '%s'. Valid values are %s", what, s.c_str(), valid);
 }
 
-inline void ApplyOption(const string &raw_key, const Value &v, HipFitOptions &o, bool &has_alpha, double &alpha, bool &has_lambda, double &lambda) {
-	if (v.IsNull()) return;
-	const string key = Lower(raw_key);
-	if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(v);
-	else if (key == "compute_inference" || key == "inference") o.compute_inference = ExtractBool(v);
-	else if (key == "confidence_level" || key == "confidence") o.confidence_level = v.GetValue<double>(); // no range check upstream
-	else if (key == "alpha") { has_alpha = true; alpha = v.GetValue<double>(); }
-	else if (key == "lambda") { has_lambda = true; lambda = v.GetValue<double>(); }
-	else if (key == "solver")
-		o.solver = ExtractEnum<AnofoxSolverType>(v, "solver", "'qr', 'svd', 'cholesky'",
-		                                         {{"qr", ANOFOX_SOLVER_QR}, {"svd", ANOFOX_SOLVER_SVD}, {"cholesky", ANOFOX_SOLVER_CHOLESKY}});
-	else if (key == "hc_type")
-		o.hc_type = ExtractEnum<AnofoxHcType>(v, "hc_type", "'none', 'hc0', 'hc1', 'hc2', 'hc3'",
-		                                      {{"none", ANOFOX_HC_NONE}, {"hc0", ANOFOX_HC_HC0}, {"hc1", ANOFOX_HC_HC1}, {"hc2", ANOFOX_HC_HC2}, {"hc3", ANOFOX_HC_HC3}});
-	else if (key == "lambda_scaling")
-		o.lambda_scaling = ExtractEnum<AnofoxLambdaScaling>(v, "lambda_scaling", "'raw', 'glmnet'",
-		                                                    {{"raw", ANOFOX_LAMBDA_SCALING_RAW}, {"glmnet", ANOFOX_LAMBDA_SCALING_GLMNET}});
-	else if (key == "null_policy") { // ExtractNullPolicy map_options_parser.cpp:80-93 (every aggregate validates it, the predict ones use it)
-		const string s = Lower(v.type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(v) : v.ToString());
-		if (s == "drop") o.drop_y_zero_x = false;
-		else if (s == "drop_y_zero_x") o.drop_y_zero_x = true;
-		else throw InvalidInputException("Invalid null_policy: '%s'. Valid values are 'drop', 'drop_y_zero_x'", s.c_str());
-	}
-	// every other key: ignored, as upstream (the legacy {'full_output': true} of the reference's examples must bind)
+inline AnofoxLambdaScaling ExtractLambdaScaling(const Value &v) {
+	return ExtractEnum<AnofoxLambdaScaling>(v, "lambda_scaling", "'raw', 'glmnet'", {{"raw", ANOFOX_LAMBDA_SCALING_RAW}, {"glmnet", ANOFOX_LAMBDA_SCALING_GLMNET}});
 }
 
-inline void ParseHipFitOptions(const Value &v, HipFitOptions &o) {
-	if (v.IsNull()) return;
-	bool has_alpha = false, has_lambda = false;
-	double alpha = 0.0, lambda = 0.0;
+inline uint32_t ExtractUInteger(const Value &v) { // max_iterations: the reference's cast to UINTEGER
+	const double d = v.GetValue<double>();
+	if (!(d >= 0.0 && d <= 4294967295.0)) throw InvalidInputException("Value %s is out of range for UINTEGER", v.ToString().c_str());
+	return (uint32_t)d;
+}
+
+// null_policy (ExtractNullPolicy map_options_parser.cpp:80-93): true for 'drop_y_zero_x', false for 'drop'; every aggregate
+// validates it, the predict ones use it
+inline bool ExtractNullPolicy(const Value &v) {
+	const string s = OptionString(v);
+	if (s != "drop" && s != "drop_y_zero_x") throw InvalidInputException("Invalid null_policy: '%s'. Valid values are 'drop', 'drop_y_zero_x'", s.c_str());
+	return s == "drop_y_zero_x";
+}
+
+// The entries of a STRUCT or MAP literal as visit(lower-cased key, value), in the literal's order (VisitOptionEntries
+// map_options_parser.cpp:343-373).  A NULL value is handed on: most keys ignore it, the quantile path's `tau` does not.
+template <class F>
+void VisitOptionEntries(const Value &v, F &&visit) {
 	if (v.type().id() == LogicalTypeId::STRUCT) {
 		auto &kids = StructValue::GetChildren(v);
-		for (idx_t i = 0; i < kids.size(); i++) ApplyOption(StructType::GetChildName(v.type(), i), kids[i], o, has_alpha, alpha, has_lambda, lambda);
+		for (idx_t i = 0; i < kids.size(); i++) visit(Lower(StructType::GetChildName(v.type(), i)), kids[i]);
 	} else if (v.type().id() == LogicalTypeId::MAP) {
 		for (auto &entry : MapValue::GetChildren(v)) { // a list of {key, value} structs
 			auto &kv = StructValue::GetChildren(entry);
 			if (kv.size() != 2 || kv[0].IsNull()) continue;
-			ApplyOption(kv[0].type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(kv[0]) : kv[0].ToString(), kv[1], o, has_alpha, alpha,
-			            has_lambda, lambda);
+			visit(OptionString(kv[0]), kv[1]);
 		}
 	} else {
 		throw InvalidInputException("Options must be a MAP or STRUCT, got %s", v.type().ToString().c_str());
 	}
-	if (has_alpha) o.alpha = alpha; // alpha wins over lambda
-	else if (has_lambda) o.alpha = lambda;
+}
+
+// `alpha` and its alias `lambda`: alpha wins wherever both stand in the literal (GetRegularizationStrength
+// map_options_parser.hpp:265-270)
+struct AlphaOrLambda {
+	bool has_alpha = false, has_lambda = false;
+	double alpha = 0.0, lambda = 0.0;
+	bool Read(const string &key, const Value &v) {
+		if (key == "alpha") { has_alpha = true; alpha = v.GetValue<double>(); }
+		else if (key == "lambda") { has_lambda = true; lambda = v.GetValue<double>(); }
+		else return false;
+		return true;
+	}
+	void Store(double &strength, bool use_lambda = true) const {
+		if (has_alpha) strength = alpha;
+		else if (has_lambda && use_lambda) strength = lambda;
+	}
+};
+
+inline void ParseHipFitOptions(const Value &v, HipFitOptions &o) {
+	if (v.IsNull()) return;
+	AlphaOrLambda strength;
+	VisitOptionEntries(v, [&](const string &key, const Value &val) {
+		if (val.IsNull() || strength.Read(key, val)) return;
+		if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(val);
+		else if (key == "compute_inference" || key == "inference") o.compute_inference = ExtractBool(val);
+		else if (key == "confidence_level" || key == "confidence") o.confidence_level = val.GetValue<double>(); // no range check upstream
+		else if (key == "solver")
+			o.solver = ExtractEnum<AnofoxSolverType>(val, "solver", "'qr', 'svd', 'cholesky'",
+			                                         {{"qr", ANOFOX_SOLVER_QR}, {"svd", ANOFOX_SOLVER_SVD}, {"cholesky", ANOFOX_SOLVER_CHOLESKY}});
+		else if (key == "hc_type")
+			o.hc_type = ExtractEnum<AnofoxHcType>(val, "hc_type", "'none', 'hc0', 'hc1', 'hc2', 'hc3'",
+			                                      {{"none", ANOFOX_HC_NONE}, {"hc0", ANOFOX_HC_HC0}, {"hc1", ANOFOX_HC_HC1}, {"hc2", ANOFOX_HC_HC2}, {"hc3", ANOFOX_HC_HC3}});
+		else if (key == "lambda_scaling") o.lambda_scaling = ExtractLambdaScaling(val);
+		else if (key == "null_policy") o.drop_y_zero_x = ExtractNullPolicy(val);
+		// every other key: ignored, as upstream (the legacy {'full_output': true} of the reference's examples must bind)
+	});
+	strength.Store(o.alpha);
 }
 
 inline AnofoxHipBatchOptions MakeHipOptions(HipModel model, const HipFitOptions &o) {
@@ -148,46 +180,23 @@ struct HipElasticNetOptions {
 	}
 };
 
-inline void ApplyElasticNetOption(const string &raw_key, const Value &v, HipElasticNetOptions &o, bool &has_alpha, double &alpha, bool &has_lambda,
-                                  double &lambda) {
-	if (v.IsNull()) return;
-	const string key = Lower(raw_key);
+// one entry of the elastic net's options; key lower-cased (also what rls_family_hip.cpp converts and does not read)
+inline void ApplyElasticNetOption(const string &key, const Value &v, HipElasticNetOptions &o, AlphaOrLambda &strength) {
+	if (v.IsNull() || strength.Read(key, v)) return;
 	if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(v);
-	else if (key == "alpha") { has_alpha = true; alpha = v.GetValue<double>(); }
-	else if (key == "lambda") { has_lambda = true; lambda = v.GetValue<double>(); }
 	else if (key == "l1_ratio") o.l1_ratio = v.GetValue<double>();
-	else if (key == "max_iterations" || key == "max_iter") {
-		const double it = v.GetValue<double>();
-		if (!(it >= 0.0 && it <= 4294967295.0)) throw InvalidInputException("Value %s is out of range for UINTEGER", v.ToString().c_str());
-		o.max_iterations = (uint32_t)it;
-	} else if (key == "tolerance" || key == "tol") o.tolerance = v.GetValue<double>();
-	else if (key == "lambda_scaling")
-		o.lambda_scaling = ExtractEnum<AnofoxLambdaScaling>(v, "lambda_scaling", "'raw', 'glmnet'",
-		                                                    {{"raw", ANOFOX_LAMBDA_SCALING_RAW}, {"glmnet", ANOFOX_LAMBDA_SCALING_GLMNET}});
+	else if (key == "max_iterations" || key == "max_iter") o.max_iterations = ExtractUInteger(v);
+	else if (key == "tolerance" || key == "tol") o.tolerance = v.GetValue<double>();
+	else if (key == "lambda_scaling") o.lambda_scaling = ExtractLambdaScaling(v);
 	// every other key: ignored, as upstream
 }
 
 // STRUCT or MAP literal, keys case-insensitive, alpha wins over lambda (GetRegularizationStrength)
 inline void ParseHipElasticNetOptions(const Value &v, HipElasticNetOptions &o) {
 	if (v.IsNull()) return;
-	bool has_alpha = false, has_lambda = false;
-	double alpha = 0.0, lambda = 0.0;
-	if (v.type().id() == LogicalTypeId::STRUCT) {
-		auto &kids = StructValue::GetChildren(v);
-		for (idx_t i = 0; i < kids.size(); i++)
-			ApplyElasticNetOption(StructType::GetChildName(v.type(), i), kids[i], o, has_alpha, alpha, has_lambda, lambda);
-	} else if (v.type().id() == LogicalTypeId::MAP) {
-		for (auto &entry : MapValue::GetChildren(v)) {
-			auto &kv = StructValue::GetChildren(entry);
-			if (kv.size() != 2 || kv[0].IsNull()) continue;
-			ApplyElasticNetOption(kv[0].type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(kv[0]) : kv[0].ToString(), kv[1], o, has_alpha, alpha,
-			                      has_lambda, lambda);
-		}
-	} else {
-		throw InvalidInputException("Options must be a MAP or STRUCT, got %s", v.type().ToString().c_str());
-	}
-	if (has_alpha) o.alpha = alpha;
-	else if (has_lambda) o.alpha = lambda;
+	AlphaOrLambda strength;
+	VisitOptionEntries(v, [&](const string &key, const Value &val) { ApplyElasticNetOption(key, val, o, strength); });
+	strength.Store(o.alpha);
 }
 
 } // namespace hip_glue

@@ -45,11 +45,14 @@
 #include "anofox_stats_hip.h"
 #include "quantile_family_hip.hpp"
 #include "hip_options.hpp"
+#include "row_glue.hpp"
 
 namespace duckdb {
 
 namespace {
 using namespace hip_glue;
+
+const vector<string> kCategories = {"regression", "quantile"};
 
 // ---- options ----
 constexpr idx_t kMaxTaus = 64; // the library's grid limit (anofox_hip_quantile_fit_predict_path_batch_host)
@@ -79,50 +82,29 @@ struct HipQuantileOptions {
 	}
 };
 
-void ApplyQuantileOption(const string &raw_key, const Value &v, HipQuantileOptions &o) {
+void ApplyQuantileOption(const string &key, const Value &v, HipQuantileOptions &o) { // key lower-cased
 	if (v.IsNull()) return;
-	const string key = Lower(raw_key);
 	if (key == "tau") o.tau = v.GetValue<double>();
 	else if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(v);
-	else if (key == "max_iterations" || key == "max_iter") {
-		const double it = v.GetValue<double>();
-		if (!(it >= 0.0 && it <= 4294967295.0)) throw InvalidInputException("Value %s is out of range for UINTEGER", v.ToString().c_str());
-		o.max_iterations = (uint32_t)it;
-	} else if (key == "tolerance" || key == "tol") o.tolerance = v.GetValue<double>();
+	else if (key == "max_iterations" || key == "max_iter") o.max_iterations = ExtractUInteger(v);
+	else if (key == "tolerance" || key == "tol") o.tolerance = v.GetValue<double>();
 	// every other key: ignored, as in the reference ({'quantile': 0.5} of its example binds and changes nothing)
-}
-
-// a STRUCT or MAP literal as (key, value) pairs
-template <class F>
-void VisitHipQuantileOptions(const Value &v, F &&visit) {
-	if (v.type().id() == LogicalTypeId::STRUCT) {
-		auto &kids = StructValue::GetChildren(v);
-		for (idx_t i = 0; i < kids.size(); i++) visit(StructType::GetChildName(v.type(), i), kids[i]);
-	} else if (v.type().id() == LogicalTypeId::MAP) {
-		for (auto &entry : MapValue::GetChildren(v)) {
-			auto &kv = StructValue::GetChildren(entry);
-			if (kv.size() != 2 || kv[0].IsNull()) continue;
-			visit(kv[0].type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(kv[0]) : kv[0].ToString(), kv[1]);
-		}
-	} else {
-		throw InvalidInputException("Options must be a MAP or STRUCT, got %s", v.type().ToString().c_str());
-	}
 }
 
 void ParseHipQuantileOptions(const Value &v, HipQuantileOptions &o) {
 	if (v.IsNull()) return;
-	VisitHipQuantileOptions(v, [&](const string &key, const Value &val) { ApplyQuantileOption(key, val, o); });
+	VisitOptionEntries(v, [&](const string &key, const Value &val) { ApplyQuantileOption(key, val, o); });
 }
 
 // options.parse_quantile_path_options: `tau` is rejected whatever its value, `taus` must be a non-empty LIST; a NULL element
 // is kept as NaN and an out-of-range one as it is (the fit reports both at their position: status 1, NULL predictions)
 void ParseHipQuantilePathOptions(const Value &v, HipQuantileOptions &o) {
 	if (v.IsNull()) throw InvalidInputException("%s", kTausMissing);
-	VisitHipQuantileOptions(v, [&](const string &key, const Value &) {
-		if (Lower(key) == "tau") throw InvalidInputException("%s", kTauGiven);
+	VisitOptionEntries(v, [&](const string &key, const Value &) {
+		if (key == "tau") throw InvalidInputException("%s", kTauGiven);
 	});
-	VisitHipQuantileOptions(v, [&](const string &key, const Value &val) {
-		if (Lower(key) != "taus") {
+	VisitOptionEntries(v, [&](const string &key, const Value &val) {
+		if (key != "taus") {
 			ApplyQuantileOption(key, val, o);
 			return;
 		}
@@ -144,52 +126,6 @@ struct HipQuantileBindData : public FunctionData {
 		return opts == other.opts && use_split_col == other.use_split_col;
 	}
 };
-
-// ---- the row buffer behind a DuckDB state (the layout of rls_family_hip.cpp's) ----
-constexpr uint8_t kYNull = 1, kTraining = 2;
-struct QuantileRowBuffer {
-	idx_t n_features = 0;
-	vector<double> y;      // NaN where y was NULL
-	vector<double> x;      // row-major; a NULL list element is NaN
-	vector<uint8_t> flags; // kYNull | kTraining
-	idx_t n_training = 0;
-	vector<double> current_x; // the window aggregate: x of the last row Update saw
-	bool has_current_x = false;
-	idx_t Rows() const { return y.size(); }
-};
-struct HipQuantileRowsState {
-	QuantileRowBuffer *rows; // nullptr: never initialised (:37)
-};
-
-void HipQuantileRowsInitialize(const AggregateFunction &, data_ptr_t state_p) { reinterpret_cast<HipQuantileRowsState *>(state_p)->rows = nullptr; }
-
-void HipQuantileRowsDestroy(Vector &state_vector, AggregateInputData &, idx_t count) {
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipQuantileRowsState **)sdata.data;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		delete state.rows;
-		state.rows = nullptr;
-	}
-}
-
-QuantileRowBuffer &QuantileRows(HipQuantileRowsState &state, idx_t n_features) {
-	if (!state.rows) {
-		state.rows = new QuantileRowBuffer();
-		state.rows->n_features = n_features;
-	}
-	if (state.rows->n_features != n_features) // :162-164
-		throw InvalidInputException("Inconsistent feature count: expected %llu, got %llu", (unsigned long long)state.rows->n_features,
-		                            (unsigned long long)n_features);
-	return *state.rows;
-}
-
-bool IsQuantileSplitTraining(const string_t &split) { // QuantileIsSplitTraining :88-94: 'train' / 'training', any case
-	string v = split.GetString();
-	for (auto &c : v) c = (char)std::tolower((unsigned char)c);
-	return v == "train" || v == "training";
-}
 
 // Update (:115-211): a row with a NULL x list is skipped; every other row is kept for the output, a NULL list element as NaN.
 // It trains iff its y is not NULL — and, with a split column, its split value is not NULL and says train.  A NaN y that is
@@ -213,7 +149,7 @@ void HipQuantileRowsUpdate(Vector inputs[], AggregateInputData &aggr_input_data,
 		split_values = UnifiedVectorFormat::GetData<string_t>(split_data);
 	}
 	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipQuantileRowsState **)sdata.data;
+	auto states = (RowsState **)sdata.data;
 	for (idx_t i = 0; i < count; i++) {
 		auto &state = *states[sdata.sel->get_index(i)];
 		auto x_idx = x_data.sel->get_index(i);
@@ -222,13 +158,10 @@ void HipQuantileRowsUpdate(Vector inputs[], AggregateInputData &aggr_input_data,
 			continue;
 		}
 		const auto entry = x_list[x_idx];
-		auto &rows = QuantileRows(state, entry.length);
+		auto &rows = RowsOf(state, entry.length, true) /* :162-164 */;
 		const size_t at = rows.x.size();
 		rows.x.resize(at + entry.length);
-		for (idx_t j = 0; j < entry.length; j++) {
-			const idx_t pos = entry.offset + j;
-			rows.x[at + j] = x_child_validity.RowIsValid(pos) ? x_child_data[pos] : NAN; // never read the slot of a NULL (:169-173)
-		}
+		ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at); // never reads the slot of a NULL (:169-173)
 		if (WINDOW) {
 			rows.current_x.assign(rows.x.begin() + (ptrdiff_t)at, rows.x.end());
 			rows.has_current_x = true;
@@ -238,7 +171,7 @@ void HipQuantileRowsUpdate(Vector inputs[], AggregateInputData &aggr_input_data,
 		bool training = y_valid;
 		if (bind.use_split_col && split_values) {
 			auto s_idx = split_data.sel->get_index(i);
-			training = split_data.validity.RowIsValid(s_idx) && IsQuantileSplitTraining(split_values[s_idx]) && y_valid;
+			training = split_data.validity.RowIsValid(s_idx) && IsSplitTraining(split_values[s_idx]) && y_valid;
 		}
 		rows.y.push_back(y_valid ? y_values[y_idx] : NAN);
 		rows.flags.push_back((uint8_t)((y_valid ? 0 : kYNull) | (training ? kTraining : 0)));
@@ -246,102 +179,32 @@ void HipQuantileRowsUpdate(Vector inputs[], AggregateInputData &aggr_input_data,
 	}
 }
 
-// Combine (:213-257): the source's rows after the target's; ALLOW_DESTRUCTIVE moves, PRESERVE_INPUT copies
-template <bool WINDOW>
-void HipQuantileRowsCombine(Vector &source_vector, Vector &target_vector, AggregateInputData &aggr_input_data, idx_t count) {
-	UnifiedVectorFormat source_data, target_data;
-	source_vector.ToUnifiedFormat(count, source_data);
-	target_vector.ToUnifiedFormat(count, target_data);
-	auto sources = (HipQuantileRowsState **)source_data.data;
-	auto targets = (HipQuantileRowsState **)target_data.data;
-	const bool preserve = aggr_input_data.combine_type == AggregateCombineType::PRESERVE_INPUT;
-	for (idx_t i = 0; i < count; i++) {
-		auto &source = *sources[source_data.sel->get_index(i)];
-		auto &target = *targets[target_data.sel->get_index(i)];
-		if (!source.rows || &source == &target) continue;
-		if (!target.rows) {
-			if (preserve) {
-				target.rows = new QuantileRowBuffer(*source.rows);
-			} else {
-				target.rows = source.rows;
-				source.rows = nullptr;
-			}
-			continue;
-		}
-		if (source.rows->n_features != target.rows->n_features) throw InvalidInputException("Cannot combine states with different feature counts");
-		auto &t = *target.rows;
-		const auto &s = *source.rows;
-		t.y.insert(t.y.end(), s.y.begin(), s.y.end());
-		t.x.insert(t.x.end(), s.x.begin(), s.x.end());
-		t.flags.insert(t.flags.end(), s.flags.begin(), s.flags.end());
-		t.n_training += s.n_training;
-		if (WINDOW && s.has_current_x) { // the later state's row is the frame's last
-			t.current_x = s.current_x;
-			t.has_current_x = true;
-		}
-	}
-}
-
-// the states of one Finalize vector as one batch per feature count
-struct QuantileBatch {
-	idx_t p = 0;
-	vector<idx_t> result_rows;
-	vector<QuantileRowBuffer *> buffers;
-	vector<int64_t> offsets {0};
-	vector<int64_t> train_counts;
-	vector<double> y, cols, records, pred;
-	vector<const double *> col_ptrs;
-	// rows that do not train reach the ABI with y = NaN; extra_row: the window aggregate's current x as a last such row
-	int64_t Stage(bool extra_row) {
-		int64_t n = 0;
-		for (auto *b : buffers) {
-			n += (int64_t)b->Rows() + (extra_row ? 1 : 0);
-			offsets.push_back(n);
-			train_counts.push_back((int64_t)b->n_training);
-		}
-		y.resize((size_t)n);
-		cols.resize((size_t)n * p);
-		int64_t at = 0;
-		for (auto *b : buffers) {
-			const idx_t rows = b->Rows();
-			for (idx_t r = 0; r < rows; r++) {
-				y[at + r] = (b->flags[r] & kTraining) ? b->y[r] : NAN;
-				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at + r] = b->x[r * p + j];
-			}
-			at += (int64_t)rows;
-			if (extra_row) {
-				y[at] = NAN;
-				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at] = b->current_x[j];
-				at++;
-			}
-		}
-		col_ptrs.resize(p);
-		for (idx_t j = 0; j < p; j++) col_ptrs[j] = cols.data() + j * (size_t)n;
-		return n;
-	}
+// the states of one Finalize vector as one batch per feature count (RowBatch) through the family's two ABI calls; rows that
+// do not train reach the ABI with y = NaN
+struct QuantileBatch : RowBatch {
+	vector<double> records, pred;
 	// records [G x (p + 6)] in the regression layout, pred [n x 3] = {yhat, NaN, NaN}: the two NaN bounds are dropped by the callers
 	void Run(const HipQuantileOptions &opts, bool extra_row) {
-		const int64_t n = Stage(extra_row);
-		records.resize(buffers.size() * (p + 6));
+		const int64_t n = Stage(false, extra_row);
+		records.resize(Groups() * (p + 6));
 		pred.resize((size_t)n * 3);
 		AnofoxError err;
 		memset(&err, 0, sizeof err);
-		if (!anofox_hip_quantile_fit_predict_batch_host(nullptr, (int64_t)buffers.size(), p, n, offsets.data(), y.data(), col_ptrs.data(),
-		                                                train_counts.data(), opts.Batch(), records.data(), pred.data(), &err))
-			throw InvalidInputException("anofox_stats (HIP): %s", err.message[0] ? err.message : "the batched call failed");
+		if (!anofox_hip_quantile_fit_predict_batch_host(nullptr, (int64_t)Groups(), p, n, offsets.data(), y.data(), col_ptrs.data(), train_counts.data(),
+		                                                opts.Batch(), records.data(), pred.data(), &err))
+			ThrowAbi(err);
 	}
 	// records [G x T x (p + 6)] in the quantile layout, pred [n x T]
 	void RunPath(const HipQuantileOptions &opts) {
-		const int64_t n = Stage(false);
+		const int64_t n = Stage(false, false);
 		const size_t T = opts.taus.size();
-		records.resize(buffers.size() * T * (p + 6));
+		records.resize(Groups() * T * (p + 6));
 		pred.resize((size_t)n * T);
 		AnofoxError err;
 		memset(&err, 0, sizeof err);
-		if (!anofox_hip_quantile_fit_predict_path_batch_host(nullptr, (int64_t)buffers.size(), p, n, offsets.data(), y.data(), col_ptrs.data(),
-		                                                     train_counts.data(), opts.Batch(), opts.taus.data(), T, records.data(), nullptr,
-		                                                     pred.data(), &err))
-			throw InvalidInputException("anofox_stats (HIP): %s", err.message[0] ? err.message : "the batched call failed");
+		if (!anofox_hip_quantile_fit_predict_path_batch_host(nullptr, (int64_t)Groups(), p, n, offsets.data(), y.data(), col_ptrs.data(), train_counts.data(),
+		                                                     opts.Batch(), opts.taus.data(), T, records.data(), nullptr, pred.data(), &err))
+			ThrowAbi(err);
 	}
 	bool Failed(idx_t g, idx_t T = 1, idx_t t = 0) const { return records[(g * T + t) * (p + 6) + p + 5] != 0.0; }
 };
@@ -350,38 +213,8 @@ struct QuantileBatch {
 // than 2 training rows; WINDOW: no current row either)
 template <bool WINDOW>
 std::map<idx_t, QuantileBatch> CollectQuantileBatches(Vector &state_vector, Vector &result, idx_t count, idx_t offset) {
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipQuantileRowsState **)sdata.data;
-	std::map<idx_t, QuantileBatch> batches;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		if (!state.rows || state.rows->n_training < 2 || state.rows->n_features == 0 || (WINDOW && !state.rows->has_current_x)) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		auto &b = batches[state.rows->n_features];
-		b.p = state.rows->n_features;
-		b.result_rows.push_back(i + offset);
-		b.buffers.push_back(state.rows);
-	}
-	return batches;
-}
-
-// a LIST entry of `length` STRUCT rows at the end of the result's child, reserved before it is written
-idx_t AppendQuantileListEntry(Vector &result, idx_t row, idx_t length) {
-	const idx_t list_offset = ListVector::GetListSize(result);
-	ListVector::Reserve(result, list_offset + length);
-	ListVector::SetListSize(result, list_offset + length);
-	auto list_data = ListVector::GetData(result);
-	list_data[row].offset = list_offset;
-	list_data[row].length = length;
-	return list_offset;
-}
-
-void SetDoubleOrNull(Vector &field, idx_t at, double v, bool is_null) {
-	if (is_null) FlatVector::SetNull(field, at, true);
-	else FlatVector::GetData<double>(field)[at] = v;
+	return CollectBatches<QuantileBatch>(state_vector, result, count, offset,
+	                                     [](const RowBuffer &rows) { return rows.n_training >= 2 && (!WINDOW || rows.has_current_x); });
 }
 
 // =====================================================================================================================
@@ -409,9 +242,9 @@ void HipQuantilePredictAggFinalize(Vector &state_vector, AggregateInputData &agg
 				FlatVector::SetNull(result, r, true);
 				continue;
 			}
-			const QuantileRowBuffer &rows = *b.buffers[g];
+			const RowBuffer &rows = *b.buffers[g];
 			const idx_t n_rows = rows.Rows();
-			const idx_t list_offset = AppendQuantileListEntry(result, r, n_rows);
+			const idx_t list_offset = AppendListEntry(result, r, n_rows);
 			auto &fields = StructVector::GetEntries(ListVector::GetEntry(result));
 			const double *pred = &b.pred[(size_t)b.offsets[g] * 3];
 			for (idx_t row = 0; row < n_rows; row++) {
@@ -465,9 +298,9 @@ void HipQuantilePathAggFinalize(Vector &state_vector, AggregateInputData &aggr_i
 				FlatVector::SetNull(result, r, true);
 				continue;
 			}
-			const QuantileRowBuffer &rows = *b.buffers[g];
+			const RowBuffer &rows = *b.buffers[g];
 			const idx_t n_rows = rows.Rows();
-			const idx_t list_offset = AppendQuantileListEntry(result, r, n_rows * T);
+			const idx_t list_offset = AppendListEntry(result, r, n_rows * T);
 			auto &fields = StructVector::GetEntries(ListVector::GetEntry(result));
 			const double *pred = &b.pred[(size_t)b.offsets[g] * T];
 			for (idx_t row = 0; row < n_rows; row++) {
@@ -500,14 +333,6 @@ unique_ptr<FunctionData> HipQuantilePathAggBind(ClientContext &context, Aggregat
 // the result type of the *_fit_predict family, so the name can be swapped into an ols_fit_predict query; there is no interval:
 // both bounds are always NULL
 // =====================================================================================================================
-LogicalType GetHipQuantileFitPredictResultType() {
-	child_list_t<LogicalType> children;
-	children.push_back(make_pair("yhat", LogicalType::DOUBLE));
-	children.push_back(make_pair("yhat_lower", LogicalType::DOUBLE));
-	children.push_back(make_pair("yhat_upper", LogicalType::DOUBLE));
-	return LogicalType::STRUCT(std::move(children));
-}
-
 // Finalize: the frame's rows plus the current x as a last row that does not train, whose yhat is the result.  NULL: a state
 // never initialised, no current row, fewer than 2 training rows in the frame, a failed fit, a non-finite yhat.
 void HipQuantileFitPredictFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
@@ -534,28 +359,8 @@ void HipQuantileFitPredictFinalize(Vector &state_vector, AggregateInputData &agg
 unique_ptr<FunctionData> HipQuantileFitPredictBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
 	HipQuantileOptions opts;
 	if (arguments.size() > 2 && arguments[2]->IsFoldable()) ParseHipQuantileOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[2]), opts);
-	function.return_type = GetHipQuantileFitPredictResultType();
+	function.return_type = FitPredictResultType();
 	return make_uniq<HipQuantileBindData>(opts, false);
-}
-
-FunctionDescription Describe(const char *what, const string &example, vector<string> names, const vector<LogicalType> &types) {
-	FunctionDescription d;
-	d.description = what;
-	d.examples = {example};
-	d.categories = {"regression", "quantile"};
-	d.parameter_names = std::move(names);
-	d.parameter_types = types;
-	return d;
-}
-
-void RegisterWithAlias(ExtensionLoader &loader, CreateAggregateFunctionInfo info, AggregateFunctionSet alias_set) {
-	const string name = info.functions.name;
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	loader.RegisterFunction(std::move(info));
-	CreateAggregateFunctionInfo alias_info(std::move(alias_set));
-	alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	alias_info.alias_of = name;
-	loader.RegisterFunction(std::move(alias_info));
 }
 
 } // namespace
@@ -568,9 +373,9 @@ void RegisterHipQuantileFitPredictAggregateFunction(ExtensionLoader &loader) {
 	const vector<LogicalType> split_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR};
 	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
 	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<HipQuantileRowsState>,
-		                         HipQuantileRowsInitialize, HipQuantileRowsUpdate<false>, HipQuantileRowsCombine<false>, HipQuantilePredictAggFinalize,
-		                         nullptr, split ? HipQuantilePredictAggBind<true> : HipQuantilePredictAggBind<false>, HipQuantileRowsDestroy);
+		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>,
+		                         RowsInitialize, HipQuantileRowsUpdate<false>, RowsCombine<false>, HipQuantilePredictAggFinalize,
+		                         nullptr, split ? HipQuantilePredictAggBind<true> : HipQuantilePredictAggBind<false>, RowsDestroy);
 	};
 	auto fill = [&](const string &fname) {
 		AggregateFunctionSet set(fname);
@@ -582,10 +387,10 @@ void RegisterHipQuantileFitPredictAggregateFunction(ExtensionLoader &loader) {
 	};
 	CreateAggregateFunctionInfo info(fill(name));
 	const string head = string(name) + "(y, x";
-	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic));
-	info.descriptions.push_back(Describe(what, head + ", {'tau': 0.5})", {"y", "x", "options"}, map_args));
-	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args));
-	info.descriptions.push_back(Describe(what, head + ", split_col, {'tau': 0.5})", {"y", "x", "split_col", "options"}, split_map_args));
+	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", {'tau': 0.5})", {"y", "x", "options"}, map_args, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", split_col, {'tau': 0.5})", {"y", "x", "split_col", "options"}, split_map_args, kCategories));
 	RegisterWithAlias(loader, std::move(info), fill("quantile_fit_predict_agg"));
 }
 
@@ -595,9 +400,9 @@ void RegisterHipQuantilePathFitPredictAggregateFunction(ExtensionLoader &loader)
 	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
 	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
 	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<HipQuantileRowsState>,
-		                         HipQuantileRowsInitialize, HipQuantileRowsUpdate<false>, HipQuantileRowsCombine<false>, HipQuantilePathAggFinalize,
-		                         nullptr, split ? HipQuantilePathAggBind<true> : HipQuantilePathAggBind<false>, HipQuantileRowsDestroy);
+		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>,
+		                         RowsInitialize, HipQuantileRowsUpdate<false>, RowsCombine<false>, HipQuantilePathAggFinalize,
+		                         nullptr, split ? HipQuantilePathAggBind<true> : HipQuantilePathAggBind<false>, RowsDestroy);
 	};
 	auto fill = [&](const string &fname) {
 		AggregateFunctionSet set(fname);
@@ -607,8 +412,8 @@ void RegisterHipQuantilePathFitPredictAggregateFunction(ExtensionLoader &loader)
 	};
 	CreateAggregateFunctionInfo info(fill(name));
 	const string head = string(name) + "(y, x";
-	info.descriptions.push_back(Describe(what, head + ", {'taus': [0.1, 0.5, 0.9]})", {"y", "x", "options"}, map_args));
-	info.descriptions.push_back(Describe(what, head + ", split_col, {'taus': [0.1, 0.5, 0.9]})", {"y", "x", "split_col", "options"}, split_map_args));
+	info.descriptions.push_back(Describe(what, head + ", {'taus': [0.1, 0.5, 0.9]})", {"y", "x", "options"}, map_args, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", split_col, {'taus': [0.1, 0.5, 0.9]})", {"y", "x", "split_col", "options"}, split_map_args, kCategories));
 	RegisterWithAlias(loader, std::move(info), fill("quantile_path_fit_predict_agg"));
 }
 
@@ -620,14 +425,14 @@ void RegisterHipQuantileFitPredictFunction(ExtensionLoader &loader) {
 	auto fill = [&](const string &fname) {
 		AggregateFunctionSet set(fname);
 		for (auto *args : {&basic, &map_args})
-			set.AddFunction(AggregateFunction(fname, *args, GetHipQuantileFitPredictResultType(), AggregateFunction::StateSize<HipQuantileRowsState>,
-			                                  HipQuantileRowsInitialize, HipQuantileRowsUpdate<true>, HipQuantileRowsCombine<true>,
-			                                  HipQuantileFitPredictFinalize, nullptr, HipQuantileFitPredictBind, HipQuantileRowsDestroy));
+			set.AddFunction(AggregateFunction(fname, *args, FitPredictResultType(), AggregateFunction::StateSize<RowsState>,
+			                                  RowsInitialize, HipQuantileRowsUpdate<true>, RowsCombine<true>,
+			                                  HipQuantileFitPredictFinalize, nullptr, HipQuantileFitPredictBind, RowsDestroy));
 		return set;
 	};
 	CreateAggregateFunctionInfo info(fill(name));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'tau': 0.9})", {"y", "x", "options"}, map_args));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic, kCategories));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'tau': 0.9})", {"y", "x", "options"}, map_args, kCategories));
 	RegisterWithAlias(loader, std::move(info), fill("quantile_fit_predict"));
 }
 

@@ -33,11 +33,14 @@
 #include "anofox_stats_hip.h"
 #include "rls_family_hip.hpp"
 #include "hip_options.hpp"
+#include "row_glue.hpp"
 
 namespace duckdb {
 
 namespace {
 using namespace hip_glue;
+
+const vector<string> kCategories = {"regression", "prediction"};
 
 // ---- options ----
 struct HipRlsOptions {
@@ -60,41 +63,20 @@ struct HipRlsOptions {
 	}
 };
 
-void ApplyRlsOption(const string &raw_key, const Value &v, HipRlsOptions &o) {
-	if (v.IsNull()) return;
-	const string key = Lower(raw_key);
-	if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(v);
-	else if (key == "forgetting_factor") o.forgetting_factor = v.GetValue<double>();
-	else if (key == "initial_p_diagonal" || key == "p_diagonal") o.initial_p_diagonal = v.GetValue<double>();
-	else if (key == "confidence_level" || key == "confidence") o.confidence_level = v.GetValue<double>();
-	else if (key == "compute_inference" || key == "inference") (void)ExtractBool(v);
-	else if (key == "null_policy") {
-		const string s = Lower(v.type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(v) : v.ToString());
-		if (s == "drop") o.drop_y_zero_x = false;
-		else if (s == "drop_y_zero_x") o.drop_y_zero_x = true;
-		else throw InvalidInputException("Invalid null_policy: '%s'. Valid values are 'drop', 'drop_y_zero_x'", s.c_str());
-	} else { // parsed by the shared parser, not read by RLS: only its conversion errors matter
-		HipElasticNetOptions ignored;
-		bool has_alpha = false, has_lambda = false;
-		double alpha = 0.0, lambda = 0.0;
-		ApplyElasticNetOption(raw_key, v, ignored, has_alpha, alpha, has_lambda, lambda);
-	}
-}
-
 void ParseHipRlsOptions(const Value &v, HipRlsOptions &o) {
 	if (v.IsNull()) return;
-	if (v.type().id() == LogicalTypeId::STRUCT) {
-		auto &kids = StructValue::GetChildren(v);
-		for (idx_t i = 0; i < kids.size(); i++) ApplyRlsOption(StructType::GetChildName(v.type(), i), kids[i], o);
-	} else if (v.type().id() == LogicalTypeId::MAP) {
-		for (auto &entry : MapValue::GetChildren(v)) {
-			auto &kv = StructValue::GetChildren(entry);
-			if (kv.size() != 2 || kv[0].IsNull()) continue;
-			ApplyRlsOption(kv[0].type().id() == LogicalTypeId::VARCHAR ? StringValue::Get(kv[0]) : kv[0].ToString(), kv[1], o);
-		}
-	} else {
-		throw InvalidInputException("Options must be a MAP or STRUCT, got %s", v.type().ToString().c_str());
-	}
+	HipElasticNetOptions ignored;
+	AlphaOrLambda ignored_strength;
+	VisitOptionEntries(v, [&](const string &key, const Value &val) {
+		if (val.IsNull()) return;
+		if (key == "fit_intercept" || key == "intercept") o.fit_intercept = ExtractBool(val);
+		else if (key == "forgetting_factor") o.forgetting_factor = val.GetValue<double>();
+		else if (key == "initial_p_diagonal" || key == "p_diagonal") o.initial_p_diagonal = val.GetValue<double>();
+		else if (key == "confidence_level" || key == "confidence") o.confidence_level = val.GetValue<double>();
+		else if (key == "compute_inference" || key == "inference") (void)ExtractBool(val);
+		else if (key == "null_policy") o.drop_y_zero_x = ExtractNullPolicy(val);
+		else ApplyElasticNetOption(key, val, ignored, ignored_strength); // parsed by the shared parser, not read by RLS: only its conversion errors matter
+	});
 }
 
 struct HipRlsFamilyBindData : public FunctionData {
@@ -108,125 +90,18 @@ struct HipRlsFamilyBindData : public FunctionData {
 	}
 };
 
-// ---- the row buffer behind a DuckDB state (the layout of family_agg_hip.cpp's) ----
-constexpr uint8_t kYNull = 1, kTraining = 2;
-struct RlsRowBuffer {
-	idx_t n_features = 0;
-	vector<double> y;      // NaN where y was NULL
-	vector<double> x;      // row-major; a NULL list element is NaN
-	vector<uint8_t> flags; // kYNull | kTraining
-	idx_t n_training = 0;
-	vector<double> current_x; // the window aggregate: x of the last row Update saw
-	bool has_current_x = false;
-	idx_t Rows() const { return y.size(); }
-};
-struct HipRlsRowsState {
-	RlsRowBuffer *rows;
-};
-
-void HipRlsRowsInitialize(const AggregateFunction &, data_ptr_t state_p) { reinterpret_cast<HipRlsRowsState *>(state_p)->rows = nullptr; }
-
-void HipRlsRowsDestroy(Vector &state_vector, AggregateInputData &, idx_t count) {
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRlsRowsState **)sdata.data;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		delete state.rows;
-		state.rows = nullptr;
-	}
-}
-
-RlsRowBuffer &RlsRows(HipRlsRowsState &state, idx_t n_features) {
-	if (!state.rows) {
-		state.rows = new RlsRowBuffer();
-		state.rows->n_features = n_features;
-	}
-	if (state.rows->n_features != n_features) throw InvalidInputException("Inconsistent feature count"); // rls_predict_aggregate.cpp:190-192
-	return *state.rows;
-}
-
-bool IsRlsSplitTraining(const string_t &split) { // IsSplitTraining: 'train' / 'training', any case
-	string v = split.GetString();
-	for (auto &c : v) c = (char)std::tolower((unsigned char)c);
-	return v == "train" || v == "training";
-}
-
-template <bool WINDOW>
-void HipRlsRowsCombine(Vector &source_vector, Vector &target_vector, AggregateInputData &aggr_input_data, idx_t count) {
-	UnifiedVectorFormat source_data, target_data;
-	source_vector.ToUnifiedFormat(count, source_data);
-	target_vector.ToUnifiedFormat(count, target_data);
-	auto sources = (HipRlsRowsState **)source_data.data;
-	auto targets = (HipRlsRowsState **)target_data.data;
-	const bool preserve = aggr_input_data.combine_type == AggregateCombineType::PRESERVE_INPUT;
-	for (idx_t i = 0; i < count; i++) {
-		auto &source = *sources[source_data.sel->get_index(i)];
-		auto &target = *targets[target_data.sel->get_index(i)];
-		if (!source.rows || &source == &target) continue;
-		if (!target.rows) {
-			if (preserve) {
-				target.rows = new RlsRowBuffer(*source.rows);
-			} else {
-				target.rows = source.rows;
-				source.rows = nullptr;
-			}
-			continue;
-		}
-		if (source.rows->n_features != target.rows->n_features) throw InvalidInputException("Cannot combine states with different feature counts");
-		auto &t = *target.rows;
-		const auto &s = *source.rows;
-		t.y.insert(t.y.end(), s.y.begin(), s.y.end());
-		t.x.insert(t.x.end(), s.x.begin(), s.x.end());
-		t.flags.insert(t.flags.end(), s.flags.begin(), s.flags.end());
-		t.n_training += s.n_training;
-		if (WINDOW && s.has_current_x) { // the later state's row is the frame's last (rls_fit_predict.cpp:224-227)
-			t.current_x = s.current_x;
-			t.has_current_x = true;
-		}
-	}
-}
-
-// the states of one Finalize vector as one batch per feature count
-struct RlsBatch {
-	idx_t p = 0;
-	vector<idx_t> result_rows;
-	vector<RlsRowBuffer *> buffers;
-	vector<int64_t> offsets {0};
-	vector<int64_t> train_counts;
-	vector<double> y, cols, core, pred;
+// the states of one Finalize vector as one batch per feature count (RowBatch) through the fit-predict call
+struct RlsBatch : RowBatch {
+	vector<double> core, pred;
 	void Run(const HipRlsOptions &opts, bool extra_row) {
-		int64_t n = 0;
-		for (auto *b : buffers) {
-			n += (int64_t)b->Rows() + (extra_row ? 1 : 0);
-			offsets.push_back(n);
-			train_counts.push_back((int64_t)b->n_training);
-		}
-		y.resize((size_t)n);
-		cols.resize((size_t)n * p);
-		int64_t at = 0;
-		for (auto *b : buffers) {
-			const idx_t rows = b->Rows();
-			for (idx_t r = 0; r < rows; r++) {
-				y[at + r] = (b->flags[r] & kTraining) ? b->y[r] : NAN;
-				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at + r] = b->x[r * p + j];
-			}
-			at += (int64_t)rows;
-			if (extra_row) {
-				y[at] = NAN;
-				for (idx_t j = 0; j < p; j++) cols[j * (size_t)n + at] = b->current_x[j];
-				at++;
-			}
-		}
-		vector<const double *> col_ptrs(p);
-		for (idx_t j = 0; j < p; j++) col_ptrs[j] = cols.data() + j * (size_t)n;
-		core.resize(buffers.size() * (p + 6));
+		const int64_t n = Stage(false, extra_row);
+		core.resize(Groups() * (p + 6));
 		pred.resize((size_t)n * 3);
 		AnofoxError err;
 		memset(&err, 0, sizeof err);
-		if (!anofox_hip_rls_fit_predict_batch_host(nullptr, (int64_t)buffers.size(), p, n, offsets.data(), y.data(), col_ptrs.data(),
-		                                           train_counts.data(), opts.Batch(), opts.confidence_level, core.data(), pred.data(), &err))
-			throw InvalidInputException("anofox_stats (HIP): %s", err.message[0] ? err.message : "the batched call failed");
+		if (!anofox_hip_rls_fit_predict_batch_host(nullptr, (int64_t)Groups(), p, n, offsets.data(), y.data(), col_ptrs.data(), train_counts.data(),
+		                                           opts.Batch(), opts.confidence_level, core.data(), pred.data(), &err))
+			ThrowAbi(err);
 	}
 	bool Failed(idx_t g) const { return core[g * (p + 6) + p + 5] != 0.0; }
 };
@@ -234,16 +109,6 @@ struct RlsBatch {
 // =====================================================================================================================
 // anofox_stats_rls_fit_predict_agg(y, x[, split_col][, options]) -> LIST(STRUCT(y, yhat, yhat_lower, yhat_upper, is_training))
 // =====================================================================================================================
-LogicalType GetHipRlsPredictAggResultType() { // rls_predict_aggregate.cpp:94-106
-	child_list_t<LogicalType> row_children;
-	row_children.push_back(make_pair("y", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("yhat", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("yhat_lower", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("yhat_upper", LogicalType::DOUBLE));
-	row_children.push_back(make_pair("is_training", LogicalType::BOOLEAN));
-	return LogicalType::LIST(LogicalType::STRUCT(std::move(row_children)));
-}
-
 // Update (:150-245): every row with a non-NULL x list is kept for the output; it trains iff y is not NULL (and the split column
 // says train), and under null_policy = 'drop_y_zero_x' no feature is exactly 0.  A NULL list element is NaN: the row is handed
 // to the fit, whose row filter drops it.
@@ -264,31 +129,24 @@ void HipRlsPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data
 		split_values = UnifiedVectorFormat::GetData<string_t>(split_data);
 	}
 	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRlsRowsState **)sdata.data;
+	auto states = (RowsState **)sdata.data;
 	const idx_t max_features = anofox_hip_max_features();
 	for (idx_t i = 0; i < count; i++) {
 		auto &state = *states[sdata.sel->get_index(i)];
 		auto x_idx = x_data.sel->get_index(i);
 		if (!x_data.validity.RowIsValid(x_idx)) continue;
 		const auto entry = x_list[x_idx];
-		if (entry.length > max_features)
-			throw InvalidInputException("anofox_stats rls_fit_predict_agg (HIP): at most %llu features are supported, got %llu",
-			                            (unsigned long long)max_features, (unsigned long long)entry.length);
-		auto &rows = RlsRows(state, entry.length);
-		bool has_zero = false;
+		CheckMaxFeatures("rls_fit_predict_agg", entry.length, max_features);
+		auto &rows = RowsOf(state, entry.length, false);
 		const size_t at = rows.x.size();
 		rows.x.resize(at + entry.length);
-		for (idx_t j = 0; j < entry.length; j++) {
-			const idx_t pos = entry.offset + j;
-			rows.x[at + j] = x_child_validity.RowIsValid(pos) ? x_child_data[pos] : NAN; // never read the slot of a NULL
-			has_zero = has_zero || rows.x[at + j] == 0.0;
-		}
+		const bool has_zero = ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at).has_zero;
 		auto y_idx = y_data.sel->get_index(i);
 		const bool y_valid = y_data.validity.RowIsValid(y_idx);
 		bool training = y_valid;
 		if (bind.use_split_col && split_values) {
 			auto s_idx = split_data.sel->get_index(i);
-			training = split_data.validity.RowIsValid(s_idx) && IsRlsSplitTraining(split_values[s_idx]) && y_valid;
+			training = split_data.validity.RowIsValid(s_idx) && IsSplitTraining(split_values[s_idx]) && y_valid;
 		}
 		if (training && bind.opts.drop_y_zero_x && has_zero) training = false;
 		rows.y.push_back(y_valid ? y_values[y_idx] : NAN);
@@ -300,51 +158,13 @@ void HipRlsPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data
 // Finalize (:299-395): NULL with fewer than 2 training rows or a failed fit; otherwise every buffered row with its prediction
 void HipRlsPredictAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipRlsFamilyBindData>();
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRlsRowsState **)sdata.data;
-	std::map<idx_t, RlsBatch> batches;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		if (!state.rows || state.rows->n_training < 2 || state.rows->n_features == 0) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		auto &b = batches[state.rows->n_features];
-		b.p = state.rows->n_features;
-		b.result_rows.push_back(i + offset);
-		b.buffers.push_back(state.rows);
-	}
+	auto batches = CollectBatches<RlsBatch>(state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.n_training >= 2; });
 	for (auto &kv : batches) kv.second.Run(bind.opts, false);
-	auto list_data = ListVector::GetData(result);
 	for (auto &kv : batches) {
 		auto &b = kv.second;
-		for (idx_t g = 0; g < b.buffers.size(); g++) {
-			const idx_t r = b.result_rows[g];
-			if (b.Failed(g)) {
-				FlatVector::SetNull(result, r, true);
-				continue;
-			}
-			const RlsRowBuffer &rows = *b.buffers[g];
-			const idx_t n_rows = rows.Rows();
-			const idx_t list_offset = ListVector::GetListSize(result);
-			ListVector::Reserve(result, list_offset + n_rows);
-			ListVector::SetListSize(result, list_offset + n_rows);
-			list_data[r].offset = list_offset;
-			list_data[r].length = n_rows;
-			auto &fields = StructVector::GetEntries(ListVector::GetEntry(result));
-			const double *pred = &b.pred[(size_t)b.offsets[g] * 3];
-			for (idx_t row = 0; row < n_rows; row++) {
-				const idx_t at = list_offset + row;
-				if (rows.flags[row] & kYNull) FlatVector::SetNull(*fields[0], at, true);
-				else FlatVector::GetData<double>(*fields[0])[at] = rows.y[row];
-				if (isfinite(pred[row * 3])) {
-					for (idx_t k = 0; k < 3; k++) FlatVector::GetData<double>(*fields[1 + k])[at] = pred[row * 3 + k];
-				} else {
-					for (idx_t k = 0; k < 3; k++) FlatVector::SetNull(*fields[1 + k], at, true);
-				}
-				FlatVector::GetData<bool>(*fields[4])[at] = (rows.flags[row] & kTraining) != 0;
-			}
+		for (idx_t g = 0; g < b.Groups(); g++) {
+			if (b.Failed(g)) FlatVector::SetNull(result, b.result_rows[g], true);
+			else AppendPredictRows(result, b.result_rows[g], *b.buffers[g], &b.pred[(size_t)b.offsets[g] * 3]);
 		}
 	}
 }
@@ -355,21 +175,13 @@ unique_ptr<FunctionData> HipRlsPredictAggBind(ClientContext &context, AggregateF
 	const idx_t opt_idx = SPLIT ? 3 : 2;
 	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable())
 		ParseHipRlsOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts);
-	function.return_type = GetHipRlsPredictAggResultType();
+	function.return_type = PredictAggResultType();
 	return make_uniq<HipRlsFamilyBindData>(opts, SPLIT);
 }
 
 // =====================================================================================================================
 // anofox_stats_rls_fit_predict(y, x[, options]) OVER (...) -> STRUCT(yhat, yhat_lower, yhat_upper)
 // =====================================================================================================================
-LogicalType GetHipRlsFitPredictResultType() {
-	child_list_t<LogicalType> children;
-	children.push_back(make_pair("yhat", LogicalType::DOUBLE));
-	children.push_back(make_pair("yhat_lower", LogicalType::DOUBLE));
-	children.push_back(make_pair("yhat_upper", LogicalType::DOUBLE));
-	return LogicalType::STRUCT(std::move(children));
-}
-
 // Update (rls_fit_predict.cpp:110-180): the last row with a non-NULL x list is the row to predict; every row with a
 // non-NULL y trains (not under drop_y_zero_x when a feature is 0).  Only training rows are buffered.
 void HipRlsFitPredictUpdate(Vector inputs[], AggregateInputData &aggr_input_data, idx_t input_count, Vector &state_vector, idx_t count) {
@@ -384,7 +196,7 @@ void HipRlsFitPredictUpdate(Vector inputs[], AggregateInputData &aggr_input_data
 	auto x_child_data = FlatVector::GetData<double>(x_child);
 	auto &x_child_validity = FlatVector::Validity(x_child);
 	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRlsRowsState **)sdata.data;
+	auto states = (RowsState **)sdata.data;
 	const idx_t max_features = anofox_hip_max_features();
 	for (idx_t i = 0; i < count; i++) {
 		auto &state = *states[sdata.sel->get_index(i)];
@@ -394,17 +206,10 @@ void HipRlsFitPredictUpdate(Vector inputs[], AggregateInputData &aggr_input_data
 			continue;
 		}
 		const auto entry = x_list[x_idx];
-		if (entry.length > max_features)
-			throw InvalidInputException("anofox_stats rls_fit_predict (HIP): at most %llu features are supported, got %llu",
-			                            (unsigned long long)max_features, (unsigned long long)entry.length);
-		auto &rows = RlsRows(state, entry.length);
+		CheckMaxFeatures("rls_fit_predict", entry.length, max_features);
+		auto &rows = RowsOf(state, entry.length, false);
 		rows.current_x.resize(entry.length);
-		bool has_zero = false;
-		for (idx_t j = 0; j < entry.length; j++) {
-			const idx_t pos = entry.offset + j;
-			rows.current_x[j] = x_child_validity.RowIsValid(pos) ? x_child_data[pos] : NAN;
-			has_zero = has_zero || rows.current_x[j] == 0.0;
-		}
+		const bool has_zero = ReadListRow(entry, x_child_data, x_child_validity, rows.current_x.data()).has_zero;
 		rows.has_current_x = true;
 		auto y_idx = y_data.sel->get_index(i);
 		bool training = y_data.validity.RowIsValid(y_idx);
@@ -420,26 +225,10 @@ void HipRlsFitPredictUpdate(Vector inputs[], AggregateInputData &aggr_input_data
 // Finalize (:235-290): NULL without a current row or with at most p + [intercept] training rows, or when the fit fails
 void HipRlsFitPredictFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipRlsFamilyBindData>();
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRlsRowsState **)sdata.data;
-	std::map<idx_t, RlsBatch> batches;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		if (!state.rows || !state.rows->has_current_x || state.rows->n_features == 0) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		const idx_t min_obs = state.rows->n_features + (bind.opts.fit_intercept ? 1 : 0);
-		if (state.rows->n_training <= min_obs) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		auto &b = batches[state.rows->n_features];
-		b.p = state.rows->n_features;
-		b.result_rows.push_back(i + offset);
-		b.buffers.push_back(state.rows);
-	}
+	const idx_t intercept = bind.opts.fit_intercept ? 1 : 0;
+	auto batches = CollectBatches<RlsBatch>(state_vector, result, count, offset, [&](const RowBuffer &rows) {
+		return rows.has_current_x && rows.n_training > rows.n_features + intercept;
+	});
 	for (auto &kv : batches) kv.second.Run(bind.opts, true);
 	auto &fields = StructVector::GetEntries(result);
 	for (auto &kv : batches) {
@@ -459,7 +248,7 @@ void HipRlsFitPredictFinalize(Vector &state_vector, AggregateInputData &aggr_inp
 unique_ptr<FunctionData> HipRlsFitPredictBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
 	HipRlsOptions opts;
 	if (arguments.size() > 2 && arguments[2]->IsFoldable()) ParseHipRlsOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[2]), opts);
-	function.return_type = GetHipRlsFitPredictResultType();
+	function.return_type = FitPredictResultType();
 	return make_uniq<HipRlsFamilyBindData>(opts, false);
 }
 
@@ -492,84 +281,41 @@ void HipRlsFitAggUpdate(Vector inputs[], AggregateInputData &, idx_t input_count
 	auto x_child_data = FlatVector::GetData<double>(x_child);
 	auto &x_child_validity = FlatVector::Validity(x_child);
 	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRlsRowsState **)sdata.data;
+	auto states = (RowsState **)sdata.data;
 	const idx_t max_features = anofox_hip_max_features();
 	for (idx_t i = 0; i < count; i++) {
 		auto &state = *states[sdata.sel->get_index(i)];
 		auto x_idx = x_data.sel->get_index(i), y_idx = y_data.sel->get_index(i);
 		if (!x_data.validity.RowIsValid(x_idx) || !y_data.validity.RowIsValid(y_idx)) continue;
 		const auto entry = x_list[x_idx];
-		if (entry.length > max_features)
-			throw InvalidInputException("anofox_stats rls_fit_agg (HIP): at most %llu features are supported, got %llu",
-			                            (unsigned long long)max_features, (unsigned long long)entry.length);
-		auto &rows = RlsRows(state, entry.length);
-		for (idx_t j = 0; j < entry.length; j++) {
-			const idx_t pos = entry.offset + j;
-			rows.x.push_back(x_child_validity.RowIsValid(pos) ? x_child_data[pos] : NAN);
-		}
+		CheckMaxFeatures("rls_fit_agg", entry.length, max_features);
+		auto &rows = RowsOf(state, entry.length, false);
+		const size_t at = rows.x.size();
+		rows.x.resize(at + entry.length);
+		ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at);
 		rows.y.push_back(y_values[y_idx]);
 		rows.flags.push_back(kTraining);
 		rows.n_training++;
 	}
 }
 
-void AppendList(Vector &list_vec, idx_t row, const double *src, idx_t n) {
-	auto entries = ListVector::GetData(list_vec);
-	auto offset = ListVector::GetListSize(list_vec);
-	ListVector::Reserve(list_vec, offset + n);
-	auto child = FlatVector::GetData<double>(ListVector::GetEntry(list_vec));
-	for (idx_t k = 0; k < n; k++) child[offset + k] = src[k];
-	entries[row].offset = offset;
-	entries[row].length = n;
-	ListVector::SetListSize(list_vec, offset + n);
-}
-
 // Finalize: NULL with fewer than 2 rows or a failed fit; the vector's other states in ONE batched call per feature count
 void HipRlsFitAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipRlsFamilyBindData>();
-	UnifiedVectorFormat sdata;
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (HipRlsRowsState **)sdata.data;
-	struct Batch {
-		vector<idx_t> result_rows;
-		vector<RlsRowBuffer *> rows;
-	};
-	std::map<idx_t, Batch> batches;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		if (!state.rows || state.rows->Rows() < 2 || state.rows->n_features == 0) {
-			FlatVector::SetNull(result, i + offset, true);
-			continue;
-		}
-		auto &b = batches[state.rows->n_features];
-		b.result_rows.push_back(i + offset);
-		b.rows.push_back(state.rows);
-	}
+	auto batches = CollectBatches<RowBatch>(state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.Rows() >= 2; });
 	auto &entries = StructVector::GetEntries(result);
 	for (auto &kv : batches) {
 		const idx_t p = kv.first;
 		auto &b = kv.second;
-		vector<int64_t> offsets {0};
-		for (auto *r : b.rows) offsets.push_back(offsets.back() + (int64_t)r->Rows());
-		const size_t n = (size_t)offsets.back();
-		vector<double> y(n), cols(n * p);
-		for (idx_t g = 0; g < b.rows.size(); g++) {
-			const RlsRowBuffer &r = *b.rows[g];
-			for (idx_t row = 0; row < r.Rows(); row++) {
-				y[(size_t)offsets[g] + row] = r.y[row];
-				for (idx_t j = 0; j < p; j++) cols[j * n + (size_t)offsets[g] + row] = r.x[row * p + j];
-			}
-		}
-		vector<const double *> col_ptrs(p);
-		for (idx_t j = 0; j < p; j++) col_ptrs[j] = cols.data() + j * n;
+		const int64_t n = b.Stage(false, false); // (every buffered row trains)
 		const size_t rec = anofox_hip_core_record_len(p);
-		vector<double> core(b.rows.size() * rec);
+		vector<double> core(b.Groups() * rec);
 		AnofoxError err;
 		memset(&err, 0, sizeof err);
-		if (!anofox_hip_rls_fit_batch_host(nullptr, (int64_t)b.rows.size(), p, (int64_t)n, offsets.data(), y.data(), col_ptrs.data(), bind.opts.Batch(),
-		                                   core.data(), &err))
-			throw InvalidInputException("anofox_stats (HIP): %s", err.message[0] ? err.message : "the batched call failed");
-		for (idx_t g = 0; g < b.rows.size(); g++) {
+		if (!anofox_hip_rls_fit_batch_host(nullptr, (int64_t)b.Groups(), p, n, b.offsets.data(), b.y.data(), b.col_ptrs.data(), bind.opts.Batch(), core.data(),
+		                                   &err))
+			ThrowAbi(err);
+		for (idx_t g = 0; g < b.Groups(); g++) {
 			const idx_t r = b.result_rows[g];
 			const double *c = core.data() + g * rec;
 			if (c[p + 5] != 0.0) {
@@ -591,16 +337,6 @@ unique_ptr<FunctionData> HipRlsFitAggBind(ClientContext &context, AggregateFunct
 	return make_uniq<HipRlsFamilyBindData>(opts, false);
 }
 
-FunctionDescription Describe(const char *what, const string &example, vector<string> names, const vector<LogicalType> &types) {
-	FunctionDescription d;
-	d.description = what;
-	d.examples = {example};
-	d.categories = {"regression", "prediction"};
-	d.parameter_names = std::move(names);
-	d.parameter_types = types;
-	return d;
-}
-
 } // namespace
 
 void RegisterHipRlsAggregateFunction(ExtensionLoader &loader) {
@@ -611,20 +347,15 @@ void RegisterHipRlsAggregateFunction(ExtensionLoader &loader) {
 	auto fill = [&](const string &fname) {
 		AggregateFunctionSet set(fname);
 		for (auto *args : {&basic, &map_args})
-			set.AddFunction(AggregateFunction(fname, *args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<HipRlsRowsState>,
-			                                  HipRlsRowsInitialize, HipRlsFitAggUpdate, HipRlsRowsCombine<false>, HipRlsFitAggFinalize, nullptr,
-			                                  HipRlsFitAggBind, HipRlsRowsDestroy));
+			set.AddFunction(AggregateFunction(fname, *args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>,
+			                                  RowsInitialize, HipRlsFitAggUpdate, RowsCombine<false>, HipRlsFitAggFinalize, nullptr,
+			                                  HipRlsFitAggBind, RowsDestroy));
 		return set;
 	};
 	CreateAggregateFunctionInfo info(fill(name));
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'forgetting_factor': 0.99})", {"y", "x", "options"}, map_args));
-	loader.RegisterFunction(std::move(info));
-	CreateAggregateFunctionInfo alias_info(fill("rls_fit_agg"));
-	alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	alias_info.alias_of = name;
-	loader.RegisterFunction(std::move(alias_info));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic, kCategories));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'forgetting_factor': 0.99})", {"y", "x", "options"}, map_args, kCategories));
+	RegisterWithAlias(loader, std::move(info), fill("rls_fit_agg"));
 }
 
 void RegisterHipRlsFitPredictAggregateFunction(ExtensionLoader &loader) {
@@ -635,9 +366,9 @@ void RegisterHipRlsFitPredictAggregateFunction(ExtensionLoader &loader) {
 	const vector<LogicalType> split_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR};
 	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
 	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<HipRlsRowsState>, HipRlsRowsInitialize,
-		                         HipRlsPredictAggUpdate, HipRlsRowsCombine<false>, HipRlsPredictAggFinalize, nullptr,
-		                         split ? HipRlsPredictAggBind<true> : HipRlsPredictAggBind<false>, HipRlsRowsDestroy);
+		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>, RowsInitialize,
+		                         HipRlsPredictAggUpdate, RowsCombine<false>, HipRlsPredictAggFinalize, nullptr,
+		                         split ? HipRlsPredictAggBind<true> : HipRlsPredictAggBind<false>, RowsDestroy);
 	};
 	auto fill = [&](const string &fname) {
 		AggregateFunctionSet set(fname);
@@ -648,19 +379,13 @@ void RegisterHipRlsFitPredictAggregateFunction(ExtensionLoader &loader) {
 		return set;
 	};
 	CreateAggregateFunctionInfo info(fill(name));
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
 	const string head = string(name) + "(y, x";
-	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic));
-	info.descriptions.push_back(Describe(what, head + ", {'forgetting_factor': 0.99})", {"y", "x", "options"}, map_args));
-	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args));
-	info.descriptions.push_back(Describe(what, head + ", split_col, {'forgetting_factor': 0.99})", {"y", "x", "split_col", "options"}, split_map_args));
-	loader.RegisterFunction(std::move(info));
-	for (const char *alias : {"rls_fit_predict_agg", "rls_predict_agg", "anofox_stats_rls_predict_agg"}) {
-		CreateAggregateFunctionInfo alias_info(fill(alias));
-		alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-		alias_info.alias_of = name;
-		loader.RegisterFunction(std::move(alias_info));
-	}
+	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", {'forgetting_factor': 0.99})", {"y", "x", "options"}, map_args, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args, kCategories));
+	info.descriptions.push_back(Describe(what, head + ", split_col, {'forgetting_factor': 0.99})", {"y", "x", "split_col", "options"}, split_map_args, kCategories));
+	RegisterWithAlias(loader, std::move(info), fill("rls_fit_predict_agg"));
+	for (const char *alias : {"rls_predict_agg", "anofox_stats_rls_predict_agg"}) RegisterAlias(loader, name, fill(alias)); // the deprecated names
 }
 
 void RegisterHipRlsFitPredictFunction(ExtensionLoader &loader) {
@@ -671,20 +396,15 @@ void RegisterHipRlsFitPredictFunction(ExtensionLoader &loader) {
 	auto fill = [&](const string &fname) {
 		AggregateFunctionSet set(fname);
 		for (auto *args : {&basic, &map_args})
-			set.AddFunction(AggregateFunction(fname, *args, GetHipRlsFitPredictResultType(), AggregateFunction::StateSize<HipRlsRowsState>, HipRlsRowsInitialize,
-			                                  HipRlsFitPredictUpdate, HipRlsRowsCombine<true>, HipRlsFitPredictFinalize, nullptr, HipRlsFitPredictBind,
-			                                  HipRlsRowsDestroy));
+			set.AddFunction(AggregateFunction(fname, *args, FitPredictResultType(), AggregateFunction::StateSize<RowsState>, RowsInitialize,
+			                                  HipRlsFitPredictUpdate, RowsCombine<true>, HipRlsFitPredictFinalize, nullptr, HipRlsFitPredictBind,
+			                                  RowsDestroy));
 		return set;
 	};
 	CreateAggregateFunctionInfo info(fill(name));
-	info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'null_policy': 'drop'})", {"y", "x", "options"}, map_args));
-	loader.RegisterFunction(std::move(info));
-	CreateAggregateFunctionInfo alias_info(fill("rls_fit_predict"));
-	alias_info.on_conflict = OnCreateConflict::ALTER_ON_CONFLICT;
-	alias_info.alias_of = name;
-	loader.RegisterFunction(std::move(alias_info));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic, kCategories));
+	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'null_policy': 'drop'})", {"y", "x", "options"}, map_args, kCategories));
+	RegisterWithAlias(loader, std::move(info), fill("rls_fit_predict"));
 }
 
 } // namespace duckdb

@@ -263,6 +263,27 @@ def test_argument_errors_precede_device_use():
         pkg.elasticnet_fit([1.0, 2.0, 3.5], [[1.0, 2.0]])
 
 
+# ---- the DuckDB glue (duckdb_shim/elasticnet_agg_hip.cpp) through its test driver ----
+
+def test_glue_feature_count_errors_name_the_counts():
+    """elasticnet_fit_agg: one state given a 2-feature row and then a 3-feature row, and a 2-feature state combined into a
+    3-feature state — the texts of elasticnet_aggregate.cpp, with the counts.  Both are thrown before Finalize: no device."""
+    import ctypes as C
+    import_pkg()
+    lib = C.CDLL(os.path.join(ROOT, "anofox-statistics_amd", "duckdb_shim", "libanofox_elasticnet_glue_capi.so"))
+    lib.en_open.restype = C.c_void_p
+    lib.en_open.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
+    lib.en_close.argtypes = [C.c_void_p]
+    lib.en_feature_count_errors.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+    msg, update, combine = (C.create_string_buffer(512) for _ in range(3))
+    q = lib.en_open(b"elasticnet_fit_agg", None, 0, msg)
+    assert q, msg.value.decode()
+    lib.en_feature_count_errors(q, update, combine)
+    lib.en_close(q)
+    assert update.value.decode() == "Inconsistent feature count: expected 2, got 3"
+    assert combine.value.decode() == "Cannot combine states with different feature counts: 2 vs 3"
+
+
 # ---- the DuckDB glue compiles cleanly against the stand-in of DuckDB's headers ----
 
 def test_glue_compiles_warning_free():
@@ -270,3 +291,14 @@ def test_glue_compiles_warning_free():
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Werror",
                            "-I", os.path.join(ROOT, "tests", "tools", "duckdb_stub"), "-I", os.path.join(ROOT, "include"), "-I", shim,
                            os.path.join(shim, "elasticnet_agg_hip.cpp")])
+
+
+def test_row_glue_header_stands_alone(tmp_path):
+    """duckdb_shim/row_glue.hpp included alone: it leans on nothing a particular .cpp included before it."""
+    shim = os.path.join(ROOT, "anofox-statistics_amd", "duckdb_shim")
+    src = tmp_path / "row_glue_alone.cpp"
+    src.write_text('#include "row_glue.hpp"\n')
+    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Werror",
+                        "-I", os.path.join(ROOT, "tests", "tools", "duckdb_stub"), "-I", os.path.join(ROOT, "include"), "-I", shim, str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr

@@ -198,6 +198,22 @@ def test_glue_bad_options_fail_at_bind(fn):
         assert text in msg.value.decode(), msg.value.decode()
 
 
+@pytest.mark.parametrize("fn", ["elasticnet_fit_predict_agg", "elasticnet_fit_predict"])
+def test_glue_feature_count_errors_carry_no_counts(fn):
+    """One state given a 2-feature row and then a 3-feature row, and a 2-feature state combined into a 3-feature state: the
+    bare texts of elasticnet_predict_aggregate.cpp / elasticnet_fit_predict.cpp.  Both are thrown before Finalize: no device."""
+    import ctypes as C
+    lib = _glue()
+    lib.enf_feature_count_errors.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+    msg, update, combine = (C.create_string_buffer(512) for _ in range(3))
+    q = lib.enf_open(fn.encode(), None, 0, 0, msg)
+    assert q, msg.value.decode()
+    lib.enf_feature_count_errors(q, update, combine)
+    lib.enf_close(q)
+    assert update.value.decode() == "Inconsistent feature count"
+    assert combine.value.decode() == "Cannot combine states with different feature counts"
+
+
 def test_glue_compiles_warning_free(tmp_path):
     import subprocess
     shim = ROOT / "anofox-statistics_amd" / "duckdb_shim"

@@ -319,4 +319,14 @@ BLS_API int64_t blsp_group_by(void *q, size_t n, size_t p, const uint32_t *key, 
 	}
 }
 
+// the texts of the two feature-count errors at their smallest (FamilyQuery::FeatureCountErrors): update_msg, combine_msg [512]
+BLS_API void blsp_feature_count_errors(void *q, char *update_msg, char *combine_msg) {
+	std::string update, combine;
+	static_cast<FamilyQuery *>(q)->FeatureCountErrors(update, combine);
+	strncpy(update_msg, update.c_str(), 511);
+	update_msg[511] = 0;
+	strncpy(combine_msg, combine.c_str(), 511);
+	combine_msg[511] = 0;
+}
+
 } // extern "C"

@@ -49,6 +49,7 @@ void *blsp_open(const char *, const char *, int, int, char *);
 void blsp_close(void *);
 int64_t blsp_group_by(void *, size_t, size_t, const uint32_t *, size_t, const double *, const double *, const uint8_t *, const uint8_t *, const uint8_t *,
                       const uint8_t *, int, size_t, int64_t *, double *, uint8_t *, uint8_t *, char *);
+void blsp_feature_count_errors(void *, char *, char *);
 }
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "bls_glue_sanitize: %s failed at line %d: %s\n", #c, __LINE__, msg); return 1; } } while (0)
@@ -96,6 +97,13 @@ int main() {
 		const int64_t rows = blsp_group_by(q, n, p, key.data(), K, y.data(), x.data(), y_null.data(), x_null.data(), xe_null.data(), split ? sp.data() : nullptr,
 		                                   3, 128, off.data(), vals.data(), flags.data(), is_null.data(), msg);
 		CHECK(rows > 0 && rows <= (int64_t)n && off[K] == rows);
+		// one state given a 2-feature row and then a 3-feature row; a 2-feature state combined into a 3-feature state: the texts of
+		// bls_fit_predict_aggregate.cpp, without the counts
+		char combine_msg[512];
+		blsp_feature_count_errors(q, msg, combine_msg);
+		CHECK(strcmp(msg, "Inconsistent feature count") == 0);
+		memcpy(msg, combine_msg, sizeof msg);
+		CHECK(strcmp(msg, "Cannot combine states with different feature counts") == 0);
 		blsp_close(q);
 	}
 	printf("bls_glue_sanitize: all scenarios passed\n");

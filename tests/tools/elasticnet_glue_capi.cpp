@@ -72,8 +72,9 @@ public:
 	size_t Registered(const char *name) const { return loader_.registered.count(name); }
 
 	// rows r with key[r]; y_null / x_null per row (may be NULL); out_core [n_keys x (p + 6)], last column = n_features
+	// x_len: optional LIST length per row (<= p; default p)
 	void GroupBy(size_t n, size_t p, const uint32_t *key, size_t n_keys, const double *y, const double *x, const uint8_t *y_null, const uint8_t *x_null,
-	             int n_threads, size_t vector_size, double *out_core, uint8_t *is_null) {
+	             int n_threads, size_t vector_size, double *out_core, uint8_t *is_null, const uint32_t *x_len = nullptr) {
 		if (n_threads < 1) n_threads = 1;
 		std::vector<std::vector<data_ptr_t>> local(n_threads, std::vector<data_ptr_t>(n_keys, nullptr));
 		std::vector<std::string> errors(n_threads);
@@ -93,7 +94,7 @@ public:
 						if (!st) st = NewState();
 						sp[i] = st;
 					}
-					Update(aid, r0, cnt, p, y, x, y_null, x_null, sp);
+					Update(aid, r0, cnt, p, y, x, y_null, x_null, x_len, sp);
 				}
 			} catch (const std::exception &e) {
 				errors[t] = e.what();
@@ -160,7 +161,7 @@ private:
 		}
 	}
 	void Update(AggregateInputData &aid, size_t r0, size_t cnt, size_t p, const double *y, const double *x, const uint8_t *y_null, const uint8_t *x_null,
-	            std::vector<data_ptr_t> &states) {
+	            const uint32_t *x_len, std::vector<data_ptr_t> &states) {
 		std::vector<Vector> inputs;
 		inputs.emplace_back(LogicalType(LogicalType::DOUBLE), cnt);
 		inputs.emplace_back(LogicalType::LIST(LogicalType::DOUBLE), cnt);
@@ -174,7 +175,7 @@ private:
 			yv[i] = y[r];
 			if (y_null && y_null[r]) FlatVector::SetNull(inputs[0], i, true);
 			le[i].offset = i * p;
-			le[i].length = p;
+			le[i].length = x_len ? x_len[r] : p;
 			for (size_t j = 0; j < p; ++j) cv[i * p + j] = x[r * p + j];
 			if (x_null && x_null[r]) FlatVector::SetNull(inputs[1], i, true);
 		}
@@ -235,6 +236,28 @@ EN_API int en_group_by(void *q, size_t n, size_t p, const uint32_t *key, size_t 
 		if (msg) { strncpy(msg, e.what(), 511); msg[511] = 0; }
 		return -1;
 	}
+}
+
+// the texts of the two feature-count errors at their smallest: one state given a 2-feature row and then a 3-feature row
+// (update_msg), and a 2-feature state combined into a 3-feature state (combine_msg: two worker threads' states of one group);
+// both [512].  Both are thrown before Finalize, so no fit is made and no device is needed.
+EN_API void en_feature_count_errors(void *q, char *update_msg, char *combine_msg) {
+	const double y[2] = {1.0, 2.0}, x[6] = {1.0, 2.0, 3.0, 4.0, 5.0, 6.0};
+	const uint32_t key[2] = {0, 0};
+	double core[3 + 6];
+	uint8_t is_null[1];
+	auto run = [&](uint32_t first, uint32_t second, bool combining, char *msg) {
+		const uint32_t len[2] = {first, second};
+		msg[0] = 0;
+		try {
+			static_cast<EnQuery *>(q)->GroupBy(2, 3, key, 1, y, x, nullptr, nullptr, combining ? 2 : 1, combining ? 1 : 2048, core, is_null, len);
+		} catch (const std::exception &e) {
+			strncpy(msg, e.what(), 511);
+			msg[511] = 0;
+		}
+	};
+	run(2, 3, false, update_msg);
+	run(3, 2, true, combine_msg); // the second row's state (2 features) is the source, the first row's (3 features) the target
 }
 
 } // extern "C"

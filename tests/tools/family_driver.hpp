@@ -222,6 +222,34 @@ public:
 		return all;
 	}
 
+	// The two feature-count errors at their smallest, as the texts thrown ("" = nothing thrown).  update: one state given a
+	// 2-feature row and then a 3-feature row.  combine: a 2-feature state combined into a 3-feature state — two worker threads'
+	// states of one group (ALLOW_DESTRUCTIVE), for the window functions two leaves of a segment tree (PRESERVE_INPUT).  Both
+	// are thrown before Finalize, so no fit is made and no device is needed.
+	void FeatureCountErrors(std::string &update, std::string &combine) {
+		const double y[2] = {1.0, 2.0}, x[6] = {1.0, 2.0, 3.0, 4.0, 5.0, 6.0};
+		const uint32_t key[2] = {0, 0};
+		auto run = [&](uint32_t first, uint32_t second, bool combining) -> std::string {
+			const uint32_t len[2] = {first, second};
+			Inputs in;
+			in.n = 2;
+			in.p = 3;
+			in.y = y;
+			in.x = x;
+			in.x_len = len;
+			try {
+				if (kind_ != Kind::WINDOW) GroupBy(in, nullptr, key, 1, combining ? 2 : 1, combining ? 1 : 2048, false);
+				else if (combining) TreeWindow(in, 1, 1, 2048);
+				else Window(in, 1, 2048);
+			} catch (const std::exception &e) {
+				return e.what();
+			}
+			return "";
+		};
+		update = run(2, 3, false);
+		combine = run(3, 2, true); // the second row's state (2 features) is the source, the first row's (3 features) the target
+	}
+
 private:
 	data_ptr_t NewState() {
 		data_ptr_t s = new data_t[fn_->state_size(*fn_)];

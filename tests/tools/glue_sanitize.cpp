@@ -568,6 +568,23 @@ static void family_errors() {
 		CHECK(msg.find("Inconsistent feature count") != std::string::npos);
 		if (std::string(fn) != "ridge_fit_predict_agg") CHECK(msg.find("expected 3, got 2") != std::string::npos);
 	}
+	// The texts differ on purpose, as the reference's files do: one state given a 2-feature row and then a 3-feature row names
+	// the counts in the OLS files only; a 2-feature state combined into a 3-feature one names them in the aggregates, never in
+	// the window functions.
+	const std::string inconsistent = "Inconsistent feature count", cannot = "Cannot combine states with different feature counts";
+	const struct {
+		const char *fn;
+		std::string update, combine;
+	} want[] = {{"ols_fit_predict_agg", inconsistent + ": expected 2, got 3", cannot + ": 2 vs 3"}, {"ridge_fit_predict_agg", inconsistent, cannot + ": 2 vs 3"},
+	            {"wls_fit_predict_agg", inconsistent, cannot + ": 2 vs 3"},                         {"ols_fit_predict", inconsistent + ": expected 2, got 3", cannot},
+	            {"ridge_fit_predict", inconsistent, cannot},                                       {"wls_fit_predict", inconsistent, cannot}};
+	for (auto &w : want) {
+		FamilyQuery q(w.fn, nullptr, false, false);
+		std::string update, combine;
+		q.FeatureCountErrors(update, combine);
+		CHECK(update == w.update);
+		CHECK(combine == w.combine);
+	}
 }
 
 int main() {

@@ -398,6 +398,16 @@ int MixedWidthScenario() {
 		snprintf(msg, sizeof msg, "%s", e.what());
 	}
 	CHECK(threw && strcmp(msg, "Inconsistent feature count: expected 2, got 3") == 0);
+	// a 2-feature state combined into a 3-feature state: the reference's text, without the counts
+	threw = false;
+	try {
+		Vector source = pointers({states[0]}), target = pointers({states[1]});
+		fn.combine(source, target, aid, 1);
+	} catch (const std::exception &e) {
+		threw = true;
+		snprintf(msg, sizeof msg, "%s", e.what());
+	}
+	CHECK(threw && strcmp(msg, "Cannot combine states with different feature counts") == 0);
 	fn.destructor(sv, aid, n_states);
 	return 0;
 }
