@@ -439,6 +439,18 @@ SYMBOLS = {
     "anofox_hip_glm_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
                                                          C.POINTER(_DP), _DP, C.POINTER(C.c_int64), AnofoxHipGlmBatchOptions, _DP, _DP,
                                                          _ERRP]),
+    "anofox_hip_glm_fit_predict_interval_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                                    C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                                                    AnofoxHipGlmBatchOptions, C.c_double, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_glm_fit_predict_interval_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                                  C.POINTER(_DP), _DP, C.POINTER(C.c_int64), AnofoxHipGlmBatchOptions,
+                                                                  C.c_double, _DP, _DP, _ERRP]),
+    "anofox_hip_glm_fit_accuracy_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                            C.POINTER(C.c_void_p), C.c_void_p, AnofoxHipGlmBatchOptions, C.c_double,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_glm_fit_accuracy_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                          C.POINTER(_DP), _DP, AnofoxHipGlmBatchOptions, C.c_double, _DP, _DP, _DP,
+                                                          _ERRP]),
     "anofox_poisson_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxPoissonOptions,
                                       C.POINTER(AnofoxGlmFitResultCore), C.POINTER(AnofoxFitResultInference), _ERRP]),
     "anofox_binomial_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxBinomialOptions,

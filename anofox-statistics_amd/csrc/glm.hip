@@ -1,6 +1,7 @@
 // glm.hip — grouped generalised linear models (Poisson / log, binomial / logit): one wavefront per group runs the whole IRLS
 // loop of glm_irls.h, and the entry points anofox_hip_glm_fit_batch_{device,host}, anofox_hip_glm_fit_predict_batch_*,
-// anofox_poisson_fit / anofox_binomial_fit / anofox_logistic_fit / anofox_free_glm_result.
+// anofox_hip_glm_fit_predict_interval_batch_*, anofox_hip_glm_fit_accuracy_batch_*, anofox_poisson_fit / anofox_binomial_fit /
+// anofox_logistic_fit / anofox_free_glm_result.
 //
 // The contract and the method: glm_irls.h and DESIGN.md §1, "Generalised linear models".
 //   glm_irls_kernel<EM>: 64 lanes per workgroup = one wavefront per group (grid-stride over the groups).  LDS holds the
@@ -52,6 +53,16 @@ struct GlmArgs {
 	double *rec;   // [G x (p + 11)]
 	double *inf;   // [G x 5 p] or nullptr
 	double *pred;  // [n_rows x 3] or nullptr
+	double interval_z; // > 0: the Poisson interval into pred[:, 1:]
+	double threshold;  // of the accuracy
+	double *accuracy;  // [G] or nullptr
+};
+
+// what the interval and accuracy entry points add to a launch; the other entry points pass none
+struct GlmExtras {
+	double interval_z = 0.0;
+	double threshold = 0.5;
+	double *accuracy = nullptr; // device: [G]; glm_host: the host array the result is copied to
 };
 
 template <int EM>
@@ -81,6 +92,9 @@ __global__ __launch_bounds__(64) void glm_irls_kernel(GlmArgs a) {
 		P.zq = a.zq;
 		P.eta = a.scratch;
 		P.mu = a.scratch + a.n_rows;
+		P.interval_z = a.interval_z;
+		P.threshold = a.threshold;
+		P.accuracy = a.accuracy ? a.accuracy + g : nullptr;
 		gi_fit<EM>(P, a.invalid != 0, glm_lds, a.rec + g * (int64_t)(a.p + 11), a.inf ? a.inf + g * (int64_t)(5 * a.p) : nullptr, a.pred);
 		__syncthreads(); // the next group reuses the LDS
 	}
@@ -148,7 +162,7 @@ bool check_host_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxErr
 // the fit of G groups on device-resident inputs, enqueued on the context's stream (ctx->mu held by the caller)
 bool launch_glm(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y,
                 const double *const *x_cols, const double *d_offset, const int64_t *d_tc, const AnofoxHipGlmBatchOptions &o, int rule,
-                double *d_rec, double *d_inf, double *d_pred, AnofoxError *e) {
+                double *d_rec, double *d_inf, double *d_pred, AnofoxError *e, const GlmExtras &x = GlmExtras()) {
 	if (G == 0) return true;
 	const size_t rows = n_rows > 0 ? (size_t)n_rows : 1;
 	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, 2 * rows * sizeof(double), "glm scratch", e)) return false;
@@ -175,6 +189,9 @@ bool launch_glm(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, cons
 	a.rec = d_rec;
 	a.inf = d_inf;
 	a.pred = d_pred;
+	a.interval_z = x.interval_z;
+	a.threshold = x.threshold;
+	a.accuracy = x.accuracy;
 	const int k = (int)p + a.fit_intercept;
 	const size_t lds = gi_work_doubles(k) * sizeof(double);
 	const int64_t max_blocks = 1 << 20;
@@ -209,13 +226,13 @@ bool d2h(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *
 // host pointers: one staging of the whole call, the kernel, the copies back (fit: pred == nullptr; fit-predict: inf == nullptr)
 bool glm_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets, const double *y,
               const double *const *x_cols, const double *offset, const int64_t *train_counts, const AnofoxHipGlmBatchOptions &o, int rule,
-              double *rec, double *inf, double *pred, AnofoxError *e) {
+              double *rec, double *inf, double *pred, AnofoxError *e, const GlmExtras &x = GlmExtras()) {
 	if (!ctx && !(ctx = thread_default_context(e))) return false;
 	const size_t G = (size_t)n_groups, N = (size_t)n_rows, rec_len = p + 11;
 	std::lock_guard<std::mutex> lk(ctx->mu); // one lock over staging, the kernel and the copies back
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", e)) return false;
 	const size_t need = Stage::bytes(G + 1, 8) + Stage::bytes(G, 8) + (p + 2) * Stage::bytes(N, 8) + Stage::bytes(G * rec_len, 8) +
-	                    Stage::bytes(G * 5 * p, 8) + Stage::bytes(3 * N, 8);
+	                    Stage::bytes(G * 5 * p, 8) + Stage::bytes(3 * N, 8) + (x.accuracy ? Stage::bytes(G, 8) : 0);
 	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", e)) return false;
 	hipStream_t st = ctx->stream;
 	Stage s{(char *)ctx->stage};
@@ -236,13 +253,32 @@ bool glm_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows,
 	double *d_rec = s.take<double>(G * rec_len);
 	double *d_inf = s.take<double>(G * 5 * p);
 	double *d_pred = s.take<double>(3 * N);
+	GlmExtras dx = x;
+	if (x.accuracy) dx.accuracy = s.take<double>(G); // (taken last: without it the layout is the one it was)
 	if (!launch_glm(ctx, n_groups, p, n_rows, d_off, d_y, d_x, offset ? d_o : nullptr, train_counts ? d_tc : nullptr, o, rule, d_rec,
-	                inf ? d_inf : nullptr, pred ? d_pred : nullptr, e))
+	                inf ? d_inf : nullptr, pred ? d_pred : nullptr, e, dx))
 		return false;
+	if (x.accuracy && !d2h(x.accuracy, dx.accuracy, G * sizeof(double), st, e)) return false;
 	if (!d2h(rec, d_rec, G * rec_len * sizeof(double), st, e)) return false;
 	if (inf && !d2h(inf, d_inf, G * 5 * p * sizeof(double), st, e)) return false;
 	if (pred && !d2h(pred, d_pred, 3 * N * sizeof(double), st, e)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", e);
+}
+
+// the interval entry: z = 0 is the plain fit-predict; the bounds are the Poisson family's
+bool check_interval(const AnofoxHipGlmBatchOptions &o, double z, AnofoxError *e) {
+	if (!(z >= 0.0) || !isfinite(z)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: interval_z must be finite and not negative"); return false; }
+	if (z > 0.0 && o.family == ANOFOX_HIP_GLM_BINOMIAL) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: the prediction interval of the binomial family is not built");
+		return false;
+	}
+	return true;
+}
+
+bool check_accuracy(const AnofoxHipGlmBatchOptions &o, double threshold, AnofoxError *e) {
+	if (o.family != ANOFOX_HIP_GLM_BINOMIAL) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: the accuracy is the binomial family's"); return false; }
+	if (!isfinite(threshold)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: threshold must be finite"); return false; }
+	return true;
 }
 
 bool check_whole_range(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
@@ -473,6 +509,76 @@ bool anofox_hip_glm_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_grou
 	if (n_groups == 0) return true;
 	if (!check_whole_range(n_groups, n_rows, row_offsets, out_error)) return false;
 	return glm_host(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, offset, train_counts, options, 1, core, nullptr, pred, out_error);
+}
+
+bool anofox_hip_glm_fit_predict_interval_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                      const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                                      const double *d_offset, const int64_t *d_train_counts,
+                                                      AnofoxHipGlmBatchOptions options, double interval_z, double *d_core, double *d_pred,
+                                                      AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_interval(options, interval_z, out_error)) return false;
+	if (!check_glm(n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_core, out_error)) return false;
+	if (n_groups > 0 && !d_pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	GlmExtras x;
+	x.interval_z = interval_z;
+	return launch_glm(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_offset, d_train_counts, options, 1, d_core, nullptr,
+	                  d_pred, out_error, x);
+}
+
+bool anofox_hip_glm_fit_predict_interval_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                                    const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                                    const double *offset, const int64_t *train_counts, AnofoxHipGlmBatchOptions options,
+                                                    double interval_z, double *core, double *pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_interval(options, interval_z, out_error)) return false;
+	if (!check_glm(n_groups, n_features, n_rows, row_offsets, y, x_cols, core, out_error)) return false;
+	if (n_groups > 0 && !pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
+	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (n_groups == 0) return true;
+	if (!check_whole_range(n_groups, n_rows, row_offsets, out_error)) return false;
+	GlmExtras x;
+	x.interval_z = interval_z;
+	return glm_host(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, offset, train_counts, options, 1, core, nullptr, pred,
+	                out_error, x);
+}
+
+bool anofox_hip_glm_fit_accuracy_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                              const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                              const double *d_offset, AnofoxHipGlmBatchOptions options, double threshold, double *d_records,
+                                              double *d_inference, double *d_accuracy, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_accuracy(options, threshold, out_error)) return false;
+	if (!check_glm(n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_records, out_error)) return false;
+	if (n_groups > 0 && !d_accuracy) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "accuracy is NULL"); return false; }
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	GlmExtras x;
+	x.threshold = threshold;
+	x.accuracy = d_accuracy;
+	return launch_glm(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_offset, nullptr, options, 0, d_records, d_inference,
+	                  nullptr, out_error, x);
+}
+
+bool anofox_hip_glm_fit_accuracy_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                            const int64_t *row_offsets, const double *y, const double *const *x_cols, const double *offset,
+                                            AnofoxHipGlmBatchOptions options, double threshold, double *records, double *inference,
+                                            double *accuracy, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_accuracy(options, threshold, out_error)) return false;
+	if (!check_glm(n_groups, n_features, n_rows, row_offsets, y, x_cols, records, out_error)) return false;
+	if (n_groups > 0 && !accuracy) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "accuracy is NULL"); return false; }
+	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (n_groups == 0) return true;
+	GlmExtras x;
+	x.threshold = threshold;
+	x.accuracy = accuracy;
+	return glm_host(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, offset, nullptr, options, 0, records, inference, nullptr,
+	                out_error, x);
 }
 
 bool anofox_poisson_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, AnofoxPoissonOptions options,

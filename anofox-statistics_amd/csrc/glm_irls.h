@@ -31,6 +31,10 @@
 //              mu and 1 - mu at 1e-15.  Neither is active while |eta| <= 30.
 //   finish     weights at the mode -> X'WX + lambda I' -> its Cholesky -> the diagonal of the inverse (lane j solves L v = e_j);
 //              deviance, log-likelihood and Pearson chi^2 in one pass; then mu of every row for fit-predict.
+//   extras     interval_z > 0 (Poisson): the lane that writes mu of a row also writes the reference's bounds
+//              exp(eta -+ interval_z sqrt(dispersion) / max(mu, 0.001)), the lower one floored at 0.  accuracy
+//              (binomial): the share of the fitted rows with (mu >= threshold) == y, mu by the prediction pass's own expression
+//              (gi_row_mu) so that it equals a count over pred[:, 0]; two integer sums through the butterfly, lane 0 writes.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -102,6 +106,10 @@ struct GiProblem {
 	int compute_inference;
 	double zq;         // the normal quantile of the confidence level
 	double *eta, *mu;  // scratch, one double per row each, indexed by the row number
+	// the extras; a caller that does not set them gets none
+	double interval_z = 0.0;    // fit-predict, Poisson: > 0 fills pred[3 i + 1], pred[3 i + 2] with the bounds; 0: they stay NaN
+	double threshold = 0.5;     // accuracy: a row is classified 1 when mu >= threshold
+	double *accuracy = nullptr; // binomial: where the group's training accuracy goes (NaN for a failed group), or nullptr
 };
 
 template <class T>
@@ -239,6 +247,23 @@ GI_DEV void gi_nan_pred(const GiProblem &P, double *pred) {
 	GI_LANES_BEGIN(lane)
 	for (int64_t i = P.lo + lane; i < P.hi; i += 64) pred[3 * i] = pred[3 * i + 1] = pred[3 * i + 2] = NAN;
 	GI_LANES_END
+}
+
+GI_DEV void gi_nan_accuracy(const GiProblem &P) {
+	if (!P.accuracy) return;
+	GI_LANES_BEGIN(lane)
+	if (lane == 0) *P.accuracy = NAN;
+	GI_LANES_END
+}
+
+// eta (the full linear predictor, the offset included) and mu of row i at beta; a non-finite eta gives mu = NaN
+GI_DEV double gi_row_mu(const GiProblem &P, int k, const double *beta, int64_t i, double &eta) {
+	eta = P.offset ? P.offset[i] : 0.0;
+	GI_NOUNROLL
+	for (int c = 0; c < k; ++c) eta += gi_elem(P, c, i) * beta[c];
+	double mu = NAN, q, lmu, lq;
+	if (gi_finite(eta)) gi_inverse_link(P.family, eta, mu, q, lmu, lq);
+	return mu;
 }
 
 template <int EM>
@@ -409,7 +434,8 @@ GI_DEV double gi_penalty(const GiProblem &P, int k, const double *beta) {
 
 // The fit of one group.  rec: p + 11 doubles {b[p], intercept, deviance, null_deviance, pseudo_r_squared, aic, dispersion,
 // n_observations, n_params, iterations, converged, status}; inf (optional): 5 p doubles {se[p], z[p], p[p], ci_lower[p],
-// ci_upper[p]}; pred (optional): [.. x 3] indexed by the row number, {mu, NaN, NaN} for every row of [lo, hi).
+// ci_upper[p]}; pred (optional): [.. x 3] indexed by the row number, {mu, NaN, NaN} for every row of [lo, hi), or {mu, lower,
+// upper} with P.interval_z > 0 (Poisson).
 template <int EM>
 GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, double *inf, double *pred) {
 	const int p = P.p, k = p + (P.fit_intercept ? 1 : 0), ld = gi_aug_ld(k), tl = gi_tile_ld(k), ic = P.fit_intercept ? 1 : 0;
@@ -420,6 +446,7 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 	if (status) {
 		gi_fail(rec, inf, p, status);
 		gi_nan_pred(P, pred);
+		gi_nan_accuracy(P);
 		return;
 	}
 	// ---- first pass: the row mask, the start values, sum y, the first valid row ----
@@ -487,6 +514,7 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 	if (status) {
 		gi_fail(rec, inf, p, status);
 		gi_nan_pred(P, pred);
+		gi_nan_accuracy(P);
 		return;
 	}
 	// ---- the start: objective at mustart (beta = 0), the null deviance at mu = ybar ----
@@ -596,6 +624,7 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 	if (!converged) {
 		gi_fail(rec, inf, p, kGiStatusConvergence);
 		gi_nan_pred(P, pred);
+		gi_nan_accuracy(P);
 		return;
 	}
 	// ---- the finish: deviance, log-likelihood, Pearson chi^2 at the mode ----
@@ -684,17 +713,46 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 	GI_LANES_END
 	// ---- fit-predict: mu of every row of the group ----
 	if (pred) {
+		const bool interval = P.interval_z > 0.0 && P.family == kGiFamilyPoisson;
+		const double zs = interval ? P.interval_z * sqrt(dispersion) : 0.0;
 		GI_LANES_BEGIN(lane)
 		for (int64_t i = P.lo + lane; i < P.hi; i += 64) {
-			double eta = P.offset ? P.offset[i] : 0.0;
-			GI_NOUNROLL
-			for (int c = 0; c < k; ++c) eta += gi_elem(P, c, i) * beta[c];
-			double mu = NAN, q, lmu, lq;
-			if (gi_finite(eta)) gi_inverse_link(P.family, eta, mu, q, lmu, lq);
+			double eta;
+			const double mu = gi_row_mu(P, k, beta, i, eta);
+			double lower = NAN, upper = NAN;
+			if (interval && gi_finite(mu)) { // the reference's bounds, kept as they stand
+				const double h = zs / (mu > 0.001 ? mu : 0.001);
+				lower = exp(eta - h);
+				upper = exp(eta + h);
+				if (!(lower > 0.0)) lower = 0.0;
+			}
 			pred[3 * i] = mu;
-			pred[3 * i + 1] = NAN;
-			pred[3 * i + 2] = NAN;
+			pred[3 * i + 1] = lower;
+			pred[3 * i + 2] = upper;
 		}
+		GI_LANES_END
+	}
+	// ---- the training accuracy at the threshold: over the rows the fit used, mu as the prediction pass computes it ----
+	if (P.accuracy) {
+		GiPL<int64_t> hit, cnt;
+		GI_LANES_BEGIN(lane)
+		int64_t h = 0, c = 0;
+		for (int64_t i = P.lo + lane; i < P.hi; i += 64) {
+			if (!(P.mu[i] == P.mu[i])) continue;
+			double eta;
+			const double mu = gi_row_mu(P, k, beta, i, eta);
+			if (!(mu == mu)) continue;
+			++c;
+			h += ((mu >= P.threshold ? 1.0 : 0.0) == P.y[i]) ? 1 : 0;
+		}
+		hit.v[GI_AT(lane)] = h;
+		cnt.v[GI_AT(lane)] = c;
+		GI_LANES_END
+		// a group that reaches this point converged on at least max(k, 1) >= 1 valid rows, so fitted >= 1; the guard only keeps a 0 / 0
+		// out of the division should a row's recomputed mu ever be NaN where the scratch mu was not
+		const int64_t hits = gi_sum_i(hit), fitted = gi_sum_i(cnt);
+		GI_LANES_BEGIN(lane)
+		if (lane == 0) *P.accuracy = (double)hits / (double)(fitted > 0 ? fitted : 1);
 		GI_LANES_END
 	}
 	gi_sync();

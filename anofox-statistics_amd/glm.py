@@ -1,7 +1,7 @@
 """Generalised linear models on the fused IRLS kernel (csrc/glm.hip): poisson_fit_agg, binomial_fit_agg, logistic_fit_agg,
 poisson_fit_predict_agg, the scalar poisson_fit / logistic_fit, and the numpy drivers of anofox_hip_glm_fit_batch_host /
-anofox_hip_glm_fit_predict_batch_host.  The contract: DESIGN.md §1 "Generalised linear models".  Results mirror the fields of
-the reference's AnofoxGlmFitResultCore; a group whose status is not 0 is None (SQL NULL)."""
+anofox_hip_glm_fit_predict_batch_host and of their interval / accuracy forms.  The contract: DESIGN.md §1 "Generalised linear
+models".  Results mirror the fields of the reference's AnofoxGlmFitResultCore; a group whose status is not 0 is None (SQL NULL)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -31,27 +31,42 @@ def _prepare(row_offsets, y, x_cols, offset):
 
 
 def glm_fit_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, offset=None, inference: bool = False,
-                       ctx=None):
+                       ctx=None, threshold=None):
     """Grouped GLM fits, numpy in / out: records[G, p + 11] (and inference[G, 5 p] with inference=True); the layouts are
-    anofox_hip_glm_fit_batch_host's (include/anofox_stats_hip.h)."""
+    anofox_hip_glm_fit_batch_host's (include/anofox_stats_hip.h).  With a threshold (binomial) the call goes through
+    anofox_hip_glm_fit_accuracy_batch_host and accuracy[G] is appended to what is returned."""
     lib = _abi.load()
     off, yv, cols, ov, colp = _prepare(row_offsets, y, x_cols, offset)
     p, G, N = len(cols), len(off) - 1, len(yv)
     rec = np.empty((G, p + 11), dtype=np.float64)
     inf = np.empty((G, 5 * p), dtype=np.float64) if inference else None
     err = _abi.AnofoxError()
-    ok = lib.anofox_hip_glm_fit_batch_host(
-        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(_I64P), yv.ctypes.data_as(_DP), colp,
-        None if ov is None else ov.ctypes.data_as(_DP), options, rec.ctypes.data_as(_DP),
-        None if inf is None else inf.ctypes.data_as(_DP), C.byref(err))
+    head = (ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(_I64P), yv.ctypes.data_as(_DP), colp,
+            None if ov is None else ov.ctypes.data_as(_DP), options)
+    out = (rec.ctypes.data_as(_DP), None if inf is None else inf.ctypes.data_as(_DP))
+    if threshold is None:
+        ok = lib.anofox_hip_glm_fit_batch_host(*head, *out, C.byref(err))
+    else:
+        acc = np.empty(G, dtype=np.float64)
+        ok = lib.anofox_hip_glm_fit_accuracy_batch_host(*head, float(threshold), *out, acc.ctypes.data_as(_DP), C.byref(err))
     if not ok:
         raise AnofoxStatsError(err.code, err.text())
-    return (rec, inf) if inference else rec
+    res = (rec, inf) if inference else (rec,)
+    if threshold is not None:
+        res += (acc,)
+    return res if len(res) > 1 else rec
+
+
+def glm_fit_accuracy_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, threshold: float = 0.5,
+                                offset=None, inference: bool = False, ctx=None):
+    """anofox_hip_glm_fit_accuracy_batch_host: (records, [inference,] accuracy[G]); binomial family only."""
+    return glm_fit_batch_host(row_offsets, y, x_cols, options, offset, inference, ctx, threshold=threshold)
 
 
 def glm_fit_predict_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, offset=None, train_counts=None,
-                               ctx=None):
-    """GLM fit + predict, numpy in / out: (core[G, p + 11], pred[N, 3] = mu, NaN, NaN; a NaN mu = NULL)."""
+                               ctx=None, interval_z=None):
+    """GLM fit + predict, numpy in / out: (core[G, p + 11], pred[N, 3] = mu, NaN, NaN; a NaN mu = NULL).  With interval_z the
+    call goes through anofox_hip_glm_fit_predict_interval_batch_host: pred = mu, lower, upper for interval_z > 0 (Poisson)."""
     lib = _abi.load()
     off, yv, cols, ov, colp = _prepare(row_offsets, y, x_cols, offset)
     tc = None if train_counts is None else np.ascontiguousarray(train_counts, dtype=np.int64)
@@ -59,19 +74,26 @@ def glm_fit_predict_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.A
     core = np.empty((G, p + 11), dtype=np.float64)
     pred = np.empty((N, 3), dtype=np.float64)
     err = _abi.AnofoxError()
-    ok = lib.anofox_hip_glm_fit_predict_batch_host(
-        ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(_I64P), yv.ctypes.data_as(_DP), colp,
-        None if ov is None else ov.ctypes.data_as(_DP), None if tc is None else tc.ctypes.data_as(_I64P), options,
-        core.ctypes.data_as(_DP), pred.ctypes.data_as(_DP), C.byref(err))
+    fn = lib.anofox_hip_glm_fit_predict_batch_host if interval_z is None else lib.anofox_hip_glm_fit_predict_interval_batch_host
+    ok = fn(ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(_I64P), yv.ctypes.data_as(_DP), colp,
+            None if ov is None else ov.ctypes.data_as(_DP), None if tc is None else tc.ctypes.data_as(_I64P), options,
+            *(() if interval_z is None else (float(interval_z),)), core.ctypes.data_as(_DP), pred.ctypes.data_as(_DP), C.byref(err))
     if not ok:
         raise AnofoxStatsError(err.code, err.text())
     return core, pred
 
 
+def glm_fit_predict_interval_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, interval_z: float,
+                                        offset=None, train_counts=None, ctx=None):
+    """anofox_hip_glm_fit_predict_interval_batch_host: (core[G, p + 11], pred[N, 3] = mu, lower, upper)."""
+    return glm_fit_predict_batch_host(row_offsets, y, x_cols, options, offset, train_counts, ctx, interval_z=interval_z)
+
+
 def glm_fit_batch_device(ctx, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, offset=None,
-                         inference: bool = False, use_current_torch_stream: bool = True):
+                         inference: bool = False, use_current_torch_stream: bool = True, threshold=None):
     """Grouped GLM fits on CUDA tensors (row_offsets int64[G + 1], y / x_cols[j] / offset float64[N]).  Asynchronous.
-    Returns records[G, p + 11], or (records, inference[G, 5 p]) with inference=True."""
+    Returns records[G, p + 11], or (records, inference[G, 5 p]) with inference=True; with a threshold (binomial, through
+    anofox_hip_glm_fit_accuracy_batch_device) accuracy[G] is appended."""
     import torch
 
     p, G, N = len(x_cols), int(row_offsets.numel()) - 1, int(y.numel())
@@ -89,18 +111,26 @@ def glm_fit_batch_device(ctx, row_offsets, y, x_cols: Sequence, options: _abi.An
         ctx.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
     cols = (C.c_void_p * max(p, 1))(*[c.data_ptr() for c in x_cols])
     err = _abi.AnofoxError()
-    ok = ctx._lib.anofox_hip_glm_fit_batch_device(
-        ctx._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols,
-        C.c_void_p(offset.data_ptr()) if offset is not None else None, options, C.c_void_p(rec.data_ptr()),
-        C.c_void_p(inf.data_ptr()) if inf is not None else None, C.byref(err))
+    head = (ctx._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols,
+            C.c_void_p(offset.data_ptr()) if offset is not None else None, options)
+    out = (C.c_void_p(rec.data_ptr()), C.c_void_p(inf.data_ptr()) if inf is not None else None)
+    if threshold is None:
+        ok = ctx._lib.anofox_hip_glm_fit_batch_device(*head, *out, C.byref(err))
+    else:
+        acc = torch.empty((G,), dtype=torch.float64, device=y.device)
+        ok = ctx._lib.anofox_hip_glm_fit_accuracy_batch_device(*head, float(threshold), *out, C.c_void_p(acc.data_ptr()), C.byref(err))
     ctx._check(ok, err)
-    return (rec, inf) if inference else rec
+    res = (rec, inf) if inference else (rec,)
+    if threshold is not None:
+        res += (acc,)
+    return res if len(res) > 1 else rec
 
 
 def glm_fit_predict_batch_device(ctx, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, offset=None,
-                                 train_counts=None, use_current_torch_stream: bool = True):
+                                 train_counts=None, use_current_torch_stream: bool = True, interval_z=None):
     """GLM fit + predict on CUDA tensors (inputs as glm_fit_batch_device; train_counts int64[G] or None).  Asynchronous.
-    Returns (core[G, p + 11], pred[N, 3]); rows outside [row_offsets[0], row_offsets[G]) are not written."""
+    Returns (core[G, p + 11], pred[N, 3]); rows outside [row_offsets[0], row_offsets[G]) are not written.  With interval_z the
+    call goes through anofox_hip_glm_fit_predict_interval_batch_device."""
     import torch
 
     p, G, N = len(x_cols), int(row_offsets.numel()) - 1, int(y.numel())
@@ -119,11 +149,11 @@ def glm_fit_predict_batch_device(ctx, row_offsets, y, x_cols: Sequence, options:
         ctx.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
     cols = (C.c_void_p * max(p, 1))(*[c.data_ptr() for c in x_cols])
     err = _abi.AnofoxError()
-    ok = ctx._lib.anofox_hip_glm_fit_predict_batch_device(
-        ctx._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols,
-        C.c_void_p(offset.data_ptr()) if offset is not None else None,
-        C.c_void_p(train_counts.data_ptr()) if train_counts is not None else None, options, C.c_void_p(core.data_ptr()),
-        C.c_void_p(pred.data_ptr()), C.byref(err))
+    fn = ctx._lib.anofox_hip_glm_fit_predict_batch_device if interval_z is None else ctx._lib.anofox_hip_glm_fit_predict_interval_batch_device
+    ok = fn(ctx._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols,
+            C.c_void_p(offset.data_ptr()) if offset is not None else None,
+            C.c_void_p(train_counts.data_ptr()) if train_counts is not None else None, options,
+            *(() if interval_z is None else (float(interval_z),)), C.c_void_p(core.data_ptr()), C.c_void_p(pred.data_ptr()), C.byref(err))
     ctx._check(ok, err)
     return core, pred
 
@@ -137,6 +167,8 @@ class GlmFitAggResult:
     n_features: int
     pred: Optional[np.ndarray] = None         # fit-predict: [N, 3] in the order of the input rows
     row_group: Optional[np.ndarray] = None
+    accuracy: Optional[np.ndarray] = None     # logistic_fit_agg: [G], NaN for a NULL group
+    threshold: Optional[float] = None
 
     @property
     def status(self) -> np.ndarray:
@@ -153,6 +185,8 @@ class GlmFitAggResult:
             f = self.inference[i]
             for j, name in enumerate(("std_errors", "z_values", "p_values", "ci_lower", "ci_upper")):
                 d[name] = f[j * p:(j + 1) * p].tolist()
+        if self.accuracy is not None:
+            d["accuracy"], d["threshold"] = float(self.accuracy[i]), self.threshold
         return d
 
     def as_dict(self) -> dict:
@@ -194,19 +228,43 @@ def binomial_fit_agg(group_keys, y, x, options=None, context=None) -> GlmFitAggR
     return _fit_agg(group_keys, y, x, parse_binomial_options(options), context)
 
 
+def _option(options, names, default):
+    for k, v in (options or {}).items():
+        if str(k).lower() in names and v is not None:
+            return v
+    return default
+
+
+def interval_z(confidence_level: float) -> float:
+    """The reference's GetTCritical table: 0.95 -> 1.96, 0.99 -> 2.576, 0.90 -> 1.645 (each within 0.001), anything else 1.96."""
+    for level, z in ((0.95, 1.96), (0.99, 2.576), (0.90, 1.645)):
+        if abs(confidence_level - level) < 0.001:
+            return z
+    return 1.96
+
+
 def logistic_fit_agg(group_keys, y, x, options=None, context=None) -> GlmFitAggResult:
-    """binomial_fit_agg under its other name: the same logit fit."""
-    return _fit_agg(group_keys, y, x, parse_binomial_options(options), context)
+    """The logit fit of binomial_fit_agg plus, per group, the training accuracy at options['threshold'] (default 0.5), counted by
+    the wavefront that fitted the group (anofox_hip_glm_fit_accuracy_batch_host)."""
+    opts = parse_binomial_options(options)
+    thr = float(_option(options, ("threshold",), 0.5))
+    uniq, _, _, offsets, ys, cols, off = _grouped(group_keys, y, x, opts)
+    out = glm_fit_batch_host(offsets, ys, cols, opts.batch_options(), offset=off, inference=opts.compute_inference, ctx=context, threshold=thr)
+    rec, inf, acc = out if opts.compute_inference else (out[0], None, out[1])
+    return GlmFitAggResult(uniq, rec, inf, len(cols), accuracy=acc, threshold=thr)
 
 
 def poisson_fit_predict_agg(group_keys, y, x, options=None, context=None) -> GlmFitAggResult:
     """poisson_fit_predict_agg: the fit on each group's rows with a y (None / NaN = a row to predict only), then mu for every row.
-    result.pred[i] = (mu, NaN, NaN) of input row i; the reference's interval is not built."""
+    result.pred[i] = (mu, NaN, NaN) of input row i; with options['interval'] = True it is (mu, yhat_lower, yhat_upper), the
+    reference's interval at interval_z(confidence_level)."""
     opts = parse_poisson_options(options)
+    z = interval_z(opts.confidence_level) if bool(_option(options, ("interval",), False)) else None
     uniq, inv, perm, offsets, ys, cols, off = _grouped(group_keys, y, x, opts)
     train = np.add.reduceat(np.isfinite(ys).astype(np.int64), offsets[:-1]) if len(ys) else np.zeros(len(uniq), np.int64)
     train = np.where(np.diff(offsets) > 0, train, 0)
-    core, pred_sorted = glm_fit_predict_batch_host(offsets, ys, cols, opts.batch_options(), offset=off, train_counts=train, ctx=context)
+    core, pred_sorted = glm_fit_predict_batch_host(offsets, ys, cols, opts.batch_options(), offset=off, train_counts=train, ctx=context,
+                                                   interval_z=z)
     pred = np.empty_like(pred_sorted)
     pred[perm] = pred_sorted
     return GlmFitAggResult(uniq, core, None, len(cols), pred=pred, row_group=inv)

@@ -343,6 +343,30 @@ class Context:
         from .glm import glm_fit_batch_host
         return glm_fit_batch_host(row_offsets, y, x_cols, options, offset, inference, ctx=self)
 
+    def glm_fit_predict_interval_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions,
+                                              interval_z: float, offset=None, train_counts=None, use_current_torch_stream: bool = True):
+        """GLM fit + predict with the Poisson interval on CUDA tensors: (core[G, p + 11], pred[N, 3] = mu, lower, upper)."""
+        from .glm import glm_fit_predict_batch_device
+        return glm_fit_predict_batch_device(self, row_offsets, y, x_cols, options, offset, train_counts, use_current_torch_stream,
+                                            interval_z=interval_z)
+
+    def glm_fit_predict_interval_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions,
+                                            interval_z: float, offset=None, train_counts=None):
+        from .glm import glm_fit_predict_batch_host
+        return glm_fit_predict_batch_host(row_offsets, y, x_cols, options, offset, train_counts, ctx=self, interval_z=interval_z)
+
+    def glm_fit_accuracy_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions,
+                                      threshold: float = 0.5, offset=None, inference: bool = False,
+                                      use_current_torch_stream: bool = True):
+        """Binomial fits with the training accuracy on CUDA tensors: (records, [inference,] accuracy[G])."""
+        from .glm import glm_fit_batch_device
+        return glm_fit_batch_device(self, row_offsets, y, x_cols, options, offset, inference, use_current_torch_stream, threshold=threshold)
+
+    def glm_fit_accuracy_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions,
+                                    threshold: float = 0.5, offset=None, inference: bool = False):
+        from .glm import glm_fit_batch_host
+        return glm_fit_batch_host(row_offsets, y, x_cols, options, offset, inference, ctx=self, threshold=threshold)
+
     def quantile_fit_path_batch_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipQuantileBatchOptions, taus,
                                        records=None, iterations=None, use_current_torch_stream: bool = True):
         """The tau path on CUDA tensors (inputs as quantile_fit_batch_device; taus: a host sequence of 1 .. 64 floats).

@@ -767,6 +767,39 @@ ANOFOX_HIP_API bool anofox_hip_glm_fit_predict_batch_host(AnofoxHipContext *ctx,
                                            const int64_t *row_offsets, const double *y, const double *const *x_cols,
                                            const double *offset, const int64_t *train_counts, AnofoxHipGlmBatchOptions options,
                                            double *core, double *pred, AnofoxError *out_error);
+/*
+ * Fit + predict with the interval of poisson_fit_predict_agg: the entry points above plus interval_z.  interval_z == 0 is exactly
+ * anofox_hip_glm_fit_predict_batch_*.  interval_z > 0 (finite), Poisson: the lane that writes mu of a row also writes, for every
+ * row with a finite mu,  s = sqrt(dispersion) / max(mu, 0.001),  pred[3 i + 1] = max(0, exp(eta - interval_z s)),
+ * pred[3 i + 2] = exp(eta + interval_z s),  eta the full linear predictor (offset included): the reference's formula
+ * (poisson_fit_predict_aggregate.cpp:471-478, 498-502), kept as it stands.  A non-finite mu leaves all three NaN.
+ * interval_z negative or not finite, or > 0 with the binomial family: false, ANOFOX_ERROR_INVALID_INPUT, "glm: ...", no launch.
+ */
+ANOFOX_HIP_API bool anofox_hip_glm_fit_predict_interval_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features,
+                                                      int64_t n_rows, const int64_t *d_row_offsets, const double *d_y,
+                                                      const double *const *x_cols, const double *d_offset,
+                                                      const int64_t *d_train_counts, AnofoxHipGlmBatchOptions options,
+                                                      double interval_z, double *d_core, double *d_pred, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_glm_fit_predict_interval_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features,
+                                                    int64_t n_rows, const int64_t *row_offsets, const double *y,
+                                                    const double *const *x_cols, const double *offset, const int64_t *train_counts,
+                                                    AnofoxHipGlmBatchOptions options, double interval_z, double *core, double *pred,
+                                                    AnofoxError *out_error);
+/*
+ * The fit with the training accuracy of logistic_fit_agg: anofox_hip_glm_fit_batch_* plus accuracy[n_groups], binomial family only
+ * (Poisson, or a threshold that is not finite: false with a "glm: ..." message, no launch).  accuracy[g] = the share of the group's
+ * fitted rows (y, x and offset finite) with (mu >= threshold ? 1.0 : 0.0) == y, mu computed as the prediction pass of fit-predict
+ * computes it, so that it equals a count over pred[:, 0] exactly; the wavefront that holds beta counts, nothing per row leaves the
+ * device.  NaN for a failed group; a fitted group has at least one such row (status 6 / 10 otherwise), so never 0 / 0.
+ */
+ANOFOX_HIP_API bool anofox_hip_glm_fit_accuracy_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                              const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                              const double *d_offset, AnofoxHipGlmBatchOptions options, double threshold,
+                                              double *d_records, double *d_inference, double *d_accuracy, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_glm_fit_accuracy_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                            const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                            const double *offset, AnofoxHipGlmBatchOptions options, double threshold, double *records,
+                                            double *inference, double *accuracy, AnofoxError *out_error);
 
 /*
  * Information criteria as batched outputs of the fit records: what the SQL functions
