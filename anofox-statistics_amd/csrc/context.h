@@ -1,5 +1,5 @@
 // context.h — the context object and the small host-side helpers shared by the translation units that implement
-// the C ABI (host_api.hip, agg_state.hip).  Internal: nothing here is exported.
+// the C ABI (host_api.hip, agg_state.hip, the model families).  Internal: nothing here is exported.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -91,8 +91,9 @@ SolveStages bls_state_stages(BlsParamsT<kWideMaxP> *bp);
 // holds ctx->mu (a family that fits outside the moment path — quantile.hip — keeps one lock over fit and predict)
 bool predict_records_locked(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,
                             const double *const *x_cols, const double *d_core, double confidence_level, double *d_pred, AnofoxError *e);
-// host_api.hip: the calling thread's default context on the current device (the host entry points' ctx == NULL)
-AnofoxHipContext *thread_default_context(AnofoxError *e);
+// host_api.hip: the context of a host entry point: `ctx`, or for ctx == NULL the calling thread's default context on the
+// current device (created on first use; nullptr and `e` set when that fails)
+AnofoxHipContext *host_context(AnofoxHipContext *ctx, AnofoxError *e);
 // The window path of another model (the elastic net): its solve stages for the frames path, and its in-register window kernels
 // for p <= 8 (launch == nullptr: every frame through the frames path)
 struct WindowSolve {
@@ -168,6 +169,37 @@ inline bool ensure_buffer(void **buf, size_t *cap, size_t need, const char *what
 	}
 	*cap = want;
 	return true;
+}
+
+// ---- argument checks and input conversion shared by the host entry points ----
+
+// the offsets of a host batch: group g owns rows [off[g], off[g + 1]) of the n_rows that the caller's arrays hold
+inline bool check_host_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
+	for (int64_t g = 0; g < G; ++g) {
+		if (off[g + 1] < off[g] || off[g] < 0 || off[g + 1] > n_rows) {
+			set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing and within [0, n_rows]");
+			return false;
+		}
+	}
+	return true;
+}
+
+// entries with one output per row: every row belongs to a group
+inline bool check_whole_range(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
+	if (G > 0 && (off[0] != 0 || off[G] != n_rows)) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
+		return false;
+	}
+	return true;
+}
+
+// DataArray::to_vec (types.rs:79-89): NULL entries -> NaN through the validity bitmask; rows past a.len, up to len, are NaN
+inline void expand_data_array(const AnofoxDataArray &a, std::vector<double> &out, size_t len = 0) {
+	out.assign(len > a.len ? len : a.len, NAN);
+	for (size_t i = 0; i < a.len; ++i) {
+		const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
+		out[i] = valid ? a.data[i] : NAN;
+	}
 }
 
 inline hipEvent_t get_event(AnofoxHipContext *ctx) {

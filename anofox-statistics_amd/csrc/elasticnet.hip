@@ -27,7 +27,8 @@
 
 using namespace anofox;
 
-#include "context.h"
+#include "host_stage.h"
+#include "row_slabs.h"
 
 using namespace anofox::host;
 
@@ -406,59 +407,33 @@ bool anofox_hip_elasticnet_fit_batch_host(AnofoxHipContext *ctx, int64_t n_group
                                           AnofoxHipElasticNetBatchOptions options, double *core, int32_t *iterations,
                                           AnofoxError *out_error) {
 	reset_error(out_error);
-	if (!ctx) {
-		ctx = thread_default_context(out_error);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	if (!validate_en(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, options, core, out_error)) return false;
 	if (n_groups == 0) return true;
-	for (int64_t g = 0; g < n_groups; ++g) {
-		if (row_offsets[g + 1] < row_offsets[g] || row_offsets[g] < 0 || row_offsets[g + 1] > n_rows) {
-			set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing and within [0, n_rows]");
-			return false;
-		}
-	}
+	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t p = n_features, core_len = p + 6;
-	// the groups pass through the GPU in slabs of at most ~32M rows (as anofox_hip_fit_batch_host)
-	const int64_t slab_rows = 32ll << 20;
 	std::vector<int64_t> off;
-	int64_t g0 = 0;
-	while (g0 < n_groups) {
-		int64_t g1 = g0 + 1;
-		while (g1 < n_groups && row_offsets[g1 + 1] - row_offsets[g0] <= slab_rows) ++g1;
-		const int64_t G = g1 - g0;
-		const int64_t r0 = row_offsets[g0], R = row_offsets[g1] - r0;
-		off.resize((size_t)G + 1);
-		for (int64_t g = 0; g <= G; ++g) off[(size_t)g] = row_offsets[g0 + g] - r0;
-		const size_t b_off = align_up(((size_t)G + 1) * sizeof(int64_t), 256);
-		const size_t b_col = align_up(((size_t)R + 2) * sizeof(double), 256);
-		const size_t b_core = align_up((size_t)G * core_len * sizeof(double), 256);
-		const size_t b_it = align_up((size_t)G * sizeof(int32_t), 256);
-		if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, b_off + (p + 1) * b_col + b_core + b_it, "staging", out_error)) return false;
-		char *cur = (char *)ctx->stage;
-		int64_t *d_off = (int64_t *)cur;
-		cur += b_off;
-		hipStream_t st = ctx->stream;
-		if (hip_fail(hipMemcpyAsync(d_off, off.data(), ((size_t)G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D offsets", out_error)) return false;
-		const double *d_x[kWideMaxP];
-		for (size_t j = 0; j < p; ++j) {
-			if (R > 0 && hip_fail(hipMemcpyAsync(cur, x_cols[j] + r0, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st), "H2D x", out_error)) return false;
-			d_x[j] = (const double *)cur;
-			cur += b_col;
-		}
-		if (R > 0 && hip_fail(hipMemcpyAsync(cur, y + r0, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st), "H2D y", out_error)) return false;
-		const double *d_y = (const double *)cur;
-		cur += b_col;
-		double *d_core = (double *)cur;
-		cur += b_core;
-		int32_t *d_it = iterations ? (int32_t *)cur : nullptr;
-		if (!run_en(ctx, G, p, R, d_off, d_y, d_x, options, d_core, d_it, out_error)) return false;
-		if (hip_fail(hipMemcpyAsync(core + (size_t)g0 * core_len, d_core, (size_t)G * core_len * sizeof(double), hipMemcpyDeviceToHost, st), "D2H core", out_error)) return false;
-		if (d_it && hip_fail(hipMemcpyAsync(iterations + g0, d_it, (size_t)G * sizeof(int32_t), hipMemcpyDeviceToHost, st), "D2H iterations", out_error)) return false;
+	hipStream_t st = ctx->stream;
+	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
+		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
+		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
+		int64_t *d_off;
+		StagedColumns c;
+		double *d_core;
+		int32_t *d_it;
+		if (!stage_call(ctx, out_error, [&](Stage &s) {
+			    d_off = s.put(off.data(), (size_t)G + 1, "H2D offsets");
+			    c = s.columns(p, r0, R, x_cols, y);
+			    d_core = s.take<double>((size_t)G * core_len);
+			    d_it = iterations ? s.take<int32_t>((size_t)G) : nullptr;
+		    }))
+			return false;
+		if (!run_en(ctx, G, p, R, d_off, c.y, c.x, options, d_core, d_it, out_error)) return false;
+		if (!d2h(core + (size_t)g0 * core_len, d_core, (size_t)G * core_len * sizeof(double), st, out_error, "D2H core")) return false;
+		if (d_it && !d2h(iterations + g0, d_it, (size_t)G * sizeof(int32_t), st, out_error, "D2H iterations")) return false;
 		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-		g0 = g1;
 	}
 	return true;
 }
@@ -492,18 +467,11 @@ bool anofox_elasticnet_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x
 		return false;
 	}
 	const size_t n_pad = n < 2 ? 2 : n;
-	auto expand = [](const AnofoxDataArray &a, std::vector<double> &out, size_t len) {
-		out.assign(len, NAN);
-		for (size_t i = 0; i < a.len; ++i) {
-			const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
-			out[i] = valid ? a.data[i] : NAN;
-		}
-	};
 	std::vector<std::vector<double>> cols(p);
 	std::vector<double> yv;
-	expand(y, yv, n_pad);
+	expand_data_array(y, yv, n_pad);
 	std::vector<const double *> xp(p);
-	for (size_t j = 0; j < p; ++j) { expand(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
+	for (size_t j = 0; j < p; ++j) { expand_data_array(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
 	AnofoxHipElasticNetBatchOptions o;
 	memset(&o, 0, sizeof o);
 	o.fit_intercept = options.fit_intercept;

@@ -24,7 +24,7 @@
 
 using namespace anofox;
 
-#include "context.h"
+#include "host_stage.h"
 
 using namespace anofox::host;
 using namespace anofox::glm;
@@ -149,16 +149,6 @@ bool check_glm(int64_t G, size_t p, int64_t n_rows, const void *off, const void 
 	return true;
 }
 
-bool check_host_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
-	for (int64_t g = 0; g < G; ++g) {
-		if (off[g + 1] < off[g] || off[g] < 0 || off[g + 1] > n_rows) {
-			set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing and within [0, n_rows]");
-			return false;
-		}
-	}
-	return true;
-}
-
 // the fit of G groups on device-resident inputs, enqueued on the context's stream (ctx->mu held by the caller)
 bool launch_glm(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y,
                 const double *const *x_cols, const double *d_offset, const int64_t *d_tc, const AnofoxHipGlmBatchOptions &o, int rule,
@@ -204,60 +194,30 @@ bool launch_glm(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, cons
 	return !hip_fail(hipGetLastError(), "glm_irls_kernel", e);
 }
 
-struct Stage {
-	char *cur;
-	template <class T>
-	T *take(size_t n) {
-		T *p = (T *)cur;
-		cur += align_up(n * sizeof(T) + 16, 256);
-		return p;
-	}
-	static size_t bytes(size_t n, size_t elem) { return align_up(n * elem + 16, 256); }
-};
-
-bool h2d(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *e) {
-	return bytes == 0 || !hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "H2D", e);
-}
-
-bool d2h(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *e) {
-	return bytes == 0 || !hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "D2H", e);
-}
-
 // host pointers: one staging of the whole call, the kernel, the copies back (fit: pred == nullptr; fit-predict: inf == nullptr)
 bool glm_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets, const double *y,
               const double *const *x_cols, const double *offset, const int64_t *train_counts, const AnofoxHipGlmBatchOptions &o, int rule,
               double *rec, double *inf, double *pred, AnofoxError *e, const GlmExtras &x = GlmExtras()) {
-	if (!ctx && !(ctx = thread_default_context(e))) return false;
+	if (!(ctx = host_context(ctx, e))) return false;
 	const size_t G = (size_t)n_groups, N = (size_t)n_rows, rec_len = p + 11;
 	std::lock_guard<std::mutex> lk(ctx->mu); // one lock over staging, the kernel and the copies back
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", e)) return false;
-	const size_t need = Stage::bytes(G + 1, 8) + Stage::bytes(G, 8) + (p + 2) * Stage::bytes(N, 8) + Stage::bytes(G * rec_len, 8) +
-	                    Stage::bytes(G * 5 * p, 8) + Stage::bytes(3 * N, 8) + (x.accuracy ? Stage::bytes(G, 8) : 0);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", e)) return false;
 	hipStream_t st = ctx->stream;
-	Stage s{(char *)ctx->stage};
-	int64_t *d_off = s.take<int64_t>(G + 1);
-	int64_t *d_tc = s.take<int64_t>(G);
-	if (!h2d(d_off, row_offsets, (G + 1) * sizeof(int64_t), st, e)) return false;
-	if (train_counts && !h2d(d_tc, train_counts, G * sizeof(int64_t), st, e)) return false;
-	const double *d_x[kGiMaxP];
-	for (size_t j = 0; j < p; ++j) {
-		double *c = s.take<double>(N);
-		if (!h2d(c, x_cols[j], N * sizeof(double), st, e)) return false;
-		d_x[j] = c;
-	}
-	double *d_y = s.take<double>(N);
-	if (!h2d(d_y, y, N * sizeof(double), st, e)) return false;
-	double *d_o = s.take<double>(N);
-	if (offset && !h2d(d_o, offset, N * sizeof(double), st, e)) return false;
-	double *d_rec = s.take<double>(G * rec_len);
-	double *d_inf = s.take<double>(G * 5 * p);
-	double *d_pred = s.take<double>(3 * N);
+	int64_t *d_off, *d_tc;
+	StagedColumns c;
+	double *d_rec, *d_inf, *d_pred;
 	GlmExtras dx = x;
-	if (x.accuracy) dx.accuracy = s.take<double>(G); // (taken last: without it the layout is the one it was)
-	if (!launch_glm(ctx, n_groups, p, n_rows, d_off, d_y, d_x, offset ? d_o : nullptr, train_counts ? d_tc : nullptr, o, rule, d_rec,
-	                inf ? d_inf : nullptr, pred ? d_pred : nullptr, e, dx))
+	if (!stage_call(ctx, e, [&](Stage &s) {
+		    d_off = s.put(row_offsets, G + 1);
+		    d_tc = s.put(train_counts, G);
+		    c = s.columns(p, 0, n_rows, x_cols, y, nullptr, offset, kPlainColumns);
+		    d_rec = s.take<double>(G * rec_len);
+		    d_inf = inf ? s.take<double>(G * 5 * p) : nullptr;
+		    d_pred = pred ? s.take<double>(3 * N) : nullptr;
+		    if (x.accuracy) dx.accuracy = s.take<double>(G);
+	    }))
 		return false;
+	if (!launch_glm(ctx, n_groups, p, n_rows, d_off, c.y, c.x, c.offset, d_tc, o, rule, d_rec, d_inf, d_pred, e, dx)) return false;
 	if (x.accuracy && !d2h(x.accuracy, dx.accuracy, G * sizeof(double), st, e)) return false;
 	if (!d2h(rec, d_rec, G * rec_len * sizeof(double), st, e)) return false;
 	if (inf && !d2h(inf, d_inf, G * 5 * p * sizeof(double), st, e)) return false;
@@ -281,24 +241,7 @@ bool check_accuracy(const AnofoxHipGlmBatchOptions &o, double threshold, AnofoxE
 	return true;
 }
 
-bool check_whole_range(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
-	if (off[0] != 0 || off[G] != n_rows) { // every row of pred belongs to a group's wavefront
-		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
-		return false;
-	}
-	return true;
-}
-
 // ---- the one-group entry points ----
-// NULL entries -> NaN through the validity bitmask
-void expand_data_array(const AnofoxDataArray &a, std::vector<double> &out) {
-	out.assign(a.len, NAN);
-	for (size_t i = 0; i < a.len; ++i) {
-		const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
-		out[i] = valid ? a.data[i] : NAN;
-	}
-}
-
 void reset_inference(AnofoxFitResultInference *inf) {
 	if (!inf) return;
 	inf->std_errors = inf->t_values = inf->p_values = inf->ci_lower = inf->ci_upper = nullptr;

@@ -21,7 +21,8 @@
 
 using namespace anofox;
 
-#include "context.h"
+#include "host_stage.h"
+#include "row_slabs.h"
 
 using namespace anofox::host;
 
@@ -415,13 +416,15 @@ bool validate_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
 
 thread_local std::unique_ptr<AnofoxHipContext, void (*)(AnofoxHipContext *)> tls_ctx(nullptr, anofox_hip_context_destroy);
 
-AnofoxHipContext *default_context(AnofoxError *e) {
-	if (!tls_ctx) {
-		AnofoxHipContext *c = nullptr;
-		if (!anofox_hip_context_create(-1, &c, e)) return nullptr;
-		tls_ctx.reset(c);
-	}
-	return tls_ctx.get();
+// the offsets of a host entry with one output per row: the groups cover the rows, in order
+bool check_covering_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
+	if (!check_whole_range(G, n_rows, off, e)) return false;
+	for (int64_t g = 0; g < G; ++g)
+		if (off[g + 1] < off[g]) {
+			set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing");
+			return false;
+		}
+	return true;
 }
 
 } // namespace
@@ -438,7 +441,15 @@ bool moment_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int6
                          double *d_core, AnofoxError *e) {
 	return run_device_batch(ctx, n_groups, p, n_rows, d_row_offsets, d_y, x_cols, nullptr, opt, d_core, nullptr, e, nullptr, stages);
 }
-AnofoxHipContext *thread_default_context(AnofoxError *e) { return default_context(e); }
+AnofoxHipContext *host_context(AnofoxHipContext *ctx, AnofoxError *e) {
+	if (ctx) return ctx;
+	if (!tls_ctx) {
+		AnofoxHipContext *c = nullptr;
+		if (!anofox_hip_context_create(-1, &c, e)) return nullptr;
+		tls_ctx.reset(c);
+	}
+	return tls_ctx.get();
+}
 } // namespace host
 } // namespace anofox
 
@@ -703,10 +714,7 @@ bool anofox_hip_information_criteria_batch_device(AnofoxHipContext *ctx, int64_t
 bool anofox_hip_information_criteria_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, const double *core,
                                                 AnofoxHipBatchOptions options, double *out, AnofoxError *out_error) {
 	reset_error(out_error);
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	if (n_groups < 0 || n_features == 0 || n_features > (size_t)kWideMaxP) {
 		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "invalid n_groups / n_features");
 		return false;
@@ -715,16 +723,19 @@ bool anofox_hip_information_criteria_batch_host(AnofoxHipContext *ctx, int64_t n
 	if (!core || !out) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "core or out is NULL"); return false; }
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t G = (size_t)n_groups, b_core = align_up(G * (n_features + 6) * sizeof(double), 256);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, b_core + G * 3 * sizeof(double), "staging", out_error)) return false;
-	double *d_core = (double *)ctx->stage, *d_out = (double *)((char *)ctx->stage + b_core);
+	const size_t G = (size_t)n_groups;
 	hipStream_t st = ctx->stream;
-	if (hip_fail(hipMemcpyAsync(d_core, core, G * (n_features + 6) * sizeof(double), hipMemcpyHostToDevice, st), "H2D core", out_error)) return false;
+	double *d_core, *d_out;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_core = s.put(core, G * (n_features + 6), "H2D core");
+		    d_out = s.take<double>(G * 3);
+	    }))
+		return false;
 	if (hip_fail(launch_information_criteria(d_core, n_groups, (int)n_features, options.fit_intercept ? 1 : 0,
 	                                         options.model == ANOFOX_HIP_MODEL_WLS ? 1 : 0, d_out, st),
 	             "information criteria kernel launch", out_error))
 		return false;
-	if (hip_fail(hipMemcpyAsync(out, d_out, G * 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H", out_error)) return false;
+	if (!d2h(out, d_out, G * 3 * sizeof(double), st, out_error)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
 
@@ -755,62 +766,27 @@ bool fit_predict_batch_host_run(AnofoxHipContext *ctx, int64_t n_groups, size_t 
                                 const AnofoxHipBatchOptions &options, const SolveStages &stages, double *core, double *pred, AnofoxError *out_error) {
 	if (n_groups == 0) return true;
 	if (!pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
-	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) {
-		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
-		return false;
-	}
-	for (int64_t g = 0; g < n_groups; ++g)
-		if (row_offsets[g + 1] < row_offsets[g]) {
-			set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing");
-			return false;
-		}
+	if (!check_covering_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t p = n_features;
-	const bool weighted = options.model == ANOFOX_HIP_MODEL_WLS;
-	const size_t ncol = p + 1 + (weighted ? 1 : 0);
-	const size_t core_len = p + 6;
+	const size_t p = n_features, core_len = p + 6;
 	const size_t R = (size_t)n_rows, G = (size_t)n_groups;
-	const size_t b_off = align_up((G + 1) * sizeof(int64_t), 256);
-	const size_t b_cnt = train_counts ? align_up(G * sizeof(int64_t), 256) : 0;
-	const size_t b_col = align_up((R + 2) * sizeof(double), 256);
-	const size_t b_core = align_up(G * core_len * sizeof(double), 256);
-	const size_t b_pred = align_up(R * 3 * sizeof(double) + 8, 256);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, b_off + b_cnt + ncol * b_col + b_core + b_pred, "staging", out_error))
-		return false;
-	char *cur = (char *)ctx->stage;
 	hipStream_t st = ctx->stream;
-	int64_t *d_off = (int64_t *)cur;
-	cur += b_off;
-	if (hip_fail(hipMemcpyAsync(d_off, row_offsets, (G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D offsets", out_error)) return false;
-	int64_t *d_cnt = nullptr;
-	if (train_counts) {
-		d_cnt = (int64_t *)cur;
-		cur += b_cnt;
-		if (hip_fail(hipMemcpyAsync(d_cnt, train_counts, G * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D counts", out_error)) return false;
-	}
-	const double *d_x[kWideMaxP];
-	for (size_t j = 0; j < p; ++j) {
-		if (R > 0 && hip_fail(hipMemcpyAsync(cur, x_cols[j], R * sizeof(double), hipMemcpyHostToDevice, st), "H2D x", out_error)) return false;
-		d_x[j] = (const double *)cur;
-		cur += b_col;
-	}
-	if (R > 0 && hip_fail(hipMemcpyAsync(cur, y, R * sizeof(double), hipMemcpyHostToDevice, st), "H2D y", out_error)) return false;
-	const double *d_y = (const double *)cur;
-	cur += b_col;
-	const double *d_w = nullptr;
-	if (weighted) {
-		if (R > 0 && hip_fail(hipMemcpyAsync(cur, w, R * sizeof(double), hipMemcpyHostToDevice, st), "H2D w", out_error)) return false;
-		d_w = (const double *)cur;
-		cur += b_col;
-	}
-	double *d_core = (double *)cur;
-	cur += b_core;
-	double *d_pred = (double *)cur;
-	if (!run_device_batch(ctx, n_groups, p, n_rows, d_off, d_y, d_x, d_w, options, d_core, nullptr, out_error, d_cnt, stages)) return false;
-	if (!run_predict(ctx, n_groups, p, n_rows, d_off, d_x, d_core, options.confidence_level, d_pred, out_error)) return false;
-	if (hip_fail(hipMemcpyAsync(core, d_core, G * core_len * sizeof(double), hipMemcpyDeviceToHost, st), "D2H core", out_error)) return false;
-	if (R > 0 && hip_fail(hipMemcpyAsync(pred, d_pred, R * 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H pred", out_error)) return false;
+	int64_t *d_off, *d_cnt;
+	StagedColumns c;
+	double *d_core, *d_pred;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_off = s.put(row_offsets, G + 1, "H2D offsets");
+		    d_cnt = s.put(train_counts, G, "H2D counts");
+		    c = s.columns(p, 0, n_rows, x_cols, y, options.model == ANOFOX_HIP_MODEL_WLS ? w : nullptr);
+		    d_core = s.take<double>(G * core_len);
+		    d_pred = s.take<double>(R * 3);
+	    }))
+		return false;
+	if (!run_device_batch(ctx, n_groups, p, n_rows, d_off, c.y, c.x, c.w, options, d_core, nullptr, out_error, d_cnt, stages)) return false;
+	if (!run_predict(ctx, n_groups, p, n_rows, d_off, c.x, d_core, options.confidence_level, d_pred, out_error)) return false;
+	if (!d2h(core, d_core, G * core_len * sizeof(double), st, out_error, "D2H core")) return false;
+	if (!d2h(pred, d_pred, R * 3 * sizeof(double), st, out_error, "D2H pred")) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
 
@@ -822,10 +798,7 @@ bool anofox_hip_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, 
                                        double *core, double *pred, AnofoxError *out_error) {
 	reset_error(out_error);
 	options.compute_inference = false;
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	if (!validate_batch(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, w, options, core, nullptr, out_error))
 		return false;
 	return fit_predict_batch_host_run(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, w, train_counts, options, kRegressionStages,
@@ -1089,40 +1062,22 @@ bool frames_host_run(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, c
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t p = n_features, R = (size_t)n_rows;
-	const bool weighted = options.model == ANOFOX_HIP_MODEL_WLS;
-	const size_t ncol = p + 1 + (weighted ? 1 : 0);
-	const size_t b_col = align_up((R + 2) * sizeof(double), 256), b_bnd = align_up(R * sizeof(int64_t), 256);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, ncol * b_col + 2 * b_bnd + align_up(R * 3 * sizeof(double) + 8, 256), "staging", out_error))
-		return false;
-	char *cur = (char *)ctx->stage;
 	hipStream_t st = ctx->stream;
-	const double *d_x[kWideMaxP];
-	for (size_t j = 0; j < p; ++j) {
-		if (hip_fail(hipMemcpyAsync(cur, x_cols[j], R * sizeof(double), hipMemcpyHostToDevice, st), "H2D x", out_error)) return false;
-		d_x[j] = (const double *)cur;
-		cur += b_col;
-	}
-	if (hip_fail(hipMemcpyAsync(cur, y, R * sizeof(double), hipMemcpyHostToDevice, st), "H2D y", out_error)) return false;
-	const double *d_y = (const double *)cur;
-	cur += b_col;
-	const double *d_w = nullptr;
-	if (weighted) {
-		if (hip_fail(hipMemcpyAsync(cur, w, R * sizeof(double), hipMemcpyHostToDevice, st), "H2D w", out_error)) return false;
-		d_w = (const double *)cur;
-		cur += b_col;
-	}
-	int64_t *d_lo = (int64_t *)cur;
-	cur += b_bnd;
-	int64_t *d_hi = (int64_t *)cur;
-	cur += b_bnd;
-	double *d_pred = (double *)cur;
-	if (hip_fail(hipMemcpyAsync(d_lo, frame_lo, R * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D frame_lo", out_error)) return false;
-	if (hip_fail(hipMemcpyAsync(d_hi, frame_hi, R * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D frame_hi", out_error)) return false;
+	StagedColumns c;
+	int64_t *d_lo, *d_hi;
+	double *d_pred;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    c = s.columns(p, 0, n_rows, x_cols, y, options.model == ANOFOX_HIP_MODEL_WLS ? w : nullptr);
+		    d_lo = s.put(frame_lo, R, "H2D frame_lo");
+		    d_hi = s.put(frame_hi, R, "H2D frame_hi");
+		    d_pred = s.take<double>(R * 3);
+	    }))
+		return false;
 	FrameScratch fs;
 	if (!carve_frames(ctx, n_rows, n_rows, p, false, &fs, out_error)) return false;
-	if (hip_fail(launch_frames_ynn(d_y, n_rows, fs.ynn, fs.scan_tmp, fs.scan_tmp_bytes, st), "frame scan launch", out_error)) return false;
-	if (!run_frames(ctx, fs, n_rows, p, n_rows, d_y, d_x, d_w, d_lo, d_hi, options, d_pred, nullptr, out_error, stages)) return false;
-	if (hip_fail(hipMemcpyAsync(pred, d_pred, R * 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H pred", out_error)) return false;
+	if (hip_fail(launch_frames_ynn(c.y, n_rows, fs.ynn, fs.scan_tmp, fs.scan_tmp_bytes, st), "frame scan launch", out_error)) return false;
+	if (!run_frames(ctx, fs, n_rows, p, n_rows, c.y, c.x, c.w, d_lo, d_hi, options, d_pred, nullptr, out_error, stages)) return false;
+	if (!d2h(pred, d_pred, R * 3 * sizeof(double), st, out_error, "D2H pred")) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
 
@@ -1132,10 +1087,7 @@ bool anofox_hip_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, s
                                         const double *const *x_cols, const double *w, const int64_t *frame_lo,
                                         const int64_t *frame_hi, AnofoxHipBatchOptions options, double *pred, AnofoxError *out_error) {
 	reset_error(out_error);
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	if (!validate_frames(ctx, n_rows, n_features, y, x_cols, w, frame_lo, frame_hi, options, pred, out_error)) return false;
 	return frames_host_run(ctx, n_rows, n_features, y, x_cols, w, frame_lo, frame_hi, options, kRegressionStages, pred, out_error);
 }
@@ -1165,47 +1117,22 @@ bool window_host_run(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features,
                      const double *const *x_cols, const double *w, const AnofoxHipWindowFrame &frame, const AnofoxHipBatchOptions &options,
                      const WindowSolve *ws, double *pred, AnofoxError *out_error) {
 	if (n_groups == 0) return true;
-	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) {
-		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
-		return false;
-	}
-	for (int64_t g = 0; g < n_groups; ++g)
-		if (row_offsets[g + 1] < row_offsets[g]) {
-			set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing");
-			return false;
-		}
+	if (!check_covering_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t p = n_features, R = (size_t)n_rows, G = (size_t)n_groups;
-	const bool weighted = options.model == ANOFOX_HIP_MODEL_WLS;
-	const size_t ncol = p + 1 + (weighted ? 1 : 0);
-	const size_t b_off = align_up((G + 1) * sizeof(int64_t), 256);
-	const size_t b_col = align_up((R + 2) * sizeof(double), 256);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, b_off + ncol * b_col + align_up(R * 3 * sizeof(double) + 8, 256), "staging", out_error))
-		return false;
-	char *cur = (char *)ctx->stage;
 	hipStream_t st = ctx->stream;
-	int64_t *d_off = (int64_t *)cur;
-	cur += b_off;
-	if (hip_fail(hipMemcpyAsync(d_off, row_offsets, (G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D offsets", out_error)) return false;
-	const double *d_x[kWideMaxP];
-	for (size_t j = 0; j < p; ++j) {
-		if (R > 0 && hip_fail(hipMemcpyAsync(cur, x_cols[j], R * sizeof(double), hipMemcpyHostToDevice, st), "H2D x", out_error)) return false;
-		d_x[j] = (const double *)cur;
-		cur += b_col;
-	}
-	if (R > 0 && hip_fail(hipMemcpyAsync(cur, y, R * sizeof(double), hipMemcpyHostToDevice, st), "H2D y", out_error)) return false;
-	const double *d_y = (const double *)cur;
-	cur += b_col;
-	const double *d_w = nullptr;
-	if (weighted) {
-		if (R > 0 && hip_fail(hipMemcpyAsync(cur, w, R * sizeof(double), hipMemcpyHostToDevice, st), "H2D w", out_error)) return false;
-		d_w = (const double *)cur;
-		cur += b_col;
-	}
-	double *d_pred = (double *)cur;
-	if (!run_window(ctx, n_groups, p, n_rows, d_off, d_y, d_x, d_w, frame, options, d_pred, out_error, ws)) return false;
-	if (R > 0 && hip_fail(hipMemcpyAsync(pred, d_pred, R * 3 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H pred", out_error)) return false;
+	int64_t *d_off;
+	StagedColumns c;
+	double *d_pred;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_off = s.put(row_offsets, G + 1, "H2D offsets");
+		    c = s.columns(p, 0, n_rows, x_cols, y, options.model == ANOFOX_HIP_MODEL_WLS ? w : nullptr);
+		    d_pred = s.take<double>(R * 3);
+	    }))
+		return false;
+	if (!run_window(ctx, n_groups, p, n_rows, d_off, c.y, c.x, c.w, frame, options, d_pred, out_error, ws)) return false;
+	if (!d2h(pred, d_pred, R * 3 * sizeof(double), st, out_error, "D2H pred")) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
 
@@ -1216,10 +1143,7 @@ bool anofox_hip_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups,
                                         const double *w, AnofoxHipWindowFrame frame, AnofoxHipBatchOptions options,
                                         double *pred, AnofoxError *out_error) {
 	reset_error(out_error);
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	if (!validate_window(ctx, n_groups, n_features, row_offsets, y, x_cols, w, frame, options, pred, out_error)) return false;
 	return window_host_run(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, w, frame, options, nullptr, pred, out_error);
 }
@@ -1230,74 +1154,34 @@ bool anofox_hip_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n
                                const double *w, AnofoxHipBatchOptions options, double *core, double *inference,
                                AnofoxError *out_error) {
 	reset_error(out_error);
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	if (!validate_batch(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, w, options, core, inference,
 	                    out_error))
 		return false;
 	if (n_groups == 0) return true;
-	for (int64_t g = 0; g < n_groups; ++g) {
-		if (row_offsets[g + 1] < row_offsets[g] || row_offsets[g] < 0 || row_offsets[g + 1] > n_rows) {
-			set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing and within [0, n_rows]");
-			return false;
-		}
-	}
+	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-
-	const size_t p = n_features;
-	const bool weighted = options.model == ANOFOX_HIP_MODEL_WLS;
-	const size_t ncol = p + 1 + (weighted ? 1 : 0);
-	const size_t core_len = p + 6, inf_len = 5 * p + 2;
-	// stream the groups through the GPU in slabs of at most ~32M rows
-	const int64_t slab_rows = 32ll << 20;
+	const size_t p = n_features, core_len = p + 6, inf_len = 5 * p + 2;
 	std::vector<int64_t> off;
-	int64_t g0 = 0;
-	while (g0 < n_groups) {
-		int64_t g1 = g0 + 1;
-		while (g1 < n_groups && row_offsets[g1 + 1] - row_offsets[g0] <= slab_rows) ++g1;
-		const int64_t G = g1 - g0;
-		const int64_t r0 = row_offsets[g0], r1 = row_offsets[g1];
-		const int64_t R = r1 - r0;
-		off.resize((size_t)G + 1);
-		for (int64_t g = 0; g <= G; ++g) off[(size_t)g] = row_offsets[g0 + g] - r0;
-
-		const size_t b_off = align_up(((size_t)G + 1) * sizeof(int64_t), 256);
-		const size_t b_col = align_up(((size_t)R + 2) * sizeof(double), 256);
-		const size_t b_core = align_up((size_t)G * core_len * sizeof(double), 256);
-		const size_t b_inf = options.compute_inference ? align_up((size_t)G * inf_len * sizeof(double), 256) : 0;
-		const size_t total = b_off + ncol * b_col + b_core + b_inf;
-		if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, total, "staging", out_error)) return false;
-		char *base = (char *)ctx->stage;
-		int64_t *d_off = (int64_t *)base;
-		char *cur = base + b_off;
-		hipStream_t st = ctx->stream;
-		if (hip_fail(hipMemcpyAsync(d_off, off.data(), ((size_t)G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D offsets", out_error)) return false;
-		const double *d_x[kWideMaxP];
-		for (size_t j = 0; j < p; ++j) {
-			if (R > 0 && hip_fail(hipMemcpyAsync(cur, x_cols[j] + r0, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st), "H2D x", out_error)) return false;
-			d_x[j] = (const double *)cur;
-			cur += b_col;
-		}
-		if (R > 0 && hip_fail(hipMemcpyAsync(cur, y + r0, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st), "H2D y", out_error)) return false;
-		const double *d_y = (const double *)cur;
-		cur += b_col;
-		const double *d_w = nullptr;
-		if (weighted) {
-			if (R > 0 && hip_fail(hipMemcpyAsync(cur, w + r0, (size_t)R * sizeof(double), hipMemcpyHostToDevice, st), "H2D w", out_error)) return false;
-			d_w = (const double *)cur;
-			cur += b_col;
-		}
-		double *d_core = (double *)cur;
-		cur += b_core;
-		double *d_inf = options.compute_inference ? (double *)cur : nullptr;
-		if (!run_device_batch(ctx, G, p, R, d_off, d_y, d_x, d_w, options, d_core, d_inf, out_error)) return false;
-		if (hip_fail(hipMemcpyAsync(core + (size_t)g0 * core_len, d_core, (size_t)G * core_len * sizeof(double), hipMemcpyDeviceToHost, st), "D2H core", out_error)) return false;
-		if (d_inf && hip_fail(hipMemcpyAsync(inference + (size_t)g0 * inf_len, d_inf, (size_t)G * inf_len * sizeof(double), hipMemcpyDeviceToHost, st), "D2H inference", out_error)) return false;
+	hipStream_t st = ctx->stream;
+	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
+		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
+		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
+		int64_t *d_off;
+		StagedColumns c;
+		double *d_core, *d_inf;
+		if (!stage_call(ctx, out_error, [&](Stage &s) {
+			    d_off = s.put(off.data(), (size_t)G + 1, "H2D offsets");
+			    c = s.columns(p, r0, R, x_cols, y, options.model == ANOFOX_HIP_MODEL_WLS ? w : nullptr);
+			    d_core = s.take<double>((size_t)G * core_len);
+			    d_inf = options.compute_inference ? s.take<double>((size_t)G * inf_len) : nullptr;
+		    }))
+			return false;
+		if (!run_device_batch(ctx, G, p, R, d_off, c.y, c.x, c.w, options, d_core, d_inf, out_error)) return false;
+		if (!d2h(core + (size_t)g0 * core_len, d_core, (size_t)G * core_len * sizeof(double), st, out_error, "D2H core")) return false;
+		if (d_inf && !d2h(inference + (size_t)g0 * inf_len, d_inf, (size_t)G * inf_len * sizeof(double), st, out_error, "D2H inference")) return false;
 		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-		g0 = g1;
 	}
 	return true;
 }
@@ -1310,15 +1194,6 @@ bool anofox_hip_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n
 /* ------------------------------------------------------------------------------------------------ */
 
 namespace {
-
-// DataArray::to_vec (types.rs:79-89): NULL -> NaN
-void expand(const AnofoxDataArray &a, std::vector<double> &out) {
-	out.resize(a.len);
-	for (size_t i = 0; i < a.len; ++i) {
-		const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
-		out[i] = valid ? a.data[i] : NAN;
-	}
-}
 
 std::string fmt_g(double v) {
 	char buf[64];
@@ -1369,10 +1244,9 @@ bool fit_single(const char *what, AnofoxDataArray y, const AnofoxDataArray *x, s
 	const size_t n_pad = n < 2 ? 2 : n;
 	std::vector<std::vector<double>> cols(p);
 	std::vector<double> yv, wv;
-	expand(y, yv);
-	yv.resize(n_pad, NAN);
-	for (size_t j = 0; j < p; ++j) { expand(x[j], cols[j]); cols[j].resize(n_pad, NAN); }
-	if (weights) { expand(*weights, wv); wv.resize(n_pad, NAN); }
+	expand_data_array(y, yv, n_pad);
+	for (size_t j = 0; j < p; ++j) expand_data_array(x[j], cols[j], n_pad);
+	if (weights) expand_data_array(*weights, wv, n_pad);
 
 	std::vector<const double *> xp(p);
 	for (size_t j = 0; j < p; ++j) xp[j] = cols[j].data();
@@ -1585,41 +1459,37 @@ bool anofox_predict(const AnofoxDataArray *x, size_t x_count, const double *coef
 	double *out = (double *)malloc((n ? n : 1) * sizeof(double));
 	if (!out) { set_error(out_error, ANOFOX_ERROR_ALLOCATION_FAILURE, "Failed to allocate predictions"); return false; }
 	if (n > 0) {
-		AnofoxHipContext *ctx = default_context(out_error);
+		AnofoxHipContext *ctx = host_context(nullptr, out_error);
 		if (!ctx) { free(out); return false; }
 		std::lock_guard<std::mutex> lk(ctx->mu);
 		bool ok = !hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error);
 		// one group holding every row; a fit record carrying the coefficients (n_obs = 0 -> no interval)
 		std::vector<std::vector<double>> cols(p);
+		std::vector<const double *> xp(p);
 		std::vector<double> core(p + 6, 0.0), pred(3 * n);
 		bool nan_coef = false;
-		for (size_t j = 0; j < p; ++j) { expand(x[j], cols[j]); core[j] = coefficients[j]; nan_coef = nan_coef || isnan(coefficients[j]); }
+		for (size_t j = 0; j < p; ++j) {
+			expand_data_array(x[j], cols[j]);
+			xp[j] = cols[j].data();
+			core[j] = coefficients[j];
+			nan_coef = nan_coef || isnan(coefficients[j]);
+		}
 		core[p] = intercept;
 		core[p + 3] = NAN;
-		const size_t b_col = align_up(n * sizeof(double), 256);
-		const size_t total = 256 + p * b_col + align_up(core.size() * sizeof(double), 256) + 3 * n * sizeof(double);
-		ok = ok && ensure_buffer(&ctx->stage, &ctx->stage_bytes, total, "staging", out_error);
-		if (ok) {
-			char *cur = (char *)ctx->stage;
-			hipStream_t st = ctx->stream;
-			const int64_t off[2] = {0, (int64_t)n};
-			int64_t *d_off = (int64_t *)cur;
-			cur += 256;
-			ok = !hip_fail(hipMemcpyAsync(d_off, off, sizeof off, hipMemcpyHostToDevice, st), "H2D", out_error);
-			const double *d_x[kWideMaxP];
-			for (size_t j = 0; ok && j < p; ++j) {
-				ok = !hip_fail(hipMemcpyAsync(cur, cols[j].data(), n * sizeof(double), hipMemcpyHostToDevice, st), "H2D", out_error);
-				d_x[j] = (const double *)cur;
-				cur += b_col;
-			}
-			double *d_core = (double *)cur;
-			cur += align_up(core.size() * sizeof(double), 256);
-			double *d_pred = (double *)cur;
-			ok = ok && !hip_fail(hipMemcpyAsync(d_core, core.data(), core.size() * sizeof(double), hipMemcpyHostToDevice, st), "H2D", out_error);
-			ok = ok && run_predict(ctx, 1, p, (int64_t)n, d_off, d_x, d_core, 0.95, d_pred, out_error);
-			ok = ok && !hip_fail(hipMemcpyAsync(pred.data(), d_pred, 3 * n * sizeof(double), hipMemcpyDeviceToHost, st), "D2H", out_error);
-			ok = ok && !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
-		}
+		const int64_t off[2] = {0, (int64_t)n};
+		hipStream_t st = ctx->stream;
+		int64_t *d_off;
+		StagedColumns c;
+		double *d_core, *d_pred;
+		ok = ok && stage_call(ctx, out_error, [&](Stage &s) {
+			     d_off = s.put(off, 2);
+			     c = s.columns(p, 0, (int64_t)n, xp.data(), nullptr, nullptr, nullptr, kPlainColumns);
+			     d_core = s.put(core.data(), core.size());
+			     d_pred = s.take<double>(3 * n);
+		     });
+		ok = ok && run_predict(ctx, 1, p, (int64_t)n, d_off, c.x, d_core, 0.95, d_pred, out_error);
+		ok = ok && d2h(pred.data(), d_pred, 3 * n * sizeof(double), st, out_error);
+		ok = ok && !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 		if (!ok) { free(out); return false; }
 		// upstream's plain predict lets a NaN coefficient poison every prediction (predict.rs:55-61)
 		for (size_t i = 0; i < n; ++i) out[i] = nan_coef ? NAN : pred[3 * i];
@@ -1717,42 +1587,25 @@ bool validate_vif(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, co
 
 bool vif_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets,
               const double *const *x_cols, int64_t min_rows, double *vif, AnofoxError *out_error) {
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	if (!validate_vif(ctx, n_groups, p, n_rows, row_offsets, x_cols, vif, out_error)) return false;
 	if (n_groups == 0) return true;
-	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) {
-		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
-		return false;
-	}
-	for (int64_t g = 0; g < n_groups; ++g)
-		if (row_offsets[g + 1] < row_offsets[g]) {
-			set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing");
-			return false;
-		}
+	if (!check_covering_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t R = (size_t)n_rows, G = (size_t)n_groups;
-	const size_t b_off = align_up((G + 1) * sizeof(int64_t), 256);
-	const size_t b_col = align_up((R + 2) * sizeof(double), 256);
-	const size_t b_out = align_up(G * (p + 1) * sizeof(double), 256);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, b_off + p * b_col + b_out, "staging", out_error)) return false;
-	char *cur = (char *)ctx->stage;
+	const size_t G = (size_t)n_groups;
 	hipStream_t st = ctx->stream;
-	int64_t *d_off = (int64_t *)cur;
-	cur += b_off;
-	if (hip_fail(hipMemcpyAsync(d_off, row_offsets, (G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D offsets", out_error)) return false;
-	std::vector<const double *> d_x(p);
-	for (size_t j = 0; j < p; ++j) {
-		if (R > 0 && hip_fail(hipMemcpyAsync(cur, x_cols[j], R * sizeof(double), hipMemcpyHostToDevice, st), "H2D x", out_error)) return false;
-		d_x[j] = (const double *)cur;
-		cur += b_col;
-	}
-	double *d_vif = (double *)cur;
-	if (!run_vif(ctx, n_groups, p, n_rows, d_off, d_x.data(), min_rows, d_vif, out_error)) return false;
-	if (hip_fail(hipMemcpyAsync(vif, d_vif, G * (p + 1) * sizeof(double), hipMemcpyDeviceToHost, st), "D2H vif", out_error)) return false;
+	int64_t *d_off;
+	StagedColumns c;
+	double *d_vif;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_off = s.put(row_offsets, G + 1, "H2D offsets");
+		    c = s.columns(p, 0, n_rows, x_cols, nullptr);
+		    d_vif = s.take<double>(G * (p + 1));
+	    }))
+		return false;
+	if (!run_vif(ctx, n_groups, p, n_rows, d_off, c.x, min_rows, d_vif, out_error)) return false;
+	if (!d2h(vif, d_vif, G * (p + 1) * sizeof(double), st, out_error, "D2H vif")) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
 
@@ -1804,7 +1657,7 @@ bool anofox_compute_vif(const AnofoxDataArray *x, size_t x_count, double **out_v
 	std::vector<std::vector<double>> cols(x_count);
 	std::vector<const double *> ptrs(x_count);
 	for (size_t j = 0; j < x_count; ++j) {
-		expand(x[j], cols[j]);
+		expand_data_array(x[j], cols[j]);
 		ptrs[j] = cols[j].data();
 	}
 	const int64_t off[2] = {0, (int64_t)n};
@@ -1874,61 +1727,31 @@ bool run_residuals(AnofoxHipContext *ctx, int64_t G, size_t p, const int64_t *d_
 bool residuals_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets,
                     const double *y, const double *y_hat, const double *const *x_cols, const double *rse,
                     bool include_studentized, bool drop_nan_rows, double *out, double *group, AnofoxError *out_error) {
-	if (!ctx) {
-		ctx = default_context(out_error);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	if (!validate_residuals(ctx, n_groups, p, n_rows, row_offsets, y, y_hat, x_cols, out, group, out_error)) return false;
 	if (n_groups == 0) return true;
-	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) {
-		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
-		return false;
-	}
-	for (int64_t g = 0; g < n_groups; ++g)
-		if (row_offsets[g + 1] < row_offsets[g]) {
-			set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing");
-			return false;
-		}
+	if (!check_covering_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t R = (size_t)n_rows, G = (size_t)n_groups;
-	const size_t b_off = align_up((G + 1) * sizeof(int64_t), 256);
-	const size_t b_col = align_up((R + 2) * sizeof(double), 256);
-	const size_t b_grp = align_up(G * 2 * sizeof(double), 256);
-	const size_t b_out = align_up(R * 4 * sizeof(double) + 8, 256);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, b_off + (p + 2) * b_col + 2 * b_grp + b_out, "staging", out_error)) return false;
-	char *cur = (char *)ctx->stage;
 	hipStream_t st = ctx->stream;
-	int64_t *d_off = (int64_t *)cur;
-	cur += b_off;
-	if (hip_fail(hipMemcpyAsync(d_off, row_offsets, (G + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st), "H2D offsets", out_error)) return false;
-	const double *src[2] = {y, y_hat};
-	const double *d_yy[2];
-	for (int k = 0; k < 2; ++k) {
-		if (R > 0 && hip_fail(hipMemcpyAsync(cur, src[k], R * sizeof(double), hipMemcpyHostToDevice, st), "H2D y", out_error)) return false;
-		d_yy[k] = (const double *)cur;
-		cur += b_col;
-	}
-	std::vector<const double *> d_x(p);
-	for (size_t j = 0; j < p; ++j) {
-		if (R > 0 && hip_fail(hipMemcpyAsync(cur, x_cols[j], R * sizeof(double), hipMemcpyHostToDevice, st), "H2D x", out_error)) return false;
-		d_x[j] = (const double *)cur;
-		cur += b_col;
-	}
-	double *d_rse = nullptr;
-	if (rse) {
-		d_rse = (double *)cur;
-		if (hip_fail(hipMemcpyAsync(d_rse, rse, G * sizeof(double), hipMemcpyHostToDevice, st), "H2D rse", out_error)) return false;
-	}
-	cur += b_grp;
-	double *d_group = (double *)cur;
-	cur += b_grp;
-	double *d_out = (double *)cur;
-	if (!run_residuals(ctx, n_groups, p, d_off, d_yy[0], d_yy[1], d_x.data(), d_rse, include_studentized, drop_nan_rows, d_out,
-	                   d_group, out_error))
+	int64_t *d_off;
+	StagedColumns c;
+	const double *d_y_hat;
+	double *d_rse, *d_group, *d_out;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_off = s.put(row_offsets, G + 1, "H2D offsets");
+		    c = s.columns(p, 0, n_rows, x_cols, y);
+		    d_y_hat = s.column(y_hat, 0, n_rows, "H2D y");
+		    d_rse = s.put(rse, G, "H2D rse");
+		    d_group = s.take<double>(G * 2);
+		    d_out = s.take<double>(R * 4);
+	    }))
 		return false;
-	if (R > 0 && hip_fail(hipMemcpyAsync(out, d_out, R * 4 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H residuals", out_error)) return false;
-	if (hip_fail(hipMemcpyAsync(group, d_group, G * 2 * sizeof(double), hipMemcpyDeviceToHost, st), "D2H residual groups", out_error)) return false;
+	if (!run_residuals(ctx, n_groups, p, d_off, c.y, d_y_hat, c.x, d_rse, include_studentized, drop_nan_rows, d_out, d_group, out_error))
+		return false;
+	if (!d2h(out, d_out, R * 4 * sizeof(double), st, out_error, "D2H residuals")) return false;
+	if (!d2h(group, d_group, G * 2 * sizeof(double), st, out_error, "D2H residual groups")) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
 
@@ -1976,8 +1799,8 @@ bool anofox_compute_residuals(AnofoxDataArray y, AnofoxDataArray y_hat, const An
 	}
 	const size_t p = (x && x_count > 0) ? x_count : 0;
 	std::vector<double> yv, yh;
-	expand(y, yv);
-	expand(y_hat, yh);
+	expand_data_array(y, yv);
+	expand_data_array(y_hat, yh);
 	std::vector<std::vector<double>> cols(p);
 	std::vector<const double *> ptrs(p);
 	for (size_t j = 0; j < p; ++j) {
@@ -1986,7 +1809,7 @@ bool anofox_compute_residuals(AnofoxDataArray y, AnofoxDataArray y_hat, const An
 			          std::to_string(x[j].len) + " observations, expected " + std::to_string(n));
 			return false;
 		}
-		expand(x[j], cols[j]);
+		expand_data_array(x[j], cols[j]);
 		cols[j].resize(n, NAN);
 		ptrs[j] = cols[j].data();
 	}
@@ -2064,10 +1887,7 @@ bool model_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, siz
 bool model_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets,
                                   const double *y, const double *const *x_cols, const int64_t *train_counts, const AnofoxHipBatchOptions &opt,
                                   const SolveStages &stages, double *core, double *pred, AnofoxError *e) {
-	if (!ctx) {
-		ctx = default_context(e);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, e))) return false;
 	if (!validate_batch(ctx, n_groups, p, n_rows, row_offsets, y, x_cols, nullptr, opt, core, nullptr, e)) return false;
 	return fit_predict_batch_host_run(ctx, n_groups, p, n_rows, row_offsets, y, x_cols, nullptr, train_counts, opt, stages, core, pred, e);
 }
@@ -2084,10 +1904,7 @@ bool model_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, si
 bool model_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets,
                                    const double *y, const double *const *x_cols, const AnofoxHipWindowFrame &frame,
                                    const AnofoxHipBatchOptions &opt, const WindowSolve &ws, double *pred, AnofoxError *e) {
-	if (!ctx) {
-		ctx = default_context(e);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, e))) return false;
 	if (!validate_window(ctx, n_groups, p, row_offsets, y, x_cols, nullptr, frame, opt, pred, e)) return false;
 	return window_host_run(ctx, n_groups, p, n_rows, row_offsets, y, x_cols, nullptr, frame, opt, &ws, pred, e);
 }
@@ -2108,10 +1925,7 @@ bool model_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size
 bool model_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t p, const double *y, const double *const *x_cols,
                                    const int64_t *frame_lo, const int64_t *frame_hi, const AnofoxHipBatchOptions &opt,
                                    const SolveStages &stages, double *pred, AnofoxError *e) {
-	if (!ctx) {
-		ctx = default_context(e);
-		if (!ctx) return false;
-	}
+	if (!(ctx = host_context(ctx, e))) return false;
 	if (!validate_frames(ctx, n_rows, p, y, x_cols, nullptr, frame_lo, frame_hi, opt, pred, e)) return false;
 	return frames_host_run(ctx, n_rows, p, y, x_cols, nullptr, frame_lo, frame_hi, opt, stages, pred, e);
 }

@@ -34,7 +34,8 @@
 
 using namespace anofox;
 
-#include "context.h"
+#include "host_stage.h"
+#include "row_slabs.h"
 
 using namespace anofox::host;
 using namespace anofox::quantile;
@@ -180,16 +181,6 @@ bool check_quantile(int64_t G, size_t p, int64_t n_rows, const void *off, const 
 	return true;
 }
 
-bool check_host_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
-	for (int64_t g = 0; g < G; ++g) {
-		if (off[g + 1] < off[g] || off[g] < 0 || off[g + 1] > n_rows) {
-			set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing and within [0, n_rows]");
-			return false;
-		}
-	}
-	return true;
-}
-
 void fill_args(QuantileArgs &a, AnofoxHipContext *ctx, int64_t G, size_t p, size_t rows, const int64_t *d_off, const double *d_y,
                const double *const *x_cols, const int64_t *d_tc, const AnofoxHipQuantileBatchOptions &o, int predict_layout, double *d_core,
                int32_t *d_iterations) {
@@ -260,35 +251,7 @@ bool launch_nan_bounds(AnofoxHipContext *ctx, int64_t n_rows, double *d_pred, An
 	return !hip_fail(hipGetLastError(), "quantile_nan_bounds_kernel", e);
 }
 
-struct Stage {
-	char *cur;
-	template <class T>
-	T *take(size_t n) {
-		T *p = (T *)cur;
-		cur += align_up(n * sizeof(T) + 16, 256);
-		return p;
-	}
-	static size_t bytes(size_t n, size_t elem) { return align_up(n * elem + 16, 256); }
-};
-
-bool h2d(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *e) {
-	return bytes == 0 || !hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "H2D", e);
-}
-
-bool d2h(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *e) {
-	return bytes == 0 || !hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "D2H", e);
-}
-
 // ---- the one-group entry points (anofox_quantile_fit, anofox_quantile_fit_path) ----
-// NULL entries -> NaN through the validity bitmask; a one-row input is padded with an all-NaN row
-void expand_data_array(const AnofoxDataArray &a, std::vector<double> &out, size_t len) {
-	out.assign(len, NAN);
-	for (size_t i = 0; i < a.len; ++i) {
-		const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
-		out[i] = valid ? a.data[i] : NAN;
-	}
-}
-
 // a record's status != 0 as the reference's error (crates/anofox-stats-core/src/errors.rs)
 void set_scalar_fit_error(int status, size_t n, size_t p, const std::vector<double> &yv, const std::vector<std::vector<double>> &cols,
                           AnofoxError *out_error) {
@@ -432,12 +395,8 @@ bool check_window_frame(const AnofoxHipWindowFrame &f, AnofoxError *e) {
 }
 
 bool check_window_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
-	if (!check_host_offsets(G, n_rows, off, e)) return false;
-	if (G > 0 && (off[0] != 0 || off[G] != n_rows)) { // every output row belongs to a partition's walker
-		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
-		return false;
-	}
-	return true;
+	// (the whole range: every output row belongs to a partition's walker)
+	return check_host_offsets(G, n_rows, off, e) && check_whole_range(G, n_rows, off, e);
 }
 
 bool check_host_frames(int64_t n_rows, const int64_t *lo, const int64_t *hi, AnofoxError *e) {
@@ -540,40 +499,30 @@ bool anofox_hip_quantile_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups,
 	if (!check_quantile(n_groups, n_features, n_rows, row_offsets, y, x_cols, quantile, out_error)) return false;
 	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	if (n_groups == 0) return true;
-	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t p = n_features, rec_len = p + 6;
-	const int64_t slab_rows = 32ll << 20; // the groups pass through the GPU in slabs of at most ~32M rows
 	std::vector<int64_t> off;
 	hipStream_t st = ctx->stream;
-	for (int64_t g0 = 0; g0 < n_groups;) {
-		int64_t g1 = g0 + 1;
-		while (g1 < n_groups && row_offsets[g1 + 1] - row_offsets[g0] <= slab_rows) ++g1;
-		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = row_offsets[g1] - r0;
-		off.resize((size_t)G + 1);
-		for (int64_t g = 0; g <= G; ++g) off[(size_t)g] = row_offsets[g0 + g] - r0;
-		const size_t need = Stage::bytes((size_t)G + 1, 8) + (p + 1) * Stage::bytes((size_t)R, 8) + Stage::bytes((size_t)G * rec_len, 8) +
-		                    Stage::bytes((size_t)G, 4);
-		if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
-		Stage s{(char *)ctx->stage};
-		int64_t *d_off = s.take<int64_t>((size_t)G + 1);
-		if (!h2d(d_off, off.data(), ((size_t)G + 1) * sizeof(int64_t), st, out_error)) return false;
-		const double *d_x[kQsMaxP];
-		for (size_t j = 0; j < p; ++j) {
-			double *c = s.take<double>((size_t)R);
-			if (!h2d(c, x_cols[j] + r0, (size_t)R * sizeof(double), st, out_error)) return false;
-			d_x[j] = c;
-		}
-		double *d_y = s.take<double>((size_t)R);
-		if (!h2d(d_y, y + r0, (size_t)R * sizeof(double), st, out_error)) return false;
-		double *d_rec = s.take<double>((size_t)G * rec_len);
-		int32_t *d_it = iterations ? s.take<int32_t>((size_t)G) : nullptr;
-		if (!launch_quantile(ctx, G, p, R, d_off, d_y, d_x, nullptr, options, 0, d_rec, d_it, out_error)) return false;
+	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
+		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
+		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
+		int64_t *d_off;
+		StagedColumns c;
+		double *d_rec;
+		int32_t *d_it;
+		if (!stage_call(ctx, out_error, [&](Stage &s) {
+			    d_off = s.put(off.data(), (size_t)G + 1);
+			    c = s.columns(p, r0, R, x_cols, y, nullptr, nullptr, kPlainColumns);
+			    d_rec = s.take<double>((size_t)G * rec_len);
+			    d_it = iterations ? s.take<int32_t>((size_t)G) : nullptr;
+		    }))
+			return false;
+		if (!launch_quantile(ctx, G, p, R, d_off, c.y, c.x, nullptr, options, 0, d_rec, d_it, out_error)) return false;
 		if (!d2h(quantile + (size_t)g0 * rec_len, d_rec, (size_t)G * rec_len * sizeof(double), st, out_error)) return false;
 		if (d_it && !d2h(iterations + g0, d_it, (size_t)G * sizeof(int32_t), st, out_error)) return false;
 		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-		g0 = g1;
 	}
 	return true;
 }
@@ -604,35 +553,25 @@ bool anofox_hip_quantile_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n
 	if (n_groups > 0 && !pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
 	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	if (n_groups == 0) return true;
-	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) {
-		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
-		return false;
-	}
-	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	if (!check_whole_range(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	const size_t p = n_features, core_len = p + 6, G = (size_t)n_groups, N = (size_t)n_rows;
 	std::lock_guard<std::mutex> lk(ctx->mu); // one lock over staging, fit, predict and the copies back
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t need = Stage::bytes(G + 1, 8) + Stage::bytes(G, 8) + (p + 1) * Stage::bytes(N + 2, 8) + Stage::bytes(G * core_len, 8) +
-	                    Stage::bytes(3 * N, 8);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
 	hipStream_t st = ctx->stream;
-	Stage s{(char *)ctx->stage};
-	int64_t *d_off = s.take<int64_t>(G + 1);
-	int64_t *d_tc = s.take<int64_t>(G);
-	if (!h2d(d_off, row_offsets, (G + 1) * sizeof(int64_t), st, out_error)) return false;
-	if (train_counts && !h2d(d_tc, train_counts, G * sizeof(int64_t), st, out_error)) return false;
-	const double *d_x[kQsMaxP];
-	for (size_t j = 0; j < p; ++j) { // (two doubles of slack: the narrow predict kernel loads rows in pairs)
-		double *c = s.take<double>(N + 2);
-		if (!h2d(c, x_cols[j], N * sizeof(double), st, out_error)) return false;
-		d_x[j] = c;
-	}
-	double *d_y = s.take<double>(N + 2);
-	if (!h2d(d_y, y, N * sizeof(double), st, out_error)) return false;
-	double *d_core = s.take<double>(G * core_len);
-	double *d_pred = s.take<double>(3 * N);
-	if (!launch_quantile(ctx, n_groups, p, n_rows, d_off, d_y, d_x, train_counts ? d_tc : nullptr, options, 1, d_core, nullptr, out_error)) return false;
-	if (!predict_records_locked(ctx, n_groups, p, n_rows, d_off, d_x, d_core, 0.95, d_pred, out_error)) return false;
+	int64_t *d_off, *d_tc;
+	StagedColumns c;
+	double *d_core, *d_pred;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_off = s.put(row_offsets, G + 1);
+		    d_tc = s.put(train_counts, G);
+		    c = s.columns(p, 0, n_rows, x_cols, y, nullptr, nullptr, kPlainColumns);
+		    d_core = s.take<double>(G * core_len);
+		    d_pred = s.take<double>(3 * N);
+	    }))
+		return false;
+	if (!launch_quantile(ctx, n_groups, p, n_rows, d_off, c.y, c.x, d_tc, options, 1, d_core, nullptr, out_error)) return false;
+	if (!predict_records_locked(ctx, n_groups, p, n_rows, d_off, c.x, d_core, 0.95, d_pred, out_error)) return false;
 	if (!launch_nan_bounds(ctx, n_rows, d_pred, out_error)) return false;
 	if (!d2h(core, d_core, G * core_len * sizeof(double), st, out_error)) return false;
 	if (!d2h(pred, d_pred, 3 * N * sizeof(double), st, out_error)) return false;
@@ -662,40 +601,30 @@ bool anofox_hip_quantile_fit_path_batch_host(AnofoxHipContext *ctx, int64_t n_gr
 	if (!check_taus(taus, n_taus, out_error)) return false;
 	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	if (n_groups == 0) return true;
-	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t p = n_features, T = n_taus, rec_len = T * (p + 6);
-	const int64_t slab_rows = 32ll << 20; // the groups pass through the GPU in slabs of at most ~32M rows
 	std::vector<int64_t> off;
 	hipStream_t st = ctx->stream;
-	for (int64_t g0 = 0; g0 < n_groups;) {
-		int64_t g1 = g0 + 1;
-		while (g1 < n_groups && row_offsets[g1 + 1] - row_offsets[g0] <= slab_rows) ++g1;
-		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = row_offsets[g1] - r0;
-		off.resize((size_t)G + 1);
-		for (int64_t g = 0; g <= G; ++g) off[(size_t)g] = row_offsets[g0 + g] - r0;
-		const size_t need = Stage::bytes((size_t)G + 1, 8) + (p + 1) * Stage::bytes((size_t)R, 8) + Stage::bytes((size_t)G * rec_len, 8) +
-		                    Stage::bytes((size_t)G * T, 4);
-		if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
-		Stage s{(char *)ctx->stage};
-		int64_t *d_off = s.take<int64_t>((size_t)G + 1);
-		if (!h2d(d_off, off.data(), ((size_t)G + 1) * sizeof(int64_t), st, out_error)) return false;
-		const double *d_x[kQsMaxP];
-		for (size_t j = 0; j < p; ++j) {
-			double *c = s.take<double>((size_t)R);
-			if (!h2d(c, x_cols[j] + r0, (size_t)R * sizeof(double), st, out_error)) return false;
-			d_x[j] = c;
-		}
-		double *d_y = s.take<double>((size_t)R);
-		if (!h2d(d_y, y + r0, (size_t)R * sizeof(double), st, out_error)) return false;
-		double *d_rec = s.take<double>((size_t)G * rec_len);
-		int32_t *d_it = iterations ? s.take<int32_t>((size_t)G * T) : nullptr;
-		if (!launch_quantile_path(ctx, G, p, R, d_off, d_y, d_x, nullptr, options, taus, T, d_rec, d_it, nullptr, out_error)) return false;
+	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
+		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
+		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
+		int64_t *d_off;
+		StagedColumns c;
+		double *d_rec;
+		int32_t *d_it;
+		if (!stage_call(ctx, out_error, [&](Stage &s) {
+			    d_off = s.put(off.data(), (size_t)G + 1);
+			    c = s.columns(p, r0, R, x_cols, y, nullptr, nullptr, kPlainColumns);
+			    d_rec = s.take<double>((size_t)G * rec_len);
+			    d_it = iterations ? s.take<int32_t>((size_t)G * T) : nullptr;
+		    }))
+			return false;
+		if (!launch_quantile_path(ctx, G, p, R, d_off, c.y, c.x, nullptr, options, taus, T, d_rec, d_it, nullptr, out_error)) return false;
 		if (!d2h(quantile + (size_t)g0 * rec_len, d_rec, (size_t)G * rec_len * sizeof(double), st, out_error)) return false;
 		if (d_it && !d2h(iterations + (size_t)g0 * T, d_it, (size_t)G * T * sizeof(int32_t), st, out_error)) return false;
 		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-		g0 = g1;
 	}
 	return true;
 }
@@ -728,37 +657,26 @@ bool anofox_hip_quantile_fit_predict_path_batch_host(AnofoxHipContext *ctx, int6
 	if (n_groups > 0 && !pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
 	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	if (n_groups == 0) return true;
-	if (row_offsets[0] != 0 || row_offsets[n_groups] != n_rows) { // every row of pred belongs to a group's wavefront
-		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must start at 0 and end at n_rows");
-		return false;
-	}
-	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	if (!check_whole_range(n_groups, n_rows, row_offsets, out_error)) return false; // every row of pred belongs to a group's wavefront
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	const size_t p = n_features, T = n_taus, rec_len = T * (p + 6), G = (size_t)n_groups, N = (size_t)n_rows;
 	std::lock_guard<std::mutex> lk(ctx->mu); // one lock over staging, the kernel and the copies back
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t need = Stage::bytes(G + 1, 8) + Stage::bytes(G, 8) + (p + 1) * Stage::bytes(N, 8) + Stage::bytes(G * rec_len, 8) +
-	                    Stage::bytes(G * T, 4) + Stage::bytes(N * T, 8);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
 	hipStream_t st = ctx->stream;
-	Stage s{(char *)ctx->stage};
-	int64_t *d_off = s.take<int64_t>(G + 1);
-	int64_t *d_tc = s.take<int64_t>(G);
-	if (!h2d(d_off, row_offsets, (G + 1) * sizeof(int64_t), st, out_error)) return false;
-	if (train_counts && !h2d(d_tc, train_counts, G * sizeof(int64_t), st, out_error)) return false;
-	const double *d_x[kQsMaxP];
-	for (size_t j = 0; j < p; ++j) {
-		double *c = s.take<double>(N);
-		if (!h2d(c, x_cols[j], N * sizeof(double), st, out_error)) return false;
-		d_x[j] = c;
-	}
-	double *d_y = s.take<double>(N);
-	if (!h2d(d_y, y, N * sizeof(double), st, out_error)) return false;
-	double *d_rec = s.take<double>(G * rec_len);
-	int32_t *d_it = s.take<int32_t>(G * T);
-	double *d_pred = s.take<double>(N * T);
-	if (!launch_quantile_path(ctx, n_groups, p, n_rows, d_off, d_y, d_x, train_counts ? d_tc : nullptr, options, taus, T, d_rec,
-	                          iterations ? d_it : nullptr, d_pred, out_error))
+	int64_t *d_off, *d_tc;
+	StagedColumns c;
+	double *d_rec, *d_pred;
+	int32_t *d_it;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_off = s.put(row_offsets, G + 1);
+		    d_tc = s.put(train_counts, G);
+		    c = s.columns(p, 0, n_rows, x_cols, y, nullptr, nullptr, kPlainColumns);
+		    d_rec = s.take<double>(G * rec_len);
+		    d_it = iterations ? s.take<int32_t>(G * T) : nullptr;
+		    d_pred = s.take<double>(N * T);
+	    }))
 		return false;
+	if (!launch_quantile_path(ctx, n_groups, p, n_rows, d_off, c.y, c.x, d_tc, options, taus, T, d_rec, d_it, d_pred, out_error)) return false;
 	if (!d2h(quantile, d_rec, G * rec_len * sizeof(double), st, out_error)) return false;
 	if (iterations && !d2h(iterations, d_it, G * T * sizeof(int32_t), st, out_error)) return false;
 	if (!d2h(pred, d_pred, N * T * sizeof(double), st, out_error)) return false;
@@ -926,31 +844,25 @@ bool quantile_window_host(AnofoxHipContext *ctx, int64_t n_parts, const int64_t 
 	window_hooks(&run_length, &cap);
 	WindowPlan plan;
 	if (!plan_window(n_parts, off, lo, hi, run_length, cap, plan, out_error)) return false;
-	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	const size_t N = (size_t)n_rows, rec_len = p + 6;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t need = 2 * Stage::bytes(N, 8) + (p + 1) * Stage::bytes(N, 8) + Stage::bytes(3 * N, 8) + Stage::bytes(N * rec_len, 8) +
-	                    Stage::bytes(N, 4);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
 	hipStream_t st = ctx->stream;
-	Stage s{(char *)ctx->stage};
-	int64_t *d_lo = s.take<int64_t>(N), *d_hi = s.take<int64_t>(N);
-	if (!h2d(d_lo, lo, N * sizeof(int64_t), st, out_error) || !h2d(d_hi, hi, N * sizeof(int64_t), st, out_error)) return false;
-	const double *d_x[kQsMaxP];
-	for (size_t j = 0; j < p; ++j) {
-		double *c = s.take<double>(N);
-		if (!h2d(c, x_cols[j], N * sizeof(double), st, out_error)) return false;
-		d_x[j] = c;
-	}
-	double *d_y = s.take<double>(N);
-	if (!h2d(d_y, y, N * sizeof(double), st, out_error)) return false;
-	double *d_pred = s.take<double>(3 * N);
-	double *d_rec = s.take<double>(N * rec_len);
-	int32_t *d_it = s.take<int32_t>(N);
-	if (!launch_quantile_window(ctx, p, n_rows, d_y, d_x, d_lo, d_hi, plan, options, d_pred, quantile ? d_rec : nullptr,
-	                            iterations ? d_it : nullptr, out_error))
+	int64_t *d_lo, *d_hi;
+	StagedColumns c;
+	double *d_pred, *d_rec;
+	int32_t *d_it;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_lo = s.put(lo, N);
+		    d_hi = s.put(hi, N);
+		    c = s.columns(p, 0, n_rows, x_cols, y, nullptr, nullptr, kPlainColumns);
+		    d_pred = s.take<double>(3 * N);
+		    d_rec = quantile ? s.take<double>(N * rec_len) : nullptr;
+		    d_it = iterations ? s.take<int32_t>(N) : nullptr;
+	    }))
 		return false;
+	if (!launch_quantile_window(ctx, p, n_rows, c.y, c.x, d_lo, d_hi, plan, options, d_pred, d_rec, d_it, out_error)) return false;
 	if (!d2h(pred, d_pred, 3 * N * sizeof(double), st, out_error)) return false;
 	if (quantile && !d2h(quantile, d_rec, N * rec_len * sizeof(double), st, out_error)) return false;
 	if (iterations && !d2h(iterations, d_it, N * sizeof(int32_t), st, out_error)) return false;
@@ -1027,7 +939,7 @@ void anofox_hip_quantile_window_test_hooks(int64_t run_length, int64_t scratch_c
 bool anofox_hip_quantile_window_stats(AnofoxHipContext *ctx, int64_t *out, AnofoxError *out_error) {
 	reset_error(out_error);
 	if (!out) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "out is NULL"); return false; }
-	if (!ctx && !(ctx = thread_default_context(out_error))) return false;
+	if (!(ctx = host_context(ctx, out_error))) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (!ctx->qw_valid) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "quantile window stats: no window call on this context"); return false; }
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;

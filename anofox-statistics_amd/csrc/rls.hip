@@ -20,7 +20,8 @@
 
 using namespace anofox;
 
-#include "context.h"
+#include "host_stage.h"
+#include "row_slabs.h"
 
 using namespace anofox::host;
 using namespace anofox::rls;
@@ -270,16 +271,6 @@ bool check_common(int64_t G, size_t p, int64_t n_rows, const void *off, const vo
 	return true;
 }
 
-bool check_host_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
-	for (int64_t g = 0; g < G; ++g) {
-		if (off[g + 1] < off[g] || off[g] < 0 || off[g + 1] > n_rows) {
-			set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets must be non-decreasing and within [0, n_rows]");
-			return false;
-		}
-	}
-	return true;
-}
-
 bool check_frame(const AnofoxHipWindowFrame &f, AnofoxError *e) {
 	if (f.start_preceding < f.end_preceding || f.start_preceding == -ANOFOX_HIP_FRAME_UNBOUNDED || f.end_preceding == ANOFOX_HIP_FRAME_UNBOUNDED) {
 		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "window frame must start at or before its end");
@@ -298,40 +289,10 @@ bool check_host_frames(int64_t n_rows, const int64_t *lo, const int64_t *hi, Ano
 	return true;
 }
 
-AnofoxHipContext *host_context(AnofoxHipContext *ctx, AnofoxError *e) { return ctx ? ctx : thread_default_context(e); }
-
-// Staging of one host call: offsets / counts / bounds (int64), y and the columns, outputs; one buffer of the context.
-struct Stage {
-	char *cur;
-	template <class T>
-	T *take(size_t n) {
-		T *p = (T *)cur;
-		cur += align_up(n * sizeof(T) + 16, 256);
-		return p;
-	}
-	static size_t bytes(size_t n, size_t elem) { return align_up(n * elem + 16, 256); }
-};
-
-bool h2d(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *e) {
-	return bytes == 0 || !hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), "H2D", e);
-}
-
-bool d2h(void *dst, const void *src, size_t bytes, hipStream_t st, AnofoxError *e) {
-	return bytes == 0 || !hip_fail(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st), "D2H", e);
-}
-
-// y and the columns of rows [r0, r0 + R) to the device; d_x receives the column pointers
-bool stage_rows(Stage &s, hipStream_t st, size_t p, int64_t r0, int64_t R, const double *y, const double *const *x_cols, const double **d_y,
-                const double **d_x, AnofoxError *e) {
-	for (size_t j = 0; j < p; ++j) {
-		double *c = s.take<double>((size_t)R);
-		if (!h2d(c, x_cols[j] + r0, (size_t)R * sizeof(double), st, e)) return false;
-		d_x[j] = c;
-	}
-	double *dy = s.take<double>((size_t)R);
-	if (!h2d(dy, y + r0, (size_t)R * sizeof(double), st, e)) return false;
-	*d_y = dy;
-	return true;
+int64_t max_group_rows(int64_t G, const int64_t *off) {
+	int64_t m = 0;
+	for (int64_t g = 0; g < G; ++g) m = off[g + 1] - off[g] > m ? off[g + 1] - off[g] : m;
+	return m;
 }
 
 bool window_frames_device(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y,
@@ -396,29 +357,23 @@ bool anofox_hip_rls_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t p = n_features, core_len = p + 6;
-	const int64_t slab_rows = 32ll << 20; // the groups pass through the GPU in slabs of at most ~32M rows
 	std::vector<int64_t> off;
 	hipStream_t st = ctx->stream;
-	for (int64_t g0 = 0; g0 < n_groups;) {
-		int64_t g1 = g0 + 1;
-		while (g1 < n_groups && row_offsets[g1 + 1] - row_offsets[g0] <= slab_rows) ++g1;
-		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = row_offsets[g1] - r0;
-		off.resize((size_t)G + 1);
-		for (int64_t g = 0; g <= G; ++g) off[(size_t)g] = row_offsets[g0 + g] - r0;
-		const size_t need = Stage::bytes((size_t)G + 1, 8) + (p + 1) * Stage::bytes((size_t)R, 8) + Stage::bytes((size_t)G * core_len, 8);
-		if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
-		Stage s{(char *)ctx->stage};
-		int64_t *d_off = s.take<int64_t>((size_t)G + 1);
-		if (!h2d(d_off, off.data(), ((size_t)G + 1) * sizeof(int64_t), st, out_error)) return false;
-		const double *d_y, *d_x[kWideMaxP];
-		if (!stage_rows(s, st, p, r0, R, y, x_cols, &d_y, d_x, out_error)) return false;
-		double *d_core = s.take<double>((size_t)G * core_len);
-		int64_t max_rows = 0;
-		for (int64_t g = 0; g < G; ++g) max_rows = off[(size_t)g + 1] - off[(size_t)g] > max_rows ? off[(size_t)g + 1] - off[(size_t)g] : max_rows;
-		if (!launch_rls_batch(ctx, G, p, d_off, d_y, d_x, nullptr, options, d_core, out_error, max_rows)) return false;
+	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
+		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
+		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
+		int64_t *d_off;
+		StagedColumns c;
+		double *d_core;
+		if (!stage_call(ctx, out_error, [&](Stage &s) {
+			    d_off = s.put(off.data(), (size_t)G + 1);
+			    c = s.columns(p, r0, R, x_cols, y, nullptr, nullptr, kPlainColumns);
+			    d_core = s.take<double>((size_t)G * core_len);
+		    }))
+			return false;
+		if (!launch_rls_batch(ctx, G, p, d_off, c.y, c.x, nullptr, options, d_core, out_error, max_group_rows(G, off.data()))) return false;
 		if (!d2h(core + (size_t)g0 * core_len, d_core, (size_t)G * core_len * sizeof(double), st, out_error)) return false;
 		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-		g0 = g1;
 	}
 	return true;
 }
@@ -452,23 +407,20 @@ bool anofox_hip_rls_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_grou
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t p = n_features, core_len = p + 6, G = (size_t)n_groups, N = (size_t)n_rows;
-	const size_t need = Stage::bytes(G + 1, 8) + Stage::bytes(G, 8) + (p + 1) * Stage::bytes(N, 8) + Stage::bytes(G * core_len, 8) +
-	                    Stage::bytes(3 * N, 8);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
 	hipStream_t st = ctx->stream;
-	Stage s{(char *)ctx->stage};
-	int64_t *d_off = s.take<int64_t>(G + 1);
-	int64_t *d_tc = s.take<int64_t>(G);
-	if (!h2d(d_off, row_offsets, (G + 1) * sizeof(int64_t), st, out_error)) return false;
-	if (train_counts && !h2d(d_tc, train_counts, G * sizeof(int64_t), st, out_error)) return false;
-	const double *d_y, *d_x[kWideMaxP];
-	if (!stage_rows(s, st, p, 0, n_rows, y, x_cols, &d_y, d_x, out_error)) return false;
-	double *d_core = s.take<double>(G * core_len);
-	double *d_pred = s.take<double>(3 * N);
-	int64_t max_rows = 0;
-	for (int64_t g = 0; g < n_groups; ++g) max_rows = row_offsets[g + 1] - row_offsets[g] > max_rows ? row_offsets[g + 1] - row_offsets[g] : max_rows;
-	if (!launch_rls_batch(ctx, n_groups, p, d_off, d_y, d_x, train_counts ? d_tc : nullptr, options, d_core, out_error, max_rows)) return false;
-	if (!launch_rls_predict(ctx, n_groups, p, d_off, d_x, d_core, d_pred, out_error)) return false;
+	int64_t *d_off, *d_tc;
+	StagedColumns c;
+	double *d_core, *d_pred;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_off = s.put(row_offsets, G + 1);
+		    d_tc = s.put(train_counts, G);
+		    c = s.columns(p, 0, n_rows, x_cols, y, nullptr, nullptr, kPlainColumns);
+		    d_core = s.take<double>(G * core_len);
+		    d_pred = s.take<double>(3 * N);
+	    }))
+		return false;
+	if (!launch_rls_batch(ctx, n_groups, p, d_off, c.y, c.x, d_tc, options, d_core, out_error, max_group_rows(n_groups, row_offsets))) return false;
+	if (!launch_rls_predict(ctx, n_groups, p, d_off, c.x, d_core, d_pred, out_error)) return false;
 	if (!d2h(core, d_core, G * core_len * sizeof(double), st, out_error)) return false;
 	if (!d2h(pred, d_pred, 3 * N * sizeof(double), st, out_error)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
@@ -502,16 +454,17 @@ bool anofox_hip_rls_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_gro
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t p = n_features, G = (size_t)n_groups, N = (size_t)n_rows;
-	const size_t need = Stage::bytes(G + 1, 8) + (p + 1) * Stage::bytes(N, 8) + Stage::bytes(3 * N, 8);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
 	hipStream_t st = ctx->stream;
-	Stage s{(char *)ctx->stage};
-	int64_t *d_off = s.take<int64_t>(G + 1);
-	if (!h2d(d_off, row_offsets, (G + 1) * sizeof(int64_t), st, out_error)) return false;
-	const double *d_y, *d_x[kWideMaxP];
-	if (!stage_rows(s, st, p, 0, n_rows, y, x_cols, &d_y, d_x, out_error)) return false;
-	double *d_pred = s.take<double>(3 * N);
-	if (!window_frames_device(ctx, n_groups, p, n_rows, d_off, d_y, d_x, frame, options, d_pred, out_error)) return false;
+	int64_t *d_off;
+	StagedColumns c;
+	double *d_pred;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_off = s.put(row_offsets, G + 1);
+		    c = s.columns(p, 0, n_rows, x_cols, y, nullptr, nullptr, kPlainColumns);
+		    d_pred = s.take<double>(3 * N);
+	    }))
+		return false;
+	if (!window_frames_device(ctx, n_groups, p, n_rows, d_off, c.y, c.x, frame, options, d_pred, out_error)) return false;
 	if (!d2h(pred, d_pred, 3 * N * sizeof(double), st, out_error)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
@@ -544,16 +497,18 @@ bool anofox_hip_rls_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_row
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
 	const size_t p = n_features, N = (size_t)n_rows;
-	const size_t need = 2 * Stage::bytes(N, 8) + (p + 1) * Stage::bytes(N, 8) + Stage::bytes(3 * N, 8);
-	if (!ensure_buffer(&ctx->stage, &ctx->stage_bytes, need, "staging", out_error)) return false;
 	hipStream_t st = ctx->stream;
-	Stage s{(char *)ctx->stage};
-	int64_t *d_lo = s.take<int64_t>(N), *d_hi = s.take<int64_t>(N);
-	if (!h2d(d_lo, frame_lo, N * sizeof(int64_t), st, out_error) || !h2d(d_hi, frame_hi, N * sizeof(int64_t), st, out_error)) return false;
-	const double *d_y, *d_x[kWideMaxP];
-	if (!stage_rows(s, st, p, 0, n_rows, y, x_cols, &d_y, d_x, out_error)) return false;
-	double *d_pred = s.take<double>(3 * N);
-	if (!launch_rls_frames(ctx, n_rows, p, d_y, d_x, d_lo, d_hi, options, d_pred, out_error)) return false;
+	int64_t *d_lo, *d_hi;
+	StagedColumns c;
+	double *d_pred;
+	if (!stage_call(ctx, out_error, [&](Stage &s) {
+		    d_lo = s.put(frame_lo, N);
+		    d_hi = s.put(frame_hi, N);
+		    c = s.columns(p, 0, n_rows, x_cols, y, nullptr, nullptr, kPlainColumns);
+		    d_pred = s.take<double>(3 * N);
+	    }))
+		return false;
+	if (!launch_rls_frames(ctx, n_rows, p, c.y, c.x, d_lo, d_hi, options, d_pred, out_error)) return false;
 	if (!d2h(pred, d_pred, 3 * N * sizeof(double), st, out_error)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error);
 }
@@ -586,19 +541,12 @@ bool anofox_rls_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count,
 		return false;
 	}
 	const size_t n_pad = n < 2 ? 2 : n;
-	auto expand = [](const AnofoxDataArray &a, std::vector<double> &out, size_t len) {
-		out.assign(len, NAN);
-		for (size_t i = 0; i < a.len; ++i) {
-			const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
-			out[i] = valid ? a.data[i] : NAN;
-		}
-	};
 	std::vector<std::vector<double>> cols(p);
 	std::vector<double> yv;
-	expand(y, yv, n_pad);
+	expand_data_array(y, yv, n_pad);
 	std::vector<const double *> xp(p);
 	for (size_t j = 0; j < p; ++j) {
-		expand(x[j], cols[j], n_pad);
+		expand_data_array(x[j], cols[j], n_pad);
 		xp[j] = cols[j].data();
 	}
 	AnofoxHipRlsBatchOptions o;
