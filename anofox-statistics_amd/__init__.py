@@ -26,7 +26,15 @@ from .options import (ElasticNetOptions, ElasticNetPredictOptions, InvalidInputE
                       parse_elasticnet_options, parse_elasticnet_predict_options, parse_options, RlsOptions,
                       parse_rls_options, BlsOptions, parse_bls_options, parse_nnls_options, parse_bls_predict_options,
                       QuantileOptions, parse_quantile_options, QuantilePathOptions, parse_quantile_path_options)
-from .runtime import AggState, Context, quantile_fit_predict_window_host, quantile_fit_predict_frames_host, quantile_window_plan, quantile_window_test_hooks, quantile_window_stats, quantile_fit_path_batch_host, quantile_fit_path_batch_device, quantile_fit_predict_path_batch_host, quantile_fit_batch_host, quantile_fit_predict_batch_host, bls_fit_batch_host, bls_fit_predict_batch_host, rls_fit_batch_host, rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host, elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host, elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host, fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host, residuals_batch_host  # noqa: E402
+from .runtime import (AggState, Context, quantile_fit_predict_window_host, quantile_fit_predict_frames_host,  # noqa: E402
+                      quantile_window_plan, quantile_window_test_hooks, quantile_window_stats, quantile_fit_path_batch_host,
+                      quantile_fit_path_batch_device, quantile_fit_predict_path_batch_host, quantile_fit_batch_host,
+                      quantile_fit_predict_batch_host, bls_fit_batch_host, bls_fit_predict_batch_host, rls_fit_batch_host,
+                      rls_fit_predict_batch_host, rls_fit_predict_window_host, rls_fit_predict_frames_host,
+                      elasticnet_fit_batch_host, elasticnet_fit_predict_batch_host, elasticnet_fit_predict_frames_host,
+                      elasticnet_fit_predict_window_host, information_criteria_host, fit_predict_frames_host, fit_batch_host,
+                      fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host,
+                      residuals_batch_host)
 from .glm import (GlmFitAggResult, binomial_fit_agg, glm_fit_batch_device, glm_fit_batch_host, glm_fit_predict_batch_device, glm_fit_predict_batch_host,  # noqa: E402
                   logistic_fit, logistic_fit_agg, poisson_fit, poisson_fit_agg, poisson_fit_predict_agg)
 from .options import GlmOptions, parse_binomial_options, parse_poisson_options  # noqa: E402

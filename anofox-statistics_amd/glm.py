@@ -12,22 +12,34 @@ import numpy as np
 
 from . import _abi
 from ._abi import AnofoxStatsError
+from ._marshal import DeviceBatch, HostBatch, call
 from .options import GlmOptions, InvalidInputException, parse_binomial_options, parse_poisson_options
 
-_DP = C.POINTER(C.c_double)
-_I64P = C.POINTER(C.c_int64)
+def _glm_fit(b, options, offset, inference, threshold):
+    """records[G, p + 11], inference[G, 5 p] on request and, with a threshold (binomial, the accuracy entry), accuracy[G]."""
+    rec = b.out((b.G, b.p + 11))
+    inf = b.out((b.G, 5 * b.p)) if inference else None
+    head = (*b.head, b.rows(offset, "offset"), options)
+    if threshold is None:
+        b.call("anofox_hip_glm_fit_batch", *head, rec, inf)
+    else:
+        acc = b.out((b.G,))
+        b.call("anofox_hip_glm_fit_accuracy_batch", *head, float(threshold), rec, inf, acc)
+    res = (rec, inf) if inference else (rec,)
+    if threshold is not None:
+        res += (acc,)
+    return res if len(res) > 1 else rec
 
 
-def _prepare(row_offsets, y, x_cols, offset):
-    off = np.ascontiguousarray(row_offsets, dtype=np.int64)
-    yv = np.ascontiguousarray(y, dtype=np.float64)
-    cols = [np.ascontiguousarray(c, dtype=np.float64) for c in x_cols]
-    ov = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64)
-    N = len(yv)
-    if any(len(c) != N for c in cols) or (ov is not None and len(ov) != N):
-        raise ValueError("every column must have y's length")
-    colp = (_DP * max(len(cols), 1))(*[c.ctypes.data_as(_DP) for c in cols])
-    return off, yv, cols, ov, colp
+def _glm_fit_predict(b, options, offset, train_counts, interval_z):
+    """(core[G, p + 11], pred[N, 3]); with interval_z through the interval entry."""
+    core, pred = b.out((b.G, b.p + 11)), b.out((b.N, 3))
+    head = (*b.head, b.rows(offset, "offset"), b.groups(train_counts, "train_counts"), options)
+    if interval_z is None:
+        b.call("anofox_hip_glm_fit_predict_batch", *head, core, pred)
+    else:
+        b.call("anofox_hip_glm_fit_predict_interval_batch", *head, float(interval_z), core, pred)
+    return core, pred
 
 
 def glm_fit_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, offset=None, inference: bool = False,
@@ -35,26 +47,7 @@ def glm_fit_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHip
     """Grouped GLM fits, numpy in / out: records[G, p + 11] (and inference[G, 5 p] with inference=True); the layouts are
     anofox_hip_glm_fit_batch_host's (include/anofox_stats_hip.h).  With a threshold (binomial) the call goes through
     anofox_hip_glm_fit_accuracy_batch_host and accuracy[G] is appended to what is returned."""
-    lib = _abi.load()
-    off, yv, cols, ov, colp = _prepare(row_offsets, y, x_cols, offset)
-    p, G, N = len(cols), len(off) - 1, len(yv)
-    rec = np.empty((G, p + 11), dtype=np.float64)
-    inf = np.empty((G, 5 * p), dtype=np.float64) if inference else None
-    err = _abi.AnofoxError()
-    head = (ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(_I64P), yv.ctypes.data_as(_DP), colp,
-            None if ov is None else ov.ctypes.data_as(_DP), options)
-    out = (rec.ctypes.data_as(_DP), None if inf is None else inf.ctypes.data_as(_DP))
-    if threshold is None:
-        ok = lib.anofox_hip_glm_fit_batch_host(*head, *out, C.byref(err))
-    else:
-        acc = np.empty(G, dtype=np.float64)
-        ok = lib.anofox_hip_glm_fit_accuracy_batch_host(*head, float(threshold), *out, acc.ctypes.data_as(_DP), C.byref(err))
-    if not ok:
-        raise AnofoxStatsError(err.code, err.text())
-    res = (rec, inf) if inference else (rec,)
-    if threshold is not None:
-        res += (acc,)
-    return res if len(res) > 1 else rec
+    return _glm_fit(HostBatch(ctx, row_offsets, y, x_cols), options, offset, inference, threshold)
 
 
 def glm_fit_accuracy_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, threshold: float = 0.5,
@@ -67,20 +60,7 @@ def glm_fit_predict_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.A
                                ctx=None, interval_z=None):
     """GLM fit + predict, numpy in / out: (core[G, p + 11], pred[N, 3] = mu, NaN, NaN; a NaN mu = NULL).  With interval_z the
     call goes through anofox_hip_glm_fit_predict_interval_batch_host: pred = mu, lower, upper for interval_z > 0 (Poisson)."""
-    lib = _abi.load()
-    off, yv, cols, ov, colp = _prepare(row_offsets, y, x_cols, offset)
-    tc = None if train_counts is None else np.ascontiguousarray(train_counts, dtype=np.int64)
-    p, G, N = len(cols), len(off) - 1, len(yv)
-    core = np.empty((G, p + 11), dtype=np.float64)
-    pred = np.empty((N, 3), dtype=np.float64)
-    err = _abi.AnofoxError()
-    fn = lib.anofox_hip_glm_fit_predict_batch_host if interval_z is None else lib.anofox_hip_glm_fit_predict_interval_batch_host
-    ok = fn(ctx._h if ctx is not None else None, G, p, N, off.ctypes.data_as(_I64P), yv.ctypes.data_as(_DP), colp,
-            None if ov is None else ov.ctypes.data_as(_DP), None if tc is None else tc.ctypes.data_as(_I64P), options,
-            *(() if interval_z is None else (float(interval_z),)), core.ctypes.data_as(_DP), pred.ctypes.data_as(_DP), C.byref(err))
-    if not ok:
-        raise AnofoxStatsError(err.code, err.text())
-    return core, pred
+    return _glm_fit_predict(HostBatch(ctx, row_offsets, y, x_cols), options, offset, train_counts, interval_z)
 
 
 def glm_fit_predict_interval_batch_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, interval_z: float,
@@ -94,36 +74,7 @@ def glm_fit_batch_device(ctx, row_offsets, y, x_cols: Sequence, options: _abi.An
     """Grouped GLM fits on CUDA tensors (row_offsets int64[G + 1], y / x_cols[j] / offset float64[N]).  Asynchronous.
     Returns records[G, p + 11], or (records, inference[G, 5 p]) with inference=True; with a threshold (binomial, through
     anofox_hip_glm_fit_accuracy_batch_device) accuracy[G] is appended."""
-    import torch
-
-    p, G, N = len(x_cols), int(row_offsets.numel()) - 1, int(y.numel())
-    tensors = (row_offsets, y, *x_cols) + (() if offset is None else (offset,))
-    for t in tensors:
-        if not t.is_cuda or not t.is_contiguous():
-            raise ValueError("device batch needs contiguous CUDA tensors")
-    if row_offsets.dtype != torch.int64 or any(t.dtype != torch.float64 for t in tensors[1:]):
-        raise ValueError("row_offsets must be int64 and data float64")
-    if any(int(t.numel()) != N for t in tensors[1:]):
-        raise ValueError("every column must have y's length")
-    rec = torch.empty((G, p + 11), dtype=torch.float64, device=y.device)
-    inf = torch.empty((G, 5 * p), dtype=torch.float64, device=y.device) if inference else None
-    if use_current_torch_stream:
-        ctx.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
-    cols = (C.c_void_p * max(p, 1))(*[c.data_ptr() for c in x_cols])
-    err = _abi.AnofoxError()
-    head = (ctx._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols,
-            C.c_void_p(offset.data_ptr()) if offset is not None else None, options)
-    out = (C.c_void_p(rec.data_ptr()), C.c_void_p(inf.data_ptr()) if inf is not None else None)
-    if threshold is None:
-        ok = ctx._lib.anofox_hip_glm_fit_batch_device(*head, *out, C.byref(err))
-    else:
-        acc = torch.empty((G,), dtype=torch.float64, device=y.device)
-        ok = ctx._lib.anofox_hip_glm_fit_accuracy_batch_device(*head, float(threshold), *out, C.c_void_p(acc.data_ptr()), C.byref(err))
-    ctx._check(ok, err)
-    res = (rec, inf) if inference else (rec,)
-    if threshold is not None:
-        res += (acc,)
-    return res if len(res) > 1 else rec
+    return _glm_fit(DeviceBatch(ctx, row_offsets, y, x_cols, use_current_torch_stream), options, offset, inference, threshold)
 
 
 def glm_fit_predict_batch_device(ctx, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, offset=None,
@@ -131,31 +82,7 @@ def glm_fit_predict_batch_device(ctx, row_offsets, y, x_cols: Sequence, options:
     """GLM fit + predict on CUDA tensors (inputs as glm_fit_batch_device; train_counts int64[G] or None).  Asynchronous.
     Returns (core[G, p + 11], pred[N, 3]); rows outside [row_offsets[0], row_offsets[G]) are not written.  With interval_z the
     call goes through anofox_hip_glm_fit_predict_interval_batch_device."""
-    import torch
-
-    p, G, N = len(x_cols), int(row_offsets.numel()) - 1, int(y.numel())
-    data = (y, *x_cols) + (() if offset is None else (offset,))
-    ints = (row_offsets,) + (() if train_counts is None else (train_counts,))
-    for t in data + ints:
-        if not t.is_cuda or not t.is_contiguous():
-            raise ValueError("device batch needs contiguous CUDA tensors")
-    if any(t.dtype != torch.int64 for t in ints) or any(t.dtype != torch.float64 for t in data):
-        raise ValueError("row_offsets / train_counts must be int64 and data float64")
-    if any(int(t.numel()) != N for t in data) or (train_counts is not None and int(train_counts.numel()) != G):
-        raise ValueError("every column must have y's length and train_counts one entry per group")
-    core = torch.empty((G, p + 11), dtype=torch.float64, device=y.device)
-    pred = torch.empty((N, 3), dtype=torch.float64, device=y.device)
-    if use_current_torch_stream:
-        ctx.set_stream(torch.cuda.current_stream(y.device).cuda_stream)
-    cols = (C.c_void_p * max(p, 1))(*[c.data_ptr() for c in x_cols])
-    err = _abi.AnofoxError()
-    fn = ctx._lib.anofox_hip_glm_fit_predict_batch_device if interval_z is None else ctx._lib.anofox_hip_glm_fit_predict_interval_batch_device
-    ok = fn(ctx._h, G, p, N, C.c_void_p(row_offsets.data_ptr()), C.c_void_p(y.data_ptr()), cols,
-            C.c_void_p(offset.data_ptr()) if offset is not None else None,
-            C.c_void_p(train_counts.data_ptr()) if train_counts is not None else None, options,
-            *(() if interval_z is None else (float(interval_z),)), C.c_void_p(core.data_ptr()), C.c_void_p(pred.data_ptr()), C.byref(err))
-    ctx._check(ok, err)
-    return core, pred
+    return _glm_fit_predict(DeviceBatch(ctx, row_offsets, y, x_cols, use_current_torch_stream), options, offset, train_counts, interval_z)
 
 
 @dataclass
@@ -280,14 +207,16 @@ def _scalar(fn_name, opt_struct, y, x, extras=False):
         a, k = _data_array(col)
         xs[j] = a
         keep.append(k)
-    core, inf, ex, err = _abi.AnofoxGlmFitResultCore(), _abi.AnofoxFitResultInference(), _abi.AnofoxLogisticFitExtras(), _abi.AnofoxError()
+    core, inf, ex = _abi.AnofoxGlmFitResultCore(), _abi.AnofoxFitResultInference(), _abi.AnofoxLogisticFitExtras()
     args = [ya, xs, len(x), opt_struct, C.byref(core), C.byref(inf) if opt_struct.compute_inference else None]
     if extras:
         args.append(C.byref(ex))
-    if not getattr(lib, fn_name)(*args, C.byref(err)):
-        e = InvalidInputException(f"GLM fit failed: {err.text()}")
-        e.code = err.code
-        raise e
+    try:
+        call(lib, fn_name, *args)
+    except AnofoxStatsError as failed:
+        e = InvalidInputException(f"GLM fit failed: {failed}")
+        e.code = failed.code
+        raise e from None
     try:
         p = core.coefficients_len
         d = {"coefficients": [core.coefficients[i] for i in range(p)], "intercept": core.intercept, "deviance": core.deviance,
