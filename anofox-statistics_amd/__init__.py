@@ -36,7 +36,10 @@ from .runtime import (AggState, Context, quantile_fit_predict_window_host, quant
                       fit_predict_batch_host, fit_predict_expanding_host, fit_predict_window_host, vif_batch_host,
                       residuals_batch_host)
 from .glm import (GlmFitAggResult, binomial_fit_agg, glm_fit_batch_device, glm_fit_batch_host, glm_fit_predict_batch_device, glm_fit_predict_batch_host,  # noqa: E402
-                  logistic_fit, logistic_fit_agg, poisson_fit, poisson_fit_agg, poisson_fit_predict_agg)
+                  logistic_fit, logistic_fit_agg, poisson_fit, poisson_fit_agg, poisson_fit_predict_agg,
+                  GlmFitPredictResult, binomial_fit_predict, logistic_fit_predict, poisson_fit_predict, glm_fit_predict_window_host,
+                  glm_fit_predict_frames_host, glm_fit_predict_window_device, glm_fit_predict_frames_device, glm_window_plan,
+                  glm_window_stats, glm_window_test_hooks)
 from .options import GlmOptions, parse_binomial_options, parse_poisson_options  # noqa: E402
 from .scalar import quantile_fit, quantile_fit_path, aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
@@ -52,6 +55,9 @@ SQL_FUNCTIONS.update({
     "anofox_stats_quantile_fit_path": quantile_fit_path, "quantile_fit_path": quantile_fit_path,
     "anofox_stats_poisson_fit": poisson_fit, "poisson_fit": poisson_fit,
     "anofox_stats_logistic_fit": logistic_fit, "logistic_fit": logistic_fit,
+    "anofox_stats_poisson_fit_predict": poisson_fit_predict, "poisson_fit_predict": poisson_fit_predict,
+    "anofox_stats_logistic_fit_predict": logistic_fit_predict, "logistic_fit_predict": logistic_fit_predict,
+    "anofox_stats_binomial_fit_predict": binomial_fit_predict, "binomial_fit_predict": binomial_fit_predict,
     "anofox_stats_predict": predict,
     "anofox_stats_aic": aic, "aic": aic, "anofox_stats_bic": bic, "bic": bic,
     "anofox_stats_vif": vif, "vif": vif,
@@ -87,6 +93,9 @@ __all__ = [
     "GlmOptions", "parse_poisson_options", "parse_binomial_options", "GlmFitAggResult", "poisson_fit_agg", "binomial_fit_agg",
     "logistic_fit_agg", "poisson_fit_predict_agg", "poisson_fit", "logistic_fit", "glm_fit_batch_host",
     "glm_fit_predict_batch_host", "glm_fit_batch_device", "glm_fit_predict_batch_device",
+    "GlmFitPredictResult", "poisson_fit_predict", "logistic_fit_predict", "binomial_fit_predict", "glm_fit_predict_window_host",
+    "glm_fit_predict_frames_host", "glm_fit_predict_window_device", "glm_fit_predict_frames_device", "glm_window_plan",
+    "glm_window_stats", "glm_window_test_hooks",
 ]
 
 

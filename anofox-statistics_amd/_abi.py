@@ -451,6 +451,23 @@ SYMBOLS = {
     "anofox_hip_glm_fit_accuracy_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
                                                           C.POINTER(_DP), _DP, AnofoxHipGlmBatchOptions, C.c_double, _DP, _DP, _DP,
                                                           _ERRP]),
+    "anofox_hip_glm_fit_predict_window_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                            C.POINTER(C.c_void_p), C.c_void_p, AnofoxHipWindowFrame,
+                                                            AnofoxHipGlmBatchOptions, C.c_double, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_glm_fit_predict_window_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                          C.POINTER(_DP), _DP, AnofoxHipWindowFrame, AnofoxHipGlmBatchOptions,
+                                                          C.c_double, _DP, _DP, _ERRP]),
+    "anofox_hip_glm_fit_predict_frames_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p),
+                                                            C.c_void_p, C.c_void_p, C.c_void_p, AnofoxHipGlmBatchOptions, C.c_double,
+                                                            C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_glm_fit_predict_frames_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, _DP, C.POINTER(_DP), _DP,
+                                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), AnofoxHipGlmBatchOptions,
+                                                          C.c_double, _DP, _DP, _ERRP]),
+    "anofox_hip_glm_window_plan": (C.c_bool, [C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64),
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ERRP]),
+    "anofox_hip_glm_window_test_hooks": (None, [C.c_int64, C.c_int64, C.c_int]),
+    "anofox_hip_glm_window_stats": (C.c_bool, [_CTX, C.POINTER(C.c_int64), _ERRP]),
     "anofox_poisson_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxPoissonOptions,
                                       C.POINTER(AnofoxGlmFitResultCore), C.POINTER(AnofoxFitResultInference), _ERRP]),
     "anofox_binomial_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxBinomialOptions,

@@ -47,6 +47,12 @@ struct AnofoxHipContext {
 	size_t qw_counts_bytes = 0;
 	int64_t qw_frames = 0, qw_walkers = 0, qw_waves = 0, qw_span = 0;
 	bool qw_valid = false;
+	// the GLM window function's last launch on this context (glm_window.hip): per walker {frames started cold, started warm,
+	// warm frames refitted cold, IRLS iterations} as int64 in a buffer of its own; reset by every GLM window call
+	void *gw_counts = nullptr;
+	size_t gw_counts_bytes = 0;
+	int64_t gw_frames = 0, gw_walkers = 0, gw_waves = 0, gw_span = 0;
+	bool gw_valid = false;
 	// timing
 	bool timing = false;
 	std::vector<hipEvent_t> free_events;
@@ -87,6 +93,9 @@ SolveStages elasticnet_state_stages(EnParams *en);
 bool bls_state_options(const AnofoxHipBlsBatchOptions &o, AnofoxError *e);
 BlsParamsT<kWideMaxP> bls_state_params(const AnofoxHipBlsBatchOptions &o, size_t p);
 SolveStages bls_state_stages(BlsParamsT<kWideMaxP> *bp);
+// glm.hip: the GLM family's option and interval checks, for its window function (glm_window.hip)
+bool glm_options_invalid(const AnofoxHipGlmBatchOptions &o);
+bool glm_check_interval(const AnofoxHipGlmBatchOptions &o, double z, AnofoxError *e);
 // host_api.hip: the predict kernels on fit records in the regression layout, enqueued on the context's stream; the caller
 // holds ctx->mu (a family that fits outside the moment path — quantile.hip — keeps one lock over fit and predict)
 bool predict_records_locked(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *d_row_offsets,

@@ -29,6 +29,32 @@ using namespace anofox;
 using namespace anofox::host;
 using namespace anofox::glm;
 
+// shared with glm_window.hip (declared in context.h)
+namespace anofox {
+namespace host {
+
+bool glm_options_invalid(const AnofoxHipGlmBatchOptions &o) {
+	if (o.family != ANOFOX_HIP_GLM_POISSON && o.family != ANOFOX_HIP_GLM_BINOMIAL) return true;
+	if (!(o.tolerance > 0.0) || !isfinite(o.tolerance)) return true;
+	if (!(o.lambda >= 0.0) || !isfinite(o.lambda)) return true;
+	if (o.max_iterations == 0) return true;
+	if (o.compute_inference && !(o.confidence_level > 0.0 && o.confidence_level < 1.0)) return true;
+	return false;
+}
+
+// the interval entry: z = 0 is the plain fit-predict; the bounds are the Poisson family's
+bool glm_check_interval(const AnofoxHipGlmBatchOptions &o, double z, AnofoxError *e) {
+	if (!(z >= 0.0) || !isfinite(z)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: interval_z must be finite and not negative"); return false; }
+	if (z > 0.0 && o.family == ANOFOX_HIP_GLM_BINOMIAL) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: the prediction interval of the binomial family is not built");
+		return false;
+	}
+	return true;
+}
+
+} // namespace host
+} // namespace anofox
+
 namespace {
 
 struct GlmArgs {
@@ -129,15 +155,6 @@ double normal_quantile(double prob) {
 	return x;
 }
 
-bool options_invalid(const AnofoxHipGlmBatchOptions &o) {
-	if (o.family != ANOFOX_HIP_GLM_POISSON && o.family != ANOFOX_HIP_GLM_BINOMIAL) return true;
-	if (!(o.tolerance > 0.0) || !isfinite(o.tolerance)) return true;
-	if (!(o.lambda >= 0.0) || !isfinite(o.lambda)) return true;
-	if (o.max_iterations == 0) return true;
-	if (o.compute_inference && !(o.confidence_level > 0.0 && o.confidence_level < 1.0)) return true;
-	return false;
-}
-
 bool check_glm(int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols, const void *out,
                AnofoxError *e) {
 	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
@@ -172,7 +189,7 @@ bool launch_glm(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, cons
 	a.max_iterations = o.max_iterations > 0x7fffffffu ? 0x7fffffff : (int)o.max_iterations;
 	a.tolerance = o.tolerance;
 	a.lambda = o.lambda;
-	a.invalid = options_invalid(o) ? 1 : 0;
+	a.invalid = glm_options_invalid(o) ? 1 : 0;
 	a.compute_inference = o.compute_inference && d_inf ? 1 : 0;
 	a.zq = a.compute_inference && !a.invalid ? normal_quantile(0.5 + o.confidence_level / 2.0) : NAN;
 	a.rule = rule;
@@ -223,16 +240,6 @@ bool glm_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows,
 	if (inf && !d2h(inf, d_inf, G * 5 * p * sizeof(double), st, e)) return false;
 	if (pred && !d2h(pred, d_pred, 3 * N * sizeof(double), st, e)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", e);
-}
-
-// the interval entry: z = 0 is the plain fit-predict; the bounds are the Poisson family's
-bool check_interval(const AnofoxHipGlmBatchOptions &o, double z, AnofoxError *e) {
-	if (!(z >= 0.0) || !isfinite(z)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: interval_z must be finite and not negative"); return false; }
-	if (z > 0.0 && o.family == ANOFOX_HIP_GLM_BINOMIAL) {
-		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: the prediction interval of the binomial family is not built");
-		return false;
-	}
-	return true;
 }
 
 bool check_accuracy(const AnofoxHipGlmBatchOptions &o, double threshold, AnofoxError *e) {
@@ -321,7 +328,7 @@ bool scalar_glm_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count,
 	o.lambda = so.lambda;
 	o.compute_inference = so.compute_inference && out_inference;
 	o.confidence_level = so.confidence_level;
-	if (options_invalid(o)) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, std::string("glm: invalid options for ") + so.name); return false; }
+	if (glm_options_invalid(o)) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, std::string("glm: invalid options for ") + so.name); return false; }
 	const int64_t off[2] = {0, (int64_t)n};
 	std::vector<double> rec(p + 11), inf(5 * p), pred(so.binary_y && out_extras ? 3 * n : 0);
 	const bool want_pred = !pred.empty();
@@ -460,7 +467,7 @@ bool anofox_hip_glm_fit_predict_interval_batch_device(AnofoxHipContext *ctx, int
                                                       AnofoxHipGlmBatchOptions options, double interval_z, double *d_core, double *d_pred,
                                                       AnofoxError *out_error) {
 	reset_error(out_error);
-	if (!check_interval(options, interval_z, out_error)) return false;
+	if (!glm_check_interval(options, interval_z, out_error)) return false;
 	if (!check_glm(n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_core, out_error)) return false;
 	if (n_groups > 0 && !d_pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
 	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
@@ -477,7 +484,7 @@ bool anofox_hip_glm_fit_predict_interval_batch_host(AnofoxHipContext *ctx, int64
                                                     const double *offset, const int64_t *train_counts, AnofoxHipGlmBatchOptions options,
                                                     double interval_z, double *core, double *pred, AnofoxError *out_error) {
 	reset_error(out_error);
-	if (!check_interval(options, interval_z, out_error)) return false;
+	if (!glm_check_interval(options, interval_z, out_error)) return false;
 	if (!check_glm(n_groups, n_features, n_rows, row_offsets, y, x_cols, core, out_error)) return false;
 	if (n_groups > 0 && !pred) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
 	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;

@@ -18,6 +18,9 @@
 //              to 10 halvings of the step while obj > obj_old + 1e-7 |obj_old| + eps (max(scale, 1) + 8 (n + sum y)),
 //              scale = |null deviance|, the last term the rounding of the deviance's own sum (the first iteration's obj_old
 //              is the deviance at mustart, which no beta attains: nothing to halve against).
+//   warm start P.start = k carried coefficients: the first pass takes eta = a_i'start + offset and mu from it instead of mustart,
+//              obj_old of the first iteration is the objective at `start`, and the step may be halved from the first iteration.
+//              The minimiser is the problem's, so the start changes the path and not the answer (gi_fit_window).
 //   Gram       the augmented matrix [X z]'W[X z], (k + 1)(k + 2) / 2 sums (595 at k = 33), by LANES OVER MATRIX ENTRIES ON A
 //              ROW TILE STAGED IN LDS: the 64 lanes stage 64 rows {a_i, z_i, w_i} (each lane its own row), then every lane
 //              adds the tile's rows, in row order, into the entries it owns, which stay in registers (ceil(595 / 64) = 10 at
@@ -110,6 +113,8 @@ struct GiProblem {
 	double interval_z = 0.0;    // fit-predict, Poisson: > 0 fills pred[3 i + 1], pred[3 i + 2] with the bounds; 0: they stay NaN
 	double threshold = 0.5;     // accuracy: a row is classified 1 when mu >= threshold
 	double *accuracy = nullptr; // binomial: where the group's training accuracy goes (NaN for a failed group), or nullptr
+	// a warm start (gi_fit_window): k carried coefficients in the order of a_i, all finite; nullptr: the cold start at mustart
+	const double *start = nullptr;
 };
 
 template <class T>
@@ -466,9 +471,18 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 			for (int j = 0; ok && j < p; ++j) ok = gi_finite(P.x[j][i]);
 			if (ok && P.offset) ok = gi_finite(P.offset[i]);
 			if (ok) {
-				const double m0 = P.family == kGiFamilyPoisson ? y + 0.1 : (y + 0.5) / 2.0;
-				P.mu[i] = m0;
-				P.eta[i] = P.family == kGiFamilyPoisson ? log(m0) : log(m0 / (1.0 - m0));
+				if (P.start) { // eta and mu at the carried coefficients, as gi_update writes them
+					double eta = P.offset ? P.offset[i] : 0.0, mu, q, lmu, lq;
+					GI_NOUNROLL
+					for (int cc = 0; cc < k; ++cc) eta += gi_elem(P, cc, i) * P.start[cc];
+					gi_inverse_link(P.family, eta, mu, q, lmu, lq);
+					P.eta[i] = eta;
+					P.mu[i] = mu == mu ? mu : 1.0;
+				} else {
+					const double m0 = P.family == kGiFamilyPoisson ? y + 0.1 : (y + 0.5) / 2.0;
+					P.mu[i] = m0;
+					P.eta[i] = P.family == kGiFamilyPoisson ? log(m0) : log(m0 / (1.0 - m0));
+				}
 				++c;
 				s += y;
 				if (i < f) f = i;
@@ -517,7 +531,7 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 		gi_nan_accuracy(P);
 		return;
 	}
-	// ---- the start: objective at mustart (beta = 0), the null deviance at mu = ybar ----
+	// ---- the start: objective at mustart (beta = 0) or at the carried coefficients, the null deviance at mu = ybar ----
 	double obj, null_dev;
 	{
 		GiPL<double> d0, dn;
@@ -549,6 +563,7 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 		GI_LANES_END
 		obj = gi_sum(d0);
 		null_dev = gi_sum(dn);
+		if (P.start) obj += gi_penalty(P, k, P.start);
 	}
 	// ---- which entries of the augmented Gram matrix each lane owns ----
 	const int T = (k + 1) * (k + 2) / 2;
@@ -575,7 +590,7 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 	}
 	GI_LANES_END
 	GI_LANES_BEGIN(lane)
-	if (lane <= k) beta[lane] = beta_old[lane] = 0.0;
+	if (lane <= k) beta[lane] = beta_old[lane] = P.start && lane < k ? P.start[lane] : 0.0;
 	GI_LANES_END
 	gi_sync();
 	// ---- the loop ----
@@ -607,7 +622,8 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 		}
 		// (not on the first iteration: its obj_old is the deviance at mustart, nearly the saturated fit, which no beta attains;
 		// every first step is "worse" than it, and ten halvings towards beta = 0 strand a fit with large counts)
-		if (it > 0 && gi_finite(obj) && gi_finite(obj_old)) {
+		// (a warm start's obj_old is the objective at the carried coefficients, which a beta attains: it halves from the first step)
+		if ((it > 0 || P.start) && gi_finite(obj) && gi_finite(obj_old)) {
 			int halvings = 0;
 			while (obj > obj_old + 1e-7 * fabs(obj_old) + floor_ && halvings < kGiMaxHalvings) {
 				++halvings;
@@ -762,6 +778,129 @@ GI_DEV void gi_fit(const GiProblem &P, bool invalid, double *work, double *rec, 
 GI_HD int gi_entry_class(int k) {
 	const int e = gi_entries_per_lane(k);
 	return e <= 1 ? 1 : (e <= 4 ? 4 : 10);
+}
+
+// ---- the window walk: one wavefront fits the frames of a run of consecutive output rows, one after the other ----
+// doubles of work memory of a walk: gi_fit's, then the frame's record (p + 11) and the carried coefficients (k + 1)
+GI_HD size_t gi_window_work_doubles(int p, int k) { return gi_work_doubles(k) + (size_t)(p + 11) + (size_t)(k + 1); }
+
+// the largest |eta| of a fit whose coefficients are carried, and of a warm-started fit that is kept: beyond it the clamps of
+// gi_inverse_link come into play, the objective is flat, and a start there can "converge" where it stands
+constexpr double kGiWarmEtaMax = 30.0;
+
+// max |eta| over the valid rows of the scratch (after a fit that converged: every one of them is finite)
+GI_DEV double gi_max_abs_eta(const GiProblem &P) {
+	GiPL<double> part;
+	GI_LANES_BEGIN(lane)
+	double m = 0.0;
+	for (int64_t i = P.lo + lane; i < P.hi; i += 64)
+		if (P.mu[i] == P.mu[i] && !(fabs(P.eta[i]) <= m)) m = fabs(P.eta[i]);
+	part.v[GI_AT(lane)] = m;
+	GI_LANES_END
+	return gi_max(part);
+}
+
+constexpr int kGiStartCold = 0, kGiStartWarm = 1, kGiStartRefit = 2; // how a frame was started (gi_fit_window's `started`)
+
+// The frames [flo[e], fhi[e]) of the output rows e = e0 .. e1 - 1 (fhi <= flo: an empty frame).  P: the columns, the options
+// and a slab of 2 x slab_rows doubles in P.eta (eta of the frame's row i sits in slot i - lo, mu slab_rows further on; only
+// the current frame's are live, every fit writes them before it reads them).  Per output row: pred[3 e] = {mu, lower, upper}
+// at the frame's last row (the bounds as gi_fit's, with P.interval_z), and, with `records`, the frame's record.
+//   cold   a frame is fitted by gi_fit from mustart when `warm` is off, when it is the first of the run, when the previous
+//          frame failed, was empty, left a NaN (dropped or aliased) coefficient or an |eta| above kGiWarmEtaMax (a fit near
+//          separation), when a bound is below the previous frame's, or when it does not overlap the previous frame;
+//   warm   every other frame starts from the previous frame's coefficients (P.start);
+//   refit  a warm-started frame that ends without convergence, with a NaN coefficient or with an |eta| above kGiWarmEtaMax is
+//          fitted again cold: a record with a failure, a skipped column or a saturated row is always the cold fit's, so a warm
+//          start never makes a NULL of its own, and never stops in the flat part of the objective where it began.
+// counts (lane 0's, added to): {frames started cold, started warm, warm frames refitted cold, IRLS iterations (a fit that
+// did not converge counts max_iterations)}.  started (optional): per output row one of kGiStart*.
+template <int EM>
+GI_DEV void gi_fit_window(GiProblem P, bool invalid, bool warm, const int64_t *flo, const int64_t *fhi, int64_t e0, int64_t e1,
+                          int64_t slab_rows, double *work, double *pred, double *records, int64_t *counts, int32_t *started) {
+	const int p = P.p, k = p + (P.fit_intercept ? 1 : 0), ic = P.fit_intercept ? 1 : 0;
+	const double *beta = work + (size_t)(k + 1) * gi_aug_ld(k) + 64 * (size_t)gi_tile_ld(k); // where gi_fit leaves its coefficients
+	double *rec = work + gi_work_doubles(k), *carry = rec + (p + 11);
+	double *slab = P.eta;
+	bool have = false; // carry holds the coefficients of the frame [plo, phi), all of them finite
+	int64_t plo = 0, phi = 0, n_cold = 0, n_warm = 0, n_refit = 0, n_iter = 0;
+	for (int64_t e = e0; e < e1; ++e) {
+		int64_t lo = flo[e], hi = fhi[e];
+		if (hi <= lo) lo = hi = 0; // an empty frame, whatever its bounds are
+		const bool fits = hi - lo <= slab_rows; // (the planner sizes the slab by the longest frame: always true)
+		const bool use = warm && have && fits && hi > lo && lo >= plo && hi >= phi && lo < phi;
+		GiPL<int64_t> rule;
+		GI_LANES_BEGIN(lane)
+		int64_t c = 0;
+		for (int64_t i = lo + lane; i < hi; i += 64) c += P.y[i] == P.y[i] ? 1 : 0;
+		rule.v[GI_AT(lane)] = c;
+		GI_LANES_END
+		P.lo = lo;
+		P.hi = hi;
+		P.rule_count = gi_sum_i(rule);
+		P.eta = slab - lo;
+		P.mu = slab + slab_rows - lo;
+		P.start = use ? carry : nullptr;
+		int kind = use ? kGiStartWarm : kGiStartCold;
+		gi_fit<EM>(P, invalid || !fits, work, rec, nullptr, nullptr);
+		gi_sync(); // (a failed fit returns right after it has written the record)
+		bool nan_coef = false;
+		for (int j = 0; j < p + ic; ++j) nan_coef = nan_coef || !(rec[j] == rec[j]);
+		int status = (int)rec[p + 10];
+		double eta_max = status == 0 ? gi_max_abs_eta(P) : 0.0;
+		if (use) {
+			n_iter += status == 0 ? (int64_t)rec[p + 8] : (status == kGiStatusConvergence ? P.max_iterations : 0);
+			if (status == kGiStatusConvergence || (status == 0 && (nan_coef || !(eta_max <= kGiWarmEtaMax)))) {
+				kind = kGiStartRefit;
+				P.start = nullptr;
+				gi_sync();
+				gi_fit<EM>(P, invalid, work, rec, nullptr, nullptr);
+				gi_sync();
+				nan_coef = false;
+				for (int j = 0; j < p + ic; ++j) nan_coef = nan_coef || !(rec[j] == rec[j]);
+				status = (int)rec[p + 10];
+				eta_max = status == 0 ? gi_max_abs_eta(P) : 0.0;
+			}
+		}
+		if (kind != kGiStartWarm) n_iter += status == 0 ? (int64_t)rec[p + 8] : (status == kGiStatusConvergence ? P.max_iterations : 0);
+		n_cold += kind == kGiStartCold;
+		n_warm += kind != kGiStartCold;
+		n_refit += kind == kGiStartRefit;
+		have = status == 0 && !nan_coef && eta_max <= kGiWarmEtaMax;
+		plo = lo;
+		phi = hi;
+		GI_LANES_BEGIN(lane)
+		if (have && lane < k) carry[lane] = beta[lane];
+		if (records)
+			for (int j = lane; j < p + 11; j += 64) records[e * (int64_t)(p + 11) + j] = rec[j];
+		if (lane == 0) {
+			double mu = NAN, lower = NAN, upper = NAN;
+			if (status == 0) {
+				double eta;
+				mu = gi_row_mu(P, k, beta, hi - 1, eta);
+				if (P.interval_z > 0.0 && P.family == kGiFamilyPoisson && gi_finite(mu)) { // gi_fit's bounds
+					const double h = P.interval_z * sqrt(rec[p + 5]) / (mu > 0.001 ? mu : 0.001);
+					lower = exp(eta - h);
+					upper = exp(eta + h);
+					if (!(lower > 0.0)) lower = 0.0;
+				}
+			}
+			pred[3 * e] = mu;
+			pred[3 * e + 1] = lower;
+			pred[3 * e + 2] = upper;
+			if (started) started[e] = kind;
+		}
+		GI_LANES_END
+		gi_sync(); // the next frame's fit overwrites the record and the coefficients
+	}
+	GI_LANES_BEGIN(lane)
+	if (lane == 0) {
+		counts[0] += n_cold;
+		counts[1] += n_warm;
+		counts[2] += n_refit;
+		counts[3] += n_iter;
+	}
+	GI_LANES_END
 }
 
 } // namespace glm

@@ -510,6 +510,7 @@ void anofox_hip_context_destroy(AnofoxHipContext *ctx) {
 	if (ctx->aux) (void)hipFree(ctx->aux);
 	if (ctx->wtab) (void)hipFree(ctx->wtab);
 	if (ctx->qw_counts) (void)hipFree(ctx->qw_counts);
+	if (ctx->gw_counts) (void)hipFree(ctx->gw_counts);
 	for (auto &pr : ctx->predict_events) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
 	if (ctx->solve_stream) {
 		(void)hipStreamSynchronize(ctx->solve_stream);

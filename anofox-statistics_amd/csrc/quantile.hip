@@ -35,6 +35,7 @@
 using namespace anofox;
 
 #include "host_stage.h"
+#include "window_plan.h"
 #include "row_slabs.h"
 
 using namespace anofox::host;
@@ -287,18 +288,12 @@ bool fill_scalar_result(const double *rec, size_t p, AnofoxQuantileFitResultCore
 }
 
 // ---- the window function ----
-// The planner.  Walkers: every partition is cut into runs of consecutive output rows, min(ceil(n_g / L), n_g / kQwMinRun) of
-// them (at least one) of equal length (the last one shorter), L = ceil(n_rows / kQwTargetWalkers): with many partitions a run
-// is a whole partition, with few long ones there are about kQwTargetWalkers walkers, and no run is shorter than kQwMinRun
-// rows unless its partition is (every run begins with a cold fit, which the rows after it have to pay for).  A partition all of whose frames start at the same
-// row (UNBOUNDED PRECEDING) is one run: every run of it would span the partition anyway.  span = the longest
+// The planner.  cut_window_runs (window_plan.h) cuts the partitions into the walkers' runs.  span = the longest
 // chain of a run (last hi - first lo of consecutive monotone, overlapping frames); a launched wavefront owns 3 span doubles, and
 // waves = min(runs, kQwMaxWaves, cap / (24 span)): the scratch never exceeds the cap (kQwScratchCap unless a test sets
 // another), and a span that does not fit once fails the call.
-constexpr int64_t kQwMinRun = 64;
-constexpr int64_t kQwTargetWalkers = 8192;
-constexpr int64_t kQwMaxWaves = 8192;
-constexpr int64_t kQwScratchCap = 1ll << 30;
+constexpr int64_t kQwMaxWaves = kWalkMaxWaves;
+constexpr int64_t kQwScratchCap = kWalkScratchCap;
 
 std::mutex g_qw_mu;
 int64_t g_qw_run_length = 0, g_qw_scratch_cap = 0; // anofox_hip_quantile_window_test_hooks (0: the rule above)
@@ -310,38 +305,11 @@ struct WindowPlan {
 
 bool plan_window(int64_t n_parts, const int64_t *off, const int64_t *lo, const int64_t *hi, int64_t run_length, int64_t cap_bytes,
                  WindowPlan &plan, AnofoxError *e) {
-	plan.run_begin.clear();
 	plan.span = plan.waves = 0;
-	const int64_t N = n_parts > 0 ? off[n_parts] - off[0] : 0;
 	if (cap_bytes <= 0) cap_bytes = kQwScratchCap;
-	int64_t L = run_length;
-	if (L <= 0) {
-		L = (N + kQwTargetWalkers - 1) / kQwTargetWalkers;
-		if (L < 1) L = 1;
-	}
-	for (int64_t g = 0; g < n_parts; ++g) {
-		const int64_t b = off[g], n = off[g + 1] - b;
-		if (n <= 0) continue;
-		int64_t pieces = (n + L - 1) / L;
-		if (run_length <= 0 && pieces > n / kQwMinRun) pieces = n / kQwMinRun > 0 ? n / kQwMinRun : 1; // no run below kQwMinRun rows
-		if (run_length <= 0 && pieces > 1) { // frames that all start at one row: one walker
-			int64_t first = -1;
-			bool same = true;
-			for (int64_t r = b; r < b + n && same; ++r) {
-				if (hi[r] <= lo[r]) continue;
-				if (first < 0) first = lo[r];
-				same = lo[r] == first;
-			}
-			if (same) pieces = 1;
-		}
-		const int64_t len = (n + pieces - 1) / pieces;
-		for (int64_t r = b; r < b + n; r += len) plan.run_begin.push_back(r);
-	}
-	const int64_t runs = (int64_t)plan.run_begin.size();
-	plan.run_begin.push_back(n_parts > 0 ? off[n_parts] : 0);
+	cut_window_runs(n_parts, off, lo, hi, run_length, plan.run_begin);
+	const int64_t runs = (int64_t)plan.run_begin.size() - 1;
 	if (runs == 0) return true;
-	// (a run ends where the next begins or at its partition's end: the runs are contiguous over the partitions' rows, and an
-	// empty partition owns none)
 	// the walk sets its scratch origin wherever it begins afresh, so a slab has to hold the longest CHAIN of a run: consecutive
 	// non-empty frames whose bounds are both non-decreasing and that overlap (qs_fit_window's rule; a basis row that leaves or
 	// a failed frame only cuts a chain shorter).  Unsorted or far-apart explicit frames therefore cost no scratch.
@@ -367,45 +335,6 @@ bool plan_window(int64_t n_parts, const int64_t *off, const int64_t *lo, const i
 	}
 	plan.waves = runs < kQwMaxWaves ? runs : kQwMaxWaves;
 	if (fit < plan.waves) plan.waves = fit;
-	return true;
-}
-
-// the frames of ROWS BETWEEN start PRECEDING AND end PRECEDING, clipped to the partition: frames_spec_kernel's arithmetic
-void rows_frames(int64_t G, const int64_t *off, const AnofoxHipWindowFrame &f, int64_t *lo, int64_t *hi) {
-	for (int64_t g = 0; g < G; ++g) {
-		const int64_t plo = off[g], phi = off[g + 1];
-		for (int64_t r = plo; r < phi; ++r) {
-			int64_t first = f.start_preceding == ANOFOX_HIP_FRAME_UNBOUNDED ? plo : r - f.start_preceding;
-			int64_t last = f.end_preceding == -ANOFOX_HIP_FRAME_UNBOUNDED ? phi - 1 : r - f.end_preceding;
-			if (first < plo) first = plo;
-			if (last > phi - 1) last = phi - 1;
-			const bool empty = last < first;
-			lo[r] = empty ? r : first;
-			hi[r] = empty ? r : last + 1;
-		}
-	}
-}
-
-bool check_window_frame(const AnofoxHipWindowFrame &f, AnofoxError *e) {
-	if (f.start_preceding < f.end_preceding || f.start_preceding == -ANOFOX_HIP_FRAME_UNBOUNDED || f.end_preceding == ANOFOX_HIP_FRAME_UNBOUNDED) {
-		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "window frame must start at or before its end");
-		return false;
-	}
-	return true;
-}
-
-bool check_window_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {
-	// (the whole range: every output row belongs to a partition's walker)
-	return check_host_offsets(G, n_rows, off, e) && check_whole_range(G, n_rows, off, e);
-}
-
-bool check_host_frames(int64_t n_rows, const int64_t *lo, const int64_t *hi, AnofoxError *e) {
-	for (int64_t r = 0; r < n_rows; ++r) {
-		if (hi[r] > lo[r] && (lo[r] < 0 || hi[r] > n_rows)) {
-			set_error(e, ANOFOX_ERROR_INVALID_INPUT, "frame bounds must lie within [0, n_rows]");
-			return false;
-		}
-	}
 	return true;
 }
 

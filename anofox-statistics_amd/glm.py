@@ -1,7 +1,8 @@
 """Generalised linear models on the fused IRLS kernel (csrc/glm.hip): poisson_fit_agg, binomial_fit_agg, logistic_fit_agg,
 poisson_fit_predict_agg, the scalar poisson_fit / logistic_fit, and the numpy drivers of anofox_hip_glm_fit_batch_host /
-anofox_hip_glm_fit_predict_batch_host and of their interval / accuracy forms.  The contract: DESIGN.md §1 "Generalised linear
-models".  Results mirror the fields of the reference's AnofoxGlmFitResultCore; a group whose status is not 0 is None (SQL NULL)."""
+anofox_hip_glm_fit_predict_batch_host and of their interval / accuracy forms; and the window functions poisson_fit_predict /
+logistic_fit_predict / binomial_fit_predict with the drivers of anofox_hip_glm_fit_predict_{window,frames}_* (csrc/glm_window.hip).
+The contract: DESIGN.md §1 "Generalised linear models".  Results mirror the fields of the reference's AnofoxGlmFitResultCore; a group whose status is not 0 is None (SQL NULL)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,7 +13,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import AnofoxStatsError
-from ._marshal import DeviceBatch, HostBatch, call
+from ._marshal import I64, DeviceBatch, HostBatch, call, handle, host_array
 from .options import GlmOptions, InvalidInputException, parse_binomial_options, parse_poisson_options
 
 def _glm_fit(b, options, offset, inference, threshold):
@@ -83,6 +84,128 @@ def glm_fit_predict_batch_device(ctx, row_offsets, y, x_cols: Sequence, options:
     Returns (core[G, p + 11], pred[N, 3]); rows outside [row_offsets[0], row_offsets[G]) are not written.  With interval_z the
     call goes through anofox_hip_glm_fit_predict_interval_batch_device."""
     return _glm_fit_predict(DeviceBatch(ctx, row_offsets, y, x_cols, use_current_torch_stream), options, offset, train_counts, interval_z)
+
+
+def _glm_window(b, options, offset, interval_z, want_records, frame=None, bounds=None):
+    """pred[N, 3] (and records[N, p + 11] with want_records) of the window function: ROWS frames (`frame`) or explicit `bounds`."""
+    from .runtime import _frame
+    pred = b.out((b.N, 3))
+    rec = b.out((b.N, b.p + 11)) if want_records else None
+    z = 0.0 if interval_z is None else float(interval_z)
+    if bounds is None:
+        b.call("anofox_hip_glm_fit_predict_window", *b.head, b.rows(offset, "offset"), _frame(frame), options, z, pred, rec)
+    else:
+        b.call("anofox_hip_glm_fit_predict_frames", *b.rows_head, b.rows(offset, "offset"), *b.frames(*bounds), options, z, pred, rec)
+    return (pred, rec) if want_records else pred
+
+
+def glm_fit_predict_window_host(row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, frame=(None, 0), offset=None,
+                                interval_z=None, want_records: bool = False, ctx=None):
+    """The GLM window function over ROWS frames, numpy in / out: pred[N, 3] = (mu, lower, upper) at the frame's last row per
+    output row (a NaN mu = NULL), or (pred, records[N, p + 11]) with want_records.  frame = (start, end) in rows PRECEDING the
+    current row (negative = FOLLOWING; None = UNBOUNDED)."""
+    return _glm_window(HostBatch(ctx, row_offsets, y, x_cols), options, offset, interval_z, want_records, frame=frame)
+
+
+def glm_fit_predict_frames_host(y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipGlmBatchOptions, offset=None,
+                                interval_z=None, want_records: bool = False, ctx=None):
+    """The GLM window function over explicit frames [frame_lo[e], frame_hi[e]) of any shape (hi <= lo: an empty frame)."""
+    return _glm_window(HostBatch(ctx, None, y, x_cols), options, offset, interval_z, want_records, bounds=(frame_lo, frame_hi))
+
+
+def glm_fit_predict_window_device(ctx, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, frame=(None, 0),
+                                  offset=None, interval_z=None, want_records: bool = False, use_current_torch_stream: bool = True):
+    """glm_fit_predict_window_host on CUDA tensors.  The offsets are copied to the host for the planner (one synchronising copy);
+    the walk itself is asynchronous."""
+    return _glm_window(DeviceBatch(ctx, row_offsets, y, x_cols, use_current_torch_stream), options, offset, interval_z, want_records,
+                       frame=frame)
+
+
+def glm_fit_predict_frames_device(ctx, y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipGlmBatchOptions, offset=None,
+                                  interval_z=None, want_records: bool = False, use_current_torch_stream: bool = True):
+    """glm_fit_predict_frames_host on CUDA tensors (frame_lo / frame_hi int64[N])."""
+    return _glm_window(DeviceBatch(ctx, None, y, x_cols, use_current_torch_stream), options, offset, interval_z, want_records,
+                       bounds=(frame_lo, frame_hi))
+
+
+def glm_window_plan(row_offsets, frame_lo, frame_hi):
+    """The planner of the GLM window function alone (host arrays, no device), under the test hooks in force: -> (run_begin
+    int64[walkers + 1], scratch rows per wavefront = the longest frame, launched wavefronts)."""
+    off = host_array(row_offsets, I64, None, "row_offsets")
+    lo = host_array(frame_lo, I64, None, "frame_lo")
+    hi = host_array(frame_hi, I64, lo.size, "frame_hi")
+    runs = np.empty(lo.size + 2, dtype=np.int64)
+    n_runs, span, waves = C.c_int64(), C.c_int64(), C.c_int64()
+    call(_abi.load(), "anofox_hip_glm_window_plan", off.size - 1, off, lo.size, lo, hi, runs, runs.size, C.byref(n_runs), C.byref(span),
+         C.byref(waves))
+    return runs[:n_runs.value + 1].copy(), int(span.value), int(waves.value)
+
+
+def glm_window_test_hooks(run_length: int = 0, scratch_cap_bytes: int = 0, warm: bool = True):
+    """For tests and measurements: the run length and the scratch cap of every later GLM window call (0: the library's rule), and
+    whether a frame may start from its predecessor's coefficients (False: every frame starts cold)."""
+    _abi.load().anofox_hip_glm_window_test_hooks(int(run_length), int(scratch_cap_bytes), 1 if warm else 0)
+
+
+def glm_window_stats(ctx=None):
+    """The most recent GLM window call on the context: dict(frames, cold_starts, warm_starts, refits (warm frames fitted again
+    cold), iterations (IRLS iterations summed over the frames), walkers, waves, span_rows)."""
+    out = (C.c_int64 * 8)()
+    call(_abi.load(), "anofox_hip_glm_window_stats", handle(ctx), out)
+    return dict(zip(("frames", "cold_starts", "warm_starts", "refits", "iterations", "walkers", "waves", "span_rows"), (int(v) for v in out)))
+
+
+@dataclass
+class GlmFitPredictResult:
+    """The window functions' result: pred[N, 3] = (mu, yhat_lower, yhat_upper) in the order of the input rows (NaN = NULL)."""
+    pred: np.ndarray
+
+    @property
+    def yhat(self) -> np.ndarray:
+        return self.pred[:, 0]
+
+
+def _fit_predict(partition_keys, order, y, x, opts: GlmOptions, options, frame, context) -> GlmFitPredictResult:
+    from .aggregate import _parse_frame
+    start, end = _parse_frame(frame, 0)
+    keys = np.asarray(partition_keys)
+    yv = np.array([np.nan if v is None else v for v in y], dtype=np.float64) if np.asarray(y).dtype == object else np.asarray(y, np.float64)
+    X = np.asarray(x, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    if len(keys) != len(yv) or X.shape[0] != len(yv) or len(np.asarray(order)) != len(yv):
+        raise InvalidInputException("partition keys, order, y and x must have the same number of rows")
+    if opts.offset < 0 or opts.offset > X.shape[1]:
+        raise InvalidInputException("offset must be a 1-based index into x (1..=%d), got %d" % (X.shape[1], opts.offset))
+    ukeys, gid = np.unique(keys, return_inverse=True)
+    perm = np.lexsort((np.asarray(order), gid))
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(gid, minlength=len(ukeys)))]).astype(np.int64)
+    cols = [np.ascontiguousarray(X[perm, j]) for j in range(X.shape[1]) if j != opts.offset - 1]
+    off = np.ascontiguousarray(X[perm, opts.offset - 1]) if opts.offset else None
+    z = interval_z(opts.confidence_level) if bool(_option(options, ("interval",), False)) else None
+    pred_sorted = glm_fit_predict_window_host(offsets, yv[perm], cols, opts.batch_options(), (start, end), offset=off, interval_z=z,
+                                              ctx=context)
+    pred = np.empty_like(pred_sorted)
+    pred[perm] = pred_sorted
+    return GlmFitPredictResult(pred)
+
+
+def poisson_fit_predict(partition_keys, order, y, x, options=None, frame=(None, 0), context=None) -> GlmFitPredictResult:
+    """poisson_fit_predict(y, x [, options]) OVER (PARTITION BY partition_keys ORDER BY order ROWS frame): the Poisson fit of every
+    row's frame, predicting at the x (and offset) of the frame's last row.  Options as poisson_fit_predict_agg (offset, interval /
+    confidence_level, lambda, tolerance, max_iterations, fit_intercept); frame = (start, end) as ols_fit_predict's.  result.pred
+    is [n_rows, 3] in input row order; the bounds are NaN without options['interval']."""
+    return _fit_predict(partition_keys, order, y, x, parse_poisson_options(options), options, frame, context)
+
+
+def binomial_fit_predict(partition_keys, order, y, x, options=None, frame=(None, 0), context=None) -> GlmFitPredictResult:
+    """The binomial / logit window function; an interval is not built for this family (the library refuses it)."""
+    return _fit_predict(partition_keys, order, y, x, parse_binomial_options(options), options, frame, context)
+
+
+def logistic_fit_predict(partition_keys, order, y, x, options=None, frame=(None, 0), context=None) -> GlmFitPredictResult:
+    """binomial_fit_predict under the reference's name for a 0 / 1 response: rolling logistic scores."""
+    return binomial_fit_predict(partition_keys, order, y, x, options, frame, context)
 
 
 @dataclass

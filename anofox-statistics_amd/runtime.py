@@ -341,6 +341,20 @@ class Context:
         from .glm import glm_fit_batch_device
         return glm_fit_batch_device(self, row_offsets, y, x_cols, options, offset, inference, use_current_torch_stream, threshold=threshold)
 
+    def glm_fit_predict_window_device(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions, frame=(None, 0),
+                                      offset=None, interval_z=None, want_records: bool = False, use_current_torch_stream: bool = True):
+        """The GLM window function over ROWS frames on CUDA tensors: pred[N, 3], or (pred, records[N, p + 11])."""
+        from .glm import glm_fit_predict_window_device
+        return glm_fit_predict_window_device(self, row_offsets, y, x_cols, options, frame, offset, interval_z, want_records,
+                                             use_current_torch_stream)
+
+    def glm_fit_predict_frames_device(self, y, x_cols: Sequence, frame_lo, frame_hi, options: _abi.AnofoxHipGlmBatchOptions,
+                                      offset=None, interval_z=None, want_records: bool = False, use_current_torch_stream: bool = True):
+        """The GLM window function over explicit frames [frame_lo[e], frame_hi[e]) on CUDA tensors."""
+        from .glm import glm_fit_predict_frames_device
+        return glm_fit_predict_frames_device(self, y, x_cols, frame_lo, frame_hi, options, offset, interval_z, want_records,
+                                             use_current_torch_stream)
+
     def glm_fit_accuracy_batch_host(self, row_offsets, y, x_cols: Sequence, options: _abi.AnofoxHipGlmBatchOptions,
                                     threshold: float = 0.5, offset=None, inference: bool = False):
         from .glm import glm_fit_batch_host

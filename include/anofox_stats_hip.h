@@ -1042,6 +1042,63 @@ ANOFOX_HIP_API void anofox_hip_quantile_window_test_hooks(int64_t run_length, in
 ANOFOX_HIP_API bool anofox_hip_quantile_window_stats(AnofoxHipContext *ctx, int64_t *out, AnofoxError *out_error);
 
 /*
+ * The window function of the GLM family: poisson_fit_predict / logistic_fit_predict OVER (PARTITION BY .. ORDER BY .. ROWS ..).
+ * Output row e gets the fit of its frame's rows: pred[3 e] = {mu, lower, upper} at the x (and offset) of the FRAME'S LAST ROW,
+ * and, with glm_records != NULL, the frame's record of p + 11 doubles in anofox_hip_glm_fit_batch_*'s layout.  One wavefront
+ * walks a run of consecutive output rows of a partition; a frame whose bounds are both at or after those of the frame before it,
+ * that overlaps it, and whose predecessor was fitted with every coefficient estimated starts IRLS from the predecessor's
+ * coefficients, every other frame from mustart; a warm-started frame that does not converge or ends with a skipped column is
+ * fitted again from mustart.  The answer is the minimiser of deviance + lambda sum b^2 either way.
+ *   window  ROWS frames, clipped to the partition as anofox_hip_fit_predict_window_* clips them; row_offsets cover [0, n_rows].
+ *   frames  explicit bounds [frame_lo[e], frame_hi[e]) of any shape; frame_hi <= frame_lo is an empty frame.
+ * Row rules per frame, those of anofox_hip_glm_fit_predict_batch_* with train_counts = the frame's rows with a non-NaN y: fewer
+ * than 2 of them -> ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS (an empty frame too); a finite y outside the support -> status 1, for
+ * the frames that contain it; no valid row -> 10; fewer valid rows than fitted columns -> 6.  A failed frame, a non-finite x /
+ * offset of the predicted row or a non-finite mu: NaN.  Invalid options: status 1 on every row.  n_features > 32 fails the call.
+ * interval_z as in anofox_hip_glm_fit_predict_interval_batch_*: 0 leaves the bounds NaN, > 0 gives the Poisson bounds, > 0 with
+ * the binomial family fails the call.  Scratch: 16 bytes per row of the call's longest frame per launched wavefront, from the
+ * context's workspace, 1 GiB at most in all (fewer wavefronts are launched to stay below it); a single frame above that fails
+ * the call: "glm window: frame of .. rows exceeds the scratch budget".  The device forms copy the offsets / the bounds to the
+ * host for the planner (one synchronising copy).
+ */
+ANOFOX_HIP_API bool anofox_hip_glm_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                              const int64_t *d_row_offsets, const double *d_y, const double *const *x_cols,
+                                              const double *d_offset, AnofoxHipWindowFrame frame, AnofoxHipGlmBatchOptions options,
+                                              double interval_z, double *d_pred, double *d_glm_records, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_glm_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                            const int64_t *row_offsets, const double *y, const double *const *x_cols,
+                                            const double *offset, AnofoxHipWindowFrame frame, AnofoxHipGlmBatchOptions options,
+                                            double interval_z, double *pred, double *glm_records, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_glm_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *d_y,
+                                              const double *const *x_cols, const double *d_offset, const int64_t *d_frame_lo,
+                                              const int64_t *d_frame_hi, AnofoxHipGlmBatchOptions options, double interval_z,
+                                              double *d_pred, double *d_glm_records, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_glm_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y,
+                                            const double *const *x_cols, const double *offset, const int64_t *frame_lo,
+                                            const int64_t *frame_hi, AnofoxHipGlmBatchOptions options, double interval_z,
+                                            double *pred, double *glm_records, AnofoxError *out_error);
+/*
+ * The planner of the GLM window function alone, on host arrays, under the test hooks in force: run_begin (capacity entries, may
+ * be NULL with capacity 0) receives the first output row of every walker and one entry past them, *n_runs their number,
+ * *span_rows the scratch rows of one wavefront (the longest frame), *n_waves the wavefronts a launch would use.  No device.
+ */
+ANOFOX_HIP_API bool anofox_hip_glm_window_plan(int64_t n_groups, const int64_t *row_offsets, int64_t n_rows, const int64_t *frame_lo,
+                                const int64_t *frame_hi, int64_t *run_begin, int64_t capacity, int64_t *n_runs,
+                                int64_t *span_rows, int64_t *n_waves, AnofoxError *out_error);
+/*
+ * A test's hook: the run length and the scratch cap (0: the library's rule) and whether frames may start warm (1, the default;
+ * 0: every frame starts cold, and a frame's record and mu are bit for bit anofox_hip_glm_fit_predict_batch_*'s on a group of
+ * exactly the frame's rows) of every later GLM window call of the process.  No environment variable is read.
+ */
+ANOFOX_HIP_API void anofox_hip_glm_window_test_hooks(int64_t run_length, int64_t scratch_cap_bytes, int warm);
+/*
+ * What the most recent GLM window call on ctx (NULL: the thread's default context) did: out[8] = {output rows, frames started
+ * cold, frames started warm, warm frames refitted cold, IRLS iterations summed over the frames, walkers, launched wavefronts,
+ * scratch rows per wavefront}.  Waits for the context's stream.  Per context, reset by every GLM window call on it.
+ */
+ANOFOX_HIP_API bool anofox_hip_glm_window_stats(AnofoxHipContext *ctx, int64_t *out, AnofoxError *out_error);
+
+/*
  * Grouped variance inflation factors: the Finalize loop of vif_agg (src/aggregate_functions/vif_aggregate.cpp:
  * 144-185) in one call.  x_cols as in the fit entry points (rows of a group contiguous; the aggregate's Update
  * has already dropped NULL rows and NaN values, :67-93).  d_vif[g] = { vif[n_features], status }
