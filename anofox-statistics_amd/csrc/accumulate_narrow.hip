@@ -529,17 +529,7 @@ static hipError_t launch_p(const BatchArgs &a, const int32_t *list, const int32_
 
 static hipError_t launch_any(const BatchArgs &a, const int32_t *list, const int32_t *count, bool fused, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
-	switch (a.p) {
-	case 1: return launch_p<1>(a, list, count, fused, stream);
-	case 2: return launch_p<2>(a, list, count, fused, stream);
-	case 3: return launch_p<3>(a, list, count, fused, stream);
-	case 4: return launch_p<4>(a, list, count, fused, stream);
-	case 5: return launch_p<5>(a, list, count, fused, stream);
-	case 6: return launch_p<6>(a, list, count, fused, stream);
-	case 7: return launch_p<7>(a, list, count, fused, stream);
-	case 8: return launch_p<8>(a, list, count, fused, stream);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_p<P()>(a, list, count, fused, stream); });
 }
 
 // a.primary_solved: accumulate and primary solve in one kernel — core records and the refinement queue as the solve kernel

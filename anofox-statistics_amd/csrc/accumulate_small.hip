@@ -233,17 +233,7 @@ int accumulate_small_segment_width(double avg_rows) {
 
 hipError_t launch_accumulate_small(const BatchArgs &a, int segw, int32_t *big_list, int32_t *big_count, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
-	switch (a.p) {
-	case 1: return launch_small_p<1>(a, segw, big_list, big_count, stream);
-	case 2: return launch_small_p<2>(a, segw, big_list, big_count, stream);
-	case 3: return launch_small_p<3>(a, segw, big_list, big_count, stream);
-	case 4: return launch_small_p<4>(a, segw, big_list, big_count, stream);
-	case 5: return launch_small_p<5>(a, segw, big_list, big_count, stream);
-	case 6: return launch_small_p<6>(a, segw, big_list, big_count, stream);
-	case 7: return launch_small_p<7>(a, segw, big_list, big_count, stream);
-	case 8: return launch_small_p<8>(a, segw, big_list, big_count, stream);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_small_p<P()>(a, segw, big_list, big_count, stream); });
 }
 
 } // namespace anofox

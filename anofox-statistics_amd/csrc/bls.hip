@@ -24,7 +24,8 @@
 using namespace anofox;
 
 #include "host_stage.h"
-#include "row_slabs.h"
+#include "moment_solve.h"
+#include "scalar_fit.h"
 
 using namespace anofox::host;
 
@@ -61,24 +62,19 @@ template <int R>
 __global__ __launch_bounds__(64) void bls_solve_wide_kernel(WideArgs a, BlsWideParams bp) {
 	extern __shared__ double bls_lds[];
 	const int p = a.p;
-	const int T = wide_tiles(p), P16 = 16 * T, NT = T * (T + 1) / 2;
 	const int ntri = p * (p + 1) / 2;
 	const int lane = threadIdx.x;
 	const int64_t gl = blockIdx.x;
 	const int64_t g = a.group_base + gl;
 	const bool icpt = a.fit_intercept != 0;
 	const int pl = bp.predict_layout;
-	const double *rec = a.moments + gl * (int64_t)wide_record_len(T);
-	const double *vec = rec + (int64_t)NT * 256;
-	const double *sx = vec, *sxy = vec + P16, *fx = vec + 2 * P16, *nonconst = vec + 3 * P16;
-	const double *sc = vec + 4 * P16;
+	const WideMoments m(a.moments, gl, p);
+	const double *sx = m.sx, *sxy = m.sxy, *fx = m.fx, *nonconst = m.nonconst;
 	double *core = a.core + g * (int64_t)(pl ? p + 6 : 3 * p + 6);
-	const double sy = sc[0], syy = sc[1], sw = sc[2], cnt = sc[3], first_y = sc[4];
+	const double sy = m.sy, syy = m.syy, sw = m.sw, cnt = m.cnt, cyy_c = m.cyy_c;
 	const int64_t nrows = a.rule_counts ? a.rule_counts[g] : group_row_end(a, g) - a.row_offsets[g];
-	int p_eff = 0;
-	for (int j = 0; j < p; ++j) p_eff += nonconst[j] != 0.0 ? 1 : 0;
-	const double cyy_c = syy - sy * sy / sw;
-	const double ymean = (icpt ? first_y : 0.0) + sy / sw;
+	const int p_eff = m.p_eff;
+	const double ymean = m.ymean(icpt);
 	if (lane == 0) a.refine_list[gl] = 0;
 	bool shortcut;
 	const int status = bls_prechecks(bp.invalid, nrows, cnt, p_eff, icpt, &shortcut); // (uniform: lane 0 writes)
@@ -101,9 +97,7 @@ __global__ __launch_bounds__(64) void bls_solve_wide_kernel(WideArgs a, BlsWideP
 		const int k = lane + 64 * h;
 		qv[h] = 0.0;
 		if (k < p) {
-			const int I = k >> 4;
-			const int tile = I * T - I * (I - 1) / 2;
-			const double cii = rec[(int64_t)tile * 256 + (k & 15) * 17] - (icpt ? sx[k] * sx[k] * inv_sw : 0.0);
+			const double cii = m.raw(k, k) - (icpt ? sx[k] * sx[k] * inv_sw : 0.0);
 			const bool live = nonconst[k] != 0.0 && cii > 0.0;
 			const double d = live ? sqrt(cii) : 1.0;
 			const double blo = bp.lo[k], bhi = bp.hi[k];
@@ -125,13 +119,9 @@ __global__ __launch_bounds__(64) void bls_solve_wide_kernel(WideArgs a, BlsWideP
 	}
 	__syncthreads();
 	for (int i = 0; i < p; ++i) {
-		const int I = i >> 4;
 		const bool li = st[i] != 0;
 		for (int j = lane; j <= i; j += 64) {
-			const int J = j >> 4; // j <= i: element (j, i) of the upper triangle the record keeps
-			const int tile = J * T - J * (J - 1) / 2 + (I - J);
-			double v = rec[(int64_t)tile * 256 + (j & 15) * 16 + (i & 15)];
-			if (icpt) v -= sx[i] * sx[j] * inv_sw;
+			double v = m.c(j, i, icpt, inv_sw); // j <= i: element (j, i) of the upper triangle the record keeps
 			v = (li && st[j] != 0) ? v / (dsc[i] * dsc[j]) : 0.0;
 			At[tri(i, j)] = i == j ? 1.0 : v;
 		}
@@ -367,44 +357,16 @@ __global__ __launch_bounds__(64) void bls_solve_wide_kernel(WideArgs a, BlsWideP
 	}
 }
 
-// ---- ssr from the rows of the groups whose moment identity cancelled (flag[gl] == 1), one wavefront per group ----
-struct BlsRowsArgs {
-	const int64_t *row_offsets;
-	const int64_t *row_ends; // optional (BatchArgs::row_ends)
-	const double *y;
-	const double *x_table[kWideMaxP];
-	double *core;
-	const int32_t *flag; // [n_groups] of this launch
-	int64_t group_base, n_groups;
-	int p;
-	int fit_intercept;
-	int predict_layout;
-};
-
-__global__ __launch_bounds__(64) void bls_rows_kernel(BlsRowsArgs a) {
+// ---- ssr from the rows of the groups whose moment identity cancelled (moment_solve.h) ----
+__global__ __launch_bounds__(64) void bls_rows_kernel(RowsArgs a, int pl) {
 	const int lane = threadIdx.x;
-	const int p = a.p, pl = a.predict_layout;
+	const int p = a.p;
 	for (int64_t gl = blockIdx.x; gl < a.n_groups; gl += gridDim.x) {
 		if (a.flag[gl] == 0) continue;
 		const int64_t g = a.group_base + gl;
 		double *core = a.core + g * (int64_t)(pl ? p + 6 : 3 * p + 6);
 		const double b0 = a.fit_intercept ? core[p] : 0.0;
-		double ssr = 0.0;
-		const int64_t hi = a.row_ends ? a.row_ends[g] : a.row_offsets[g + 1];
-		for (int64_t row = a.row_offsets[g] + lane; row < hi; row += 64) {
-			const double yv = a.y[row];
-			bool ok = isfinite(yv);
-			double fit = b0;
-			for (int j = 0; j < p; ++j) {
-				const double xv = a.x_table[j][row];
-				ok = ok && isfinite(xv);
-				const double bj = core[j];
-				if (!isnan(bj)) fit = fma(bj, xv, fit);
-			}
-			const double e = yv - fit;
-			if (ok) ssr = fma(e, e, ssr);
-		}
-		for (int m = 32; m >= 1; m >>= 1) ssr += __shfl_xor(ssr, m, 64);
+		const double ssr = rows_ssr(a, g, core, b0, lane);
 		if (lane == 0) {
 			if (pl) {
 				const double tss = core[p + 1]; // parked by the solve
@@ -420,44 +382,22 @@ __global__ __launch_bounds__(64) void bls_rows_kernel(BlsRowsArgs a) {
 	}
 }
 
-template <int P>
-hipError_t launch_bls_narrow_p(const BatchArgs &a, const BlsNarrowParams &bp, hipStream_t st) {
-	hipLaunchKernelGGL((bls_solve_narrow_kernel<P>), dim3((unsigned)((a.n_groups + 63) / 64)), dim3(64), 0, st, a, bp);
-	return hipGetLastError();
-}
-
 hipError_t launch_bls_narrow(const BatchArgs &a, const BlsNarrowParams &bp, hipStream_t st) {
-	switch (a.p) {
-	case 1: return launch_bls_narrow_p<1>(a, bp, st);
-	case 2: return launch_bls_narrow_p<2>(a, bp, st);
-	case 3: return launch_bls_narrow_p<3>(a, bp, st);
-	case 4: return launch_bls_narrow_p<4>(a, bp, st);
-	case 5: return launch_bls_narrow_p<5>(a, bp, st);
-	case 6: return launch_bls_narrow_p<6>(a, bp, st);
-	case 7: return launch_bls_narrow_p<7>(a, bp, st);
-	case 8: return launch_bls_narrow_p<8>(a, bp, st);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) {
+		hipLaunchKernelGGL((bls_solve_narrow_kernel<P()>), dim3((unsigned)((a.n_groups + 63) / 64)), dim3(64), 0, st, a, bp);
+		return hipGetLastError();
+	});
 }
 
 size_t bls_wide_lds_bytes(int p) { return ((size_t)p * (p + 1) + 7 * (size_t)p) * sizeof(double); }
 
 hipError_t launch_bls_wide(const WideArgs &a, const BlsWideParams &bp, hipStream_t st) {
-	const size_t lds = bls_wide_lds_bytes(a.p); // 139 264 bytes at p = 128
-	static const bool attr_set = [] {
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&bls_solve_wide_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&bls_solve_wide_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		return true;
-	}();
-	(void)attr_set;
-	if (a.p <= 64) hipLaunchKernelGGL((bls_solve_wide_kernel<1>), dim3((unsigned)a.n_groups), dim3(64), lds, st, a, bp);
-	else hipLaunchKernelGGL((bls_solve_wide_kernel<2>), dim3((unsigned)a.n_groups), dim3(64), lds, st, a, bp);
-	return hipGetLastError();
+	// (139 264 bytes of LDS at p = 128)
+	return launch_wide_r<bls_solve_wide_kernel<1>, bls_solve_wide_kernel<2>>(a, bp, bls_wide_lds_bytes(a.p), st);
 }
 
-hipError_t launch_bls_rows(const BlsRowsArgs &ra, hipStream_t st) {
-	const unsigned grid = ra.n_groups < 16384 ? (unsigned)ra.n_groups : 16384u;
-	hipLaunchKernelGGL(bls_rows_kernel, dim3(grid), dim3(64), 0, st, ra);
+hipError_t launch_bls_rows(const RowsArgs &ra, int predict_layout, hipStream_t st) {
+	hipLaunchKernelGGL(bls_rows_kernel, dim3(rows_grid(ra.n_groups)), dim3(64), 0, st, ra, predict_layout);
 	return hipGetLastError();
 }
 
@@ -476,39 +416,13 @@ bool bls_narrow_stage(AnofoxHipContext *, BatchArgs &a, hipStream_t st, void *us
 	bp.iterations = bw.iterations;
 	if (hip_fail(launch_bls_narrow(a, bp, st), "bounded least squares solve kernel launch", e)) return false;
 	if (!a.row_offsets) return true; // the records of a streaming state: no rows here, its Finalize answers the flagged groups
-	BlsRowsArgs ra;
-	memset(&ra, 0, sizeof ra);
-	ra.row_offsets = a.row_offsets;
-	ra.row_ends = a.row_ends;
-	ra.y = a.y;
-	for (int j = 0; j < a.p; ++j) ra.x_table[j] = a.x[j];
-	ra.core = a.core;
-	ra.flag = a.refine_list;
-	ra.group_base = 0;
-	ra.n_groups = a.n_groups;
-	ra.p = a.p;
-	ra.fit_intercept = a.fit_intercept;
-	ra.predict_layout = bw.predict_layout;
-	return !hip_fail(launch_bls_rows(ra, st), "bounded least squares rows kernel launch", e);
+	return !hip_fail(launch_bls_rows(rows_args(a), bw.predict_layout, st), "bounded least squares rows kernel launch", e);
 }
 
 bool bls_wide_stage(AnofoxHipContext *, WideArgs &a, hipStream_t st, int64_t, void *user, AnofoxError *e) {
 	const BlsWideParams &bw = *static_cast<const BlsWideParams *>(user);
 	if (hip_fail(launch_bls_wide(a, bw, st), "bounded least squares solve kernel launch", e)) return false;
-	BlsRowsArgs ra;
-	memset(&ra, 0, sizeof ra);
-	ra.row_offsets = a.row_offsets;
-	ra.row_ends = a.row_ends;
-	ra.y = a.y;
-	for (int j = 0; j < a.p; ++j) ra.x_table[j] = a.x_table[j];
-	ra.core = a.core;
-	ra.flag = a.refine_list;
-	ra.group_base = a.group_base;
-	ra.n_groups = a.n_groups;
-	ra.p = a.p;
-	ra.fit_intercept = a.fit_intercept;
-	ra.predict_layout = bw.predict_layout;
-	return !hip_fail(launch_bls_rows(ra, st), "bounded least squares rows kernel launch", e);
+	return !hip_fail(launch_bls_rows(rows_args(a), bw.predict_layout, st), "bounded least squares rows kernel launch", e);
 }
 
 SolveStages bls_stages(BlsWideParams *bp) { return SolveStages{bls_narrow_stage, bls_wide_stage, bp}; }
@@ -538,29 +452,12 @@ BlsWideParams bls_params(const AnofoxHipBlsBatchOptions &o, size_t p, int predic
 	return bp;
 }
 
-AnofoxHipBatchOptions bls_moment_options(const AnofoxHipBlsBatchOptions &o, double confidence_level) {
-	AnofoxHipBatchOptions acc; // the moments of an unweighted fit
-	memset(&acc, 0, sizeof acc);
-	acc.model = ANOFOX_HIP_MODEL_OLS;
-	acc.fit_intercept = o.fit_intercept;
-	acc.confidence_level = confidence_level;
-	acc.hc_type = ANOFOX_HC_NONE;
-	return acc;
-}
-
 bool validate_bls(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols,
                   const AnofoxHipBlsBatchOptions &o, const void *core, AnofoxError *e) {
 	if (!ctx) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
-	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
-	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
-	if (p > (size_t)kWideMaxP) {
-		set_error(e, ANOFOX_ERROR_INVALID_INPUT,
-		          "n_features = " + std::to_string(p) + " exceeds the supported maximum of " + std::to_string(kWideMaxP));
+	if (!check_batch_args(G, p, n_rows, off, y, x_cols, core, kWideMaxP, nullptr,
+	                      "row_offsets, y or the record buffer is NULL", false, e))
 		return false;
-	}
-	if (G > 0 && (!off || !y || !core)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets, y or the record buffer is NULL"); return false; }
-	for (size_t j = 0; j < p; ++j)
-		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
 	if (!(o.tolerance >= 0.0)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "tolerance must be >= 0"); return false; }
 	return true;
 }
@@ -570,7 +467,7 @@ bool run_bls(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const i
 	if (G == 0) return true;
 	BlsWideParams bp = bls_params(o, p, 0, d_iterations);
 	// (the stages run before this call returns: `bp` is captured by value into the kernel arguments at launch)
-	return moment_batch_device(ctx, G, p, n_rows, d_off, d_y, x_cols, bls_moment_options(o, 0.95), bls_stages(&bp), d_bls, e);
+	return moment_batch_device(ctx, G, p, n_rows, d_off, d_y, x_cols, unweighted_moment_options(o.fit_intercept, 0.95), bls_stages(&bp), d_bls, e);
 }
 
 } // namespace
@@ -613,29 +510,12 @@ bool anofox_hip_bls_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size
 	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t p = n_features, rec_len = 3 * p + 6;
-	std::vector<int64_t> off;
-	hipStream_t st = ctx->stream;
-	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
-		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
-		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
-		int64_t *d_off;
-		StagedColumns c;
-		double *d_rec;
-		int32_t *d_it;
-		if (!stage_call(ctx, out_error, [&](Stage &s) {
-			    d_off = s.put(off.data(), (size_t)G + 1, "H2D offsets");
-			    c = s.columns(p, r0, R, x_cols, y);
-			    d_rec = s.take<double>((size_t)G * rec_len);
-			    d_it = iterations ? s.take<int32_t>((size_t)G) : nullptr;
-		    }))
-			return false;
-		if (!run_bls(ctx, G, p, R, d_off, c.y, c.x, options, d_rec, d_it, out_error)) return false;
-		if (!d2h(bls + (size_t)g0 * rec_len, d_rec, (size_t)G * rec_len * sizeof(double), st, out_error, "D2H records")) return false;
-		if (d_it && !d2h(iterations + g0, d_it, (size_t)G * sizeof(int32_t), st, out_error, "D2H iterations")) return false;
-		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-	}
-	return true;
+	const size_t p = n_features;
+	return fit_slabs_host(ctx, n_groups, p, row_offsets, y, x_cols, nullptr, SlabOutputs{bls, 3 * p + 6, iterations, 1},
+	                      SlabLabels{kNamedColumns, "H2D offsets", "D2H records", "D2H iterations", "D2H"}, out_error,
+	                      [&](int64_t G, int64_t R, const int64_t *, const int64_t *d_off, const StagedColumns &c, double *d_rec, int32_t *d_it, double *) {
+		                      return run_bls(ctx, G, p, R, d_off, c.y, c.x, options, d_rec, d_it, out_error);
+	                      });
 }
 
 // A batch of one group with anofox_elasticnet_fit's conventions: argument checks first (lib.rs:3510-3522), NULL entries ->
@@ -647,23 +527,13 @@ bool anofox_bls_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count,
 	if (!out_core) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "out_result is NULL"); return false; }
 	if (!x || x_count == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
 	if (y.len == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Empty input: y cannot be empty"); return false; }
-	for (size_t j = 0; j < x_count; ++j) {
-		if (x[j].len != y.len) {
-			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH, "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(x[j].len) + " rows");
-			return false;
-		}
-	}
-	const size_t p = x_count, n = y.len;
+	if (!check_column_lengths(y.len, x, x_count, out_error)) return false;
+	const size_t p = x_count;
 	if (p > (size_t)kWideMaxP) {
 		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "BLS fit: more than " + std::to_string(kWideMaxP) + " features are not supported by the GPU path");
 		return false;
 	}
-	const size_t n_pad = n < 2 ? 2 : n;
-	std::vector<std::vector<double>> cols(p);
-	std::vector<double> yv;
-	expand_data_array(y, yv, n_pad);
-	std::vector<const double *> xp(p);
-	for (size_t j = 0; j < p; ++j) { expand_data_array(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
+	const ScalarFitInput in(y, x, x_count);
 	AnofoxHipBlsBatchOptions o;
 	memset(&o, 0, sizeof o);
 	o.fit_intercept = options.fit_intercept;
@@ -673,27 +543,14 @@ bool anofox_bls_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count,
 	o.upper_bounds_len = options.upper_bounds ? options.upper_bounds_len : 0;
 	o.max_iterations = options.max_iterations;
 	o.tolerance = options.tolerance;
-	const int64_t off[2] = {0, (int64_t)n_pad};
 	std::vector<double> rec(3 * p + 6);
-	if (!anofox_hip_bls_fit_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), o, rec.data(), nullptr, out_error)) return false;
+	if (!anofox_hip_bls_fit_batch_host(nullptr, 1, p, (int64_t)in.n_pad, in.off, in.yv.data(), in.xp.data(), o, rec.data(), nullptr, out_error)) return false;
 	const int status = (int)rec[p + 5];
 	if (status != ANOFOX_ERROR_SUCCESS) {
-		size_t n_valid = 0;
-		for (size_t i = 0; i < n; ++i) {
-			bool ok = isfinite(yv[i]);
-			for (size_t j = 0; ok && j < p; ++j) ok = isfinite(cols[j][i]);
-			n_valid += ok;
-		}
-		std::string msg;
-		switch (status) { // crates/anofox-stats-core/src/errors.rs
-		case ANOFOX_ERROR_NO_VALID_DATA: msg = "All rows filtered due to NULL/NaN values"; break;
-		case ANOFOX_ERROR_INSUFFICIENT_DATA:
-			msg = "Insufficient data: " + std::to_string(n_valid) + " rows, " + std::to_string(p) + " features (need rows > features)";
-			break;
-		case ANOFOX_ERROR_INVALID_INPUT: msg = "Invalid bounds: each side takes 0, 1 or n_features values, none NaN, lower <= upper"; break;
-		default: msg = "BLS fit failed on the GPU path"; break;
-		}
-		set_error(out_error, (AnofoxErrorCode)status, msg);
+		set_scalar_fit_error(status, (AnofoxErrorCode)status, in,
+		                     status == ANOFOX_ERROR_INVALID_INPUT ? "Invalid bounds: each side takes 0, 1 or n_features values, none NaN, lower <= upper"
+		                                                          : "BLS fit failed on the GPU path",
+		                     out_error);
 		return false;
 	}
 	double *coef = (double *)malloc(p * sizeof(double));
@@ -755,7 +612,7 @@ bool anofox_hip_bls_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_gr
 	if (!validate_bls(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, options, d_core, out_error)) return false;
 	BlsWideParams bp = bls_params(options, n_features, 1, nullptr);
 	return model_fit_predict_batch_device(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_train_counts,
-	                                      bls_moment_options(options, confidence_level), bls_stages(&bp), d_core, d_pred, out_error);
+	                                      unweighted_moment_options(options.fit_intercept, confidence_level), bls_stages(&bp), d_core, d_pred, out_error);
 }
 
 bool anofox_hip_bls_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
@@ -767,7 +624,7 @@ bool anofox_hip_bls_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_grou
 	if (!validate_bls(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, options, core, out_error)) return false;
 	BlsWideParams bp = bls_params(options, n_features, 1, nullptr);
 	return model_fit_predict_batch_host(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, train_counts,
-	                                    bls_moment_options(options, confidence_level), bls_stages(&bp), core, pred, out_error);
+	                                    unweighted_moment_options(options.fit_intercept, confidence_level), bls_stages(&bp), core, pred, out_error);
 }
 
 } // extern "C"

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/anofox_stats_hip.h"
 
 namespace anofox {
@@ -10,6 +12,23 @@ namespace anofox {
 // Register-resident ("narrow") path: one wavefront streams one group, every lane keeps the whole
 // (p+1)(p+2)/2 moment triangle in VGPRs.  Above this the LDS/MFMA ("wide") path takes over.
 constexpr int kNarrowMaxP = 8;
+
+// The narrow path's dispatch on the width: f(std::integral_constant<int, P>{}) for p = P in 1..kNarrowMaxP, and what it
+// returns; `other` for any other p.
+template <class T, class F>
+inline T dispatch_narrow(int p, T other, F &&f) {
+	switch (p) {
+	case 1: return f(std::integral_constant<int, 1>{});
+	case 2: return f(std::integral_constant<int, 2>{});
+	case 3: return f(std::integral_constant<int, 3>{});
+	case 4: return f(std::integral_constant<int, 4>{});
+	case 5: return f(std::integral_constant<int, 5>{});
+	case 6: return f(std::integral_constant<int, 6>{});
+	case 7: return f(std::integral_constant<int, 7>{});
+	case 8: return f(std::integral_constant<int, 8>{});
+	default: return other;
+	}
+}
 
 // bytes of the t critical value memo (device_math.h: TcritSlot[kTcritSlots]) at the end of a workspace
 constexpr size_t kTcritTableBytes = 4096;

@@ -2,6 +2,7 @@
 // the C ABI (host_api.hip, agg_state.hip, the model families).  Internal: nothing here is exported.
 #pragma once
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <mutex>
@@ -181,6 +182,34 @@ inline bool ensure_buffer(void **buf, size_t *cap, size_t need, const char *what
 }
 
 // ---- argument checks and input conversion shared by the host entry points ----
+
+inline std::string fmt_g(double v) {
+	char buf[64];
+	snprintf(buf, sizeof buf, "%g", v);
+	return buf;
+}
+
+// The argument checks that every batch entry point makes, in their order: the signs, x, the width, the NULL arrays
+// (`null_text`), the NULL columns.  Above `max_p` the text is `over_text`, or for nullptr "n_features = <p> exceeds the supported
+// maximum of <max_p>", built only then.  by_rows == false: the arrays are needed when G > 0 (the fit entries); true: when
+// n_rows > 0, and neither G nor `off` is looked at (the window entries, one output per row).  The context is not checked here:
+// every entry keeps its own place for that step and for its family's options.
+inline bool check_batch_args(int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols,
+                             const void *out, size_t max_p, const char *over_text, const char *null_text, bool by_rows, AnofoxError *e) {
+	if ((!by_rows && G < 0) || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
+	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
+	if (p > max_p) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT,
+		          over_text ? std::string(over_text)
+		                    : "n_features = " + std::to_string(p) + " exceeds the supported maximum of " + std::to_string(max_p));
+		return false;
+	}
+	const bool need = by_rows ? n_rows > 0 : G > 0;
+	if (need && ((!by_rows && !off) || !y || !out)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, null_text); return false; }
+	for (size_t j = 0; j < p; ++j)
+		if (need && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
+	return true;
+}
 
 // the offsets of a host batch: group g owns rows [off[g], off[g + 1]) of the n_rows that the caller's arrays hold
 inline bool check_host_offsets(int64_t G, int64_t n_rows, const int64_t *off, AnofoxError *e) {

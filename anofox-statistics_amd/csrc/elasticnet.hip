@@ -28,7 +28,8 @@
 using namespace anofox;
 
 #include "host_stage.h"
-#include "row_slabs.h"
+#include "moment_solve.h"
+#include "scalar_fit.h"
 
 using namespace anofox::host;
 
@@ -58,22 +59,17 @@ template <int R>
 __global__ __launch_bounds__(64) void en_solve_wide_kernel(WideArgs a, EnParams en) {
 	extern __shared__ double en_lds[]; // [p * p] column-major C, then [p] active flags (as doubles)
 	const int p = a.p;
-	const int T = wide_tiles(p), P16 = 16 * T, NT = T * (T + 1) / 2;
 	const int lane = threadIdx.x;
 	const int64_t gl = blockIdx.x;
 	const int64_t g = a.group_base + gl;
 	const bool icpt = a.fit_intercept != 0;
-	const double *rec = a.moments + gl * (int64_t)wide_record_len(T);
-	const double *vec = rec + (int64_t)NT * 256;
-	const double *sx = vec, *sxy = vec + P16, *fx = vec + 2 * P16, *nonconst = vec + 3 * P16;
-	const double *sc = vec + 4 * P16;
+	const WideMoments m(a.moments, gl, p);
+	const double *sx = m.sx, *sxy = m.sxy, *fx = m.fx, *nonconst = m.nonconst;
 	double *core = a.core + g * (int64_t)(p + 6);
-	const double sy = sc[0], syy = sc[1], sw = sc[2], cnt = sc[3], first_y = sc[4];
+	const double sy = m.sy, syy = m.syy, sw = m.sw, cnt = m.cnt, cyy_c = m.cyy_c;
 	const int64_t nrows = a.rule_counts ? a.rule_counts[g] : group_row_end(a, g) - a.row_offsets[g];
-	int p_eff = 0;
-	for (int j = 0; j < p; ++j) p_eff += nonconst[j] != 0.0 ? 1 : 0;
-	const double cyy_c = syy - sy * sy / sw;
-	const double ymean = (icpt ? first_y : 0.0) + sy / sw;
+	const int p_eff = m.p_eff;
+	const double ymean = m.ymean(icpt);
 	if (lane == 0) a.refine_list[gl] = 0;
 	bool shortcut;
 	const int status = en_prechecks(en, nrows, cnt, p_eff, icpt, &shortcut); // (uniform: lane 0 writes)
@@ -90,12 +86,7 @@ __global__ __launch_bounds__(64) void en_solve_wide_kernel(WideArgs a, EnParams 
 	const double inv_sw = 1.0 / sw;
 	for (int idx = lane; idx < p * p; idx += 64) {
 		const int j = idx / p, k = idx - j * p; // Cs[j * p + k] = C[k][j]
-		const int lo = j < k ? j : k, hi = j < k ? k : j;
-		const int I = lo >> 4, J = hi >> 4;
-		const int tile = I * T - I * (I - 1) / 2 + (J - I);
-		double v = rec[(int64_t)tile * 256 + (lo & 15) * 16 + (hi & 15)];
-		if (icpt) v -= sx[lo] * sx[hi] * inv_sw;
-		Cs[idx] = v;
+		Cs[idx] = m.c(j < k ? j : k, j < k ? k : j, icpt, inv_sw);
 	}
 	for (int j = lane; j < p; j += 64) act[j] = nonconst[j] != 0.0 ? 1.0 : 0.0;
 	__syncthreads();
@@ -168,19 +159,7 @@ __global__ __launch_bounds__(64) void en_solve_wide_kernel(WideArgs a, EnParams 
 	}
 }
 
-// ---- rss from the rows of the groups whose moment identity cancelled (flag[gl] == 1), one wavefront per group ----
-struct RowsArgs {
-	const int64_t *row_offsets;
-	const int64_t *row_ends; // optional: group g owns rows [row_offsets[g], row_ends[g]) (BatchArgs::row_ends)
-	const double *y;
-	const double *x_table[kWideMaxP];
-	double *core;
-	const int32_t *flag; // [n_groups] of this launch
-	int64_t group_base, n_groups;
-	int p;
-	int fit_intercept;
-};
-
+// ---- rss from the rows of the groups whose moment identity cancelled (moment_solve.h) ----
 __global__ __launch_bounds__(64) void rows_rss_kernel(RowsArgs a) {
 	const int lane = threadIdx.x;
 	const int p = a.p;
@@ -191,22 +170,7 @@ __global__ __launch_bounds__(64) void rows_rss_kernel(RowsArgs a) {
 		const double b0 = a.fit_intercept ? core[p] : 0.0;
 		int p_eff = 0;
 		for (int j = 0; j < p; ++j) p_eff += isnan(core[j]) ? 0 : 1;
-		double rss = 0.0;
-		const int64_t hi = a.row_ends ? a.row_ends[g] : a.row_offsets[g + 1];
-		for (int64_t row = a.row_offsets[g] + lane; row < hi; row += 64) {
-			const double yv = a.y[row];
-			bool ok = isfinite(yv);
-			double fit = b0;
-			for (int j = 0; j < p; ++j) {
-				const double xv = a.x_table[j][row];
-				ok = ok && isfinite(xv);
-				const double bj = core[j];
-				if (!isnan(bj)) fit = fma(bj, xv, fit);
-			}
-			const double e = yv - fit;
-			if (ok) rss = fma(e, e, rss);
-		}
-		for (int m = 32; m >= 1; m >>= 1) rss += __shfl_xor(rss, m, 64);
+		const double rss = rows_ssr(a, g, core, b0, lane);
 		if (lane == 0) {
 			const bool icpt = a.fit_intercept != 0;
 			const double tss = core[p + 1], cnt = core[p + 4]; // tss parked by the solve
@@ -219,42 +183,20 @@ __global__ __launch_bounds__(64) void rows_rss_kernel(RowsArgs a) {
 	}
 }
 
-template <int P>
-hipError_t launch_en_narrow_p(const BatchArgs &a, const EnParams &en, hipStream_t st) {
-	hipLaunchKernelGGL((en_solve_narrow_kernel<P>), dim3((unsigned)((a.n_groups + 63) / 64)), dim3(64), 0, st, a, en);
-	return hipGetLastError();
-}
-
 hipError_t launch_en_narrow(const BatchArgs &a, const EnParams &en, hipStream_t st) {
-	switch (a.p) {
-	case 1: return launch_en_narrow_p<1>(a, en, st);
-	case 2: return launch_en_narrow_p<2>(a, en, st);
-	case 3: return launch_en_narrow_p<3>(a, en, st);
-	case 4: return launch_en_narrow_p<4>(a, en, st);
-	case 5: return launch_en_narrow_p<5>(a, en, st);
-	case 6: return launch_en_narrow_p<6>(a, en, st);
-	case 7: return launch_en_narrow_p<7>(a, en, st);
-	case 8: return launch_en_narrow_p<8>(a, en, st);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) {
+		hipLaunchKernelGGL((en_solve_narrow_kernel<P()>), dim3((unsigned)((a.n_groups + 63) / 64)), dim3(64), 0, st, a, en);
+		return hipGetLastError();
+	});
 }
 
 hipError_t launch_en_wide(const WideArgs &a, const EnParams &en, hipStream_t st) {
 	const size_t lds = ((size_t)a.p * a.p + (size_t)a.p) * sizeof(double);
-	static const bool attr_set = [] {
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&en_solve_wide_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&en_solve_wide_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		return true;
-	}();
-	(void)attr_set;
-	if (a.p <= 64) hipLaunchKernelGGL((en_solve_wide_kernel<1>), dim3((unsigned)a.n_groups), dim3(64), lds, st, a, en);
-	else hipLaunchKernelGGL((en_solve_wide_kernel<2>), dim3((unsigned)a.n_groups), dim3(64), lds, st, a, en);
-	return hipGetLastError();
+	return launch_wide_r<en_solve_wide_kernel<1>, en_solve_wide_kernel<2>>(a, en, lds, st);
 }
 
 hipError_t launch_rows_rss(const RowsArgs &ra, hipStream_t st) {
-	const unsigned grid = ra.n_groups < 16384 ? (unsigned)ra.n_groups : 16384u;
-	hipLaunchKernelGGL(rows_rss_kernel, dim3(grid), dim3(64), 0, st, ra);
+	hipLaunchKernelGGL(rows_rss_kernel, dim3(rows_grid(ra.n_groups)), dim3(64), 0, st, ra);
 	return hipGetLastError();
 }
 
@@ -263,65 +205,31 @@ bool en_narrow_stage(AnofoxHipContext *, BatchArgs &a, hipStream_t st, void *use
 	const EnParams &en = *static_cast<const EnParams *>(user);
 	if (hip_fail(launch_en_narrow(a, en, st), "elastic net solve kernel launch", e)) return false;
 	if (!a.row_offsets) return true; // the records of a streaming state: no rows here, its Finalize answers the flagged groups
-	RowsArgs ra;
-	memset(&ra, 0, sizeof ra);
-	ra.row_offsets = a.row_offsets;
-	ra.row_ends = a.row_ends;
-	ra.y = a.y;
-	for (int j = 0; j < a.p; ++j) ra.x_table[j] = a.x[j];
-	ra.core = a.core;
-	ra.flag = a.refine_list;
-	ra.group_base = 0;
-	ra.n_groups = a.n_groups;
-	ra.p = a.p;
-	ra.fit_intercept = a.fit_intercept;
-	return !hip_fail(launch_rows_rss(ra, st), "elastic net rows kernel launch", e);
+	return !hip_fail(launch_rows_rss(rows_args(a), st), "elastic net rows kernel launch", e);
 }
 
 bool en_wide_stage(AnofoxHipContext *, WideArgs &a, hipStream_t st, int64_t, void *user, AnofoxError *e) {
 	const EnParams &en = *static_cast<const EnParams *>(user);
 	if (hip_fail(launch_en_wide(a, en, st), "elastic net solve kernel launch", e)) return false;
-	RowsArgs ra;
-	memset(&ra, 0, sizeof ra);
-	ra.row_offsets = a.row_offsets;
-	ra.row_ends = a.row_ends;
-	ra.y = a.y;
-	for (int j = 0; j < a.p; ++j) ra.x_table[j] = a.x_table[j];
-	ra.core = a.core;
-	ra.flag = a.refine_list;
-	ra.group_base = a.group_base;
-	ra.n_groups = a.n_groups;
-	ra.p = a.p;
-	ra.fit_intercept = a.fit_intercept;
-	return !hip_fail(launch_rows_rss(ra, st), "elastic net rows kernel launch", e);
+	return !hip_fail(launch_rows_rss(rows_args(a), st), "elastic net rows kernel launch", e);
 }
 
 bool validate_elasticnet_options(const AnofoxHipElasticNetBatchOptions &o, AnofoxError *e);
 EnParams elasticnet_params(const AnofoxHipElasticNetBatchOptions &o, int32_t *d_iterations);
-AnofoxHipBatchOptions elasticnet_moment_options(const AnofoxHipElasticNetBatchOptions &o, double confidence_level);
 SolveStages elasticnet_stages(EnParams *en);
 
 bool validate_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols,
                  const AnofoxHipElasticNetBatchOptions &o, const void *core, AnofoxError *e) {
 	if (!ctx) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
-	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
-	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
-	if (p > (size_t)kWideMaxP) {
-		set_error(e, ANOFOX_ERROR_INVALID_INPUT,
-		          "n_features = " + std::to_string(p) + " exceeds the supported maximum of " + std::to_string(kWideMaxP));
-		return false;
-	}
-	if (G > 0 && (!off || !y || !core)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets, y or core is NULL"); return false; }
-	for (size_t j = 0; j < p; ++j)
-		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
-	return validate_elasticnet_options(o, e);
+	return check_batch_args(G, p, n_rows, off, y, x_cols, core, kWideMaxP, nullptr, "row_offsets, y or core is NULL", false, e) &&
+	       validate_elasticnet_options(o, e);
 }
 
 bool run_en(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_y, const double *const *x_cols,
             const AnofoxHipElasticNetBatchOptions &o, double *d_core, int32_t *d_iterations, AnofoxError *e) {
 	if (G == 0) return true;
 	EnParams en = elasticnet_params(o, d_iterations);
-	const AnofoxHipBatchOptions acc = elasticnet_moment_options(o, 0.95);
+	const AnofoxHipBatchOptions acc = unweighted_moment_options(o.fit_intercept, 0.95);
 	const SolveStages stages = elasticnet_stages(&en);
 	// (the stages run before this call returns: `en` is captured by value into the kernel arguments at launch)
 	return moment_batch_device(ctx, G, p, n_rows, d_off, d_y, x_cols, acc, stages, d_core, e);
@@ -347,16 +255,6 @@ EnParams elasticnet_params(const AnofoxHipElasticNetBatchOptions &o, int32_t *d_
 	return en;
 }
 
-AnofoxHipBatchOptions elasticnet_moment_options(const AnofoxHipElasticNetBatchOptions &o, double confidence_level) {
-	AnofoxHipBatchOptions acc; // the moments of an unweighted fit
-	memset(&acc, 0, sizeof acc);
-	acc.model = ANOFOX_HIP_MODEL_OLS;
-	acc.fit_intercept = o.fit_intercept;
-	acc.confidence_level = confidence_level;
-	acc.hc_type = ANOFOX_HC_NONE;
-	return acc;
-}
-
 SolveStages elasticnet_stages(EnParams *en) { return SolveStages{en_narrow_stage, en_wide_stage, en}; }
 
 // the in-register window kernels (window_narrow.hip, ElasticNetFit); ANOFOX_EN_WINDOW_NARROW=0 sends p <= 8 to the frames path
@@ -368,12 +266,6 @@ hipError_t en_window_launch(const WindowArgs &a, void *user, hipStream_t st) {
 WindowSolve elasticnet_window(EnParams *en) {
 	static const bool narrow_on = !(getenv("ANOFOX_EN_WINDOW_NARROW") && atoi(getenv("ANOFOX_EN_WINDOW_NARROW")) == 0);
 	return WindowSolve{elasticnet_stages(en), narrow_on ? en_window_launch : nullptr, en};
-}
-
-std::string fmt_g(double v) {
-	char buf[64];
-	snprintf(buf, sizeof buf, "%g", v);
-	return buf;
 }
 
 } // namespace
@@ -413,29 +305,12 @@ bool anofox_hip_elasticnet_fit_batch_host(AnofoxHipContext *ctx, int64_t n_group
 	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t p = n_features, core_len = p + 6;
-	std::vector<int64_t> off;
-	hipStream_t st = ctx->stream;
-	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
-		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
-		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
-		int64_t *d_off;
-		StagedColumns c;
-		double *d_core;
-		int32_t *d_it;
-		if (!stage_call(ctx, out_error, [&](Stage &s) {
-			    d_off = s.put(off.data(), (size_t)G + 1, "H2D offsets");
-			    c = s.columns(p, r0, R, x_cols, y);
-			    d_core = s.take<double>((size_t)G * core_len);
-			    d_it = iterations ? s.take<int32_t>((size_t)G) : nullptr;
-		    }))
-			return false;
-		if (!run_en(ctx, G, p, R, d_off, c.y, c.x, options, d_core, d_it, out_error)) return false;
-		if (!d2h(core + (size_t)g0 * core_len, d_core, (size_t)G * core_len * sizeof(double), st, out_error, "D2H core")) return false;
-		if (d_it && !d2h(iterations + g0, d_it, (size_t)G * sizeof(int32_t), st, out_error, "D2H iterations")) return false;
-		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-	}
-	return true;
+	const size_t p = n_features;
+	return fit_slabs_host(ctx, n_groups, p, row_offsets, y, x_cols, nullptr, SlabOutputs{core, p + 6, iterations, 1},
+	                      SlabLabels{kNamedColumns, "H2D offsets", "D2H core", "D2H iterations", "D2H"}, out_error,
+	                      [&](int64_t G, int64_t R, const int64_t *, const int64_t *d_off, const StagedColumns &c, double *d_core, int32_t *d_it, double *) {
+		                      return run_en(ctx, G, p, R, d_off, c.y, c.x, options, d_core, d_it, out_error);
+	                      });
 }
 
 // A batch of one group with fit_single's conventions (host_api.hip): argument checks first, NULL entries -> NaN through the
@@ -455,23 +330,13 @@ bool anofox_elasticnet_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x
 		return false;
 	}
 	if (y.len == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Empty input: y cannot be empty"); return false; }
-	for (size_t j = 0; j < x_count; ++j) {
-		if (x[j].len != y.len) {
-			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH, "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(x[j].len) + " rows");
-			return false;
-		}
-	}
-	const size_t p = x_count, n = y.len;
+	if (!check_column_lengths(y.len, x, x_count, out_error)) return false;
+	const size_t p = x_count;
 	if (p > (size_t)kWideMaxP) {
 		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Elastic Net fit: more than " + std::to_string(kWideMaxP) + " features are not supported by the GPU path");
 		return false;
 	}
-	const size_t n_pad = n < 2 ? 2 : n;
-	std::vector<std::vector<double>> cols(p);
-	std::vector<double> yv;
-	expand_data_array(y, yv, n_pad);
-	std::vector<const double *> xp(p);
-	for (size_t j = 0; j < p; ++j) { expand_data_array(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
+	const ScalarFitInput in(y, x, x_count);
 	AnofoxHipElasticNetBatchOptions o;
 	memset(&o, 0, sizeof o);
 	o.fit_intercept = options.fit_intercept;
@@ -480,41 +345,15 @@ bool anofox_elasticnet_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x
 	o.max_iterations = options.max_iterations;
 	o.tolerance = options.tolerance;
 	o.lambda_scaling = options.lambda_scaling;
-	const int64_t off[2] = {0, (int64_t)n_pad};
 	std::vector<double> core(p + 6);
-	if (!anofox_hip_elasticnet_fit_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), o, core.data(), nullptr, out_error))
+	if (!anofox_hip_elasticnet_fit_batch_host(nullptr, 1, p, (int64_t)in.n_pad, in.off, in.yv.data(), in.xp.data(), o, core.data(), nullptr, out_error))
 		return false;
 	const int status = (int)core[p + 5];
 	if (status != ANOFOX_ERROR_SUCCESS) {
-		size_t n_valid = 0;
-		for (size_t i = 0; i < n; ++i) {
-			bool ok = isfinite(yv[i]);
-			for (size_t j = 0; ok && j < p; ++j) ok = isfinite(cols[j][i]);
-			n_valid += ok;
-		}
-		std::string msg;
-		switch (status) { // crates/anofox-stats-core/src/errors.rs
-		case ANOFOX_ERROR_NO_VALID_DATA: msg = "All rows filtered due to NULL/NaN values"; break;
-		case ANOFOX_ERROR_INSUFFICIENT_DATA:
-			msg = "Insufficient data: " + std::to_string(n_valid) + " rows, " + std::to_string(p) + " features (need rows > features)";
-			break;
-		default: msg = "Elastic Net fit failed on the GPU path"; break;
-		}
-		set_error(out_error, (AnofoxErrorCode)status, msg);
+		set_scalar_fit_error(status, (AnofoxErrorCode)status, in, "Elastic Net fit failed on the GPU path", out_error);
 		return false;
 	}
-	double *coef = (double *)malloc(p * sizeof(double));
-	if (!coef) { set_error(out_error, ANOFOX_ERROR_ALLOCATION_FAILURE, "Failed to allocate coefficients"); return false; }
-	memcpy(coef, core.data(), p * sizeof(double));
-	out_core->coefficients = coef;
-	out_core->coefficients_len = p;
-	out_core->intercept = core[p];
-	out_core->r_squared = core[p + 1];
-	out_core->adj_r_squared = core[p + 2];
-	out_core->residual_std_error = core[p + 3];
-	out_core->n_observations = (size_t)core[p + 4];
-	out_core->n_features = p;
-	return true;
+	return fill_scalar_result(core.data(), p, out_core, out_error);
 }
 
 // ---- elastic net fit-predict (anofox_stats_elasticnet_fit_predict_agg, anofox_stats_elasticnet_fit_predict): the elastic net
@@ -528,7 +367,7 @@ bool anofox_hip_elasticnet_fit_predict_batch_device(AnofoxHipContext *ctx, int64
 	if (!validate_elasticnet_options(options, out_error)) return false;
 	EnParams en = elasticnet_params(options, nullptr);
 	return model_fit_predict_batch_device(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, d_train_counts,
-	                                      elasticnet_moment_options(options, confidence_level), elasticnet_stages(&en), d_core, d_pred, out_error);
+	                                      unweighted_moment_options(options.fit_intercept, confidence_level), elasticnet_stages(&en), d_core, d_pred, out_error);
 }
 
 bool anofox_hip_elasticnet_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
@@ -539,7 +378,7 @@ bool anofox_hip_elasticnet_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t
 	if (!validate_elasticnet_options(options, out_error)) return false;
 	EnParams en = elasticnet_params(options, nullptr);
 	return model_fit_predict_batch_host(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, train_counts,
-	                                    elasticnet_moment_options(options, confidence_level), elasticnet_stages(&en), core, pred, out_error);
+	                                    unweighted_moment_options(options.fit_intercept, confidence_level), elasticnet_stages(&en), core, pred, out_error);
 }
 
 bool anofox_hip_elasticnet_fit_predict_window_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
@@ -550,7 +389,7 @@ bool anofox_hip_elasticnet_fit_predict_window_device(AnofoxHipContext *ctx, int6
 	if (!validate_elasticnet_options(options, out_error)) return false;
 	EnParams en = elasticnet_params(options, nullptr);
 	return model_fit_predict_window_device(ctx, n_groups, n_features, n_rows, d_row_offsets, d_y, x_cols, frame,
-	                                       elasticnet_moment_options(options, confidence_level), elasticnet_window(&en), d_pred, out_error);
+	                                       unweighted_moment_options(options.fit_intercept, confidence_level), elasticnet_window(&en), d_pred, out_error);
 }
 
 bool anofox_hip_elasticnet_fit_predict_window_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
@@ -561,7 +400,7 @@ bool anofox_hip_elasticnet_fit_predict_window_host(AnofoxHipContext *ctx, int64_
 	if (!validate_elasticnet_options(options, out_error)) return false;
 	EnParams en = elasticnet_params(options, nullptr);
 	return model_fit_predict_window_host(ctx, n_groups, n_features, n_rows, row_offsets, y, x_cols, frame,
-	                                     elasticnet_moment_options(options, confidence_level), elasticnet_window(&en), pred, out_error);
+	                                     unweighted_moment_options(options.fit_intercept, confidence_level), elasticnet_window(&en), pred, out_error);
 }
 
 bool anofox_hip_elasticnet_fit_predict_frames_device(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *d_y,
@@ -572,7 +411,7 @@ bool anofox_hip_elasticnet_fit_predict_frames_device(AnofoxHipContext *ctx, int6
 	if (!validate_elasticnet_options(options, out_error)) return false;
 	EnParams en = elasticnet_params(options, nullptr);
 	return model_fit_predict_frames_device(ctx, n_rows, n_features, d_y, x_cols, d_frame_lo, d_frame_hi,
-	                                       elasticnet_moment_options(options, confidence_level), elasticnet_stages(&en), d_pred, out_error);
+	                                       unweighted_moment_options(options.fit_intercept, confidence_level), elasticnet_stages(&en), d_pred, out_error);
 }
 
 bool anofox_hip_elasticnet_fit_predict_frames_host(AnofoxHipContext *ctx, int64_t n_rows, size_t n_features, const double *y,
@@ -583,7 +422,7 @@ bool anofox_hip_elasticnet_fit_predict_frames_host(AnofoxHipContext *ctx, int64_
 	if (!validate_elasticnet_options(options, out_error)) return false;
 	EnParams en = elasticnet_params(options, nullptr);
 	return model_fit_predict_frames_host(ctx, n_rows, n_features, y, x_cols, frame_lo, frame_hi,
-	                                     elasticnet_moment_options(options, confidence_level), elasticnet_stages(&en), pred, out_error);
+	                                     unweighted_moment_options(options.fit_intercept, confidence_level), elasticnet_stages(&en), pred, out_error);
 }
 
 } // extern "C"

@@ -157,13 +157,8 @@ double normal_quantile(double prob) {
 
 bool check_glm(int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols, const void *out,
                AnofoxError *e) {
-	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
-	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
-	if (p > (size_t)kGiMaxP) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: n_features > 32 is not built"); return false; }
-	if (G > 0 && (!off || !y || !out)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets, y or an output is NULL"); return false; }
-	for (size_t j = 0; j < p; ++j)
-		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
-	return true;
+	return check_batch_args(G, p, n_rows, off, y, x_cols, out, kGiMaxP, "glm: n_features > 32 is not built", "row_offsets, y or an output is NULL",
+	                        false, e);
 }
 
 // the fit of G groups on device-resident inputs, enqueued on the context's stream (ctx->mu held by the caller)

@@ -131,13 +131,7 @@ bool plan_glm_window(int64_t n_parts, const int64_t *off, const int64_t *lo, con
 }
 
 bool check_window_args(int64_t n_rows, size_t p, const void *y, const double *const *x_cols, const void *pred, AnofoxError *e) {
-	if (n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
-	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
-	if (p > (size_t)kGiMaxP) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glm: n_features > 32 is not built"); return false; }
-	if (n_rows > 0 && (!y || !pred)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "y or pred is NULL"); return false; }
-	for (size_t j = 0; j < p; ++j)
-		if (n_rows > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
-	return true;
+	return check_batch_args(0, p, n_rows, nullptr, y, x_cols, pred, kGiMaxP, "glm: n_features > 32 is not built", "y or pred is NULL", true, e);
 }
 
 // The walk of a planned call on device-resident rows and frames (ctx->mu held by the caller).  The workspace holds the slabs,

@@ -286,17 +286,7 @@ size_t hc_prep_bytes(int64_t n_groups, int p) {
 hipError_t launch_hc_narrow(const BatchArgs &a, double *prep, void *overflow, hipStream_t stream) {
 	if (a.n_groups <= 0 || !a.inference) return hipSuccess;
 	if (a.n_groups > (int64_t)0x7fffffff / 4) return hipErrorInvalidValue;
-	switch (a.p) {
-	case 1: return launch_hc_p<1>(a, prep, overflow, stream);
-	case 2: return launch_hc_p<2>(a, prep, overflow, stream);
-	case 3: return launch_hc_p<3>(a, prep, overflow, stream);
-	case 4: return launch_hc_p<4>(a, prep, overflow, stream);
-	case 5: return launch_hc_p<5>(a, prep, overflow, stream);
-	case 6: return launch_hc_p<6>(a, prep, overflow, stream);
-	case 7: return launch_hc_p<7>(a, prep, overflow, stream);
-	case 8: return launch_hc_p<8>(a, prep, overflow, stream);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_hc_p<P()>(a, prep, overflow, stream); });
 }
 
 } // namespace anofox

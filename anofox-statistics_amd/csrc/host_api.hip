@@ -22,7 +22,7 @@
 using namespace anofox;
 
 #include "host_stage.h"
-#include "row_slabs.h"
+#include "scalar_fit.h"
 
 using namespace anofox::host;
 
@@ -391,16 +391,8 @@ bool validate_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
                     const double *const *x_cols, const void *w, const AnofoxHipBatchOptions &opt, const void *core,
                     const void *inf, AnofoxError *e) {
 	if (!ctx) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
-	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
-	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
-	if (p > (size_t)kWideMaxP) {
-		set_error(e, ANOFOX_ERROR_INVALID_INPUT,
-		          "n_features = " + std::to_string(p) + " exceeds the supported maximum of " + std::to_string(kWideMaxP));
+	if (!check_batch_args(G, p, n_rows, off, y, x_cols, core, kWideMaxP, nullptr, "row_offsets, y or core is NULL", false, e))
 		return false;
-	}
-	if (G > 0 && (!off || !y || !core)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets, y or core is NULL"); return false; }
-	for (size_t j = 0; j < p; ++j)
-		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
 	if (opt.model != ANOFOX_HIP_MODEL_OLS && opt.model != ANOFOX_HIP_MODEL_RIDGE && opt.model != ANOFOX_HIP_MODEL_WLS) {
 		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "unknown model");
 		return false;
@@ -1163,28 +1155,13 @@ bool anofox_hip_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n
 	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t p = n_features, core_len = p + 6, inf_len = 5 * p + 2;
-	std::vector<int64_t> off;
-	hipStream_t st = ctx->stream;
-	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
-		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
-		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
-		int64_t *d_off;
-		StagedColumns c;
-		double *d_core, *d_inf;
-		if (!stage_call(ctx, out_error, [&](Stage &s) {
-			    d_off = s.put(off.data(), (size_t)G + 1, "H2D offsets");
-			    c = s.columns(p, r0, R, x_cols, y, options.model == ANOFOX_HIP_MODEL_WLS ? w : nullptr);
-			    d_core = s.take<double>((size_t)G * core_len);
-			    d_inf = options.compute_inference ? s.take<double>((size_t)G * inf_len) : nullptr;
-		    }))
-			return false;
-		if (!run_device_batch(ctx, G, p, R, d_off, c.y, c.x, c.w, options, d_core, d_inf, out_error)) return false;
-		if (!d2h(core + (size_t)g0 * core_len, d_core, (size_t)G * core_len * sizeof(double), st, out_error, "D2H core")) return false;
-		if (d_inf && !d2h(inference + (size_t)g0 * inf_len, d_inf, (size_t)G * inf_len * sizeof(double), st, out_error, "D2H inference")) return false;
-		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-	}
-	return true;
+	const size_t p = n_features;
+	return fit_slabs_host(ctx, n_groups, p, row_offsets, y, x_cols, options.model == ANOFOX_HIP_MODEL_WLS ? w : nullptr,
+	                      SlabOutputs{core, p + 6, nullptr, 0, options.compute_inference ? inference : nullptr, 5 * p + 2},
+	                      SlabLabels{kNamedColumns, "H2D offsets", "D2H core", "D2H", "D2H inference"}, out_error,
+	                      [&](int64_t G, int64_t R, const int64_t *, const int64_t *d_off, const StagedColumns &c, double *d_core, int32_t *, double *d_inf) {
+		                      return run_device_batch(ctx, G, p, R, d_off, c.y, c.x, c.w, options, d_core, d_inf, out_error);
+	                      });
 }
 
 
@@ -1195,12 +1172,6 @@ bool anofox_hip_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n
 /* ------------------------------------------------------------------------------------------------ */
 
 namespace {
-
-std::string fmt_g(double v) {
-	char buf[64];
-	snprintf(buf, sizeof buf, "%g", v);
-	return buf;
-}
 
 void default_inference(AnofoxFitResultInference *inf) { // FitResultInference::default(), types.rs:151-165
 	memset(inf, 0, sizeof *inf);
@@ -1224,62 +1195,31 @@ bool fit_single(const char *what, AnofoxDataArray y, const AnofoxDataArray *x, s
 	if (weights) {
 		if (weights->len == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Empty input: weights cannot be empty"); return false; }
 		if (weights->len != y.len) {
-			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH, "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(weights->len) + " rows");
+			set_dimension_mismatch(y.len, weights->len, out_error);
 			return false;
 		}
 	}
-	for (size_t j = 0; j < x_count; ++j) {
-		if (x[j].len != y.len) {
-			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH, "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(x[j].len) + " rows");
-			return false;
-		}
-	}
-	const size_t p = x_count, n = y.len;
+	if (!check_column_lengths(y.len, x, x_count, out_error)) return false;
+	const size_t p = x_count;
 	if (p > (size_t)kWideMaxP) {
 		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, std::string(what) + ": more than " + std::to_string(kWideMaxP) + " features are not supported by the GPU path");
 		return false;
 	}
-	// The kernels apply the aggregate's "< 2 rows -> NULL" rule from row_offsets; a single-group call has no
-	// such rule (ols.rs accepts n == 1), so a one-row input is padded with one all-NaN row, which the row
-	// filter drops again.
-	const size_t n_pad = n < 2 ? 2 : n;
-	std::vector<std::vector<double>> cols(p);
-	std::vector<double> yv, wv;
-	expand_data_array(y, yv, n_pad);
-	for (size_t j = 0; j < p; ++j) expand_data_array(x[j], cols[j], n_pad);
-	if (weights) expand_data_array(*weights, wv, n_pad);
-
-	std::vector<const double *> xp(p);
-	for (size_t j = 0; j < p; ++j) xp[j] = cols[j].data();
-	const int64_t off[2] = {0, (int64_t)n_pad};
+	const ScalarFitInput in(y, x, x_count, weights);
 	std::vector<double> core(p + 6), inf(5 * p + 2);
-	if (!anofox_hip_fit_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), weights ? wv.data() : nullptr, opt,
-	                               core.data(), inf.data(), out_error))
+	if (!anofox_hip_fit_batch_host(nullptr, 1, p, (int64_t)in.n_pad, in.off, in.yv.data(), in.xp.data(), in.w(), opt, core.data(), inf.data(),
+	                               out_error))
 		return false;
 	const int status = (int)core[p + 5];
-	if (status != ANOFOX_ERROR_SUCCESS) {
-		size_t n_valid = 0;
-		for (size_t i = 0; i < n; ++i) {
-			bool ok = isfinite(yv[i]);
-			for (size_t j = 0; ok && j < p; ++j) ok = isfinite(cols[j][i]);
-			if (ok && weights) ok = wv[i] > 0.0 && isfinite(wv[i]);
-			n_valid += ok;
-		}
-		std::string msg;
-		switch (status) { // error strings: crates/anofox-stats-core/src/errors.rs:5-59
-		case ANOFOX_ERROR_NO_VALID_DATA: msg = "All rows filtered due to NULL/NaN values"; break;
-		case ANOFOX_ERROR_INSUFFICIENT_DATA:
-			msg = "Insufficient data: " + std::to_string(n_valid) + " rows, " + std::to_string(p) + " features (need rows > features)";
-			break;
-		case ANOFOX_ERROR_INVALID_ALPHA: msg = "Invalid alpha parameter: " + fmt_g(opt.alpha) + " (must be >= 0)"; break;
-		default: msg = std::string(what) + " failed on the GPU path"; break;
-		}
-		set_error(out_error, (AnofoxErrorCode)status, msg);
+	if (status != ANOFOX_ERROR_SUCCESS) { // error strings: crates/anofox-stats-core/src/errors.rs:5-59
+		set_scalar_fit_error(status, (AnofoxErrorCode)status, in,
+		                     status == ANOFOX_ERROR_INVALID_ALPHA ? "Invalid alpha parameter: " + fmt_g(opt.alpha) + " (must be >= 0)"
+		                                                          : std::string(what) + " failed on the GPU path",
+		                     out_error);
 		return false;
 	}
-	double *coef = (double *)malloc(p * sizeof(double));
-	if (!coef) { set_error(out_error, ANOFOX_ERROR_ALLOCATION_FAILURE, "Failed to allocate coefficients"); return false; }
-	memcpy(coef, core.data(), p * sizeof(double));
+	double *coef = copy_coefficients(core.data(), p, out_error);
+	if (!coef) return false;
 	double *arr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 	// the reference returns inference: None for the intercept-only shortcut even when requested (ols.rs:128);
 	// that shortcut is the only successful fit whose coefficients are all NaN
@@ -1573,17 +1513,9 @@ bool run_vif(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const i
 bool validate_vif(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const void *off, const double *const *x_cols,
                   const void *out, AnofoxError *e) {
 	if (!ctx) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
-	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
-	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
-	if (p > (size_t)kWideMaxP + 1) {
-		set_error(e, ANOFOX_ERROR_INVALID_INPUT,
-		          "n_features = " + std::to_string(p) + " exceeds the supported maximum of " + std::to_string(kWideMaxP + 1));
-		return false;
-	}
-	if (G > 0 && (!off || !out)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets or output is NULL"); return false; }
-	for (size_t j = 0; j < p; ++j)
-		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
-	return true;
+	// (the VIF has no y: the offsets stand in for it)
+	return check_batch_args(G, p, n_rows, off, off, x_cols, out, kWideMaxP + 1, nullptr, "row_offsets or output is NULL",
+	                        false, e);
 }
 
 bool vif_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets,

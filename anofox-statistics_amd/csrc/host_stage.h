@@ -4,6 +4,7 @@
 // the arrays and enqueues the copies to the device.  The size and the placement cannot disagree: they are the same code.
 #pragma once
 #include "context.h"
+#include "row_slabs.h"
 
 namespace anofox {
 namespace host {
@@ -81,6 +82,56 @@ bool stage_call(AnofoxHipContext *ctx, AnofoxError *e, Layout &&layout) {
 	Stage s{(char *)ctx->stage, ctx->stream, e};
 	layout(s);
 	return s.ok;
+}
+
+// ---- the host form of a batch fit: slab by slab (row_slabs.h) through the staging buffer ----
+
+// what a host fit returns per group: the records, and optionally int32 iteration counts and a second block of doubles (the
+// inference of the regression models); a NULL pointer is an output the call does not ask for
+struct SlabOutputs {
+	double *rec;
+	size_t rec_len;
+	int32_t *iterations = nullptr;
+	size_t it_len = 0;
+	double *extra = nullptr;
+	size_t extra_len = 0;
+};
+
+// the labels of a slab's copies, as they appear in a HIP error's text
+struct SlabLabels {
+	ColumnLabels columns;
+	const char *offsets, *rec, *iterations, *extra;
+};
+constexpr SlabLabels kPlainSlab = {kPlainColumns, "H2D", "D2H", "D2H", "D2H"};
+
+// Stages each slab's rebased offsets, columns and output blocks, calls run(G, R, off, d_off, columns, d_rec, d_iterations,
+// d_extra) — `off` the slab's offsets on the host, the rest device addresses — which enqueues the family's fit of the slab's
+// G groups and R rows on the context's stream, copies the outputs back to their place in the caller's arrays and synchronises.
+// ctx->mu is held by the caller.
+template <class Run>
+bool fit_slabs_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, const int64_t *row_offsets, const double *y,
+                    const double *const *x_cols, const double *w, const SlabOutputs &out, const SlabLabels &l, AnofoxError *e, Run &&run) {
+	hipStream_t st = ctx->stream;
+	return for_each_row_slab(row_offsets, n_groups, kHostSlabRows, [&](int64_t g0, int64_t G, int64_t r0, int64_t R, const int64_t *off) {
+		const size_t n = (size_t)G, at = (size_t)g0;
+		int64_t *d_off;
+		StagedColumns c;
+		double *d_rec, *d_extra;
+		int32_t *d_it;
+		if (!stage_call(ctx, e, [&](Stage &s) {
+			    d_off = s.put(off, n + 1, l.offsets);
+			    c = s.columns(p, r0, R, x_cols, y, w, nullptr, l.columns);
+			    d_rec = s.take<double>(n * out.rec_len);
+			    d_it = out.iterations ? s.take<int32_t>(n * out.it_len) : nullptr;
+			    d_extra = out.extra ? s.take<double>(n * out.extra_len) : nullptr;
+		    }))
+			return false;
+		if (!run(G, R, off, (const int64_t *)d_off, (const StagedColumns &)c, d_rec, d_it, d_extra)) return false;
+		if (!d2h(out.rec + at * out.rec_len, d_rec, n * out.rec_len * sizeof(double), st, e, l.rec)) return false;
+		if (d_it && !d2h(out.iterations + at * out.it_len, d_it, n * out.it_len * sizeof(int32_t), st, e, l.iterations)) return false;
+		if (d_extra && !d2h(out.extra + at * out.extra_len, d_extra, n * out.extra_len * sizeof(double), st, e, l.extra)) return false;
+		return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", e);
+	});
 }
 
 } // namespace host

@@ -402,17 +402,7 @@ size_t ingest_sort_temp_bytes(int64_t n) {
 hipError_t launch_ingest_chunk(const IngestArgs &a, hipStream_t stream) {
 	if (a.n <= 0) return hipSuccess;
 	if (a.n > kIngestChunkRows || a.n_slots <= 0 || a.n_slots > (int64_t)0x7fffffff) return hipErrorInvalidValue;
-	switch (a.p) {
-	case 1: return launch_chunk_p<1>(a, stream);
-	case 2: return launch_chunk_p<2>(a, stream);
-	case 3: return launch_chunk_p<3>(a, stream);
-	case 4: return launch_chunk_p<4>(a, stream);
-	case 5: return launch_chunk_p<5>(a, stream);
-	case 6: return launch_chunk_p<6>(a, stream);
-	case 7: return launch_chunk_p<7>(a, stream);
-	case 8: return launch_chunk_p<8>(a, stream);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_chunk_p<P()>(a, stream); });
 }
 
 namespace {
@@ -473,17 +463,7 @@ hipError_t launch_ingest_clear_slots(double *moments, int64_t *n_accum, const ui
 hipError_t launch_ingest_combine(double *moments, int64_t *n_accum, int64_t n_slots, const uint32_t *src, const uint32_t *dst,
                                  int64_t n_pairs, int p, int center, int preserve, hipStream_t stream) {
 	if (n_pairs <= 0) return hipSuccess;
-	switch (p) {
-	case 1: return launch_combine_p<1>(moments, n_accum, n_slots, src, dst, n_pairs, center, preserve, stream);
-	case 2: return launch_combine_p<2>(moments, n_accum, n_slots, src, dst, n_pairs, center, preserve, stream);
-	case 3: return launch_combine_p<3>(moments, n_accum, n_slots, src, dst, n_pairs, center, preserve, stream);
-	case 4: return launch_combine_p<4>(moments, n_accum, n_slots, src, dst, n_pairs, center, preserve, stream);
-	case 5: return launch_combine_p<5>(moments, n_accum, n_slots, src, dst, n_pairs, center, preserve, stream);
-	case 6: return launch_combine_p<6>(moments, n_accum, n_slots, src, dst, n_pairs, center, preserve, stream);
-	case 7: return launch_combine_p<7>(moments, n_accum, n_slots, src, dst, n_pairs, center, preserve, stream);
-	case 8: return launch_combine_p<8>(moments, n_accum, n_slots, src, dst, n_pairs, center, preserve, stream);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(p, hipErrorInvalidValue, [&](auto P) { return launch_combine_p<P()>(moments, n_accum, n_slots, src, dst, n_pairs, center, preserve, stream); });
 }
 
 } // namespace anofox

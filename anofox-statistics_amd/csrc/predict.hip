@@ -324,17 +324,7 @@ hipError_t launch_information_criteria(const double *core, int64_t n_groups, int
 hipError_t launch_predict(const PredictArgs &a, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
 	hipLaunchKernelGGL(predict_margin_kernel, dim3((unsigned)((a.n_groups + 255) / 256)), dim3(256), 0, stream, a);
-	switch (a.p) {
-	case 1: return launch_predict_p<1>(a, stream);
-	case 2: return launch_predict_p<2>(a, stream);
-	case 3: return launch_predict_p<3>(a, stream);
-	case 4: return launch_predict_p<4>(a, stream);
-	case 5: return launch_predict_p<5>(a, stream);
-	case 6: return launch_predict_p<6>(a, stream);
-	case 7: return launch_predict_p<7>(a, stream);
-	case 8: return launch_predict_p<8>(a, stream);
-	default: break;
-	}
+	if (a.p >= 1 && a.p <= kNarrowMaxP) return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_predict_p<P()>(a, stream); });
 	hipLaunchKernelGGL(predict_kernel<false>, dim3((unsigned)((a.n_groups + 3) / 4)), dim3(256), 0, stream, a);
 	if (a.seg_table) hipLaunchKernelGGL(predict_kernel<true>, dim3((unsigned)((kSegTargetWaves + 16 + 3) / 4)), dim3(256), 0, stream, a);
 	return hipGetLastError();

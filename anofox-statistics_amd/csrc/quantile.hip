@@ -35,8 +35,8 @@
 using namespace anofox;
 
 #include "host_stage.h"
+#include "scalar_fit.h"
 #include "window_plan.h"
-#include "row_slabs.h"
 
 using namespace anofox::host;
 using namespace anofox::quantile;
@@ -171,15 +171,11 @@ __global__ __launch_bounds__(256) void quantile_nan_bounds_kernel(double *pred, 
 
 bool tau_invalid(double tau) { return !(tau > 0.0 && tau < 1.0); } // (NaN fails both)
 
+const char *const kOverWidth = "quantile regression: n_features > 32 is not built";
+
 bool check_quantile(int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols, const void *out,
                     AnofoxError *e) {
-	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
-	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
-	if (p > (size_t)kQsMaxP) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "quantile regression: n_features > 32 is not built"); return false; }
-	if (G > 0 && (!off || !y || !out)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets, y or an output is NULL"); return false; }
-	for (size_t j = 0; j < p; ++j)
-		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
-	return true;
+	return check_batch_args(G, p, n_rows, off, y, x_cols, out, kQsMaxP, kOverWidth, "row_offsets, y or an output is NULL", false, e);
 }
 
 void fill_args(QuantileArgs &a, AnofoxHipContext *ctx, int64_t G, size_t p, size_t rows, const int64_t *d_off, const double *d_y,
@@ -253,31 +249,16 @@ bool launch_nan_bounds(AnofoxHipContext *ctx, int64_t n_rows, double *d_pred, An
 }
 
 // ---- the one-group entry points (anofox_quantile_fit, anofox_quantile_fit_path) ----
-// a record's status != 0 as the reference's error (crates/anofox-stats-core/src/errors.rs)
-void set_scalar_fit_error(int status, size_t n, size_t p, const std::vector<double> &yv, const std::vector<std::vector<double>> &cols,
-                          AnofoxError *out_error) {
-	size_t n_valid = 0;
-	for (size_t i = 0; i < n; ++i) {
-		bool ok = isfinite(yv[i]);
-		for (size_t j = 0; ok && j < p; ++j) ok = isfinite(cols[j][i]);
-		n_valid += ok;
-	}
-	std::string msg;
-	switch (status) {
-	case ANOFOX_ERROR_NO_VALID_DATA: msg = "All rows filtered due to NULL/NaN values"; break;
-	case ANOFOX_ERROR_INSUFFICIENT_DATA:
-		msg = "Insufficient data: " + std::to_string(n_valid) + " rows, " + std::to_string(p) + " features (need rows > features)";
-		break;
-	default: msg = "Quantile fit failed on the GPU path"; break;
-	}
-	set_error(out_error, status == ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS ? ANOFOX_ERROR_INSUFFICIENT_DATA : (AnofoxErrorCode)status, msg);
+// a record's status != 0 as the reference's error
+void set_quantile_fit_error(int status, const ScalarFitInput &in, AnofoxError *out_error) {
+	set_scalar_fit_error(status, status == ANOFOX_HIP_STATUS_NULL_TOO_FEW_ROWS ? ANOFOX_ERROR_INSUFFICIENT_DATA : (AnofoxErrorCode)status, in,
+	                     "Quantile fit failed on the GPU path", out_error);
 }
 
 // the malloc'ed result of one record
-bool fill_scalar_result(const double *rec, size_t p, AnofoxQuantileFitResultCore *out_core, AnofoxError *out_error) {
-	double *coef = (double *)malloc(p * sizeof(double));
-	if (!coef) { set_error(out_error, ANOFOX_ERROR_ALLOCATION_FAILURE, "Failed to allocate coefficients"); return false; }
-	memcpy(coef, rec, p * sizeof(double));
+bool fill_quantile_result(const double *rec, size_t p, AnofoxQuantileFitResultCore *out_core, AnofoxError *out_error) {
+	double *coef = copy_coefficients(rec, p, out_error);
+	if (!coef) return false;
 	out_core->coefficients = coef;
 	out_core->coefficients_len = p;
 	out_core->intercept = rec[p];
@@ -339,13 +320,7 @@ bool plan_window(int64_t n_parts, const int64_t *off, const int64_t *lo, const i
 }
 
 bool check_window_args(int64_t n_rows, size_t p, const void *y, const double *const *x_cols, const void *pred, AnofoxError *e) {
-	if (n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
-	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
-	if (p > (size_t)kQsMaxP) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "quantile regression: n_features > 32 is not built"); return false; }
-	if (n_rows > 0 && (!y || !pred)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "y or pred is NULL"); return false; }
-	for (size_t j = 0; j < p; ++j)
-		if (n_rows > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
-	return true;
+	return check_batch_args(0, p, n_rows, nullptr, y, x_cols, pred, kQsMaxP, kOverWidth, "y or pred is NULL", true, e);
 }
 
 // The walk of a planned call on device-resident rows and frames (ctx->mu held by the caller).  The workspace holds the slabs,
@@ -431,29 +406,11 @@ bool anofox_hip_quantile_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups,
 	if (!(ctx = host_context(ctx, out_error))) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t p = n_features, rec_len = p + 6;
-	std::vector<int64_t> off;
-	hipStream_t st = ctx->stream;
-	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
-		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
-		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
-		int64_t *d_off;
-		StagedColumns c;
-		double *d_rec;
-		int32_t *d_it;
-		if (!stage_call(ctx, out_error, [&](Stage &s) {
-			    d_off = s.put(off.data(), (size_t)G + 1);
-			    c = s.columns(p, r0, R, x_cols, y, nullptr, nullptr, kPlainColumns);
-			    d_rec = s.take<double>((size_t)G * rec_len);
-			    d_it = iterations ? s.take<int32_t>((size_t)G) : nullptr;
-		    }))
-			return false;
-		if (!launch_quantile(ctx, G, p, R, d_off, c.y, c.x, nullptr, options, 0, d_rec, d_it, out_error)) return false;
-		if (!d2h(quantile + (size_t)g0 * rec_len, d_rec, (size_t)G * rec_len * sizeof(double), st, out_error)) return false;
-		if (d_it && !d2h(iterations + g0, d_it, (size_t)G * sizeof(int32_t), st, out_error)) return false;
-		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-	}
-	return true;
+	const size_t p = n_features;
+	return fit_slabs_host(ctx, n_groups, p, row_offsets, y, x_cols, nullptr, SlabOutputs{quantile, p + 6, iterations, 1}, kPlainSlab, out_error,
+	                      [&](int64_t G, int64_t R, const int64_t *, const int64_t *d_off, const StagedColumns &c, double *d_rec, int32_t *d_it, double *) {
+		                      return launch_quantile(ctx, G, p, R, d_off, c.y, c.x, nullptr, options, 0, d_rec, d_it, out_error);
+	                      });
 }
 
 bool anofox_hip_quantile_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
@@ -533,29 +490,11 @@ bool anofox_hip_quantile_fit_path_batch_host(AnofoxHipContext *ctx, int64_t n_gr
 	if (!(ctx = host_context(ctx, out_error))) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t p = n_features, T = n_taus, rec_len = T * (p + 6);
-	std::vector<int64_t> off;
-	hipStream_t st = ctx->stream;
-	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
-		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
-		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
-		int64_t *d_off;
-		StagedColumns c;
-		double *d_rec;
-		int32_t *d_it;
-		if (!stage_call(ctx, out_error, [&](Stage &s) {
-			    d_off = s.put(off.data(), (size_t)G + 1);
-			    c = s.columns(p, r0, R, x_cols, y, nullptr, nullptr, kPlainColumns);
-			    d_rec = s.take<double>((size_t)G * rec_len);
-			    d_it = iterations ? s.take<int32_t>((size_t)G * T) : nullptr;
-		    }))
-			return false;
-		if (!launch_quantile_path(ctx, G, p, R, d_off, c.y, c.x, nullptr, options, taus, T, d_rec, d_it, nullptr, out_error)) return false;
-		if (!d2h(quantile + (size_t)g0 * rec_len, d_rec, (size_t)G * rec_len * sizeof(double), st, out_error)) return false;
-		if (d_it && !d2h(iterations + (size_t)g0 * T, d_it, (size_t)G * T * sizeof(int32_t), st, out_error)) return false;
-		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-	}
-	return true;
+	const size_t p = n_features, T = n_taus;
+	return fit_slabs_host(ctx, n_groups, p, row_offsets, y, x_cols, nullptr, SlabOutputs{quantile, T * (p + 6), iterations, T}, kPlainSlab, out_error,
+	                      [&](int64_t G, int64_t R, const int64_t *, const int64_t *d_off, const StagedColumns &c, double *d_rec, int32_t *d_it, double *) {
+		                      return launch_quantile_path(ctx, G, p, R, d_off, c.y, c.x, nullptr, options, taus, T, d_rec, d_it, nullptr, out_error);
+	                      });
 }
 
 bool anofox_hip_quantile_fit_predict_path_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
@@ -622,36 +561,25 @@ bool anofox_quantile_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_c
 	if (!x || x_count == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
 	if (y.len == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Empty input: y cannot be empty"); return false; }
 	if (tau_invalid(options.tau)) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Invalid value for tau: tau must be in (0, 1)"); return false; }
-	for (size_t j = 0; j < x_count; ++j) {
-		if (x[j].len != y.len) {
-			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH,
-			          "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(x[j].len) + " rows");
-			return false;
-		}
-	}
-	const size_t p = x_count, n = y.len;
-	if (p > (size_t)kQsMaxP) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "quantile regression: n_features > 32 is not built"); return false; }
-	const size_t n_pad = n < 2 ? 2 : n;
-	std::vector<std::vector<double>> cols(p);
-	std::vector<double> yv;
-	expand_data_array(y, yv, n_pad);
-	std::vector<const double *> xp(p);
-	for (size_t j = 0; j < p; ++j) { expand_data_array(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
+	if (!check_column_lengths(y.len, x, x_count, out_error)) return false;
+	const size_t p = x_count;
+	if (p > (size_t)kQsMaxP) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, kOverWidth); return false; }
+	const ScalarFitInput in(y, x, x_count);
 	AnofoxHipQuantileBatchOptions o;
 	memset(&o, 0, sizeof o);
 	o.tau = options.tau;
 	o.fit_intercept = options.fit_intercept;
 	o.max_iterations = options.max_iterations;
 	o.tolerance = options.tolerance;
-	const int64_t off[2] = {0, (int64_t)n_pad};
 	std::vector<double> rec(p + 6);
-	if (!anofox_hip_quantile_fit_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), o, rec.data(), nullptr, out_error)) return false;
+	if (!anofox_hip_quantile_fit_batch_host(nullptr, 1, p, (int64_t)in.n_pad, in.off, in.yv.data(), in.xp.data(), o, rec.data(), nullptr, out_error))
+		return false;
 	const int status = (int)rec[p + 5];
 	if (status != ANOFOX_ERROR_SUCCESS) {
-		set_scalar_fit_error(status, n, p, yv, cols, out_error);
+		set_quantile_fit_error(status, in, out_error);
 		return false;
 	}
-	return fill_scalar_result(rec.data(), p, out_core, out_error);
+	return fill_quantile_result(rec.data(), p, out_core, out_error);
 }
 
 // anofox_quantile_fit at every tau of a grid, through one anofox_hip_quantile_fit_path_batch_host call of one group.  The
@@ -666,36 +594,24 @@ bool anofox_quantile_fit_path(AnofoxDataArray y, const AnofoxDataArray *x, size_
 	if (!check_taus(taus, n_taus, out_error)) return false;
 	for (size_t t = 0; t < n_taus; ++t)
 		if (tau_invalid(taus[t])) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Invalid value for tau: tau must be in (0, 1)"); return false; }
-	for (size_t j = 0; j < x_count; ++j) {
-		if (x[j].len != y.len) {
-			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH,
-			          "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(x[j].len) + " rows");
-			return false;
-		}
-	}
-	const size_t p = x_count, n = y.len;
-	if (p > (size_t)kQsMaxP) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "quantile regression: n_features > 32 is not built"); return false; }
-	const size_t n_pad = n < 2 ? 2 : n;
-	std::vector<std::vector<double>> cols(p);
-	std::vector<double> yv;
-	expand_data_array(y, yv, n_pad);
-	std::vector<const double *> xp(p);
-	for (size_t j = 0; j < p; ++j) { expand_data_array(x[j], cols[j], n_pad); xp[j] = cols[j].data(); }
+	if (!check_column_lengths(y.len, x, x_count, out_error)) return false;
+	const size_t p = x_count;
+	if (p > (size_t)kQsMaxP) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, kOverWidth); return false; }
+	const ScalarFitInput in(y, x, x_count);
 	AnofoxHipQuantileBatchOptions o;
 	memset(&o, 0, sizeof o);
 	o.fit_intercept = options.fit_intercept;
 	o.max_iterations = options.max_iterations;
 	o.tolerance = options.tolerance;
-	const int64_t off[2] = {0, (int64_t)n_pad};
 	std::vector<double> rec(n_taus * (p + 6));
-	if (!anofox_hip_quantile_fit_path_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), o, taus, n_taus, rec.data(), nullptr,
-	                                             out_error))
+	if (!anofox_hip_quantile_fit_path_batch_host(nullptr, 1, p, (int64_t)in.n_pad, in.off, in.yv.data(), in.xp.data(), o, taus, n_taus, rec.data(),
+	                                             nullptr, out_error))
 		return false;
 	for (size_t t = 0; t < n_taus; ++t) {
 		const double *r = rec.data() + t * (p + 6);
 		const int status = (int)r[p + 5];
-		if (status != ANOFOX_ERROR_SUCCESS) set_scalar_fit_error(status, n, p, yv, cols, out_error);
-		if (status != ANOFOX_ERROR_SUCCESS || !fill_scalar_result(r, p, &out_results[t], out_error)) {
+		if (status != ANOFOX_ERROR_SUCCESS) set_quantile_fit_error(status, in, out_error);
+		if (status != ANOFOX_ERROR_SUCCESS || !fill_quantile_result(r, p, &out_results[t], out_error)) {
 			for (size_t u = 0; u < t; ++u) anofox_free_quantile_result(&out_results[u]);
 			return false;
 		}

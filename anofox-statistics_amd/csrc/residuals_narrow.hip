@@ -223,18 +223,8 @@ hipError_t launch_p(const ResidualArgs &a, hipStream_t stream) {
 
 hipError_t launch_residuals_narrow(const ResidualArgs &a, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
-	switch (a.p) {
-	case 0: return launch_p<0>(a, stream);
-	case 1: return launch_p<1>(a, stream);
-	case 2: return launch_p<2>(a, stream);
-	case 3: return launch_p<3>(a, stream);
-	case 4: return launch_p<4>(a, stream);
-	case 5: return launch_p<5>(a, stream);
-	case 6: return launch_p<6>(a, stream);
-	case 7: return launch_p<7>(a, stream);
-	case 8: return launch_p<8>(a, stream);
-	default: return hipErrorInvalidValue;
-	}
+	if (a.p == 0) return launch_p<0>(a, stream);
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_p<P()>(a, stream); });
 }
 
 } // namespace anofox

@@ -21,7 +21,7 @@
 using namespace anofox;
 
 #include "host_stage.h"
-#include "row_slabs.h"
+#include "scalar_fit.h"
 
 using namespace anofox::host;
 using namespace anofox::rls;
@@ -196,12 +196,7 @@ bool launch_rls_batch(AnofoxHipContext *ctx, int64_t G, size_t p, const int64_t 
 	hipStream_t st = ctx->stream;
 	if (!a.wave_all) {
 		const dim3 grid((unsigned)((G + 63) / 64));
-		switch (p) {
-#define RLS_LANE(P) \
-	case P: hipLaunchKernelGGL(rls_batch_lane_kernel<P>, grid, dim3(64), 0, st, a); break;
-			RLS_LANE(1) RLS_LANE(2) RLS_LANE(3) RLS_LANE(4) RLS_LANE(5) RLS_LANE(6) RLS_LANE(7) RLS_LANE(8)
-#undef RLS_LANE
-		}
+		dispatch_narrow((int)p, 0, [&](auto P) { hipLaunchKernelGGL(rls_batch_lane_kernel<P()>, grid, dim3(64), 0, st, a); return 0; });
 		if (hip_fail(hipGetLastError(), "rls_batch_lane_kernel", e)) return false;
 	}
 	if (!a.wave_all && max_rows >= 0 && max_rows <= a.long_rows) return true; // the host knows there is no long group
@@ -240,12 +235,7 @@ bool launch_rls_frames(AnofoxHipContext *ctx, int64_t n_frames, size_t p, const 
 	hipStream_t st = ctx->stream;
 	if (p <= (size_t)kNarrowMaxP) {
 		const dim3 grid((unsigned)((n_frames + 63) / 64));
-		switch (p) {
-#define RLS_LANE(P) \
-	case P: hipLaunchKernelGGL(rls_frames_lane_kernel<P>, grid, dim3(64), 0, st, a); break;
-			RLS_LANE(1) RLS_LANE(2) RLS_LANE(3) RLS_LANE(4) RLS_LANE(5) RLS_LANE(6) RLS_LANE(7) RLS_LANE(8)
-#undef RLS_LANE
-		}
+		dispatch_narrow((int)p, 0, [&](auto P) { hipLaunchKernelGGL(rls_frames_lane_kernel<P()>, grid, dim3(64), 0, st, a); return 0; });
 		return !hip_fail(hipGetLastError(), "rls_frames_lane_kernel", e);
 	}
 	static std::once_flag once;
@@ -258,17 +248,7 @@ bool launch_rls_frames(AnofoxHipContext *ctx, int64_t n_frames, size_t p, const 
 
 bool check_common(int64_t G, size_t p, int64_t n_rows, const void *off, const void *y, const double *const *x_cols, const void *out,
                   AnofoxError *e) {
-	if (G < 0 || n_rows < 0) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "negative n_groups or n_rows"); return false; }
-	if (p == 0 || !x_cols) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
-	if (p > (size_t)kWideMaxP) {
-		set_error(e, ANOFOX_ERROR_INVALID_INPUT,
-		          "n_features = " + std::to_string(p) + " exceeds the supported maximum of " + std::to_string(kWideMaxP));
-		return false;
-	}
-	if (G > 0 && (!off || !y || !out)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "row_offsets, y or an output is NULL"); return false; }
-	for (size_t j = 0; j < p; ++j)
-		if (G > 0 && !x_cols[j]) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "x column pointer is NULL"); return false; }
-	return true;
+	return check_batch_args(G, p, n_rows, off, y, x_cols, out, kWideMaxP, nullptr, "row_offsets, y or an output is NULL", false, e);
 }
 
 bool check_frame(const AnofoxHipWindowFrame &f, AnofoxError *e) {
@@ -308,12 +288,7 @@ bool window_frames_device(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_
 		a.o = rls_params(o);
 		a.pred = d_pred;
 		const dim3 grid((unsigned)((G + 63) / 64));
-		switch (p) {
-#define RLS_LANE(P) \
-	case P: hipLaunchKernelGGL(rls_expanding_lane_kernel<P>, grid, dim3(64), 0, ctx->stream, d_off, G, a); break;
-			RLS_LANE(1) RLS_LANE(2) RLS_LANE(3) RLS_LANE(4) RLS_LANE(5) RLS_LANE(6) RLS_LANE(7) RLS_LANE(8)
-#undef RLS_LANE
-		}
+		dispatch_narrow((int)p, 0, [&](auto P) { hipLaunchKernelGGL(rls_expanding_lane_kernel<P()>, grid, dim3(64), 0, ctx->stream, d_off, G, a); return 0; });
 		return !hip_fail(hipGetLastError(), "rls_expanding_lane_kernel", e);
 	}
 	const size_t b = Stage::bytes((size_t)n_rows, sizeof(int64_t));
@@ -323,12 +298,6 @@ bool window_frames_device(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_
 	             "frames_spec_kernel", e))
 		return false;
 	return launch_rls_frames(ctx, n_rows, p, d_y, x_cols, lo, hi, o, d_pred, e);
-}
-
-std::string fmt_g(double v) {
-	char buf[64];
-	snprintf(buf, sizeof buf, "%g", v);
-	return buf;
 }
 
 } // namespace
@@ -356,26 +325,11 @@ bool anofox_hip_rls_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size
 	if (!(ctx = host_context(ctx, out_error))) return false;
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
-	const size_t p = n_features, core_len = p + 6;
-	std::vector<int64_t> off;
-	hipStream_t st = ctx->stream;
-	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
-		g1 = next_row_slab(row_offsets, n_groups, g0, kHostSlabRows, off);
-		const int64_t G = g1 - g0, r0 = row_offsets[g0], R = off[(size_t)G];
-		int64_t *d_off;
-		StagedColumns c;
-		double *d_core;
-		if (!stage_call(ctx, out_error, [&](Stage &s) {
-			    d_off = s.put(off.data(), (size_t)G + 1);
-			    c = s.columns(p, r0, R, x_cols, y, nullptr, nullptr, kPlainColumns);
-			    d_core = s.take<double>((size_t)G * core_len);
-		    }))
-			return false;
-		if (!launch_rls_batch(ctx, G, p, d_off, c.y, c.x, nullptr, options, d_core, out_error, max_group_rows(G, off.data()))) return false;
-		if (!d2h(core + (size_t)g0 * core_len, d_core, (size_t)G * core_len * sizeof(double), st, out_error)) return false;
-		if (hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", out_error)) return false;
-	}
-	return true;
+	const size_t p = n_features;
+	return fit_slabs_host(ctx, n_groups, p, row_offsets, y, x_cols, nullptr, SlabOutputs{core, p + 6}, kPlainSlab, out_error,
+	                      [&](int64_t G, int64_t, const int64_t *off, const int64_t *d_off, const StagedColumns &c, double *d_core, int32_t *, double *) {
+		                      return launch_rls_batch(ctx, G, p, d_off, c.y, c.x, nullptr, options, d_core, out_error, max_group_rows(G, off));
+	                      });
 }
 
 bool anofox_hip_rls_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
@@ -523,76 +477,35 @@ bool anofox_rls_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count,
 	if (!x || x_count == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "x is NULL or empty"); return false; }
 	if (x[0].len == 0) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "Empty input: x[0] cannot be empty"); return false; }
 	if (y.len != x[0].len) {
-		set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH,
-		          "Dimension mismatch: y has " + std::to_string(y.len) + " elements, X has " + std::to_string(x[0].len) + " rows");
+		set_dimension_mismatch(y.len, x[0].len, out_error);
 		return false;
 	}
-	const size_t p = x_count, n = y.len;
-	for (size_t j = 1; j < p; ++j) {
-		if (x[j].len != n) {
-			set_error(out_error, ANOFOX_ERROR_DIMENSION_MISMATCH,
-			          "Dimension mismatch: y has " + std::to_string(n) + " elements, X has " + std::to_string(x[j].len) + " rows");
-			return false;
-		}
-	}
+	const size_t p = x_count;
+	if (!check_column_lengths(y.len, x + 1, p - 1, out_error)) return false;
 	if (p > (size_t)kWideMaxP) {
 		set_error(out_error, ANOFOX_ERROR_INVALID_INPUT,
 		          "RLS fit: more than " + std::to_string(kWideMaxP) + " features are not supported by the GPU path");
 		return false;
 	}
-	const size_t n_pad = n < 2 ? 2 : n;
-	std::vector<std::vector<double>> cols(p);
-	std::vector<double> yv;
-	expand_data_array(y, yv, n_pad);
-	std::vector<const double *> xp(p);
-	for (size_t j = 0; j < p; ++j) {
-		expand_data_array(x[j], cols[j], n_pad);
-		xp[j] = cols[j].data();
-	}
+	const ScalarFitInput in(y, x, x_count);
 	AnofoxHipRlsBatchOptions o;
 	memset(&o, 0, sizeof o);
 	o.forgetting_factor = options.forgetting_factor;
 	o.fit_intercept = options.fit_intercept;
 	o.initial_p_diagonal = options.initial_p_diagonal;
-	const int64_t off[2] = {0, (int64_t)n_pad};
 	std::vector<double> core(p + 6);
-	if (!anofox_hip_rls_fit_batch_host(nullptr, 1, p, (int64_t)n_pad, off, yv.data(), xp.data(), o, core.data(), out_error)) return false;
+	if (!anofox_hip_rls_fit_batch_host(nullptr, 1, p, (int64_t)in.n_pad, in.off, in.yv.data(), in.xp.data(), o, core.data(), out_error)) return false;
 	const int status = (int)core[p + 5];
-	if (status != ANOFOX_ERROR_SUCCESS) {
-		size_t n_valid = 0;
-		for (size_t i = 0; i < n; ++i) {
-			bool ok = isfinite(yv[i]);
-			for (size_t j = 0; ok && j < p; ++j) ok = isfinite(cols[j][i]);
-			n_valid += ok;
-		}
-		std::string msg;
-		switch (status) { // crates/anofox-stats-core/src/errors.rs, rls.rs:56-69
-		case ANOFOX_ERROR_NO_VALID_DATA: msg = "All rows filtered due to NULL/NaN values"; break;
-		case ANOFOX_ERROR_INSUFFICIENT_DATA:
-			msg = "Insufficient data: " + std::to_string(n_valid) + " rows, " + std::to_string(p) + " features (need rows > features)";
-			break;
-		case ANOFOX_ERROR_INVALID_INPUT:
-			msg = !(options.forgetting_factor <= 0.0 || options.forgetting_factor > 1.0)
-			          ? "Invalid input: initial_p_diagonal must be > 0 (got " + fmt_g(options.initial_p_diagonal) + ")"
-			          : "Invalid input: forgetting_factor must be in (0, 1] (got " + fmt_g(options.forgetting_factor) + ")";
-			break;
-		default: msg = "RLS fit failed on the GPU path"; break;
-		}
-		set_error(out_error, (AnofoxErrorCode)status, msg);
+	if (status != ANOFOX_ERROR_SUCCESS) { // rls.rs:56-69
+		std::string other = "RLS fit failed on the GPU path";
+		if (status == ANOFOX_ERROR_INVALID_INPUT)
+			other = !(options.forgetting_factor <= 0.0 || options.forgetting_factor > 1.0)
+			            ? "Invalid input: initial_p_diagonal must be > 0 (got " + fmt_g(options.initial_p_diagonal) + ")"
+			            : "Invalid input: forgetting_factor must be in (0, 1] (got " + fmt_g(options.forgetting_factor) + ")";
+		set_scalar_fit_error(status, (AnofoxErrorCode)status, in, other, out_error);
 		return false;
 	}
-	double *coef = (double *)malloc(p * sizeof(double));
-	if (!coef) { set_error(out_error, ANOFOX_ERROR_ALLOCATION_FAILURE, "Failed to allocate coefficients"); return false; }
-	memcpy(coef, core.data(), p * sizeof(double));
-	out_core->coefficients = coef;
-	out_core->coefficients_len = p;
-	out_core->intercept = core[p];
-	out_core->r_squared = core[p + 1];
-	out_core->adj_r_squared = core[p + 2];
-	out_core->residual_std_error = core[p + 3];
-	out_core->n_observations = (size_t)core[p + 4];
-	out_core->n_features = p;
-	return true;
+	return fill_scalar_result(core.data(), p, out_core, out_error);
 }
 
 } // extern "C"

@@ -21,5 +21,17 @@ inline int64_t next_row_slab(const int64_t *row_offsets, int64_t n_groups, int64
 	return g1;
 }
 
+// The slabs of a batch in order: fn(g0, G, r0, R, rebased) for the G groups from g0, whose R rows begin at row r0 of the
+// caller's arrays; `rebased` points at the slab's G + 1 offsets.  Stops at the first `false` and returns it.
+template <class Fn>
+bool for_each_row_slab(const int64_t *row_offsets, int64_t n_groups, int64_t slab_rows, Fn &&fn) {
+	std::vector<int64_t> off;
+	for (int64_t g0 = 0, g1; g0 < n_groups; g0 = g1) {
+		g1 = next_row_slab(row_offsets, n_groups, g0, slab_rows, off);
+		if (!fn(g0, g1 - g0, row_offsets[g0], off[(size_t)(g1 - g0)], (const int64_t *)off.data())) return false;
+	}
+	return true;
+}
+
 } // namespace host
 } // namespace anofox

@@ -156,17 +156,7 @@ hipError_t launch_solve_p(const BatchArgs &a, hipStream_t stream) {
 
 hipError_t launch_solve_narrow(const BatchArgs &a, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
-	switch (a.p) {
-	case 1: return launch_solve_p<1>(a, stream);
-	case 2: return launch_solve_p<2>(a, stream);
-	case 3: return launch_solve_p<3>(a, stream);
-	case 4: return launch_solve_p<4>(a, stream);
-	case 5: return launch_solve_p<5>(a, stream);
-	case 6: return launch_solve_p<6>(a, stream);
-	case 7: return launch_solve_p<7>(a, stream);
-	case 8: return launch_solve_p<8>(a, stream);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_solve_p<P()>(a, stream); });
 }
 
 template <int P>
@@ -180,17 +170,7 @@ hipError_t launch_refine_p(const BatchArgs &a, int steps, hipStream_t stream) {
 
 hipError_t launch_refine_fused_narrow(const BatchArgs &a, int steps, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
-	switch (a.p) {
-	case 1: return launch_refine_p<1>(a, steps, stream);
-	case 2: return launch_refine_p<2>(a, steps, stream);
-	case 3: return launch_refine_p<3>(a, steps, stream);
-	case 4: return launch_refine_p<4>(a, steps, stream);
-	case 5: return launch_refine_p<5>(a, steps, stream);
-	case 6: return launch_refine_p<6>(a, steps, stream);
-	case 7: return launch_refine_p<7>(a, steps, stream);
-	case 8: return launch_refine_p<8>(a, steps, stream);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_refine_p<P()>(a, steps, stream); });
 }
 
 } // namespace anofox

@@ -145,18 +145,10 @@ hipError_t launch_vif_narrow(const double *moments, const int64_t *row_offsets, 
                              double *out, hipStream_t stream) {
 	if (n_groups <= 0) return hipSuccess;
 	const dim3 grid((unsigned)((n_groups + 63) / 64)), block(64);
-	switch (p) {
-	case 1: hipLaunchKernelGGL((vif_narrow_kernel<1>), grid, block, 0, stream, moments, row_offsets, n_groups, min_rows, out); break;
-	case 2: hipLaunchKernelGGL((vif_narrow_kernel<2>), grid, block, 0, stream, moments, row_offsets, n_groups, min_rows, out); break;
-	case 3: hipLaunchKernelGGL((vif_narrow_kernel<3>), grid, block, 0, stream, moments, row_offsets, n_groups, min_rows, out); break;
-	case 4: hipLaunchKernelGGL((vif_narrow_kernel<4>), grid, block, 0, stream, moments, row_offsets, n_groups, min_rows, out); break;
-	case 5: hipLaunchKernelGGL((vif_narrow_kernel<5>), grid, block, 0, stream, moments, row_offsets, n_groups, min_rows, out); break;
-	case 6: hipLaunchKernelGGL((vif_narrow_kernel<6>), grid, block, 0, stream, moments, row_offsets, n_groups, min_rows, out); break;
-	case 7: hipLaunchKernelGGL((vif_narrow_kernel<7>), grid, block, 0, stream, moments, row_offsets, n_groups, min_rows, out); break;
-	case 8: hipLaunchKernelGGL((vif_narrow_kernel<8>), grid, block, 0, stream, moments, row_offsets, n_groups, min_rows, out); break;
-	default: return hipErrorInvalidValue;
-	}
-	return hipGetLastError();
+	return dispatch_narrow(p, hipErrorInvalidValue, [&](auto P) {
+		hipLaunchKernelGGL((vif_narrow_kernel<P()>), grid, block, 0, stream, moments, row_offsets, n_groups, min_rows, out);
+		return hipGetLastError();
+	});
 }
 
 } // namespace anofox

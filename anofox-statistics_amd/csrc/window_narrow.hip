@@ -657,33 +657,13 @@ hipError_t launch_tcrit_table(double *table, int cap, double prob, hipStream_t s
 hipError_t launch_window_predict(const WindowArgs &a, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
 	if (a.frame_start < a.frame_end || a.frame_start == -kFrameUnbounded || a.frame_end == kFrameUnbounded) return hipErrorInvalidValue;
-	switch (a.p) {
-	case 1: return launch_window_p<1>(a, stream);
-	case 2: return launch_window_p<2>(a, stream);
-	case 3: return launch_window_p<3>(a, stream);
-	case 4: return launch_window_p<4>(a, stream);
-	case 5: return launch_window_p<5>(a, stream);
-	case 6: return launch_window_p<6>(a, stream);
-	case 7: return launch_window_p<7>(a, stream);
-	case 8: return launch_window_p<8>(a, stream);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_window_p<P()>(a, stream); });
 }
 
 hipError_t launch_window_predict_en(const WindowArgs &a, const EnParams &en, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
 	if (a.frame_start < a.frame_end || a.frame_start == -kFrameUnbounded || a.frame_end == kFrameUnbounded) return hipErrorInvalidValue;
-	switch (a.p) {
-	case 1: return launch_window_en_p<1>(a, en, stream);
-	case 2: return launch_window_en_p<2>(a, en, stream);
-	case 3: return launch_window_en_p<3>(a, en, stream);
-	case 4: return launch_window_en_p<4>(a, en, stream);
-	case 5: return launch_window_en_p<5>(a, en, stream);
-	case 6: return launch_window_en_p<6>(a, en, stream);
-	case 7: return launch_window_en_p<7>(a, en, stream);
-	case 8: return launch_window_en_p<8>(a, en, stream);
-	default: return hipErrorInvalidValue;
-	}
+	return dispatch_narrow(a.p, hipErrorInvalidValue, [&](auto P) { return launch_window_en_p<P()>(a, en, stream); });
 }
 
 } // namespace anofox

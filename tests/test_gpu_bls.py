@@ -121,6 +121,26 @@ def test_statuses_and_shortcut(p):
         assert np.isnan(np.delete(rec, p + 5, axis=1)).all()
 
 
+@pytest.mark.parametrize("p", [1, 8, 9, 64, 65, 128])
+def test_five_kinds_of_group_at_the_path_boundaries(p):
+    """Both ends of the narrow path, the first wide width and both sides of the wide kernel's one / two columns per lane: a plain
+    group of 2p + 3 rows, an exact fit inside the box (the moment ssr cancels: the rows give it), every column constant (the
+    shortcut), p rows (status 6) and an empty group (status 100), against the restatement, twice with identical bytes."""
+    pkg = import_pkg()
+    rng = np.random.default_rng(4500 + p)
+    plain = br.make_case(rng, 2 * p + 3, p)
+    _, Xe = br.make_case(rng, 2 * p + 25, p)
+    exact = (Xe @ rng.uniform(0.5, 2.0, size=p) + 4.0, Xe)
+    groups = [plain, exact, (plain[0].copy(), np.full((2 * p + 3, p), 3.0)), (plain[0][:p].copy(), plain[1][:p].copy()),
+              (np.zeros(0), np.zeros((0, p)))]
+    kw = dict(fit_intercept=True, lower_bound=0.0, upper_bound=3.0)
+    rec, its = _check(pkg, groups, f"p={p} five kinds", **kw)
+    assert list(rec[:, p + 5]) == [0, 0, 0, 6 if p > 1 else 100, 100]    # (p = 1: the group of p rows has fewer than 2)
+    assert rec[1, p + 4] == 0 and np.isnan(rec[2, :p]).all()    # (the exact fit lies inside the box: no active bound)
+    rec2, its2 = _fit(pkg, *_batch(groups), **kw)
+    assert rec.tobytes() == rec2.tobytes() and its.tobytes() == its2.tobytes()
+
+
 @pytest.mark.parametrize("p", [3, 8, 20, 64])
 def test_exact_fits_take_ssr_from_the_rows(p):
     """y = X beta exactly with beta inside the box: the moment ssr cancels, the rows give it (1e-12 absolute)."""

@@ -249,3 +249,36 @@ def test_several_slabs_of_wide_records_match_single_slab_calls():
     assert np.all(core[:, p + 5] == 0) and np.all(its > 0)
     assert np.array_equal(core, np.vstack([c1, c2]), equal_nan=True)
     assert np.array_equal(its, np.concatenate([i1, i2]))
+
+
+@pytest.mark.parametrize("p", [1, 8, 9, 64, 65, 128])
+def test_five_kinds_of_group_at_the_path_boundaries(p):
+    """Both ends of the narrow path, the first wide width and both sides of the wide kernel's one / two columns per lane: a plain
+    group of 2p + 3 rows, an exact fit (the moment identity cancels: the rows give the statistics), every column constant (the
+    shortcut), p rows (status 6) and an empty group (status 100; the reference takes no empty input), twice with identical bytes."""
+    pkg = import_pkg()
+    rng = np.random.default_rng(900 + p)
+    n_plain, n_exact = 2 * p + 3, 5 * p + 40
+    Xp = rng.normal(size=(n_plain, p)) * 3.0 + 10.0
+    Xe = rng.normal(size=(n_exact, p)) * 3.0 + 10.0
+    blocks = [(Xp @ rng.normal(size=p) + 2.0 + 0.5 * rng.normal(size=n_plain), Xp), (Xe @ rng.normal(size=p) + 2.0, Xe),
+              (rng.normal(size=n_plain), np.full((n_plain, p), 2.5)), (rng.normal(size=p), rng.normal(size=(p, p))),
+              (np.zeros(0), np.zeros((0, p)))]
+    off = np.concatenate([[0], np.cumsum([len(b[0]) for b in blocks])]).astype(np.int64)
+    y, X = np.concatenate([b[0] for b in blocks]), np.concatenate([b[1] for b in blocks])
+    kw = dict(alpha=1e-6, l1_ratio=0.5, tolerance=1e-13, max_iterations=100000)
+    core, its = _fit(pkg, off, y, X, **kw)
+    assert list(core[:, p + 5]) == [0, 0, 0, 6 if p > 1 else 100, 100]    # (p = 1: the group of p rows has fewer than 2)
+    for g in range(4):
+        ref = en_reference(blocks[g][0], blocks[g][1], 1e-6, 0.5)
+        assert core[g, p + 5] == ref[p + 5], g
+        if g == 1:
+            assert 1.0 - ref[p + 1] < 1e-9                      # the regime of the row path
+            err = np.linalg.norm(core[g, :p] - ref[:p]) / max(np.linalg.norm(ref[:p]), 1.0)
+            assert err <= 1e-8 and abs(core[g, p] - ref[p]) <= 1e-8 * max(abs(ref[p]), 1.0)
+            assert abs(core[g, p + 1] - ref[p + 1]) <= 1e-12 and abs(core[g, p + 2] - ref[p + 2]) <= 1e-12 and core[g, p + 4] == ref[p + 4]
+        else:
+            assert np.allclose(core[g], ref, rtol=1e-8, atol=1e-10, equal_nan=True), (g, core[g], ref)
+    assert np.all(np.isnan(core[2, :p])) and core[2, p + 1] == 0.0 and np.all(np.isnan(core[3:, :p + 5]))
+    core2, its2 = _fit(pkg, off, y, X, **kw)
+    assert core.tobytes() == core2.tobytes() and its.tobytes() == its2.tobytes()
