@@ -189,6 +189,33 @@ class AnofoxHipGlmBatchOptions(C.Structure):
                 ("lambda_", C.c_double), ("compute_inference", C.c_bool), ("confidence_level", C.c_double)]
 
 
+AFT_WEIBULL, AFT_LOGNORMAL, AFT_LOGLOGISTIC, AFT_EXPONENTIAL = 0, 1, 2, 3
+
+
+class AnofoxAftOptions(C.Structure):  # anofox_stats_ffi.h:2304-2315, 64 bytes
+    _fields_ = [("dist", C.c_int), ("fit_intercept", C.c_bool), ("max_iterations", C.c_uint32), ("tolerance", C.c_double),
+                ("compute_inference", C.c_bool), ("confidence_level", C.c_double), ("priors", C.POINTER(AnofoxPriorSpec)),
+                ("priors_len", C.c_size_t), ("vcov", C.c_int)]
+
+
+class AnofoxAftFitResultCore(C.Structure):  # anofox_stats_ffi.h:2320-2337, 104 bytes
+    _fields_ = [("coefficients", _DP), ("coefficients_len", C.c_size_t), ("intercept", C.c_double), ("scale", C.c_double),
+                ("log_likelihood", C.c_double), ("null_log_likelihood", C.c_double), ("aic", C.c_double), ("bic", C.c_double),
+                ("n_observations", C.c_size_t), ("n_events", C.c_size_t), ("n_censored", C.c_size_t), ("n_features", C.c_size_t),
+                ("iterations", C.c_uint32), ("converged", C.c_bool)]
+
+
+class AnofoxAftInference(C.Structure):  # anofox_stats_ffi.h:2342-2354, 72 bytes
+    _fields_ = [("std_errors", _DP), ("z_values", _DP), ("p_values", _DP), ("ci_lower", _DP), ("ci_upper", _DP),
+                ("len", C.c_size_t), ("confidence_level", C.c_double), ("intercept_std_error", C.c_double),
+                ("log_scale_std_error", C.c_double)]
+
+
+class AnofoxHipAftBatchOptions(C.Structure):
+    _fields_ = [("dist", C.c_int), ("fit_intercept", C.c_int), ("max_iterations", C.c_uint32), ("tolerance", C.c_double),
+                ("compute_inference", C.c_int), ("confidence_level", C.c_double)]
+
+
 # every symbol include/anofox_stats_hip.h declares: name -> (restype, argtypes)
 _ERRP = C.POINTER(AnofoxError)
 _CTX = C.c_void_p
@@ -476,6 +503,18 @@ SYMBOLS = {
                                        C.POINTER(AnofoxGlmFitResultCore), C.POINTER(AnofoxFitResultInference),
                                        C.POINTER(AnofoxLogisticFitExtras), _ERRP]),
     "anofox_free_glm_result": (None, [C.POINTER(AnofoxGlmFitResultCore)]),
+    "anofox_hip_aft_record_len": (C.c_size_t, [C.c_size_t]),
+    "anofox_hip_aft_fit_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p),
+                                                   C.c_void_p, AnofoxHipAftBatchOptions, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_aft_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP, C.POINTER(_DP), _DP,
+                                                 AnofoxHipAftBatchOptions, _DP, _DP, _ERRP]),
+    "anofox_hip_aft_test_hooks": (None, [C.c_int64]),
+    "anofox_aft_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxDataArray, AnofoxAftOptions,
+                                  C.POINTER(AnofoxAftFitResultCore), C.POINTER(AnofoxAftInference), _ERRP]),
+    "anofox_free_aft_result": (None, [C.POINTER(AnofoxAftFitResultCore)]),
+    "anofox_free_aft_inference": (None, [C.POINTER(AnofoxAftInference)]),
+    "anofox_aft_cdf": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_int]),
+    "anofox_aft_quantile": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_int]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "anofox_hip_host_free": (None, [C.c_void_p]),
 }

@@ -1,6 +1,7 @@
 // host_math.h — scalar Student-t quantile for the host-side helpers (anofox_t_critical,
 // anofox_predict_with_interval).  Same formulas as device_math.h; the reference takes the value from
-// statrs::StudentsT::inverse_cdf (crates/anofox-stats-ffi/src/lib.rs:2217-2231).
+// statrs::StudentsT::inverse_cdf (crates/anofox-stats-ffi/src/lib.rs:2217-2231).  And the standard normal quantile of the
+// GLM and AFT families' confidence intervals (glm.hip, aft.hip).
 #pragma once
 #include <math.h>
 
@@ -69,6 +70,35 @@ inline double t_quantile_upper(double prob, double df) {
 		t = tn;
 	}
 	return t;
+}
+
+// the standard normal quantile: Acklam's rational approximation, then two Halley steps on erfc (full double precision)
+inline double normal_quantile(double prob) {
+	if (!(prob > 0.0 && prob < 1.0)) return NAN;
+	static const double a[] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02,
+	                           1.383577518672690e+02,  -3.066479806614716e+01, 2.506628277459239e+00};
+	static const double b[] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02, 6.680131188771972e+01,
+	                           -1.328068155288572e+01};
+	static const double c[] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00,
+	                           -2.549732539343734e+00, 4.374664141464968e+00,  2.938163982698783e+00};
+	static const double d[] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00};
+	double x;
+	if (prob < 0.02425) {
+		const double q = sqrt(-2.0 * log(prob));
+		x = (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.0);
+	} else if (prob > 1.0 - 0.02425) {
+		const double q = sqrt(-2.0 * log(1.0 - prob));
+		x = -(((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1.0);
+	} else {
+		const double q = prob - 0.5, r = q * q;
+		x = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
+		    (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1.0);
+	}
+	for (int it = 0; it < 2; ++it) {
+		const double e = 0.5 * erfc(-x / sqrt(2.0)) - prob, u = e * sqrt(2.0 * M_PI) * exp(x * x / 2.0);
+		x = x - u / (1.0 + x * u / 2.0);
+	}
+	return x;
 }
 
 } // namespace hostmath

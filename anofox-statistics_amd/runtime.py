@@ -360,6 +360,18 @@ class Context:
         from .glm import glm_fit_batch_host
         return glm_fit_batch_host(row_offsets, y, x_cols, options, offset, inference, ctx=self, threshold=threshold)
 
+    # ---- accelerated failure time models (aft.py) --------------------------------------------------
+    def aft_fit_batch_device(self, row_offsets, time, x_cols: Sequence, event, options: _abi.AnofoxHipAftBatchOptions,
+                             inference: bool = False, use_current_torch_stream: bool = True):
+        """Grouped AFT fits on CUDA tensors through the fused Newton kernel (aft.aft_fit_batch_device)."""
+        from .aft import aft_fit_batch_device
+        return aft_fit_batch_device(self, row_offsets, time, x_cols, event, options, inference, use_current_torch_stream)
+
+    def aft_fit_batch_host(self, row_offsets, time, x_cols: Sequence, event, options: _abi.AnofoxHipAftBatchOptions,
+                           inference: bool = False):
+        from .aft import aft_fit_batch_host
+        return aft_fit_batch_host(row_offsets, time, x_cols, event, options, inference, ctx=self)
+
 
 class AggState:
     """The streaming aggregate state of {ols,ridge,wls}_fit_agg on the GPU (anofox_hip_agg_state_*): one O(p^2)

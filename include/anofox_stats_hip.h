@@ -438,6 +438,80 @@ ANOFOX_HIP_API bool anofox_logistic_fit(AnofoxDataArray y, const AnofoxDataArray
                          AnofoxLogisticFitExtras *out_extras, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_glm_result(AnofoxGlmFitResultCore *result);
 
+/* replaces AnofoxAftDistribution, anofox_stats_ffi.h:2293-2299: the distribution of T; exponential is Weibull with scale 1 */
+typedef enum {
+	ANOFOX_AFT_WEIBULL = 0,
+	ANOFOX_AFT_LOGNORMAL = 1,
+	ANOFOX_AFT_LOGLOGISTIC = 2,
+	ANOFOX_AFT_EXPONENTIAL = 3
+} AnofoxAftDistribution;
+
+/* replaces AnofoxAftOptions, anofox_stats_ffi.h:2304-2315 — 64 bytes: dist @0, fit_intercept @4, max_iterations @8,
+ * tolerance @16, compute_inference @24, confidence_level @32, priors @40, priors_len @48, vcov @56 */
+typedef struct {
+	AnofoxAftDistribution dist;
+	bool fit_intercept;
+	uint32_t max_iterations;
+	double tolerance;
+	bool compute_inference;
+	double confidence_level;
+	const AnofoxPriorSpec *priors; /* not built: has to be NULL */
+	size_t priors_len;
+	AnofoxVcovType vcov; /* every value gives the same covariance without priors */
+} AnofoxAftOptions;
+
+/* replaces AnofoxAftFitResultCore, anofox_stats_ffi.h:2320-2337 — 104 bytes: coefficients @0, coefficients_len @8, intercept @16,
+ * scale @24, log_likelihood @32, null_log_likelihood @40, aic @48, bic @56, n_observations @64, n_events @72, n_censored @80,
+ * n_features @88, iterations @96, converged @100 */
+typedef struct {
+	double *coefficients; /* on the log-time scale; malloc'ed by the callee, released by anofox_free_aft_result */
+	size_t coefficients_len;
+	double intercept; /* NaN without an intercept */
+	double scale;     /* sigma; exactly 1.0 for the exponential distribution */
+	double log_likelihood;
+	double null_log_likelihood; /* of the intercept-only model; NaN without an intercept */
+	double aic;
+	double bic;
+	size_t n_observations;
+	size_t n_events;
+	size_t n_censored;
+	size_t n_features;
+	uint32_t iterations;
+	bool converged;
+} AnofoxAftFitResultCore;
+
+/* replaces AnofoxAftInference, anofox_stats_ffi.h:2342-2354 — 72 bytes: five arrays @0..32, len @40, confidence_level @48,
+ * intercept_std_error @56, log_scale_std_error @64 */
+typedef struct {
+	double *std_errors; /* the five arrays: one entry per feature, released by anofox_free_aft_inference */
+	double *z_values;
+	double *p_values;
+	double *ci_lower;
+	double *ci_upper;
+	size_t len;
+	double confidence_level;
+	double intercept_std_error; /* NaN without an intercept */
+	double log_scale_std_error; /* NaN when the scale is fixed */
+} AnofoxAftInference;
+
+/* replace anofox_aft_fit / anofox_free_aft_result / anofox_free_aft_inference / anofox_aft_cdf / anofox_aft_quantile,
+ * anofox_stats_ffi.h:2356-2383 (over crates/anofox-stats-core/src/models/aft.rs and aft_dist.rs): one group through
+ * anofox_hip_aft_fit_batch_host below, with anofox_ols_fit's conventions.  event: 1 = observed, 0 = right-censored.  Non-NULL
+ * priors: false with ANOFOX_ERROR_INVALID_INPUT and "aft: priors are not built"; more than 32 features: "aft: n_features > 32
+ * is not built"; a tolerance that is not finite and positive, max_iterations = 0, an unknown dist, or a confidence_level outside
+ * (0, 1) with inference: "aft: invalid options"; all three before any device is touched.  A group status other than 0 is false
+ * with that status as the error code.  The contract: DESIGN.md §1 "Accelerated failure time models".  A call that fails leaves
+ * out_core zeroed (NaN in its doubles) and out_inference reset to {NULLs, len 0, NaNs}: nothing to free.
+ * anofox_aft_cdf: P(T <= t) at the linear predictor eta and the scale, 0 for t <= 0.  anofox_aft_quantile: the p-quantile of T,
+ * p clamped to [1e-12, 1 - 1e-12].  Plain host functions. */
+ANOFOX_HIP_API bool anofox_aft_fit(AnofoxDataArray time, const AnofoxDataArray *x, size_t x_count, AnofoxDataArray event,
+                    AnofoxAftOptions options, AnofoxAftFitResultCore *out_core, AnofoxAftInference *out_inference,
+                    AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_aft_result(AnofoxAftFitResultCore *result);
+ANOFOX_HIP_API void anofox_free_aft_inference(AnofoxAftInference *inf);
+ANOFOX_HIP_API double anofox_aft_cdf(double t, double eta, double scale, AnofoxAftDistribution dist);
+ANOFOX_HIP_API double anofox_aft_quantile(double p, double eta, double scale, AnofoxAftDistribution dist);
+
 #endif /* ANOFOX_STATS_FFI_H */
 
 /* ------------------------------------------------------------------------ */
@@ -1097,6 +1171,50 @@ ANOFOX_HIP_API void anofox_hip_glm_window_test_hooks(int64_t run_length, int64_t
  * scratch rows per wavefront}.  Waits for the context's stream.  Per context, reset by every GLM window call on it.
  */
 ANOFOX_HIP_API bool anofox_hip_glm_window_stats(AnofoxHipContext *ctx, int64_t *out, AnofoxError *out_error);
+
+/*
+ * Grouped accelerated failure time (AFT) survival regression with right censoring (anofox_aft_fit and the aggregate
+ * aft_fit_agg): log T = x'beta + sigma W.  Per group, over the rows whose time, event and x are all finite, THE stationary point
+ * of the censored log-likelihood in (intercept, beta, log sigma), by the reference's Newton loop with step halving fused into
+ * one kernel, one wavefront per group (DESIGN.md §1 "Accelerated failure time models").  event: 1 = the time is an observed
+ * event, 0 = the row is right-censored at it.  1 <= n_features <= 32; more fails the call.  dist: ANOFOX_AFT_WEIBULL 0,
+ * ANOFOX_AFT_LOGNORMAL 1, ANOFOX_AFT_LOGLOGISTIC 2, ANOFOX_AFT_EXPONENTIAL 3 (Weibull with sigma = 1, not estimated).
+ * Records (anofox_hip_aft_record_len(p) = p + 13 doubles):
+ *   aft[g] = { coefficients[0..p), intercept (NaN without one), scale (exactly 1 for exponential), log_likelihood,
+ *              null_log_likelihood (the intercept-only model; NaN without an intercept or when that fit fails), aic = 2 k - 2 l,
+ *              bic = k ln n - 2 l, n_observations, n_events, n_censored, n_params (k), iterations, converged, status }
+ * status != 0 => every other field is NaN; statuses 1 (invalid options: every group of the call; or, among the rows that are
+ * otherwise finite, a time <= 0 or an event other than 0 / 1; or every row censored), 10 (no valid row), 6 (fewer valid rows
+ * than k + 1), 3 (no convergence in max_iterations), checked in this order.
+ * inference (may be NULL): [n_groups x (5 p + 2)] = { se[p], z[p], p[p], ci_lower[p], ci_upper[p], intercept_std_error,
+ * log_scale_std_error } per group, from the inverse of -H at the mode; NaN when compute_inference is 0, for a failed group and
+ * for a parameter that is not fitted.
+ * Invalid options: tolerance not finite and positive, max_iterations = 0, an unknown dist, and a confidence_level outside
+ * (0, 1) while compute_inference is set.
+ */
+typedef struct {
+	int dist;
+	int fit_intercept;
+	uint32_t max_iterations;
+	double tolerance;
+	int compute_inference;
+	double confidence_level;
+} AnofoxHipAftBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_aft_record_len(size_t n_features);
+ANOFOX_HIP_API bool anofox_hip_aft_fit_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                     const int64_t *d_row_offsets, const double *d_time, const double *const *d_x_cols,
+                                     const double *d_event, AnofoxHipAftBatchOptions options, double *d_records,
+                                     double *d_inference, AnofoxError *out_error);
+/* host pointers, synchronous; ctx may be NULL (per-thread default context) */
+ANOFOX_HIP_API bool anofox_hip_aft_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                   const int64_t *row_offsets, const double *time, const double *const *x_cols, const double *event,
+                                   AnofoxHipAftBatchOptions options, double *records, double *inference, AnofoxError *out_error);
+/*
+ * A test's hook: the most workgroups a later AFT launch of the process starts (0: the library's rule, one per group up to
+ * 2^20), so that a small batch exercises the kernel's stride over the groups.  The records do not depend on it.
+ */
+ANOFOX_HIP_API void anofox_hip_aft_test_hooks(int64_t max_blocks);
 
 /*
  * Grouped variance inflation factors: the Finalize loop of vif_agg (src/aggregate_functions/vif_aggregate.cpp:
