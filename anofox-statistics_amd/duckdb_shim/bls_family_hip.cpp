@@ -34,7 +34,7 @@
 #include "anofox_stats_hip.h"
 #include "bls_family_hip.hpp"
 #include "hip_options.hpp"
-#include "row_glue.hpp"
+#include "row_shapes.hpp"
 
 namespace duckdb {
 
@@ -97,104 +97,45 @@ void ParseHipBlsOptions(const Value &v, HipBlsOptions &o, bool bounds, bool pred
 	});
 }
 
-struct HipBlsBindData : public FunctionData {
-	HipBlsBindData(const HipBlsOptions &opts_p, bool use_split_col_p) : opts(opts_p), use_split_col(use_split_col_p) {}
-	HipBlsOptions opts;
-	bool use_split_col;
-	unique_ptr<FunctionData> Copy() const override { return make_uniq<HipBlsBindData>(opts, use_split_col); }
-	bool Equals(const FunctionData &other_p) const override {
-		auto &other = other_p.Cast<HipBlsBindData>();
-		return opts == other.opts && use_split_col == other.use_split_col;
-	}
-};
+using HipBlsBindData = RowsBindData<HipBlsOptions>;
 
-// the states of one Finalize vector as one batch per feature count (RowBatch) through the fit-predict call
-struct BlsPredictBatch : RowBatch {
-	vector<double> core, pred;
+// the states of one Finalize vector as one batch per feature count through the fit-predict call
+struct BlsPredictBatch : PredictBatch {
 	void Run(const HipBlsOptions &opts) {
-		const int64_t n = Stage(false, false);
-		core.resize(Groups() * (p + 6));
-		pred.resize((size_t)n * 3);
+		const int64_t n = StagePredict(false, false);
 		AnofoxError err;
 		memset(&err, 0, sizeof err);
 		if (!anofox_hip_bls_fit_predict_batch_host(nullptr, (int64_t)Groups(), p, n, offsets.data(), y.data(), col_ptrs.data(), train_counts.data(),
 		                                           opts.Batch(), opts.confidence_level, core.data(), pred.data(), &err))
 			ThrowAbi(err);
 	}
-	bool Failed(idx_t g) const { return core[g * (p + 6) + p + 5] != 0.0; }
 };
+
+// Update: bls_fit_predict_aggregate.cpp:146-265 (RowsOf's bare text :204-207); bls_aggregate.cpp:118-180 for both fit aggregates,
+// nnls_fit_agg under the name of bls_fit_agg
+struct BlsPredictAggTraits : RowTraits {
+	using Bind = HipBlsBindData;
+	static constexpr const char *kName = "bls_fit_predict_agg";
+	static bool DropYZeroX(const Bind &bind) { return bind.opts.drop_y_zero_x; }
+};
+struct BlsFitAggTraits : RowTraits { static constexpr const char *kName = "bls_fit_agg"; };
+
+// bounds = false: nnls_fit_agg's bind; predict = true: the fit-predict aggregate's
+template <bool BOUNDS, bool PREDICT, bool SPLIT, LogicalType (*TYPE)()>
+unique_ptr<FunctionData> HipBlsBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
+	return BindRows<HipBlsOptions>(
+	    context, function, arguments, SPLIT ? 3 : 2, SPLIT, [](const Value &v, HipBlsOptions &o) { ParseHipBlsOptions(v, o, BOUNDS, PREDICT); },
+	    [](const HipBlsOptions &) { return TYPE(); });
+}
 
 // =====================================================================================================================
 // anofox_stats_bls_fit_predict_agg(y, x[, split_col][, options]) -> LIST(STRUCT(y, yhat, yhat_lower, yhat_upper, is_training))
 // =====================================================================================================================
-// Update (bls_fit_predict_aggregate.cpp:146-265): every row with a non-NULL x list is kept for the output; it trains iff y is not NULL (and the split column
-// says train), and under null_policy = 'drop_y_zero_x' no feature is exactly 0.  A NULL list element is NaN: the row is handed
-// to the fit, whose row filter drops it.
-void HipBlsPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data, idx_t input_count, Vector &state_vector, idx_t count) {
-	auto &bind = aggr_input_data.bind_data->Cast<HipBlsBindData>();
-	if (input_count < 2) throw InvalidInputException("anofox_stats bls_fit_predict_agg (HIP): too few arguments");
-	UnifiedVectorFormat y_data, x_data, split_data, sdata;
-	inputs[0].ToUnifiedFormat(count, y_data);
-	inputs[1].ToUnifiedFormat(count, x_data);
-	auto y_values = UnifiedVectorFormat::GetData<double>(y_data);
-	auto x_list = UnifiedVectorFormat::GetData<list_entry_t>(x_data);
-	auto &x_child = ListVector::GetEntry(inputs[1]);
-	auto x_child_data = FlatVector::GetData<double>(x_child);
-	auto &x_child_validity = FlatVector::Validity(x_child);
-	const string_t *split_values = nullptr;
-	if (bind.use_split_col && input_count > 2) {
-		inputs[2].ToUnifiedFormat(count, split_data);
-		split_values = UnifiedVectorFormat::GetData<string_t>(split_data);
-	}
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (RowsState **)sdata.data;
-	const idx_t max_features = anofox_hip_max_features();
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		auto x_idx = x_data.sel->get_index(i);
-		if (!x_data.validity.RowIsValid(x_idx)) continue;
-		const auto entry = x_list[x_idx];
-		CheckMaxFeatures("bls_fit_predict_agg", entry.length, max_features);
-		auto &rows = RowsOf(state, entry.length, false);
-		const size_t at = rows.x.size();
-		rows.x.resize(at + entry.length);
-		const bool has_zero = ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at).has_zero;
-		auto y_idx = y_data.sel->get_index(i);
-		const bool y_valid = y_data.validity.RowIsValid(y_idx);
-		bool training = y_valid;
-		if (bind.use_split_col && split_values) {
-			auto s_idx = split_data.sel->get_index(i);
-			training = split_data.validity.RowIsValid(s_idx) && IsSplitTraining(split_values[s_idx]) && y_valid;
-		}
-		if (training && bind.opts.drop_y_zero_x && has_zero) training = false;
-		rows.y.push_back(y_valid ? y_values[y_idx] : NAN);
-		rows.flags.push_back((uint8_t)((y_valid ? 0 : kYNull) | (training ? kTraining : 0)));
-		rows.n_training += training ? 1 : 0;
-	}
-}
-
 // Finalize (bls_fit_predict_aggregate.cpp:326-452): NULL with fewer than 2 training rows or a failed fit; otherwise every buffered row with its prediction
 void HipBlsPredictAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipBlsBindData>();
-	auto batches = CollectBatches<BlsPredictBatch>(state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.n_training >= 2; });
-	for (auto &kv : batches) kv.second.Run(bind.opts);
-	for (auto &kv : batches) {
-		auto &b = kv.second;
-		for (idx_t g = 0; g < b.Groups(); g++) {
-			if (b.Failed(g)) FlatVector::SetNull(result, b.result_rows[g], true);
-			else AppendPredictRows(result, b.result_rows[g], *b.buffers[g], &b.pred[(size_t)b.offsets[g] * 3]);
-		}
-	}
-}
-
-template <bool SPLIT>
-unique_ptr<FunctionData> HipBlsPredictAggBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
-	HipBlsOptions opts;
-	const idx_t opt_idx = SPLIT ? 3 : 2;
-	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable())
-		ParseHipBlsOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts, true, true);
-	function.return_type = PredictAggResultType();
-	return make_uniq<HipBlsBindData>(opts, SPLIT);
+	FinalizePredictRows<BlsPredictBatch>(
+	    state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.n_training >= 2; }, [&](BlsPredictBatch &b) { b.Run(bind.opts); });
 }
 
 // =====================================================================================================================
@@ -213,39 +154,6 @@ LogicalType GetHipBlsAggResultType() { // bls_aggregate.cpp:83-96
 	children.push_back(make_pair("at_lower_bound", LogicalType::LIST(LogicalType::BOOLEAN)));
 	children.push_back(make_pair("at_upper_bound", LogicalType::LIST(LogicalType::BOOLEAN)));
 	return LogicalType::STRUCT(std::move(children));
-}
-
-// Update (bls_aggregate.cpp:118-180): rows with a NULL y or a NULL x list are skipped; a NULL list element is NaN here (the
-// reference reads the slot unchecked), so the fit's row filter drops the row
-void HipBlsAggUpdate(Vector inputs[], AggregateInputData &, idx_t input_count, Vector &state_vector, idx_t count) {
-	if (input_count < 2) throw InvalidInputException("anofox_stats bls_fit_agg (HIP): too few arguments");
-	UnifiedVectorFormat y_data, x_data, sdata;
-	inputs[0].ToUnifiedFormat(count, y_data);
-	inputs[1].ToUnifiedFormat(count, x_data);
-	auto y_values = UnifiedVectorFormat::GetData<double>(y_data);
-	auto x_list = UnifiedVectorFormat::GetData<list_entry_t>(x_data);
-	auto &x_child = ListVector::GetEntry(inputs[1]);
-	auto x_child_data = FlatVector::GetData<double>(x_child);
-	auto &x_child_validity = FlatVector::Validity(x_child);
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (RowsState **)sdata.data;
-	const idx_t max_features = anofox_hip_max_features();
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		auto y_idx = y_data.sel->get_index(i);
-		if (!y_data.validity.RowIsValid(y_idx)) continue;
-		auto x_idx = x_data.sel->get_index(i);
-		if (!x_data.validity.RowIsValid(x_idx)) continue;
-		const auto entry = x_list[x_idx];
-		CheckMaxFeatures("bls_fit_agg", entry.length, max_features);
-		auto &rows = RowsOf(state, entry.length, false);
-		const size_t at = rows.x.size();
-		rows.x.resize(at + entry.length);
-		ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at);
-		rows.y.push_back(y_values[y_idx]);
-		rows.flags.push_back(kTraining);
-		rows.n_training++;
-	}
 }
 
 // Finalize (bls_aggregate.cpp:249-330): NULL with fewer than 2 buffered rows or a failed fit; ONE batched call per feature count
@@ -297,28 +205,12 @@ void HipBlsAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data
 }
 
 template <bool NNLS>
-unique_ptr<FunctionData> HipBlsAggBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
-	HipBlsOptions opts;
-	if (arguments.size() > 2 && arguments[2]->IsFoldable()) ParseHipBlsOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[2]), opts, !NNLS, false);
-	function.return_type = GetHipBlsAggResultType();
-	return make_uniq<HipBlsBindData>(opts, false);
-}
-
-template <bool NNLS>
 void RegisterFit(ExtensionLoader &loader, const char *name, const char *alias, const char *what) {
-	const vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
-	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
-	auto fill = [&](const string &fname) {
-		AggregateFunctionSet set(fname);
-		for (auto *args : {&basic, &map_args})
-			set.AddFunction(AggregateFunction(fname, *args, GetHipBlsAggResultType(), AggregateFunction::StateSize<RowsState>, RowsInitialize,
-			                                  HipBlsAggUpdate, RowsCombine<false>, HipBlsAggFinalize, nullptr, HipBlsAggBind<NNLS>, RowsDestroy));
-		return set;
-	};
-	CreateAggregateFunctionInfo info(fill(name));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic, kCategories));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'fit_intercept': true})", {"y", "x", "options"}, map_args, kCategories));
-	RegisterWithAlias(loader, std::move(info), fill(alias));
+	const RowsFunctionNames f {name, alias, {}, what, kCategories};
+	RegisterWithOptions(loader, f, "{'fit_intercept': true}", [](const string &fname, const vector<LogicalType> &args) {
+		return RowsFunction(fname, args, GetHipBlsAggResultType(), RowsFitAggUpdate<BlsFitAggTraits>, RowsCombine<false>, HipBlsAggFinalize,
+		                    HipBlsBind<!NNLS, false, false, GetHipBlsAggResultType>);
+	});
 }
 
 } // namespace
@@ -332,32 +224,12 @@ void RegisterHipBlsNnlsAggregateFunction(ExtensionLoader &loader) {
 }
 
 void RegisterHipBlsFitPredictAggregateFunction(ExtensionLoader &loader) {
-	const char *name = "anofox_stats_bls_fit_predict_agg";
-	const char *what = "Fits bounded least squares over a partition and returns per-row predictions with confidence intervals.";
-	const vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
-	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
-	const vector<LogicalType> split_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR};
-	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
-	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>, RowsInitialize,
-		                         HipBlsPredictAggUpdate, RowsCombine<false>, HipBlsPredictAggFinalize, nullptr,
-		                         split ? HipBlsPredictAggBind<true> : HipBlsPredictAggBind<false>, RowsDestroy);
-	};
-	auto fill = [&](const string &fname) {
-		AggregateFunctionSet set(fname);
-		set.AddFunction(make(fname, basic, false));          // (y, x)
-		set.AddFunction(make(fname, map_args, false));       // (y, x, options)
-		set.AddFunction(make(fname, split_args, true));      // (y, x, split_col)
-		set.AddFunction(make(fname, split_map_args, true));  // (y, x, split_col, options)
-		return set;
-	};
-	CreateAggregateFunctionInfo info(fill(name));
-	const string head = string(name) + "(y, x";
-	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", {'lower_bound': 0.0})", {"y", "x", "options"}, map_args, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", split_col, {'upper_bound': 1.0})", {"y", "x", "split_col", "options"}, split_map_args, kCategories));
-	RegisterWithAlias(loader, std::move(info), fill("bls_fit_predict_agg"));
+	const RowsFunctionNames f {"anofox_stats_bls_fit_predict_agg", "bls_fit_predict_agg", {},
+	                           "Fits bounded least squares over a partition and returns per-row predictions with confidence intervals.", kCategories};
+	RegisterWithSplitAndOptions(loader, f, "{'lower_bound': 0.0}", "{'upper_bound': 1.0}", [](const string &fname, const vector<LogicalType> &args, bool split) {
+		return RowsFunction(fname, args, LogicalType::ANY /* set in bind */, RowsPredictAggUpdate<BlsPredictAggTraits>, RowsCombine<false>, HipBlsPredictAggFinalize,
+		                    split ? HipBlsBind<true, true, true, PredictAggResultType> : HipBlsBind<true, true, false, PredictAggResultType>);
+	});
 }
 
 } // namespace duckdb

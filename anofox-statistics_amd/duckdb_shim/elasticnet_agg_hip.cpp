@@ -24,18 +24,21 @@
 #include "anofox_stats_hip.h"
 #include "elasticnet_agg_hip.hpp"
 #include "hip_options.hpp"
-#include "row_glue.hpp"
+#include "row_shapes.hpp"
 
 namespace duckdb {
 
 namespace {
 using namespace hip_glue;
 
-struct HipElasticNetBindData : public FunctionData {
-	explicit HipElasticNetBindData(const HipElasticNetOptions &opts_p) : opts(opts_p) {}
-	HipElasticNetOptions opts;
-	unique_ptr<FunctionData> Copy() const override { return make_uniq<HipElasticNetBindData>(opts); }
-	bool Equals(const FunctionData &other_p) const override { return opts == other_p.Cast<HipElasticNetBindData>().opts; }
+using HipElasticNetBindData = RowsBindData<HipElasticNetOptions>;
+
+// Update (elasticnet_aggregate.cpp Update): the feature count is fixed by the first accepted row and RowsOf's text has the
+// counts; the width is checked in Finalize, of what is about to be fitted
+struct EnFitAggTraits : RowTraits {
+	static constexpr const char *kName = "elasticnet_fit_agg";
+	static constexpr bool kCheckMaxFeatures = false;
+	static constexpr bool kCountsInError = true;
 };
 
 LogicalType GetElasticNetResultType() { // elasticnet_aggregate.cpp:78-90
@@ -48,35 +51,6 @@ LogicalType GetElasticNetResultType() { // elasticnet_aggregate.cpp:78-90
 	children.push_back(make_pair("n_observations", LogicalType::BIGINT));
 	children.push_back(make_pair("n_features", LogicalType::BIGINT));
 	return LogicalType::STRUCT(std::move(children));
-}
-
-// Update (elasticnet_aggregate.cpp Update): rows with a NULL y or a NULL x list are skipped; the feature count is fixed by
-// the first accepted row
-void HipEnUpdate(Vector inputs[], AggregateInputData &, idx_t input_count, Vector &state_vector, idx_t count) {
-	if (input_count < 2) throw InvalidInputException("anofox_stats elasticnet_fit_agg (HIP): too few arguments");
-	UnifiedVectorFormat y_data, x_data, sdata;
-	inputs[0].ToUnifiedFormat(count, y_data);
-	inputs[1].ToUnifiedFormat(count, x_data);
-	auto y_vals = UnifiedVectorFormat::GetData<double>(y_data);
-	auto x_list = UnifiedVectorFormat::GetData<list_entry_t>(x_data);
-	auto &x_child = ListVector::GetEntry(inputs[1]);
-	auto x_child_data = FlatVector::GetData<double>(x_child);
-	auto &x_child_validity = FlatVector::Validity(x_child);
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (RowsState **)sdata.data;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		const auto y_idx = y_data.sel->get_index(i), x_idx = x_data.sel->get_index(i);
-		if (!y_data.validity.RowIsValid(y_idx) || !x_data.validity.RowIsValid(x_idx)) continue;
-		const auto entry = x_list[x_idx];
-		auto &rows = RowsOf(state, entry.length, true);
-		const size_t at = rows.x.size();
-		rows.x.resize(at + entry.length);
-		ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at); // (a NULL list element is NaN, which the row filter drops)
-		rows.y.push_back(y_vals[y_idx]);
-		rows.flags.push_back(kTraining);
-		rows.n_training++;
-	}
 }
 
 // Finalize: NULL without rows or with fewer than 2 (the reference's check before its FFI call); every other state of the
@@ -119,33 +93,21 @@ void HipEnFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Ve
 
 // Bind: the options argument is read when it folds to a constant (elasticnet_aggregate.cpp Bind)
 unique_ptr<FunctionData> HipEnBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
-	HipElasticNetOptions opts;
-	if (arguments.size() >= 3 && arguments[2]->IsFoldable()) ParseHipElasticNetOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[2]), opts);
-	function.return_type = GetElasticNetResultType();
-	return make_uniq<HipElasticNetBindData>(opts);
+	return BindRows<HipElasticNetOptions>(context, function, arguments, 2, false, ParseHipElasticNetOptions,
+	                                      [](const HipElasticNetOptions &) { return GetElasticNetResultType(); });
 }
 
 } // namespace
 
 void RegisterHipElasticNetAggregateFunction(ExtensionLoader &loader) {
-	const vector<LogicalType> basic_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
-	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
-	auto make = [](const string &fname, const vector<LogicalType> &args) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>, RowsInitialize, HipEnUpdate,
-		                         RowsCombine<false, true>, HipEnFinalize, nullptr, HipEnBind, RowsDestroy);
-	};
-	const char *name = "anofox_stats_elasticnet_fit_agg";
-	const char *what = "Fits an Elastic Net regression model (L1 + L2) and returns coefficients and fit statistics as a struct.";
-	AggregateFunctionSet func_set(name);
-	func_set.AddFunction(make(name, basic_args));
-	func_set.AddFunction(make(name, map_args));
-	CreateAggregateFunctionInfo info(std::move(func_set));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'alpha': 1.0, 'l1_ratio': 0.5})", {"y", "x", "options"}, map_args, {"regression"}));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic_args, {"regression"}));
-	AggregateFunctionSet alias_set("elasticnet_fit_agg");
-	alias_set.AddFunction(make("elasticnet_fit_agg", basic_args));
-	alias_set.AddFunction(make("elasticnet_fit_agg", map_args));
-	RegisterWithAlias(loader, std::move(info), std::move(alias_set));
+	const RowsFunctionNames f {"anofox_stats_elasticnet_fit_agg", "elasticnet_fit_agg", {},
+	                           "Fits an Elastic Net regression model (L1 + L2) and returns coefficients and fit statistics as a struct.", {"regression"}};
+	RegisterWithOptions(
+	    loader, f, "{'alpha': 1.0, 'l1_ratio': 0.5}",
+	    [](const string &fname, const vector<LogicalType> &args) {
+		    return RowsFunction(fname, args, LogicalType::ANY /* set in bind */, RowsFitAggUpdate<EnFitAggTraits>, RowsCombine<false, true>, HipEnFinalize, HipEnBind);
+	    },
+	    true /* the overload with options is described first */);
 }
 
 } // namespace duckdb

@@ -36,7 +36,7 @@
 #include "anofox_stats_hip.h"
 #include "family_agg_hip.hpp"
 #include "hip_options.hpp"
-#include "row_glue.hpp"
+#include "row_shapes.hpp"
 
 namespace duckdb {
 
@@ -45,300 +45,104 @@ using namespace hip_glue;
 
 const vector<string> kCategories = {"regression", "prediction"};
 
-// ---- bind data of the predict aggregate and the window aggregate: the parsed options ----
-struct HipFamilyBindData : public FunctionData {
-	HipFamilyBindData(HipModel model_p, const HipFitOptions &opts_p, bool use_split_col_p) : model(model_p), opts(opts_p), use_split_col(use_split_col_p) {}
-	HipModel model;
-	HipFitOptions opts;
-	bool use_split_col;
-	AnofoxHipBatchOptions Batch() const {
-		HipFitOptions o = opts;
-		o.compute_inference = false; // both aggregates fit with inference off (ols_predict_aggregate.cpp:356, ols_fit_predict.cpp:283)
-		return MakeHipOptions(model, o);
-	}
-	unique_ptr<FunctionData> Copy() const override { return make_uniq<HipFamilyBindData>(model, opts, use_split_col); }
-	bool Equals(const FunctionData &other_p) const override {
-		auto &other = other_p.Cast<HipFamilyBindData>();
-		return model == other.model && opts == other.opts && use_split_col == other.use_split_col;
-	}
-};
+// ---- bind data of the predict aggregate and the window aggregate: the parsed options and the model ----
+using HipFamilyBindData = RowsBindData<HipFitOptions, HipModel>;
 
-// ---- the states of one Finalize vector as one batch per feature count (RowBatch) through the family's ABI call ----
-struct FamilyBatch : RowBatch {
-	vector<double> core, pred;
+AnofoxHipBatchOptions BatchOptions(const HipFamilyBindData &bind) {
+	HipFitOptions o = bind.opts;
+	o.compute_inference = false; // both aggregates fit with inference off (ols_predict_aggregate.cpp:356, ols_fit_predict.cpp:283)
+	return MakeHipOptions(bind.kind, o);
+}
+
+// ---- the states of one Finalize vector as one batch per feature count through the family's ABI call ----
+struct FamilyBatch : PredictBatch {
 	// extra_row: the window aggregate appends its current x as a row that does not train
 	void Run(const AnofoxHipBatchOptions &options, bool weighted, bool extra_row) {
-		const int64_t n = Stage(weighted, extra_row);
-		core.resize(Groups() * (p + 6));
-		pred.resize((size_t)n * 3);
+		const int64_t n = StagePredict(weighted, extra_row);
 		AnofoxError err;
 		memset(&err, 0, sizeof err);
 		if (!anofox_hip_fit_predict_batch_host(nullptr, (int64_t)Groups(), p, n, offsets.data(), y.data(), col_ptrs.data(), weighted ? w.data() : nullptr,
 		                                       train_counts.data(), options, core.data(), pred.data(), &err))
 			ThrowAbi(err);
 	}
-	bool Failed(idx_t g) const { return core[g * (p + 6) + p + 5] != 0.0; }
 };
+
+// What differs between the three models' Updates.  RowsOf's text has the counts in ols_predict_aggregate.cpp / ols_fit_predict.cpp
+// and is bare in the ridge / wls files.  A NULL feature: the OLS file clears the training flag (ols_predict_aggregate.cpp:236-239);
+// the ridge / wls files keep it — the row is handed to the fit, whose row filter drops it — and so does the is_training column
+// of their output.  Weights: wls_predict_aggregate.cpp:160-240, wls_fit_predict.cpp:150-154.
+template <HipModel MODEL, bool WINDOW>
+struct FamilyTraits : RowTraits {
+	using Bind = HipFamilyBindData;
+	static constexpr const char *kName = WINDOW ? "fit_predict" : "fit_predict_agg";
+	static constexpr bool kCountsInError = MODEL == HipModel::OLS;
+	static constexpr bool kWeighted = MODEL == HipModel::WLS;
+	static constexpr bool kNullElementStopsTraining = MODEL == HipModel::OLS; // (the predict aggregate; the window never looks)
+	static bool DropYZeroX(const Bind &bind) { return bind.opts.drop_y_zero_x; }
+};
+
+constexpr idx_t FirstOptional(HipModel model) { return model == HipModel::WLS ? 3 : 2; } // after y, x[, weights]
 
 // =====================================================================================================================
 // *_fit_predict_agg(y, x[, weights][, split_col][, options]) -> LIST(STRUCT(y, yhat, yhat_lower, yhat_upper, is_training))
 // =====================================================================================================================
-// Update: every row with a non-NULL x list (and, weighted, a non-NULL weight) is kept for the output; it trains iff y is not
-// NULL (or the split column says so AND y is not NULL), no list element is NULL, the weight is positive, and — under
-// null_policy = 'drop_y_zero_x' — no feature is exactly 0 (ols_predict_aggregate.cpp:134-268, wls_predict_aggregate.cpp:160-240)
-template <HipModel MODEL>
-void HipPredictAggUpdate(Vector inputs[], AggregateInputData &aggr_input_data, idx_t input_count, Vector &state_vector, idx_t count) {
-	constexpr bool kWeighted = MODEL == HipModel::WLS;
-	auto &bind = aggr_input_data.bind_data->Cast<HipFamilyBindData>();
-	const idx_t split_idx_arg = kWeighted ? 3 : 2;
-	if (input_count < (kWeighted ? 3u : 2u)) throw InvalidInputException("anofox_stats fit_predict_agg (HIP): too few arguments");
-	UnifiedVectorFormat y_data, x_data, w_data, split_data, sdata;
-	inputs[0].ToUnifiedFormat(count, y_data);
-	inputs[1].ToUnifiedFormat(count, x_data);
-	if (kWeighted) inputs[2].ToUnifiedFormat(count, w_data);
-	auto y_values = UnifiedVectorFormat::GetData<double>(y_data);
-	auto w_values = kWeighted ? UnifiedVectorFormat::GetData<double>(w_data) : nullptr;
-	auto x_list = UnifiedVectorFormat::GetData<list_entry_t>(x_data);
-	auto &x_child = ListVector::GetEntry(inputs[1]);
-	auto x_child_data = FlatVector::GetData<double>(x_child);
-	auto &x_child_validity = FlatVector::Validity(x_child);
-	const string_t *split_values = nullptr;
-	if (bind.use_split_col && input_count > split_idx_arg) {
-		inputs[split_idx_arg].ToUnifiedFormat(count, split_data);
-		split_values = UnifiedVectorFormat::GetData<string_t>(split_data);
-	}
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (RowsState **)sdata.data;
-	const idx_t max_features = anofox_hip_max_features();
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		auto x_idx = x_data.sel->get_index(i);
-		if (!x_data.validity.RowIsValid(x_idx)) continue; // a NULL x list: the row does not exist for this aggregate
-		double weight = 1.0;
-		if (kWeighted) {
-			auto w_idx = w_data.sel->get_index(i);
-			if (!w_data.validity.RowIsValid(w_idx)) continue;
-			weight = w_values[w_idx];
-		}
-		const auto entry = x_list[x_idx];
-		CheckMaxFeatures("fit_predict_agg", entry.length, max_features);
-		auto &rows = RowsOf(state, entry.length, MODEL == HipModel::OLS); // bare: the text of the ridge / wls files
-		const size_t at = rows.x.size();
-		rows.x.resize(at + entry.length);
-		const ListRowFlags x_flags = ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at);
-		auto y_idx = y_data.sel->get_index(i);
-		const bool y_valid = y_data.validity.RowIsValid(y_idx);
-		bool training = y_valid;
-		if (bind.use_split_col && split_values) {
-			auto s_idx = split_data.sel->get_index(i);
-			training = split_data.validity.RowIsValid(s_idx) && IsSplitTraining(split_values[s_idx]) && y_valid;
-		}
-		if (kWeighted && !(weight > 0)) training = false; // wls_predict_aggregate.cpp:212-217 (`weight <= 0`; a NaN weight trains upstream and
-		                                                    // fails the fit there — here it does not train)
-		// a NULL feature: the OLS file clears the flag (ols_predict_aggregate.cpp:236-239); the ridge / wls files keep it — the row
-		// is handed to the fit, whose row filter drops it — and so does the is_training column of their output
-		if (x_flags.has_null && MODEL == HipModel::OLS) training = false;
-		if (training && bind.opts.drop_y_zero_x && x_flags.has_zero) training = false;
-		rows.y.push_back(y_valid ? y_values[y_idx] : NAN);
-		if (kWeighted) rows.w.push_back(weight);
-		rows.flags.push_back((uint8_t)((y_valid ? 0 : kYNull) | (training ? kTraining : 0)));
-		rows.n_training += training ? 1 : 0;
-	}
-}
-
 void HipPredictAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipFamilyBindData>();
-	const bool weighted = bind.model == HipModel::WLS;
+	const auto options = BatchOptions(bind);
 	// fewer than 2 training rows -> NULL (ols_predict_aggregate.cpp:343-346)
-	auto batches = CollectBatches<FamilyBatch>(state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.n_training >= 2; });
-	const auto options = bind.Batch();
-	for (auto &kv : batches) kv.second.Run(options, weighted, false);
-	for (auto &kv : batches) {
-		auto &b = kv.second;
-		for (idx_t g = 0; g < b.Groups(); g++) {
-			if (b.Failed(g)) FlatVector::SetNull(result, b.result_rows[g], true); // the fit failed -> NULL (ols_predict_aggregate.cpp:366-369)
-			else AppendPredictRows(result, b.result_rows[g], *b.buffers[g], &b.pred[(size_t)b.offsets[g] * 3]);
-		}
-	}
-	// (the reference's state.Reset() after a successful fit: Destroy frees the buffers here)
+	FinalizePredictRows<FamilyBatch>(
+	    state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.n_training >= 2; },
+	    [&](FamilyBatch &b) { b.Run(options, bind.kind == HipModel::WLS, false); });
 }
 
 template <HipModel MODEL, bool SPLIT>
 unique_ptr<FunctionData> HipPredictAggBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
-	HipFitOptions opts;
-	const idx_t opt_idx = (MODEL == HipModel::WLS ? 3 : 2) + (SPLIT ? 1 : 0); // ols_predict_aggregate.cpp:435 / :466
-	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable()) ParseHipFitOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts);
-	function.return_type = PredictAggResultType();
-	return make_uniq<HipFamilyBindData>(MODEL, opts, SPLIT);
+	return BindRows<HipFitOptions>(context, function, arguments, FirstOptional(MODEL) + (SPLIT ? 1 : 0) /* ols_predict_aggregate.cpp:435 / :466 */, SPLIT,
+	                               ParseHipFitOptions, [](const HipFitOptions &) { return PredictAggResultType(); }, MODEL);
 }
 
 template <HipModel MODEL>
 void RegisterHipPredictAggregate(ExtensionLoader &loader, const string &model_name, const char *what) {
-	constexpr bool kWeighted = MODEL == HipModel::WLS;
-	const string name = "anofox_stats_" + model_name + "_fit_predict_agg";
-	vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
-	vector<string> basic_names = {"y", "x"};
-	if (kWeighted) {
-		basic.push_back(LogicalType::DOUBLE);
-		basic_names.push_back("weights");
+	RowsFunctionNames f {"anofox_stats_" + model_name + "_fit_predict_agg", model_name + "_fit_predict_agg",
+	                     // the two deprecated names (ols_predict_aggregate.cpp:563-602)
+	                     {model_name + "_predict_agg", "anofox_stats_" + model_name + "_predict_agg"}, what, kCategories};
+	if (MODEL == HipModel::WLS) {
+		f.base.push_back(LogicalType::DOUBLE);
+		f.base_names.push_back("weights");
 	}
-	auto with = [](vector<LogicalType> v, std::initializer_list<LogicalType> more) {
-		for (auto &t : more) v.push_back(t);
-		return v;
-	};
-	auto make = [&](const string &fname, const vector<LogicalType> &args, bool split) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>, RowsInitialize,
-		                         HipPredictAggUpdate<MODEL>, RowsCombine<false, true>, HipPredictAggFinalize, nullptr,
-		                         split ? HipPredictAggBind<MODEL, true> : HipPredictAggBind<MODEL, false>, RowsDestroy);
-	};
-	const vector<LogicalType> map_args = with(basic, {LogicalType::ANY}), split_args = with(basic, {LogicalType::VARCHAR}),
-	                          split_map_args = with(basic, {LogicalType::VARCHAR, LogicalType::ANY});
-	auto fill = [&](const string &fname) {
-		AggregateFunctionSet set(fname);
-		set.AddFunction(make(fname, basic, false));         // (y, x[, weights])
-		set.AddFunction(make(fname, map_args, false));      // (y, x[, weights], {'null_policy': 'drop', ...})
-		set.AddFunction(make(fname, split_args, true));     // (y, x[, weights], split_col)
-		set.AddFunction(make(fname, split_map_args, true)); // (y, x[, weights], split_col, options)
-		return set;
-	};
-	CreateAggregateFunctionInfo info(fill(name));
-	const string head = name + "(y, x" + (kWeighted ? ", weights" : "");
-	auto describe = [&](const string &example, vector<string> names, const vector<LogicalType> &types) {
-		info.descriptions.push_back(Describe(what, example, std::move(names), types, kCategories));
-	};
-	auto names_with = [&](std::initializer_list<const char *> more) {
-		vector<string> v = basic_names;
-		for (auto m : more) v.push_back(m);
-		return v;
-	};
-	describe(head + ")", names_with({}), basic);
-	describe(head + ", {'null_policy': 'drop'})", names_with({"options"}), map_args);
-	describe(head + ", split_col)", names_with({"split_col"}), split_args);
-	describe(head + ", split_col, {'null_policy': 'drop'})", names_with({"split_col", "options"}), split_map_args);
-	// the short alias and the two deprecated names (ols_predict_aggregate.cpp:563-602)
-	RegisterWithAlias(loader, std::move(info), fill(model_name + "_fit_predict_agg"));
-	for (const string &alias : {model_name + "_predict_agg", "anofox_stats_" + model_name + "_predict_agg"}) RegisterAlias(loader, name, fill(alias));
+	RegisterWithSplitAndOptions(loader, f, "{'null_policy': 'drop'}", "{'null_policy': 'drop'}", [](const string &fname, const vector<LogicalType> &args, bool split) {
+		return RowsFunction(fname, args, LogicalType::ANY /* set in bind */, RowsPredictAggUpdate<FamilyTraits<MODEL, false>>, RowsCombine<false, true>,
+		                    HipPredictAggFinalize, split ? HipPredictAggBind<MODEL, true> : HipPredictAggBind<MODEL, false>);
+	});
 }
 
 // =====================================================================================================================
 // *_fit_predict(y, x[, weight][, options]) OVER (...) -> STRUCT(yhat, yhat_lower, yhat_upper)
 // =====================================================================================================================
-// Update (ols_fit_predict.cpp:110-193): the frame's rows arrive one by one; the last one with a non-NULL x list is the row to
-// predict, every one with a non-NULL y (and weight) trains.  Only training rows are buffered.
-template <HipModel MODEL>
-void HipFitPredictUpdate(Vector inputs[], AggregateInputData &aggr_input_data, idx_t input_count, Vector &state_vector, idx_t count) {
-	constexpr bool kWeighted = MODEL == HipModel::WLS;
-	auto &bind = aggr_input_data.bind_data->Cast<HipFamilyBindData>();
-	if (input_count < (kWeighted ? 3u : 2u)) throw InvalidInputException("anofox_stats fit_predict (HIP): too few arguments");
-	UnifiedVectorFormat y_data, x_data, w_data, sdata;
-	inputs[0].ToUnifiedFormat(count, y_data);
-	inputs[1].ToUnifiedFormat(count, x_data);
-	if (kWeighted) inputs[2].ToUnifiedFormat(count, w_data);
-	auto y_values = UnifiedVectorFormat::GetData<double>(y_data);
-	auto w_values = kWeighted ? UnifiedVectorFormat::GetData<double>(w_data) : nullptr;
-	auto x_list = UnifiedVectorFormat::GetData<list_entry_t>(x_data);
-	auto &x_child = ListVector::GetEntry(inputs[1]);
-	auto x_child_data = FlatVector::GetData<double>(x_child);
-	auto &x_child_validity = FlatVector::Validity(x_child);
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (RowsState **)sdata.data;
-	const idx_t max_features = anofox_hip_max_features();
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		auto x_idx = x_data.sel->get_index(i);
-		if (!x_data.validity.RowIsValid(x_idx)) {
-			if (state.rows) state.rows->has_current_x = false; // :141-144
-			continue;
-		}
-		const auto entry = x_list[x_idx];
-		CheckMaxFeatures("fit_predict", entry.length, max_features);
-		auto &rows = RowsOf(state, entry.length, MODEL == HipModel::OLS);
-		rows.current_x.resize(entry.length);
-		// (a NULL list element: NaN — the reference reads the slot as it is)
-		const bool has_zero = ReadListRow(entry, x_child_data, x_child_validity, rows.current_x.data()).has_zero;
-		rows.has_current_x = true;
-		auto y_idx = y_data.sel->get_index(i);
-		bool training = y_data.validity.RowIsValid(y_idx);
-		double weight = 1.0;
-		if (kWeighted) {
-			auto w_idx = w_data.sel->get_index(i);
-			training = training && w_data.validity.RowIsValid(w_idx); // wls_fit_predict.cpp:150-154
-			if (training) weight = w_values[w_idx];
-		}
-		if (training && bind.opts.drop_y_zero_x && has_zero) training = false;
-		if (!training) continue;
-		rows.y.push_back(y_values[y_idx]);
-		rows.x.insert(rows.x.end(), rows.current_x.begin(), rows.current_x.end());
-		if (kWeighted) rows.w.push_back(weight);
-		rows.flags.push_back(kTraining);
-		rows.n_training++;
-	}
-}
-
-// Finalize (ols_fit_predict.cpp:246-324): NULL without a current row or with at most p + [intercept] training rows; otherwise
-// the state's training rows plus its current row form one group of the batch, and the prediction of that last row is the result
 void HipFitPredictFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipFamilyBindData>();
-	const bool weighted = bind.model == HipModel::WLS;
-	const idx_t intercept = bind.opts.fit_intercept ? 1 : 0;
-	auto batches = CollectBatches<FamilyBatch>(state_vector, result, count, offset, [&](const RowBuffer &rows) {
-		return rows.has_current_x && rows.n_training > rows.n_features + intercept;
-	});
-	const auto options = bind.Batch();
-	for (auto &kv : batches) kv.second.Run(options, weighted, true);
-	auto &fields = StructVector::GetEntries(result);
-	for (auto &kv : batches) {
-		auto &b = kv.second;
-		for (idx_t g = 0; g < b.Groups(); g++) {
-			const idx_t r = b.result_rows[g];
-			if (b.Failed(g)) {
-				FlatVector::SetNull(result, r, true);
-				continue;
-			}
-			// the current row is the group's last; a prediction that is not finite stays what the library made of it (NaN), as the
-			// reference writes whatever anofox_predict_with_interval returned (:311-318)
-			const double *pred = &b.pred[((size_t)b.offsets[g + 1] - 1) * 3];
-			for (idx_t k = 0; k < 3; k++) FlatVector::GetData<double>(*fields[k])[r] = pred[k];
-		}
-	}
+	const auto options = BatchOptions(bind);
+	FinalizeWindowRows<FamilyBatch, false>(state_vector, result, count, offset, bind.opts.fit_intercept,
+	                                       [&](FamilyBatch &b) { b.Run(options, bind.kind == HipModel::WLS, true); });
 }
 
 template <HipModel MODEL>
 unique_ptr<FunctionData> HipFitPredictBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
-	HipFitOptions opts;
-	const idx_t opt_idx = MODEL == HipModel::WLS ? 3 : 2; // ols_fit_predict.cpp:333
-	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable()) ParseHipFitOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts);
-	function.return_type = FitPredictResultType();
-	return make_uniq<HipFamilyBindData>(MODEL, opts, false);
+	return BindRows<HipFitOptions>(context, function, arguments, FirstOptional(MODEL) /* ols_fit_predict.cpp:333 */, false, ParseHipFitOptions,
+	                               [](const HipFitOptions &) { return FitPredictResultType(); }, MODEL);
 }
 
 template <HipModel MODEL>
 void RegisterHipFitPredict(ExtensionLoader &loader, const string &model_name, const char *what) {
-	constexpr bool kWeighted = MODEL == HipModel::WLS;
-	const string name = "anofox_stats_" + model_name + "_fit_predict";
-	vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
-	vector<string> basic_names = {"y", "x"};
-	if (kWeighted) {
-		basic.push_back(LogicalType::DOUBLE);
-		basic_names.push_back("weight");
+	RowsFunctionNames f {"anofox_stats_" + model_name + "_fit_predict", model_name + "_fit_predict", {}, what, kCategories};
+	if (MODEL == HipModel::WLS) {
+		f.base.push_back(LogicalType::DOUBLE);
+		f.base_names.push_back("weight");
 	}
-	vector<LogicalType> map_args = basic;
-	map_args.push_back(LogicalType::ANY);
-	vector<string> map_names = basic_names;
-	map_names.push_back("options");
-	auto fill = [&](const string &fname) {
-		AggregateFunctionSet set(fname);
-		for (auto *args : {&basic, &map_args})
-			set.AddFunction(AggregateFunction(fname, *args, FitPredictResultType(), AggregateFunction::StateSize<RowsState>, RowsInitialize,
-			                                  HipFitPredictUpdate<MODEL>, RowsCombine<true>, HipFitPredictFinalize, nullptr, HipFitPredictBind<MODEL>,
-			                                  RowsDestroy));
-		return set;
-	};
-	CreateAggregateFunctionInfo info(fill(name));
-	const string head = name + "(y, x" + (kWeighted ? ", weight" : "");
-	info.descriptions.push_back(Describe(what, head + ")", basic_names, basic, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", {'null_policy': 'drop'})", map_names, map_args, kCategories));
-	RegisterWithAlias(loader, std::move(info), fill(model_name + "_fit_predict"));
+	RegisterWithOptions(loader, f, "{'null_policy': 'drop'}", [](const string &fname, const vector<LogicalType> &args) {
+		return RowsFunction(fname, args, FitPredictResultType(), RowsWindowUpdate<FamilyTraits<MODEL, true>>, RowsCombine<true>, HipFitPredictFinalize,
+		                    HipFitPredictBind<MODEL>);
+	});
 }
 
 // =====================================================================================================================

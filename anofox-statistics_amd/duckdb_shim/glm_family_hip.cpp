@@ -49,7 +49,7 @@
 #include "anofox_stats_hip.h"
 #include "glm_family_hip.hpp"
 #include "hip_options.hpp"
-#include "row_glue.hpp"
+#include "row_shapes.hpp"
 
 namespace duckdb {
 
@@ -141,64 +141,18 @@ double IntervalZ(double confidence_level) {
 	return 1.96;
 }
 
-struct HipGlmBindData : public FunctionData {
-	HipGlmBindData(GlmKind kind_p, const HipGlmOptions &opts_p, bool use_split_col_p) : kind(kind_p), opts(opts_p), use_split_col(use_split_col_p) {}
-	GlmKind kind;
-	HipGlmOptions opts;
-	bool use_split_col;
-	unique_ptr<FunctionData> Copy() const override { return make_uniq<HipGlmBindData>(kind, opts, use_split_col); }
-	bool Equals(const FunctionData &other_p) const override {
-		auto &other = other_p.Cast<HipGlmBindData>();
-		return kind == other.kind && opts == other.opts && use_split_col == other.use_split_col;
-	}
-};
+using HipGlmBindData = RowsBindData<HipGlmOptions, GlmKind>;
 
-// Update.  PREDICT = false (poisson_aggregate.cpp:149-218 and its twins): a row with a NULL y or a NULL x list is skipped, every
-// other row is buffered, a NULL list element as NaN.  PREDICT = true (poisson_fit_predict_aggregate.cpp:186-306): every row with
-// a non-NULL x list is kept for the output; it trains iff its y is not NULL — and, with a split column, its split value is not
-// NULL and says train — and, under null_policy = 'drop_y_zero_x', no x element is exactly 0 (:283-290).
-template <bool PREDICT>
-void HipGlmRowsUpdate(Vector inputs[], AggregateInputData &aggr_input_data, idx_t input_count, Vector &state_vector, idx_t count) {
-	auto &bind = aggr_input_data.bind_data->Cast<HipGlmBindData>();
-	if (input_count < 2) throw InvalidInputException("anofox_stats glm aggregates (HIP): too few arguments");
-	UnifiedVectorFormat y_data, x_data, split_data, sdata;
-	inputs[0].ToUnifiedFormat(count, y_data);
-	inputs[1].ToUnifiedFormat(count, x_data);
-	auto y_values = UnifiedVectorFormat::GetData<double>(y_data);
-	auto x_list = UnifiedVectorFormat::GetData<list_entry_t>(x_data);
-	auto &x_child = ListVector::GetEntry(inputs[1]);
-	auto x_child_data = FlatVector::GetData<double>(x_child);
-	auto &x_child_validity = FlatVector::Validity(x_child);
-	const string_t *split_values = nullptr;
-	if (PREDICT && bind.use_split_col && input_count > 2) {
-		inputs[2].ToUnifiedFormat(count, split_data);
-		split_values = UnifiedVectorFormat::GetData<string_t>(split_data);
-	}
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (RowsState **)sdata.data;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		auto y_idx = y_data.sel->get_index(i);
-		const bool y_valid = y_data.validity.RowIsValid(y_idx);
-		if (!PREDICT && !y_valid) continue;
-		auto x_idx = x_data.sel->get_index(i);
-		if (!x_data.validity.RowIsValid(x_idx)) continue;
-		const auto entry = x_list[x_idx];
-		auto &rows = RowsOf(state, entry.length, true);
-		const size_t at = rows.x.size();
-		rows.x.resize(at + entry.length);
-		const ListRowFlags f = ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at); // never reads the slot of a NULL
-		bool training = y_valid;
-		if (split_values) {
-			auto s_idx = split_data.sel->get_index(i);
-			training = split_data.validity.RowIsValid(s_idx) && IsSplitTraining(split_values[s_idx]) && y_valid;
-		}
-		if (PREDICT && bind.opts.drop_y_zero_x && f.has_zero) training = false;
-		rows.y.push_back(y_valid ? y_values[y_idx] : NAN);
-		rows.flags.push_back((uint8_t)((y_valid ? 0 : kYNull) | (training ? kTraining : 0)));
-		rows.n_training += training ? 1 : 0;
-	}
-}
+// Update.  The fit aggregates: poisson_aggregate.cpp:149-218 and its twins.  The predict aggregate: poisson_fit_predict_aggregate.cpp
+// :186-306, drop_y_zero_x :283-290.  Neither checks the width (the library's call reports it), RowsOf's text has the counts, and
+// every function of the family goes by one name in "too few arguments".
+struct GlmTraits : RowTraits {
+	using Bind = HipGlmBindData;
+	static constexpr const char *kName = "glm aggregates";
+	static constexpr bool kCheckMaxFeatures = false;
+	static constexpr bool kCountsInError = true;
+	static bool DropYZeroX(const Bind &bind) { return bind.opts.drop_y_zero_x; } // (the predict aggregate; the fit aggregates never read it)
+};
 
 // the states of one Finalize vector as one batch per feature count (RowBatch) through the family's ABI calls
 struct GlmBatch : RowBatch {
@@ -320,29 +274,21 @@ void HipGlmAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data
 	}
 }
 
-template <GlmKind KIND>
-unique_ptr<FunctionData> HipGlmAggBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
-	HipGlmOptions opts;
-	if (arguments.size() > 2 && arguments[2]->IsFoldable()) ParseHipGlmOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[2]), KIND, opts);
-	function.return_type = GetHipGlmAggResultType(KIND, opts.compute_inference);
-	return make_uniq<HipGlmBindData>(KIND, opts, false);
+// the fit aggregates' result type depends on compute_inference; SPLIT: the predict aggregate behind a split column
+template <GlmKind KIND, bool SPLIT>
+unique_ptr<FunctionData> HipGlmBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
+	return BindRows<HipGlmOptions>(
+	    context, function, arguments, SPLIT ? 3 : 2, SPLIT, [](const Value &v, HipGlmOptions &o) { ParseHipGlmOptions(v, KIND, o); },
+	    [](const HipGlmOptions &o) { return KIND == GlmKind::POISSON_PREDICT ? PredictAggResultType() : GetHipGlmAggResultType(KIND, o.compute_inference); }, KIND);
 }
 
 template <GlmKind KIND>
 void RegisterHipGlmAgg(ExtensionLoader &loader, const char *name, const char *alias, const char *what, const char *example_options) {
-	const vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
-	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
-	auto fill = [&](const string &fname) {
-		AggregateFunctionSet set(fname);
-		for (auto *args : {&basic, &map_args})
-			set.AddFunction(AggregateFunction(fname, *args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>, RowsInitialize,
-			                                  HipGlmRowsUpdate<false>, RowsCombine<false, true>, HipGlmAggFinalize, nullptr, HipGlmAggBind<KIND>, RowsDestroy));
-		return set;
-	};
-	CreateAggregateFunctionInfo info(fill(name));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic, kCategories));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x, " + example_options + ")", {"y", "x", "options"}, map_args, kCategories));
-	RegisterWithAlias(loader, std::move(info), fill(alias));
+	const RowsFunctionNames f {name, alias, {}, what, kCategories};
+	RegisterWithOptions(loader, f, example_options, [](const string &fname, const vector<LogicalType> &args) {
+		return RowsFunction(fname, args, LogicalType::ANY /* set in bind */, RowsFitAggUpdate<GlmTraits>, RowsCombine<false, true>, HipGlmAggFinalize,
+		                    HipGlmBind<KIND, false>);
+	});
 }
 
 // =====================================================================================================================
@@ -352,25 +298,8 @@ void RegisterHipGlmAgg(ExtensionLoader &loader, const char *name, const char *al
 // interval (three NULLs where mu is not finite :498-508, y NULL where the input was :447-451)
 void HipGlmPredictAggFinalize(Vector &state_vector, AggregateInputData &aggr_input_data, Vector &result, idx_t count, idx_t offset) {
 	auto &bind = aggr_input_data.bind_data->Cast<HipGlmBindData>();
-	auto batches = CollectBatches<GlmBatch>(state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.n_training >= 2; });
-	for (auto &kv : batches) kv.second.RunPredict(bind);
-	for (auto &kv : batches) {
-		auto &b = kv.second;
-		for (idx_t g = 0; g < b.Groups(); g++) {
-			if (b.Failed(g)) FlatVector::SetNull(result, b.result_rows[g], true);
-			else AppendPredictRows(result, b.result_rows[g], *b.buffers[g], &b.pred[(size_t)b.offsets[g] * 3]);
-		}
-	}
-}
-
-template <bool SPLIT>
-unique_ptr<FunctionData> HipGlmPredictAggBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
-	HipGlmOptions opts;
-	const idx_t opt_idx = SPLIT ? 3 : 2;
-	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable())
-		ParseHipGlmOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), GlmKind::POISSON_PREDICT, opts);
-	function.return_type = PredictAggResultType();
-	return make_uniq<HipGlmBindData>(GlmKind::POISSON_PREDICT, opts, SPLIT);
+	FinalizePredictRows<GlmBatch>(
+	    state_vector, result, count, offset, [](const RowBuffer &rows) { return rows.n_training >= 2; }, [&](GlmBatch &b) { b.RunPredict(bind); });
 }
 
 } // namespace
@@ -393,32 +322,12 @@ void RegisterHipLogisticAggregateFunction(ExtensionLoader &loader) {
 }
 
 void RegisterHipPoissonFitPredictAggregateFunction(ExtensionLoader &loader) {
-	const char *name = "anofox_stats_poisson_fit_predict_agg";
-	const char *what = "Fits a Poisson regression over a partition and returns per-row predictions with an interval.";
-	const vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
-	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
-	const vector<LogicalType> split_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR};
-	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
-	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>, RowsInitialize,
-		                         HipGlmRowsUpdate<true>, RowsCombine<false, true>, HipGlmPredictAggFinalize, nullptr,
-		                         split ? HipGlmPredictAggBind<true> : HipGlmPredictAggBind<false>, RowsDestroy);
-	};
-	auto fill = [&](const string &fname) {
-		AggregateFunctionSet set(fname);
-		set.AddFunction(make(fname, basic, false));          // (y, x)
-		set.AddFunction(make(fname, map_args, false));       // (y, x, options)
-		set.AddFunction(make(fname, split_args, true));      // (y, x, split_col)
-		set.AddFunction(make(fname, split_map_args, true));  // (y, x, split_col, options)
-		return set;
-	};
-	CreateAggregateFunctionInfo info(fill(name));
-	const string head = string(name) + "(y, x";
-	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", {'confidence_level': 0.99})", {"y", "x", "options"}, map_args, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", split_col, {'confidence_level': 0.99})", {"y", "x", "split_col", "options"}, split_map_args, kCategories));
-	RegisterWithAlias(loader, std::move(info), fill("poisson_fit_predict_agg"));
+	const RowsFunctionNames f {"anofox_stats_poisson_fit_predict_agg", "poisson_fit_predict_agg", {},
+	                           "Fits a Poisson regression over a partition and returns per-row predictions with an interval.", kCategories};
+	RegisterWithSplitAndOptions(loader, f, "{'confidence_level': 0.99}", "{'confidence_level': 0.99}", [](const string &fname, const vector<LogicalType> &args, bool split) {
+		return RowsFunction(fname, args, LogicalType::ANY /* set in bind */, RowsPredictAggUpdate<GlmTraits>, RowsCombine<false, true>, HipGlmPredictAggFinalize,
+		                    split ? HipGlmBind<GlmKind::POISSON_PREDICT, true> : HipGlmBind<GlmKind::POISSON_PREDICT, false>);
+	});
 }
 
 } // namespace duckdb

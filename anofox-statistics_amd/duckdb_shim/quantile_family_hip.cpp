@@ -45,7 +45,7 @@
 #include "anofox_stats_hip.h"
 #include "quantile_family_hip.hpp"
 #include "hip_options.hpp"
-#include "row_glue.hpp"
+#include "row_shapes.hpp"
 
 namespace duckdb {
 
@@ -116,68 +116,20 @@ void ParseHipQuantilePathOptions(const Value &v, HipQuantileOptions &o) {
 	if (o.taus.size() > kMaxTaus) throw InvalidInputException("quantile path: n_taus > 64 is not built");
 }
 
-struct HipQuantileBindData : public FunctionData {
-	HipQuantileBindData(const HipQuantileOptions &opts_p, bool use_split_col_p) : opts(opts_p), use_split_col(use_split_col_p) {}
-	HipQuantileOptions opts;
-	bool use_split_col;
-	unique_ptr<FunctionData> Copy() const override { return make_uniq<HipQuantileBindData>(opts, use_split_col); }
-	bool Equals(const FunctionData &other_p) const override {
-		auto &other = other_p.Cast<HipQuantileBindData>();
-		return opts == other.opts && use_split_col == other.use_split_col;
-	}
-};
+using HipQuantileBindData = RowsBindData<HipQuantileOptions>;
 
-// Update (:115-211): a row with a NULL x list is skipped; every other row is kept for the output, a NULL list element as NaN.
-// It trains iff its y is not NULL — and, with a split column, its split value is not NULL and says train.  A NaN y that is
-// not NULL counts as a training row (:204-209); the fit's row filter drops it.  WINDOW: the last row Update saw is the row to
-// predict (a NULL x list there: nothing to predict).
-template <bool WINDOW>
-void HipQuantileRowsUpdate(Vector inputs[], AggregateInputData &aggr_input_data, idx_t input_count, Vector &state_vector, idx_t count) {
-	auto &bind = aggr_input_data.bind_data->Cast<HipQuantileBindData>();
-	if (input_count < 2) throw InvalidInputException("anofox_stats quantile_fit_predict (HIP): too few arguments");
-	UnifiedVectorFormat y_data, x_data, split_data, sdata;
-	inputs[0].ToUnifiedFormat(count, y_data);
-	inputs[1].ToUnifiedFormat(count, x_data);
-	auto y_values = UnifiedVectorFormat::GetData<double>(y_data);
-	auto x_list = UnifiedVectorFormat::GetData<list_entry_t>(x_data);
-	auto &x_child = ListVector::GetEntry(inputs[1]);
-	auto x_child_data = FlatVector::GetData<double>(x_child);
-	auto &x_child_validity = FlatVector::Validity(x_child);
-	const string_t *split_values = nullptr;
-	if (bind.use_split_col && input_count > 2) {
-		inputs[2].ToUnifiedFormat(count, split_data);
-		split_values = UnifiedVectorFormat::GetData<string_t>(split_data);
-	}
-	state_vector.ToUnifiedFormat(count, sdata);
-	auto states = (RowsState **)sdata.data;
-	for (idx_t i = 0; i < count; i++) {
-		auto &state = *states[sdata.sel->get_index(i)];
-		auto x_idx = x_data.sel->get_index(i);
-		if (!x_data.validity.RowIsValid(x_idx)) {
-			if (WINDOW && state.rows) state.rows->has_current_x = false;
-			continue;
-		}
-		const auto entry = x_list[x_idx];
-		auto &rows = RowsOf(state, entry.length, true) /* :162-164 */;
-		const size_t at = rows.x.size();
-		rows.x.resize(at + entry.length);
-		ReadListRow(entry, x_child_data, x_child_validity, rows.x.data() + at); // never reads the slot of a NULL (:169-173)
-		if (WINDOW) {
-			rows.current_x.assign(rows.x.begin() + (ptrdiff_t)at, rows.x.end());
-			rows.has_current_x = true;
-		}
-		auto y_idx = y_data.sel->get_index(i);
-		const bool y_valid = y_data.validity.RowIsValid(y_idx);
-		bool training = y_valid;
-		if (bind.use_split_col && split_values) {
-			auto s_idx = split_data.sel->get_index(i);
-			training = split_data.validity.RowIsValid(s_idx) && IsSplitTraining(split_values[s_idx]) && y_valid;
-		}
-		rows.y.push_back(y_valid ? y_values[y_idx] : NAN);
-		rows.flags.push_back((uint8_t)((y_valid ? 0 : kYNull) | (training ? kTraining : 0)));
-		rows.n_training += training ? 1 : 0;
-	}
-}
+// Update (quantile_fit_predict_aggregate.cpp:115-211): the width is not checked (the library's call reports it), RowsOf's text
+// has the counts (:162-164), null_policy is never read, and a NaN y that is not NULL counts as a training row (:204-209; the
+// fit's row filter drops it).  The window buffers every row with its flags, the last one also as the row to predict; it binds
+// no split column.  Both shapes go by one name in "too few arguments".
+struct QuantileTraits : RowTraits {
+	using Bind = HipQuantileBindData;
+	static constexpr const char *kName = "quantile_fit_predict";
+	static constexpr bool kCheckMaxFeatures = false;
+	static constexpr bool kCountsInError = true;
+	static constexpr bool kBuffersEveryRow = true;
+	static bool DropYZeroX(const Bind &) { return false; }
+};
 
 // the states of one Finalize vector as one batch per feature count (RowBatch) through the family's two ABI calls; rows that
 // do not train reach the ABI with y = NaN
@@ -257,14 +209,9 @@ void HipQuantilePredictAggFinalize(Vector &state_vector, AggregateInputData &agg
 	}
 }
 
-template <bool SPLIT>
-unique_ptr<FunctionData> HipQuantilePredictAggBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
-	HipQuantileOptions opts;
-	const idx_t opt_idx = SPLIT ? 3 : 2;
-	if (arguments.size() > opt_idx && arguments[opt_idx]->IsFoldable())
-		ParseHipQuantileOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[opt_idx]), opts);
-	function.return_type = GetHipQuantilePredictAggResultType();
-	return make_uniq<HipQuantileBindData>(opts, SPLIT);
+template <bool SPLIT, LogicalType (*TYPE)()>
+unique_ptr<FunctionData> HipQuantileBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
+	return BindRows<HipQuantileOptions>(context, function, arguments, SPLIT ? 3 : 2, SPLIT, ParseHipQuantileOptions, [](const HipQuantileOptions &) { return TYPE(); });
 }
 
 // =====================================================================================================================
@@ -356,42 +303,15 @@ void HipQuantileFitPredictFinalize(Vector &state_vector, AggregateInputData &agg
 	}
 }
 
-unique_ptr<FunctionData> HipQuantileFitPredictBind(ClientContext &context, AggregateFunction &function, vector<unique_ptr<Expression>> &arguments) {
-	HipQuantileOptions opts;
-	if (arguments.size() > 2 && arguments[2]->IsFoldable()) ParseHipQuantileOptions(ExpressionExecutor::EvaluateScalar(context, *arguments[2]), opts);
-	function.return_type = FitPredictResultType();
-	return make_uniq<HipQuantileBindData>(opts, false);
-}
-
 } // namespace
 
 void RegisterHipQuantileFitPredictAggregateFunction(ExtensionLoader &loader) {
-	const char *name = "anofox_stats_quantile_fit_predict_agg";
-	const char *what = "Fits a quantile regression model over a partition and returns per-row predictions.";
-	const vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
-	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
-	const vector<LogicalType> split_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR};
-	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
-	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
-		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>,
-		                         RowsInitialize, HipQuantileRowsUpdate<false>, RowsCombine<false>, HipQuantilePredictAggFinalize,
-		                         nullptr, split ? HipQuantilePredictAggBind<true> : HipQuantilePredictAggBind<false>, RowsDestroy);
-	};
-	auto fill = [&](const string &fname) {
-		AggregateFunctionSet set(fname);
-		set.AddFunction(make(fname, basic, false));          // (y, x)
-		set.AddFunction(make(fname, map_args, false));       // (y, x, options)
-		set.AddFunction(make(fname, split_args, true));      // (y, x, split_col)
-		set.AddFunction(make(fname, split_map_args, true));  // (y, x, split_col, options)
-		return set;
-	};
-	CreateAggregateFunctionInfo info(fill(name));
-	const string head = string(name) + "(y, x";
-	info.descriptions.push_back(Describe(what, head + ")", {"y", "x"}, basic, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", {'tau': 0.5})", {"y", "x", "options"}, map_args, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", split_col)", {"y", "x", "split_col"}, split_args, kCategories));
-	info.descriptions.push_back(Describe(what, head + ", split_col, {'tau': 0.5})", {"y", "x", "split_col", "options"}, split_map_args, kCategories));
-	RegisterWithAlias(loader, std::move(info), fill("quantile_fit_predict_agg"));
+	const RowsFunctionNames f {"anofox_stats_quantile_fit_predict_agg", "quantile_fit_predict_agg", {},
+	                           "Fits a quantile regression model over a partition and returns per-row predictions.", kCategories};
+	RegisterWithSplitAndOptions(loader, f, "{'tau': 0.5}", "{'tau': 0.5}", [](const string &fname, const vector<LogicalType> &args, bool split) {
+		return RowsFunction(fname, args, LogicalType::ANY /* set in bind */, RowsPredictAggUpdate<QuantileTraits>, RowsCombine<false>, HipQuantilePredictAggFinalize,
+		                    split ? HipQuantileBind<true, GetHipQuantilePredictAggResultType> : HipQuantileBind<false, GetHipQuantilePredictAggResultType>);
+	});
 }
 
 void RegisterHipQuantilePathFitPredictAggregateFunction(ExtensionLoader &loader) {
@@ -401,7 +321,7 @@ void RegisterHipQuantilePathFitPredictAggregateFunction(ExtensionLoader &loader)
 	const vector<LogicalType> split_map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::VARCHAR, LogicalType::ANY};
 	auto make = [](const string &fname, const vector<LogicalType> &args, bool split) {
 		return AggregateFunction(fname, args, LogicalType::ANY /* set in bind */, AggregateFunction::StateSize<RowsState>,
-		                         RowsInitialize, HipQuantileRowsUpdate<false>, RowsCombine<false>, HipQuantilePathAggFinalize,
+		                         RowsInitialize, RowsPredictAggUpdate<QuantileTraits>, RowsCombine<false>, HipQuantilePathAggFinalize,
 		                         nullptr, split ? HipQuantilePathAggBind<true> : HipQuantilePathAggBind<false>, RowsDestroy);
 	};
 	auto fill = [&](const string &fname) {
@@ -418,22 +338,12 @@ void RegisterHipQuantilePathFitPredictAggregateFunction(ExtensionLoader &loader)
 }
 
 void RegisterHipQuantileFitPredictFunction(ExtensionLoader &loader) {
-	const char *name = "anofox_stats_quantile_fit_predict";
-	const char *what = "Fits a quantile regression model over a window frame and returns the prediction of the current row.";
-	const vector<LogicalType> basic = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE)};
-	const vector<LogicalType> map_args = {LogicalType::DOUBLE, LogicalType::LIST(LogicalType::DOUBLE), LogicalType::ANY};
-	auto fill = [&](const string &fname) {
-		AggregateFunctionSet set(fname);
-		for (auto *args : {&basic, &map_args})
-			set.AddFunction(AggregateFunction(fname, *args, FitPredictResultType(), AggregateFunction::StateSize<RowsState>,
-			                                  RowsInitialize, HipQuantileRowsUpdate<true>, RowsCombine<true>,
-			                                  HipQuantileFitPredictFinalize, nullptr, HipQuantileFitPredictBind, RowsDestroy));
-		return set;
-	};
-	CreateAggregateFunctionInfo info(fill(name));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x)", {"y", "x"}, basic, kCategories));
-	info.descriptions.push_back(Describe(what, string(name) + "(y, x, {'tau': 0.9})", {"y", "x", "options"}, map_args, kCategories));
-	RegisterWithAlias(loader, std::move(info), fill("quantile_fit_predict"));
+	const RowsFunctionNames f {"anofox_stats_quantile_fit_predict", "quantile_fit_predict", {},
+	                           "Fits a quantile regression model over a window frame and returns the prediction of the current row.", kCategories};
+	RegisterWithOptions(loader, f, "{'tau': 0.9}", [](const string &fname, const vector<LogicalType> &args) {
+		return RowsFunction(fname, args, FitPredictResultType(), RowsWindowUpdate<QuantileTraits>, RowsCombine<true>, HipQuantileFitPredictFinalize,
+		                    HipQuantileBind<false, FitPredictResultType>);
+	});
 }
 
 } // namespace duckdb

@@ -1,11 +1,13 @@
 // row_glue.hpp — what the row-buffering DuckDB glue files of this directory share (family_agg_hip.cpp, elasticnet_agg_hip.cpp,
-// elasticnet_family_hip.cpp, rls_family_hip.cpp, bls_family_hip.cpp, quantile_family_hip.cpp; fit_agg_hip.cpp takes the
-// small pieces at the end): the host-side row buffer behind a one-pointer DuckDB state, its Initialize / Destroy / Combine,
-// the Finalize vector as one batch per feature count staged for the batched C ABI, and the helpers that write results and
-// register function sets.  Everything is inline or a template: several of these .cpp files are linked into one extension.
+// elasticnet_family_hip.cpp, rls_family_hip.cpp, bls_family_hip.cpp, quantile_family_hip.cpp, glm_family_hip.cpp;
+// fit_agg_hip.cpp takes the small pieces at the end): the host-side row buffer behind a one-pointer DuckDB state, its
+// Initialize / Destroy / Combine, the Finalize vector as one batch per feature count staged for the batched C ABI, and the
+// helpers that write results and register function sets.  row_shapes.hpp builds the callbacks that come in a few shapes on
+// top of it: Update, Bind, the Finalize tails of the prediction rows and the overload blocks of a registration.
+// Everything is inline or a template: several of these .cpp files are linked into one extension.
 //
-// Each family keeps what is its own: its options and bind data, which rows train (Update), which states are fitted (the keep
-// predicate of CollectBatches), its one ABI call (Run) and its record layout.
+// Each family keeps what is its own: its options and their parser, which rows train (its traits for row_shapes.hpp's Update),
+// which states are fitted (the keep predicate of CollectBatches), its one ABI call (Run) and its record layout and result types.
 #pragma once
 #include <math.h>
 #include <string.h>
