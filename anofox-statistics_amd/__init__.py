@@ -41,8 +41,9 @@ from .glm import (GlmFitAggResult, binomial_fit_agg, glm_fit_batch_device, glm_f
                   glm_fit_predict_frames_host, glm_fit_predict_window_device, glm_fit_predict_frames_device, glm_window_plan,
                   glm_window_stats, glm_window_test_hooks)
 from .options import GlmOptions, parse_binomial_options, parse_poisson_options  # noqa: E402
-from .aft import (AftFitAggResult, AftOptions, aft_cdf, aft_fit, aft_fit_agg, aft_fit_batch_device, aft_fit_batch_host,  # noqa: E402
-                  aft_quantile, aft_test_hooks, parse_aft_options)
+from .aft import (AftFitAggResult, AftFitPredictAggResult, AftOptions, aft_cdf, aft_fit, aft_fit_agg, aft_fit_batch_device,  # noqa: E402
+                  aft_fit_batch_host, aft_fit_predict_agg, aft_fit_predict_batch_device, aft_fit_predict_batch_host, aft_quantile,
+                  aft_test_hooks, parse_aft_options)
 from .scalar import quantile_fit, quantile_fit_path, aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
@@ -101,7 +102,8 @@ __all__ = [
     "glm_fit_predict_frames_host", "glm_fit_predict_window_device", "glm_fit_predict_frames_device", "glm_window_plan",
     "glm_window_stats", "glm_window_test_hooks",
     "AftOptions", "parse_aft_options", "AftFitAggResult", "aft_fit_agg", "aft_fit", "aft_cdf", "aft_quantile", "aft_fit_batch_host",
-    "aft_fit_batch_device", "aft_test_hooks",
+    "aft_fit_batch_device", "aft_test_hooks", "AftFitPredictAggResult", "aft_fit_predict_agg", "aft_fit_predict_batch_host",
+    "aft_fit_predict_batch_device",
 ]
 
 

@@ -216,6 +216,10 @@ class AnofoxHipAftBatchOptions(C.Structure):
                 ("compute_inference", C.c_int), ("confidence_level", C.c_double)]
 
 
+class AnofoxHipAftPredictOptions(C.Structure):  # horizon NaN: risk is not asked for
+    _fields_ = [("quantile", C.c_double), ("horizon", C.c_double)]
+
+
 # every symbol include/anofox_stats_hip.h declares: name -> (restype, argtypes)
 _ERRP = C.POINTER(AnofoxError)
 _CTX = C.c_void_p
@@ -509,6 +513,13 @@ SYMBOLS = {
     "anofox_hip_aft_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP, C.POINTER(_DP), _DP,
                                                  AnofoxHipAftBatchOptions, _DP, _DP, _ERRP]),
     "anofox_hip_aft_test_hooks": (None, [C.c_int64]),
+    "anofox_hip_aft_pred_len": (C.c_size_t, []),
+    "anofox_hip_aft_fit_predict_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                           C.POINTER(C.c_void_p), C.c_void_p, AnofoxHipAftBatchOptions,
+                                                           AnofoxHipAftPredictOptions, C.c_void_p, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_aft_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), _DP,
+                                                         C.POINTER(_DP), _DP, AnofoxHipAftBatchOptions, AnofoxHipAftPredictOptions,
+                                                         _DP, _DP, _DP, _ERRP]),
     "anofox_aft_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, AnofoxDataArray, AnofoxAftOptions,
                                   C.POINTER(AnofoxAftFitResultCore), C.POINTER(AnofoxAftInference), _ERRP]),
     "anofox_free_aft_result": (None, [C.POINTER(AnofoxAftFitResultCore)]),

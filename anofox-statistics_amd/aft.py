@@ -1,5 +1,6 @@
 """Accelerated failure time (AFT) survival regression with right censoring on the fused Newton kernel (csrc/aft.hip): aft_fit_agg,
-the scalar aft_fit, aft_cdf / aft_quantile, and the numpy / tensor drivers of anofox_hip_aft_fit_batch_{host,device}.
+aft_fit_predict_agg (the fit and a score per row), the scalar aft_fit, aft_cdf / aft_quantile, and the numpy / tensor drivers of
+anofox_hip_aft_fit_batch_{host,device} and anofox_hip_aft_fit_predict_batch_{host,device}.
 The contract: DESIGN.md §1 "Accelerated failure time models".  Results mirror the fields of the reference's AnofoxAftFitResultCore
 and AnofoxAftInference; a group whose status is not 0 is None (SQL NULL)."""
 from __future__ import annotations
@@ -30,6 +31,11 @@ class AftOptions:
     tolerance: float = 1e-9
     compute_inference: bool = False
     confidence_level: float = 0.95
+    quantile: float = 0.5              # aft_fit_predict_agg: the quantile of T that time_quantile is
+    horizon: Optional[float] = None    # aft_fit_predict_agg: risk = P(T <= time + horizon | T > time); None: not asked for
+
+    def predict_options(self) -> "_abi.AnofoxHipAftPredictOptions":
+        return _abi.AnofoxHipAftPredictOptions(self.quantile, float("nan") if self.horizon is None else self.horizon)
 
     def batch_options(self) -> "_abi.AnofoxHipAftBatchOptions":
         return _abi.AnofoxHipAftBatchOptions(self.dist, int(self.fit_intercept), self.max_iterations, self.tolerance,
@@ -52,7 +58,8 @@ def aft_dist_code(name) -> int:
 
 def parse_aft_options(opts: Optional[Mapping[str, Any]]) -> AftOptions:
     """aft_fit_agg's MAP options: dist (a name of AFT_DIST), fit_intercept / intercept, max_iterations / max_iter, tolerance /
-    tol, compute_inference, confidence_level.  Keys are case-insensitive; other keys are ignored, except that priors fail with
+    tol, compute_inference, confidence_level, and for aft_fit_predict_agg quantile and horizon (checked by the library: a quantile
+    outside (0, 1) or a negative or infinite horizon fails the call).  Keys are case-insensitive; other keys are ignored, except that priors fail with
     "aft: priors are not built"; every vcov is accepted (without priors they coincide).  The values are not range-checked here:
     the fit reports them (status 1 / InvalidInput)."""
     out = AftOptions()
@@ -84,6 +91,12 @@ def parse_aft_options(opts: Optional[Mapping[str, Any]]) -> AftOptions:
             v = _extract_double(val)
             if v is not None:
                 out.confidence_level = v
+        elif key == "quantile":
+            v = _extract_double(val)
+            if v is not None:
+                out.quantile = v
+        elif key == "horizon":
+            out.horizon = _extract_double(val)
         elif key in ("priors", "prior") and val is not None:
             raise InvalidInputException("aft: priors are not built")
     return out
@@ -113,6 +126,36 @@ def aft_fit_batch_device(ctx, row_offsets, time, x_cols: Sequence, event, option
     if event is None:
         raise ValueError("event is needed: one 0 / 1 per row")
     return _aft_fit(DeviceBatch(ctx, row_offsets, time, x_cols, use_current_torch_stream), event, options, inference)
+
+
+def _aft_fit_predict(b, event, options, predict, inference, pred_out=None):
+    """(records[G, p + 13], inference[G, 5 p + 2] or None, pred[N, 4])."""
+    rec = b.out((b.G, b.p + 13))
+    inf = b.out((b.G, 5 * b.p + 2)) if inference else None
+    pred = b.out((b.N, 4), given=pred_out)
+    b.call("anofox_hip_aft_fit_predict_batch", *b.head, b.rows(event, "event"), options, predict, rec, inf, pred)
+    return rec, inf, pred
+
+
+def aft_fit_predict_batch_host(row_offsets, time, x_cols: Sequence, event, options: _abi.AnofoxHipAftBatchOptions,
+                               predict: _abi.AnofoxHipAftPredictOptions, inference: bool = False, ctx=None):
+    """Grouped AFT fits and a score per row, numpy in / out: (records[G, p + 13], inference[G, 5 p + 2] or None, pred[N, 4] =
+    {eta, time_quantile, cdf, risk} per row); anofox_hip_aft_fit_predict_batch_host's layouts.  A row with event = NaN is scored
+    and not fitted."""
+    if event is None:
+        raise ValueError("event is needed: 0 / 1 per row, NaN for a row to score only")
+    return _aft_fit_predict(HostBatch(ctx, row_offsets, time, x_cols), event, options, predict, inference)
+
+
+def aft_fit_predict_batch_device(ctx, row_offsets, time, x_cols: Sequence, event, options: _abi.AnofoxHipAftBatchOptions,
+                                 predict: _abi.AnofoxHipAftPredictOptions, inference: bool = False, use_current_torch_stream: bool = True,
+                                 pred_out=None):
+    """aft_fit_predict_batch_host on CUDA tensors.  Asynchronous.  pred_out: a float64 tensor of 4 N elements to write into; rows
+    outside [row_offsets[0], row_offsets[G]) keep what it held."""
+    if event is None:
+        raise ValueError("event is needed: 0 / 1 per row, NaN for a row to score only")
+    return _aft_fit_predict(DeviceBatch(ctx, row_offsets, time, x_cols, use_current_torch_stream), event, options, predict, inference,
+                            pred_out)
 
 
 def aft_test_hooks(max_blocks: int = 0):
@@ -154,15 +197,36 @@ class AftFitAggResult:
         return {k: self.row(i) for i, k in enumerate(self.keys.tolist())}
 
 
+@dataclass
+class AftFitPredictAggResult(AftFitAggResult):
+    """aft_fit_predict_agg: the fit per group (as AftFitAggResult) and pred[N, 4] = {eta, time_quantile, cdf, risk} per input row,
+    in the input's row order; NaN where a value is not defined ("Fit-predict")."""
+    pred: np.ndarray = None
+
+    @property
+    def eta(self) -> np.ndarray:
+        return self.pred[:, 0]
+
+    @property
+    def time_quantile(self) -> np.ndarray:
+        return self.pred[:, 1]
+
+    @property
+    def cdf(self) -> np.ndarray:
+        return self.pred[:, 2]
+
+    @property
+    def risk(self) -> np.ndarray:
+        return self.pred[:, 3]
+
+
 def _column(values):
     a = np.asarray(values)
     return np.array([np.nan if v is None else v for v in values], dtype=np.float64) if a.dtype == object else np.asarray(a, np.float64)
 
 
-def aft_fit_agg(group_keys, time, x, event, options=None, context=None) -> AftFitAggResult:
-    """aft_fit_agg(time, x, event, options) GROUP BY group_keys: x is [N, p], event 1 = observed, 0 = right-censored; None / NaN in a
-    row leaves the row out.  Options: parse_aft_options."""
-    opts = parse_aft_options(options)
+def _grouped(group_keys, time, x, event):
+    """The rows sorted by key (stably): -> (sorted keys, the permutation, offsets[G + 1], time, columns, event)."""
     keys = np.asarray(group_keys)
     tv, ev = _column(time), _column(event)
     X = np.asarray(x, dtype=np.float64)
@@ -174,9 +238,30 @@ def aft_fit_agg(group_keys, time, x, event, options=None, context=None) -> AftFi
     perm = np.argsort(inv, kind="stable")
     offsets = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=len(uniq)))]).astype(np.int64)
     cols = [np.ascontiguousarray(X[perm, j]) for j in range(X.shape[1])]
-    out = aft_fit_batch_host(offsets, tv[perm], cols, ev[perm], opts.batch_options(), inference=opts.compute_inference, ctx=context)
+    return uniq, perm, offsets, tv[perm], cols, ev[perm]
+
+
+def aft_fit_agg(group_keys, time, x, event, options=None, context=None) -> AftFitAggResult:
+    """aft_fit_agg(time, x, event, options) GROUP BY group_keys: x is [N, p], event 1 = observed, 0 = right-censored; None / NaN in a
+    row leaves the row out.  Options: parse_aft_options."""
+    opts = parse_aft_options(options)
+    uniq, perm, offsets, tv, cols, ev = _grouped(group_keys, time, x, event)
+    out = aft_fit_batch_host(offsets, tv, cols, ev, opts.batch_options(), inference=opts.compute_inference, ctx=context)
     rec, inf = out if opts.compute_inference else (out, None)
     return AftFitAggResult(uniq, rec, inf, len(cols))
+
+
+def aft_fit_predict_agg(group_keys, time, x, event, options=None, context=None) -> AftFitPredictAggResult:
+    """aft_fit_predict_agg(time, x, event, options) GROUP BY group_keys: aft_fit_agg's fit per group and, for every input row, its
+    linear predictor, the `quantile`-quantile of its time (default 0.5: the median), P(T <= time) and, with a `horizon`, the chance
+    of failing within it given survival to `time`.  A row whose event (or time) is None / NaN is scored and not fitted."""
+    opts = parse_aft_options(options)
+    uniq, perm, offsets, tv, cols, ev = _grouped(group_keys, time, x, event)
+    rec, inf, sorted_pred = aft_fit_predict_batch_host(offsets, tv, cols, ev, opts.batch_options(), opts.predict_options(),
+                                                       inference=opts.compute_inference, ctx=context)
+    pred = np.empty_like(sorted_pred)
+    pred[perm] = sorted_pred
+    return AftFitPredictAggResult(uniq, rec, inf, len(cols), pred)
 
 
 def aft_fit(time, x, event, options=None) -> dict:

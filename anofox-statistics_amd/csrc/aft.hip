@@ -1,6 +1,7 @@
 // aft.hip — grouped accelerated failure time (AFT) survival regression with right censoring: one wavefront per group runs the
-// whole Newton loop of aft_newton.h, and the entry points anofox_hip_aft_fit_batch_{device,host}, anofox_aft_fit /
-// anofox_free_aft_result / anofox_free_aft_inference, anofox_aft_cdf / anofox_aft_quantile.
+// whole Newton loop of aft_newton.h, and the entry points anofox_hip_aft_fit_batch_{device,host},
+// anofox_hip_aft_fit_predict_batch_{device,host}, anofox_aft_fit / anofox_free_aft_result / anofox_free_aft_inference,
+// anofox_aft_cdf / anofox_aft_quantile.
 //
 // The contract and the method: aft_newton.h and DESIGN.md §1, "Accelerated failure time models".
 //   aft_newton_kernel<EM>: 64 lanes per workgroup = one wavefront per group (grid-stride over the groups).  LDS holds the
@@ -9,6 +10,9 @@
 //     k).  log t of a row sits in a per-call device scratch (one double per row, the context's workspace) that only the row's
 //     own lane touches and that the first pass writes before anything reads it.  Nothing returns to the host between
 //     iterations; the same wavefront writes the record and the inference and fits the intercept-only model.
+//   aft_newton_kernel<EM, true>: the fit-predict launch.  The same fit, then an_predict: the wavefront walks its rows once more
+//     and writes {eta, time_quantile, cdf, risk} per row, each lane its own rows' 32 bytes.  PRED is a template parameter so
+//     that the fit-only kernel's code is the one it was; LDS is the same (beta and sigma are in it).
 // No atomics: a group is one wavefront's own work in a fixed order, so repeated calls give identical bytes.
 #include <math.h>
 #include <stdlib.h>
@@ -51,9 +55,13 @@ struct AftArgs {
 	int invalid; // invalid options: every group gets ANOFOX_ERROR_INVALID_INPUT
 	double *rec; // [G x (p + 13)]
 	double *inf; // [G x (5 p + 2)] or nullptr
+	// the fit-predict launch
+	double *pred;   // [n_rows x 4]
+	double wq;      // the predict quantile of W
+	double horizon; // NaN: risk is not asked for
 };
 
-template <int EM>
+template <int EM, bool PRED>
 __global__ __launch_bounds__(64) void aft_newton_kernel(AftArgs a) {
 	extern __shared__ double aft_lds[];
 	// the column pointers in LDS: indexing the kernel arguments by a run-time column would make a private copy of them
@@ -77,10 +85,17 @@ __global__ __launch_bounds__(64) void aft_newton_kernel(AftArgs a) {
 		P.compute_inference = a.compute_inference;
 		P.zq = a.zq;
 		P.logt = a.scratch;
+		if (PRED) {
+			P.pred = a.pred;
+			P.wq = a.wq;
+			P.horizon = a.horizon;
+		}
 		an_fit<EM>(P, a.invalid != 0, aft_lds, a.rec + g * (int64_t)(a.p + 13), a.inf ? a.inf + g * (int64_t)(5 * a.p + 2) : nullptr);
 		__syncthreads(); // the next group reuses the LDS
 	}
 }
+
+double kernel_quantile(int dist, double p);
 
 bool aft_options_invalid(const AnofoxHipAftBatchOptions &o) {
 	if (o.dist < ANOFOX_AFT_WEIBULL || o.dist > ANOFOX_AFT_EXPONENTIAL) return true;
@@ -100,9 +115,10 @@ bool check_aft(int64_t G, size_t p, int64_t n_rows, const void *off, const void 
 }
 
 // the fit of G groups on device-resident inputs, enqueued on the context's stream (ctx->mu held by the caller)
+// predict (with d_pred) or neither: the fit-predict launch, which also scores every row
 bool launch_aft(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, const int64_t *d_off, const double *d_time,
                 const double *const *x_cols, const double *d_event, const AnofoxHipAftBatchOptions &o, double *d_rec, double *d_inf,
-                AnofoxError *e) {
+                AnofoxError *e, const AnofoxHipAftPredictOptions *predict = nullptr, double *d_pred = nullptr) {
 	if (G == 0) return true;
 	const size_t rows = n_rows > 0 ? (size_t)n_rows : 1;
 	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, rows * sizeof(double), "aft scratch", e)) return false;
@@ -124,22 +140,39 @@ bool launch_aft(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, cons
 	a.zq = a.compute_inference && !a.invalid ? hostmath::normal_quantile(0.5 + o.confidence_level / 2.0) : NAN;
 	a.rec = d_rec;
 	a.inf = d_inf;
+	a.pred = d_pred;
+	a.wq = d_pred ? kernel_quantile(a.dist, predict->quantile) : NAN;
+	a.horizon = d_pred ? predict->horizon : NAN;
 	const int k = (int)p + a.fit_intercept + (an_scale_is_fixed(a.dist) ? 0 : 1);
 	const size_t lds = an_work_doubles(k) * sizeof(double);
 	const int64_t hook = g_max_blocks.load(), max_blocks = hook > 0 ? hook : 1 << 20;
 	const dim3 grid((unsigned)(G < max_blocks ? G : max_blocks)), block(64);
-	switch (an_entry_class(k)) {
-	case 1: hipLaunchKernelGGL(aft_newton_kernel<1>, grid, block, lds, ctx->stream, a); break;
-	case 4: hipLaunchKernelGGL(aft_newton_kernel<4>, grid, block, lds, ctx->stream, a); break;
-	default: hipLaunchKernelGGL(aft_newton_kernel<10>, grid, block, lds, ctx->stream, a); break;
+	switch (an_entry_class(k) + (d_pred ? 100 : 0)) {
+	case 1: hipLaunchKernelGGL((aft_newton_kernel<1, false>), grid, block, lds, ctx->stream, a); break;
+	case 4: hipLaunchKernelGGL((aft_newton_kernel<4, false>), grid, block, lds, ctx->stream, a); break;
+	case 10: hipLaunchKernelGGL((aft_newton_kernel<10, false>), grid, block, lds, ctx->stream, a); break;
+	case 101: hipLaunchKernelGGL((aft_newton_kernel<1, true>), grid, block, lds, ctx->stream, a); break;
+	case 104: hipLaunchKernelGGL((aft_newton_kernel<4, true>), grid, block, lds, ctx->stream, a); break;
+	default: hipLaunchKernelGGL((aft_newton_kernel<10, true>), grid, block, lds, ctx->stream, a); break;
 	}
 	return !hip_fail(hipGetLastError(), "aft_newton_kernel", e);
+}
+
+// the predict options' own rules, answered before any device is touched
+bool check_aft_predict(const AnofoxHipAftPredictOptions &q, const void *pred, int64_t G, AnofoxError *e) {
+	if (G > 0 && !pred) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
+	if (!(q.quantile > 0.0 && q.quantile < 1.0)) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "aft: quantile must be in (0, 1)"); return false; }
+	if (q.horizon == q.horizon && !(q.horizon >= 0.0 && isfinite(q.horizon))) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "aft: horizon must be finite and >= 0");
+		return false;
+	}
+	return true;
 }
 
 // host pointers: one staging of the whole call, the kernel, the copies back
 bool aft_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows, const int64_t *row_offsets, const double *time,
               const double *const *x_cols, const double *event, const AnofoxHipAftBatchOptions &o, double *rec, double *inf,
-              AnofoxError *e) {
+              AnofoxError *e, const AnofoxHipAftPredictOptions *predict = nullptr, double *pred = nullptr) {
 	if (!(ctx = host_context(ctx, e))) return false;
 	const size_t G = (size_t)n_groups, rec_len = p + 13, inf_len = 5 * p + 2;
 	std::lock_guard<std::mutex> lk(ctx->mu); // one lock over staging, the kernel and the copies back
@@ -147,16 +180,18 @@ bool aft_host(AnofoxHipContext *ctx, int64_t n_groups, size_t p, int64_t n_rows,
 	hipStream_t st = ctx->stream;
 	int64_t *d_off;
 	StagedColumns c;
-	double *d_rec, *d_inf;
+	double *d_rec, *d_inf, *d_pred = nullptr;
 	if (!stage_call(ctx, e, [&](Stage &s) {
 		    d_off = s.put(row_offsets, G + 1);
 		    c = s.columns(p, 0, n_rows, x_cols, time, event, nullptr, kPlainColumns); // (the event column in the weight slot)
 		    d_rec = s.take<double>(G * rec_len);
 		    d_inf = inf ? s.take<double>(G * inf_len) : nullptr;
+		    if (pred) d_pred = s.take<double>((size_t)n_rows * 4);
 	    }))
 		return false;
-	if (!launch_aft(ctx, n_groups, p, n_rows, d_off, c.y, c.x, c.w, o, d_rec, d_inf, e)) return false;
+	if (!launch_aft(ctx, n_groups, p, n_rows, d_off, c.y, c.x, c.w, o, d_rec, d_inf, e, predict, d_pred)) return false;
 	if (!d2h(rec, d_rec, G * rec_len * sizeof(double), st, e)) return false;
+	if (pred && n_rows > 0 && !d2h(pred, d_pred, (size_t)n_rows * 4 * sizeof(double), st, e)) return false;
 	if (inf && !d2h(inf, d_inf, G * inf_len * sizeof(double), st, e)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", e);
 }
@@ -221,6 +256,34 @@ bool anofox_hip_aft_fit_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size
 	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
 	if (n_groups == 0) return true;
 	return aft_host(ctx, n_groups, n_features, n_rows, row_offsets, time, x_cols, event, options, records, inference, out_error);
+}
+
+size_t anofox_hip_aft_pred_len(void) { return 4; }
+
+bool anofox_hip_aft_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                             const int64_t *d_row_offsets, const double *d_time, const double *const *d_x_cols,
+                                             const double *d_event, AnofoxHipAftBatchOptions options, AnofoxHipAftPredictOptions predict,
+                                             double *d_records, double *d_inference, double *d_pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_aft(n_groups, n_features, n_rows, d_row_offsets, d_time, d_x_cols, d_event, d_records, out_error)) return false;
+	if (!check_aft_predict(predict, d_pred, n_groups, out_error)) return false;
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	return launch_aft(ctx, n_groups, n_features, n_rows, d_row_offsets, d_time, d_x_cols, d_event, options, d_records, d_inference, out_error,
+	                  &predict, d_pred);
+}
+
+bool anofox_hip_aft_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                           const int64_t *row_offsets, const double *time, const double *const *x_cols, const double *event,
+                                           AnofoxHipAftBatchOptions options, AnofoxHipAftPredictOptions predict, double *records,
+                                           double *inference, double *pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_aft(n_groups, n_features, n_rows, row_offsets, time, x_cols, event, records, out_error)) return false;
+	if (!check_aft_predict(predict, pred, n_groups, out_error)) return false;
+	if (!check_host_offsets(n_groups, n_rows, row_offsets, out_error)) return false;
+	if (n_groups == 0) return true;
+	return aft_host(ctx, n_groups, n_features, n_rows, row_offsets, time, x_cols, event, options, records, inference, out_error, &predict, pred);
 }
 
 // A batch of one group with anofox_ols_fit's conventions: argument checks first, NULL entries -> NaN, the arrays malloc'ed.

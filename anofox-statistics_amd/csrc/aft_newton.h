@@ -32,6 +32,9 @@
 //              from erfc(z / sqrt 2); where that falls below 1e-300 the Mills-ratio expansion (z + 1/z - 2/z^3).
 //   finish     the same wavefront writes the record, inverts -H at the mode for the standard errors (lane j solves L v = e_j)
 //              and fits the intercept-only model for null_log_likelihood.
+//   predict    (P.pred given) after all that, one more walk over the group's rows, strided over the lanes as in the likelihood
+//              pass: per row four doubles {eta, time_quantile, cdf, risk} at pred[4 i], from beta and sigma still in the work
+//              memory (an_predict).  A row is scored whether or not it was in the fit; only its x must be finite.
 #pragma once
 #include "glm_irls.h"
 
@@ -75,6 +78,10 @@ struct AnProblem {
 	double *logt; // scratch, one double per row, indexed by the row number
 	// measurements (tests/tools/aft_host.cpp): Newton iterations that entered the damping ladder, main and null fit together
 	int *ladder_entries = nullptr;
+	// the prediction pass (an_predict); pred == nullptr: no pass
+	double *pred = nullptr; // four doubles per row, indexed by the row number
+	double wq = NAN;        // the quantile of W that time_quantile is taken at
+	double horizon = NAN;   // NaN: risk is not asked for
 };
 
 // a model the loop fits: the group's own (the design a_i) or the intercept-only one (the design 1)
@@ -342,6 +349,8 @@ GI_DEV int an_newton(const AnProblem &P, const AnModel &M, int64_t n_valid, int6
 	GiPL<GiEntries<EM>> map;
 	int S, Tp;
 	an_map<EM>(kk, map, S, Tp);
+	// (theta is written at [0, kk) only, here and at every accepted step: an_fit's prediction pass relies on that when it saves
+	// and restores what the intercept-only fit, kk <= 2, overwrites)
 	// ---- the start: least squares of log t, then log sigma from its residuals ----
 	an_sums<EM>(P, M, kAnSumsStart, theta, n_events, aug, tile, map, S, Tp);
 	{
@@ -462,6 +471,65 @@ GI_DEV int an_newton(const AnProblem &P, const AnModel &M, int64_t n_valid, int6
 	return 0;
 }
 
+// P(W <= z) with the clamps of an_row_terms
+GI_DEV double an_kernel_cdf(int dist, double z) {
+	if (dist == kAnLogNormal) return 0.5 * erfc(-z * 0.70710678118654752440);
+	if (dist == kAnLogLogistic) {
+		const double e = exp(-fabs(z));
+		return z >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+	}
+	return -expm1(-an_safe_exp(z));
+}
+
+// The prediction pass of one group: pred[4 i ..] = {eta, time_quantile, cdf, risk} of every row i of [lo, hi), all NaN when the
+// fit failed (status != 0) or an x of the row is not finite.  theta: the fitted parameters.  A lane writes its own rows only.
+//   eta            a_i'beta by an_eta: for a row of the fit, the bits the last likelihood pass saw
+//   time_quantile  exp(eta + sigma wq)
+//   cdf            P(T <= t_i): 0 for a finite t_i <= 0, NaN for a t_i that is not finite
+//   risk           P(T <= t_i + h | T > t_i) = -expm1(log S(z(t_i + h)) - log S(z(t_i))), the log-survival terms being those of a
+//                  censored row (an_row_terms), so a survival that underflows still gives its ratio; t_i <= 0: the cdf at
+//                  t_i + h; NaN without a horizon or for a t_i that is not finite
+GI_DEV void an_predict(const AnProblem &P, int status, const double *theta) {
+	const int p = P.p, kb = p + (P.fit_intercept ? 1 : 0), fs = an_scale_is_fixed(P.dist) ? 0 : 1;
+	const AnModel M = {kb, fs, false};
+	const double sigma = status == 0 && fs ? exp(theta[kb]) : 1.0; // (the record's scale)
+	const bool ask_risk = P.horizon == P.horizon;
+	GI_LANES_BEGIN(lane)
+	for (int64_t i = P.lo + lane; i < P.hi; i += 64) {
+		double *out = P.pred + 4 * i;
+		bool ok = status == 0;
+		GI_NOUNROLL
+		for (int j = 0; ok && j < p; ++j) ok = gi_finite(P.x[j][i]);
+		double eta = NAN, tq = NAN, cdf = NAN, risk = NAN;
+		if (ok) {
+			eta = an_eta(P, M, theta, i);
+			tq = exp(eta + sigma * P.wq);
+			const double t = P.time[i];
+			if (gi_finite(t)) {
+				const double t2 = t + P.horizon;
+				if (t > 0.0) {
+					const double z = (log(t) - eta) / sigma;
+					cdf = an_kernel_cdf(P.dist, z);
+					if (ask_risk) {
+						double c1, c2, u, v;
+						an_row_terms(P.dist, false, z, c1, u, v);
+						an_row_terms(P.dist, false, (log(t2) - eta) / sigma, c2, u, v);
+						risk = 0.0 - expm1(c2 - c1);
+					}
+				} else {
+					cdf = 0.0;
+					if (ask_risk) risk = t2 > 0.0 ? an_kernel_cdf(P.dist, (log(t2) - eta) / sigma) : 0.0;
+				}
+			}
+		}
+		out[0] = eta;
+		out[1] = tq;
+		out[2] = cdf;
+		out[3] = risk;
+	}
+	GI_LANES_END
+}
+
 // The fit of one group.  rec: p + 13 doubles {b[p], intercept, scale, log_likelihood, null_log_likelihood, aic, bic,
 // n_observations, n_events, n_censored, n_params, iterations, converged, status}; inf (optional): 5 p + 2 doubles {se[p], z[p],
 // p[p], ci_lower[p], ci_upper[p], intercept_std_error, log_scale_std_error}.
@@ -470,6 +538,7 @@ GI_DEV void an_fit(const AnProblem &P, bool invalid, double *work, double *rec, 
 	const int p = P.p, ic = P.fit_intercept ? 1 : 0, fs = an_scale_is_fixed(P.dist) ? 0 : 1, kb = p + ic, k = kb + fs;
 	if (invalid) {
 		an_fail(rec, inf, p, kGiStatusInvalidInput);
+		if (P.pred) an_predict(P, kGiStatusInvalidInput, nullptr);
 		return;
 	}
 	// ---- first pass: the row mask, log t, the counts ----
@@ -514,6 +583,7 @@ GI_DEV void an_fit(const AnProblem &P, bool invalid, double *work, double *rec, 
 	}
 	if (status) {
 		an_fail(rec, inf, p, status);
+		if (P.pred) an_predict(P, status, nullptr);
 		return;
 	}
 	const int ld = an_aug_ld(k), tl = an_tile_ld(k);
@@ -585,14 +655,28 @@ GI_DEV void an_fit(const AnProblem &P, bool invalid, double *work, double *rec, 
 	gi_sync();
 	double null_ll = NAN;
 	if (ic) {
+		// the intercept-only fit runs in the same work memory and leaves its own parameters in theta[0], theta[1]: the
+		// prediction pass gets the group's back
+		const double keep0 = P.pred ? theta[0] : 0.0, keep1 = P.pred ? theta[1] : 0.0;
 		const AnModel M0 = {1, fs, true};
 		int it0 = 0;
 		if (an_newton<EM>(P, M0, n_valid, n_events, work, k, null_ll, it0) != 0) null_ll = NAN;
+		if (P.pred) {
+			gi_sync();
+			GI_LANES_BEGIN(lane)
+			if (lane == 0) {
+				theta[0] = keep0;
+				theta[1] = keep1;
+			}
+			GI_LANES_END
+			gi_sync();
+		}
 	}
 	GI_LANES_BEGIN(lane)
 	if (lane == 0) rec[p + 3] = null_ll;
 	GI_LANES_END
 	gi_sync();
+	if (P.pred) an_predict(P, 0, theta);
 }
 
 } // namespace aft

@@ -372,6 +372,19 @@ class Context:
         from .aft import aft_fit_batch_host
         return aft_fit_batch_host(row_offsets, time, x_cols, event, options, inference, ctx=self)
 
+    def aft_fit_predict_batch_device(self, row_offsets, time, x_cols: Sequence, event, options: _abi.AnofoxHipAftBatchOptions,
+                                     predict: _abi.AnofoxHipAftPredictOptions, inference: bool = False,
+                                     use_current_torch_stream: bool = True, pred_out=None):
+        """Grouped AFT fits and a score per row on CUDA tensors (aft.aft_fit_predict_batch_device)."""
+        from .aft import aft_fit_predict_batch_device
+        return aft_fit_predict_batch_device(self, row_offsets, time, x_cols, event, options, predict, inference, use_current_torch_stream,
+                                            pred_out)
+
+    def aft_fit_predict_batch_host(self, row_offsets, time, x_cols: Sequence, event, options: _abi.AnofoxHipAftBatchOptions,
+                                   predict: _abi.AnofoxHipAftPredictOptions, inference: bool = False):
+        from .aft import aft_fit_predict_batch_host
+        return aft_fit_predict_batch_host(row_offsets, time, x_cols, event, options, predict, inference, ctx=self)
+
 
 class AggState:
     """The streaming aggregate state of {ols,ridge,wls}_fit_agg on the GPU (anofox_hip_agg_state_*): one O(p^2)

@@ -1217,6 +1217,41 @@ ANOFOX_HIP_API bool anofox_hip_aft_fit_batch_host(AnofoxHipContext *ctx, int64_t
 ANOFOX_HIP_API void anofox_hip_aft_test_hooks(int64_t max_blocks);
 
 /*
+ * AFT fit-predict (the aggregate aft_fit_predict_agg): the fit above and, by the same wavefront right after it, a score for every
+ * row of the call.  records and inference are byte for byte those of anofox_hip_aft_fit_batch_* on the same inputs.  A row whose
+ * event or time is not finite takes no part in the fit (the fit's own row rule) but is scored: a prediction row is a row with
+ * event = NaN.  pred: [n_rows x anofox_hip_aft_pred_len() = 4] doubles, row i of the call at pred[4 i]:
+ *   eta            x_i'beta (+ intercept), for a row of the fit the very value its likelihood term was computed from
+ *   time_quantile  exp(eta + scale w_q), w_q the `quantile`-quantile of W (the median time at the default the bindings pass, 0.5)
+ *   cdf            P(T <= time_i); 0 for a finite time_i <= 0; NaN where time_i is not finite
+ *   risk           P(T <= time_i + horizon | T > time_i), from the difference of the two log-survival terms; for a finite
+ *                  time_i <= 0 the cdf at time_i + horizon; exactly 0 at horizon = 0; NaN where time_i is not finite or
+ *                  horizon is NaN ("risk not asked for")
+ * All four are NaN for a row with an x that is not finite and for every row of a group whose status is not 0.  Rows outside
+ * [row_offsets[0], row_offsets[n_groups]) are not written.  quantile NaN or outside the open interval (0, 1):
+ * ANOFOX_ERROR_INVALID_INPUT, "aft: quantile must be in (0, 1)" (unlike anofox_aft_quantile, nothing is clamped); horizon negative
+ * or infinite: "aft: horizon must be finite and >= 0"; pred NULL with n_groups > 0: "pred is NULL" (with no groups nothing is
+ * written and NULL is taken, as for the other outputs); all before any device is touched.
+ * anofox_hip_aft_test_hooks applies.
+ */
+typedef struct {
+	double quantile;
+	double horizon; /* NaN: risk is not asked for */
+} AnofoxHipAftPredictOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_aft_pred_len(void);
+ANOFOX_HIP_API bool anofox_hip_aft_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                             const int64_t *d_row_offsets, const double *d_time, const double *const *d_x_cols,
+                                             const double *d_event, AnofoxHipAftBatchOptions options,
+                                             AnofoxHipAftPredictOptions predict, double *d_records, double *d_inference,
+                                             double *d_pred, AnofoxError *out_error);
+/* host pointers, synchronous; ctx may be NULL (per-thread default context) */
+ANOFOX_HIP_API bool anofox_hip_aft_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_groups, size_t n_features, int64_t n_rows,
+                                           const int64_t *row_offsets, const double *time, const double *const *x_cols,
+                                           const double *event, AnofoxHipAftBatchOptions options, AnofoxHipAftPredictOptions predict,
+                                           double *records, double *inference, double *pred, AnofoxError *out_error);
+
+/*
  * Grouped variance inflation factors: the Finalize loop of vif_agg (src/aggregate_functions/vif_aggregate.cpp:
  * 144-185) in one call.  x_cols as in the fit entry points (rows of a group contiguous; the aggregate's Update
  * has already dropped NULL rows and NaN values, :67-93).  d_vif[g] = { vif[n_features], status }

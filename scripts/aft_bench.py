@@ -3,7 +3,10 @@ process (OLS of log t, then the Weibull AFT fit with about 30 % of the rows cens
 over the repetitions, the Newton iterations per fit, the time per iteration and the bytes a pass over the rows reads against the
 time it takes.  One JSON line per shape, appended to profiles/aft_bench.jsonl with --out.
 
-    python scripts/aft_bench.py [--reps 5] [--scale 1.0] [--shapes 100000x200x3,100000x200x8] [--dist weibull] [--out FILE]
+    python scripts/aft_bench.py [--reps 5] [--scale 1.0] [--shapes 100000x200x3,100000x200x8] [--dist weibull] [--predict] [--out FILE]
+
+--predict alternates a third call, the fit-predict (quantile 0.5, horizon 1) into a preallocated [N, 4] tensor, and reports what the
+prediction pass adds to the fit: in ms, as a ratio, and in units of one Newton iteration.
 
 --scale multiplies the group counts (smaller runs of the same shapes).  The OLS time is context only: OLS is one pass over the
 rows; a Newton iteration is one pass for l, g and -H plus one likelihood-only pass per trial step, the start adds two passes, the
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--shapes", default="100000x200x3,100000x200x8")
     ap.add_argument("--dist", default="weibull")
+    ap.add_argument("--predict", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -60,14 +64,20 @@ def main():
         aft = pkg.parse_aft_options({"dist": args.dist}).batch_options()
         times = {"ols": [], "aft": []}
         rec = None
+        if args.predict:
+            times["aft_predict"] = []
+            predict = pkg.parse_aft_options({"quantile": 0.5, "horizon": 1.0}).predict_options()
+            pred = torch.empty((G * n, 4), dtype=torch.float64, device=dev)
         for rep in range(args.reps + 1):  # the first round warms up
             for name in times:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 if name == "ols":
                     ctx.fit_batch_device(off, logt, xs, None, ols)
-                else:
+                elif name == "aft":
                     rec = ctx.aft_fit_batch_device(off, time, xs, event, aft)
+                else:
+                    ctx.aft_fit_predict_batch_device(off, time, xs, event, aft, predict, pred_out=pred)
                 e1.record()
                 torch.cuda.synchronize()
                 if rep:
@@ -90,6 +100,12 @@ def main():
         out["ms_per_iteration"] = round(med / float(it.mean()), 4)
         out["pass_gbytes"] = round(pass_bytes / 1e9, 3)
         out["tbytes_per_s_if_two_passes_per_iteration"] = round(2.0 * pass_bytes * float(it.mean()) / (med * 1e-3) / 1e12, 3)
+        if args.predict:
+            pmed = float(np.median(times["aft_predict"]))
+            out["predict_pass_ms"] = round(pmed - med, 3)
+            out["predict_over_fit"] = round(pmed / med, 4)
+            out["predict_pass_in_iterations"] = round((pmed - med) / (med / float(it.mean())), 3)
+            out["pred_gbytes_written"] = round(G * n * 32 / 1e9, 3)
         ctx.close()
         line = json.dumps(out)
         print(line, flush=True)
