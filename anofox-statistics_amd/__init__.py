@@ -44,6 +44,8 @@ from .options import GlmOptions, parse_binomial_options, parse_poisson_options  
 from .aft import (AftFitAggResult, AftFitPredictAggResult, AftOptions, aft_cdf, aft_fit, aft_fit_agg, aft_fit_batch_device,  # noqa: E402
                   aft_fit_batch_host, aft_fit_predict_agg, aft_fit_predict_batch_device, aft_fit_predict_batch_host, aft_quantile,
                   aft_test_hooks, parse_aft_options)
+from .eb_shrink import (EbShrinkOptions, ShrunkCoefficients, eb_shrink, eb_shrink_agg, eb_shrink_batch_device, eb_shrink_batch_host,  # noqa: E402
+                        eb_shrink_test_hooks, parse_eb_shrink_options, shrink_coefficients)
 from .scalar import quantile_fit, quantile_fit_path, aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
@@ -63,6 +65,8 @@ SQL_FUNCTIONS.update({
     "anofox_stats_binomial_fit_predict": binomial_fit_predict, "binomial_fit_predict": binomial_fit_predict,
     "anofox_stats_aft_fit": aft_fit, "aft_fit": aft_fit,
     "anofox_stats_aft_cdf": aft_cdf, "aft_cdf": aft_cdf, "anofox_stats_aft_quantile": aft_quantile, "aft_quantile": aft_quantile,
+    "anofox_stats_eb_shrink": eb_shrink, "eb_shrink": eb_shrink,
+    "anofox_stats_eb_shrink_agg": eb_shrink_agg, "eb_shrink_agg": eb_shrink_agg,
     "anofox_stats_predict": predict,
     "anofox_stats_aic": aic, "aic": aic, "anofox_stats_bic": bic, "bic": bic,
     "anofox_stats_vif": vif, "vif": vif,
@@ -104,6 +108,8 @@ __all__ = [
     "AftOptions", "parse_aft_options", "AftFitAggResult", "aft_fit_agg", "aft_fit", "aft_cdf", "aft_quantile", "aft_fit_batch_host",
     "aft_fit_batch_device", "aft_test_hooks", "AftFitPredictAggResult", "aft_fit_predict_agg", "aft_fit_predict_batch_host",
     "aft_fit_predict_batch_device",
+    "EbShrinkOptions", "parse_eb_shrink_options", "ShrunkCoefficients", "eb_shrink", "eb_shrink_agg", "eb_shrink_batch_host",
+    "eb_shrink_batch_device", "eb_shrink_test_hooks", "shrink_coefficients",
 ]
 
 

@@ -220,6 +220,24 @@ class AnofoxHipAftPredictOptions(C.Structure):  # horizon NaN: risk is not asked
     _fields_ = [("quantile", C.c_double), ("horizon", C.c_double)]
 
 
+TAU_DERSIMONIAN_LAIRD, TAU_NONE = 0, 1
+
+
+class AnofoxEbShrinkOptions(C.Structure):  # anofox_stats_ffi.h:2396-2400, 16 bytes; tau_squared NaN: estimate it
+    _fields_ = [("method", C.c_int), ("tau_squared", C.c_double)]
+
+
+class AnofoxHipEbShrinkOptions(C.Structure):  # the batch entries' options: the same layout
+    _fields_ = [("method", C.c_int), ("tau_squared", C.c_double)]
+
+
+class AnofoxEbShrinkResult(C.Structure):  # anofox_stats_ffi.h:2405-2418, 96 bytes
+    _fields_ = [("mu", C.c_double), ("mu_se", C.c_double), ("tau_squared", C.c_double), ("i_squared", C.c_double), ("q", C.c_double),
+                ("n_groups", C.c_size_t), ("estimate", C.POINTER(C.c_double)), ("se", C.POINTER(C.c_double)),
+                ("shrunken", C.POINTER(C.c_double)), ("shrunken_se", C.POINTER(C.c_double)), ("weight", C.POINTER(C.c_double)),
+                ("len", C.c_size_t)]
+
+
 # every symbol include/anofox_stats_hip.h declares: name -> (restype, argtypes)
 _ERRP = C.POINTER(AnofoxError)
 _CTX = C.c_void_p
@@ -524,6 +542,14 @@ SYMBOLS = {
                                   C.POINTER(AnofoxAftFitResultCore), C.POINTER(AnofoxAftInference), _ERRP]),
     "anofox_free_aft_result": (None, [C.POINTER(AnofoxAftFitResultCore)]),
     "anofox_free_aft_inference": (None, [C.POINTER(AnofoxAftInference)]),
+    "anofox_hip_eb_shrink_summary_len": (C.c_size_t, []),
+    "anofox_hip_eb_shrink_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_int64, AnofoxHipEbShrinkOptions, C.c_void_p, C.c_void_p, _ERRP]),
+    "anofox_hip_eb_shrink_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.c_size_t, _DP, C.c_int64, _DP,
+                                                   C.c_int64, AnofoxHipEbShrinkOptions, _DP, _DP, _ERRP]),
+    "anofox_hip_eb_shrink_test_hooks": (None, [C.c_int, C.c_int64, C.c_int64]),
+    "anofox_eb_shrink": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxEbShrinkOptions, C.POINTER(AnofoxEbShrinkResult), _ERRP]),
+    "anofox_free_eb_shrink_result": (None, [C.POINTER(AnofoxEbShrinkResult)]),
     "anofox_aft_cdf": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_int]),
     "anofox_aft_quantile": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_int]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),

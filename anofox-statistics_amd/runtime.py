@@ -361,6 +361,17 @@ class Context:
         return glm_fit_batch_host(row_offsets, y, x_cols, options, offset, inference, ctx=self, threshold=threshold)
 
     # ---- accelerated failure time models (aft.py) --------------------------------------------------
+    def eb_shrink_batch_device(self, set_offsets, est, se, n_cols: int = 1, est_stride=None, se_stride=None, options=None, n_items=None,
+                               use_current_torch_stream: bool = True):
+        """Empirical-Bayes shrinkage of (estimate, se) pairs on CUDA tensors, the strided matrix form (eb_shrink.eb_shrink_batch_device):
+        (out[n_items, n_cols, 3], summary[n_sets, n_cols, 8])."""
+        from .eb_shrink import eb_shrink_batch_device
+        return eb_shrink_batch_device(self, set_offsets, est, se, n_cols, est_stride, se_stride, options, n_items, use_current_torch_stream)
+
+    def eb_shrink_batch_host(self, set_offsets, est, se, n_cols: int = 1, est_stride=None, se_stride=None, options=None, n_items=None):
+        from .eb_shrink import eb_shrink_batch_host
+        return eb_shrink_batch_host(set_offsets, est, se, n_cols, est_stride, se_stride, options, n_items, ctx=self)
+
     def aft_fit_batch_device(self, row_offsets, time, x_cols: Sequence, event, options: _abi.AnofoxHipAftBatchOptions,
                              inference: bool = False, use_current_torch_stream: bool = True):
         """Grouped AFT fits on CUDA tensors through the fused Newton kernel (aft.aft_fit_batch_device)."""

@@ -512,6 +512,41 @@ ANOFOX_HIP_API void anofox_free_aft_inference(AnofoxAftInference *inf);
 ANOFOX_HIP_API double anofox_aft_cdf(double t, double eta, double scale, AnofoxAftDistribution dist);
 ANOFOX_HIP_API double anofox_aft_quantile(double p, double eta, double scale, AnofoxAftDistribution dist);
 
+/* replaces AnofoxTauMethod, anofox_stats_ffi.h:2390-2394 */
+typedef enum { ANOFOX_TAU_DERSIMONIAN_LAIRD = 0, ANOFOX_TAU_NONE = 1 } AnofoxTauMethod;
+
+/* replaces AnofoxEbShrinkOptions, anofox_stats_ffi.h:2396-2400 — 16 bytes: method @0, tau_squared @8 */
+typedef struct {
+	AnofoxTauMethod method;
+	double tau_squared; /* NaN: estimate it */
+} AnofoxEbShrinkOptions;
+
+/* replaces AnofoxEbShrinkResult, anofox_stats_ffi.h:2405-2418 — 96 bytes: five doubles @0..32, n_groups @40, five arrays
+ * @48..80 (each `len` long, in input order, malloc'ed by the callee, released by anofox_free_eb_shrink_result), len @88 */
+typedef struct {
+	double mu;
+	double mu_se;
+	double tau_squared;
+	double i_squared;
+	double q;
+	size_t n_groups;
+	double *estimate;
+	double *se;
+	double *shrunken;
+	double *shrunken_se;
+	double *weight;
+	size_t len;
+} AnofoxEbShrinkResult;
+
+/* replace anofox_eb_shrink / anofox_free_eb_shrink_result, anofox_stats_ffi.h:2423-2427: one set through
+ * anofox_hip_eb_shrink_batch_host (below), NULL entries of the validity bitmaps as NaN (pairs that are not usable).  False, with the
+ * result zeroed and nothing to free: an empty input (ANOFOX_ERROR_INVALID_INPUT), unequal lengths
+ * (ANOFOX_ERROR_DIMENSION_MISMATCH), a fixed tau_squared that is negative or infinite (ANOFOX_ERROR_INVALID_INPUT), the first
+ * three before any device is touched, and fewer than 2 usable pairs (ANOFOX_ERROR_INSUFFICIENT_DATA). */
+ANOFOX_HIP_API bool anofox_eb_shrink(AnofoxDataArray estimate, AnofoxDataArray se, AnofoxEbShrinkOptions options,
+                      AnofoxEbShrinkResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_eb_shrink_result(AnofoxEbShrinkResult *result);
+
 #endif /* ANOFOX_STATS_FFI_H */
 
 /* ------------------------------------------------------------------------ */
@@ -1250,6 +1285,49 @@ ANOFOX_HIP_API bool anofox_hip_aft_fit_predict_batch_host(AnofoxHipContext *ctx,
                                            const int64_t *row_offsets, const double *time, const double *const *x_cols,
                                            const double *event, AnofoxHipAftBatchOptions options, AnofoxHipAftPredictOptions predict,
                                            double *records, double *inference, double *pred, AnofoxError *out_error);
+
+/*
+ * Empirical-Bayes shrinkage of per-group estimates (anofox_eb_shrink and the aggregate eb_shrink_agg; the reference's
+ * crates/anofox-stats-core/src/models/eb_shrink.rs): the DerSimonian-Laird random-effects model, closed form.  A pair
+ * (est, se) is usable when est is finite and se is finite and > 0; k = the usable pairs of a set, sums over them only:
+ *   w = 1/se^2, Sw = sum w, fixed = sum w est / Sw, Q = sum w (est - fixed)^2 (a second pass about `fixed`), df = k - 1,
+ *   C = Sw - sum w^2 / Sw;  tau^2 = options.tau_squared if it is not NaN, else 0 (ANOFOX_TAU_NONE), else
+ *   max(0, (Q - df) / C) if C > 0 else 0;  wr = 1/(se^2 + tau^2), mu = sum wr est / sum wr, mu_se = sqrt(1 / sum wr),
+ *   I^2 = clamp((Q - df) / Q, 0, 1) if Q > df and Q > 0 else 0.
+ * Input: est[g * est_stride + c], se[g * se_stride + c], item g in [0, n_items), column c in [0, n_cols); set_offsets[n_sets + 1]
+ * are contiguous item ranges, and a set is (item range s, column c): a call holds n_sets * n_cols sets.  n_cols = 1 with both
+ * strides 1 is the plain vector call; n_cols = p, est = a GLM record batch with est_stride = its record length and se = its
+ * inference batch with se_stride = 5 p shrinks every coefficient column in place, without a transpose.
+ *   out[(g * n_cols + c) * 3]         {shrunken, shrunken_se, weight}; usable pair, tau^2 > 0: weight = (1/se^2) / (1/se^2 + 1/tau^2),
+ *                                     shrunken = weight est + (1 - weight) mu, shrunken_se = sqrt(1 / (1/se^2 + 1/tau^2)); tau^2 = 0:
+ *                                     {mu, mu_se, 0}; a pair that is not usable: NaN, NaN, NaN.  Items outside every set are not written.
+ *   summary[(s * n_cols + c) * 8]     {mu, mu_se, tau_squared, i_squared, q, n_groups (= k), n_input (= the set's items), status}
+ * Status per set: 0; ANOFOX_ERROR_INVALID_INPUT 1 for every set of a call whose options are invalid (an unknown method, a
+ * tau_squared that is negative or infinite); ANOFOX_ERROR_NO_VALID_DATA 10 for a set without items; ANOFOX_ERROR_INSUFFICIENT_DATA
+ * 6 for k < 2.  A status other than 0 makes the other seven summary fields and all the set's outputs NaN.
+ * Two paths, chosen from n_sets, n_items and n_cols alone (the average set size): one wavefront per set, or, for few large
+ * sets, chunk partials in a scratch added in a fixed order.  No atomics: repeated calls give identical bytes on either path.
+ * Argument errors (false before any device is touched): a NULL pointer where there is something to read or write, n_cols = 0,
+ * a stride smaller than n_cols, negative counts, and for the host form offsets that are not non-decreasing within [0, n_items].
+ * The device form is asynchronous on the context's stream.
+ * anofox_hip_eb_shrink_test_hooks (for tests; 0 restores the library's rule): force_path 1 = one wavefront per set, 2 = chunks;
+ * chunk_items = the items of a chunk; max_workgroups = the most workgroups a launch starts.
+ */
+/* the batch entries' options: AnofoxEbShrinkOptions' layout (method: ANOFOX_TAU_DERSIMONIAN_LAIRD 0, ANOFOX_TAU_NONE 1), a type of
+ * this header's own so that the batch surface stands next to the reference's header as well */
+typedef struct {
+	int method;
+	double tau_squared; /* NaN: estimate it */
+} AnofoxHipEbShrinkOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_eb_shrink_summary_len(void); /* 8 */
+ANOFOX_HIP_API bool anofox_hip_eb_shrink_batch_device(AnofoxHipContext *ctx, int64_t n_sets, int64_t n_items, const int64_t *d_set_offsets,
+                                       size_t n_cols, const double *d_est, int64_t est_stride, const double *d_se, int64_t se_stride,
+                                       AnofoxHipEbShrinkOptions options, double *d_out, double *d_summary, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_eb_shrink_batch_host(AnofoxHipContext *ctx, int64_t n_sets, int64_t n_items, const int64_t *set_offsets,
+                                     size_t n_cols, const double *est, int64_t est_stride, const double *se, int64_t se_stride,
+                                     AnofoxHipEbShrinkOptions options, double *out, double *summary, AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_hip_eb_shrink_test_hooks(int force_path, int64_t chunk_items, int64_t max_workgroups);
 
 /*
  * Grouped variance inflation factors: the Finalize loop of vif_agg (src/aggregate_functions/vif_aggregate.cpp:
