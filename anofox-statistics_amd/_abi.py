@@ -231,6 +231,32 @@ class AnofoxHipEbShrinkOptions(C.Structure):  # the batch entries' options: the 
     _fields_ = [("method", C.c_int), ("tau_squared", C.c_double)]
 
 
+class AnofoxHipGlmmOptions(C.Structure):  # the batch entries' options (anofox_stats_hip.h), 40 bytes
+    _fields_ = [("family", C.c_int), ("fit_intercept", C.c_int), ("reml", C.c_int), ("max_iterations", C.c_uint32),
+                ("tolerance", C.c_double), ("compute_inference", C.c_int), ("confidence_level", C.c_double)]
+
+
+class AnofoxGlmmOptions(C.Structure):  # anofox_stats_ffi.h:2442-2460, 88 bytes
+    _fields_ = [("family", C.c_int), ("fit_intercept", C.c_bool), ("max_iterations", C.c_uint32), ("tolerance", C.c_double),
+                ("compute_inference", C.c_bool), ("confidence_level", C.c_double), ("reml", C.c_bool), ("theta", C.c_double),
+                ("power", C.c_double), ("offset_column", C.c_size_t), ("random_slopes", C.POINTER(C.c_size_t)),
+                ("random_slopes_len", C.c_size_t)]
+
+
+class AnofoxGlmmResult(C.Structure):  # anofox_stats_ffi.h:2462-2504, 264 bytes
+    _fields_ = [("coefficients", C.POINTER(C.c_double)), ("coefficients_len", C.c_size_t), ("intercept", C.c_double),
+                ("std_errors", C.POINTER(C.c_double)), ("z_values", C.POINTER(C.c_double)), ("p_values", C.POINTER(C.c_double)),
+                ("ci_lower", C.POINTER(C.c_double)), ("ci_upper", C.POINTER(C.c_double)), ("inference_len", C.c_size_t),
+                ("intercept_std_error", C.c_double), ("confidence_level", C.c_double), ("var_group", C.c_double),
+                ("var_residual", C.c_double), ("icc", C.c_double), ("log_likelihood", C.c_double), ("aic", C.c_double), ("bic", C.c_double),
+                ("deviance", C.c_double), ("n_observations", C.c_size_t), ("n_groups", C.c_size_t), ("n_features", C.c_size_t),
+                ("iterations", C.c_uint32), ("converged", C.c_bool), ("ranef_group", C.POINTER(C.c_int32)),
+                ("ranef_value", C.POINTER(C.c_double)), ("ranef_se", C.POINTER(C.c_double)), ("ranef_n", C.POINTER(C.c_int64)),
+                ("ranef_len", C.c_size_t), ("random_cov", C.POINTER(C.c_double)), ("random_dim", C.c_size_t),
+                ("ranef_effects", C.POINTER(C.c_double)), ("factor_var", C.POINTER(C.c_double)), ("factor_n_levels", C.POINTER(C.c_int64)),
+                ("factor_len", C.c_size_t)]
+
+
 class AnofoxEbShrinkResult(C.Structure):  # anofox_stats_ffi.h:2405-2418, 96 bytes
     _fields_ = [("mu", C.c_double), ("mu_se", C.c_double), ("tau_squared", C.c_double), ("i_squared", C.c_double), ("q", C.c_double),
                 ("n_groups", C.c_size_t), ("estimate", C.POINTER(C.c_double)), ("se", C.POINTER(C.c_double)),
@@ -550,6 +576,18 @@ SYMBOLS = {
     "anofox_hip_eb_shrink_test_hooks": (None, [C.c_int, C.c_int64, C.c_int64]),
     "anofox_eb_shrink": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxEbShrinkOptions, C.POINTER(AnofoxEbShrinkResult), _ERRP]),
     "anofox_free_eb_shrink_result": (None, [C.POINTER(AnofoxEbShrinkResult)]),
+    "anofox_hip_glmm_record_len": (C.c_size_t, [C.c_size_t]),
+    "anofox_hip_glmm_inference_len": (C.c_size_t, [C.c_size_t]),
+    "anofox_hip_glmm_test_hooks": (None, [C.c_int, C.c_int]),
+    "anofox_hip_glmm_fit_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(C.c_void_p), AnofoxHipGlmmOptions, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, _ERRP]),
+    "anofox_hip_glmm_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64),
+                                                  C.POINTER(C.c_int64), _DP, C.POINTER(_DP), AnofoxHipGlmmOptions, _DP, _DP, _DP,
+                                                  C.POINTER(C.c_int64), _ERRP]),
+    "anofox_glmm_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, C.POINTER(C.c_int32), C.c_size_t,
+                                   C.c_void_p, C.c_size_t, AnofoxGlmmOptions, C.POINTER(AnofoxGlmmResult), _ERRP]),
+    "anofox_free_glmm_result": (None, [C.POINTER(AnofoxGlmmResult)]),
     "anofox_aft_cdf": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_int]),
     "anofox_aft_quantile": (C.c_double, [C.c_double, C.c_double, C.c_double, C.c_int]),
     "anofox_hip_host_alloc": (C.c_void_p, [C.c_size_t]),

@@ -372,6 +372,17 @@ class Context:
         from .eb_shrink import eb_shrink_batch_host
         return eb_shrink_batch_host(set_offsets, est, se, n_cols, est_stride, se_stride, options, n_items, ctx=self)
 
+    def glmm_fit_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False,
+                              use_current_torch_stream: bool = True):
+        """Grouped Gaussian random-intercept mixed models on CUDA tensors (glmm.glmm_fit_batch_device): (records, inference or None,
+        ranef, level_n)."""
+        from .glmm import glmm_fit_batch_device
+        return glmm_fit_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols, options, inference, use_current_torch_stream)
+
+    def glmm_fit_batch_host(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False):
+        from .glmm import glmm_fit_batch_host
+        return glmm_fit_batch_host(panel_level_offsets, level_row_offsets, y, x_cols, options, inference, ctx=self)
+
     def aft_fit_batch_device(self, row_offsets, time, x_cols: Sequence, event, options: _abi.AnofoxHipAftBatchOptions,
                              inference: bool = False, use_current_torch_stream: bool = True):
         """Grouped AFT fits on CUDA tensors through the fused Newton kernel (aft.aft_fit_batch_device)."""

@@ -547,6 +547,88 @@ ANOFOX_HIP_API bool anofox_eb_shrink(AnofoxDataArray estimate, AnofoxDataArray s
                       AnofoxEbShrinkResult *out_result, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_eb_shrink_result(AnofoxEbShrinkResult *result);
 
+/* replaces AnofoxGlmmFamily, anofox_stats_ffi.h:2433-2440 */
+typedef enum {
+	ANOFOX_GLMM_GAUSSIAN = 0,
+	ANOFOX_GLMM_POISSON = 1,
+	ANOFOX_GLMM_BINOMIAL = 2,
+	ANOFOX_GLMM_NEGBINOMIAL = 3,
+	ANOFOX_GLMM_GAMMA = 4,
+	ANOFOX_GLMM_TWEEDIE = 5
+} AnofoxGlmmFamily;
+
+/* replaces AnofoxGlmmOptions, anofox_stats_ffi.h:2442-2460 — 88 bytes: family @0, fit_intercept @4, max_iterations @8,
+ * tolerance @16, compute_inference @24, confidence_level @32, reml @40, theta @48, power @56, offset_column @64 (1-based, 0:
+ * none), random_slopes @72, random_slopes_len @80.  Only the Gaussian family without an offset and without random slopes is
+ * built (DESIGN.md §1 "Linear mixed models"); theta and power are not read. */
+typedef struct {
+	AnofoxGlmmFamily family;
+	bool fit_intercept;
+	uint32_t max_iterations;
+	double tolerance;
+	bool compute_inference;
+	double confidence_level;
+	bool reml;
+	double theta;
+	double power;
+	size_t offset_column;
+	const size_t *random_slopes;
+	size_t random_slopes_len;
+} AnofoxGlmmOptions;
+
+/* replaces AnofoxGlmmResult, anofox_stats_ffi.h:2462-2504 — 264 bytes.  coefficients (coefficients_len = n_features); the five
+ * inference arrays (inference_len = n_features with compute_inference, else NULL and 0); per level, in first-seen order of the
+ * caller's ids, ranef_group / ranef_value / ranef_se (NaN: not built) / ranef_n and ranef_effects (= ranef_value, random_dim =
+ * 1); random_cov = {var_group}; factor_var and factor_n_levels NULL with factor_len 0.  Every array is malloc'ed by the callee
+ * and released by anofox_free_glmm_result. */
+typedef struct {
+	double *coefficients;
+	size_t coefficients_len;
+	double intercept;
+	double *std_errors;
+	double *z_values;
+	double *p_values;
+	double *ci_lower;
+	double *ci_upper;
+	size_t inference_len;
+	double intercept_std_error;
+	double confidence_level;
+	double var_group;
+	double var_residual;
+	double icc;
+	double log_likelihood;
+	double aic;
+	double bic;
+	double deviance;
+	size_t n_observations;
+	size_t n_groups;
+	size_t n_features;
+	uint32_t iterations;
+	bool converged;
+	int32_t *ranef_group;
+	double *ranef_value;
+	double *ranef_se;
+	int64_t *ranef_n;
+	size_t ranef_len;
+	double *random_cov;
+	size_t random_dim;
+	double *ranef_effects;
+	double *factor_var;
+	int64_t *factor_n_levels;
+	size_t factor_len;
+} AnofoxGlmmResult;
+
+/* replace anofox_glmm_fit / anofox_free_glmm_result, anofox_stats_ffi.h:2511-2516: one panel through
+ * anofox_hip_glmm_fit_batch_host (below).  Rows are grouped by group_ids (ids < 0 are dropped, the others compacted in
+ * first-seen order); NULL entries of the validity bitmaps are NaN (rows that are not valid).  False with the result zeroed and
+ * nothing to free, before any device is touched: an empty y, unequal lengths, more than 32 features, invalid options, and
+ * ANOFOX_ERROR_INVALID_INPUT with "glmm: ... is not built" for a family other than Gaussian, n_extra_factors > 0, a non-empty
+ * random_slopes or an offset column.  A panel status other than 0 is false with that status as the error code. */
+ANOFOX_HIP_API bool anofox_glmm_fit(AnofoxDataArray y, const AnofoxDataArray *x, size_t x_count, const int32_t *group_ids, size_t n_obs,
+                     const int32_t *const *extra_group_ids, size_t n_extra_factors, AnofoxGlmmOptions options,
+                     AnofoxGlmmResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_glmm_result(AnofoxGlmmResult *result);
+
 #endif /* ANOFOX_STATS_FFI_H */
 
 /* ------------------------------------------------------------------------ */
@@ -1328,6 +1410,61 @@ ANOFOX_HIP_API bool anofox_hip_eb_shrink_batch_host(AnofoxHipContext *ctx, int64
                                      size_t n_cols, const double *est, int64_t est_stride, const double *se, int64_t se_stride,
                                      AnofoxHipEbShrinkOptions options, double *out, double *summary, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_hip_eb_shrink_test_hooks(int force_path, int64_t chunk_items, int64_t max_workgroups);
+
+/*
+ * Grouped Gaussian linear mixed models with one random intercept (glmm_fit_agg): per panel  y_ij = a_ij'beta + b_j + e_ij,
+ * b_j ~ N(0, var_group), e ~ N(0, var_residual), fitted by profiled REML or ML.  The contract, the formulas and what is not
+ * built: DESIGN.md §1 "Linear mixed models" and csrc/lmm_profile.h.
+ * Input: the grouped-columns layout with one more layer of offsets; rows are sorted by (panel, level).
+ *   panel_level_offsets[n_panels + 1]  panel g owns levels [plo[g], plo[g + 1]); plo[0] = 0 and plo[n_panels] = n_levels
+ *   level_row_offsets[n_levels + 1]    level l owns rows [lro[l], lro[l + 1])
+ *   y, x_cols[j]                       n_rows doubles each, NaN = NULL; a row is valid when y and every x are finite
+ * Output:
+ *   glmm[g * (p + 13)]      { coefficients[p], intercept (NaN without one), var_group, var_residual, icc, log_likelihood, aic, bic,
+ *                             deviance (= -2 log_likelihood), n_observations, n_groups (levels with a valid row), iterations
+ *                             (evaluations of the search loop), converged, status }
+ *   inference[g * (5 p + 1)] { se[p], z[p], p[p], ci_lower[p], ci_upper[p], intercept_std_error }, normal-based; may be NULL
+ *   ranef[n_levels]          the BLUP of every level; NaN for a level without a valid row and for a failed panel
+ *   level_n[n_levels]        valid rows per level (int64); may be NULL
+ * Status per panel: 0; 1 invalid options (every panel of the call: a tolerance that is not finite and positive, max_iterations
+ * = 0, a confidence_level outside (0, 1) with inference), fewer than two non-empty levels, or every non-empty level with one
+ * row; 10 no valid row; 6 n <= k + 1.  A status other than 0 makes every other field NaN.  theta^ = 0 (the score is not
+ * positive at the lower end of the bracket [1e-10, 1e10]): var_group = icc = 0.0, BLUPs 0.0, beta the pooled fit, converged = 1.
+ * A search that ends on the upper end: converged = 0, status 0.  A column that is aliased (or constant next to an intercept)
+ * is dropped by the pivot rule: NaN coefficient and inference, and k counts the kept columns.
+ * Two stages on the context's stream: level statistics (one wavefront per chunk of 64 levels) and the profile search (one
+ * workgroup of 1, 4 or 16 wavefronts per panel, by its level count: <= 64, <= 1024, more).  No atomics: repeated calls give
+ * identical bytes, and a panel's bytes do not depend on the other panels of the call.
+ * Argument errors (false before any device is touched): NULL pointers where there is something to read or write, n_features
+ * outside [1, 32], negative counts, a family other than ANOFOX_GLMM_GAUSSIAN ("glmm: ... is not built"), and for the host form
+ * offsets that are not non-decreasing or do not cover [0, n_levels] and stay within [0, n_rows].  The device form is
+ * asynchronous; x_cols is a host array of device pointers, as in the other families.
+ * anofox_hip_glmm_test_hooks (for measurements and tests; 0 restores the library's rule): stats_only != 0 makes a call stop
+ * after the level statistics, so that the stage can be timed alone (the outputs are then not written); wave_mask (bit 0, 1, 2:
+ * the search launch of 1, 4, 16 wavefronts) keeps the device form from making the other launches, whose workgroups would find
+ * no panel of their size: panels of a size that is masked out are then not fitted.
+ */
+typedef struct {
+	int family; /* ANOFOX_GLMM_GAUSSIAN 0 */
+	int fit_intercept;
+	int reml;
+	uint32_t max_iterations;
+	double tolerance;
+	int compute_inference;
+	double confidence_level;
+} AnofoxHipGlmmOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_glmm_record_len(size_t n_features);    /* p + 13 */
+ANOFOX_HIP_API size_t anofox_hip_glmm_inference_len(size_t n_features); /* 5 p + 1 */
+ANOFOX_HIP_API void anofox_hip_glmm_test_hooks(int stats_only, int wave_mask);
+ANOFOX_HIP_API bool anofox_hip_glmm_fit_batch_device(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t n_features,
+                                      int64_t n_rows, const int64_t *d_panel_level_offsets, const int64_t *d_level_row_offsets,
+                                      const double *d_y, const double *const *d_x_cols, AnofoxHipGlmmOptions options, double *d_glmm,
+                                      double *d_inference, double *d_ranef, int64_t *d_level_n, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_glmm_fit_batch_host(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t n_features,
+                                    int64_t n_rows, const int64_t *panel_level_offsets, const int64_t *level_row_offsets,
+                                    const double *y, const double *const *x_cols, AnofoxHipGlmmOptions options, double *glmm,
+                                    double *inference, double *ranef, int64_t *level_n, AnofoxError *out_error);
 
 /*
  * Grouped variance inflation factors: the Finalize loop of vif_agg (src/aggregate_functions/vif_aggregate.cpp:
