@@ -46,8 +46,9 @@ from .aft import (AftFitAggResult, AftFitPredictAggResult, AftOptions, aft_cdf, 
                   aft_test_hooks, parse_aft_options)
 from .eb_shrink import (EbShrinkOptions, ShrunkCoefficients, eb_shrink, eb_shrink_agg, eb_shrink_batch_device, eb_shrink_batch_host,  # noqa: E402
                         eb_shrink_test_hooks, parse_eb_shrink_options, shrink_coefficients)
-from .glmm import (GlmmFitAggResult, GlmmOptions, glmm_fit, glmm_fit_agg, glmm_fit_batch_device, glmm_fit_batch_host,  # noqa: E402
-                   glmm_test_hooks, parse_glmm_options)
+from .glmm import (GlmmFitAggResult, GlmmFitPredictAggResult, GlmmOptions, glmm_fit, glmm_fit_agg, glmm_fit_batch_device,  # noqa: E402
+                   glmm_fit_batch_host, glmm_fit_predict_agg, glmm_fit_predict_batch_device, glmm_fit_predict_batch_host, glmm_test_hooks,
+                   parse_glmm_options)
 from .scalar import quantile_fit, quantile_fit_path, aic, bic, elasticnet_fit, rls_fit, ols_fit, predict, predict_with_interval, ridge_fit, t_critical, vif, wls_fit, residuals_diagnostics  # noqa: E402
 
 # the scalar functions under their SQL names (src/table_functions/{ols,ridge,wls}_fit.cpp, predict.cpp,
@@ -70,6 +71,7 @@ SQL_FUNCTIONS.update({
     "anofox_stats_eb_shrink": eb_shrink, "eb_shrink": eb_shrink,
     "anofox_stats_eb_shrink_agg": eb_shrink_agg, "eb_shrink_agg": eb_shrink_agg,
     "anofox_stats_glmm_fit": glmm_fit, "glmm_fit": glmm_fit, "anofox_stats_glmm_fit_agg": glmm_fit_agg, "glmm_fit_agg": glmm_fit_agg,
+    "anofox_stats_glmm_fit_predict_agg": glmm_fit_predict_agg, "glmm_fit_predict_agg": glmm_fit_predict_agg,
     "anofox_stats_predict": predict,
     "anofox_stats_aic": aic, "aic": aic, "anofox_stats_bic": bic, "bic": bic,
     "anofox_stats_vif": vif, "vif": vif,
@@ -114,6 +116,7 @@ __all__ = [
     "EbShrinkOptions", "parse_eb_shrink_options", "ShrunkCoefficients", "eb_shrink", "eb_shrink_agg", "eb_shrink_batch_host",
     "eb_shrink_batch_device", "eb_shrink_test_hooks", "shrink_coefficients",
     "GlmmOptions", "GlmmFitAggResult", "parse_glmm_options", "glmm_fit", "glmm_fit_agg", "glmm_fit_batch_host", "glmm_fit_batch_device", "glmm_test_hooks",
+    "GlmmFitPredictAggResult", "glmm_fit_predict_agg", "glmm_fit_predict_batch_host", "glmm_fit_predict_batch_device",
 ]
 
 

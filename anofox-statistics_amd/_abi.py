@@ -236,6 +236,10 @@ class AnofoxHipGlmmOptions(C.Structure):  # the batch entries' options (anofox_s
                 ("tolerance", C.c_double), ("compute_inference", C.c_int), ("confidence_level", C.c_double)]
 
 
+class AnofoxHipGlmmPredictOptions(C.Structure):  # anofox_stats_hip.h, 16 bytes; interval 0 none, 1 confidence, 2 prediction
+    _fields_ = [("interval", C.c_int), ("level", C.c_double)]
+
+
 class AnofoxGlmmOptions(C.Structure):  # anofox_stats_ffi.h:2442-2460, 88 bytes
     _fields_ = [("family", C.c_int), ("fit_intercept", C.c_bool), ("max_iterations", C.c_uint32), ("tolerance", C.c_double),
                 ("compute_inference", C.c_bool), ("confidence_level", C.c_double), ("reml", C.c_bool), ("theta", C.c_double),
@@ -585,6 +589,14 @@ SYMBOLS = {
     "anofox_hip_glmm_fit_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64),
                                                   C.POINTER(C.c_int64), _DP, C.POINTER(_DP), AnofoxHipGlmmOptions, _DP, _DP, _DP,
                                                   C.POINTER(C.c_int64), _ERRP]),
+    "anofox_hip_glmm_pred_len": (C.c_size_t, []),
+    "anofox_hip_glmm_fit_predict_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.POINTER(C.c_void_p), AnofoxHipGlmmOptions,
+                                                            AnofoxHipGlmmPredictOptions, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, _ERRP]),
+    "anofox_hip_glmm_fit_predict_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_size_t, C.c_int64, C.POINTER(C.c_int64),
+                                                          C.POINTER(C.c_int64), _DP, C.POINTER(_DP), AnofoxHipGlmmOptions,
+                                                          AnofoxHipGlmmPredictOptions, _DP, _DP, _DP, C.POINTER(C.c_int64), _DP, _ERRP]),
     "anofox_glmm_fit": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxDataArray), C.c_size_t, C.POINTER(C.c_int32), C.c_size_t,
                                    C.c_void_p, C.c_size_t, AnofoxGlmmOptions, C.POINTER(AnofoxGlmmResult), _ERRP]),
     "anofox_free_glmm_result": (None, [C.POINTER(AnofoxGlmmResult)]),

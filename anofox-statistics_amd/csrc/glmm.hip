@@ -1,15 +1,22 @@
-// glmm.hip — grouped Gaussian linear mixed models with one random intercept (lmm_profile.h): the two kernels and the entry points
-// anofox_hip_glmm_fit_batch_{device,host}, anofox_hip_glmm_record_len / _inference_len / _test_hooks, anofox_glmm_fit / anofox_free_glmm_result.
+// glmm.hip — grouped Gaussian linear mixed models with one random intercept (lmm_profile.h): the three kernels and the entry points
+// anofox_hip_glmm_fit_batch_{device,host}, anofox_hip_glmm_fit_predict_batch_{device,host}, anofox_hip_glmm_record_len /
+// _inference_len / _pred_len / _test_hooks, anofox_glmm_fit / anofox_free_glmm_result.
 //
 // The contract and the method: lmm_profile.h and DESIGN.md §1, "Linear mixed models".
 //   lm_stats_kernel: 64 lanes per workgroup = one wavefront per chunk of 64 levels of a panel (grid-stride over the chunk
 //     numbers).  Writes the level records {n, ybar, abar[k]}, a validity byte per row and the chunk's partial of [W w; w' omega]
 //     into the context's workspace.  It passes k + 2 + E times over a chunk's rows; only the first pass is HBM traffic while the
 //     chunk fits the caches (lmm_profile.h; docs/MEASUREMENTS.md, "glmm", has the rates).
-//   lm_search_kernel<W>: one workgroup of W wavefronts per panel; a launch per W in {1, 4, 16}, and a workgroup whose panel
+//   lm_search_kernel<W, KEEP> (KEEP: with the writes a fit-predict needs; a fit runs the kernel compiled without them):
+//     one workgroup of W wavefronts per panel; a launch per W in {1, 4, 16}, and a workgroup whose panel
 //     belongs to another W leaves at once, so that the wavefront count of a panel depends on its own level count alone and
 //     neither form of the entry reads offsets back to size a launch (the host form, which has them, skips the launches that no
 //     panel needs).  LDS: lm_work_doubles(k, W) * 8 bytes, 32.6 KB at k = 33, W = 16.
+//   lm_predict_kernel<KC> (fit-predict only): one wavefront per tile of 256 rows of a panel, the tiles numbered without a prefix
+//     sum (panel g owns the numbers from (its first row - the call's first row) / 256 + g on).  The wavefront stages the panel's
+//     {theta, s2, beta, L^-1} from the call's scratch in LDS (4.8 KB at k = 33), then every lane scores its rows: the columns are
+//     read once, lanes over rows, and the level of a row is found by bisection of the level offsets between the levels of the
+//     tile's first and last row.  KC in {4, 9, 17, 33} is the compiled width (the lane's L^-1 c lives in KC registers).
 // No atomics: the partials of a panel are added in a fixed order, so repeated calls give identical bytes.
 #include <math.h>
 #include <stdlib.h>
@@ -39,7 +46,14 @@ std::atomic<int> g_stats_only{0}, g_wave_mask{0}; // anofox_hip_glmm_test_hooks
 struct LmArgs {
 	LmProblem P; // P.x is set in the kernel
 	const double *x[kLmMaxP];
+	// fit-predict
+	double *pred; // [n_rows x 5]
+	int interval;
+	double z;
+	int64_t n_tiles; // n_rows / kLmPredTile + n_panels
 };
+
+constexpr int64_t kLmPredTile = 256;
 
 __device__ __forceinline__ LmProblem lm_problem(const LmArgs &a, const double **lds_x) {
 #pragma unroll
@@ -61,7 +75,7 @@ __global__ __launch_bounds__(64) void lm_stats_kernel(LmArgs a) {
 	}
 }
 
-template <int W>
+template <int W, bool KEEP>
 __global__ __launch_bounds__(64 * W) void lm_search_kernel(LmArgs a) {
 	extern __shared__ double lm_lds[];
 	__shared__ const double *lm_x[kLmMaxP];
@@ -69,7 +83,79 @@ __global__ __launch_bounds__(64 * W) void lm_search_kernel(LmArgs a) {
 	for (int64_t g = blockIdx.x; g < P.n_panels; g += gridDim.x) {
 		const int64_t l0 = lm_clip(P.plo[g], P.n_levels), l1 = lm_clip(P.plo[g + 1], P.n_levels);
 		if (lm_wave_count(l1 > l0 ? l1 - l0 : 0) != W) continue;
-		lm_fit_panel(P, g, W, lm_lds);
+		lm_fit_panel<KEEP>(P, g, W, lm_lds);
+	}
+}
+
+// the first row of panel g (g == n_panels: the end of the last), clipped into the arrays
+__device__ __forceinline__ int64_t lm_panel_row(const LmProblem &P, int64_t g) {
+	return lm_clip(P.lro[lm_clip(P.plo[g], P.n_levels)], P.n_rows);
+}
+__device__ __forceinline__ int64_t lm_tile_base(const LmProblem &P, int64_t g) {
+	const int64_t d = lm_panel_row(P, g) - lm_panel_row(P, 0);
+	return (d > 0 ? d : 0) / kLmPredTile + g;
+}
+
+template <int KC>
+__global__ __launch_bounds__(64) void lm_predict_kernel(LmArgs a) {
+	__shared__ const double *lm_x[kLmMaxP];
+	__shared__ double s_keep[2 + KC];
+	__shared__ double s_linv[KC * (KC + 1) / 2];
+	const LmProblem P = lm_problem(a, lm_x);
+	const int k = lm_k(P.p, P.fit_intercept), lane = (int)threadIdx.x, tri = k * (k + 1) / 2;
+	for (int64_t v = blockIdx.x; v < a.n_tiles; v += gridDim.x) {
+		// the panel of tile number v: the last one whose base is not above v (every lane makes the same search)
+		int64_t ga = 0, gb = P.n_panels - 1;
+		while (ga < gb) {
+			const int64_t mid = ga + (gb - ga + 1) / 2;
+			if (lm_tile_base(P, mid) <= v) ga = mid;
+			else gb = mid - 1;
+		}
+		const int64_t g = ga, j = v - lm_tile_base(P, g);
+		const int64_t l0 = lm_clip(P.plo[g], P.n_levels);
+		int64_t l1 = lm_clip(P.plo[g + 1], P.n_levels);
+		if (l1 < l0) l1 = l0;
+		const int64_t p0 = lm_clip(P.lro[l0], P.n_rows);
+		int64_t p1 = lm_clip(P.lro[l1], P.n_rows);
+		if (p1 < p0) p1 = p0;
+		if (j < 0 || l1 == l0) continue;
+		const int64_t r0 = p0 + j * kLmPredTile;
+		if (r0 >= p1) continue;
+		const int64_t r1 = r0 + kLmPredTile < p1 ? r0 + kLmPredTile : p1;
+		if (!(P.keep_ok[g] == 1.0)) { // a failed panel (or one whose search was masked out)
+			for (int64_t i = r0 + lane; i < r1; i += 64)
+				for (int q = 0; q < kLmPredLen; ++q) a.pred[i * kLmPredLen + q] = NAN;
+			continue;
+		}
+		const double *kp = P.keep + g * lm_keep_len(k);
+		__syncthreads(); // the tile before
+		for (int c = lane; c < 2 + k; c += 64) s_keep[c] = kp[c];
+		for (int e = lane; e < KC * (KC + 1) / 2; e += 64) s_linv[e] = e < tri ? kp[2 + k + e] : 0.0;
+		__syncthreads();
+		// the level of a row: the last level of [l0, l1) that starts at or before it (levels without rows are passed over)
+		auto level_of = [&](int64_t i, int64_t lo, int64_t hi) {
+			while (lo < hi) {
+				const int64_t mid = lo + (hi - lo + 1) / 2;
+				if (lm_clip(P.lro[mid], P.n_rows) <= i) lo = mid;
+				else hi = mid - 1;
+			}
+			return lo;
+		};
+		const int64_t la = level_of(r0, l0, l1 - 1), lb = level_of(r1 - 1, la, l1 - 1);
+		for (int64_t i = r0 + lane; i < r1; i += 64) {
+			const int64_t l = level_of(i, la, lb);
+			double out[kLmPredLen];
+			// L^-1 is read from LDS for every row: an offset the compiler cannot see through keeps it from moving the KC (KC + 1)
+			// / 2 loads, which do not depend on the row, out of this loop into registers (1364 bytes of scratch per lane at KC = 33).
+			// To re-check: hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-fast-math --cuda-device-only
+			// -Rpass-analysis=kernel-resource-usage -c glmm.hip; lm_predict_kernel<4 | 9 | 17 | 33> must report ScratchSize 0
+			// (50 / 71 / 101 / 138 VGPRs with ROCm 7's clang).  If a compiler sees through the offset the kernel stays correct and
+			// only spills.
+			int at = 0;
+			asm volatile("" : "+v"(at));
+			lm_predict_row<KC>(P, k, i, P.level_pred + l * lm_level_pred_len(k), s_keep[1], s_keep + 2, s_linv + at, a.interval, a.z, out);
+			for (int q = 0; q < kLmPredLen; ++q) a.pred[i * kLmPredLen + q] = out[q];
+		}
 	}
 }
 
@@ -113,7 +199,8 @@ struct Classes {
 // the fit of n_panels panels on device-resident inputs, enqueued on the context's stream (ctx->mu held by the caller)
 bool launch_glmm(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t p, int64_t n_rows, const int64_t *d_plo,
                  const int64_t *d_lro, const double *d_y, const double *const *x_cols, const AnofoxHipGlmmOptions &o, double *d_rec,
-                 double *d_inf, double *d_ranef, int64_t *d_level_n, const Classes &cls, AnofoxError *e) {
+                 double *d_inf, double *d_ranef, int64_t *d_level_n, const Classes &cls, AnofoxError *e,
+                 const AnofoxHipGlmmPredictOptions *predict = nullptr, double *d_pred = nullptr) {
 	if (n_panels == 0) return true;
 	LmArgs a;
 	memset(&a, 0, sizeof a);
@@ -124,7 +211,14 @@ bool launch_glmm(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size
 	const size_t lev = align_up((size_t)(n_levels > 0 ? n_levels : 1) * (k + 2) * sizeof(double), 256);
 	const size_t parts = align_up((size_t)P.n_numbers * E * sizeof(double), 256);
 	const size_t valid = (size_t)(n_rows > 0 ? n_rows : 1);
-	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, lev + parts + valid, "glmm scratch", e)) return false;
+	// a fit-predict keeps more in the same scratch, behind what the fit uses: the fit's own bytes and their places do not change
+	const size_t valid_al = align_up(valid, 256);
+	const size_t keep = predict ? align_up((size_t)n_panels * lm_keep_len(k) * sizeof(double), 256) : 0;
+	const size_t keep_ok = predict ? align_up((size_t)n_panels * sizeof(double), 256) : 0;
+	const size_t level_pred = predict ? (size_t)(n_levels > 0 ? n_levels : 1) * lm_level_pred_len(k) * sizeof(double) : 0;
+	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, predict ? lev + parts + valid_al + keep + keep_ok + level_pred : lev + parts + valid,
+	                   "glmm scratch", e))
+		return false;
 	P.y = d_y;
 	for (size_t j = 0; j < p; ++j) a.x[j] = x_cols[j];
 	P.p = (int)p;
@@ -147,6 +241,17 @@ bool launch_glmm(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size
 	P.ranef = d_ranef;
 	P.level_n = d_level_n;
 	hipStream_t st = ctx->stream;
+	if (predict) {
+		char *base = (char *)ctx->ws + lev + parts + valid_al;
+		P.keep = (double *)base;
+		P.keep_ok = (double *)(base + keep);
+		P.level_pred = (double *)(base + keep + keep_ok);
+		a.pred = d_pred;
+		a.interval = predict->interval;
+		a.z = predict->interval ? hostmath::normal_quantile(0.5 + predict->level / 2.0) : NAN;
+		a.n_tiles = n_rows / kLmPredTile + n_panels;
+		if (hip_fail(hipMemsetAsync(P.keep_ok, 0, (size_t)n_panels * sizeof(double), st), "hipMemsetAsync", e)) return false;
+	}
 	// The search kernels stride over the panels, so a launch needs no more workgroups than fill the device; the caps also keep
 	// the launches of the sizes that no panel of a device-form call needs to a few thousand workgroups that only read offsets
 	// (100 000 workgroups of 1024 threads cost 7.6 ms, docs/MEASUREMENTS.md).
@@ -158,16 +263,38 @@ bool launch_glmm(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size
 	if (g_stats_only.load()) return true;
 	const int mask = g_wave_mask.load() ? g_wave_mask.load() : 7;
 	if (cls.need[0] && (mask & 1)) {
-		hipLaunchKernelGGL(lm_search_kernel<1>, pgrid(1 << 16), dim3(64), lm_work_doubles(k, 1) * sizeof(double), st, a);
+		if (predict) hipLaunchKernelGGL((lm_search_kernel<1, true>), pgrid(1 << 16), dim3(64), lm_work_doubles(k, 1) * sizeof(double), st, a);
+		else hipLaunchKernelGGL((lm_search_kernel<1, false>), pgrid(1 << 16), dim3(64), lm_work_doubles(k, 1) * sizeof(double), st, a);
 		if (hip_fail(hipGetLastError(), "lm_search_kernel<1>", e)) return false;
 	}
 	if (cls.need[1] && (mask & 2)) {
-		hipLaunchKernelGGL(lm_search_kernel<4>, pgrid(1 << 12), dim3(256), lm_work_doubles(k, 4) * sizeof(double), st, a);
+		if (predict) hipLaunchKernelGGL((lm_search_kernel<4, true>), pgrid(1 << 12), dim3(256), lm_work_doubles(k, 4) * sizeof(double), st, a);
+		else hipLaunchKernelGGL((lm_search_kernel<4, false>), pgrid(1 << 12), dim3(256), lm_work_doubles(k, 4) * sizeof(double), st, a);
 		if (hip_fail(hipGetLastError(), "lm_search_kernel<4>", e)) return false;
 	}
 	if (cls.need[2] && (mask & 4)) {
-		hipLaunchKernelGGL(lm_search_kernel<16>, pgrid(1 << 10), dim3(1024), lm_work_doubles(k, 16) * sizeof(double), st, a);
+		if (predict) hipLaunchKernelGGL((lm_search_kernel<16, true>), pgrid(1 << 10), dim3(1024), lm_work_doubles(k, 16) * sizeof(double), st, a);
+		else hipLaunchKernelGGL((lm_search_kernel<16, false>), pgrid(1 << 10), dim3(1024), lm_work_doubles(k, 16) * sizeof(double), st, a);
 		if (hip_fail(hipGetLastError(), "lm_search_kernel<16>", e)) return false;
+	}
+	if (predict) {
+		const dim3 tgrid((unsigned)(a.n_tiles < cap ? a.n_tiles : cap));
+		if (k <= 4) hipLaunchKernelGGL(lm_predict_kernel<4>, tgrid, dim3(64), 0, st, a);
+		else if (k <= 9) hipLaunchKernelGGL(lm_predict_kernel<9>, tgrid, dim3(64), 0, st, a);
+		else if (k <= 17) hipLaunchKernelGGL(lm_predict_kernel<17>, tgrid, dim3(64), 0, st, a);
+		else hipLaunchKernelGGL(lm_predict_kernel<33>, tgrid, dim3(64), 0, st, a);
+		if (hip_fail(hipGetLastError(), "lm_predict_kernel", e)) return false;
+	}
+	return true;
+}
+
+// the predict options' own rules, answered before any device is touched
+bool check_glmm_predict(const AnofoxHipGlmmPredictOptions &q, const void *pred, int64_t n_panels, AnofoxError *e) {
+	if (n_panels > 0 && !pred) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "pred is NULL"); return false; }
+	if (q.interval < 0 || q.interval > 2) { set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glmm: interval must be 0, 1 or 2"); return false; }
+	if (q.interval != 0 && !(q.level > 0.0 && q.level < 1.0)) {
+		set_error(e, ANOFOX_ERROR_INVALID_INPUT, "glmm: level must be in (0, 1)");
+		return false;
 	}
 	return true;
 }
@@ -188,7 +315,7 @@ bool check_glmm_offsets(int64_t n_panels, int64_t n_levels, int64_t n_rows, cons
 // host pointers: one staging of the whole call, the kernels, the copies back
 bool glmm_host(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t p, int64_t n_rows, const int64_t *plo, const int64_t *lro,
                const double *y, const double *const *x_cols, const AnofoxHipGlmmOptions &o, double *rec, double *inf, double *ranef,
-               int64_t *level_n, AnofoxError *e) {
+               int64_t *level_n, AnofoxError *e, const AnofoxHipGlmmPredictOptions *predict = nullptr, double *pred = nullptr) {
 	if (!(ctx = host_context(ctx, e))) return false;
 	const size_t G = (size_t)n_panels, L = (size_t)n_levels, rec_len = p + 13, inf_len = 5 * p + 1;
 	Classes cls;
@@ -202,7 +329,9 @@ bool glmm_host(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t
 	hipStream_t st = ctx->stream;
 	int64_t *d_plo, *d_lro, *d_ln;
 	StagedColumns c;
-	double *d_rec, *d_inf, *d_ranef;
+	double *d_rec, *d_inf, *d_ranef, *d_pred = nullptr;
+	// only the rows of [lro[0], lro[n_levels]) are written, so only they are copied back
+	const size_t w0 = predict ? (size_t)lro[0] * kLmPredLen : 0, w1 = predict ? (size_t)lro[L] * kLmPredLen : 0;
 	if (!stage_call(ctx, e, [&](Stage &s) {
 		    d_plo = s.put(plo, G + 1);
 		    d_lro = s.put(lro, L + 1);
@@ -211,9 +340,12 @@ bool glmm_host(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t
 		    d_inf = inf ? s.take<double>(G * inf_len) : nullptr;
 		    d_ranef = s.take<double>(L);
 		    d_ln = level_n ? s.take<int64_t>(L) : nullptr;
+		    if (predict) d_pred = s.take<double>((size_t)n_rows * kLmPredLen);
 	    }))
 		return false;
-	if (!launch_glmm(ctx, n_panels, n_levels, p, n_rows, d_plo, d_lro, c.y, c.x, o, d_rec, d_inf, d_ranef, d_ln, cls, e)) return false;
+	if (!launch_glmm(ctx, n_panels, n_levels, p, n_rows, d_plo, d_lro, c.y, c.x, o, d_rec, d_inf, d_ranef, d_ln, cls, e, predict, d_pred))
+		return false;
+	if (w1 > w0 && !d2h(pred + w0, d_pred + w0, (w1 - w0) * sizeof(double), st, e)) return false;
 	if (!d2h(rec, d_rec, G * rec_len * sizeof(double), st, e)) return false;
 	if (inf && !d2h(inf, d_inf, G * inf_len * sizeof(double), st, e)) return false;
 	if (!d2h(ranef, d_ranef, L * sizeof(double), st, e)) return false;
@@ -289,6 +421,41 @@ bool anofox_hip_glmm_fit_batch_host(AnofoxHipContext *ctx, int64_t n_panels, int
 	if (n_panels == 0) return true;
 	return glmm_host(ctx, n_panels, n_levels, n_features, n_rows, panel_level_offsets, level_row_offsets, y, x_cols, options, glmm, inference,
 	                 ranef, level_n, out_error);
+}
+
+size_t anofox_hip_glmm_pred_len(void) { return kLmPredLen; }
+
+bool anofox_hip_glmm_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t n_features, int64_t n_rows,
+                                              const int64_t *d_panel_level_offsets, const int64_t *d_level_row_offsets, const double *d_y,
+                                              const double *const *d_x_cols, AnofoxHipGlmmOptions options,
+                                              AnofoxHipGlmmPredictOptions predict, double *d_glmm, double *d_inference, double *d_ranef,
+                                              int64_t *d_level_n, double *d_pred, AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_glmm(n_panels, n_levels, n_features, n_rows, d_panel_level_offsets, d_level_row_offsets, d_y, d_x_cols, options.family, d_glmm,
+	                d_ranef, out_error))
+		return false;
+	if (!check_glmm_predict(predict, d_pred, n_panels, out_error)) return false;
+	if (!ctx) { set_error(out_error, ANOFOX_ERROR_INVALID_INPUT, "context is NULL"); return false; }
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	if (hip_fail(hipSetDevice(ctx->device), "hipSetDevice", out_error)) return false;
+	return launch_glmm(ctx, n_panels, n_levels, n_features, n_rows, d_panel_level_offsets, d_level_row_offsets, d_y, d_x_cols, options, d_glmm,
+	                   d_inference, d_ranef, d_level_n, Classes(), out_error, &predict, d_pred);
+}
+
+bool anofox_hip_glmm_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t n_features, int64_t n_rows,
+                                            const int64_t *panel_level_offsets, const int64_t *level_row_offsets, const double *y,
+                                            const double *const *x_cols, AnofoxHipGlmmOptions options, AnofoxHipGlmmPredictOptions predict,
+                                            double *glmm, double *inference, double *ranef, int64_t *level_n, double *pred,
+                                            AnofoxError *out_error) {
+	reset_error(out_error);
+	if (!check_glmm(n_panels, n_levels, n_features, n_rows, panel_level_offsets, level_row_offsets, y, x_cols, options.family, glmm, ranef,
+	                out_error))
+		return false;
+	if (!check_glmm_predict(predict, pred, n_panels, out_error)) return false;
+	if (!check_glmm_offsets(n_panels, n_levels, n_rows, panel_level_offsets, level_row_offsets, out_error)) return false;
+	if (n_panels == 0) return true;
+	return glmm_host(ctx, n_panels, n_levels, n_features, n_rows, panel_level_offsets, level_row_offsets, y, x_cols, options, glmm, inference,
+	                 ranef, level_n, out_error, &predict, pred);
 }
 
 // A batch of one panel with anofox_ols_fit's conventions: argument checks first, NULL entries -> NaN, the arrays malloc'ed.

@@ -14,6 +14,21 @@
 //     theta^ : the root of u -> theta dl/dtheta, u = log theta, on [log 1e-10, log 1e10] (lm_fit_panel)
 //     BLUP b_j = theta lambda_j r_j
 //
+// Fit-predict ("Mixed-model fit-predict").  A row a of level j is scored with
+//     yhat_fixed = a'beta^      yhat = yhat_fixed + b^_j      s_j = theta^ lambda_j  (0, like b^_j, for a level without a valid row)
+//     se^2 = s2 [ c'A^-1 c + theta^ / (1 + n_j theta^) ],   c = a - s_j abar_j
+// the variance of the prediction error (a'beta^ + b^_j) - (a'beta + b_j) at known theta.  Derivation: at known beta the BLUP is
+// b~_j = s_j (ybar_j - abar_j'beta), and b~_j - b_j has variance s2 theta / (1 + n_j theta) (the posterior variance of b_j given
+// the level's mean: sb2 - sb2^2 / (sb2 + s2 / n_j)).  With beta^ in place of beta, b^_j = b~_j - s_j abar_j'(beta^ - beta), so the
+// error is  c'(beta^ - beta) + (b~_j - b_j).  b~_j - b_j is the error of a conditional mean given y and hence uncorrelated with
+// every linear function of y, beta^ - beta (GLS, variance s2 A^-1) among them: the two variances add.  n_j = 0: c = a and the
+// variance is s2 (a'A^-1 a + theta^), an unseen level.  theta^ = 0: the OLS confidence variance s2 a'(X'X)^-1 a.
+// c'A^-1 c = |L^-1 c|^2 with A = L L': a forward substitution against the factor's inverse, which the last evaluation of the
+// search has already formed, and not the expanded a'Ma - 2 a'(M s_j abar_j) + s_j^2 abar_j'M abar_j: for a level with many rows
+// s_j -> 1 and c = a - abar_j is small against a, so the expanded form loses what the difference cancels and may turn negative,
+// while the sum of squares cannot; it also needs no k x k product per level.  A column dropped by the pivot rule has a zero row
+// and column in L^-1 and a zero coefficient, so it contributes nothing.
+//
 // One source for both builds (the lanes of glm_irls.h).  Two stages:
 //   lm_chunk_stats  ONE WAVEFRONT per chunk of 64 levels of a panel.  Sweep A: per level the valid rows (a byte per row in a
 //                   scratch that only the row's own lane touches), n_j and the means, into the level record {n, ybar, abar[k]}.
@@ -91,6 +106,10 @@ struct LmProblem {
 	double *inf;      // [n_panels x (5 p + 1)] or nullptr
 	double *ranef;    // [n_levels]
 	int64_t *level_n; // [n_levels] or nullptr
+	// fit-predict only (nullptr for a fit): what the search keeps for the prediction pass, in the call's scratch
+	double *keep;       // [n_panels x lm_keep_len(k)]: {theta, s2, beta[k] (0 for a dropped column), L^-1 packed lower (lm_idx)}
+	double *keep_ok;    // [n_panels]: 1.0 once the panel's record above is written (the entry zeroes it before the launches)
+	double *level_pred; // [n_levels x (k + 3)]: {s_j, b_j, theta / (1 + n_j theta), s_j abar_j[k]}
 };
 
 GI_HD int lm_k(int p, int fit_intercept) { return p + (fit_intercept ? 1 : 0); }
@@ -107,6 +126,9 @@ GI_HD int lm_red_doubles(int k, int W) {
 GI_HD size_t lm_work_doubles(int k, int W) {
 	return 2 * (size_t)(k + 1) * glm::gi_aug_ld(k) + (size_t)lm_entries(k) + 2 * (size_t)(k + 1) + (size_t)lm_red_doubles(k, W);
 }
+GI_HD int lm_keep_len(int k) { return 2 + k + k * (k + 1) / 2; }
+GI_HD int lm_level_pred_len(int k) { return k + 3; }
+constexpr int kLmPredLen = 5; // yhat, yhat_fixed, se, lower, upper
 GI_HD int64_t lm_clip(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 // the first chunk number of panel g (g == n_panels: the count of numbers is at most this)
 GI_HD int64_t lm_chunk_base(const int64_t *plo, int64_t g) { return (plo[g] - plo[0]) / kLmChunkLevels + g; }
@@ -501,7 +523,9 @@ GI_DEV void lm_fail_panel(const LmProblem &P, int64_t g, int64_t l0, int64_t N, 
 	LM_WAVES_END
 }
 
-// The fit of panel g by a workgroup of W wavefronts on `mem` (lm_work_doubles(k, W) doubles).
+// The fit of panel g by a workgroup of W wavefronts on `mem` (lm_work_doubles(k, W) doubles).  KEEP false: a fit that is compiled
+// without the writes of a fit-predict (P.keep and P.level_pred are then not looked at), so a fit runs the code it always ran.
+template <bool KEEP = true>
 GI_DEV void lm_fit_panel(const LmProblem &P, int64_t g, int W, double *mem) {
 	const int k = lm_k(P.p, P.fit_intercept), E = lm_entries(k), rl = k + 2, p = P.p, T = 64 * W;
 	const LmWork M = lm_work(mem, k);
@@ -638,7 +662,7 @@ GI_DEV void lm_fit_panel(const LmProblem &P, int64_t g, int W, double *mem) {
 		if (lane == 0 && !P.fit_intercept) inf[5 * p] = NAN;
 	}
 	LM_WAVE0_END
-	// the BLUPs
+	// the BLUPs, and for a fit-predict the prologue of every level
 	LM_WAVES_BEGIN(w, W)
 	GI_LANES_BEGIN(lane)
 	for (int64_t j = w * 64 + lane; j < N; j += T) {
@@ -651,9 +675,78 @@ GI_DEV void lm_fit_panel(const LmProblem &P, int64_t g, int W, double *mem) {
 			bl = theta > 0.0 ? theta * (nj / (1.0 + nj * theta)) * res : 0.0;
 		}
 		P.ranef[l0 + j] = bl;
+		if (KEEP && P.level_pred) {
+			double *lp = P.level_pred + (l0 + j) * lm_level_pred_len(k);
+			const double sj = nj > 0.0 && theta > 0.0 ? theta * (nj / (1.0 + nj * theta)) : 0.0;
+			lp[0] = sj;
+			lp[1] = nj > 0.0 ? bl : 0.0;
+			lp[2] = nj > 0.0 ? theta / (1.0 + nj * theta) : theta;
+			for (int c = 0; c < k; ++c) lp[3 + c] = sj * r[2 + c];
+		}
 	}
 	GI_LANES_END
 	LM_WAVES_END
+	// what the prediction pass needs of the panel: M.beta and M.linv are those of the last evaluation
+	if (KEEP && P.keep) {
+		double *kp = P.keep + g * lm_keep_len(k);
+		const int tri = k * (k + 1) / 2;
+		LM_WAVES_BEGIN(w, W)
+		GI_LANES_BEGIN(lane)
+		const int t = w * 64 + lane;
+		if (t == 0) {
+			kp[0] = theta;
+			kp[1] = ev.sigma2;
+			P.keep_ok[g] = 1.0;
+		}
+		for (int c = t; c < k; c += T) kp[2 + c] = M.beta[c];
+		for (int e = t; e < tri; e += T) {
+			int a, b;
+			lm_entry(e, a, b);
+			kp[2 + k + e] = M.linv[a * ld + b];
+		}
+		GI_LANES_END
+		LM_WAVES_END
+	}
+}
+
+// ---- the prediction pass: one row, by one lane ----
+
+// The five values of row i of a fitted panel into out.  KC >= k is the compiled width: `beta` holds k coefficients and `linv` the
+// packed L^-1 padded with zeros to KC (KC + 1) / 2 entries (both staged per workgroup), `lp` is the level's prologue record.
+template <int KC>
+GI_DEV void lm_predict_row(const LmProblem &P, int k, int64_t i, const double *lp, double s2, const double *beta, const double *linv,
+                           int interval, double z, double *out) {
+	double u[KC];
+	GI_UNROLL
+	for (int r = 0; r < KC; ++r) u[r] = 0.0;
+	double fixed = 0.0;
+	bool ok = true;
+	GI_UNROLL
+	for (int c = 0; c < KC; ++c) {
+		if (c < k) {
+			const double a = lm_elem(P, k, c, i);
+			ok = ok && gi_finite(a);
+			fixed += a * beta[c];
+			const double cc = a - lp[3 + c];
+			GI_UNROLL
+			for (int r = c; r < KC; ++r) u[r] += linv[lm_idx(r, c)] * cc;
+		}
+	}
+	double quad = 0.0;
+	GI_UNROLL
+	for (int r = 0; r < KC; ++r) quad += u[r] * u[r];
+	const double se2 = s2 * (quad + lp[2]), yhat = fixed + lp[1];
+	double lower = NAN, upper = NAN;
+	if (interval != 0) {
+		const double half = z * sqrt(interval == 2 ? se2 + s2 : se2);
+		lower = yhat - half;
+		upper = yhat + half;
+	}
+	out[0] = ok ? yhat : NAN;
+	out[1] = ok ? fixed : NAN;
+	out[2] = ok ? sqrt(se2) : NAN;
+	out[3] = ok ? lower : NAN;
+	out[4] = ok ? upper : NAN;
 }
 
 } // namespace lmm

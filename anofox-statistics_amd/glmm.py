@@ -1,5 +1,6 @@
-"""Grouped Gaussian linear mixed models with one random intercept (csrc/glmm.hip): the aggregate glmm_fit_agg, the scalar glmm_fit
-and the numpy / tensor drivers of anofox_hip_glmm_fit_batch_{host,device}.  The contract: DESIGN.md §1 "Linear mixed models".  A
+"""Grouped Gaussian linear mixed models with one random intercept (csrc/glmm.hip): the aggregates glmm_fit_agg and
+glmm_fit_predict_agg, the scalar glmm_fit and the numpy / tensor drivers of anofox_hip_glmm_fit_batch_{host,device} and
+anofox_hip_glmm_fit_predict_batch_{host,device}.  The contract: DESIGN.md §1 "Linear mixed models".  A
 panel whose status is not 0 is None (SQL NULL) in the aggregate and NaN in the arrays."""
 from __future__ import annotations
 
@@ -16,6 +17,8 @@ from .options import InvalidInputException, _extract_double
 
 GAUSSIAN_NAMES = ("gaussian", "normal", "lmm")
 NOT_BUILT_FAMILIES = {"poisson": 1, "binomial": 2, "logistic": 2, "negbinomial": 3, "gamma": 4, "tweedie": 5}
+PRED_NAMES = ("yhat", "yhat_fixed", "se", "lower", "upper")
+INTERVALS = {"none": 0, "confidence": 1, "prediction": 2}
 RECORD_NAMES = ("intercept", "var_group", "var_residual", "icc", "log_likelihood", "aic", "bic", "deviance", "n_observations", "n_groups",
                 "iterations", "converged", "status")
 
@@ -29,6 +32,11 @@ class GlmmOptions:
     tolerance: float = 1e-8
     compute_inference: bool = False
     confidence_level: float = 0.95
+    interval: int = 0                  # fit-predict only: 0 none, 1 confidence, 2 prediction
+    level: Optional[float] = None      # fit-predict only; None: confidence_level
+
+    def predict_options(self) -> "_abi.AnofoxHipGlmmPredictOptions":
+        return _abi.AnofoxHipGlmmPredictOptions(int(self.interval), float(self.confidence_level if self.level is None else self.level))
 
     def batch_options(self) -> "_abi.AnofoxHipGlmmOptions":
         return _abi.AnofoxHipGlmmOptions(self.family, int(self.fit_intercept), int(self.reml), int(self.max_iterations), float(self.tolerance),
@@ -43,9 +51,22 @@ def _flag(v) -> bool:
     return str(v).lower() in ("true", "1", "t", "yes") if isinstance(v, str) else bool(v)
 
 
-def parse_glmm_options(opts) -> GlmmOptions:
+def parse_interval(val) -> int:
+    """False, None or 'none' -> 0; 'confidence' -> 1; 'prediction' or True -> 2"""
+    if val is None or val is False:
+        return 0
+    if val is True:
+        return 2
+    name = str(val).lower()
+    if name not in INTERVALS:
+        raise InvalidInputException("Unknown interval '%s'. Expected 'none', 'confidence' or 'prediction'." % (val,))
+    return INTERVALS[name]
+
+
+def parse_glmm_options(opts, predict: bool = False) -> GlmmOptions:
     """glmm_fit_agg's MAP options: family (gaussian | normal | lmm), fit_intercept | intercept, reml, max_iterations | max_iter,
-    tolerance | tol, compute_inference, confidence_level.  Keys and values are case-insensitive; other keys are ignored, except
+    tolerance | tol, compute_inference, confidence_level, and for a fit-predict interval (False | None | 'none' | 'confidence' |
+    'prediction'; True: 'prediction') and level (default: confidence_level).  Keys and values are case-insensitive; other keys are ignored, except
     those that ask for what is not built (an offset, random_slopes, a family other than Gaussian), which raise."""
     if isinstance(opts, GlmmOptions):
         return opts
@@ -78,11 +99,15 @@ def parse_glmm_options(opts) -> GlmmOptions:
             out.compute_inference = _flag(val)
         elif key == "confidence_level":
             out.confidence_level = _extract_double(val)
+        elif predict and key == "interval":   # (a fit ignores the two keys of a fit-predict, like every key it does not know)
+            out.interval = parse_interval(val)
+        elif predict and key == "level" and val is not None:
+            out.level = _extract_double(val)
     return out
 
 
-def _batch(b, plo, lro, options, inference):
-    o = parse_glmm_options(options)
+def _batch(b, plo, lro, options, inference, predict=False):
+    o = parse_glmm_options(options, predict)
     plo, lro = b.array(plo, I64, None, "panel_level_offsets"), b.array(lro, I64, None, "level_row_offsets")
     G, L = b._size(plo) - 1, b._size(lro) - 1
     if G < 0 or L < 0:
@@ -93,6 +118,10 @@ def _batch(b, plo, lro, options, inference):
     inf = b.out((G, 5 * b.p + 1)) if inference or o.compute_inference else None
     batch = o.batch_options()
     batch.compute_inference = int(inf is not None)
+    if predict:
+        pred = b.out((b.N, 5))
+        b.call("anofox_hip_glmm_fit_predict_batch", G, L, b.p, b.N, plo, lro, b.y, b.cols, batch, o.predict_options(), rec, inf, ranef, ln, pred)
+        return rec, inf, ranef, ln, pred
     b.call("anofox_hip_glmm_fit_batch", G, L, b.p, b.N, plo, lro, b.y, b.cols, batch, rec, inf, ranef, ln)
     return rec, inf, ranef, ln
 
@@ -107,6 +136,18 @@ def glmm_fit_batch_device(ctx, panel_level_offsets, level_row_offsets, y, x_cols
                           use_current_torch_stream: bool = True):
     """glmm_fit_batch_host on CUDA tensors (offsets int64, y / columns float64).  Asynchronous."""
     return _batch(DeviceBatch(ctx, None, y, x_cols, use_current_torch_stream), panel_level_offsets, level_row_offsets, options, inference)
+
+
+def glmm_fit_predict_batch_host(panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False, ctx=None):
+    """glmm_fit_batch_host's four arrays (the same bytes) and pred[n_rows, 5] = (yhat, yhat_fixed, se, lower, upper);
+    anofox_hip_glmm_fit_predict_batch_host's layouts.  Rows outside the level offsets are not written."""
+    return _batch(HostBatch(ctx, None, y, x_cols), panel_level_offsets, level_row_offsets, options, inference, True)
+
+
+def glmm_fit_predict_batch_device(ctx, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False,
+                                  use_current_torch_stream: bool = True):
+    """glmm_fit_predict_batch_host on CUDA tensors.  Asynchronous."""
+    return _batch(DeviceBatch(ctx, None, y, x_cols, use_current_torch_stream), panel_level_offsets, level_row_offsets, options, inference, True)
 
 
 def glmm_test_hooks(stats_only: int = 0, wave_mask: int = 0):
@@ -172,9 +213,31 @@ def _first_seen(values):
     return codes, labels
 
 
+@dataclass
+class GlmmFitPredictAggResult(GlmmFitAggResult):
+    """glmm_fit_predict_agg's result: the fit's, and pred[n_input_rows, 5] in input row order (NaN for a row whose group is None)."""
+    pred: Optional[np.ndarray] = None
+
+    def __getattr__(self, name):   # the named views yhat, yhat_fixed, se, lower, upper
+        pred = self.__dict__.get("pred")
+        if name in PRED_NAMES and pred is not None:
+            return pred[:, PRED_NAMES.index(name)]
+        raise AttributeError(name)
+
+
 def glmm_fit_agg(keys, y, x: Sequence, group, options=None, context=None) -> GlmmFitAggResult:
     """glmm_fit_agg(y, [x...], group, options) GROUP BY keys (None: one panel).  Rows may come in any order: they are sorted by
     (key, group), a key's levels in first-seen order; a row whose group is None is dropped, as the aggregate's Update drops it."""
+    return _agg(keys, y, x, group, options, context, False)
+
+
+def glmm_fit_predict_agg(keys, y, x: Sequence, group, options=None, context=None) -> GlmmFitPredictAggResult:
+    """glmm_fit_predict_agg(y, [x...], group, options) GROUP BY keys: glmm_fit_agg's result and a score of every input row (a row
+    with y None / NaN is a prediction row: the fit drops it and it is scored all the same)."""
+    return _agg(keys, y, x, group, options, context, True)
+
+
+def _agg(keys, y, x, group, options, context, predict):
     yv = _column(y)
     n = len(yv)
     cols = [_column(c) for c in x]
@@ -199,6 +262,12 @@ def glmm_fit_agg(keys, y, x: Sequence, group, options=None, context=None) -> Glm
     L, G = len(pair_labels), len(key_labels)
     lro = np.concatenate([[0], np.cumsum(np.bincount(row_level, minlength=L))]).astype(np.int64)
     plo = np.concatenate([[0], np.cumsum(np.bincount(level_panel, minlength=G))]).astype(np.int64)
+    labels = [pair_labels[i][1] for i in level_order]
+    if predict:
+        rec, inf, ranef, ln, sorted_pred = glmm_fit_predict_batch_host(plo, lro, yv[perm], [c[perm] for c in cols], options, ctx=context)
+        pred = np.full((n, 5), np.nan)
+        pred[perm] = sorted_pred
+        return GlmmFitPredictAggResult([key_labels[i] for i in order_keys], len(cols), rec, inf, plo, labels, ranef, ln, pred)
     rec, inf, ranef, ln = glmm_fit_batch_host(plo, lro, yv[perm], [c[perm] for c in cols], options, ctx=context)
     return GlmmFitAggResult([key_labels[i] for i in order_keys], len(cols), rec, inf, plo, [pair_labels[i][1] for i in level_order], ranef, ln)
 

@@ -383,6 +383,18 @@ class Context:
         from .glmm import glmm_fit_batch_host
         return glmm_fit_batch_host(panel_level_offsets, level_row_offsets, y, x_cols, options, inference, ctx=self)
 
+    def glmm_fit_predict_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False,
+                                      use_current_torch_stream: bool = True):
+        """glmm_fit_batch_device and a score of every row (glmm.glmm_fit_predict_batch_device): (records, inference or None, ranef,
+        level_n, pred[n_rows, 5])."""
+        from .glmm import glmm_fit_predict_batch_device
+        return glmm_fit_predict_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols, options, inference,
+                                             use_current_torch_stream)
+
+    def glmm_fit_predict_batch_host(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False):
+        from .glmm import glmm_fit_predict_batch_host
+        return glmm_fit_predict_batch_host(panel_level_offsets, level_row_offsets, y, x_cols, options, inference, ctx=self)
+
     def aft_fit_batch_device(self, row_offsets, time, x_cols: Sequence, event, options: _abi.AnofoxHipAftBatchOptions,
                              inference: bool = False, use_current_torch_stream: bool = True):
         """Grouped AFT fits on CUDA tensors through the fused Newton kernel (aft.aft_fit_batch_device)."""

@@ -1467,6 +1467,42 @@ ANOFOX_HIP_API bool anofox_hip_glmm_fit_batch_host(AnofoxHipContext *ctx, int64_
                                     double *inference, double *ranef, int64_t *level_n, AnofoxError *out_error);
 
 /*
+ * Mixed-model fit-predict (glmm_fit_predict_agg): the fit above and, in the same call, a score of every row of
+ * [lro[0], lro[n_levels]).  glmm, inference, ranef and level_n are byte for byte those of anofox_hip_glmm_fit_batch_* on the
+ * same inputs.  A row of level j of a panel with status 0 whose x are all finite is scored whether or not its y is finite (a row
+ * with y = NaN is a prediction row; the fit drops it).  With s_j = theta^ lambda_j (0, like the BLUP b^_j, for a level without a
+ * valid row), abar_j the level's mean design row, A = X'V^-1 X over the kept columns and s2 = var_residual:
+ *   pred[i * 5] = { yhat = yhat_fixed + b^_j,  yhat_fixed = a_i'beta^ (what a new level gets),
+ *                   se = sqrt(s2 [c'A^-1 c + theta^ / (1 + n_j theta^)]),  c = a_i - s_j abar_j,  lower, upper }
+ * se^2 is the variance of the prediction error (a'beta^ + b^_j) - (a'beta + b_j) at known theta (csrc/lmm_profile.h has the
+ * derivation).  interval 0: lower = upper = NaN; 1 (confidence): yhat -+ z se; 2 (prediction): yhat -+ z sqrt(se^2 + s2);
+ * z the normal quantile of 1/2 + level / 2.  A column dropped by the pivot rule contributes nothing.  All five values are NaN
+ * for a row with an x that is not finite and for every row of a panel whose status is not 0.  Rows outside
+ * [lro[0], lro[n_levels]) are not written.
+ * Argument errors (false before any device is touched): the fit's own; pred NULL with n_panels > 0 ("pred is NULL"); an
+ * interval outside {0, 1, 2} ("glmm: interval must be 0, 1 or 2"); with interval != 0 a level that is NaN or outside the open
+ * (0, 1) ("glmm: level must be in (0, 1)").  anofox_hip_glmm_test_hooks applies: after stats_only nothing is scored, and the rows
+ * of a panel whose search launch is masked out are NaN.  No atomics; a panel's rows do not depend on the other panels.
+ */
+typedef struct {
+	int interval; /* 0 none, 1 confidence, 2 prediction */
+	double level;
+} AnofoxHipGlmmPredictOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_glmm_pred_len(void); /* 5: yhat, yhat_fixed, se, lower, upper */
+ANOFOX_HIP_API bool anofox_hip_glmm_fit_predict_batch_device(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t n_features,
+                                              int64_t n_rows, const int64_t *d_panel_level_offsets,
+                                              const int64_t *d_level_row_offsets, const double *d_y, const double *const *d_x_cols,
+                                              AnofoxHipGlmmOptions options, AnofoxHipGlmmPredictOptions predict, double *d_glmm,
+                                              double *d_inference, double *d_ranef, int64_t *d_level_n, double *d_pred,
+                                              AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_glmm_fit_predict_batch_host(AnofoxHipContext *ctx, int64_t n_panels, int64_t n_levels, size_t n_features,
+                                            int64_t n_rows, const int64_t *panel_level_offsets, const int64_t *level_row_offsets,
+                                            const double *y, const double *const *x_cols, AnofoxHipGlmmOptions options,
+                                            AnofoxHipGlmmPredictOptions predict, double *glmm, double *inference, double *ranef,
+                                            int64_t *level_n, double *pred, AnofoxError *out_error);
+
+/*
  * Grouped variance inflation factors: the Finalize loop of vif_agg (src/aggregate_functions/vif_aggregate.cpp:
  * 144-185) in one call.  x_cols as in the fit entry points (rows of a group contiguous; the aggregate's Update
  * has already dropped NULL rows and NaN values, :67-93).  d_vif[g] = { vif[n_features], status }
