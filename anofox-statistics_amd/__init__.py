@@ -46,6 +46,8 @@ from .aft import (AftFitAggResult, AftFitPredictAggResult, AftOptions, aft_cdf, 
                   aft_test_hooks, parse_aft_options)
 from .eb_shrink import (EbShrinkOptions, ShrunkCoefficients, eb_shrink, eb_shrink_agg, eb_shrink_batch_device, eb_shrink_batch_host,  # noqa: E402
                         eb_shrink_test_hooks, parse_eb_shrink_options, shrink_coefficients)
+from .correlation import (CorrelationAggResult, CorrelationOptions, cor_batch_device, cor_batch_host, cor_test_hooks, kendall,  # noqa: E402
+                          kendall_agg, parse_correlation_options, pearson, pearson_agg, spearman, spearman_agg)
 from .glmm import (GlmmFitAggResult, GlmmFitPredictAggResult, GlmmOptions, glmm_fit, glmm_fit_agg, glmm_fit_batch_device,  # noqa: E402
                    glmm_fit_batch_host, glmm_fit_predict_agg, glmm_fit_predict_batch_device, glmm_fit_predict_batch_host, glmm_test_hooks,
                    parse_glmm_options)
@@ -70,6 +72,9 @@ SQL_FUNCTIONS.update({
     "anofox_stats_aft_cdf": aft_cdf, "aft_cdf": aft_cdf, "anofox_stats_aft_quantile": aft_quantile, "aft_quantile": aft_quantile,
     "anofox_stats_eb_shrink": eb_shrink, "eb_shrink": eb_shrink,
     "anofox_stats_eb_shrink_agg": eb_shrink_agg, "eb_shrink_agg": eb_shrink_agg,
+    "anofox_stats_pearson": pearson, "pearson": pearson, "anofox_stats_pearson_agg": pearson_agg, "pearson_agg": pearson_agg,
+    "anofox_stats_spearman": spearman, "spearman": spearman, "anofox_stats_spearman_agg": spearman_agg, "spearman_agg": spearman_agg,
+    "anofox_stats_kendall": kendall, "kendall": kendall, "anofox_stats_kendall_agg": kendall_agg, "kendall_agg": kendall_agg,
     "anofox_stats_glmm_fit": glmm_fit, "glmm_fit": glmm_fit, "anofox_stats_glmm_fit_agg": glmm_fit_agg, "glmm_fit_agg": glmm_fit_agg,
     "anofox_stats_glmm_fit_predict_agg": glmm_fit_predict_agg, "glmm_fit_predict_agg": glmm_fit_predict_agg,
     "anofox_stats_predict": predict,
@@ -115,6 +120,8 @@ __all__ = [
     "aft_fit_predict_batch_device",
     "EbShrinkOptions", "parse_eb_shrink_options", "ShrunkCoefficients", "eb_shrink", "eb_shrink_agg", "eb_shrink_batch_host",
     "eb_shrink_batch_device", "eb_shrink_test_hooks", "shrink_coefficients",
+    "CorrelationOptions", "CorrelationAggResult", "parse_correlation_options", "pearson", "spearman", "kendall", "pearson_agg",
+    "spearman_agg", "kendall_agg", "cor_batch_host", "cor_batch_device", "cor_test_hooks",
     "GlmmOptions", "GlmmFitAggResult", "parse_glmm_options", "glmm_fit", "glmm_fit_agg", "glmm_fit_batch_host", "glmm_fit_batch_device", "glmm_test_hooks",
     "GlmmFitPredictAggResult", "glmm_fit_predict_agg", "glmm_fit_predict_batch_host", "glmm_fit_predict_batch_device",
 ]

@@ -231,6 +231,23 @@ class AnofoxHipEbShrinkOptions(C.Structure):  # the batch entries' options: the 
     _fields_ = [("method", C.c_int), ("tau_squared", C.c_double)]
 
 
+class AnofoxCorrelationOptions(C.Structure):  # anofox_stats_ffi.h:1709-1714, 16 bytes; confidence_level NaN: no interval
+    _fields_ = [("alternative", C.c_int), ("confidence_level", C.c_double)]
+
+
+class AnofoxKendallOptions(C.Structure):  # anofox_stats_ffi.h:1731-1738, 16 bytes
+    _fields_ = [("alternative", C.c_int), ("tau_type", C.c_int), ("confidence_level", C.c_double)]
+
+
+class AnofoxCorrelationResult(C.Structure):  # anofox_stats_ffi.h:1611-1628, 64 bytes
+    _fields_ = [("r", C.c_double), ("statistic", C.c_double), ("p_value", C.c_double), ("ci_lower", C.c_double), ("ci_upper", C.c_double),
+                ("confidence_level", C.c_double), ("n", C.c_size_t), ("method", C.c_char_p)]
+
+
+class AnofoxHipCorBatchOptions(C.Structure):  # the correlation batch entries' options, 24 bytes
+    _fields_ = [("method", C.c_int32), ("alternative", C.c_int32), ("tau_type", C.c_int32), ("confidence_level", C.c_double)]
+
+
 class AnofoxHipGlmmOptions(C.Structure):  # the batch entries' options (anofox_stats_hip.h), 40 bytes
     _fields_ = [("family", C.c_int), ("fit_intercept", C.c_int), ("reml", C.c_int), ("max_iterations", C.c_uint32),
                 ("tolerance", C.c_double), ("compute_inference", C.c_int), ("confidence_level", C.c_double)]
@@ -580,6 +597,15 @@ SYMBOLS = {
     "anofox_hip_eb_shrink_test_hooks": (None, [C.c_int, C.c_int64, C.c_int64]),
     "anofox_eb_shrink": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxEbShrinkOptions, C.POINTER(AnofoxEbShrinkResult), _ERRP]),
     "anofox_free_eb_shrink_result": (None, [C.POINTER(AnofoxEbShrinkResult)]),
+    "anofox_hip_cor_record_len": (C.c_size_t, []),
+    "anofox_hip_cor_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, AnofoxHipCorBatchOptions,
+                                               C.c_void_p, _ERRP]),
+    "anofox_hip_cor_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _DP, _DP, AnofoxHipCorBatchOptions, _DP, _ERRP]),
+    "anofox_hip_cor_test_hooks": (None, [C.c_int64]),
+    "anofox_pearson_cor": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxCorrelationOptions, C.POINTER(AnofoxCorrelationResult), _ERRP]),
+    "anofox_spearman_cor": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxCorrelationOptions, C.POINTER(AnofoxCorrelationResult), _ERRP]),
+    "anofox_kendall_cor": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxKendallOptions, C.POINTER(AnofoxCorrelationResult), _ERRP]),
+    "anofox_free_correlation_result": (None, [C.POINTER(AnofoxCorrelationResult)]),
     "anofox_hip_glmm_record_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_inference_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_test_hooks": (None, [C.c_int, C.c_int]),

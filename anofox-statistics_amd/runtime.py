@@ -372,6 +372,15 @@ class Context:
         from .eb_shrink import eb_shrink_batch_host
         return eb_shrink_batch_host(set_offsets, est, se, n_cols, est_stride, se_stride, options, n_items, ctx=self)
 
+    def cor_batch_device(self, row_offsets, x, y, method: int, options=None, use_current_torch_stream: bool = True):
+        """Grouped Pearson (0), Spearman (1) or Kendall (2) correlation on CUDA tensors (correlation.cor_batch_device): records[n_groups, 8]."""
+        from .correlation import cor_batch_device
+        return cor_batch_device(self, row_offsets, x, y, method, options, use_current_torch_stream)
+
+    def cor_batch_host(self, row_offsets, x, y, method: int, options=None):
+        from .correlation import cor_batch_host
+        return cor_batch_host(row_offsets, x, y, method, options, ctx=self)
+
     def glmm_fit_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False,
                               use_current_torch_stream: bool = True):
         """Grouped Gaussian random-intercept mixed models on CUDA tensors (glmm.glmm_fit_batch_device): (records, inference or None,

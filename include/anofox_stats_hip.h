@@ -547,6 +547,51 @@ ANOFOX_HIP_API bool anofox_eb_shrink(AnofoxDataArray estimate, AnofoxDataArray s
                       AnofoxEbShrinkResult *out_result, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_eb_shrink_result(AnofoxEbShrinkResult *result);
 
+/* replace AnofoxAlternative and AnofoxKendallType, anofox_stats_ffi.h:1549-1553 and 1722-1726 */
+typedef enum { ANOFOX_ALTERNATIVE_TWO_SIDED = 0, ANOFOX_ALTERNATIVE_LESS = 1, ANOFOX_ALTERNATIVE_GREATER = 2 } AnofoxAlternative;
+typedef enum { ANOFOX_KENDALL_TAU_A = 0, ANOFOX_KENDALL_TAU_B = 1, ANOFOX_KENDALL_TAU_C = 2 } AnofoxKendallType;
+
+/* replaces AnofoxCorrelationOptions, anofox_stats_ffi.h:1709-1714 — 16 bytes: alternative @0, confidence_level @8 */
+typedef struct {
+	AnofoxAlternative alternative;
+	double confidence_level; /* in (0, 1); NaN: no interval */
+} AnofoxCorrelationOptions;
+
+/* replaces AnofoxKendallOptions, anofox_stats_ffi.h:1731-1738 — 16 bytes: alternative @0, tau_type @4, confidence_level @8 (not
+ * read: Kendall's tau has no interval) */
+typedef struct {
+	AnofoxAlternative alternative;
+	AnofoxKendallType tau_type;
+	double confidence_level;
+} AnofoxKendallOptions;
+
+/* replaces AnofoxCorrelationResult, anofox_stats_ffi.h:1611-1628 — 64 bytes: six doubles @0..40, n @48, method @56 (malloc'ed by the
+ * callee, released by anofox_free_correlation_result) */
+typedef struct {
+	double r; /* Kendall: tau */
+	double statistic;
+	double p_value;
+	double ci_lower;
+	double ci_upper;
+	double confidence_level; /* Kendall: NaN */
+	size_t n;
+	char *method; /* "Pearson correlation", "Spearman rank correlation", "Kendall's TauA" / "TauB" / "TauC" */
+} AnofoxCorrelationResult;
+
+/* replace anofox_pearson_cor / anofox_spearman_cor / anofox_kendall_cor / anofox_free_correlation_result,
+ * anofox_stats_ffi.h:1827-1840 and 2198: one group through anofox_hip_cor_batch_host (below), NULL entries of the validity
+ * bitmaps as NaN (rows that are not valid).  False with ANOFOX_ERROR_INVALID_INPUT (the reference's code for every failure of
+ * these three), the result zeroed and nothing to free, before any device is touched: out_result NULL, unequal lengths
+ * ("<Name> correlation requires equal length vectors"), an unknown alternative or tau type or a confidence level outside (0, 1)
+ * ("correlation: ..."), fewer than 3 valid pairs ("<Name> correlation requires at least 3 valid pairs"). */
+ANOFOX_HIP_API bool anofox_pearson_cor(AnofoxDataArray x, AnofoxDataArray y, AnofoxCorrelationOptions options,
+                        AnofoxCorrelationResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_spearman_cor(AnofoxDataArray x, AnofoxDataArray y, AnofoxCorrelationOptions options,
+                         AnofoxCorrelationResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_kendall_cor(AnofoxDataArray x, AnofoxDataArray y, AnofoxKendallOptions options,
+                        AnofoxCorrelationResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_correlation_result(AnofoxCorrelationResult *result);
+
 /* replaces AnofoxGlmmFamily, anofox_stats_ffi.h:2433-2440 */
 typedef enum {
 	ANOFOX_GLMM_GAUSSIAN = 0,
@@ -1410,6 +1455,46 @@ ANOFOX_HIP_API bool anofox_hip_eb_shrink_batch_host(AnofoxHipContext *ctx, int64
                                      size_t n_cols, const double *est, int64_t est_stride, const double *se, int64_t se_stride,
                                      AnofoxHipEbShrinkOptions options, double *out, double *summary, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_hip_eb_shrink_test_hooks(int force_path, int64_t chunk_items, int64_t max_workgroups);
+
+/*
+ * Grouped Pearson, Spearman and Kendall correlation with the test of no association (pearson_agg, spearman_agg, kendall_agg and
+ * the three scalars above): R's cor.test with exact = FALSE in closed form.  The formulas: DESIGN.md §1 "Rank and product-moment
+ * correlation" and csrc/rank_cor.h.
+ * Input: row_offsets[n_groups + 1], group g owns rows [off[g], off[g + 1]) of x and y (n_rows doubles each).  A row is valid when
+ * x and y are both not NaN (infinities stay in); n = a group's valid rows.
+ * Output: records[g * 8] = {estimate (r, rho or tau), statistic (t; Kendall: z), p_value, ci_lower, ci_upper, n, s (Kendall's
+ * concordant minus discordant pairs, exact; NaN otherwise), status}.
+ * Status per group: 0; ANOFOX_ERROR_INSUFFICIENT_DATA 6 for n < 3, which makes every other field but n NaN.  A group whose valid
+ * x or y is constant has status 0 with estimate, statistic, p_value and the interval NaN, for all three methods.
+ * Pearson: two passes (means, then centred sums); t = r sqrt((n - 2) / (1 - r^2)) under Student's t with n - 2 degrees of
+ * freedom, |r| = 1: t = +-inf and p = 0; interval tanh(atanh r -+ z / sqrt(n - 3)), z the normal quantile of
+ * (1 + confidence_level) / 2, two-sided whatever the alternative, NaN at n = 3 and for a NaN confidence_level.  Spearman: the same
+ * on the midranks.  Kendall: tau-b (default), tau-a or tau-c; z = s / sqrt(var) with R's tie-corrected variance under the normal
+ * distribution; no interval.
+ * Groups of up to 1462 rows are worked in LDS by one wavefront each; larger ones in the context's workspace (28 bytes per row of
+ * the call), Kendall's pairs then spread over the whole device and added as integers.  Both paths give the same n, s and rho to
+ * the bit; Pearson streams on one path whatever the size.
+ * Argument errors (false before any device is touched): negative counts, a NULL array where there are groups, an unknown
+ * method, alternative or tau type, a confidence level outside (0, 1) that is not NaN (all "correlation: ..."), and for the host
+ * form offsets that are not non-decreasing within [0, n_rows].  The device form is asynchronous on the context's stream.
+ * anofox_hip_cor_test_hooks (for tests): small_cap lowers the rows a group may have on the small path for later calls of the
+ * process; 0 restores 1462.
+ */
+typedef struct {
+	int32_t method;      /* 0 Pearson, 1 Spearman, 2 Kendall */
+	int32_t alternative; /* AnofoxAlternative */
+	int32_t tau_type;    /* AnofoxKendallType; read for every method */
+	double confidence_level; /* in (0, 1); NaN: no interval */
+} AnofoxHipCorBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_cor_record_len(void); /* 8 */
+ANOFOX_HIP_API bool anofox_hip_cor_batch_device(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *d_row_offsets,
+                                 const double *d_x, const double *d_y, AnofoxHipCorBatchOptions options, double *d_records,
+                                 AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_cor_batch_host(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *row_offsets,
+                               const double *x, const double *y, AnofoxHipCorBatchOptions options, double *records,
+                               AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_hip_cor_test_hooks(int64_t small_cap);
 
 /*
  * Grouped Gaussian linear mixed models with one random intercept (glmm_fit_agg): per panel  y_ij = a_ij'beta + b_j + e_ij,
