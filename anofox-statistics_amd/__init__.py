@@ -48,6 +48,9 @@ from .eb_shrink import (EbShrinkOptions, ShrunkCoefficients, eb_shrink, eb_shrin
                         eb_shrink_test_hooks, parse_eb_shrink_options, shrink_coefficients)
 from .correlation import (CorrelationAggResult, CorrelationOptions, cor_batch_device, cor_batch_host, cor_test_hooks, kendall,  # noqa: E402
                           kendall_agg, parse_correlation_options, pearson, pearson_agg, spearman, spearman_agg)
+from .rank_tests import (RankTestAggResult, RankTestOptions, kruskal_wallis, kruskal_wallis_agg, mann_whitney_u, mann_whitney_u_agg,  # noqa: E402
+                         parse_rank_test_options, rank_test_batch_device, rank_test_batch_host, rank_test_hooks, wilcoxon_signed_rank,
+                         wilcoxon_signed_rank_agg)
 from .glmm import (GlmmFitAggResult, GlmmFitPredictAggResult, GlmmOptions, glmm_fit, glmm_fit_agg, glmm_fit_batch_device,  # noqa: E402
                    glmm_fit_batch_host, glmm_fit_predict_agg, glmm_fit_predict_batch_device, glmm_fit_predict_batch_host, glmm_test_hooks,
                    parse_glmm_options)
@@ -75,6 +78,12 @@ SQL_FUNCTIONS.update({
     "anofox_stats_pearson": pearson, "pearson": pearson, "anofox_stats_pearson_agg": pearson_agg, "pearson_agg": pearson_agg,
     "anofox_stats_spearman": spearman, "spearman": spearman, "anofox_stats_spearman_agg": spearman_agg, "spearman_agg": spearman_agg,
     "anofox_stats_kendall": kendall, "kendall": kendall, "anofox_stats_kendall_agg": kendall_agg, "kendall_agg": kendall_agg,
+    "anofox_stats_mann_whitney_u": mann_whitney_u, "mann_whitney_u": mann_whitney_u,
+    "anofox_stats_mann_whitney_u_agg": mann_whitney_u_agg, "mann_whitney_u_agg": mann_whitney_u_agg,
+    "anofox_stats_wilcoxon_signed_rank": wilcoxon_signed_rank, "wilcoxon_signed_rank": wilcoxon_signed_rank,
+    "anofox_stats_wilcoxon_signed_rank_agg": wilcoxon_signed_rank_agg, "wilcoxon_signed_rank_agg": wilcoxon_signed_rank_agg,
+    "anofox_stats_kruskal_wallis": kruskal_wallis, "kruskal_wallis": kruskal_wallis,
+    "anofox_stats_kruskal_wallis_agg": kruskal_wallis_agg, "kruskal_wallis_agg": kruskal_wallis_agg,
     "anofox_stats_glmm_fit": glmm_fit, "glmm_fit": glmm_fit, "anofox_stats_glmm_fit_agg": glmm_fit_agg, "glmm_fit_agg": glmm_fit_agg,
     "anofox_stats_glmm_fit_predict_agg": glmm_fit_predict_agg, "glmm_fit_predict_agg": glmm_fit_predict_agg,
     "anofox_stats_predict": predict,
@@ -122,6 +131,9 @@ __all__ = [
     "eb_shrink_batch_device", "eb_shrink_test_hooks", "shrink_coefficients",
     "CorrelationOptions", "CorrelationAggResult", "parse_correlation_options", "pearson", "spearman", "kendall", "pearson_agg",
     "spearman_agg", "kendall_agg", "cor_batch_host", "cor_batch_device", "cor_test_hooks",
+    "RankTestOptions", "RankTestAggResult", "parse_rank_test_options", "mann_whitney_u", "wilcoxon_signed_rank", "kruskal_wallis",
+    "mann_whitney_u_agg", "wilcoxon_signed_rank_agg", "kruskal_wallis_agg", "rank_test_batch_host", "rank_test_batch_device",
+    "rank_test_hooks",
     "GlmmOptions", "GlmmFitAggResult", "parse_glmm_options", "glmm_fit", "glmm_fit_agg", "glmm_fit_batch_host", "glmm_fit_batch_device", "glmm_test_hooks",
     "GlmmFitPredictAggResult", "glmm_fit_predict_agg", "glmm_fit_predict_batch_host", "glmm_fit_predict_batch_device",
 ]

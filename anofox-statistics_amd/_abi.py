@@ -248,6 +248,25 @@ class AnofoxHipCorBatchOptions(C.Structure):  # the correlation batch entries' o
     _fields_ = [("method", C.c_int32), ("alternative", C.c_int32), ("tau_type", C.c_int32), ("confidence_level", C.c_double)]
 
 
+class AnofoxTestResult(C.Structure):  # anofox_stats_ffi.h:1555-1583, 96 bytes
+    _fields_ = [("statistic", C.c_double), ("p_value", C.c_double), ("df", C.c_double), ("effect_size", C.c_double), ("ci_lower", C.c_double),
+                ("ci_upper", C.c_double), ("confidence_level", C.c_double), ("n", C.c_size_t), ("n1", C.c_size_t), ("n2", C.c_size_t),
+                ("alternative", C.c_int), ("method", C.c_char_p)]
+
+
+class AnofoxMannWhitneyOptions(C.Structure):  # anofox_stats_ffi.h:1696-1707, 24 bytes; exact = true is refused
+    _fields_ = [("alternative", C.c_int), ("exact", C.c_bool), ("continuity_correction", C.c_bool), ("confidence_level", C.c_double),
+                ("mu", C.c_double)]
+
+
+class AnofoxWilcoxonOptions(C.Structure):  # anofox_stats_ffi.h:1920-1931, the same 24 bytes
+    _fields_ = AnofoxMannWhitneyOptions._fields_
+
+
+class AnofoxHipRankTestBatchOptions(C.Structure):  # the rank test batch entries' options, 24 bytes
+    _fields_ = [("test", C.c_int32), ("alternative", C.c_int32), ("continuity_correction", C.c_int32), ("mu", C.c_double)]
+
+
 class AnofoxHipGlmmOptions(C.Structure):  # the batch entries' options (anofox_stats_hip.h), 40 bytes
     _fields_ = [("family", C.c_int), ("fit_intercept", C.c_int), ("reml", C.c_int), ("max_iterations", C.c_uint32),
                 ("tolerance", C.c_double), ("compute_inference", C.c_int), ("confidence_level", C.c_double)]
@@ -606,6 +625,16 @@ SYMBOLS = {
     "anofox_spearman_cor": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxCorrelationOptions, C.POINTER(AnofoxCorrelationResult), _ERRP]),
     "anofox_kendall_cor": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxKendallOptions, C.POINTER(AnofoxCorrelationResult), _ERRP]),
     "anofox_free_correlation_result": (None, [C.POINTER(AnofoxCorrelationResult)]),
+    "anofox_hip_rank_test_record_len": (C.c_size_t, []),
+    "anofox_hip_rank_test_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     AnofoxHipRankTestBatchOptions, C.c_void_p, _ERRP]),
+    "anofox_hip_rank_test_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(C.c_int32),
+                                                   AnofoxHipRankTestBatchOptions, _DP, _ERRP]),
+    "anofox_hip_rank_test_hooks": (None, [C.c_int64]),
+    "anofox_mann_whitney_u": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxMannWhitneyOptions, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_wilcoxon_signed_rank": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxWilcoxonOptions, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_kruskal_wallis": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_free_test_result": (None, [C.POINTER(AnofoxTestResult)]),
     "anofox_hip_glmm_record_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_inference_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_test_hooks": (None, [C.c_int, C.c_int]),

@@ -381,6 +381,16 @@ class Context:
         from .correlation import cor_batch_host
         return cor_batch_host(row_offsets, x, y, method, options, ctx=self)
 
+    def rank_test_batch_device(self, row_offsets, v, y, sample, test: int, options=None, use_current_torch_stream: bool = True):
+        """Grouped Mann-Whitney (0), Wilcoxon signed-rank (1) or Kruskal-Wallis (2) tests on CUDA tensors
+        (rank_tests.rank_test_batch_device): records[n_groups, 8]."""
+        from .rank_tests import rank_test_batch_device
+        return rank_test_batch_device(self, row_offsets, v, y, sample, test, options, use_current_torch_stream)
+
+    def rank_test_batch_host(self, row_offsets, v, y, sample, test: int, options=None):
+        from .rank_tests import rank_test_batch_host
+        return rank_test_batch_host(row_offsets, v, y, sample, test, options, ctx=self)
+
     def glmm_fit_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False,
                               use_current_torch_stream: bool = True):
         """Grouped Gaussian random-intercept mixed models on CUDA tensors (glmm.glmm_fit_batch_device): (records, inference or None,

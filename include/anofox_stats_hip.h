@@ -592,6 +592,60 @@ ANOFOX_HIP_API bool anofox_kendall_cor(AnofoxDataArray x, AnofoxDataArray y, Ano
                         AnofoxCorrelationResult *out_result, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_correlation_result(AnofoxCorrelationResult *result);
 
+/* replaces AnofoxTestResult, anofox_stats_ffi.h:1555-1583 — 96 bytes: seven doubles @0..48, n @56, n1 @64, n2 @72, alternative @80,
+ * method @88 (malloc'ed by the callee, released by anofox_free_test_result) */
+typedef struct {
+	double statistic; /* W, V or H */
+	double p_value;
+	double df;          /* Kruskal-Wallis: k - 1; NaN otherwise */
+	double effect_size; /* NaN, as in the reference */
+	double ci_lower;    /* NaN: the Hodges-Lehmann interval is not built */
+	double ci_upper;
+	double confidence_level; /* the option, echoed (0.95 where it is not > 0); Kruskal-Wallis: NaN */
+	size_t n;
+	size_t n1;
+	size_t n2;
+	AnofoxAlternative alternative;
+	char *method; /* "Mann-Whitney U test", "Wilcoxon signed-rank test", "Kruskal-Wallis H test" */
+} AnofoxTestResult;
+
+/* replaces AnofoxMannWhitneyOptions, anofox_stats_ffi.h:1696-1707 — 24 bytes: alternative @0, exact @4, continuity_correction @5,
+ * confidence_level @8, mu @16 (NaN: 0) */
+typedef struct {
+	AnofoxAlternative alternative;
+	bool exact; /* true fails: exact p-values are not built */
+	bool continuity_correction;
+	double confidence_level;
+	double mu;
+} AnofoxMannWhitneyOptions;
+
+/* replaces AnofoxWilcoxonOptions, anofox_stats_ffi.h:1920-1931 — the same 24 bytes */
+typedef struct {
+	AnofoxAlternative alternative;
+	bool exact;
+	bool continuity_correction;
+	double confidence_level;
+	double mu;
+} AnofoxWilcoxonOptions;
+
+/* replace anofox_mann_whitney_u / anofox_kruskal_wallis / anofox_wilcoxon_signed_rank / anofox_free_test_result,
+ * anofox_stats_ffi.h:1845, 1863, 1936 and 2188: one group through anofox_hip_rank_test_batch_host (below), NULL entries of the
+ * validity bitmaps as NaN.  Kruskal-Wallis takes the group ids as doubles and, as the reference does, pairs values and ids up to
+ * the shorter array, drops a pair with a NaN in either and keys the groups by the id cast to an integer (towards zero).
+ * n / n1 / n2 follow the reference: Mann-Whitney n1 + n2, n1, n2; Wilcoxon the valid pairs three times; Kruskal-Wallis N, 0, 0.
+ * False with ANOFOX_ERROR_INVALID_INPUT, the result zeroed and nothing to free, before any device is touched: out_result NULL,
+ * exact = true ("<method>: exact p-values are not built"), an unknown alternative or a mu that is infinite ("rank test: ..."),
+ * "Mann-Whitney U test requires at least 1 observation per group", "Wilcoxon signed-rank test requires equal length samples",
+ * "Wilcoxon signed-rank test requires at least 2 valid pairs", "Kruskal-Wallis test requires at least 2 groups" and "... at least 3
+ * observations" (the aggregate's rule). */
+ANOFOX_HIP_API bool anofox_mann_whitney_u(AnofoxDataArray group1, AnofoxDataArray group2, AnofoxMannWhitneyOptions options,
+                           AnofoxTestResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_wilcoxon_signed_rank(AnofoxDataArray x, AnofoxDataArray y, AnofoxWilcoxonOptions options,
+                                 AnofoxTestResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_kruskal_wallis(AnofoxDataArray values, AnofoxDataArray groups, AnofoxTestResult *out_result,
+                           AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_test_result(AnofoxTestResult *result);
+
 /* replaces AnofoxGlmmFamily, anofox_stats_ffi.h:2433-2440 */
 typedef enum {
 	ANOFOX_GLMM_GAUSSIAN = 0,
@@ -1495,6 +1549,44 @@ ANOFOX_HIP_API bool anofox_hip_cor_batch_host(AnofoxHipContext *ctx, int64_t n_g
                                const double *x, const double *y, AnofoxHipCorBatchOptions options, double *records,
                                AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_hip_cor_test_hooks(int64_t small_cap);
+
+/*
+ * Grouped rank-based location tests (mann_whitney_u_agg, wilcoxon_signed_rank_agg, kruskal_wallis_agg and the three scalars
+ * above): R's wilcox.test(exact = FALSE) and kruskal.test in closed form.  The formulas: DESIGN.md §1 "Rank-based location tests"
+ * and csrc/rank_tests.h.
+ * Input: row_offsets[n_groups + 1], group g owns rows [off[g], off[g + 1]) of v (n_rows doubles), of y (doubles; Wilcoxon only,
+ * otherwise it may be NULL) and of sample (int32; Mann-Whitney and Kruskal-Wallis only, otherwise it may be NULL).  A row is valid
+ * when v is not NaN, for Wilcoxon when v - y - mu is not NaN (infinities stay in).  Mann-Whitney's first sample is sample == 0, its
+ * second every other id; Kruskal-Wallis' ids are any int32.
+ * Output: records[g * 8] = {statistic (W, V or H), z, p_value, df, n, n1, n2, status}: Mann-Whitney df NaN; Wilcoxon df NaN, n the
+ * valid pairs, n1 the non-zero differences, n2 the zeros dropped; Kruskal-Wallis df = k - 1, n1 = k, n2 and z NaN.
+ * Status per group: 0; ANOFOX_ERROR_INSUFFICIENT_DATA 6 (an empty sample; fewer than 2 valid pairs; N < 3 or k < 2), which makes
+ * every field but the counts NaN.  A group without spread (every value tied, no non-zero difference) has status 0 with z (H) and
+ * p_value NaN.  W, V and the counts are exact and the same on both size paths.
+ * Groups of up to 1462 rows are worked in LDS by one wavefront each; larger ones in the context's workspace (28 bytes per row of
+ * the call) by a workgroup of 1024 threads.
+ * Argument errors (false before any device is touched): negative counts, an unknown test or alternative, a mu that is not finite,
+ * a mu != 0 for Kruskal-Wallis, a NULL array where there are groups, a missing y (Wilcoxon) or sample (the others) (all "rank
+ * test: ..."), and for the host form offsets that are not non-decreasing within [0, n_rows].  The device form is asynchronous on
+ * the context's stream.
+ * anofox_hip_rank_test_hooks (for tests): small_cap lowers the rows a group may have on the small path for later calls of the
+ * process; 0 restores 1462.
+ */
+typedef struct {
+	int32_t test;        /* 0 Mann-Whitney, 1 Wilcoxon signed-rank, 2 Kruskal-Wallis */
+	int32_t alternative; /* AnofoxAlternative; not read by Kruskal-Wallis */
+	int32_t continuity_correction; /* 0: none */
+	double mu;           /* the hypothesised shift; 0 for Kruskal-Wallis */
+} AnofoxHipRankTestBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_rank_test_record_len(void); /* 8 */
+ANOFOX_HIP_API bool anofox_hip_rank_test_batch_device(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *d_row_offsets,
+                                       const double *d_v, const double *d_y, const int32_t *d_sample,
+                                       AnofoxHipRankTestBatchOptions options, double *d_records, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_rank_test_batch_host(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *row_offsets,
+                                     const double *v, const double *y, const int32_t *sample,
+                                     AnofoxHipRankTestBatchOptions options, double *records, AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_hip_rank_test_hooks(int64_t small_cap);
 
 /*
  * Grouped Gaussian linear mixed models with one random intercept (glmm_fit_agg): per panel  y_ij = a_ij'beta + b_j + e_ij,
