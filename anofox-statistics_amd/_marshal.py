@@ -6,7 +6,9 @@
 - the table of column pointers, always max(p, 1) long;
 - outputs: allocated, or a caller's tensor checked like an input (at least the required element count);
 - the stream of a device call, the handle of an optional context, and the one-shot accumulate gate of the entries that consume it;
-- the call: arrays and tensors go in as they are, `_abi.SYMBOLS` says what each becomes, a false return raises AnofoxStatsError.
+- the call: arrays and tensors go in as they are, `_abi.SYMBOLS` says what each becomes, a false return raises AnofoxStatsError;
+- the scalar entries of the reference's layout (data arrays in, a result struct out, its text freed);
+- the rows of a GROUP BY as the batch entries take them: sorted by key, with their offsets.
 
 Every check raises ValueError before the library is reached.  runtime.py and glm.py state the contract of each entry on top of
 this: which inputs, which output shapes, which symbol, what it returns."""
@@ -19,6 +21,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import AnofoxStatsError
+from .options import InvalidInputException
 
 _DP = C.POINTER(C.c_double)
 F64, I64, I32, U32, U8 = "float64", "int64", "int32", "uint32", "uint8"
@@ -89,17 +92,52 @@ def device_tensor(t, dtype, n=None, what="tensor", device=None, at_least=False):
     return t
 
 
+def scalar_call(symbol, arrays, options, result, free, fields) -> dict:
+    """lib.<symbol>(*arrays as AnofoxDataArray (a None entry is a NULL)[, options], &result) -> {name: result.<field>} for the
+    (name, field) pairs of `fields`, a text decoded; the result is released through lib.<free>.  A failure raises
+    InvalidInputException with the library's text and its code in `.code`."""
+    from .scalar import _data_array
+    lib = _abi.load()
+    data = [_data_array(a) for a in arrays]   # (array, what keeps its memory alive)
+    res = result()
+    try:
+        call(lib, symbol, *[d[0] for d in data], *(() if options is None else (options,)), C.byref(res))
+    except AnofoxStatsError as failed:
+        e = InvalidInputException(f"{symbol.replace('anofox_', '')} failed: {failed}")
+        e.code = failed.code
+        raise e from None
+    try:
+        values = [(name, getattr(res, field)) for name, field in fields]
+        return {name: v.decode() if isinstance(v, bytes) else v for name, v in values}
+    finally:
+        getattr(lib, free)(C.byref(res))
+
+
+def column(values) -> np.ndarray:
+    """A column of an aggregate as float64; a None (SQL NULL) becomes NaN."""
+    a = np.asarray(values)
+    return np.array([np.nan if v is None else v for v in values], dtype=np.float64) if a.dtype == object else np.asarray(a, np.float64)
+
+
+def group_rows(keys):
+    """The rows of a GROUP BY -> (the sorted unique keys, the permutation that sorts the rows by key and keeps the order of a
+    key's rows, row_offsets[n_keys + 1] into the permuted rows)."""
+    uniq, inv = np.unique(np.asarray(keys), return_inverse=True)
+    perm = np.argsort(inv, kind="stable")
+    return uniq, perm, np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=len(uniq)))]).astype(np.int64)
+
+
 class _Batch:
     """The checked inputs of one call: G groups, p columns, N rows, `off` (row_offsets), `y` and `cols` (the pointer table).
-    row_offsets / y None: the entry has none (N is then the length of column 0)."""
+    row_offsets / y None: the entry has none (N is then the length of column 0).  `lead`: what an error calls `y`."""
     suffix = ""
 
-    def __init__(self, row_offsets, y, x_cols):
+    def __init__(self, row_offsets, y, x_cols, lead="y"):
         self.off = None if row_offsets is None else self.array(row_offsets, I64, None, "row_offsets")
         self.G = None if self.off is None else self._size(self.off) - 1
         if self.G is not None and self.G < 0:
             raise ValueError("row_offsets needs one entry more than there are groups")
-        self.y = None if y is None else self.array(y, F64, None, "y")
+        self.y = None if y is None else self.array(y, F64, None, lead)
         lead = self.y if y is not None else self.array(x_cols[0], F64, None, "column 0") if len(x_cols) else None
         self.N = 0 if lead is None else self._size(lead)
         self._cols = [self.array(c, F64, self.N, f"column {j}") for j, c in enumerate(x_cols)]
@@ -132,9 +170,9 @@ class HostBatch(_Batch):
     """numpy in, numpy out, on an optional Context."""
     suffix = "_host"
 
-    def __init__(self, ctx, row_offsets, y, x_cols):
+    def __init__(self, ctx, row_offsets, y, x_cols, lead="y"):
         self.lib, self.h = _abi.load(), handle(ctx)
-        super().__init__(row_offsets, y, x_cols)
+        super().__init__(row_offsets, y, x_cols, lead)
 
     array = staticmethod(host_array)
 
@@ -158,9 +196,9 @@ class DeviceBatch(_Batch):
     itself unless it is an AggState).  use_current_torch_stream: the call is enqueued on torch's current stream."""
     suffix = "_device"
 
-    def __init__(self, ctx, row_offsets, y, x_cols, use_current_torch_stream, owner=None):
+    def __init__(self, ctx, row_offsets, y, x_cols, use_current_torch_stream, owner=None, lead="y"):
         self.ctx, self.owner, self.stream, self.device = ctx, ctx if owner is None else owner, use_current_torch_stream, None
-        super().__init__(row_offsets, y, x_cols)
+        super().__init__(row_offsets, y, x_cols, lead)
 
     def array(self, t, dtype, n=None, what="tensor", at_least=False):
         device_tensor(t, dtype, n, what, self.device, at_least)

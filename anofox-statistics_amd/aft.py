@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import AnofoxStatsError
-from ._marshal import DeviceBatch, HostBatch, call
+from ._marshal import DeviceBatch, HostBatch, call, column, group_rows
 from .options import InvalidInputException, _extract_bool, _extract_double, _extract_uint32
 
 # the names a distribution goes by (the reference's AftDistribution::from_name), case-insensitive
@@ -220,23 +220,16 @@ class AftFitPredictAggResult(AftFitAggResult):
         return self.pred[:, 3]
 
 
-def _column(values):
-    a = np.asarray(values)
-    return np.array([np.nan if v is None else v for v in values], dtype=np.float64) if a.dtype == object else np.asarray(a, np.float64)
-
-
 def _grouped(group_keys, time, x, event):
     """The rows sorted by key (stably): -> (sorted keys, the permutation, offsets[G + 1], time, columns, event)."""
     keys = np.asarray(group_keys)
-    tv, ev = _column(time), _column(event)
+    tv, ev = column(time), column(event)
     X = np.asarray(x, dtype=np.float64)
     if X.ndim == 1:
         X = X[:, None]
     if len(keys) != len(tv) or X.shape[0] != len(tv) or len(ev) != len(tv):
         raise InvalidInputException("group keys, time, x and event must have the same number of rows")
-    uniq, inv = np.unique(keys, return_inverse=True)
-    perm = np.argsort(inv, kind="stable")
-    offsets = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=len(uniq)))]).astype(np.int64)
+    uniq, perm, offsets = group_rows(keys)
     cols = [np.ascontiguousarray(X[perm, j]) for j in range(X.shape[1])]
     return uniq, perm, offsets, tv[perm], cols, ev[perm]
 

@@ -4,20 +4,17 @@ the numpy / tensor drivers of anofox_hip_cor_batch_{host,device}.  The contract:
 correlation".  A group whose status is not 0 (fewer than 3 valid pairs) is None (SQL NULL) in the aggregates."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Mapping, Optional
 
 import numpy as np
 
 from . import _abi
-from ._abi import AnofoxStatsError
-from ._marshal import F64, I64, call, device_tensor, handle, host_array, _invoke
-from .options import InvalidInputException, _extract_double
+from ._marshal import F64, DeviceBatch, HostBatch, column, group_rows, scalar_call
+from .options import InvalidInputException, _extract_alternative, _extract_double
 
 PEARSON, SPEARMAN, KENDALL = 0, 1, 2
 RECORD_NAMES = ("estimate", "statistic", "p_value", "ci_lower", "ci_upper", "n", "s", "status")
-ALTERNATIVE = {"two_sided": 0, "two-sided": 0, "two.sided": 0, "twosided": 0, "less": 1, "greater": 2}
 TAU_TYPE = {"a": 0, "tau_a": 0, "taua": 0, "b": 1, "tau_b": 1, "taub": 1, "c": 2, "tau_c": 2, "tauc": 2}
 METHOD_TEXT = {PEARSON: "Pearson correlation", SPEARMAN: "Spearman rank correlation"}
 TAU_TEXT = ("Kendall's TauA", "Kendall's TauB", "Kendall's TauC")
@@ -61,10 +58,7 @@ def parse_correlation_options(opts) -> CorrelationOptions:
     for raw_key, val in opts.items():
         key = str(raw_key).lower()
         if key == "alternative" and val is not None:
-            name = str(val).lower()
-            if name not in ALTERNATIVE:
-                raise InvalidInputException("Unknown alternative '%s'. Expected 'two_sided', 'less' or 'greater'." % (val,))
-            out.alternative = ALTERNATIVE[name]
+            out.alternative = _extract_alternative(val)
         elif key == "confidence_level":
             out.confidence_level = _extract_double(val)
         elif key in ("tau_type", "variant") and val is not None:
@@ -75,37 +69,22 @@ def parse_correlation_options(opts) -> CorrelationOptions:
     return out
 
 
+def _cor_batch(b, y, method, options):
+    """records[G, 8] of the batch b, whose leading column is x."""
+    rec = b.out((b.G, 8))
+    b.call("anofox_hip_cor_batch", b.G, b.N, b.off, b.y, b.array(y, F64, b.N, "y"), parse_correlation_options(options).batch_options(method), rec)
+    return rec
+
+
 def cor_batch_host(row_offsets, x, y, method: int, options=None, ctx=None) -> np.ndarray:
     """numpy in / out: group g owns rows [row_offsets[g], row_offsets[g + 1]) of x and y.  Returns records[n_groups, 8] =
     RECORD_NAMES; anofox_hip_cor_batch_host's layout."""
-    off = host_array(row_offsets, I64, None, "row_offsets")
-    if off.size < 1:
-        raise ValueError("row_offsets needs one entry more than there are groups")
-    xv = host_array(x, F64, None, "x")
-    yv = host_array(y, F64, xv.size, "y")
-    rec = np.empty((off.size - 1, 8))
-    call(_abi.load(), "anofox_hip_cor_batch_host", handle(ctx), off.size - 1, xv.size, off, xv, yv,
-         parse_correlation_options(options).batch_options(method), rec)
-    return rec
+    return _cor_batch(HostBatch(ctx, row_offsets, x, [], lead="x"), y, method, options)
 
 
 def cor_batch_device(ctx, row_offsets, x, y, method: int, options=None, use_current_torch_stream: bool = True):
     """cor_batch_host on CUDA tensors (row_offsets int64, x / y float64).  Asynchronous.  Returns the records tensor."""
-    import torch
-
-    off = device_tensor(row_offsets, I64, None, "row_offsets")
-    if off.numel() < 1:
-        raise ValueError("row_offsets needs one entry more than there are groups")
-    xv = device_tensor(x, F64, None, "x", off.device)
-    yv = device_tensor(y, F64, xv.numel(), "y", off.device)
-    rec = torch.empty((off.numel() - 1, 8), dtype=torch.float64, device=off.device)
-    if use_current_torch_stream:
-        ctx.set_stream(torch.cuda.current_stream(off.device).cuda_stream)
-    ok, err = _invoke(ctx._lib, "anofox_hip_cor_batch_device", (ctx._h, off.numel() - 1, xv.numel(), off, xv, yv,
-                                                                parse_correlation_options(options).batch_options(method), rec))
-    if not ok:
-        raise AnofoxStatsError(err.code, err.text())
-    return rec
+    return _cor_batch(DeviceBatch(ctx, row_offsets, x, [], use_current_torch_stream, lead="x"), y, method, options)
 
 
 def cor_test_hooks(small_cap: int = 0):
@@ -133,19 +112,12 @@ class CorrelationAggResult:
         return {k: self.row(g) for g, k in enumerate(self.keys.tolist())}
 
 
-def _column(values):
-    a = np.asarray(values)
-    return np.array([np.nan if v is None else v for v in values], dtype=np.float64) if a.dtype == object else np.asarray(a, np.float64)
-
-
 def _agg(method, keys, x, y, options, context) -> CorrelationAggResult:
     o = parse_correlation_options(options)
-    xv, yv, keys = _column(x), _column(y), np.asarray(keys)
+    xv, yv = column(x), column(y)
     if not (len(xv) == len(yv) == len(keys)):
         raise InvalidInputException("the keys, x and y must have the same number of rows")
-    uniq, inv = np.unique(keys, return_inverse=True)
-    perm = np.argsort(inv, kind="stable")
-    off = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=len(uniq)))]).astype(np.int64)
+    uniq, perm, off = group_rows(keys)
     rec = cor_batch_host(off, xv[perm], yv[perm], method, o, ctx=context)
     return CorrelationAggResult(uniq, rec, method, o.method_text(method))
 
@@ -166,22 +138,8 @@ def kendall_agg(keys, x, y, options=None, context=None) -> CorrelationAggResult:
 
 
 def _scalar(symbol, x, y, ffi_options, estimate) -> dict:
-    from .scalar import _data_array
-    lib = _abi.load()
-    xa, k0 = _data_array(x)
-    ya, k1 = _data_array(y)
-    res = _abi.AnofoxCorrelationResult()
-    try:
-        call(lib, symbol, xa, ya, ffi_options, C.byref(res))
-    except AnofoxStatsError as failed:
-        e = InvalidInputException(f"{symbol.replace('anofox_', '')} failed: {failed}")
-        e.code = failed.code
-        raise e from None
-    try:
-        return {estimate: res.r, "statistic": res.statistic, "p_value": res.p_value, "ci_lower": res.ci_lower, "ci_upper": res.ci_upper,
-                "n": res.n, "method": res.method.decode() if res.method else None}
-    finally:
-        lib.anofox_free_correlation_result(C.byref(res))
+    fields = [(estimate, "r")] + [(f, f) for f in ("statistic", "p_value", "ci_lower", "ci_upper", "n", "method")]
+    return scalar_call(symbol, (x, y), ffi_options, _abi.AnofoxCorrelationResult, "anofox_free_correlation_result", fields)
 
 
 def pearson(x, y, options=None) -> dict:

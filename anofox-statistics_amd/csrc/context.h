@@ -3,6 +3,7 @@
 #pragma once
 #include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <mutex>
@@ -238,6 +239,13 @@ inline void expand_data_array(const AnofoxDataArray &a, std::vector<double> &out
 		const bool valid = !a.validity || ((a.validity[i / 8] >> (i % 8)) & 1);
 		out[i] = valid ? a.data[i] : NAN;
 	}
+}
+
+// a malloc'd copy of a result's text (the reference's results own theirs; anofox_free_* frees it); nullptr: no memory
+inline char *copy_text(const char *s) {
+	char *p = (char *)malloc(strlen(s) + 1);
+	if (p) strcpy(p, s);
+	return p;
 }
 
 inline hipEvent_t get_event(AnofoxHipContext *ctx) {

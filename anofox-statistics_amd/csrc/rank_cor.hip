@@ -1,22 +1,16 @@
-// rank_cor.hip — grouped Pearson, Spearman and Kendall correlation with their tests (rank_cor.h): the kernels of both size paths
-// and the entry points anofox_hip_cor_batch_{device,host}, anofox_hip_cor_record_len, anofox_hip_cor_test_hooks,
-// anofox_pearson_cor / anofox_spearman_cor / anofox_kendall_cor / anofox_free_correlation_result.
+// rank_cor.hip — grouped Pearson, Spearman and Kendall correlation with their tests (rank_cor.h): the family that runs on the
+// size-tiered launch driver of rank_launch.h, Kendall's pair kernels, and the entry points anofox_hip_cor_batch_{device,host},
+// anofox_hip_cor_record_len, anofox_hip_cor_test_hooks, anofox_pearson_cor / anofox_spearman_cor / anofox_kendall_cor /
+// anofox_free_correlation_result.
 //
 // The contract and the method: rank_cor.h and DESIGN.md §1, "Rank and product-moment correlation".
-//   cor_small_kernel<CAP>: one wavefront per workgroup and group, grid-stride over the groups, the group's work arrays in LDS.  Two
-//     instances share the groups by their row count: up to kCorTierRows rows (7 KiB of LDS, so a CU holds as many wavefronts as
-//     its other limits admit) and up to kCorSmallCap.  A kernel passes over the groups of the other tier.  Pearson stages nothing
-//     and runs every group, whatever its size, on the first instance: it streams the rows twice from memory.
-//   cor_large_kernel: a workgroup of 1024 threads per group above the cap, its work arrays in the context's workspace.  All
-//     sixteen wavefronts sort; the first runs the other phases with the small path's code, so a group's midranks and their sums
-//     come out bit for bit as on the small path.  A Kendall group is entered into a list instead of being counted.
+//   rank_small_kernel<CAP, CorFamily>, rank_large_kernel<CorFamily>: the two size paths (rank_launch.h).  Pearson stages nothing
+//     and runs every group, whatever its size, on the first small instance: it streams the rows twice from memory.  On the large
+//     path a Kendall group is entered into a list instead of being counted.
 //   cor_pairs_kernel: the listed groups' pairs by (i block, j block) tiles of 256 x 256 rows, the j block in LDS, grid-stride over
 //     the tiles; a wavefront adds its count into the group's int64 with one atomic add (a vector atomic; integer, so exact and
 //     independent of the order).  cor_finish_kernel: a thread per listed group writes the record.
-//   Neither form of the entry reads the offsets on the host to size a launch; the large path is launched whenever the call has
-//     more rows than the cap, and then takes kCorRowBytes of workspace per row of the call.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
@@ -25,7 +19,7 @@
 #include <vector>
 
 #include "common.h"
-#include "rank_cor.h"
+#include "rank_launch.h"
 #include "host_math.h"
 
 using namespace anofox;
@@ -34,90 +28,66 @@ using namespace anofox;
 
 using namespace anofox::host;
 using namespace anofox::cor;
+using namespace anofox::rank;
 
 namespace {
 
-// The rows of a group that the small path holds.  A workgroup of cor_small_kernel is one wavefront, and a CU has four SIMDs: with
-// 160 KiB of LDS per CU (a single workgroup may take all of it), 160 / 4 = 40 KiB per workgroup keeps one wavefront on every
-// SIMD.  40960 bytes / kCorRowBytes (28) = 1462 rows.  A larger cap would idle SIMDs; a smaller one sends groups to the large
-// path, which costs three launches and global-memory sorts.
-constexpr int kCorSmallCap = 40960 / kCorRowBytes;
-static_assert(kCorSmallCap == 1462, "the cap's derivation");
-constexpr int kCorTierRows = 256; // the first instance's groups: 256 x 28 = 7 KiB
-constexpr int64_t kCorMaxWorkgroups = 1 << 16;
-constexpr int kCorLargeThreads = 1024;
-constexpr int kCorLargeWorkgroups = 1024;
 constexpr int kCorPairWorkgroups = 2048; // 256 CUs x 8 workgroups of 256 threads
 
 std::atomic<int64_t> g_small_cap{0}; // anofox_hip_cor_test_hooks
 
-struct CorArgs {
+struct CorFamily {
+	static constexpr const char *kSmallKernel = "rank_small_kernel<CorFamily>", *kLargeKernel = "rank_large_kernel<CorFamily>",
+	                            *kScratch = "correlation scratch";
 	CorProblem P;
-	const int64_t *off;
-	int64_t n_groups;
-	int64_t above, upto; // the kernel's groups: above < rows <= upto
-	// the large path
-	CorWork W; // each n_rows long; a group's part starts at its first row
+	// the large path's Kendall groups: a counter (256 bytes to itself) and the list it fills
 	CorLarge *list;
 	unsigned long long *count;
 	int64_t slots;
-};
 
-__device__ __forceinline__ void group_rows(const CorArgs &a, int64_t g, int64_t &lo, int64_t &hi) {
-	lo = a.off[g] < 0 ? 0 : a.off[g];
-	hi = a.off[g + 1] > a.P.n_rows ? a.P.n_rows : a.off[g + 1];
-	if (hi < lo) hi = lo;
-	if (lo > a.P.n_rows) lo = hi = a.P.n_rows;
-}
+	__host__ __device__ bool staged() const { return P.method != kCorPearson; }
 
-template <int CAP>
-__global__ __launch_bounds__(64) void cor_small_kernel(CorArgs a) {
-	__shared__ double sx[CAP], sy[CAP], sk[CAP];
-	__shared__ int32_t si[CAP];
-	const CorWork W = {sx, sy, sk, si};
-	for (int64_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
-		int64_t lo, hi;
-		group_rows(a, g, lo, hi);
-		const int64_t m = hi - lo;
-		if (m <= a.above || m > a.upto) continue;
-		if (a.P.method != kCorPearson && m > CAP) continue; // (never: upto <= CAP for the staged methods)
-		rc_group(a.P, g, lo, hi, W, true, threadIdx.x, 64, nullptr);
-		__syncthreads(); // the next group's rows overwrite these
+	__device__ __forceinline__ void small_group(int64_t g, int64_t lo, int64_t hi, const CorWork &W) const {
+		rc_group(P, g, lo, hi, W, true, threadIdx.x, 64, nullptr);
 	}
-}
 
-__global__ __launch_bounds__(kCorLargeThreads) void cor_large_kernel(CorArgs a) {
-	__shared__ long long s_slot;
-	for (int64_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
-		int64_t lo, hi;
-		group_rows(a, g, lo, hi);
-		if (hi - lo <= a.above) continue;
-		const CorWork W = {a.W.x + lo, a.W.y + lo, a.W.key + lo, a.W.idx + lo};
+	__device__ __forceinline__ void large_group(int64_t g, int64_t lo, int64_t hi, const CorWork &W) const {
+		__shared__ long long s_slot;
 		CorLarge *large = nullptr;
-		if (a.P.method == kCorKendall) {
+		if (P.method == kCorKendall) {
 			if (threadIdx.x == 0) {
-				const unsigned long long k = atomicAdd(a.count, 1ull);
-				s_slot = k < (unsigned long long)a.slots ? (long long)k : -1; // (a full list: the wavefront counts the pairs itself)
+				const unsigned long long k = atomicAdd(count, 1ull);
+				s_slot = k < (unsigned long long)slots ? (long long)k : -1; // (a full list: the wavefront counts the pairs itself)
 				if (s_slot >= 0) {
-					a.list[s_slot].group = g;
-					a.list[s_slot].n = 0; // until the group is entered
+					list[s_slot].group = g;
+					list[s_slot].n = 0; // until the group is entered
 				}
 			}
 			__syncthreads();
-			if (s_slot >= 0) large = a.list + s_slot;
+			if (s_slot >= 0) large = list + s_slot;
 		}
-		rc_group(a.P, g, lo, hi, W, threadIdx.x < 64, threadIdx.x, kCorLargeThreads, large);
-		__syncthreads();
+		rc_group(P, g, lo, hi, W, threadIdx.x < 64, threadIdx.x, kRankLargeThreads, large);
 	}
-}
 
-__global__ __launch_bounds__(kCorPairTile) void cor_pairs_kernel(CorArgs a) {
+	size_t prefix_bytes(int64_t n) const { return 256 + (size_t)n * sizeof(CorLarge); }
+
+	bool begin_large(char *prefix, int64_t n, hipStream_t st, AnofoxError *e) {
+		count = (unsigned long long *)prefix;
+		list = (CorLarge *)(prefix + 256);
+		slots = n;
+		return !hip_fail(hipMemsetAsync(count, 0, 256, st), "hipMemsetAsync", e);
+	}
+
+	bool end_large(const RankCall &c, hipStream_t st, AnofoxError *e) const; // Kendall's two kernels
+};
+
+__global__ __launch_bounds__(kCorPairTile) void cor_pairs_kernel(CorFamily f, CorWork W) {
 	__shared__ double sx[kCorPairTile], sy[kCorPairTile];
-	const int64_t listed = (int64_t)(*a.count < (unsigned long long)a.slots ? *a.count : (unsigned long long)a.slots);
+	const int64_t listed = (int64_t)(*f.count < (unsigned long long)f.slots ? *f.count : (unsigned long long)f.slots);
 	for (int64_t k = 0; k < listed; ++k) {
-		const int64_t n = a.list[k].n, lo = a.list[k].lo;
+		const int64_t n = f.list[k].n, lo = f.list[k].lo;
 		if (n < 3) continue;
-		const double *x = a.W.x + lo, *y = a.W.y + lo;
+		const double *x = W.x + lo, *y = W.y + lo;
 		const int64_t nb = (n + kCorPairTile - 1) / kCorPairTile;
 		int64_t s = 0;
 		for (int64_t t = blockIdx.x; t < nb * nb; t += gridDim.x) {
@@ -136,16 +106,22 @@ __global__ __launch_bounds__(kCorPairTile) void cor_pairs_kernel(CorArgs a) {
 		GiPL<int64_t> v;
 		v.v[0] = s;
 		const int64_t total = glm::gi_sum_i(v);
-		if ((threadIdx.x & 63u) == 0 && total != 0) atomicAdd((unsigned long long *)&a.list[k].s, (unsigned long long)total);
+		if ((threadIdx.x & 63u) == 0 && total != 0) atomicAdd((unsigned long long *)&f.list[k].s, (unsigned long long)total);
 	}
 }
 
-__global__ __launch_bounds__(64) void cor_finish_kernel(CorArgs a) {
-	const int64_t listed = (int64_t)(*a.count < (unsigned long long)a.slots ? *a.count : (unsigned long long)a.slots);
+__global__ __launch_bounds__(64) void cor_finish_kernel(CorFamily f) {
+	const int64_t listed = (int64_t)(*f.count < (unsigned long long)f.slots ? *f.count : (unsigned long long)f.slots);
 	for (int64_t k = (int64_t)blockIdx.x * 64 + threadIdx.x; k < listed; k += (int64_t)gridDim.x * 64) {
-		const CorLarge &L = a.list[k];
-		if (L.n >= 3) rc_kendall_record(a.P, L.s, L.n, L.tx, L.ty, a.P.records + L.group * kCorRecordLen);
+		const CorLarge &L = f.list[k];
+		if (L.n >= 3) rc_kendall_record(f.P, L.s, L.n, L.tx, L.ty, f.P.records + L.group * kCorRecordLen);
 	}
+}
+
+bool CorFamily::end_large(const RankCall &c, hipStream_t st, AnofoxError *e) const {
+	if (P.method != kCorKendall) return true;
+	return launch(cor_pairs_kernel, "cor_pairs_kernel", kCorPairWorkgroups, kCorPairTile, st, e, *this, c.W) &&
+	       launch(cor_finish_kernel, "cor_finish_kernel", (slots + 63) / 64, 64, st, e, *this);
 }
 
 const char *options_text(const AnofoxHipCorBatchOptions &o) {
@@ -165,68 +141,26 @@ bool check_cor(int64_t n_groups, int64_t n_rows, const void *off, const double *
 	return true;
 }
 
-template <class K>
-bool launch(K kernel, const char *name, const CorArgs &a, int64_t blocks, int threads, hipStream_t st, AnofoxError *e) {
-	hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(threads), 0, st, a);
-	return !hip_fail(hipGetLastError(), name, e);
-}
-
 // the correlations of n_groups groups of device-resident rows, enqueued on the context's stream (ctx->mu held by the caller)
 bool launch_cor(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *d_off, const double *d_x, const double *d_y,
                 const AnofoxHipCorBatchOptions &o, double *d_rec, AnofoxError *e) {
 	if (n_groups == 0) return true;
-	CorArgs a;
-	memset(&a, 0, sizeof a);
-	a.P.x = d_x;
-	a.P.y = d_y;
-	a.P.n_rows = n_rows;
-	a.P.method = o.method;
-	a.P.alternative = o.alternative;
-	a.P.tau_type = o.tau_type;
-	a.P.zq = o.confidence_level == o.confidence_level ? hostmath::normal_quantile(0.5 * (1.0 + o.confidence_level)) : NAN;
-	a.P.records = d_rec;
-	a.off = d_off;
-	a.n_groups = n_groups;
-	hipStream_t st = ctx->stream;
-	const int64_t blocks = n_groups < kCorMaxWorkgroups ? n_groups : kCorMaxWorkgroups;
-	if (o.method == kCorPearson) {
-		a.above = -1;
-		a.upto = INT64_MAX;
-		return launch(cor_small_kernel<kCorTierRows>, "cor_small_kernel", a, blocks, 64, st, e);
-	}
-	const int64_t hook = g_small_cap.load(), cap = hook > 0 && hook < kCorSmallCap ? hook : kCorSmallCap;
-	const int64_t tier = cap < kCorTierRows ? cap : kCorTierRows;
-	a.above = -1;
-	a.upto = tier;
-	if (!launch(cor_small_kernel<kCorTierRows>, "cor_small_kernel", a, blocks, 64, st, e)) return false;
-	if (n_rows <= tier) return true; // no group has more rows than the call
-	if (cap > tier) {
-		a.above = tier;
-		a.upto = cap;
-		if (!launch(cor_small_kernel<kCorSmallCap>, "cor_small_kernel", a, blocks, 64, st, e)) return false;
-	}
-	if (n_rows <= cap) return true;
-	// the large path: a counter, the list (disjoint groups above the cap: n_rows / (cap + 1) at most) and the work arrays
-	const size_t N = (size_t)n_rows;
-	a.slots = n_rows / (cap + 1) + 1;
-	const size_t list_at = 256, x_at = align_up(list_at + (size_t)a.slots * sizeof(CorLarge), 256);
-	const size_t col = align_up(N * sizeof(double), 256), total = x_at + 3 * col + align_up(N * sizeof(int32_t), 256);
-	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, total, "correlation scratch", e)) return false;
-	char *ws = (char *)ctx->ws;
-	a.count = (unsigned long long *)ws;
-	a.list = (CorLarge *)(ws + list_at);
-	a.W.x = (double *)(ws + x_at);
-	a.W.y = (double *)(ws + x_at + col);
-	a.W.key = (double *)(ws + x_at + 2 * col);
-	a.W.idx = (int32_t *)(ws + x_at + 3 * col);
-	a.above = cap;
-	a.upto = INT64_MAX;
-	if (hip_fail(hipMemsetAsync(a.count, 0, 256, st), "hipMemsetAsync", e)) return false;
-	const int64_t large_blocks = n_groups < kCorLargeWorkgroups ? n_groups : kCorLargeWorkgroups;
-	if (!launch(cor_large_kernel, "cor_large_kernel", a, large_blocks, kCorLargeThreads, st, e)) return false;
-	if (o.method != kCorKendall) return true;
-	return launch(cor_pairs_kernel, "cor_pairs_kernel", a, kCorPairWorkgroups, kCorPairTile, st, e) &&
-	       launch(cor_finish_kernel, "cor_finish_kernel", a, (a.slots + 63) / 64, 64, st, e);
+	CorFamily f;
+	memset(&f, 0, sizeof f);
+	f.P.x = d_x;
+	f.P.y = d_y;
+	f.P.n_rows = n_rows;
+	f.P.method = o.method;
+	f.P.alternative = o.alternative;
+	f.P.tau_type = o.tau_type;
+	f.P.zq = o.confidence_level == o.confidence_level ? hostmath::normal_quantile(0.5 * (1.0 + o.confidence_level)) : NAN;
+	f.P.records = d_rec;
+	RankCall c;
+	memset(&c, 0, sizeof c);
+	c.off = d_off;
+	c.n_groups = n_groups;
+	c.n_rows = n_rows;
+	return launch_tiers(ctx, c, g_small_cap.load(), f, e);
 }
 
 // host pointers: one staging of the whole call, the kernels, the records back
@@ -249,12 +183,6 @@ bool cor_host(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int
 	if (!launch_cor(ctx, n_groups, n_rows, d_off, d_x, d_y, o, d_rec, e)) return false;
 	if (!d2h(records, d_rec, G * kCorRecordLen * sizeof(double), st, e)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", e);
-}
-
-char *copy_text(const char *s) {
-	char *p = (char *)malloc(strlen(s) + 1);
-	if (p) strcpy(p, s);
-	return p;
 }
 
 // One group through the host batch entry with the reference's conventions: argument checks first, NULL entries -> NaN.

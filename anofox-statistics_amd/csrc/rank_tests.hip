@@ -1,19 +1,12 @@
-// rank_tests.hip — grouped Mann-Whitney U, Wilcoxon signed-rank and Kruskal-Wallis tests (rank_tests.h): the kernels of both size
-// paths and the entry points anofox_hip_rank_test_batch_{device,host}, anofox_hip_rank_test_record_len, anofox_hip_rank_test_hooks,
-// anofox_mann_whitney_u / anofox_wilcoxon_signed_rank / anofox_kruskal_wallis / anofox_free_test_result.
+// rank_tests.hip — grouped Mann-Whitney U, Wilcoxon signed-rank and Kruskal-Wallis tests (rank_tests.h): the family that runs on
+// the size-tiered launch driver of rank_launch.h and the entry points anofox_hip_rank_test_batch_{device,host},
+// anofox_hip_rank_test_record_len, anofox_hip_rank_test_hooks, anofox_mann_whitney_u / anofox_wilcoxon_signed_rank /
+// anofox_kruskal_wallis / anofox_free_test_result.
 //
 // The contract and the method: rank_tests.h and DESIGN.md §1, "Rank-based location tests".
-//   rank_test_small_kernel<CAP>: one wavefront per workgroup and group, grid-stride over the groups, the group's work arrays in
-//     LDS, in the two instances of cor_small_kernel (rank_cor.hip): groups of at most kRtTierRows rows take 7 KiB, so a CU holds as
-//     many wavefronts as its other limits admit; groups up to kRtSmallCap rows take 40 KiB, which keeps a wavefront on every SIMD.
-//     A kernel passes over the groups of the other tier.
-//   rank_test_large_kernel: a workgroup of 1024 threads per group above the cap, its work arrays in the context's workspace.  All
-//     sixteen wavefronts sort; the first runs the other phases with the small path's code, so the midranks and their sums come out
-//     bit for bit as on the small path.
-//   Neither form of the entry reads the offsets on the host to size a launch; the large path is launched whenever the call has
-//     more rows than the cap, and then takes kCorRowBytes of workspace per row of the call.
+//   rank_small_kernel<CAP, RankTestFamily>, rank_large_kernel<RankTestFamily>: the two size paths (rank_launch.h); every test
+//     stages its rows, and nothing follows the large kernel.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -25,6 +18,7 @@
 
 #include "common.h"
 #include "rank_tests.h"
+#include "rank_launch.h"
 
 using namespace anofox;
 
@@ -33,59 +27,32 @@ using namespace anofox;
 using namespace anofox::host;
 using namespace anofox::cor;
 using namespace anofox::ranktest;
+using namespace anofox::rank;
 
 namespace {
 
-// the caps of rank_cor.hip, for the same footprint: 40960 bytes / kCorRowBytes (28) = 1462 rows keep one wavefront on every SIMD
-constexpr int kRtSmallCap = 40960 / kCorRowBytes;
-static_assert(kRtSmallCap == 1462, "the cap's derivation");
-constexpr int kRtTierRows = 256; // the first instance's groups: 256 x 28 = 7 KiB
-constexpr int64_t kRtMaxWorkgroups = 1 << 16;
-constexpr int kRtLargeThreads = 1024;
-constexpr int kRtLargeWorkgroups = 1024;
-
 std::atomic<int64_t> g_small_cap{0}; // anofox_hip_rank_test_hooks
 
-struct RankTestArgs {
+struct RankTestFamily {
+	static constexpr const char *kSmallKernel = "rank_small_kernel<RankTestFamily>", *kLargeKernel = "rank_large_kernel<RankTestFamily>",
+	                            *kScratch = "rank test scratch";
 	RankTestProblem P;
-	const int64_t *off;
-	int64_t n_groups;
-	int64_t above, upto; // the kernel's groups: above < rows <= upto
-	CorWork W;           // the large path: each n_rows long; a group's part starts at its first row
+
+	__host__ __device__ bool staged() const { return true; }
+
+	__device__ __forceinline__ void small_group(int64_t g, int64_t lo, int64_t hi, const CorWork &W) const {
+		rt_group(P, g, lo, hi, W, true, threadIdx.x, 64);
+	}
+
+	__device__ __forceinline__ void large_group(int64_t g, int64_t lo, int64_t hi, const CorWork &W) const {
+		rt_group(P, g, lo, hi, W, threadIdx.x < 64, threadIdx.x, kRankLargeThreads);
+	}
+
+	// nothing in the workspace but the work arrays, nothing around the large kernel
+	size_t prefix_bytes(int64_t) const { return 0; }
+	bool begin_large(char *, int64_t, hipStream_t, AnofoxError *) { return true; }
+	bool end_large(const RankCall &, hipStream_t, AnofoxError *) const { return true; }
 };
-
-__device__ __forceinline__ void group_rows(const RankTestArgs &a, int64_t g, int64_t &lo, int64_t &hi) {
-	lo = a.off[g] < 0 ? 0 : a.off[g];
-	hi = a.off[g + 1] > a.P.n_rows ? a.P.n_rows : a.off[g + 1];
-	if (hi < lo) hi = lo;
-	if (lo > a.P.n_rows) lo = hi = a.P.n_rows;
-}
-
-template <int CAP>
-__global__ __launch_bounds__(64) void rank_test_small_kernel(RankTestArgs a) {
-	__shared__ double sx[CAP], sy[CAP], sk[CAP];
-	__shared__ int32_t si[CAP];
-	const CorWork W = {sx, sy, sk, si};
-	for (int64_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
-		int64_t lo, hi;
-		group_rows(a, g, lo, hi);
-		const int64_t m = hi - lo;
-		if (m <= a.above || m > a.upto || m > CAP) continue; // (m > CAP never: upto <= CAP)
-		rt_group(a.P, g, lo, hi, W, true, threadIdx.x, 64);
-		__syncthreads(); // the next group's rows overwrite these
-	}
-}
-
-__global__ __launch_bounds__(kRtLargeThreads) void rank_test_large_kernel(RankTestArgs a) {
-	for (int64_t g = blockIdx.x; g < a.n_groups; g += gridDim.x) {
-		int64_t lo, hi;
-		group_rows(a, g, lo, hi);
-		if (hi - lo <= a.above) continue;
-		const CorWork W = {a.W.x + lo, a.W.y + lo, a.W.key + lo, a.W.idx + lo};
-		rt_group(a.P, g, lo, hi, W, threadIdx.x < 64, threadIdx.x, kRtLargeThreads);
-		__syncthreads();
-	}
-}
 
 bool check_rank_test(int64_t n_groups, int64_t n_rows, const void *off, const double *v, const double *y, const int32_t *sample,
                      const AnofoxHipRankTestBatchOptions &o, const void *records, AnofoxError *e) {
@@ -104,56 +71,27 @@ bool check_rank_test(int64_t n_groups, int64_t n_rows, const void *off, const do
 	return true;
 }
 
-template <class K>
-bool launch(K kernel, const char *name, const RankTestArgs &a, int64_t blocks, int threads, hipStream_t st, AnofoxError *e) {
-	hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(threads), 0, st, a);
-	return !hip_fail(hipGetLastError(), name, e);
-}
-
 // the tests of n_groups groups of device-resident rows, enqueued on the context's stream (ctx->mu held by the caller)
 bool launch_rank_test(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *d_off, const double *d_v, const double *d_y,
                       const int32_t *d_sample, const AnofoxHipRankTestBatchOptions &o, double *d_rec, AnofoxError *e) {
 	if (n_groups == 0) return true;
-	RankTestArgs a;
-	memset(&a, 0, sizeof a);
-	a.P.v = d_v;
-	a.P.y = d_y;
-	a.P.sample = d_sample;
-	a.P.n_rows = n_rows;
-	a.P.test = o.test;
-	a.P.alternative = o.alternative;
-	a.P.correction = o.continuity_correction != 0;
-	a.P.mu = o.mu;
-	a.P.records = d_rec;
-	a.off = d_off;
-	a.n_groups = n_groups;
-	hipStream_t st = ctx->stream;
-	const int64_t blocks = n_groups < kRtMaxWorkgroups ? n_groups : kRtMaxWorkgroups;
-	const int64_t hook = g_small_cap.load(), cap = hook > 0 && hook < kRtSmallCap ? hook : kRtSmallCap;
-	const int64_t tier = cap < kRtTierRows ? cap : kRtTierRows;
-	a.above = -1;
-	a.upto = tier;
-	if (!launch(rank_test_small_kernel<kRtTierRows>, "rank_test_small_kernel", a, blocks, 64, st, e)) return false;
-	if (n_rows <= tier) return true; // no group has more rows than the call
-	if (cap > tier) {
-		a.above = tier;
-		a.upto = cap;
-		if (!launch(rank_test_small_kernel<kRtSmallCap>, "rank_test_small_kernel", a, blocks, 64, st, e)) return false;
-	}
-	if (n_rows <= cap) return true;
-	// the large path: the work arrays, each as long as the call
-	const size_t N = (size_t)n_rows;
-	const size_t col = align_up(N * sizeof(double), 256), total = 3 * col + align_up(N * sizeof(int32_t), 256);
-	if (!ensure_buffer(&ctx->ws, &ctx->ws_bytes, total, "rank test scratch", e)) return false;
-	char *ws = (char *)ctx->ws;
-	a.W.x = (double *)ws;
-	a.W.y = (double *)(ws + col);
-	a.W.key = (double *)(ws + 2 * col);
-	a.W.idx = (int32_t *)(ws + 3 * col);
-	a.above = cap;
-	a.upto = INT64_MAX;
-	const int64_t large_blocks = n_groups < kRtLargeWorkgroups ? n_groups : kRtLargeWorkgroups;
-	return launch(rank_test_large_kernel, "rank_test_large_kernel", a, large_blocks, kRtLargeThreads, st, e);
+	RankTestFamily f;
+	memset(&f, 0, sizeof f);
+	f.P.v = d_v;
+	f.P.y = d_y;
+	f.P.sample = d_sample;
+	f.P.n_rows = n_rows;
+	f.P.test = o.test;
+	f.P.alternative = o.alternative;
+	f.P.correction = o.continuity_correction != 0;
+	f.P.mu = o.mu;
+	f.P.records = d_rec;
+	RankCall c;
+	memset(&c, 0, sizeof c);
+	c.off = d_off;
+	c.n_groups = n_groups;
+	c.n_rows = n_rows;
+	return launch_tiers(ctx, c, g_small_cap.load(), f, e);
 }
 
 // host pointers: one staging of the whole call, the kernels, the records back
@@ -179,12 +117,6 @@ bool rank_test_host(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, con
 	if (!launch_rank_test(ctx, n_groups, n_rows, d_off, d_v, d_y, d_sample, o, d_rec, e)) return false;
 	if (!d2h(records, d_rec, G * kRtRecordLen * sizeof(double), st, e)) return false;
 	return !hip_fail(hipStreamSynchronize(st), "hipStreamSynchronize", e);
-}
-
-char *copy_text(const char *s) {
-	char *p = (char *)malloc(strlen(s) + 1);
-	if (p) strcpy(p, s);
-	return p;
 }
 
 bool fail(AnofoxError *e, const std::string &text) {

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import AnofoxStatsError
-from ._marshal import F64, I64, call, device_tensor, handle, host_array, _invoke
+from ._marshal import F64, I64, call, column, device_tensor, group_rows, handle, host_array, _invoke
 from .options import InvalidInputException, _extract_double
 
 TAU_METHOD = {"dl": 0, "dersimonian_laird": 0, "dersimonian-laird": 0, "none": 1, "pooled": 1, "complete": 1}
@@ -149,26 +149,19 @@ def eb_shrink(estimate, se, options=None) -> dict:
         lib.anofox_free_eb_shrink_result(C.byref(res))
 
 
-def _column(values):
-    a = np.asarray(values)
-    return np.array([np.nan if v is None else v for v in values], dtype=np.float64) if a.dtype == object else np.asarray(a, np.float64)
-
-
 def _sets(keys, n):
     """The items sorted by key (stably): -> (sorted unique keys, the permutation, offsets)."""
     keys = np.asarray(keys)
     if len(keys) != n:
         raise InvalidInputException("the keys and the estimates must have the same number of rows")
-    uniq, inv = np.unique(keys, return_inverse=True)
-    perm = np.argsort(inv, kind="stable")
-    return uniq, perm, np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=len(uniq)))]).astype(np.int64)
+    return group_rows(keys)
 
 
 def eb_shrink_agg(set_keys, estimate, se, options=None, context=None) -> dict:
     """eb_shrink_agg(estimate, se, options) GROUP BY set_keys: per key the reference's result (eb_shrink's dict, the rows in input
     order), or None for a set with fewer than 2 usable pairs.  A row whose estimate or se is None is skipped, as the aggregate's
     Update skips a NULL."""
-    e, s = _column(estimate), _column(se)
+    e, s = column(estimate), column(se)
     if len(e) != len(s):
         raise InvalidInputException("estimate and se must have the same number of rows")
     raw_e, raw_s = np.asarray(estimate, dtype=object), np.asarray(se, dtype=object)

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import AnofoxStatsError
-from ._marshal import I64, DeviceBatch, HostBatch, call, handle, host_array
+from ._marshal import I64, DeviceBatch, HostBatch, call, group_rows, handle, host_array
 from .options import GlmOptions, InvalidInputException, parse_binomial_options, parse_poisson_options
 
 def _glm_fit(b, options, offset, inference, threshold):
@@ -253,13 +253,11 @@ def _grouped(group_keys, y, x, opts: GlmOptions):
         raise InvalidInputException("group keys, y and x must have the same number of rows")
     if opts.offset < 0 or opts.offset > X.shape[1]:
         raise InvalidInputException("offset must be a 1-based index into x (1..=%d), got %d" % (X.shape[1], opts.offset))
-    uniq, inv = np.unique(keys, return_inverse=True)
-    perm = np.argsort(inv, kind="stable")
-    offsets = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=len(uniq)))]).astype(np.int64)
+    uniq, perm, offsets = group_rows(keys)
     feat = [j for j in range(X.shape[1]) if j != opts.offset - 1]
     cols = [np.ascontiguousarray(X[perm, j]) for j in feat]
     off = np.ascontiguousarray(X[perm, opts.offset - 1]) if opts.offset else None
-    return uniq, inv, perm, offsets, yv[perm], cols, off
+    return uniq, np.searchsorted(uniq, keys), perm, offsets, yv[perm], cols, off
 
 
 def _fit_agg(group_keys, y, x, opts: GlmOptions, context) -> GlmFitAggResult:

@@ -50,6 +50,17 @@ def _extract_enum(val: Any, table: Mapping[str, int], what: str, valid: str) -> 
     return s
 
 
+ALTERNATIVE = {"two_sided": 0, "two-sided": 0, "two.sided": 0, "twosided": 0, "less": 1, "greater": 2}
+
+
+def _extract_alternative(val: Any) -> int:
+    """The `alternative` key of the correlation and rank test options (case-insensitive) as the reference's AnofoxAlternative."""
+    name = str(val).lower()
+    if name not in ALTERNATIVE:
+        raise InvalidInputException("Unknown alternative '%s'. Expected 'two_sided', 'less' or 'greater'." % (val,))
+    return ALTERNATIVE[name]
+
+
 @dataclass
 class RegressionOptions:
     """Resolved options (defaults = the C++ bind data of the aggregates)."""

@@ -5,17 +5,14 @@ tests".  A group whose status is not 0 (an empty sample, fewer than 2 valid pair
 NULL) in the aggregates.  Exact p-values and the Hodges-Lehmann interval are not built: ci_lower / ci_upper are NaN."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Mapping, Optional
 
 import numpy as np
 
 from . import _abi
-from ._abi import AnofoxStatsError
-from ._marshal import F64, I32, I64, call, device_tensor, handle, host_array, _invoke
-from .correlation import ALTERNATIVE, _column
-from .options import InvalidInputException, _extract_double
+from ._marshal import I32, DeviceBatch, HostBatch, column, group_rows, scalar_call
+from .options import InvalidInputException, _extract_alternative, _extract_double
 
 MANN_WHITNEY, WILCOXON, KRUSKAL_WALLIS = 0, 1, 2
 RECORD_NAMES = ("statistic", "z", "p_value", "df", "n", "n1", "n2", "status")
@@ -64,10 +61,7 @@ def parse_rank_test_options(opts) -> RankTestOptions:
     for raw_key, val in opts.items():
         key = str(raw_key).lower()
         if key == "alternative" and val is not None:
-            name = str(val).lower()
-            if name not in ALTERNATIVE:
-                raise InvalidInputException("Unknown alternative '%s'. Expected 'two_sided', 'less' or 'greater'." % (val,))
-            out.alternative = ALTERNATIVE[name]
+            out.alternative = _extract_alternative(val)
         elif key in ("continuity_correction", "correction") and val is not None:
             out.continuity_correction = _extract_bool(val)
         elif key == "mu" and val is not None:
@@ -77,44 +71,25 @@ def parse_rank_test_options(opts) -> RankTestOptions:
     return out
 
 
-def _batch_options(test: int, options):
-    return parse_rank_test_options(options).batch_options(test)
+def _rank_test_batch(b, y, sample, test, options):
+    """records[G, 8] of the batch b, whose leading column is v."""
+    rec = b.out((b.G, 8))
+    b.call("anofox_hip_rank_test_batch", b.G, b.N, b.off, b.y, b.rows(y, "y"), b.rows(sample, "sample", I32),
+           parse_rank_test_options(options).batch_options(test), rec)
+    return rec
 
 
 def rank_test_batch_host(row_offsets, v, y, sample, test: int, options=None, ctx=None) -> np.ndarray:
     """numpy in / out: group g owns rows [row_offsets[g], row_offsets[g + 1]) of v, of y (Wilcoxon, else None) and of the int32
     sample ids (Mann-Whitney and Kruskal-Wallis, else None).  Returns records[n_groups, 8] = RECORD_NAMES;
     anofox_hip_rank_test_batch_host's layout."""
-    off = host_array(row_offsets, I64, None, "row_offsets")
-    if off.size < 1:
-        raise ValueError("row_offsets needs one entry more than there are groups")
-    vv = host_array(v, F64, None, "v")
-    yv = None if y is None else host_array(y, F64, vv.size, "y")
-    sv = None if sample is None else host_array(sample, I32, vv.size, "sample")
-    rec = np.empty((off.size - 1, 8))
-    call(_abi.load(), "anofox_hip_rank_test_batch_host", handle(ctx), off.size - 1, vv.size, off, vv, yv, sv, _batch_options(test, options), rec)
-    return rec
+    return _rank_test_batch(HostBatch(ctx, row_offsets, v, [], lead="v"), y, sample, test, options)
 
 
 def rank_test_batch_device(ctx, row_offsets, v, y, sample, test: int, options=None, use_current_torch_stream: bool = True):
     """rank_test_batch_host on CUDA tensors (row_offsets int64, v / y float64, sample int32).  Asynchronous.  Returns the records
     tensor."""
-    import torch
-
-    off = device_tensor(row_offsets, I64, None, "row_offsets")
-    if off.numel() < 1:
-        raise ValueError("row_offsets needs one entry more than there are groups")
-    vv = device_tensor(v, F64, None, "v", off.device)
-    yv = None if y is None else device_tensor(y, F64, vv.numel(), "y", off.device)
-    sv = None if sample is None else device_tensor(sample, I32, vv.numel(), "sample", off.device)
-    rec = torch.empty((off.numel() - 1, 8), dtype=torch.float64, device=off.device)
-    if use_current_torch_stream:
-        ctx.set_stream(torch.cuda.current_stream(off.device).cuda_stream)
-    ok, err = _invoke(ctx._lib, "anofox_hip_rank_test_batch_device", (ctx._h, off.numel() - 1, vv.numel(), off, vv, yv, sv,
-                                                                      _batch_options(test, options), rec))
-    if not ok:
-        raise AnofoxStatsError(err.code, err.text())
-    return rec
+    return _rank_test_batch(DeviceBatch(ctx, row_offsets, v, [], use_current_torch_stream, lead="v"), y, sample, test, options)
 
 
 def rank_test_hooks(small_cap: int = 0):
@@ -160,18 +135,16 @@ def _sample_column(sample, v):
 
 def _agg(test, keys, v, y, sample, options, context) -> RankTestAggResult:
     o = parse_rank_test_options(options)
-    vv, keys = _column(v), np.asarray(keys)
+    vv = column(v)
     yv = sv = None
     if test == WILCOXON:
-        yv = _column(y)
+        yv = column(y)
     else:
         sv, vv = _sample_column(sample, vv)
     second = yv if sv is None else sv
     if not (len(vv) == len(second) == len(keys)):
         raise InvalidInputException("the keys and the two columns must have the same number of rows")
-    uniq, inv = np.unique(keys, return_inverse=True)
-    perm = np.argsort(inv, kind="stable")
-    off = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=len(uniq)))]).astype(np.int64)
+    uniq, perm, off = group_rows(keys)
     rec = rank_test_batch_host(off, vv[perm], None if yv is None else yv[perm], None if sv is None else sv[perm], test, o, ctx=context)
     return RankTestAggResult(uniq, rec, test)
 
@@ -192,25 +165,12 @@ def kruskal_wallis_agg(keys, value, sample, context=None) -> RankTestAggResult:
     return _agg(KRUSKAL_WALLIS, keys, value, None, sample, None, context)
 
 
+_RESULT_FIELDS = [(f, f) for f in ("statistic", "p_value", "df", "effect_size", "ci_lower", "ci_upper", "confidence_level", "n", "n1", "n2",
+                                    "alternative", "method")]
+
+
 def _scalar(symbol, a, b, ffi_options) -> dict:
-    from .scalar import _data_array
-    lib = _abi.load()
-    aa, k0 = _data_array(a)
-    ba, k1 = _data_array(b)
-    res = _abi.AnofoxTestResult()
-    args = (aa, ba, C.byref(res)) if ffi_options is None else (aa, ba, ffi_options, C.byref(res))
-    try:
-        call(lib, symbol, *args)
-    except AnofoxStatsError as failed:
-        e = InvalidInputException(f"{symbol.replace('anofox_', '')} failed: {failed}")
-        e.code = failed.code
-        raise e from None
-    try:
-        return {"statistic": res.statistic, "p_value": res.p_value, "df": res.df, "effect_size": res.effect_size, "ci_lower": res.ci_lower,
-                "ci_upper": res.ci_upper, "confidence_level": res.confidence_level, "n": res.n, "n1": res.n1, "n2": res.n2,
-                "alternative": res.alternative, "method": res.method.decode() if res.method else None}
-    finally:
-        lib.anofox_free_test_result(C.byref(res))
+    return scalar_call(symbol, (a, b), ffi_options, _abi.AnofoxTestResult, "anofox_free_test_result", _RESULT_FIELDS)
 
 
 def _exact(options) -> bool:

@@ -1,7 +1,8 @@
 """GPU tier of the correlation family: anofox_hip_cor_batch_{host,device} on the shapes of tests/cor_restate.py (groups of 0, 2, 3,
 4, 63, 64, 65, 129 and 300 valid rows in one call; noise, scattered NaN rows, a constant x, heavy ties, an exact monotone group),
 with the cap hooked to 128 (129 and 300 on the large path) and at the default cap (both on the small path), against the
-restatement; the two paths against each other; the scalars and the aggregates on the tables of the reference's SQL tests."""
+restatement; the two paths against each other; the last row of each size tier and the first of the next in one call; the scalars
+and the aggregates on the tables of the reference's SQL tests."""
 import numpy as np
 import pytest
 
@@ -75,6 +76,19 @@ def test_several_large_groups_share_the_pair_kernel(pkg):
         pkg.cor_test_hooks(0)
         assert pkg.cor_batch_host(off, x, y, m)[:, [0, 5, 6, 7]].tobytes() == large[:, [0, 5, 6, 7]].tobytes()
         pkg.cor_test_hooks(128)
+
+
+def boundary_call():
+    """Groups of 256, 257, 1462 and 1463 rows of rounded normals: at the default cap both small instances and the large path."""
+    rng = np.random.default_rng(17)
+    off = np.concatenate([[0], np.cumsum([256, 257, 1462, 1463])]).astype(np.int64)
+    return off, np.round(rng.standard_normal(off[-1]), 1), np.round(rng.standard_normal(off[-1]), 1)
+
+
+def test_tier_boundaries_at_the_default_cap(pkg):
+    off, x, y = boundary_call()
+    for m in METHODS.values():
+        R.check_records(pkg.cor_batch_host(off, x, y, m), R.reference(off, x, y, m))
 
 
 def test_empty_call_and_empty_groups(pkg):

@@ -1,10 +1,13 @@
 """GPU tier of the rank tests: anofox_hip_rank_test_batch_{host,device} on the shapes of tests/rank_test_restate.py (groups of 0, 1,
 2, 3, 4, 63, 64, 65, 129 and 300 valid rows in one call, for every content of every test), with the cap hooked to 128 (129 and 300
 on the large path) and at the default cap (both on the small path), against the restatement; the two paths against each other;
-one group above the true cap; the scalars and the aggregates on the tables of the reference's SQL tests."""
+one group above the true cap; the last row of each size tier and the first of the next in one call; the test hooks of this family
+and of the correlation family, each leaving the other's cap alone; the scalars and the aggregates on the tables of the reference's
+SQL tests."""
 import numpy as np
 import pytest
 
+import cor_restate
 import rank_test_restate as R
 from conftest import import_pkg
 
@@ -96,6 +99,50 @@ def test_one_group_above_the_true_cap(pkg):
     for test in R.TESTS.values():
         v, y, s = _columns(test, call)
         R.check_records(test, pkg.rank_test_batch_host(call["off"], v, y, s, test), R.reference(test, call))
+
+
+def boundary_call():
+    """Groups of 256, 257, 1462 and 1463 rows of rounded normals: at the default cap both small instances and the large path."""
+    rng = np.random.default_rng(17)
+    off = np.concatenate([[0], np.cumsum([256, 257, 1462, 1463])]).astype(np.int64)
+    n = off[-1]
+    return dict(off=off, v=np.round(rng.standard_normal(n), 1), y=np.round(rng.standard_normal(n), 1),
+                sample=rng.choice(np.array([0, 5, -1], np.int32), n), mu=0.0)
+
+
+def test_tier_boundaries_at_the_default_cap(pkg):
+    call = boundary_call()
+    for test in R.TESTS.values():
+        v, y, s = _columns(test, call)
+        R.check_records(test, pkg.rank_test_batch_host(call["off"], v, y, s, test), R.reference(test, call))
+
+
+def test_each_family_has_its_own_hook(pkg):
+    """A Mann-Whitney and a Spearman call of one 300-row group each, with one family's cap hooked to 128 and the other's not, both
+    ways round: within bounds of the restatement, and the exact columns as with neither hooked."""
+    rng = np.random.default_rng(19)
+    n = 300
+    call = dict(off=np.array([0, n], np.int64), v=np.round(rng.standard_normal(n), 1), y=np.round(rng.standard_normal(n), 1),
+                sample=rng.choice(np.array([0, 1], np.int32), n), mu=0.0)
+    refs = R.reference(R.MANN_WHITNEY, call), cor_restate.reference(call["off"], call["v"], call["y"], cor_restate.SPEARMAN)
+
+    def both(cor_cap, rank_cap):
+        pkg.cor_test_hooks(cor_cap)
+        pkg.rank_test_hooks(rank_cap)
+        return (pkg.rank_test_batch_host(call["off"], call["v"], None, call["sample"], R.MANN_WHITNEY),
+                pkg.cor_batch_host(call["off"], call["v"], call["y"], cor_restate.SPEARMAN))
+    try:
+        plain = both(0, 0)
+        for caps in ((128, 0), (0, 128)):
+            mw, rho = both(*caps)
+            R.check_records(R.MANN_WHITNEY, mw, refs[0])
+            cor_restate.check_records(rho, refs[1])
+            cols = _exact_columns(R.MANN_WHITNEY)
+            assert mw[:, cols].tobytes() == plain[0][:, cols].tobytes()
+            assert rho[:, [0, 5, 6, 7]].tobytes() == plain[1][:, [0, 5, 6, 7]].tobytes()
+    finally:
+        pkg.cor_test_hooks(0)
+        pkg.rank_test_hooks(0)
 
 
 def test_empty_call_and_empty_groups(pkg):
