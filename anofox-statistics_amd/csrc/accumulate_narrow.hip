@@ -27,9 +27,9 @@
 //
 // Roofline: HBM-bound.  Algorithmic bytes per row 8(p+1) (+8 with weights); 63 f64 VALU ops per row at
 // p = 8 (~20 % of the f64 vector rate at the HBM-bound row rate).
-#include <stdlib.h>
 
 #include "common.h"
+#include "context.h"
 #include "solve_narrow_impl.h"
 #include "wave_reduce.h"
 
@@ -37,12 +37,8 @@ namespace anofox {
 
 typedef double dbl2u __attribute__((ext_vector_type(2), aligned(8)));
 
-// 16-byte streaming load; NT = non-temporal (ANOFOX_NARROW_NT=1, fused kernel only: an A/B switch for measurements)
-template <bool NT>
-__device__ __forceinline__ dbl2u load2(const double *p) {
-	if (NT) return __builtin_nontemporal_load(reinterpret_cast<const dbl2u *>(p));
-	return *reinterpret_cast<const dbl2u *>(p);
-}
+// 16-byte streaming load
+__device__ __forceinline__ dbl2u load2(const double *p) { return *reinterpret_cast<const dbl2u *>(p); }
 
 // the loads of one 128-row tile, in flight or landed: rows 2 lane and 2 lane + 1 of every column
 template <int Z>
@@ -50,7 +46,7 @@ struct NarrowTile {
 	double n0[Z], n1[Z], nw0, nw1;
 };
 
-template <int P, bool WEIGHTED, bool NT>
+template <int P, bool WEIGHTED>
 __device__ __forceinline__ void narrow_load_tile(const BatchArgs &args, int64_t base, int64_t hi, int lane, NarrowTile<P + 1> &t) {
 	const int64_t r0 = base + 2 * lane;
 	// (measured in round 3 and taken back: loading a group's partial last tile like a full one wherever the arrays reach that
@@ -58,17 +54,17 @@ __device__ __forceinline__ void narrow_load_tile(const BatchArgs &args, int64_t 
 	if (base + 128 <= hi) { // full tile: one 16-byte load per column
 #pragma unroll
 		for (int j = 0; j < P; ++j) {
-			const dbl2u v = load2<NT>(args.x[j] + r0);
+			const dbl2u v = load2(args.x[j] + r0);
 			t.n0[j] = v.x;
 			t.n1[j] = v.y;
 		}
 		{
-			const dbl2u v = load2<NT>(args.y + r0);
+			const dbl2u v = load2(args.y + r0);
 			t.n0[P] = v.x;
 			t.n1[P] = v.y;
 		}
 		if (WEIGHTED) {
-			const dbl2u v = load2<NT>(args.w + r0);
+			const dbl2u v = load2(args.w + r0);
 			t.nw0 = v.x;
 			t.nw1 = v.y;
 		}
@@ -225,7 +221,7 @@ __device__ __forceinline__ void narrow_acc_finish(NarrowAcc<P> &c, double *rec, 
 }
 
 // The rows [lo, hi) of one group (or of one segment of a very large group) -> one moment record at `rec`.
-template <int P, bool WEIGHTED, bool CENTER, bool PREFETCH, bool NT = false>
+template <int P, bool WEIGHTED, bool CENTER, bool PREFETCH>
 __device__ __forceinline__ void accumulate_rows(const BatchArgs &args, int64_t lo, int64_t hi, double *rec, int lane) {
 	constexpr int Z = P + 1;
 	NarrowAcc<P> c;
@@ -233,9 +229,9 @@ __device__ __forceinline__ void accumulate_rows(const BatchArgs &args, int64_t l
 	NarrowTile<Z> t;
 	// the loads of tile t + 1 are issued before the arithmetic of tile t (PREFETCH), so that a wave always has
 	// one tile of loads in flight; all loads of a tile sit in one arm of the (wave-uniform) full / ragged branch
-	if (PREFETCH && lo < hi) narrow_load_tile<P, WEIGHTED, NT>(args, lo, hi, lane, t);
+	if (PREFETCH && lo < hi) narrow_load_tile<P, WEIGHTED>(args, lo, hi, lane, t);
 	for (int64_t base = lo; base < hi; base += 128) {
-		if (!PREFETCH) narrow_load_tile<P, WEIGHTED, NT>(args, base, hi, lane, t);
+		if (!PREFETCH) narrow_load_tile<P, WEIGHTED>(args, base, hi, lane, t);
 		double z0[Z], z1[Z];
 		double w0 = 1.0, w1 = 1.0;
 #pragma unroll
@@ -247,7 +243,7 @@ __device__ __forceinline__ void accumulate_rows(const BatchArgs &args, int64_t l
 			w0 = t.nw0;
 			w1 = t.nw1;
 		}
-		if (PREFETCH && base + 128 < hi) narrow_load_tile<P, WEIGHTED, NT>(args, base + 128, hi, lane, t);
+		if (PREFETCH && base + 128 < hi) narrow_load_tile<P, WEIGHTED>(args, base + 128, hi, lane, t);
 		narrow_tile_compute<P, WEIGHTED, CENTER>(c, z0, z1, w0, w1, base + 2 * lane, hi);
 	}
 	narrow_acc_finish<P, CENTER>(c, rec, lane);
@@ -314,7 +310,7 @@ __device__ __forceinline__ void accumulate_group(const BatchArgs &args, int64_t 
 constexpr int kFusedGroups = ANOFOX_NARROW_FUSED_K;
 static_assert(kFusedGroups >= 1 && kFusedGroups <= 32, "groups per wavefront: one lane each, a 32-bit skip mask");
 
-template <int P, bool WEIGHTED, bool CENTER, bool PF, bool NT>
+template <int P, bool WEIGHTED, bool CENTER, bool PF>
 __device__ __forceinline__ void accumulate_solve_groups(const BatchArgs &args, int64_t g0, int lane, double *lrec, double *lcore) {
 	using L = MomentLayout<P>;
 	constexpr int CL = P + 6; // core record
@@ -328,7 +324,7 @@ __device__ __forceinline__ void accumulate_solve_groups(const BatchArgs &args, i
 			skip |= 1u << i;
 			continue;
 		}
-		accumulate_rows<P, WEIGHTED, CENTER, PF, NT>(args, lo, hi, lrec + i * L::REC, lane);
+		accumulate_rows<P, WEIGHTED, CENTER, PF>(args, lo, hi, lrec + i * L::REC, lane);
 	}
 	// the slice is this wavefront's alone: a fence orders its LDS stores before the loads of other lanes, no barrier
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -347,7 +343,7 @@ __device__ __forceinline__ void accumulate_solve_groups(const BatchArgs &args, i
 
 // (FUSED: at most 256 registers, VGPRs and AGPRs together, so that two waves stay resident per SIMD; the inlined solve is
 // the one without inference statistics)
-template <int P, bool WEIGHTED, bool CENTER, bool PF, bool FUSED = false, bool NT = false>
+template <int P, bool WEIGHTED, bool CENTER, bool PF, bool FUSED = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FUSED ? 2 : 1))) void accumulate_narrow_kernel(BatchArgs args) {
 	const int lane = threadIdx.x & 63;
 	const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -357,7 +353,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FUSED ? 2 :
 		__shared__ double lcore[4][kFusedGroups * (P + 6)];
 		const int64_t g0 = ((int64_t)blockIdx.x * 4 + wave) * kFusedGroups;
 		if (g0 >= args.n_groups) return;
-		accumulate_solve_groups<P, WEIGHTED, CENTER, PF, NT>(args, g0, lane, lrec[wave], lcore[wave]);
+		accumulate_solve_groups<P, WEIGHTED, CENTER, PF>(args, g0, lane, lrec[wave], lcore[wave]);
 		return;
 	}
 	const int64_t g = wave + (int64_t)blockIdx.x * 4;
@@ -463,7 +459,7 @@ __global__ __launch_bounds__(64) void solve_big_narrow_kernel(BatchArgs args) {
 	solve_one<P, MODE_PRIMARY>(args, g, args.moments + g * (int64_t)MomentLayout<P>::REC, args.core + g * (int64_t)(P + 6));
 }
 
-template <int P, bool PF, bool FUSED, bool NT>
+template <int P, bool PF, bool FUSED>
 static hipError_t launch_pn(const BatchArgs &a, hipStream_t stream) {
 	const dim3 block(256);
 	const int64_t per_block = FUSED ? 4 * kFusedGroups : 4;
@@ -475,7 +471,7 @@ static hipError_t launch_pn(const BatchArgs &a, hipStream_t stream) {
 	do {                                                                                                      \
 		constexpr bool F = FUSED && narrow_fused_fits(P, W, C);                                                      \
 		if (FUSED && !F) return hipErrorNotSupported;                                                         \
-		hipLaunchKernelGGL((accumulate_narrow_kernel<P, W, C, PF, F, F && NT>), grid, block, 0, stream, a);   \
+		hipLaunchKernelGGL((accumulate_narrow_kernel<P, W, C, PF, F>), grid, block, 0, stream, a);            \
 		if (a.seg_table) hipLaunchKernelGGL((accumulate_segments_kernel<P, W, C, PF>), seg_grid, block, 0, stream, a); \
 	} while (0)
 	if (weighted) {
@@ -516,15 +512,10 @@ static hipError_t launch_list_pn(const BatchArgs &a, const int32_t *list, const 
 template <int P>
 static hipError_t launch_p(const BatchArgs &a, const int32_t *list, const int32_t *count, bool fused, hipStream_t stream) {
 	// ANOFOX_ACC_PF=0 issues a tile's loads at the top of its own iteration instead of one tile ahead (A/B measurements)
-	static const int pf = [] { const char *e = getenv("ANOFOX_ACC_PF"); return e ? atoi(e) : 1; }();
-	// ANOFOX_NARROW_NT=1: non-temporal loads in the fused kernel (with the prefetch on; A/B measurements)
-	static const int nt = [] { const char *e = getenv("ANOFOX_NARROW_NT"); return e ? atoi(e) : 0; }();
+	static const bool pf = env_on("ANOFOX_ACC_PF");
 	if (list) return pf ? launch_list_pn<P, true>(a, list, count, stream) : launch_list_pn<P, false>(a, list, count, stream);
-	if (fused) {
-		if (!pf) return launch_pn<P, false, true, false>(a, stream);
-		return nt ? launch_pn<P, true, true, true>(a, stream) : launch_pn<P, true, true, false>(a, stream);
-	}
-	return pf ? launch_pn<P, true, false, false>(a, stream) : launch_pn<P, false, false, false>(a, stream);
+	if (fused) return pf ? launch_pn<P, true, true>(a, stream) : launch_pn<P, false, true>(a, stream);
+	return pf ? launch_pn<P, true, false>(a, stream) : launch_pn<P, false, false>(a, stream);
 }
 
 static hipError_t launch_any(const BatchArgs &a, const int32_t *list, const int32_t *count, bool fused, hipStream_t stream) {

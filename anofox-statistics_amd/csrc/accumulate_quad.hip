@@ -24,18 +24,13 @@
 // wave-private LDS slice column by column (stride = 8 mod 32 doubles: the 32 lanes of a half wave read rows 0..7 of four
 // columns, 32 different banks) and every lane reads one double per column group and step.  No barrier.
 #include <stddef.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
+#include "context.h"
 #include "lds_dma.h"
 
-// what-if builds (never shipped: results are wrong): bit 0 = no MFMA, 1 = no row filter, 2 = no constant-column test,
-// 3 = a block's rows are not written to LDS, 4 = one step per block instead of 4 RL
-#ifndef ANOFOX_QUAD_SKIP
-#define ANOFOX_QUAD_SKIP 0
-#endif
 #ifndef ANOFOX_QUAD_NOUNROLL_NB
 #define ANOFOX_QUAD_NOUNROLL_NB 8 // from this many column groups on the steps of a block are not unrolled in pairs (registers)
 #endif
@@ -260,7 +255,7 @@ __device__ __forceinline__ bool quad_accumulate_rows(const WideArgs &args, int64
 			// CENTER: deviations from the group's first valid row (first = 0 for the ones); otherwise raw values, masked
 			d[g] = CENTER ? dev : (valid_all ? v : quad_mask(v, rm));
 			// constant-column predicate of ols.rs:76-87: the largest |x - x_first| per lane and column, tested once per group
-			if (!SPEC && !(ANOFOX_QUAD_SKIP & 4)) dmax[g] = fmax(dmax[g], fabs(dev));
+			if (!SPEC) dmax[g] = fmax(dmax[g], fabs(dev));
 			a[g] = WEIGHTED ? wv * d[g] : d[g];
 		}
 		int t = 0;
@@ -268,8 +263,7 @@ __device__ __forceinline__ bool quad_accumulate_rows(const WideArgs &args, int64
 		for (int g = 0; g < NB; ++g) {
 #pragma unroll
 			for (int h = g; h < NB; ++h) {
-				if (ANOFOX_QUAD_SKIP & 1) acc[t] += a[g] + d[h];
-				else acc[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[g], d[h], acc[t], 0, 0, 0);
+				acc[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[g], d[h], acc[t], 0, 0, 0);
 				++t;
 			}
 		}
@@ -282,7 +276,7 @@ __device__ __forceinline__ bool quad_accumulate_rows(const WideArgs &args, int64
 #pragma unroll
 		for (int e = 0; e < RL; ++e) {
 			double z = 0.0;
-			if (!SPEC && !(ANOFOX_QUAD_SKIP & 2)) {
+			if (!SPEC) {
 #pragma unroll
 				for (int c = 0; c < NCOL; ++c) z = fma(0.0, reg[c][e], z);
 			}
@@ -296,7 +290,7 @@ __device__ __forceinline__ bool quad_accumulate_rows(const WideArgs &args, int64
 		}
 #pragma unroll
 		for (int c = 0; c < NCOL; ++c) {
-			if (c < ncol && !(ANOFOX_QUAD_SKIP & 8)) {
+			if (c < ncol) {
 				if (RL == 2) *reinterpret_cast<quad_dbl2a *>(buf + c * RS + 2 * lane) = quad_dbl2a{reg[c][0], reg[c][RL - 1]};
 				else buf[c * RS + lane] = reg[c][0];
 			}
@@ -326,7 +320,7 @@ __device__ __forceinline__ bool quad_accumulate_rows(const WideArgs &args, int64
 					for (int sidx = 0; sidx < 4 * RL; ++sidx) step(sidx, true, 0xFFFFu);
 				} else {
 #pragma unroll 2
-					for (int sidx = 0; sidx < ((ANOFOX_QUAD_SKIP & 16) ? 1 : 4 * RL); ++sidx) step(sidx, true, 0xFFFFu);
+					for (int sidx = 0; sidx < 4 * RL; ++sidx) step(sidx, true, 0xFFFFu);
 				}
 			} else {
 				cnt += __popcll(v0) + (RL == 2 ? __popcll(v1) : 0);
@@ -357,7 +351,8 @@ __device__ __forceinline__ bool quad_accumulate_rows(const WideArgs &args, int64
 // (M0 is written in the statement that uses it), so the compiler neither counts nor waits for them: the loop waits with
 // vmcnt(number of columns) — one block stays in flight — before it reads a half.  What is left per 32-row block: 4 NB - 1 DMA
 // instructions, 2 x (NB ds_read_b64 + NB subtractions + NB (NB + 1) / 2 v_mfma_f64_4x4x4) and nothing else.
-// doubles per column of a ring of RING 32-row blocks: 32 RING + 8 (= 8 mod 32: conflict-free ds_read_b64, see above)
+constexpr int kQuadRing = 2; // 32-row blocks in a wavefront's ring: one is read while the other lands
+// doubles per column of a ring of `ring` 32-row blocks: 32 ring + 8 (= 8 mod 32: conflict-free ds_read_b64, see above)
 __host__ __device__ constexpr int quad_dma_stride(int ring) { return 32 * ring + 8; }
 __host__ __device__ constexpr int quad_dma_slice_doubles(int p, int ring) {
 	const int data = (p + 1) * quad_dma_stride(ring);
@@ -366,13 +361,11 @@ __host__ __device__ constexpr int quad_dma_slice_doubles(int p, int ring) {
 	return data > image ? data : image;
 }
 
-// RING = 2: block k + 1 lands while block k is read (one block in flight per wavefront).  RING = 3: blocks k + 1 and k + 2 are in
-// flight — the bytes in flight are what the HBM latency under load is paid with (one block per wavefront, eight wavefronts per
-// CU: 17.8 MB on the chip at p = 33, 3.8 us at the measured 4.7 TB/s) — at the price of a slice half as large again.
-template <int NB, int RING>
+// Block k + 1 lands while block k is read: one block in flight per wavefront.
+template <int NB>
 __device__ __forceinline__ bool quad_spec_dma_rows(const WideArgs &args, int64_t lo, int64_t hi, double *rec, int lane, double *buf) {
 	constexpr int NPAIR = NB * (NB + 1) / 2;
-	constexpr int RS = quad_dma_stride(RING);
+	constexpr int RS = quad_dma_stride(kQuadRing);
 	const int p = args.p;
 	const int k = lane >> 4, b = (lane >> 2) & 3, c4 = lane & 3;
 	const int rsub = 4 * k + b;
@@ -422,23 +415,9 @@ __device__ __forceinline__ bool quad_spec_dma_rows(const WideArgs &args, int64_t
 			}
 		}
 	};
-	// all but the youngest block have landed (the loads retire in order; ncol = p + 1 of them per block, 4 NB - 4 .. 4 NB - 1)
-	auto wait_but_one_block = [&]() {
-		switch (p + 1 - (4 * NB - 4)) { // wave-uniform
-		case 0: lds_dma_wait_but<4 * NB - 4>(); break;
-		case 1: lds_dma_wait_but<4 * NB - 3>(); break;
-		case 2: lds_dma_wait_but<4 * NB - 2>(); break;
-		default: lds_dma_wait_but<4 * NB - 1>(); break;
-		}
-	};
 	int h = 0;
 	dma(lo, 0);
-	if (RING == 3 && lo + 32 < hi) {
-		dma(lo + 32, 1);
-		wait_but_one_block();
-	} else {
-		lds_dma_wait_all();
-	}
+	lds_dma_wait_all();
 	__builtin_amdgcn_wave_barrier();
 	{ // the shift: the group's first row (the constants are not shifted)
 #pragma unroll
@@ -448,28 +427,14 @@ __device__ __forceinline__ bool quad_spec_dma_rows(const WideArgs &args, int64_t
 	// full blocks in a loop without a branch around the matrix instructions, the partial last block after it (with the choice
 	// inside the loop the compiler copies the accumulators at every join)
 	int64_t blk = lo;
-	if constexpr (RING == 2) {
-		for (; blk + 32 <= hi; blk += 32, h ^= 1) {
-			if (blk + 32 < hi) dma(blk + 32, h ^ 1); // lands while this block's steps run
-			__builtin_amdgcn_wave_barrier();
-			const double *hb = buf + 32 * h;
-			step(hb, 0, true, 0xFFFFu);
-			step(hb, 1, true, 0xFFFFu);
-			__builtin_amdgcn_wave_barrier(); // the reads of this half before the DMA that refills it (next trip but one)
-			lds_dma_wait_all();              // the next block has landed (it had this block's steps to do so)
-		}
-	} else {
-		for (; blk + 32 <= hi; blk += 32, h = h == 2 ? 0 : h + 1) {
-			const bool more = blk + 64 < hi;
-			if (more) dma(blk + 64, h == 0 ? 2 : h - 1); // the third of the ring that the block before this one was read from
-			__builtin_amdgcn_wave_barrier();
-			const double *hb = buf + 32 * h;
-			step(hb, 0, true, 0xFFFFu);
-			step(hb, 1, true, 0xFFFFu);
-			__builtin_amdgcn_wave_barrier();
-			if (more) wait_but_one_block(); // block + 32 has landed, block + 64 may still be under way
-			else lds_dma_wait_all();
-		}
+	for (; blk + 32 <= hi; blk += 32, h ^= 1) {
+		if (blk + 32 < hi) dma(blk + 32, h ^ 1); // lands while this block's steps run
+		__builtin_amdgcn_wave_barrier();
+		const double *hb = buf + 32 * h;
+		step(hb, 0, true, 0xFFFFu);
+		step(hb, 1, true, 0xFFFFu);
+		__builtin_amdgcn_wave_barrier(); // the reads of this half before the DMA that refills it (next trip but one)
+		lds_dma_wait_all();              // the next block has landed (it had this block's steps to do so)
 	}
 	if (blk < hi) {
 		const int64_t left = hi - blk;
@@ -479,273 +444,6 @@ __device__ __forceinline__ bool quad_spec_dma_rows(const WideArgs &args, int64_t
 		if (left > 16) step(hb, 1, false, m32 >> 16);
 	}
 	lds_dma_wait_all();
-	return quad_finish<NB, true>(args, rec, lane, buf, acc, first, dmax, isx_prev, isx_last, 0, lo, hi);
-}
-
-// ---- (r4) the same on `global_load_lds_dwordx4`: 128 rows of a column per wave-instruction ---------------------------------
-// What the dword form cannot give is the REQUEST SIZE: 256 bytes per column and instruction, 70 000 column streams in flight on
-// the chip.  The streaming kernels of this library that reach 6 TB/s ask for 1 KB per column and instruction (accumulate_narrow:
-// 16-byte loads, 128-row tiles; its 512-byte variant was 25 % slower, profiles/r03_hbm_read_variants.txt), the ones that ask for
-// 512 bytes reach 5.2-5.4 (accumulate_quad up to p = 26), the ones that ask for 256 stay at 4.1-5.0 (this kernel's dword form,
-// accumulate_wide) — and a third block in flight did not help the dword form (ANOFOX_QUAD_RING=3: slower at every width), so
-// bytes in flight are not what is missing.  Here a block is 128 rows, ONE buffer (stride 136 = 8 mod 32 doubles per column: the
-// slice of a 34-column group is 37 KB, four wavefronts per CU): load the block, wait, run its eight 16-row steps, next block —
-// nothing overlaps inside a wavefront, the other three of the CU's wavefronts cover the wait.  The last rows of a group (fewer
-// than 128) come in 32-row pieces through the dword form, whose clamped lane offsets touch nothing behind the group.
-template <int NB>
-__device__ __forceinline__ bool quad_spec_dma_rows_x4(const WideArgs &args, int64_t lo, int64_t hi, double *rec, int lane, double *buf) {
-	constexpr int NPAIR = NB * (NB + 1) / 2;
-	constexpr int BR = 128;
-	constexpr int RS = quad_dma_stride(4);
-	const int p = args.p;
-	const int k = lane >> 4, b = (lane >> 2) & 3, c4 = lane & 3;
-	const int rsub = 4 * k + b;
-	const int base_off = c4 * RS + rsub;
-	const int c_last = 4 * (NB - 1) + c4;
-	const bool rd_last = c_last <= p;
-	const int last_off = (rd_last ? c_last : p) * RS + rsub;
-	const double fill_last = c_last == p + 1 ? 1.0 : 0.0;
-	const bool isx_prev = 4 * (NB - 2) + c4 < p, isx_last = c_last < p;
-	const unsigned lds0 = lds_dma_address(buf);
-	double acc[NPAIR];
-#pragma unroll
-	for (int t = 0; t < NPAIR; ++t) acc[t] = 0.0;
-	double first[NB], dmax[NB];
-#pragma unroll
-	for (int g = 0; g < NB; ++g) first[g] = dmax[g] = 0.0;
-	const lds_dma_table_t tab = lds_dma_table((unsigned)offsetof(WideArgs, x_table));
-	auto step = [&](int s, bool valid_all, unsigned rowmask) {
-		const long long rm = valid_all ? -1ll : -(long long)((rowmask >> rsub) & 1u);
-		double d[NB];
-#pragma unroll
-		for (int g = 0; g < NB; ++g) {
-			double v;
-			if (g < NB - 1) {
-				v = buf[base_off + 16 * s + 4 * g * RS];
-			} else {
-				const double raw = buf[last_off + 16 * s];
-				v = rd_last ? raw : fill_last;
-			}
-			double dev = v - first[g];
-			if (!valid_all) dev = quad_mask(dev, rm);
-			d[g] = dev;
-		}
-		int t = 0;
-#pragma unroll
-		for (int g = 0; g < NB; ++g) {
-#pragma unroll
-			for (int h = g; h < NB; ++h) {
-				acc[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(d[g], d[h], acc[t], 0, 0, 0);
-				++t;
-			}
-		}
-	};
-	auto fetch_first = [&]() { // the shift: the group's first row (the constants are not shifted)
-#pragma unroll
-		for (int g = 0; g < NB - 1; ++g) first[g] = buf[c4 * RS + 4 * g * RS];
-		first[NB - 1] = rd_last ? buf[(rd_last ? c_last : p) * RS] : 0.0;
-	};
-	int64_t blk = lo;
-	if (lo + BR <= hi) {
-		// full blocks; the first one is peeled for the shift (a branch around the matrix instructions inside the loop makes the
-		// compiler copy the accumulators at the join)
-		lds_dma_block<RS * 8, 4 * NB - 1, true>(tab, p + 1, blk, (unsigned)lane * 16u, lds0);
-		lds_dma_wait_all();
-		__builtin_amdgcn_wave_barrier();
-		fetch_first();
-#pragma unroll
-		for (int s = 0; s < BR / 16; ++s) step(s, true, 0xFFFFu);
-		__builtin_amdgcn_wave_barrier(); // the reads of this block before the DMA that overwrites it
-		for (blk += BR; blk + BR <= hi; blk += BR) {
-			lds_dma_block<RS * 8, 4 * NB - 1, true>(tab, p + 1, blk, (unsigned)lane * 16u, lds0);
-			lds_dma_wait_all();
-			__builtin_amdgcn_wave_barrier();
-#pragma unroll
-			for (int s = 0; s < BR / 16; ++s) step(s, true, 0xFFFFu);
-			__builtin_amdgcn_wave_barrier();
-		}
-	}
-	if (blk < hi) { // the last 1 .. 127 rows: 32-row pieces through the dword form
-		const int left = (int)(hi - blk);
-		for (int sub = 0; 32 * sub < left; ++sub)
-			lds_dma_block<RS * 8, 4 * NB - 1, false>(tab, p + 1, blk + 32 * sub, lds_dma_offsets(lane, hi - (blk + 32 * sub)), lds0 + (unsigned)sub * 256u);
-		lds_dma_wait_all();
-		__builtin_amdgcn_wave_barrier();
-		if (blk == lo) fetch_first();
-		for (int s = 0; 16 * s < left; ++s) {
-			const int rows = left - 16 * s;
-			step(s, false, rows >= 16 ? 0xFFFFu : (1u << (unsigned)rows) - 1u);
-		}
-	}
-	lds_dma_wait_all();
-	return quad_finish<NB, true>(args, rec, lane, buf, acc, first, dmax, isx_prev, isx_last, 0, lo, hi);
-}
-
-// ---- (r4) the fine ring: 16-row sub-blocks of EIGHT columns per `global_load_lds_dwordx4` -------------------------------------
-// What the 32-row ring above keeps in flight per wavefront is one block — half its slice — and never more than the 63 vector-memory
-// instructions a wavefront may have outstanding, 256 bytes each; with the slices of 36 .. 65 columns a CU holds six, then four
-// wavefronts, and blocks in flight / memory latency is what those widths run at (profiles/r04_widths_n1000.md: 16.1 MB on the chip at
-// p = 40 -> 4.2 TB/s, 13.4 MB at p = 50 -> 3.1 TB/s: 3.8-4.3 us either way).  Here eight lanes carry one column: an instruction moves
-// 16 rows x 8 columns = 1 KB, each lane with its own 64-bit address (column pointer of its group of eight, two rows per lane), a
-// sub-block is ceil((p + 1) / 8) instructions, and the slice is a ring of RING sub-blocks of which RING - 1 are in flight while one
-// is read: three quarters of the slice at RING = 4 instead of one half, in an eighth of the instructions.
-// LDS of a sub-block: chunk i (1 KB) = columns 8 i .. 8 i + 7, 128 bytes each (the hardware's M0 + 16 * lane), and inside a column
-// the row PAIR pr sits at position pr ^ 4 * ((column >> 1) & 1) — the lane picks its source rows accordingly — so that the 32 lanes
-// of a half-wave of the fragment read (ds_read_b64: 4 columns x 8 rows) touch every bank once.
-// (The instruction's immediate offset cannot carry the row step of consecutive sub-blocks: the hardware adds it to the LDS address
-// as well as to the source — the first version of this loader scattered its sub-blocks over the slice that way.)
-// The last 1 .. 15 rows of a group: a lane whose pair would end behind the group loads the pair (hi - 2, hi - 1) instead; the lanes
-// of the masked step that read row `left - 1` of an odd remainder find it in the second half of that pair.  (A group of one row
-// goes to the full version.)
-__host__ __device__ constexpr int quad_fine_chunks(int p) { return (p + 1 + 7) / 8; }
-__host__ __device__ constexpr int quad_fine_slice_doubles(int p, int ring) {
-	const int data = ring * quad_fine_chunks(p) * 128;
-	const int R = 4 * quad_blocks(p);
-	const int image = R * R + 2 * R;
-	return data > image ? data : image;
-}
-
-template <int OFF> // 16 bytes from each lane's own address (+ OFF) to dst + 16 * lane
-__device__ __forceinline__ void lds_dma_x4_lanes(const double *src, unsigned dst) {
-	unsigned keep;
-	asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off offset:%3\n\ts_mov_b32 m0, %0"
-	             : "=&s"(keep)
-	             : "v"(src), "s"(dst), "n"(OFF)
-	             : "memory");
-}
-
-template <int NI, int RING>
-__device__ __forceinline__ void quad_fine_wait(int younger) { // all but the `younger` most recent sub-blocks have landed (wave-uniform)
-	static_assert((RING - 1) * NI <= 63, "vmcnt");
-	switch (younger) {
-	case 0: lds_dma_wait_but<0>(); break;
-	case 1: lds_dma_wait_but<NI>(); break;
-	case 2: lds_dma_wait_but<(RING > 2 ? 2 : 0) * NI>(); break;
-	case 3: lds_dma_wait_but<(RING > 3 ? 3 : 0) * NI>(); break;
-	case 4: lds_dma_wait_but<(RING > 4 ? 4 : 0) * NI>(); break;
-	case 5: lds_dma_wait_but<(RING > 5 ? 5 : 0) * NI>(); break;
-	case 6: lds_dma_wait_but<(RING > 6 ? 6 : 0) * NI>(); break;
-	default: lds_dma_wait_but<(RING > 7 ? 7 : 0) * NI>(); break;
-	}
-}
-
-template <int NB, int RING>
-__device__ __forceinline__ bool quad_spec_fine_rows(const WideArgs &args, int64_t lo, int64_t hi, double *rec, int lane, double *buf) {
-	static_assert(RING >= 2 && RING <= 8, "ring depth");
-	constexpr int NPAIR = NB * (NB + 1) / 2;
-	constexpr int NIMAX = (4 * NB - 1 + 7) / 8; // chunks of the widest design with NB blocks; the narrowest has NIMAX or NIMAX - 1
-	if (hi - lo < 2) return false;
-	const int p = args.p;
-	const int ni = (p + 1 + 7) >> 3;
-	const int k = lane >> 4, b = (lane >> 2) & 3, c4 = lane & 3;
-	const int rsub = 4 * k + b;
-	// the fragment read of column 4 g + c4, row rsub of a sub-block: 64 g + rd_off doubles
-	const int rd_off = 16 * c4 + 2 * ((rsub >> 1) ^ (4 * (c4 >> 1))) + (rsub & 1);
-	const int c_last = 4 * (NB - 1) + c4;
-	const bool rd_last = c_last <= p;
-	const int cl = rd_last ? c_last : p;
-	const int last_off = (cl >> 3) * 128 + (cl & 7) * 16 + 2 * ((rsub >> 1) ^ (4 * ((cl >> 1) & 1))) + (rsub & 1);
-	const double fill_last = c_last == p + 1 ? 1.0 : 0.0;
-	const bool isx_prev = 4 * (NB - 2) + c4 < p, isx_last = c_last < p;
-	const unsigned lds0 = lds_dma_address(buf);
-	const unsigned sb_bytes = (unsigned)ni * 1024u;
-	double acc[NPAIR];
-#pragma unroll
-	for (int t = 0; t < NPAIR; ++t) acc[t] = 0.0;
-	double first[NB], dmax[NB];
-#pragma unroll
-	for (int g = 0; g < NB; ++g) first[g] = dmax[g] = 0.0;
-
-	// the lane's sources: column 8 i + (lane >> 3) (columns past y repeat y: the same addresses, no traffic), row pair `pr`
-	const int s8 = lane >> 3, pr = (lane & 7) ^ (4 * ((s8 >> 1) & 1));
-	const lds_dma_table_t tab = lds_dma_table((unsigned)offsetof(WideArgs, x_table)); // (y sits behind the last feature: host_api.hip)
-	const double *ptr[NIMAX];
-#pragma unroll
-	for (int i = 0; i < NIMAX; ++i) {
-		int c = 8 * i + s8;
-		c = c < p ? c : p;
-		ptr[i] = tab[c] + lo + 2 * pr;
-	}
-	const int64_t n = hi - lo;
-	const int nfull = (int)(n >> 4), left = (int)(n & 15), nsb = nfull + (left ? 1 : 0);
-	// (the remainder) doubles to step back so that the lane's pair ends inside the group
-	const int tail_back = 2 * pr + 1 >= left ? 2 * pr - (left - 2) : 0;
-
-	// sub-block `sub` into its slot; the lanes' pointers move on by 16 rows.  (The instruction's immediate offset cannot carry the
-	// row step: the hardware adds it to the LDS address as well.)
-	auto dma = [&](int sub) {
-		const unsigned dst = lds0 + (unsigned)(sub % RING) * sb_bytes;
-		if (sub >= nfull) { // (wave-uniform) the remainder
-#pragma unroll
-			for (int i = 0; i < NIMAX; ++i)
-				if (i < ni) lds_dma_x4_lanes<0>(ptr[i] - tail_back, dst + (unsigned)i * 1024u);
-			return;
-		}
-#pragma unroll
-		for (int i = 0; i < NIMAX; ++i) {
-			if (i < ni) lds_dma_x4_lanes<0>(ptr[i], dst + (unsigned)i * 1024u);
-			ptr[i] += 16;
-		}
-	};
-	auto wait = [&](int younger) {
-		if (ni == NIMAX) quad_fine_wait<NIMAX, RING>(younger);
-		else quad_fine_wait<(NIMAX > 1 ? NIMAX - 1 : 1), RING>(younger);
-	};
-	auto step = [&](const double *hb, bool valid_all, long long rm, int fix) {
-		double d[NB];
-#pragma unroll
-		for (int g = 0; g < NB; ++g) {
-			double v;
-			if (g < NB - 1) {
-				v = hb[64 * g + rd_off + fix];
-			} else {
-				const double raw = hb[last_off + fix];
-				v = rd_last ? raw : fill_last;
-			}
-			double dev = v - first[g];
-			if (!valid_all) dev = quad_mask(dev, rm);
-			d[g] = dev;
-		}
-		int t = 0;
-#pragma unroll
-		for (int g = 0; g < NB; ++g) {
-#pragma unroll
-			for (int h = g; h < NB; ++h) {
-				acc[t] = __builtin_amdgcn_mfma_f64_4x4x4f64(d[g], d[h], acc[t], 0, 0, 0);
-				++t;
-			}
-		}
-	};
-
-	int issued = 0;
-	for (; issued < RING - 1 && issued < nsb; ++issued) dma(issued);
-	wait(issued - 1);
-	__builtin_amdgcn_wave_barrier();
-	{ // the shift: the group's first row (the constants are not shifted)
-		const int f_off = 16 * c4 + 2 * (4 * (c4 >> 1));
-#pragma unroll
-		for (int g = 0; g < NB - 1; ++g) first[g] = buf[64 * g + f_off];
-		first[NB - 1] = rd_last ? buf[(cl >> 3) * 128 + (cl & 7) * 16 + 2 * (4 * ((cl >> 1) & 1))] : 0.0;
-	}
-	for (int j = 0; j < nfull; ++j) {
-		if (issued < nsb) { // (the slot read in the trip before this one)
-			dma(issued);
-			++issued;
-		}
-		wait(issued - 1 - j);
-		__builtin_amdgcn_wave_barrier();
-		step(buf + (size_t)(j % RING) * (size_t)(ni * 128), true, -1ll, 0);
-		__builtin_amdgcn_wave_barrier(); // the reads of this slot before the DMA that refills it
-	}
-	if (left) {
-		lds_dma_wait_all();
-		__builtin_amdgcn_wave_barrier();
-		const long long rm = rsub < left ? -1ll : 0ll;
-		const int fix = ((left & 1) && rsub == left - 1) ? 1 : 0;
-		step(buf + (size_t)(nfull % RING) * (size_t)(ni * 128), false, rm, fix);
-	}
-	lds_dma_wait_all();
-	__builtin_amdgcn_wave_barrier();
 	return quad_finish<NB, true>(args, rec, lane, buf, acc, first, dmax, isx_prev, isx_last, 0, lo, hi);
 }
 
@@ -772,20 +470,10 @@ __global__ __launch_bounds__(256, WPS) void accumulate_quad_kernel(WideArgs args
 		if (wide_register_big_group(args, gl, lo, hi, T, lane, T <= 2 ? kSegMaxBig : kWideSegMaxBig, T <= 2 ? kSegMaxSegments : kWideSegMaxSegments)) return;
 	}
 	double *rec = args.moments + gl * (int64_t)wide_record_len(T);
-	if constexpr (MODE == 4) { // the speculative version on the fine LDS-DMA ring (the template's RL parameter is the ring depth)
-		double *slice = quad_lds + (threadIdx.x >> 6) * quad_fine_slice_doubles(args.p, RL);
-		if (hi > lo && quad_spec_fine_rows<NB, RL>(args, lo, hi, rec, lane, slice)) return;
-		if (lane == 0) args.refine_list[atomicAdd(args.refine_count + kWideRedoCounter, 1)] = (int32_t)gl;
-		return;
-	}
 	if constexpr (MODE == 3) { // the speculative version on LDS-DMA (its own slice size)
-		// (MODE 3: the template's RL parameter is the ring depth)
-		double *slice = quad_lds + (threadIdx.x >> 6) * quad_dma_slice_doubles(args.p, RL);
-		if constexpr (RL == 4) { // (128-row blocks on the dwordx4 form)
-			if (hi > lo && quad_spec_dma_rows_x4<NB>(args, lo, hi, rec, lane, slice)) return;
-		} else {
-			if (hi > lo && quad_spec_dma_rows<NB, RL>(args, lo, hi, rec, lane, slice)) return;
-		}
+		static_assert(RL == kQuadRing, "MODE 3: the template's RL parameter is the ring depth");
+		double *slice = quad_lds + (threadIdx.x >> 6) * quad_dma_slice_doubles(args.p, kQuadRing);
+		if (hi > lo && quad_spec_dma_rows<NB>(args, lo, hi, rec, lane, slice)) return;
 		if (lane == 0) args.refine_list[atomicAdd(args.refine_count + kWideRedoCounter, 1)] = (int32_t)gl;
 		return;
 	}
@@ -815,7 +503,7 @@ hipError_t launch_quad_nb(const WideArgs &a, hipStream_t stream) {
 	(void)attr_set;
 	// the unweighted fit with an intercept first runs the speculative kernel, then the full version on what it listed (the
 	// counter is zeroed by the caller; ANOFOX_WIDE_FAST=0 / ANOFOX_QUAD_SPEC=0: the full version only)
-	static const bool spec_on = !(getenv("ANOFOX_QUAD_SPEC") && atoi(getenv("ANOFOX_QUAD_SPEC")) == 0);
+	static const bool spec_on = env_on("ANOFOX_QUAD_SPEC");
 	// (NB = 3, 4 — p = 9 .. 14 — stay with the full version: measured 2-5 % faster there on two boxes, profiles/r04_widths_n1000.txt,
 	// r04_final_widths_n1000.txt; the speculative one pays a second launch and wins only from p = 15 on)
 	const bool spec = spec_on && !a.no_fast_path && !weighted && center && NB >= 5;
@@ -838,12 +526,12 @@ hipError_t launch_quad_nb(const WideArgs &a, hipStream_t stream) {
 // NB = 8, 9 (p = 27 .. 34): only the speculative kernel exists here (the full version's registers do not fit two waves per
 // SIMD, see below); its give-ups go to accumulate_mid (p <= 32) or accumulate_wide (p = 33, 34: three column tiles, whose
 // segment table also takes this kernel's very large groups).
-template <int NB, int WPS, int RING>
+template <int NB, int WPS>
 hipError_t launch_quad_spec_only(const WideArgs &a, hipStream_t stream) {
-	constexpr int RL = RING;
-	// eight wavefronts per CU while their slices fit its 160 KB of LDS (RING = 2, p <= 34: 35 columns x 576 bytes x 8 = 161 280
+	constexpr int RL = kQuadRing; // (the kernel's RL parameter in MODE 3: the ring depth)
+	// eight wavefronts per CU while their slices fit its 160 KB of LDS (p <= 34: 35 columns x 576 bytes x 8 = 161 280
 	// bytes) in workgroups of four; beyond, the workgroup size that leaves the fewest bytes of the CU's LDS unused
-	const size_t slice_bytes = (size_t)quad_dma_slice_doubles(a.p, RING) * sizeof(double);
+	const size_t slice_bytes = (size_t)quad_dma_slice_doubles(a.p, kQuadRing) * sizeof(double);
 	const int fit = (int)(((size_t)160 * 1024) / slice_bytes);
 	const int waves = fit >= 8 ? 4 : (fit % 2 == 0 ? 2 : 1);
 	const dim3 grid((unsigned)((a.n_groups + waves - 1) / waves)), block(64 * waves);
@@ -863,48 +551,6 @@ hipError_t launch_quad_spec_only(const WideArgs &a, hipStream_t stream) {
 	return launch_accumulate_wide_followup(a, stream);
 }
 
-// the fine ring (measurement switch ANOFOX_QUAD_FINE=3 | 4 = ring depth; OFF by default): NB = 8 .. 17, p = 27 .. 64.
-// Measured on one box (scripts/quad_fine_ab.sh, 100 000 / 50 000 groups x 1000 rows, TB/s of the kernel, default | ring 4 | ring 3):
-//   p = 33: 4.08 | 3.63 | 3.68      p = 40: 3.79 | 3.71 | 3.82      p = 50: 3.13 | 2.35 | 2.51      p = 64 (accumulate_wide<4>): 3.24 | 2.10 | 2.11
-// Correct (the GPU suite passes with it on), and slower at every width although it keeps half as much again in flight per wavefront
-// in an eighth of the instructions — so neither the bytes in flight per wavefront nor the instruction count is what holds these
-// widths.  (The contiguous run per column and request halves to 128 bytes here; that is not it either: accumulate_wide staged with
-// 256-byte instead of 128-byte runs measures the same, profiles/r04_wide_run256_ab.txt.)  NB >= 15 also spill here (20-296 bytes:
-// 512 registers hold 120-153 accumulators and little else).
-template <int NB, int WPS, int RING>
-hipError_t launch_quad_spec_fine(const WideArgs &a, hipStream_t stream) {
-	const size_t slice_bytes = (size_t)quad_fine_slice_doubles(a.p, RING) * sizeof(double);
-	int fit = (int)(((size_t)160 * 1024) / slice_bytes);
-	if (fit > 4 * WPS) fit = 4 * WPS;
-	const int waves = fit >= 8 ? 4 : (fit % 4 == 0 ? 4 : (fit % 2 == 0 ? 2 : 1));
-	const dim3 grid((unsigned)((a.n_groups + waves - 1) / waves)), block(64 * waves);
-	const size_t lds_bytes = (size_t)waves * slice_bytes;
-	static const bool attr_set = [] {
-		(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&accumulate_quad_kernel<NB, false, true, RING, WPS, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		return true;
-	}();
-	(void)attr_set;
-	hipLaunchKernelGGL((accumulate_quad_kernel<NB, false, true, RING, WPS, 4>), grid, block, lds_bytes, stream, a);
-	hipError_t rc = hipGetLastError();
-	if (rc != hipSuccess) return rc;
-	if (wide_tiles(a.p) <= 2) {
-		if (a.seg_table && (rc = launch_accumulate_mid_segments(a, stream)) != hipSuccess) return rc;
-		return launch_accumulate_mid_redo(a, stream);
-	}
-	return launch_accumulate_wide_followup(a, stream);
-}
-
-template <int NB, int WPS>
-hipError_t launch_quad_spec_fine_ring(const WideArgs &a, int ring, hipStream_t stream) {
-	if (ring == 3) return launch_quad_spec_fine<NB, WPS, 3>(a, stream);
-	return launch_quad_spec_fine<NB, WPS, 4>(a, stream);
-}
-
-int quad_fine_ring() {
-	static const int ring = getenv("ANOFOX_QUAD_FINE") ? atoi(getenv("ANOFOX_QUAD_FINE")) : 0;
-	return ring;
-}
-
 } // namespace
 
 // The full version at p = 27 .. 32 (NB = 8, 9) stays with accumulate_mid: 36 / 45 accumulators + the staged block + the running
@@ -915,14 +561,13 @@ int quad_fine_ring() {
 // per SIMD: no spills, 3.5-4.0 TB/s.  profiles/r03_quad.txt.)  (r4) The SPECULATIVE version needs neither the maxima nor the
 // masks and takes p = 27 .. 34 for the unweighted fit with an intercept.
 bool accumulate_quad_supports(int p, bool weighted, bool center, bool no_fast_path) {
-	static const bool spec_on = !(getenv("ANOFOX_QUAD_SPEC") && atoi(getenv("ANOFOX_QUAD_SPEC")) == 0);
+	static const bool spec_on = env_on("ANOFOX_QUAD_SPEC");
 	// (NB = 10, 11: p = 35 .. 42 — 55 / 66 accumulators, six wavefronts per CU; measured against accumulate_wide in docs/MEASUREMENTS.md)
 	// (r4, NB = 12, 13: 224 / 252 registers, no scratch.  Against accumulate_wide on one box, scripts/quad50_ab.sh: level at p = 43, 44,
 	// 6-10 % behind at p = 46, 48 (three column tiles are well filled there), 10 % ahead at p = 49, 50 — where four column tiles pad 51
 	// columns to 64: 160 matrix cycles per row against 91.  So: up to 42, and 49, 50.  ANOFOX_QUAD_SPEC_MAXP=50 takes 43 .. 48 as well.)
-	static const int spec_max_p = getenv("ANOFOX_QUAD_SPEC_MAXP") ? atoi(getenv("ANOFOX_QUAD_SPEC_MAXP")) : 0;
+	static const int spec_max_p = env_int("ANOFOX_QUAD_SPEC_MAXP", 0);
 	if (p > kNarrowMaxP && p <= 26) return true;
-	if (quad_fine_ring() > 0 && p > 26 && p <= 64) return spec_on && !weighted && center && !no_fast_path;
 	const bool in_range = spec_max_p > 0 ? p <= spec_max_p : (p <= 42 || p == 49 || p == 50);
 	return p > 26 && p <= 50 && in_range && spec_on && !weighted && center && !no_fast_path;
 }
@@ -933,38 +578,22 @@ hipError_t launch_accumulate_quad(const WideArgs &a, hipStream_t stream) {
 	// rows per lane and block, by measurement (profiles/r03_quad.txt): 128-row blocks for p <= 11 and p = 15..17, 64-row
 	// blocks elsewhere (from p = 18 the larger slice would leave one workgroup per CU).  A register budget for three waves
 	// per SIMD was measured slower for every NB >= 4 (spills).  ANOFOX_QUAD_RL=1/2 forces one.
-	static const int env_rl = getenv("ANOFOX_QUAD_RL") ? atoi(getenv("ANOFOX_QUAD_RL")) : 0;
+	static const int env_rl = env_int("ANOFOX_QUAD_RL", 0);
 	const int nb = quad_blocks(a.p);
-	static const int ring = getenv("ANOFOX_QUAD_RING") ? atoi(getenv("ANOFOX_QUAD_RING")) : 2; // (measurement switch: 3 = three 32-row blocks, 4 = 128-row blocks on dwordx4)
 	int rl = (a.p <= 11 || (a.p >= 15 && a.p <= 17)) ? 2 : 1;
 	if (env_rl == 1 || (env_rl == 2 && a.p <= 18)) rl = env_rl;
-	if (const int fine = quad_fine_ring(); fine > 0 && nb >= 8) {
-		switch (nb) {
-		case 8: return launch_quad_spec_fine_ring<8, 2>(a, fine, stream);
-		case 9: return launch_quad_spec_fine_ring<9, 2>(a, fine, stream);
-		case 10: return launch_quad_spec_fine_ring<10, 2>(a, fine, stream);
-		case 11: return launch_quad_spec_fine_ring<11, 2>(a, fine, stream);
-		case 12: return launch_quad_spec_fine_ring<12, 2>(a, fine, stream);
-		case 13: return launch_quad_spec_fine_ring<13, 2>(a, fine, stream);
-		case 14: return launch_quad_spec_fine_ring<14, 1>(a, fine, stream);
-		case 15: return launch_quad_spec_fine_ring<15, 1>(a, fine, stream);
-		case 16: return launch_quad_spec_fine_ring<16, 1>(a, fine, stream);
-		case 17: return launch_quad_spec_fine_ring<17, 1>(a, fine, stream);
-		default: return hipErrorInvalidValue;
-		}
-	}
 	switch (nb) { // p = 9, 10 | 11..14 | 15..18 | 19..22 | 23..26 | 27..30 | 31..34
 	case 3: return rl == 2 ? launch_quad_nb<3, 2, 3>(a, stream) : launch_quad_nb<3, 1, 3>(a, stream);
 	case 4: return rl == 2 ? launch_quad_nb<4, 2, 2>(a, stream) : launch_quad_nb<4, 1, 2>(a, stream);
 	case 5: return rl == 2 ? launch_quad_nb<5, 2, 2>(a, stream) : launch_quad_nb<5, 1, 2>(a, stream);
 	case 6: return launch_quad_nb<6, 1, 2>(a, stream);
 	case 7: return launch_quad_nb<7, 1, 2>(a, stream);
-	case 8: return ring == 4 ? launch_quad_spec_only<8, 2, 4>(a, stream) : ring == 3 ? launch_quad_spec_only<8, 2, 3>(a, stream) : launch_quad_spec_only<8, 2, 2>(a, stream);
-	case 9: return ring == 4 ? launch_quad_spec_only<9, 2, 4>(a, stream) : ring == 3 ? launch_quad_spec_only<9, 2, 3>(a, stream) : launch_quad_spec_only<9, 2, 2>(a, stream);
-	case 10: return ring == 4 ? launch_quad_spec_only<10, 2, 4>(a, stream) : ring == 3 ? launch_quad_spec_only<10, 2, 3>(a, stream) : launch_quad_spec_only<10, 2, 2>(a, stream);
-	case 11: return ring == 4 ? launch_quad_spec_only<11, 2, 4>(a, stream) : ring == 3 ? launch_quad_spec_only<11, 2, 3>(a, stream) : launch_quad_spec_only<11, 2, 2>(a, stream);
-	case 12: return launch_quad_spec_only<12, 2, 2>(a, stream);
-	case 13: return launch_quad_spec_only<13, 2, 2>(a, stream);
+	case 8: return launch_quad_spec_only<8, 2>(a, stream);
+	case 9: return launch_quad_spec_only<9, 2>(a, stream);
+	case 10: return launch_quad_spec_only<10, 2>(a, stream);
+	case 11: return launch_quad_spec_only<11, 2>(a, stream);
+	case 12: return launch_quad_spec_only<12, 2>(a, stream);
+	case 13: return launch_quad_spec_only<13, 2>(a, stream);
 	default: return hipErrorInvalidValue;
 	}
 }

@@ -26,11 +26,9 @@
 // Roofline: FP64 MFMA (matrix-core) bound for p >= ~48: 2*256*4 flop per instruction, T(T+1)/2 instructions
 // per 4 rows; HBM traffic 8(p+1) B per row is read once.
 #pragma once
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
-#include "lds_dma.h"
 
 namespace anofox {
 
@@ -119,15 +117,11 @@ struct WideCfg {
 	// every chunk ends in a barrier, so the workgroup runs at the pace of the two-tile wavefronts; wavefront w of every workgroup
 	// sits on SIMD w, so SIMDs 0 and 1 carry twice the matrix work of SIMDs 2 and 3 (the 60-65 % "matrix pipe busy" of the
 	// round-4 counters is the average of 85 % and 42 %).  Neither a lighter staging side nor LDS-DMA changes that (measured:
-	// ANOFOX_WIDE_DMA=1, -3 %).  So: the first 4 F = 4 floor(NT / 4) tiles go round-robin as before, and the R = NT mod 4 that
+	// -3 %, docs/HISTORY.md).  So: the first 4 F = 4 floor(NT / 4) tiles go round-robin as before, and the R = NT mod 4 that
 	// are left are SPLIT ALONG THE ROWS — a tile in halves between two wavefronts (even / odd slabs of every chunk), or in
 	// quarters between all four — each wavefront keeping a partial sum that the tile's owner collects once, at the end of the
 	// group.  Busiest wavefront per chunk: T = 3: 2 -> 1.5 tiles, T = 4: 3 -> 2.5, T = 5: 4 -> 3.75, T = 6: 6 -> 5.25 (T = 7, 8: R = 0).
-#ifdef ANOFOX_WIDE_NOSPLIT // (measurement build: the round-robin deal of rounds 1-3, csrc/Makefile target `nosplit`)
-	static constexpr bool kSplit = false;
-#else
-	static constexpr bool kSplit = kWaves == 4;
-#endif
+	static constexpr bool kSplit = kWaves == 4; // (8 wavefronts: the round-robin deal of rounds 1-3)
 	static constexpr int F = kSplit ? NT / 4 : 0, R = kSplit ? NT % 4 : 0;
 	static constexpr int TPW = kSplit ? F + (R > 0 ? 1 : 0) + (R == 3 ? 1 : 0) : (NT + kWaves - 1) / kWaves; // accumulator tiles per wave
 	// remaining tile j = tile - 4 F: split in halves between wavefronts 2 j, 2 j + 1 (R = 2; R = 3: j < 2) or in quarters (R = 1; R = 3: j = 2)
@@ -151,32 +145,13 @@ struct WideCfg {
 	// matrix work; with the loads of chunk c + 1 issued behind the first slab of chunk c and needed behind its last slabs, they have
 	// less than that to cross the memory system — a wavefront then waits on them in every chunk.  The staging registers of such a
 	// chunk are few (16-24 per lane), so narrow designs keep two chunks in flight; from 5 tiles on a chunk is long enough.
-	// Measured on one box (scripts/wide_depth_ab.sh, builds of `make variant`), kernel ms at 50 000 x 1000 x p = 48 / 56 / 64:
+	// Measured on one box, kernel ms at 50 000 x 1000 x p = 48 / 56 / 64:
 	// rounds 1-3 (round-robin deal, one chunk ahead) 5.59 / 7.81 / 8.43; split tiles 5.43 / 7.60 / 8.45; + two chunks ahead
 	// 5.50 / 7.52 / 8.13; three 5.41 / 7.92 / 8.51; four 5.47 / 8.01 / 8.61 (registers).  Two it is: +2 ... 4 %, not the
 	// +20 ... 33 % the arithmetic of the tile deal promised — the chunk takes its ~4 us whatever is done to its parts.
 	// (The speculative version only: the full one — row masks, repairs, weights — has no registers to spare: 224-476 bytes of
 	// scratch per lane with three chunks in flight.)
-#ifndef ANOFOX_WIDE_DEPTH
-#define ANOFOX_WIDE_DEPTH(T) ((T) <= 4 ? 2 : 1)
-#endif
-#ifndef ANOFOX_WIDE_RUN256
-#define ANOFOX_WIDE_RUN256(T) 0
-#endif
-// (r4) the ends of a group in the speculative version with two chunks of loads in flight (ANOFOX_WIDE_TAIL2=0: as before; see kTail2)
-#ifndef ANOFOX_WIDE_TAIL2
-#define ANOFOX_WIDE_TAIL2 0
-#endif
-#ifndef ANOFOX_WIDE_STAGGER
-#define ANOFOX_WIDE_STAGGER 0
-#endif
-// what-if builds of the speculative version's steady state (never shipped: the results are wrong; `make variant`): bit 0 = one v_fma_f64
-// in place of every matrix instruction, 1 = no global loads (the staging registers keep the first chunk), 2 = no barrier per chunk,
-// 3 = the fragments of a chunk's first slab are used for all of its slabs (one eighth of the LDS reads), 4 = the staged chunk is not written to LDS
-#ifndef ANOFOX_WIDE_SKIP
-#define ANOFOX_WIDE_SKIP 0
-#endif
-	static constexpr int depth(bool fast) { return kWaves == 4 && fast ? ANOFOX_WIDE_DEPTH(T) : 1; }
+	static constexpr int depth(bool fast) { return kWaves == 4 && fast ? (T <= 4 ? 2 : 1) : 1; }
 	static constexpr int chunk_rows(bool weighted, bool center = true) { return ANOFOX_WIDE_SHORT_CHUNK(T, weighted, center) ? 16 : 32; }
 	static constexpr int stride(bool weighted, bool center = true) { return chunk_rows(weighted, center) + 2; } // doubles per column in the LDS image (+2 pad: conflict-free b64 reads)
 };
@@ -190,15 +165,12 @@ struct WideCfg {
 // the four waves.)
 // `between(t)` is called once per slab, after the slab's MFMAs: the staging work of the NEXT chunk is dealt over the
 // slabs of this one (iteration() below), so that a wave has no phase without MFMAs in flight.
-// RAW ((r4) the LDS-DMA staging of the speculative version): the image holds the rows as they lie in memory and the shift by the
-// group's first row (`fsub` per column block of this lane, `fy`) is applied to the fragment on its way to the matrix cores.
-template <int T, int WAVE, bool WEIGHTED, bool CENTER, bool FAST, bool RAW = false, int CH = 0, typename Between>
+template <int T, int WAVE, bool WEIGHTED, bool CENTER, bool FAST, typename Between>
 __device__ __forceinline__ void compute_chunk(const double *img, const double *firstcol, int ycol, int lane, unsigned rowmask,
                                               dbl4 (&acc)[WideCfg<T>::TPW], double (&sx)[WideCfg<T>::OWN],
                                               double (&sxy)[WideCfg<T>::OWN], double (&dmax)[WideCfg<T>::OWN], unsigned &ncmask,
-                                              double &sy, double &syy, double &sw, Between &&between, const double *fsub = nullptr, double fy = 0.0) {
-	// (CH: rows per chunk when the caller's image is not the configuration's — the 64-row chunks of the LDS-DMA staging)
-	constexpr int kChunkRows = CH ? CH : WideCfg<T>::chunk_rows(WEIGHTED, CENTER), kLdsStride = CH ? CH + 2 : WideCfg<T>::stride(WEIGHTED, CENTER), OWN = WideCfg<T>::OWN;
+                                              double &sy, double &syy, double &sw, Between &&between) {
+	constexpr int kChunkRows = WideCfg<T>::chunk_rows(WEIGHTED, CENTER), kLdsStride = WideCfg<T>::stride(WEIGHTED, CENTER), OWN = WideCfg<T>::OWN;
 	const int k = lane >> 4;
 	const int i = lane & 15;
 	// without an intercept the image holds raw values; the constant-column test still compares with the first valid row
@@ -215,8 +187,8 @@ __device__ __forceinline__ void compute_chunk(const double *img, const double *f
 	auto read_slab = [&](int t, int s) {
 		const int row = 4 * t + k;
 #pragma unroll
-		for (int I = 0; I < T; ++I) d[s][I] = RAW ? img[(16 * I + i) * kLdsStride + row] - fsub[I] : img[(16 * I + i) * kLdsStride + row];
-		dy[s] = RAW ? img[ycol * kLdsStride + row] - fy : img[ycol * kLdsStride + row];
+		for (int I = 0; I < T; ++I) d[s][I] = img[(16 * I + i) * kLdsStride + row];
+		dy[s] = img[ycol * kLdsStride + row];
 		w[s] = WEIGHTED ? img[(ycol + 1) * kLdsStride + row] : 1.0;
 	};
 	read_slab(0, 0);
@@ -224,16 +196,6 @@ __device__ __forceinline__ void compute_chunk(const double *img, const double *f
 	for (int t = 0; t < NS; ++t) {
 		const int s = t & 1;
 		const int row = 4 * t + k;
-#if ANOFOX_WIDE_SKIP & 8
-		if (FAST) {
-			if (t + 1 < NS) {
-#pragma unroll
-				for (int I = 0; I < T; ++I) d[s ^ 1][I] = d[s][I];
-				dy[s ^ 1] = dy[s];
-				w[s ^ 1] = w[s];
-			}
-		} else
-#endif
 		if (t + 1 < NS) read_slab(t + 1, s ^ 1);
 		double a[T];
 #pragma unroll
@@ -244,13 +206,8 @@ __device__ __forceinline__ void compute_chunk(const double *img, const double *f
 		for (int I = 0; I < T; ++I) {
 #pragma unroll
 			for (int J = I; J < T; ++J) {
-				if (WideCfg<T>::works(tile, WAVE, t)) {
-#if ANOFOX_WIDE_SKIP & 1
-					if (FAST) acc[WideCfg<T>::acc_index(tile)][0] = fma(a[I], d[s][J], acc[WideCfg<T>::acc_index(tile)][0]);
-					else
-#endif
+				if (WideCfg<T>::works(tile, WAVE, t))
 					acc[WideCfg<T>::acc_index(tile)] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[I], d[s][J], acc[WideCfg<T>::acc_index(tile)], 0, 0, 0);
-				}
 				++tile;
 			}
 		}
@@ -301,27 +258,13 @@ __device__ __forceinline__ void compute_chunk(const double *img, const double *f
 // constant (|x - x_first| < 1e-10 on every row, ols.rs:76-87) if sum d^2 < 1e-20 and not constant if
 // sum d^2 >= n 1e-20.  Anything else — a NaN / inf somewhere, a column in between — returns false, and the caller
 // runs the full version on the group.  Returns true when the record at `rec` is complete.
-template <int T, int WAVE, bool WEIGHTED, bool CENTER, bool FAST = false, int DMA = 0> // DMA: rows per chunk of the LDS-DMA staging (0: registers)
+template <int T, int WAVE, bool WEIGHTED, bool CENTER, bool FAST = false>
 __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, int64_t lo, int64_t hi, double *rec,
                                                           const double *forced_first) {
 	static_assert(!FAST || (!WEIGHTED && CENTER), "the speculative version exists for the unweighted fit with an intercept");
-	static_assert(DMA == 0 || FAST, "the LDS-DMA staging exists for the speculative version");
 	using Cfg = WideCfg<T>;
-	constexpr int kChunkRows = DMA ? DMA : Cfg::chunk_rows(WEIGHTED, CENTER), kLdsStride = DMA ? DMA + 2 : Cfg::stride(WEIGHTED, CENTER);
+	constexpr int kChunkRows = Cfg::chunk_rows(WEIGHTED, CENTER), kLdsStride = Cfg::stride(WEIGHTED, CENTER);
 	constexpr bool kWideChunk = kChunkRows == 32;
-	// (r4) kRun: the speculative version's lanes stage 32 rows of FOUR columns per load instruction (16 lanes x 16 bytes = a run of 256
-	// bytes per column and request) instead of 16 rows of eight columns (128 bytes): registers `a` of a slot hold its first four columns,
-	// `b` its last four, both the same 32 rows.  (The full version keeps the 16-row classes its row masks are built from.)
-	constexpr bool kRun = FAST && DMA == 0 && kWideChunk && ANOFOX_WIDE_RUN256(T);
-	// (r4) kTail2 (measurement build -DANOFOX_WIDE_TAIL2=1; OFF).  A load takes ~9 000 cycles to come back on the loaded chip and a chunk of
-	// 3-4 column tiles ~3 500 (milestones of a group's life, profiles/r04_wide_group_life.md): at 1000 rows per group a quarter of a
-	// workgroup's life goes into its two ends — 9 500 cycles for the first row (the shift) before chunk 0 is even asked for, and ~7 800
-	// per chunk in the last four chunks, which the generic iteration loads ONE chunk ahead into the registers it has just stored.  With
-	// kTail2 chunks 0 and 1 are requested first and the shift is taken from chunk 0's registers (the lane that holds row 0 of the
-	// column), and the last chunks alternate between the two register sets of the steady state.  Correct (GPU suite), and NOT faster:
-	// T = 3 level, T = 4 3-4 % slower (scripts/wide_tail_ab.sh) — a workgroup's idle ends are filled by the CU's other workgroups
-	// already; the CU is bound by what its SIMDs issue (matrix + vector instructions add up to ~88 % of the steady chunk).
-	constexpr bool kTail2 = FAST && DMA == 0 && Cfg::depth(FAST) == 2 && ANOFOX_WIDE_TAIL2;
 	constexpr unsigned kFullMask = kWideChunk ? 0xffffffffu : 0xffffu;
 	constexpr int P16 = 16 * T;
 	const int p = args.p;
@@ -365,13 +308,11 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 	// with the pointers parked in LDS every load of a chunk waited for its own ds_read round trip, ~1000 cycles per
 	// chunk of pure latency (phase stamps, scripts/dbg_acc_stamps.py).
 	constexpr int kMaxLoads = (P16 + 2 + 7) / 8 / kWaves + 1;
-	const int colsub = kRun ? lane >> 4 : lane >> 3;
-	const int rp = kRun ? lane & 15 : lane & 7;
+	const int colsub = lane >> 3;
+	const int rp = lane & 7;
 	const int n_loads_total = (ncol + 7) / 8; // load slots: 8 source columns each
 	gptr_t colp[kMaxLoads]; // this lane's column of slot q, at the group's first row + 2 rp
 	int dcol[kMaxLoads];    // element offset of (image column, row 2 rp) within an image
-	gptr_t colpB[kRun ? kMaxLoads : 1]; // (kRun) the same for the lane's column of the slot's second half
-	int dcolB[kRun ? kMaxLoads : 1];
 	unsigned actbits = 0;   // bit q: the column exists (slots beyond ncol read y again and store into a spare column)
 	unsigned wbits = 0;     // bit q: the column is the weight column
 #pragma unroll
@@ -382,13 +323,6 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 		if (!active) col = ycol + 2 + (colsub % 6); // spare columns 16T+2 .. 16T+7: nothing reads them
 		dcol[q] = col * kLdsStride + 2 * rp;
 		colp[q] = reinterpret_cast<gptr_t>(colbase[src < ncol_pad ? src : ncol_pad - 1]) + 2 * rp;
-		if constexpr (kRun) {
-			const int srcB = src + 4;
-			int colB = srcB < p ? srcB : ycol + (srcB - p);
-			if (srcB >= ncol) colB = ycol + 2 + ((colsub + 4) % 6);
-			dcolB[q] = colB * kLdsStride + 2 * rp;
-			colpB[q] = reinterpret_cast<gptr_t>(colbase[srcB < ncol_pad ? srcB : ncol_pad - 1]) + 2 * rp;
-		}
 		actbits |= active ? (1u << q) : 0u;
 		wbits |= (WEIGHTED && src == p + 1) ? (1u << q) : 0u;
 	}
@@ -406,9 +340,6 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 	// the shift the staging side applies to the columns THIS lane stages (0 until the first valid row is known, 0 for
 	// the weight column and when there is no intercept)
 	double fq[kMaxLoads];
-	double fqB[kRun ? kMaxLoads : 1]; // (kRun: forced_first does not come with the speculative version)
-#pragma unroll
-	for (int q = 0; q < (kRun ? kMaxLoads : 1); ++q) fqB[q] = 0.0;
 #pragma unroll
 	for (int q = 0; q < kMaxLoads; ++q) {
 		fq[q] = 0.0;
@@ -416,7 +347,7 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 		if (CENTER && forced_first && src <= p) fq[q] = src < p ? forced_first[src] : forced_first[P16];
 	}
 
-	if (FAST && DMA == 0 && !kTail2) { // the shift is the group's first row (nrows > 0: the caller's condition)
+	if (FAST) { // the shift is the group's first row (nrows > 0: the caller's condition)
 #pragma unroll
 		for (int q = 0; q < kMaxLoads; ++q) {
 			const int src = 8 * (wave + kWaves * q) + colsub;
@@ -424,14 +355,6 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 				const double f = colp[q][-2 * rp];
 				fq[q] = f;
 				if (rp == 0) firstcol[src < p ? src : ycol] = f;
-			}
-			if constexpr (kRun) {
-				const int srcB = src + 4;
-				if (wave + kWaves * q < n_loads_total && srcB <= p) {
-					const double f = colpB[q][-2 * rp];
-					fqB[q] = f;
-					if (rp == 0) firstcol[srcB < p ? srcB : ycol] = f;
-				}
 			}
 		}
 		have_first = true;
@@ -441,8 +364,6 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 	// for the loop's own loads)
 #pragma unroll
 	for (int q = 0; q < kMaxLoads; ++q) asm volatile("" : "+v"(fq[q]));
-#pragma unroll
-	for (int q = 0; q < (kRun ? kMaxLoads : 0); ++q) asm volatile("" : "+v"(fqB[q]));
 	ACC_MARK(1);
 	const int64_t n_chunks = (nrows + kChunkRows - 1) / kChunkRows;
 	// staging registers of one chunk: rows 2 rp, 2 rp + 1 (v0, v1) and 16 + 2 rp, 17 + 2 rp (v2, v3) of this lane's columns
@@ -458,17 +379,7 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 			sg.b[q] = (dbl2u){0.0, 0.0};
 			if (wave + kWaves * q < n_loads_total) { // wave-uniform
 				const gptr_t b = colp[q] + c0;
-				if constexpr (kRun) {
-					const gptr_t b2 = colpB[q] + c0;
-					if (full) {
-						sg.a[q] = *reinterpret_cast<gptr2_t>(b);
-						sg.b[q] = *reinterpret_cast<gptr2_t>(b2);
-					} else {
-						const int64_t r0 = c0 + 2 * rp;
-						if (r0 < nrows) sg.a[q].x = b[0], sg.b[q].x = b2[0];
-						if (r0 + 1 < nrows) sg.a[q].y = b[1], sg.b[q].y = b2[1];
-					}
-				} else if (full) {
+				if (full) {
 					sg.a[q] = *reinterpret_cast<gptr2_t>(b);
 					if (kWideChunk) sg.b[q] = *reinterpret_cast<gptr2_t>(b + 16);
 				} else {
@@ -495,12 +406,8 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 	// and broke as soon as the compiler had a reason to copy a register whose load had not landed.)
 	auto stage_load_piece_steady = [&](int64_t chunk, Stage &sg, int q) {
 		const gptr_t b = colp[q] + chunk * kChunkRows;
-#if ANOFOX_WIDE_SKIP & 2
-		if (FAST) return;
-#endif
 		sg.a[q] = *reinterpret_cast<gptr2_t>(b);
-		if constexpr (kRun) sg.b[q] = *reinterpret_cast<gptr2_t>(colpB[q] + chunk * kChunkRows);
-		else if (kWideChunk) sg.b[q] = *reinterpret_cast<gptr2_t>(b + 16);
+		if (kWideChunk) sg.b[q] = *reinterpret_cast<gptr2_t>(b + 16);
 	};
 
 	// registers -> LDS image `buf` (shifted by fq; rows past the end of the group as zeros), plus this wave's partial
@@ -538,14 +445,7 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 				ss.wbad3 = ss.wbad3 || (isw && !(sg.b[q].y > 0.0));
 			}
 			double *dst = img + dcol[q];
-			if constexpr (kRun) {
-				double *dstB = img + dcolB[q];
-				const bool in0 = 2 * rp < left, in1 = 2 * rp + 1 < left;
-				dst[0] = in0 ? sg.a[q].x - fq[q] : 0.0;
-				dst[1] = in1 ? sg.a[q].y - fq[q] : 0.0;
-				dstB[0] = in0 ? sg.b[q].x - fqB[q] : 0.0;
-				dstB[1] = in1 ? sg.b[q].y - fqB[q] : 0.0;
-			} else if (left >= kChunkRows) { // wave-uniform: every row of the chunk exists
+			if (left >= kChunkRows) { // wave-uniform: every row of the chunk exists
 				dst[0] = sg.a[q].x - fq[q];
 				dst[1] = sg.a[q].y - fq[q];
 				if (kWideChunk) {
@@ -580,16 +480,9 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 			ss.wbad3 = ss.wbad3 || (isw && !(sg.b[q].y > 0.0));
 		}
 		double *dst = image + buf * ncol_pad * kLdsStride + dcol[q];
-#if ANOFOX_WIDE_SKIP & 16
-		if (FAST) { asm volatile("" ::"v"(sg.a[q].x), "v"(sg.a[q].y), "v"(sg.b[q].x), "v"(sg.b[q].y)); return; }
-#endif
 		dst[0] = sg.a[q].x - fq[q];
 		dst[1] = sg.a[q].y - fq[q];
-		if constexpr (kRun) {
-			double *dstB = image + buf * ncol_pad * kLdsStride + dcolB[q];
-			dstB[0] = sg.b[q].x - fqB[q];
-			dstB[1] = sg.b[q].y - fqB[q];
-		} else if (kWideChunk) {
+		if (kWideChunk) {
 			dst[16] = sg.b[q].x - fq[q];
 			dst[17] = sg.b[q].y - fq[q];
 		}
@@ -647,7 +540,8 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 	ACC_STAMP_DECL;
 	// steady = std::true_type: chunks c and c + 1 are full (the branch-free staging pieces)
 	// STEADY: the loads of chunk c + depth go into `ahead`, chunk c + 1 is stored from `landed` (the same registers when kDepth = 1)
-	// (generic iterations: `ga` = how many chunks beyond c + 1 the chunk lies that is loaded into `ahead` once chunk c + 1 is stored from it)
+	// (generic iterations: `ga` = how many chunks beyond c + 1 the chunk lies that is loaded into `ahead` once chunk c + 1 is stored
+	// from it — 1 at every call; written as a literal the index folds earlier and the kernels come out with other registers)
 	auto iteration = [&](auto steady, int64_t c, Stage &ahead, Stage &landed, int ga) {
 		constexpr bool STEADY = decltype(steady)::value;
 		ACC_STAMP_START();
@@ -738,9 +632,6 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 		ACC_STAMP(2);
 		if (more) stage_store_finish(c + 1, buf ^ 1, ss);
 		ACC_STAMP(4);
-#if ANOFOX_WIDE_SKIP & 4
-		if (!(FAST && STEADY))
-#endif
 		__syncthreads();
 		ACC_STAMP(5);
 #ifdef ANOFOX_SOLVE_STAMPS
@@ -748,92 +639,10 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 #endif
 	};
 
-	if constexpr (FAST && DMA != 0) {
-		// ---- (r4) the speculative version staged by `global_load_lds_dword` (lds_dma.h): no row passes through a register on its way
-		// into the image, no vector instruction shifts or stores it.  The x columns are dealt to the four wavefronts in contiguous
-		// ranges (the pointer table of the kernel arguments is walked as in accumulate_quad's kernel), the last wavefront also brings
-		// y; chunk c + 1 lands in the other image while the slabs of chunk c run, one barrier per chunk as before.  The image holds
-		// RAW rows: the shift by the first row is one subtraction per fragment (compute_chunk RAW).  The rows of the last chunk
-		// that lie behind the group are overwritten with the first row's values (difference 0) by the wavefront that loaded them.
-		static_assert(kChunkRows == 32 || kChunkRows == 64, "32 or 64 rows per chunk");
-		constexpr int QMAX = (P16 + kWaves - 1) / kWaves;
-		const int q_cols = (p + kWaves - 1) / kWaves;
-		const int c_begin = WAVE * q_cols;
-		int n_mine = p - c_begin;
-		n_mine = n_mine < 0 ? 0 : (n_mine > q_cols ? q_cols : n_mine);
-		// the first row, by image column (x in place, y at 16 T); the loop's first barrier orders these writes before the reads
-		for (int c = threadIdx.x; c <= p; c += kThreads) firstcol[c < p ? c : ycol] = c < p ? args.x_table[c][lo] : args.y[lo];
-		const lds_dma_table_t tab = lds_dma_table((unsigned)offsetof(WideArgs, x_table)) + c_begin;
-		const unsigned img0 = lds_dma_address(image);
-		auto dma_chunk = [&](int64_t c, int buf) {
-#pragma unroll
-			for (int sub = 0; sub < kChunkRows / 32; ++sub) { // 256 bytes of a column per instruction: a 64-row chunk takes two per column
-				const int64_t blk = lo + c * kChunkRows + 32 * sub;
-				if (blk >= hi) break; // wave-uniform (the rows are filled by fill_tail)
-				const unsigned voff = lds_dma_offsets(lane, hi - blk);
-				if (n_mine > 0) lds_dma_block<kLdsStride * 8, QMAX>(tab, n_mine, blk, voff, img0 + (unsigned)((buf * ncol_pad + c_begin) * kLdsStride * 8 + sub * 256));
-				if (WAVE == kWaves - 1) lds_dma1(voff, img0 + (unsigned)((buf * ncol_pad + ycol) * kLdsStride * 8 + sub * 256), args.y + blk);
-			}
-		};
-		auto fill_tail = [&](int buf, int left) { // rows left .. 31 of the columns this wavefront loaded := the first row
-			double *img = image + buf * ncol_pad * kLdsStride;
-			const int nr = kChunkRows - left;
-			for (int e = lane; e < n_mine * nr; e += 64) {
-				const int cc = c_begin + e / nr, r = left + e % nr;
-				img[cc * kLdsStride + r] = firstcol[cc];
-			}
-			if (WAVE == kWaves - 1)
-				for (int r = left + lane; r < kChunkRows; r += 64) img[ycol * kLdsStride + r] = firstcol[ycol];
-		};
-		const int tail = (int)(nrows % kChunkRows);
-		dma_chunk(0, 0);
-		lds_dma_wait_all();
-		__syncthreads(); // (firstcol complete, chunk 0 landed)
-		if (n_chunks == 1 && tail) {
-			fill_tail(0, tail);
-			__syncthreads();
-		}
-		double fsub[T];
-#pragma unroll
-		for (int I = 0; I < T; ++I) fsub[I] = firstcol[16 * I + (lane & 15)];
-		const double fy = firstcol[ycol];
-		for (int64_t c = 0; c < n_chunks; ++c) {
-			const int buf = (int)(c & 1);
-			const bool more = c + 1 < n_chunks; // wave-uniform
-			if (more) dma_chunk(c + 1, buf ^ 1);
-			compute_chunk<T, WAVE, WEIGHTED, CENTER, FAST, true, kChunkRows>(image + buf * ncol_pad * kLdsStride, firstcol, ycol, lane, kFullMask, acc, sx, sxy, dmax, ncmask,
-			                                                    sy, syy, sw, [](int) {}, fsub, fy);
-			lds_dma_wait_all();
-			if (more && c + 2 == n_chunks && tail) fill_tail(buf ^ 1, tail);
-			__syncthreads();
-		}
-	} else {
+	{ // (a scope of its own: the staging registers are dead before the record is written)
 	constexpr int D = Cfg::depth(FAST);
 	Stage st[D];
-	if constexpr (kTail2) {
-		stage_load(0, st[0]);
-		if (n_chunks > 1) stage_load(1, st[1]);
-		// the shift = the group's first row (nrows > 0: the caller's condition): rows 0, 1 of a column sit in the lane with rp == 0
-#pragma unroll
-		for (int q = 0; q < kMaxLoads; ++q) {
-			const int src = 8 * (wave + kWaves * q) + colsub;
-			const double f = __shfl(st[0].a[q].x, lane & (kRun ? ~15 : ~7), 64);
-			if (wave + kWaves * q < n_loads_total && src <= p) {
-				fq[q] = f;
-				if (rp == 0) firstcol[src < p ? src : ycol] = f;
-			}
-			if constexpr (kRun) {
-				const int srcB = src + 4;
-				const double fb = __shfl(st[0].b[q].x, lane & ~15, 64);
-				if (wave + kWaves * q < n_loads_total && srcB <= p) {
-					fqB[q] = fb;
-					if (rp == 0) firstcol[srcB < p ? srcB : ycol] = fb;
-				}
-			}
-		}
-		have_first = true;
-		stage_store(0, 0, st[0]);
-	} else if (n_chunks > 0) {
+	if (n_chunks > 0) {
 		stage_load(0, st[0]);
 		stage_store(0, 0, st[0]);
 	}
@@ -848,10 +657,8 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 			// trips of D chunks, so that which registers hold which chunk is known at compile time: chunk c + j + 1 sits in st[(j + 1) % D]
 			// when chunk c + j is multiplied, and the loads of chunk c + j + D go into st[j], whose chunk was stored one iteration ago
 			if (c + 2 * D - 1 < n_full) {
-				if constexpr (!kTail2) {
 #pragma unroll
-					for (int j = 1; j < D; ++j) stage_load(j, st[j]);
-				}
+				for (int j = 1; j < D; ++j) stage_load(j, st[j]);
 				for (; c + 2 * D - 1 < n_full; c += D) {
 #pragma unroll
 					for (int j = 0; j < D; ++j) iteration(std::true_type(), c + j, st[j], st[(j + 1) % D], 1);
@@ -859,23 +666,9 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 			}
 		}
 		ACC_MARK(3);
-		if constexpr (kTail2) {
-			// chunk c is staged and chunk c + 1 sits in st[1] (from before the loop, or from its last trip); chunk c + 2 goes into st[0] now and
-			// the remaining iterations alternate between the two sets
-			if (c + 2 < n_chunks) stage_load(c + 2, st[0]);
-			for (;;) {
-				if (c >= n_chunks) break;
-				iteration(std::false_type(), c, st[1], st[1], 2);
-				++c;
-				if (c >= n_chunks) break;
-				iteration(std::false_type(), c, st[0], st[0], 2);
-				++c;
-			}
-		} else {
-			// (the generic iterations expect the next chunk in registers; after steady trips it is there already and is read once more)
-			if (c + 1 < n_chunks) stage_load(c + 1, st[1 % D]);
-			for (; c < n_chunks; ++c) iteration(std::false_type(), c, st[1 % D], st[1 % D], 1);
-		}
+		// (the generic iterations expect the next chunk in registers; after steady trips it is there already and is read once more)
+		if (c + 1 < n_chunks) stage_load(c + 1, st[1 % D]);
+		for (; c < n_chunks; ++c) iteration(std::false_type(), c, st[1 % D], st[1 % D], 1);
 	}
 	}
 
@@ -1029,33 +822,29 @@ __device__ __forceinline__ bool wide_accumulate_rows_wave(const WideArgs &args, 
 
 // FAST: the speculative version (every wave returns the same verdict); otherwise the full one (always true).
 // The two never share a kernel: together they need more registers than there are (1110 spilled at T = 8).
-template <int T, bool WEIGHTED, bool CENTER, bool FAST = false, int DMA = 0>
+template <int T, bool WEIGHTED, bool CENTER, bool FAST = false>
 __device__ __forceinline__ bool wide_accumulate_rows(const WideArgs &args, int64_t lo, int64_t hi, double *rec,
                                                      const double *forced_first) {
 	switch (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) {
-	case 0: return wide_accumulate_rows_wave<T, 0, WEIGHTED, CENTER, FAST, DMA>(args, lo, hi, rec, forced_first);
-	case 1: return wide_accumulate_rows_wave<T, 1, WEIGHTED, CENTER, FAST, DMA>(args, lo, hi, rec, forced_first);
-	case 2: return wide_accumulate_rows_wave<T, 2, WEIGHTED, CENTER, FAST, DMA>(args, lo, hi, rec, forced_first);
+	case 0: return wide_accumulate_rows_wave<T, 0, WEIGHTED, CENTER, FAST>(args, lo, hi, rec, forced_first);
+	case 1: return wide_accumulate_rows_wave<T, 1, WEIGHTED, CENTER, FAST>(args, lo, hi, rec, forced_first);
+	case 2: return wide_accumulate_rows_wave<T, 2, WEIGHTED, CENTER, FAST>(args, lo, hi, rec, forced_first);
 #if ANOFOX_WIDE_WAVES == 8
-	case 3: return wide_accumulate_rows_wave<T, 3, WEIGHTED, CENTER, FAST, DMA>(args, lo, hi, rec, forced_first);
-	case 4: return wide_accumulate_rows_wave<T, 4, WEIGHTED, CENTER, FAST, DMA>(args, lo, hi, rec, forced_first);
-	case 5: return wide_accumulate_rows_wave<T, 5, WEIGHTED, CENTER, FAST, DMA>(args, lo, hi, rec, forced_first);
-	case 6: return wide_accumulate_rows_wave<T, 6, WEIGHTED, CENTER, FAST, DMA>(args, lo, hi, rec, forced_first);
-	default: return wide_accumulate_rows_wave<T, 7, WEIGHTED, CENTER, FAST, DMA>(args, lo, hi, rec, forced_first);
+	case 3: return wide_accumulate_rows_wave<T, 3, WEIGHTED, CENTER, FAST>(args, lo, hi, rec, forced_first);
+	case 4: return wide_accumulate_rows_wave<T, 4, WEIGHTED, CENTER, FAST>(args, lo, hi, rec, forced_first);
+	case 5: return wide_accumulate_rows_wave<T, 5, WEIGHTED, CENTER, FAST>(args, lo, hi, rec, forced_first);
+	case 6: return wide_accumulate_rows_wave<T, 6, WEIGHTED, CENTER, FAST>(args, lo, hi, rec, forced_first);
+	default: return wide_accumulate_rows_wave<T, 7, WEIGHTED, CENTER, FAST>(args, lo, hi, rec, forced_first);
 #else
-	default: return wide_accumulate_rows_wave<T, 3, WEIGHTED, CENTER, FAST, DMA>(args, lo, hi, rec, forced_first);
+	default: return wide_accumulate_rows_wave<T, 3, WEIGHTED, CENTER, FAST>(args, lo, hi, rec, forced_first);
 #endif
 	}
 }
 
 // FAST: the speculative version on every group; the groups it gives up on (and empty ones) go to a list — borrowed
 // from the refine queue, which the solve that follows starts to fill only later — for accumulate_wide_redo_kernel.
-// (measurement builds: the register budget of the speculative version cut for more wavefronts per SIMD, `-DANOFOX_WIDE_FAST_WPS(T)=3`)
-#ifndef ANOFOX_WIDE_FAST_WPS
-#define ANOFOX_WIDE_FAST_WPS(T) kWavesPerSimd
-#endif
-template <int T, bool WEIGHTED, bool CENTER, bool FAST, int DMA = 0>
-__global__ __launch_bounds__(kThreads, (FAST ? ANOFOX_WIDE_FAST_WPS(T) : kWavesPerSimd)) void accumulate_wide_kernel(WideArgs args) {
+template <int T, bool WEIGHTED, bool CENTER, bool FAST>
+__global__ __launch_bounds__(kThreads, kWavesPerSimd) void accumulate_wide_kernel(WideArgs args) {
 	const int64_t g = blockIdx.x;
 	const int64_t lo = args.row_offsets[args.group_base + g];
 	const int64_t hi = group_row_end(args, args.group_base + g);
@@ -1071,18 +860,7 @@ __global__ __launch_bounds__(kThreads, (FAST ? ANOFOX_WIDE_FAST_WPS(T) : kWavesP
 	}
 	double *rec = args.moments + g * (int64_t)wide_record_len(T);
 	if constexpr (FAST) {
-#if ANOFOX_WIDE_STAGGER
-		// Groups of equal length keep the workgroups that share a CU in step: they start together, share the SIMDs evenly and reach their
-		// latency-bound ends (first loads, last chunks, record) together, with nothing left to fill the matrix pipe.  The workgroups of the
-		// grid's first wave therefore start a random fraction of one group's time apart (s_sleep, ~4 us per step; large grids only).
-		if (gridDim.x >= 4096 && blockIdx.x < 1024) {
-			unsigned steps = (unsigned)(((hi - lo) * (int64_t)(args.p + 1) * 8) / (6500 * 4)); // a group's time at ~6.5 GB/s per workgroup
-			steps = steps > 64u ? 64u : steps;
-			const unsigned k = steps ? ((blockIdx.x * 2654435761u) >> 20) % steps : 0u;
-			for (unsigned i = 0; i < k; ++i) __builtin_amdgcn_s_sleep(127);
-		}
-#endif
-		if (hi > lo && wide_accumulate_rows<T, WEIGHTED, CENTER, true, DMA>(args, lo, hi, rec, nullptr)) return;
+		if (hi > lo && wide_accumulate_rows<T, WEIGHTED, CENTER, true>(args, lo, hi, rec, nullptr)) return;
 		if (threadIdx.x == 0) args.refine_list[atomicAdd(args.refine_count + kWideRedoCounter, 1)] = (int32_t)g;
 	} else {
 		wide_accumulate_rows<T, WEIGHTED, CENTER>(args, lo, hi, rec, nullptr);
@@ -1147,13 +925,10 @@ hipError_t launch_accumulate_wide_T(const WideArgs &a, hipStream_t stream) {
 	const size_t lds = (size_t)2 * ncol_pad * WideCfg<T>::stride(weighted, center) * sizeof(double) + (size_t)ncol_pad * (sizeof(double *) + sizeof(double)) + 64;
 	const dim3 grid((unsigned)a.n_groups), block(kThreads);
 	const dim3 seg_grid((unsigned)kWideSegMaxSegments); // idle unless some group exceeded seg_rows
-	// launch_part (host_api.hip, several slabs): the idle-unless-needed kernels behind the main one run on the stream of the slab's
-	// solve, so that they never queue on the accumulate stream behind the previous slab's solve (which holds every SIMD's registers)
-	const bool main_part = a.launch_part != 2, rest_part = a.launch_part != 1;
 #define ANOFOX_WIDE_LAUNCH(W, C)                                                                                  \
 	do {                                                                                                          \
-		if (main_part) hipLaunchKernelGGL((accumulate_wide_kernel<T, W, C, false>), grid, block, lds, stream, a); \
-		if (rest_part && a.seg_table) hipLaunchKernelGGL((accumulate_wide_segments_kernel<T, W, C>), seg_grid, block, lds, stream, a); \
+		hipLaunchKernelGGL((accumulate_wide_kernel<T, W, C, false>), grid, block, lds, stream, a);                \
+		if (a.seg_table) hipLaunchKernelGGL((accumulate_wide_segments_kernel<T, W, C>), seg_grid, block, lds, stream, a); \
 	} while (0)
 	if (weighted) {
 		if (center) ANOFOX_WIDE_LAUNCH(true, true);
@@ -1164,23 +939,9 @@ hipError_t launch_accumulate_wide_T(const WideArgs &a, hipStream_t stream) {
 		ANOFOX_WIDE_LAUNCH(false, true);
 	} else {
 		// speculative kernel, then the full version on whatever it listed (the counter is zeroed by the caller)
-		// (r4) ANOFOX_WIDE_DMA=1: its LDS-DMA staging (3 and 4 column tiles: 35 <= p <= 64, the widths accumulate_quad does not take)
-		static const int dma_rows = getenv("ANOFOX_WIDE_DMA") ? atoi(getenv("ANOFOX_WIDE_DMA")) : 0; // 1 / 32: 32-row chunks, 64: 64-row chunks
-		constexpr bool kHasDma = T >= kWideFastMinT && T <= 4 && kWaves == 4;
-		const size_t lds64 = (size_t)2 * ncol_pad * 66 * sizeof(double) + (size_t)ncol_pad * (sizeof(double *) + sizeof(double)) + 64;
-		if (main_part && kHasDma && dma_rows == 64) {
-			static const bool attr_set = [] {
-				(void)hipFuncSetAttribute(reinterpret_cast<const void *>(&accumulate_wide_kernel<T, false, true, (T >= kWideFastMinT), (kHasDma ? 64 : 0)>),
-				                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); // (the kernel has 4 bytes of static LDS)
-				return true;
-			}();
-			(void)attr_set;
-			hipLaunchKernelGGL((accumulate_wide_kernel<T, false, true, (T >= kWideFastMinT), (kHasDma ? 64 : 0)>), grid, block, lds64, stream, a);
-		} else if (main_part && kHasDma && dma_rows != 0) {
-			hipLaunchKernelGGL((accumulate_wide_kernel<T, false, true, (T >= kWideFastMinT), (kHasDma ? 32 : 0)>), grid, block, lds, stream, a);
-		} else if (main_part) hipLaunchKernelGGL((accumulate_wide_kernel<T, false, true, (T >= kWideFastMinT)>), grid, block, lds, stream, a);
-		if (rest_part && a.seg_table) hipLaunchKernelGGL((accumulate_wide_segments_kernel<T, false, true>), seg_grid, block, lds, stream, a);
-		if (rest_part) hipLaunchKernelGGL((accumulate_wide_redo_kernel<T, false, true>), grid, block, lds, stream, a);
+		hipLaunchKernelGGL((accumulate_wide_kernel<T, false, true, (T >= kWideFastMinT)>), grid, block, lds, stream, a);
+		if (a.seg_table) hipLaunchKernelGGL((accumulate_wide_segments_kernel<T, false, true>), seg_grid, block, lds, stream, a);
+		hipLaunchKernelGGL((accumulate_wide_redo_kernel<T, false, true>), grid, block, lds, stream, a);
 	}
 #undef ANOFOX_WIDE_LAUNCH
 	return hipGetLastError();

@@ -65,6 +65,15 @@ struct AnofoxHipContext {
 };
 
 namespace anofox {
+// The ANOFOX_* environment switches ("switches").  Every reader caches its value in a function-local
+// `static const`: a switch is read once per process.
+inline long long env_int(const char *name, long long dflt) { // the variable's integer value; `dflt` when it is unset
+	const char *v = getenv(name);
+	return v ? atoll(v) : dflt;
+}
+inline bool env_is(const char *name, int value) { return getenv(name) && env_int(name, 0) == value; } // set, and to `value`
+inline bool env_on(const char *name) { return !env_is(name, 0); } // on unless set to 0 (the A/B switches of shipped choices)
+
 namespace host {
 void agg_state_detach(struct AnofoxHipAggState *s); // agg_state.hip
 // host_api.hip: the device batch path (accumulate -> solve -> refine) on device-resident inputs, enqueued on the

@@ -264,7 +264,7 @@ hipError_t en_window_launch(const WindowArgs &a, void *user, hipStream_t st) {
 }
 
 WindowSolve elasticnet_window(EnParams *en) {
-	static const bool narrow_on = !(getenv("ANOFOX_EN_WINDOW_NARROW") && atoi(getenv("ANOFOX_EN_WINDOW_NARROW")) == 0);
+	static const bool narrow_on = env_on("ANOFOX_EN_WINDOW_NARROW");
 	return WindowSolve{elasticnet_stages(en), narrow_on ? en_window_launch : nullptr, en};
 }
 

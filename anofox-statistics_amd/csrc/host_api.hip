@@ -65,7 +65,7 @@ bool regression_wide_stage(AnofoxHipContext *ctx, WideArgs &a, hipStream_t ss, i
 	auto solve = [&](int mode) { return mid ? launch_solve_mid(a, mode, ss) : launch_solve_wide(a, mode, ss); };
 	// the primary solve of every width runs with one wavefront per group and the matrix in registers (solve_tiles.hip);
 	// the lane-per-group / workgroup-per-group kernels keep the refinement modes.  ANOFOX_SOLVE_TILES=0: without it.
-	static const bool tiles_on = !(getenv("ANOFOX_SOLVE_TILES") && atoi(getenv("ANOFOX_SOLVE_TILES")) == 0);
+	static const bool tiles_on = env_on("ANOFOX_SOLVE_TILES");
 	// (p <= 10: a 16 x 16 tile is mostly padding and the lane-per-group solve is as fast — 200 000 x 1000 x 9: 0.58 vs 0.70 ms;
 	// from there on the tiles win: p = 16 1.74 -> 0.69 ms, 100 000 x 1000 x 32 4.24 -> 0.76 ms, x 24 with inference 3.40 -> 1.77 ms)
 	const bool tiles_mid = mid && tiles_on && p >= 11 && solve_tiles_supports(p);
@@ -76,7 +76,7 @@ bool regression_wide_stage(AnofoxHipContext *ctx, WideArgs &a, hipStream_t ss, i
 	// four updates on the wide path: with the residual in double-double every update gains about two digits even at
 	// cond(X) = 2e7 (an exactly determined 67 x 67 system of the deep fuzz sweep: 5.4e-7 after two, 4.3e-9 after three,
 	// 2.3e-11 after four); the launches are idle unless groups are queued.  ANOFOX_WIDE_REFINE_STEPS overrides (measurements).
-	static const int wide_steps = getenv("ANOFOX_WIDE_REFINE_STEPS") ? atoi(getenv("ANOFOX_WIDE_REFINE_STEPS")) : 2 * kRefineSteps;
+	static const int wide_steps = env_int("ANOFOX_WIDE_REFINE_STEPS", 2 * kRefineSteps);
 	for (int it = 0; it < wide_steps; ++it) { // queued groups only: b += (X'WX)^-1 X'Wr
 		if (hip_fail(launch_residual_grad_wide(a, ss), "wide residual kernel launch", e)) return false;
 		if (hip_fail(solve(1), "wide refine kernel launch", e)) return false;
@@ -92,7 +92,7 @@ bool regression_wide_stage(AnofoxHipContext *ctx, WideArgs &a, hipStream_t ss, i
 	// (r4) LAST: the queued groups once more, from their rows in double-double — standard errors (classical and HC) that do not
 	// carry cond(X)^2 eps, and the reference's aliasing rule instead of the 1e-11 pivot test (refit_dd.hip).
 	// ANOFOX_REFIT_DD=0: without it (measurements).
-	static const bool refit_dd_on = !(getenv("ANOFOX_REFIT_DD") && atoi(getenv("ANOFOX_REFIT_DD")) == 0);
+	static const bool refit_dd_on = env_on("ANOFOX_REFIT_DD");
 	if (refit_dd_on && hip_fail(launch_refit_dd_wide(a, ss), "double-double refit kernel launch", e)) return false;
 	return true;
 }
@@ -112,7 +112,7 @@ bool regression_narrow_stage(AnofoxHipContext *ctx, BatchArgs &a, hipStream_t st
 	// (r4) LAST: the queued groups once more, from their rows in double-double (refit_dd.hip) — the reference's aliasing rule
 	// instead of the 1e-11 pivot test (round 3's narrow sweeps: 12 "rank band" groups of 240 000 cases), standard errors without
 	// cond(X)^2 eps.  ANOFOX_REFIT_DD=0: without it.
-	static const bool refit_dd_on = !(getenv("ANOFOX_REFIT_DD") && atoi(getenv("ANOFOX_REFIT_DD")) == 0);
+	static const bool refit_dd_on = env_on("ANOFOX_REFIT_DD");
 	if (refit_dd_on && hip_fail(launch_refit_dd_narrow(a, st), "double-double refit kernel launch", e)) return false;
 	return true;
 }
@@ -134,14 +134,14 @@ bool run_wide_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
 	const size_t b_mom = align_up((size_t)slab * rec_bytes, 256);
 	const size_t b_rss = align_up((size_t)G * (size_t)refine_vec_len((int)p) * sizeof(double), 256);
 	const size_t b_lst = align_up((size_t)slab * sizeof(int32_t), 256);
-	static const bool mid_acc_on = !(getenv("ANOFOX_MID_ACC") && atoi(getenv("ANOFOX_MID_ACC")) == 0); // A/B switch for measurements
+	static const bool mid_acc_on = env_on("ANOFOX_MID_ACC"); // A/B switch for measurements
 	const bool mid_acc = mid_acc_on && accumulate_mid_supports((int)p);
 	// Several slabs: slab k's solve / refinement kernels run on a second stream while the main stream accumulates slab k + 1
 	// into the other moment buffer.  Measured (profiles/r03_slab_overlap.txt): the time between the accumulate kernels
 	// drops (cfg5: 5.05 -> 1.66 ms per step) but the accumulate kernels stretch by almost as much (69.7 -> 72.3 ms) — the
 	// one-wavefront-per-group solve keeps the CUs busy, it is not idle time to hide: 74.7 -> 73.9 ms per cfg5 step, nothing
 	// at n = 1000.  ANOFOX_WIDE_OVERLAP=0: everything on the one stream, as for a single slab.
-	static const bool overlap_on = !(getenv("ANOFOX_WIDE_OVERLAP") && atoi(getenv("ANOFOX_WIDE_OVERLAP")) == 0);
+	static const bool overlap_on = env_on("ANOFOX_WIDE_OVERLAP");
 	const bool overlap = overlap_on && G > slab;
 	const int n_buf = overlap ? 2 : 1;
 	// very large groups are split into row segments (accumulate_mid.hip: a wave each; accumulate_wide.hip: a workgroup each)
@@ -175,7 +175,7 @@ bool run_wide_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
 	a.inference = opt.compute_inference ? d_inf : nullptr;
 	a.rule_counts = d_rule_counts;
 	a.row_ends = ctx->frame_ends;
-	static const bool wide_fast_on = !(getenv("ANOFOX_WIDE_FAST") && atoi(getenv("ANOFOX_WIDE_FAST")) == 0); // A/B switch
+	static const bool wide_fast_on = env_on("ANOFOX_WIDE_FAST"); // A/B switch
 	a.no_fast_path = wide_fast_on ? 0 : 1;
 
 	hipStream_t st = ctx->stream;
@@ -201,7 +201,7 @@ bool run_wide_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
 		slab_sizes.push_back(take);
 		left -= take;
 	}
-	static const bool slab_balance_on = !(getenv("ANOFOX_WIDE_SLAB_BALANCE") && atoi(getenv("ANOFOX_WIDE_SLAB_BALANCE")) == 0); // A/B switch
+	static const bool slab_balance_on = env_on("ANOFOX_WIDE_SLAB_BALANCE"); // A/B switch
 	if (const size_t K = slab_sizes.size(); slab_balance_on && K >= 2 && slab_sizes[K - 1] < slab / 4) {
 		const int64_t both = slab_sizes[K - 2] + slab_sizes[K - 1];
 		slab_sizes[K - 1] = both / 4;
@@ -237,29 +237,22 @@ bool run_wide_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
 			if (ctx->timing) (void)hipEventRecord(e0, st);
 		}
 		// 8 < p <= 32: 4 x 4-block MFMAs (accumulate_quad.hip) or 16 x 16 tiles (accumulate_mid.hip); ANOFOX_MID_QUAD=0/1
-		static const bool quad_on = !(getenv("ANOFOX_MID_QUAD") && atoi(getenv("ANOFOX_MID_QUAD")) == 0);
+		static const bool quad_on = env_on("ANOFOX_MID_QUAD");
 		// (r4: its speculative kernel also takes p = 27 .. 34 of the unweighted fit with an intercept)
 		const bool quad = mid_acc_on && quad_on && accumulate_quad_supports((int)p, opt.model == ANOFOX_HIP_MODEL_WLS, opt.fit_intercept, a.no_fast_path != 0);
-		// (r4) 34 <= p <= 64: the wave-per-group speculative kernel on LDS-DMA (accumulate_mid.hip) before accumulate_wide's full version
-		const bool tile = mid_acc_on && !quad && accumulate_tile_supports((int)p, opt.model == ANOFOX_HIP_MODEL_WLS, opt.fit_intercept, a.no_fast_path != 0);
 		// The workgroup-per-group kernel's segment / redo kernels are idle unless a group needs them, yet an idle launch is not
 		// free next to another stream's kernel: every one of its workgroups needs a slot (74 KB of LDS, 4 x 237 registers) that
 		// the other kernel's wavefronts hold, so its trace duration is the time it QUEUED — 5 us, or ~1 ms behind the previous
 		// slab's solve (512 registers per wave, one wave per SIMD): round 3's "bimodal idle launch" (profiles/r04_idle_launches.md).
-		// Moving them to the solve stream (ANOFOX_WIDE_SPLIT=1) was built and measured: there the redo kernel's 13 785
-		// workgroups queue behind the NEXT slab's accumulate kernel instead (2-18 ms) and take the slab's solve with them — worse;
-		// they stay on this stream.
-		const bool plain_wide = !quad && !tile && !mid_acc;
-		static const bool split_on = getenv("ANOFOX_WIDE_SPLIT") && atoi(getenv("ANOFOX_WIDE_SPLIT")) == 1; // measurement switch
-		a.launch_part = (plain_wide && overlap && split_on) ? 1 : 0;
+		// Moving them to the solve stream was built and measured: there the redo kernel's 13 785 workgroups queue behind the
+		// NEXT slab's accumulate kernel instead (2-18 ms) and take the slab's solve with them — worse; they stay on this stream.
 		// (r4) expanding window frames (run_window): every frame is its predecessor plus a row — their records come from
 		// accumulate_prefix.hip, n / (2 K) + 1 rows read per frame instead of n / 2.  ANOFOX_FRAMES_PREFIX=0: the kernels below.
-		static const bool prefix_on = !(getenv("ANOFOX_FRAMES_PREFIX") && atoi(getenv("ANOFOX_FRAMES_PREFIX")) == 0);
-		static const int prefix_k = getenv("ANOFOX_FRAMES_PREFIX_K") ? atoi(getenv("ANOFOX_FRAMES_PREFIX_K")) : 128;
+		static const bool prefix_on = env_on("ANOFOX_FRAMES_PREFIX");
+		static const int prefix_k = env_int("ANOFOX_FRAMES_PREFIX_K", 128);
 		const bool prefix = prefix_on && ctx->frame_prefix && a.row_ends != nullptr;
 		if (hip_fail(prefix ? launch_accumulate_prefix(a, prefix_k > 0 ? prefix_k : 128, st)
-		                    : (quad ? launch_accumulate_quad(a, st)
-		                            : (tile ? launch_accumulate_tile(a, st) : (mid_acc ? launch_accumulate_mid(a, st) : launch_accumulate_wide(a, st)))),
+		                    : (quad ? launch_accumulate_quad(a, st) : (mid_acc ? launch_accumulate_mid(a, st) : launch_accumulate_wide(a, st))),
 		             "wide accumulate kernel launch", e))
 			return false;
 		if (ctx->timing) (void)hipEventRecord(e1, st);
@@ -271,11 +264,6 @@ bool run_wide_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, 
 		if (overlap) {
 			if (hip_fail(hipEventRecord(ctx->slab_acc_done[buf], st), "hipEventRecord", e)) return false;
 			if (hip_fail(hipStreamWaitEvent(ss, ctx->slab_acc_done[buf], 0), "hipStreamWaitEvent", e)) return false;
-			if (a.launch_part == 1) {
-				a.launch_part = 2;
-				if (hip_fail(launch_accumulate_wide(a, ss), "wide accumulate follow-up launch", e)) return false;
-				a.launch_part = 0;
-			}
 		}
 		if (!stages.wide(ctx, a, ss, slab, stages.user, e)) return false;
 
@@ -354,7 +342,7 @@ bool run_device_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows
 	}
 	if (ctx->timing) (void)hipEventRecord(e0, st); // (again: the accumulate kernel starts after the gate)
 	// batches of small groups (<= 128 rows on average): several groups per wavefront, the long ones through a list
-	static const bool small_on = !(getenv("ANOFOX_ACC_SMALL") && atoi(getenv("ANOFOX_ACC_SMALL")) == 0); // A/B switch
+	static const bool small_on = env_on("ANOFOX_ACC_SMALL"); // A/B switch
 	// (window frames: overlapping row ranges given by row_ends — the packed kernel reads row_offsets[g + 1])
 	const int segw = (small_on && !a.row_ends && n_rows > 0 && G < (int64_t)0x7fffffff) ? accumulate_small_segment_width((double)n_rows / (double)G) : 0;
 	// The regression models' primary solve inside the accumulate kernel (accumulate_narrow.hip): the moment records stay in
@@ -362,7 +350,7 @@ bool run_device_batch(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows
 	// other models' stages, HC errors (hc_narrow) — nor for window frames or the packed small-group kernel, and not with
 	// inference records: their special functions need more registers than the fused kernel has.
 	// ANOFOX_NARROW_FUSED=0: the separate solve kernel (A/B measurements, parity tests).
-	static const bool fused_on = !(getenv("ANOFOX_NARROW_FUSED") && atoi(getenv("ANOFOX_NARROW_FUSED")) == 0);
+	static const bool fused_on = env_on("ANOFOX_NARROW_FUSED");
 	a.primary_solved = (fused_on && stages.narrow == regression_narrow_stage && !a.row_ends && !segw && !a.inference &&
 	                    narrow_fused_fits(a.p, a.model == ANOFOX_HIP_MODEL_WLS, a.fit_intercept != 0)) ? 1 : 0;
 	if (segw) {
@@ -897,7 +885,7 @@ bool run_window(AnofoxHipContext *ctx, int64_t G, size_t p, int64_t n_rows, cons
 	// ill-conditioned frames are flagged by the kernel and refitted with the fit path's refinement passes.  Another model's
 	// kernels rely on that refit for frames whose moment RSS cancels (the elastic net does not clamp it): without flagging,
 	// every frame of such a model goes through the frames path.
-	static const bool flag_on = !(getenv("ANOFOX_WIN_FLAG") && atoi(getenv("ANOFOX_WIN_FLAG")) == 0); // A/B switch for measurements
+	static const bool flag_on = env_on("ANOFOX_WIN_FLAG"); // A/B switch for measurements
 	const bool flagging = flag_on && n_rows > 0 && n_rows < (int64_t)0x7fffffff;
 	if (p > (size_t)kNarrowMaxP || (ws && (!ws->launch || !flagging))) {
 		// wider than the in-register window kernels: every frame becomes a virtual group of the batch fit (frames.hip)

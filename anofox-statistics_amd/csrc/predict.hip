@@ -12,7 +12,7 @@
 // Mapping: one wavefront per group, lanes stride the rows; the group's coefficients sit in LDS.
 // HBM-bound: 8p B/row read, 24 B/row written.
 #include "common.h"
-#include <cstdlib>
+#include "context.h"
 #include "device_math.h"
 
 namespace anofox {
@@ -261,7 +261,7 @@ hipError_t launch_predict_p(const PredictArgs &a, hipStream_t stream) {
 	if (a.avg_rows > 0.0 && a.avg_rows <= 12.0) segw = 8;
 	else if (a.avg_rows > 0.0 && a.avg_rows <= 24.0) segw = 16;
 	else if (a.avg_rows > 0.0 && a.avg_rows <= 64.0) segw = 32;
-	if (const char *e = getenv("ANOFOX_PRED_SEGW")) segw = atoi(e);
+	segw = (int)env_int("ANOFOX_PRED_SEGW", segw);
 	if (segw == 4) launch_predict_small<P, 4>(a, stream);
 	else if (segw == 8) launch_predict_small<P, 8>(a, stream);
 	else if (segw == 16) launch_predict_small<P, 16>(a, stream);

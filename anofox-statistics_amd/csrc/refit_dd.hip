@@ -18,10 +18,10 @@
 // Reference semantics restated (crates/anofox-stats-core/src/models/{ols,ridge,wls}.rs; oracle/anofox_oracle.c:300-600):
 // row filter ols.rs:59-66 / wls.rs:76-86, constant columns and first valid row taken from the moment record (ols.rs:76-87),
 // statistics of SURVEY.md Appendix B.7, ridge = (Xc'Xc + lambda I) beta = Xc'yc with glmnet scaling lambda n / sd_y.
-#include <stdlib.h>
 #include <string.h>
 
 #include "common.h"
+#include "context.h"
 #include "device_math.h"
 #include "dd_arith.h"
 
@@ -521,7 +521,7 @@ size_t refit_dd_lds_bytes() {
 namespace {
 // ~1-2 ms per wide group and workgroup, ~0.3 ms per narrow one; 256-512 workgroups in flight: a cap's worth costs 40-50 ms
 int refit_dd_cap(int p) {
-	static const int forced = getenv("ANOFOX_REFIT_DD_MAX") ? atoi(getenv("ANOFOX_REFIT_DD_MAX")) : -1;
+	static const int forced = env_int("ANOFOX_REFIT_DD_MAX", -1);
 	if (forced >= 0) return forced;
 	return p <= kNarrowMaxP ? 65536 : 8192;
 }

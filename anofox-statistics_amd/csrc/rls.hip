@@ -35,13 +35,13 @@ constexpr int64_t kRlsLongRows = 1 << 16;
 constexpr int64_t kRlsWaveBlocks = 1024;
 
 int64_t rls_long_rows() {
-	static const int64_t v = getenv("ANOFOX_RLS_LONG_ROWS") ? atoll(getenv("ANOFOX_RLS_LONG_ROWS")) : kRlsLongRows;
+	static const int64_t v = env_int("ANOFOX_RLS_LONG_ROWS", kRlsLongRows);
 	return v;
 }
 
 // ANOFOX_RLS_EXPANDING=0 sends the expanding window at p <= 8 through the frames path as well (A/B switch for measurements)
 bool rls_expanding_on() {
-	static const bool on = !(getenv("ANOFOX_RLS_EXPANDING") && atoi(getenv("ANOFOX_RLS_EXPANDING")) == 0);
+	static const bool on = env_on("ANOFOX_RLS_EXPANDING");
 	return on;
 }
 

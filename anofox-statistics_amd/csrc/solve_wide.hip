@@ -9,9 +9,9 @@
 //   upper triangle  : L^-1 transposed (only when inference is requested), one thread per column
 // Queued groups (small pivot ratio or RSS/TSS < 1e-7) get the same iterative-refinement passes as in
 // solve_narrow.hip: MODE 1 = b += (X'WX)^-1 X'Wr from residual_grad_wide_kernel, MODE 2 = final statistics.
-#include <stdlib.h>
 
 #include "common.h"
+#include "context.h"
 #include <mutex>
 #include "device_math.h"
 #include "dd_arith.h"
@@ -1059,19 +1059,18 @@ hipError_t launch_solve_wide(const WideArgs &a, int mode, hipStream_t stream) {
 	if (a.n_groups <= 0) return hipSuccess;
 	// the primary solve of 32 < p <= 128 runs with one wavefront per group and the matrix in registers (solve_tiles.hip);
 	// the refinement modes — a handful of queued groups — stay here.  ANOFOX_SOLVE_TILES=0: this file's kernels only.
-	static const bool tiles_on = !(getenv("ANOFOX_SOLVE_TILES") && atoi(getenv("ANOFOX_SOLVE_TILES")) == 0);
+	static const bool tiles_on = env_on("ANOFOX_SOLVE_TILES");
 	if (tiles_on && mode == MODE_PRIMARY && solve_tiles_supports(a.p)) return launch_solve_tiles(a, stream);
 	const size_t lds = solve_wide_lds_bytes(a.p);
 	// p <= 96 (two or more groups' matrices fit a CU's LDS): one wave per group.  50 000 x 1000 rows, solve without /
 	// with inference: p = 33 5.78 / 9.94 -> 2.18 / 3.30 ms, p = 64 7.20 / 12.4 -> 2.92 / 4.56 ms; 20 000 groups: p = 80
 	// 3.79 / 6.73 -> 3.32 / 5.03 ms, p = 96 4.41 / 7.65 -> 4.14 / 6.27 ms; slower from p = 97 (one group per CU:
 	// p = 112 6.24 / 8.63 -> 9.87 / 15.1 ms; two waves per group there: 7.34 / 10.4 ms).  With the register budget
-	// cut for two waves per SIMD (ANOFOX_SOLVE_WAVE=2) the spills cost more than the occupancy gains (p = 33:
-	// 2.47 / 4.67 ms).  ANOFOX_SOLVE_WAVE=0: four waves per group everywhere.
-	static const int wave_mode = getenv("ANOFOX_SOLVE_WAVE") ? atoi(getenv("ANOFOX_SOLVE_WAVE")) : 1;
-	static const int wave_max_t = getenv("ANOFOX_SOLVE_WAVE_T") ? atoi(getenv("ANOFOX_SOLVE_WAVE_T")) : 6;
-	if (wave_mode && wide_tiles(a.p) <= wave_max_t)
-		return wave_mode == 2 ? launch_solve_wide_occ<2, 64>(a, mode, lds, stream) : launch_solve_wide_occ<1, 64>(a, mode, lds, stream);
+	// cut for two waves per SIMD the spills cost more than the occupancy gains (p = 33: 2.47 / 4.67 ms).
+	// ANOFOX_SOLVE_WAVE=0: four waves per group everywhere.
+	static const bool wave_on = env_on("ANOFOX_SOLVE_WAVE");
+	static const int wave_max_t = env_int("ANOFOX_SOLVE_WAVE_T", 6);
+	if (wave_on && wide_tiles(a.p) <= wave_max_t) return launch_solve_wide_occ<1, 64>(a, mode, lds, stream);
 	return 2 * lds <= (size_t)160 * 1024 ? launch_solve_wide_occ<2, 256>(a, mode, lds, stream) : launch_solve_wide_occ<1, 256>(a, mode, lds, stream);
 }
 

@@ -23,9 +23,9 @@
 // (a 10-row frame at row 1000 of a trending regressor loses ~9 digits); the loads of neighbouring lanes are
 // consecutive rows and hit L1/L2 after the first touch, so the direct sum costs O(frame) cached loads per row.
 #include "common.h"
+#include "context.h"
 #include "device_math.h"
 #include "elasticnet_solve.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace anofox {
@@ -611,7 +611,7 @@ inline int window_segw(const WindowArgs &a) {
 			else if (a.avg_rows <= 48.0) segw = 16;
 		}
 	}
-	if (const char *e = getenv("ANOFOX_WIN_SEGW")) segw = atoi(e);
+	segw = (int)env_int("ANOFOX_WIN_SEGW", segw);
 	return segw;
 }
 

@@ -862,13 +862,14 @@ def test_wide_edge_cases_match_oracle(pkg, ctx, p):
             assert_records_match(core, rcore, p, inf, rinf, what=f"wide edge {model} p={p} icpt={icpt}", skip_diag_groups=zero_df)
 
 
-@pytest.mark.parametrize("p", [9, 10, 12, 15, 16, 18, 22, 26, 27, 30, 31, 33, 34, 40, 46, 47, 48, 49, 62, 63, 64, 100, 128])
+@pytest.mark.parametrize("p", [9, 10, 12, 15, 16, 18, 22, 26, 27, 30, 31, 33, 34, 35, 40, 42, 43, 46, 47, 48, 49, 50, 51, 62, 63, 64,
+                               100, 128])
 def test_wide_speculative_kernel_and_its_fallback(pkg, ctx, p):
     """p > 8, OLS with an intercept: the speculative accumulate kernels (every row valid, first row as the shift, constant
     columns read off the diagonal of the moments) — accumulate_quad's register-staged one (p <= 26: every column-group count
-    and both block sizes), its LDS-DMA one (27 .. 33), accumulate_mid's LDS-DMA kernel on three / four column tiles (34 .. 64:
-    with y and the ones inside the last tile, 46 / 62, and with side sums, 47 / 48 / 63 / 64) and accumulate_wide's (65 .. 128)
-    — and the groups they have to hand to the full kernel: a NaN / inf anywhere, an invalid first row, columns in the band
+    and both block sizes), its LDS-DMA one (27 .. 42 and 49, 50: both ends of each range, and the widths next to them) and
+    accumulate_wide's on three to eight column tiles (43 .. 48, 51 .. 128: with y and the ones inside the last tile, 46 / 62,
+    and behind it, 47 / 48 / 63 / 64) — and the groups they have to hand to the full kernel: a NaN / inf anywhere, an invalid first row, columns in the band
     where sum d^2 does not decide |x - x_first| < 1e-10 — next to groups they keep, of every block-count shape (0, 1, 2
     rows; exactly k x 32 rows; one row more or less)."""
     rng = np.random.default_rng(1000 + p)
