@@ -51,6 +51,9 @@ from .correlation import (CorrelationAggResult, CorrelationOptions, cor_batch_de
 from .rank_tests import (RankTestAggResult, RankTestOptions, kruskal_wallis, kruskal_wallis_agg, mann_whitney_u, mann_whitney_u_agg,  # noqa: E402
                          parse_rank_test_options, rank_test_batch_device, rank_test_batch_host, rank_test_hooks, wilcoxon_signed_rank,
                          wilcoxon_signed_rank_agg)
+from .sample_tests import (SampleTestAggResult, SampleTestOptions, brown_forsythe, brown_forsythe_agg, brunner_munzel,  # noqa: E402
+                           brunner_munzel_agg, one_way_anova, one_way_anova_agg, paired_t_test, paired_t_test_agg, parse_sample_test_options,
+                           sample_test_batch_device, sample_test_batch_host, sample_test_hooks, t_test, t_test_agg, yuen, yuen_agg)
 from .glmm import (GlmmFitAggResult, GlmmFitPredictAggResult, GlmmOptions, glmm_fit, glmm_fit_agg, glmm_fit_batch_device,  # noqa: E402
                    glmm_fit_batch_host, glmm_fit_predict_agg, glmm_fit_predict_batch_device, glmm_fit_predict_batch_host, glmm_test_hooks,
                    parse_glmm_options)
@@ -84,6 +87,16 @@ SQL_FUNCTIONS.update({
     "anofox_stats_wilcoxon_signed_rank_agg": wilcoxon_signed_rank_agg, "wilcoxon_signed_rank_agg": wilcoxon_signed_rank_agg,
     "anofox_stats_kruskal_wallis": kruskal_wallis, "kruskal_wallis": kruskal_wallis,
     "anofox_stats_kruskal_wallis_agg": kruskal_wallis_agg, "kruskal_wallis_agg": kruskal_wallis_agg,
+    "anofox_stats_t_test": t_test, "t_test": t_test, "anofox_stats_t_test_agg": t_test_agg, "t_test_agg": t_test_agg,
+    "anofox_stats_paired_t_test": paired_t_test, "paired_t_test": paired_t_test,
+    "anofox_stats_paired_t_test_agg": paired_t_test_agg, "paired_t_test_agg": paired_t_test_agg,
+    "anofox_stats_yuen": yuen, "yuen": yuen, "anofox_stats_yuen_agg": yuen_agg, "yuen_agg": yuen_agg,
+    "anofox_stats_one_way_anova": one_way_anova, "one_way_anova": one_way_anova,
+    "anofox_stats_one_way_anova_agg": one_way_anova_agg, "one_way_anova_agg": one_way_anova_agg,
+    "anofox_stats_brown_forsythe": brown_forsythe, "brown_forsythe": brown_forsythe,
+    "anofox_stats_brown_forsythe_agg": brown_forsythe_agg, "brown_forsythe_agg": brown_forsythe_agg,
+    "anofox_stats_brunner_munzel": brunner_munzel, "brunner_munzel": brunner_munzel,
+    "anofox_stats_brunner_munzel_agg": brunner_munzel_agg, "brunner_munzel_agg": brunner_munzel_agg,
     "anofox_stats_glmm_fit": glmm_fit, "glmm_fit": glmm_fit, "anofox_stats_glmm_fit_agg": glmm_fit_agg, "glmm_fit_agg": glmm_fit_agg,
     "anofox_stats_glmm_fit_predict_agg": glmm_fit_predict_agg, "glmm_fit_predict_agg": glmm_fit_predict_agg,
     "anofox_stats_predict": predict,
@@ -134,6 +147,9 @@ __all__ = [
     "RankTestOptions", "RankTestAggResult", "parse_rank_test_options", "mann_whitney_u", "wilcoxon_signed_rank", "kruskal_wallis",
     "mann_whitney_u_agg", "wilcoxon_signed_rank_agg", "kruskal_wallis_agg", "rank_test_batch_host", "rank_test_batch_device",
     "rank_test_hooks",
+    "SampleTestOptions", "SampleTestAggResult", "parse_sample_test_options", "t_test", "paired_t_test", "yuen", "one_way_anova",
+    "brown_forsythe", "brunner_munzel", "t_test_agg", "paired_t_test_agg", "yuen_agg", "one_way_anova_agg", "brown_forsythe_agg",
+    "brunner_munzel_agg", "sample_test_batch_host", "sample_test_batch_device", "sample_test_hooks",
     "GlmmOptions", "GlmmFitAggResult", "parse_glmm_options", "glmm_fit", "glmm_fit_agg", "glmm_fit_batch_host", "glmm_fit_batch_device", "glmm_test_hooks",
     "GlmmFitPredictAggResult", "glmm_fit_predict_agg", "glmm_fit_predict_batch_host", "glmm_fit_predict_batch_device",
 ]

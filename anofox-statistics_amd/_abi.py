@@ -267,6 +267,24 @@ class AnofoxHipRankTestBatchOptions(C.Structure):  # the rank test batch entries
     _fields_ = [("test", C.c_int32), ("alternative", C.c_int32), ("continuity_correction", C.c_int32), ("mu", C.c_double)]
 
 
+class AnofoxAnovaResult(C.Structure):  # anofox_stats_ffi.h:1588-1607, 72 bytes
+    _fields_ = [("f_statistic", C.c_double), ("p_value", C.c_double), ("df_between", C.c_size_t), ("df_within", C.c_size_t),
+                ("ss_between", C.c_double), ("ss_within", C.c_double), ("n_groups", C.c_size_t), ("n", C.c_size_t), ("method", C.c_char_p)]
+
+
+class AnofoxTTestOptions(C.Structure):  # anofox_stats_ffi.h:1682-1691, 32 bytes
+    _fields_ = [("alternative", C.c_int), ("confidence_level", C.c_double), ("var_equal", C.c_bool), ("mu", C.c_double)]
+
+
+class AnofoxBrunnerMunzelOptions(C.Structure):  # anofox_stats_ffi.h:1799-1804, 16 bytes
+    _fields_ = [("alternative", C.c_int), ("confidence_level", C.c_double)]
+
+
+class AnofoxHipSampleTestBatchOptions(C.Structure):  # the sample test batch entries' options, 40 bytes
+    _fields_ = [("test", C.c_int32), ("alternative", C.c_int32), ("kind", C.c_int32), ("mu", C.c_double), ("trim", C.c_double),
+                ("confidence_level", C.c_double)]
+
+
 class AnofoxHipGlmmOptions(C.Structure):  # the batch entries' options (anofox_stats_hip.h), 40 bytes
     _fields_ = [("family", C.c_int), ("fit_intercept", C.c_int), ("reml", C.c_int), ("max_iterations", C.c_uint32),
                 ("tolerance", C.c_double), ("compute_inference", C.c_int), ("confidence_level", C.c_double)]
@@ -635,6 +653,18 @@ SYMBOLS = {
     "anofox_wilcoxon_signed_rank": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxWilcoxonOptions, C.POINTER(AnofoxTestResult), _ERRP]),
     "anofox_kruskal_wallis": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, C.POINTER(AnofoxTestResult), _ERRP]),
     "anofox_free_test_result": (None, [C.POINTER(AnofoxTestResult)]),
+    "anofox_hip_sample_test_record_len": (C.c_size_t, []),
+    "anofox_hip_sample_test_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       AnofoxHipSampleTestBatchOptions, C.c_void_p, _ERRP]),
+    "anofox_hip_sample_test_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _DP, _DP, C.POINTER(C.c_int32),
+                                                     AnofoxHipSampleTestBatchOptions, _DP, _ERRP]),
+    "anofox_hip_sample_test_hooks": (None, [C.c_int64]),
+    "anofox_t_test": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxTTestOptions, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_yuen_test": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, C.c_double, C.c_int, C.c_double, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_brunner_munzel": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxBrunnerMunzelOptions, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_one_way_anova": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, C.POINTER(AnofoxAnovaResult), _ERRP]),
+    "anofox_brown_forsythe": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_free_anova_result": (None, [C.POINTER(AnofoxAnovaResult)]),
     "anofox_hip_glmm_record_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_inference_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_test_hooks": (None, [C.c_int, C.c_int]),

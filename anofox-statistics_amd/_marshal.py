@@ -94,14 +94,16 @@ def device_tensor(t, dtype, n=None, what="tensor", device=None, at_least=False):
 
 def scalar_call(symbol, arrays, options, result, free, fields) -> dict:
     """lib.<symbol>(*arrays as AnofoxDataArray (a None entry is a NULL)[, options], &result) -> {name: result.<field>} for the
-    (name, field) pairs of `fields`, a text decoded; the result is released through lib.<free>.  A failure raises
+    (name, field) pairs of `fields`, a text decoded; the result is released through lib.<free>.  `options`: None, one struct, or
+    a tuple of the arguments that stand in its place.  A failure raises
     InvalidInputException with the library's text and its code in `.code`."""
     from .scalar import _data_array
     lib = _abi.load()
     data = [_data_array(a) for a in arrays]   # (array, what keeps its memory alive)
     res = result()
     try:
-        call(lib, symbol, *[d[0] for d in data], *(() if options is None else (options,)), C.byref(res))
+        call(lib, symbol, *[d[0] for d in data], *(() if options is None else options if isinstance(options, tuple) else (options,)),
+             C.byref(res))
     except AnofoxStatsError as failed:
         e = InvalidInputException(f"{symbol.replace('anofox_', '')} failed: {failed}")
         e.code = failed.code

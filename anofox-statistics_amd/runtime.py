@@ -391,6 +391,16 @@ class Context:
         from .rank_tests import rank_test_batch_host
         return rank_test_batch_host(row_offsets, v, y, sample, test, options, ctx=self)
 
+    def sample_test_batch_device(self, row_offsets, v, y, sample, test: int, options=None, use_current_torch_stream: bool = True):
+        """Grouped t (0), Yuen (1), one-way ANOVA (2), Brown-Forsythe (3) or Brunner-Munzel (4) tests on CUDA tensors
+        (sample_tests.sample_test_batch_device): records[n_groups, 12]."""
+        from .sample_tests import sample_test_batch_device
+        return sample_test_batch_device(self, row_offsets, v, y, sample, test, options, use_current_torch_stream)
+
+    def sample_test_batch_host(self, row_offsets, v, y, sample, test: int, options=None):
+        from .sample_tests import sample_test_batch_host
+        return sample_test_batch_host(row_offsets, v, y, sample, test, options, ctx=self)
+
     def glmm_fit_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False,
                               use_current_torch_stream: bool = True):
         """Grouped Gaussian random-intercept mixed models on CUDA tensors (glmm.glmm_fit_batch_device): (records, inference or None,

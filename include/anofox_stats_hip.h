@@ -646,6 +646,58 @@ ANOFOX_HIP_API bool anofox_kruskal_wallis(AnofoxDataArray values, AnofoxDataArra
                            AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_test_result(AnofoxTestResult *result);
 
+/* replaces AnofoxAnovaResult, anofox_stats_ffi.h:1588-1607 — 72 bytes: f_statistic @0, p_value @8, df_between @16, df_within @24,
+ * ss_between @32, ss_within @40, n_groups @48, n @56, method @64 (malloc'ed by the callee, released by anofox_free_anova_result) */
+typedef struct {
+	double f_statistic;
+	double p_value;
+	size_t df_between;
+	size_t df_within;
+	double ss_between;
+	double ss_within;
+	size_t n_groups;
+	size_t n;
+	char *method; /* "Fisher One-way ANOVA" */
+} AnofoxAnovaResult;
+
+/* replaces AnofoxTTestOptions, anofox_stats_ffi.h:1682-1691 — 32 bytes: alternative @0, confidence_level @8, var_equal @16, mu @24
+ * (NaN: 0) */
+typedef struct {
+	AnofoxAlternative alternative;
+	double confidence_level;
+	bool var_equal; /* true: Student's pooled variance; false: Welch */
+	double mu;
+} AnofoxTTestOptions;
+
+/* replaces AnofoxBrunnerMunzelOptions, anofox_stats_ffi.h:1799-1804 — 16 bytes */
+typedef struct {
+	AnofoxAlternative alternative;
+	double confidence_level;
+} AnofoxBrunnerMunzelOptions;
+
+/* replace anofox_t_test / anofox_brunner_munzel / anofox_one_way_anova / anofox_yuen_test / anofox_brown_forsythe /
+ * anofox_free_anova_result, anofox_stats_ffi.h:1811, 1851, 1857, 2133, 2139 and the ANOVA result's release: one group through
+ * anofox_hip_sample_test_batch_host (below), NULL entries of the validity bitmaps as NaN.  The two-sample scalars take group1 as
+ * sample 1; the k-sample scalars take the group ids as doubles and pair, drop and key them as anofox_kruskal_wallis does.
+ * AnofoxTestResult: statistic, p_value, df, the interval (Brown-Forsythe: NaN) and the confidence level echoed (Brown-Forsythe:
+ * NaN); effect_size NaN but for Brunner-Munzel, whose it is phat; n = n1 + n2, n1, n2 (Brown-Forsythe: N, 0, 0); method
+ * "Welch t-test" / "Student t-test", "Yuen test (trim=0.20)", "Brunner-Munzel test", "Brown-Forsythe test".
+ * False with ANOFOX_ERROR_INVALID_INPUT, the result zeroed and nothing to free, before any device is touched: out_result NULL,
+ * an option the batch entry refuses ("sample test: ..."), "t-test requires at least 2 observations in group 1" (or 2; Yuen test:
+ * 4; Brunner-Munzel test: 2), "ANOVA requires at least 2 groups", "ANOVA requires at least 2 observations per group (group i has
+ * m)" (i in the order of first appearance) and the same two for "Brown-Forsythe test". */
+ANOFOX_HIP_API bool anofox_t_test(AnofoxDataArray group1, AnofoxDataArray group2, AnofoxTTestOptions options, AnofoxTestResult *out_result,
+                   AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_brunner_munzel(AnofoxDataArray group1, AnofoxDataArray group2, AnofoxBrunnerMunzelOptions options,
+                           AnofoxTestResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_one_way_anova(AnofoxDataArray values, AnofoxDataArray groups, AnofoxAnovaResult *out_result,
+                          AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_yuen_test(AnofoxDataArray group1, AnofoxDataArray group2, double trim, AnofoxAlternative alternative,
+                      double confidence_level, AnofoxTestResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_brown_forsythe(AnofoxDataArray values, AnofoxDataArray groups, AnofoxTestResult *out_result,
+                           AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_anova_result(AnofoxAnovaResult *result);
+
 /* replaces AnofoxGlmmFamily, anofox_stats_ffi.h:2433-2440 */
 typedef enum {
 	ANOFOX_GLMM_GAUSSIAN = 0,
@@ -1587,6 +1639,50 @@ ANOFOX_HIP_API bool anofox_hip_rank_test_batch_host(AnofoxHipContext *ctx, int64
                                      const double *v, const double *y, const int32_t *sample,
                                      AnofoxHipRankTestBatchOptions options, double *records, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_hip_rank_test_hooks(int64_t small_cap);
+
+/*
+ * Grouped parametric and studentised-rank tests (t_test_agg, yuen_agg, one_way_anova_agg, brown_forsythe_agg, brunner_munzel_agg and
+ * the five scalars above): R's t.test, Yuen's test, oneway.test, the median-centred Levene test and brunner.munzel.test in closed
+ * form.  The formulas: DESIGN.md §1 "Parametric and studentised-rank tests" and csrc/sample_tests.h.
+ * Input: the layout of the rank tests: row_offsets[n_groups + 1], v (n_rows doubles), y (doubles; the paired t-test only, otherwise
+ * it may be NULL) and sample (int32; every other test, NULL for the paired t-test).  A row is valid when v is not NaN, for the
+ * paired t-test when v - y - mu is not NaN (infinities stay in).  The two-sample tests (t, Yuen, Brunner-Munzel) take sample == 0
+ * as sample 1 and every other id as sample 2; the k-sample tests (ANOVA, Brown-Forsythe) take any int32 ids.
+ * Output: records[g * 12] = {statistic, p_value, df, df2, estimate, ci_lower, ci_upper, n, n1, n2, aux, status}.  t-test and Yuen:
+ * estimate the difference of the (trimmed) means, aux its standard error; the paired t-test: n = n1 = n2 = the valid pairs.
+ * ANOVA and Brown-Forsythe: statistic F on (df, df2), estimate SSB, aux SSW, n1 = k, n2 and the interval NaN.  Brunner-Munzel:
+ * estimate phat = P(X1 < X2) + P(X1 = X2) / 2 with its two-sided interval, aux its standard error.
+ * Status per group: 0; ANOFOX_ERROR_INSUFFICIENT_DATA 6 (an arm below 2 rows; Yuen: below 4, or fewer than 2 left after trimming;
+ * fewer than 2 valid pairs; k < 2), which makes every field but the counts NaN.  A zero standard error has status 0 with statistic,
+ * p_value, df and the interval NaN; SSW = 0 gives F = +inf, p = 0 (NaN when SSB = 0 too); complete separation gives Brunner-Munzel's
+ * statistic +-inf, p 0 or 1, df NaN and the interval [phat, phat].
+ * The t-test streams each group twice by one wavefront and stages nothing; the other tests work groups of up to 1462 rows in LDS
+ * by one wavefront each, larger ones in the context's workspace (28 bytes per row of the call) by a workgroup of 1024 threads.
+ * Argument errors (false before any device is touched): negative counts, an unknown test, kind or alternative, a mu that is not
+ * finite, a mu != 0 for a test other than the t-test, a trim outside [0, 0.5), a confidence level outside (0, 1) that is not NaN
+ * (NaN: no interval), a NULL array where there are groups, a missing y (paired) or sample (the others) (all "sample test: ..."), and
+ * for the host form offsets that are not non-decreasing within [0, n_rows].  The device form is asynchronous on the context's
+ * stream.
+ * anofox_hip_sample_test_hooks (for tests): small_cap lowers the rows a group may have on the small path for later calls of this
+ * family in the process (the rank test and correlation families keep theirs); 0 restores 1462.
+ */
+typedef struct {
+	int32_t test;        /* 0 t-test, 1 Yuen, 2 one-way ANOVA, 3 Brown-Forsythe, 4 Brunner-Munzel */
+	int32_t alternative; /* AnofoxAlternative; not read by ANOVA and Brown-Forsythe */
+	int32_t kind;        /* t-test: 0 Welch, 1 Student, 2 paired; ANOVA: 0 Fisher, 1 Welch; otherwise 0 */
+	double mu;           /* the t-test's hypothesised difference; 0 otherwise */
+	double trim;         /* Yuen's trimming proportion, in [0, 0.5) */
+	double confidence_level; /* in (0, 1); NaN: no interval */
+} AnofoxHipSampleTestBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_sample_test_record_len(void); /* 12 */
+ANOFOX_HIP_API bool anofox_hip_sample_test_batch_device(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *d_row_offsets,
+                                         const double *d_v, const double *d_y, const int32_t *d_sample,
+                                         AnofoxHipSampleTestBatchOptions options, double *d_records, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_sample_test_batch_host(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *row_offsets,
+                                       const double *v, const double *y, const int32_t *sample,
+                                       AnofoxHipSampleTestBatchOptions options, double *records, AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_hip_sample_test_hooks(int64_t small_cap);
 
 /*
  * Grouped Gaussian linear mixed models with one random intercept (glmm_fit_agg): per panel  y_ij = a_ij'beta + b_j + e_ij,
