@@ -54,6 +54,9 @@ from .rank_tests import (RankTestAggResult, RankTestOptions, kruskal_wallis, kru
 from .sample_tests import (SampleTestAggResult, SampleTestOptions, brown_forsythe, brown_forsythe_agg, brunner_munzel,  # noqa: E402
                            brunner_munzel_agg, one_way_anova, one_way_anova_agg, paired_t_test, paired_t_test_agg, parse_sample_test_options,
                            sample_test_batch_device, sample_test_batch_host, sample_test_hooks, t_test, t_test_agg, yuen, yuen_agg)
+from .normality_tests import (NormalityTestAggResult, dagostino_k2, dagostino_k2_agg, jarque_bera, jarque_bera_agg,  # noqa: E402
+                              normality_test_batch_device, normality_test_batch_host, normality_test_hooks, shapiro_wilk,
+                              shapiro_wilk_agg)
 from .glmm import (GlmmFitAggResult, GlmmFitPredictAggResult, GlmmOptions, glmm_fit, glmm_fit_agg, glmm_fit_batch_device,  # noqa: E402
                    glmm_fit_batch_host, glmm_fit_predict_agg, glmm_fit_predict_batch_device, glmm_fit_predict_batch_host, glmm_test_hooks,
                    parse_glmm_options)
@@ -97,6 +100,12 @@ SQL_FUNCTIONS.update({
     "anofox_stats_brown_forsythe_agg": brown_forsythe_agg, "brown_forsythe_agg": brown_forsythe_agg,
     "anofox_stats_brunner_munzel": brunner_munzel, "brunner_munzel": brunner_munzel,
     "anofox_stats_brunner_munzel_agg": brunner_munzel_agg, "brunner_munzel_agg": brunner_munzel_agg,
+    "anofox_stats_shapiro_wilk": shapiro_wilk, "shapiro_wilk": shapiro_wilk,
+    "anofox_stats_shapiro_wilk_agg": shapiro_wilk_agg, "shapiro_wilk_agg": shapiro_wilk_agg,
+    "anofox_stats_dagostino_k2": dagostino_k2, "dagostino_k2": dagostino_k2,
+    "anofox_stats_dagostino_k2_agg": dagostino_k2_agg, "dagostino_k2_agg": dagostino_k2_agg,
+    "anofox_stats_jarque_bera": jarque_bera, "jarque_bera": jarque_bera,
+    "anofox_stats_jarque_bera_agg": jarque_bera_agg, "jarque_bera_agg": jarque_bera_agg,
     "anofox_stats_glmm_fit": glmm_fit, "glmm_fit": glmm_fit, "anofox_stats_glmm_fit_agg": glmm_fit_agg, "glmm_fit_agg": glmm_fit_agg,
     "anofox_stats_glmm_fit_predict_agg": glmm_fit_predict_agg, "glmm_fit_predict_agg": glmm_fit_predict_agg,
     "anofox_stats_predict": predict,
@@ -150,6 +159,8 @@ __all__ = [
     "SampleTestOptions", "SampleTestAggResult", "parse_sample_test_options", "t_test", "paired_t_test", "yuen", "one_way_anova",
     "brown_forsythe", "brunner_munzel", "t_test_agg", "paired_t_test_agg", "yuen_agg", "one_way_anova_agg", "brown_forsythe_agg",
     "brunner_munzel_agg", "sample_test_batch_host", "sample_test_batch_device", "sample_test_hooks",
+    "NormalityTestAggResult", "shapiro_wilk", "dagostino_k2", "jarque_bera", "shapiro_wilk_agg", "dagostino_k2_agg", "jarque_bera_agg",
+    "normality_test_batch_host", "normality_test_batch_device", "normality_test_hooks",
     "GlmmOptions", "GlmmFitAggResult", "parse_glmm_options", "glmm_fit", "glmm_fit_agg", "glmm_fit_batch_host", "glmm_fit_batch_device", "glmm_test_hooks",
     "GlmmFitPredictAggResult", "glmm_fit_predict_agg", "glmm_fit_predict_batch_host", "glmm_fit_predict_batch_device",
 ]

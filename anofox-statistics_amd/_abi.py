@@ -280,6 +280,14 @@ class AnofoxBrunnerMunzelOptions(C.Structure):  # anofox_stats_ffi.h:1799-1804, 
     _fields_ = [("alternative", C.c_int), ("confidence_level", C.c_double)]
 
 
+class AnofoxJarqueBeraResult(C.Structure):  # anofox_stats_ffi.h:621-632, 40 bytes; nothing to free
+    _fields_ = [("statistic", C.c_double), ("p_value", C.c_double), ("skewness", C.c_double), ("kurtosis", C.c_double), ("n", C.c_size_t)]
+
+
+class AnofoxHipNormalityTestBatchOptions(C.Structure):  # the normality test batch entries' options, 8 bytes
+    _fields_ = [("test", C.c_int32), ("reserved", C.c_int32)]
+
+
 class AnofoxHipSampleTestBatchOptions(C.Structure):  # the sample test batch entries' options, 40 bytes
     _fields_ = [("test", C.c_int32), ("alternative", C.c_int32), ("kind", C.c_int32), ("mu", C.c_double), ("trim", C.c_double),
                 ("confidence_level", C.c_double)]
@@ -665,6 +673,15 @@ SYMBOLS = {
     "anofox_one_way_anova": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, C.POINTER(AnofoxAnovaResult), _ERRP]),
     "anofox_brown_forsythe": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, C.POINTER(AnofoxTestResult), _ERRP]),
     "anofox_free_anova_result": (None, [C.POINTER(AnofoxAnovaResult)]),
+    "anofox_hip_normality_test_record_len": (C.c_size_t, []),
+    "anofox_hip_normality_test_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, AnofoxHipNormalityTestBatchOptions,
+                                                          C.c_void_p, _ERRP]),
+    "anofox_hip_normality_test_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _DP, AnofoxHipNormalityTestBatchOptions,
+                                                        _DP, _ERRP]),
+    "anofox_hip_normality_test_hooks": (None, [C.c_int64]),
+    "anofox_shapiro_wilk": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_dagostino_k2": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_jarque_bera": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxJarqueBeraResult), _ERRP]),
     "anofox_hip_glmm_record_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_inference_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_test_hooks": (None, [C.c_int, C.c_int]),

@@ -94,9 +94,8 @@ def device_tensor(t, dtype, n=None, what="tensor", device=None, at_least=False):
 
 def scalar_call(symbol, arrays, options, result, free, fields) -> dict:
     """lib.<symbol>(*arrays as AnofoxDataArray (a None entry is a NULL)[, options], &result) -> {name: result.<field>} for the
-    (name, field) pairs of `fields`, a text decoded; the result is released through lib.<free>.  `options`: None, one struct, or
-    a tuple of the arguments that stand in its place.  A failure raises
-    InvalidInputException with the library's text and its code in `.code`."""
+    (name, field) pairs of `fields`, a text decoded; the result is released through lib.<free> (None: it holds no memory).
+    `options`: None, one struct, or a tuple of the arguments that stand in its place.  A failure raises InvalidInputException with the library's text and its code in `.code`."""
     from .scalar import _data_array
     lib = _abi.load()
     data = [_data_array(a) for a in arrays]   # (array, what keeps its memory alive)
@@ -112,7 +111,8 @@ def scalar_call(symbol, arrays, options, result, free, fields) -> dict:
         values = [(name, getattr(res, field)) for name, field in fields]
         return {name: v.decode() if isinstance(v, bytes) else v for name, v in values}
     finally:
-        getattr(lib, free)(C.byref(res))
+        if free is not None:
+            getattr(lib, free)(C.byref(res))
 
 
 def column(values) -> np.ndarray:

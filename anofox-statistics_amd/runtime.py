@@ -401,6 +401,16 @@ class Context:
         from .sample_tests import sample_test_batch_host
         return sample_test_batch_host(row_offsets, v, y, sample, test, options, ctx=self)
 
+    def normality_test_batch_device(self, row_offsets, v, test: int, use_current_torch_stream: bool = True):
+        """Grouped Shapiro-Wilk (0), D'Agostino K2 (1) or Jarque-Bera (2) tests on CUDA tensors
+        (normality_tests.normality_test_batch_device): records[n_groups, 8]."""
+        from .normality_tests import normality_test_batch_device
+        return normality_test_batch_device(self, row_offsets, v, test, use_current_torch_stream)
+
+    def normality_test_batch_host(self, row_offsets, v, test: int):
+        from .normality_tests import normality_test_batch_host
+        return normality_test_batch_host(row_offsets, v, test, ctx=self)
+
     def glmm_fit_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False,
                               use_current_torch_stream: bool = True):
         """Grouped Gaussian random-intercept mixed models on CUDA tensors (glmm.glmm_fit_batch_device): (records, inference or None,

@@ -698,6 +698,29 @@ ANOFOX_HIP_API bool anofox_brown_forsythe(AnofoxDataArray values, AnofoxDataArra
                            AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_anova_result(AnofoxAnovaResult *result);
 
+/* replaces AnofoxJarqueBeraResult, anofox_stats_ffi.h:621-632 — 40 bytes: four doubles @0..24, n @32; nothing to free */
+typedef struct {
+	double statistic;
+	double p_value;
+	double skewness;
+	double kurtosis; /* excess */
+	size_t n;
+} AnofoxJarqueBeraResult;
+
+/* replace anofox_shapiro_wilk / anofox_dagostino_k2 / anofox_jarque_bera, anofox_stats_ffi.h:1817, 1822 and 642: one group through
+ * anofox_hip_normality_test_batch_host (below), NULL entries of the validity bitmap as NaN (rows that are not valid).
+ * AnofoxTestResult: statistic (W or K2), p_value, df NaN (K2: 2.0), effect_size, the interval and the confidence level NaN,
+ * n the valid rows, n1 = n2 = 0, alternative two-sided, method "Shapiro-Wilk test" / "D'Agostino K-squared test" (released by
+ * anofox_free_test_result).
+ * False, the result zeroed and nothing to free: out_result NULL (ANOFOX_ERROR_INVALID_INPUT); before any device is touched
+ * "Shapiro-Wilk test requires at least 3 observations", "D'Agostino K-squared test requires at least 8 observations",
+ * "Jarque-Bera test requires at least 3 observations" (ANOFOX_ERROR_INSUFFICIENT_DATA) and "Shapiro-Wilk test is limited to
+ * n <= 5000" (ANOFOX_ERROR_INVALID_INPUT); "Data has zero variance" (ANOFOX_ERROR_INVALID_INPUT) for K2 and Jarque-Bera of
+ * values that are all equal.  Constant data gives Shapiro-Wilk W = 1 and p = 1. */
+ANOFOX_HIP_API bool anofox_shapiro_wilk(AnofoxDataArray data, AnofoxTestResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_dagostino_k2(AnofoxDataArray data, AnofoxTestResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_jarque_bera(AnofoxDataArray data, AnofoxJarqueBeraResult *out_result, AnofoxError *out_error);
+
 /* replaces AnofoxGlmmFamily, anofox_stats_ffi.h:2433-2440 */
 typedef enum {
 	ANOFOX_GLMM_GAUSSIAN = 0,
@@ -1683,6 +1706,40 @@ ANOFOX_HIP_API bool anofox_hip_sample_test_batch_host(AnofoxHipContext *ctx, int
                                        const double *v, const double *y, const int32_t *sample,
                                        AnofoxHipSampleTestBatchOptions options, double *records, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_hip_sample_test_hooks(int64_t small_cap);
+
+/*
+ * Grouped normality tests (shapiro_wilk_agg, dagostino_k2_agg, jarque_bera_agg and the three scalars above): the Shapiro-Wilk test
+ * as Royston's Algorithm AS R94 (R's swilk.c, scipy.stats.shapiro), D'Agostino's K2 as scipy.stats.normaltest, and the Jarque-Bera
+ * test.  The formulas: DESIGN.md §1 "Normality tests" and csrc/normality_tests.h.
+ * Input: row_offsets[n_groups + 1], group g owns rows [off[g], off[g + 1]) of v (n_rows doubles).  A row is valid when v is not NaN;
+ * infinities stay in and make the moments (and W) NaN.  n = a group's valid rows.
+ * Output: records[g * 8] = {statistic (W, K2 or JB), p_value, skewness, kurtosis (excess), z_skewness, z_kurtosis, n, status}.
+ * Shapiro-Wilk defines the first two, Jarque-Bera the first four, K2 all six; a field a test does not define is NaN.
+ * Status per group: 0; ANOFOX_ERROR_INSUFFICIENT_DATA 6 (Shapiro-Wilk and Jarque-Bera n < 3, K2 n < 8); ANOFOX_ERROR_INVALID_INPUT 1
+ * (Shapiro-Wilk n > 5000; K2 and Jarque-Bera of values that are all equal, m2 <= 0).  Either makes every field but n NaN.
+ * Shapiro-Wilk of values that are all equal has status 0 with W = 1 and p = 1.
+ * Jarque-Bera and K2 stream each group twice by one wavefront and stage nothing; Shapiro-Wilk works groups of up to 1462 rows in LDS
+ * by one wavefront each, larger ones in the context's workspace (28 bytes per row of the call) by a workgroup of 1024 threads,
+ * and gives the same W to the bit on both paths.
+ * Argument errors (false before any device is touched): negative counts, an unknown test, a NULL array where there are groups
+ * (all "normality test: ..."), and for the host form offsets that are not non-decreasing within [0, n_rows].  The device form is
+ * asynchronous on the context's stream.
+ * anofox_hip_normality_test_hooks (for tests): small_cap lowers the rows a group may have on the small path for later calls of
+ * this family in the process (the correlation, rank test and sample test families keep theirs); 0 restores 1462.
+ */
+typedef struct {
+	int32_t test; /* 0 Shapiro-Wilk, 1 D'Agostino K2, 2 Jarque-Bera */
+	int32_t reserved; /* padding to 8 bytes; not read */
+} AnofoxHipNormalityTestBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_normality_test_record_len(void); /* 8 */
+ANOFOX_HIP_API bool anofox_hip_normality_test_batch_device(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *d_row_offsets,
+                                            const double *d_v, AnofoxHipNormalityTestBatchOptions options, double *d_records,
+                                            AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_normality_test_batch_host(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *row_offsets,
+                                          const double *v, AnofoxHipNormalityTestBatchOptions options, double *records,
+                                          AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_hip_normality_test_hooks(int64_t small_cap);
 
 /*
  * Grouped Gaussian linear mixed models with one random intercept (glmm_fit_agg): per panel  y_ij = a_ij'beta + b_j + e_ij,
