@@ -57,6 +57,10 @@ from .sample_tests import (SampleTestAggResult, SampleTestOptions, brown_forsyth
 from .normality_tests import (NormalityTestAggResult, dagostino_k2, dagostino_k2_agg, jarque_bera, jarque_bera_agg,  # noqa: E402
                               normality_test_batch_device, normality_test_batch_host, normality_test_hooks, shapiro_wilk,
                               shapiro_wilk_agg)
+from .categorical_tests import (CategoricalTestAggResult, CategoricalTestOptions, categorical_test_batch_device,  # noqa: E402
+                                categorical_test_batch_host, categorical_test_hooks, chisq_test, chisq_test_agg, contingency_coef,
+                                contingency_coef_agg, cramers_v, cramers_v_agg, fisher_exact, fisher_exact_agg, g_test, g_test_agg,
+                                mcnemar_agg, mcnemar_test, parse_categorical_test_options, phi_coefficient, phi_coefficient_agg)
 from .glmm import (GlmmFitAggResult, GlmmFitPredictAggResult, GlmmOptions, glmm_fit, glmm_fit_agg, glmm_fit_batch_device,  # noqa: E402
                    glmm_fit_batch_host, glmm_fit_predict_agg, glmm_fit_predict_batch_device, glmm_fit_predict_batch_host, glmm_test_hooks,
                    parse_glmm_options)
@@ -106,6 +110,19 @@ SQL_FUNCTIONS.update({
     "anofox_stats_dagostino_k2_agg": dagostino_k2_agg, "dagostino_k2_agg": dagostino_k2_agg,
     "anofox_stats_jarque_bera": jarque_bera, "jarque_bera": jarque_bera,
     "anofox_stats_jarque_bera_agg": jarque_bera_agg, "jarque_bera_agg": jarque_bera_agg,
+    "anofox_stats_chisq_test": chisq_test, "chisq_test": chisq_test,
+    "anofox_stats_chisq_test_agg": chisq_test_agg, "chisq_test_agg": chisq_test_agg,
+    "anofox_stats_g_test": g_test, "g_test": g_test, "anofox_stats_g_test_agg": g_test_agg, "g_test_agg": g_test_agg,
+    "anofox_stats_fisher_exact": fisher_exact, "fisher_exact": fisher_exact,
+    "anofox_stats_fisher_exact_agg": fisher_exact_agg, "fisher_exact_agg": fisher_exact_agg,
+    "anofox_stats_mcnemar_test": mcnemar_test, "mcnemar_test": mcnemar_test,
+    "anofox_stats_mcnemar_agg": mcnemar_agg, "mcnemar_agg": mcnemar_agg,
+    "anofox_stats_cramers_v": cramers_v, "cramers_v": cramers_v,
+    "anofox_stats_cramers_v_agg": cramers_v_agg, "cramers_v_agg": cramers_v_agg,
+    "anofox_stats_phi_coefficient": phi_coefficient, "phi_coefficient": phi_coefficient,
+    "anofox_stats_phi_coefficient_agg": phi_coefficient_agg, "phi_coefficient_agg": phi_coefficient_agg,
+    "anofox_stats_contingency_coef": contingency_coef, "contingency_coef": contingency_coef,
+    "anofox_stats_contingency_coef_agg": contingency_coef_agg, "contingency_coef_agg": contingency_coef_agg,
     "anofox_stats_glmm_fit": glmm_fit, "glmm_fit": glmm_fit, "anofox_stats_glmm_fit_agg": glmm_fit_agg, "glmm_fit_agg": glmm_fit_agg,
     "anofox_stats_glmm_fit_predict_agg": glmm_fit_predict_agg, "glmm_fit_predict_agg": glmm_fit_predict_agg,
     "anofox_stats_predict": predict,
@@ -161,6 +178,10 @@ __all__ = [
     "brunner_munzel_agg", "sample_test_batch_host", "sample_test_batch_device", "sample_test_hooks",
     "NormalityTestAggResult", "shapiro_wilk", "dagostino_k2", "jarque_bera", "shapiro_wilk_agg", "dagostino_k2_agg", "jarque_bera_agg",
     "normality_test_batch_host", "normality_test_batch_device", "normality_test_hooks",
+    "CategoricalTestOptions", "CategoricalTestAggResult", "parse_categorical_test_options", "chisq_test", "g_test", "fisher_exact",
+    "mcnemar_test", "cramers_v", "phi_coefficient", "contingency_coef", "chisq_test_agg", "g_test_agg", "fisher_exact_agg", "mcnemar_agg",
+    "cramers_v_agg", "phi_coefficient_agg", "contingency_coef_agg", "categorical_test_batch_host", "categorical_test_batch_device",
+    "categorical_test_hooks",
     "GlmmOptions", "GlmmFitAggResult", "parse_glmm_options", "glmm_fit", "glmm_fit_agg", "glmm_fit_batch_host", "glmm_fit_batch_device", "glmm_test_hooks",
     "GlmmFitPredictAggResult", "glmm_fit_predict_agg", "glmm_fit_predict_batch_host", "glmm_fit_predict_batch_device",
 ]

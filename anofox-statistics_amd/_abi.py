@@ -288,6 +288,23 @@ class AnofoxHipNormalityTestBatchOptions(C.Structure):  # the normality test bat
     _fields_ = [("test", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AnofoxChiSquareResult(C.Structure):  # anofox_stats_ffi.h:1634-1643, 32 bytes; method released by anofox_free_chisq_result
+    _fields_ = [("statistic", C.c_double), ("p_value", C.c_double), ("df", C.c_size_t), ("method", C.c_char_p)]
+
+
+class AnofoxChiSquareOptions(C.Structure):  # anofox_stats_ffi.h:1743-1746, 1 byte
+    _fields_ = [("correction", C.c_bool)]
+
+
+class AnofoxFisherExactOptions(C.Structure):  # anofox_stats_ffi.h:1751-1756, 16 bytes
+    _fields_ = [("alternative", C.c_int), ("confidence_level", C.c_double)]
+
+
+class AnofoxHipCategoricalTestBatchOptions(C.Structure):  # the categorical test batch entries' options, 24 bytes
+    _fields_ = [("test", C.c_int32), ("alternative", C.c_int32), ("correction", C.c_int32), ("exact", C.c_int32),
+                ("confidence_level", C.c_double)]
+
+
 class AnofoxHipSampleTestBatchOptions(C.Structure):  # the sample test batch entries' options, 40 bytes
     _fields_ = [("test", C.c_int32), ("alternative", C.c_int32), ("kind", C.c_int32), ("mu", C.c_double), ("trim", C.c_double),
                 ("confidence_level", C.c_double)]
@@ -682,6 +699,22 @@ SYMBOLS = {
     "anofox_shapiro_wilk": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxTestResult), _ERRP]),
     "anofox_dagostino_k2": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxTestResult), _ERRP]),
     "anofox_jarque_bera": (C.c_bool, [AnofoxDataArray, C.POINTER(AnofoxJarqueBeraResult), _ERRP]),
+    "anofox_hip_categorical_test_record_len": (C.c_size_t, []),
+    "anofox_hip_categorical_test_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                            AnofoxHipCategoricalTestBatchOptions, C.c_void_p, _ERRP]),
+    "anofox_hip_categorical_test_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                                          C.POINTER(C.c_int32), AnofoxHipCategoricalTestBatchOptions, _DP, _ERRP]),
+    "anofox_hip_categorical_test_hooks": (None, [C.c_int64]),
+    "anofox_chisq_test": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxChiSquareOptions, C.POINTER(AnofoxChiSquareResult), _ERRP]),
+    "anofox_free_chisq_result": (None, [C.POINTER(AnofoxChiSquareResult)]),
+    "anofox_g_test": (C.c_bool, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(AnofoxChiSquareResult), _ERRP]),
+    "anofox_cramers_v": (C.c_bool, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t, _DP, _ERRP]),
+    "anofox_contingency_coef": (C.c_bool, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t, _DP, _ERRP]),
+    "anofox_phi_coefficient": (C.c_bool, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, _DP, _ERRP]),
+    "anofox_fisher_exact": (C.c_bool, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, AnofoxFisherExactOptions,
+                                       C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_mcnemar_test": (C.c_bool, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_bool, C.c_bool,
+                                       C.POINTER(AnofoxChiSquareResult), _ERRP]),
     "anofox_hip_glmm_record_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_inference_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_test_hooks": (None, [C.c_int, C.c_int]),

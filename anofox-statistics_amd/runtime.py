@@ -411,6 +411,16 @@ class Context:
         from .normality_tests import normality_test_batch_host
         return normality_test_batch_host(row_offsets, v, test, ctx=self)
 
+    def categorical_test_batch_device(self, row_offsets, a, b, test: int, options=None, use_current_torch_stream: bool = True):
+        """Grouped chi-square (0), G (1), Fisher exact (2) or McNemar (3) tests of two int32 label columns on CUDA tensors
+        (categorical_tests.categorical_test_batch_device): records[n_groups, 12]."""
+        from .categorical_tests import categorical_test_batch_device
+        return categorical_test_batch_device(self, row_offsets, a, b, test, options, use_current_torch_stream)
+
+    def categorical_test_batch_host(self, row_offsets, a, b, test: int, options=None):
+        from .categorical_tests import categorical_test_batch_host
+        return categorical_test_batch_host(row_offsets, a, b, test, options, ctx=self)
+
     def glmm_fit_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False,
                               use_current_torch_stream: bool = True):
         """Grouped Gaussian random-intercept mixed models on CUDA tensors (glmm.glmm_fit_batch_device): (records, inference or None,

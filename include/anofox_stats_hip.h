@@ -721,6 +721,54 @@ ANOFOX_HIP_API bool anofox_shapiro_wilk(AnofoxDataArray data, AnofoxTestResult *
 ANOFOX_HIP_API bool anofox_dagostino_k2(AnofoxDataArray data, AnofoxTestResult *out_result, AnofoxError *out_error);
 ANOFOX_HIP_API bool anofox_jarque_bera(AnofoxDataArray data, AnofoxJarqueBeraResult *out_result, AnofoxError *out_error);
 
+/* replaces AnofoxChiSquareResult, anofox_stats_ffi.h:1634-1643 — 32 bytes: statistic @0, p_value @8, df @16, method @24 (malloc'ed
+ * by the callee, released by anofox_free_chisq_result) */
+typedef struct {
+	double statistic;
+	double p_value;
+	size_t df;
+	char *method;
+} AnofoxChiSquareResult;
+
+/* replaces AnofoxChiSquareOptions, anofox_stats_ffi.h:1743-1746 — 1 byte */
+typedef struct {
+	bool correction; /* Yates' correction on a 2 x 2 table */
+} AnofoxChiSquareOptions;
+
+/* replaces AnofoxFisherExactOptions, anofox_stats_ffi.h:1751-1756 — 16 bytes: alternative @0, confidence_level @8 */
+typedef struct {
+	AnofoxAlternative alternative;
+	double confidence_level; /* in (0, 1); NaN: no interval */
+} AnofoxFisherExactOptions;
+
+/* replace anofox_chisq_test, anofox_fisher_exact, anofox_cramers_v, anofox_g_test, anofox_mcnemar_test, anofox_phi_coefficient,
+ * anofox_contingency_coef and anofox_free_chisq_result, anofox_stats_ffi.h:1869, 1875, 2009, 2022, 2029, 2036, 2041 and 2203.  The
+ * definitions: the grouped categorical tests below, DESIGN.md §1 "Categorical tests".
+ * anofox_chisq_test: rows where either entry is NaN or not valid are dropped, the labels are cast as `value as usize` casts them
+ * (toward zero, negative values to 0), and the group goes through anofox_hip_categorical_test_batch_host; the table is that of the
+ * labels that occur (the reference sizes its table by the largest label).  method "Pearson's Chi-squared test".
+ * The table-taking entries read a table flattened row by row, row i with row_lengths[i] cells; empty rows and columns are dropped.
+ * They and the cell-taking entries ([[a, b], [c, d]]) touch no device.  anofox_fisher_exact: statistic = the sample odds ratio
+ * a d/(b c), effect_size = the conditional maximum-likelihood odds ratio, ci_lower / ci_upper its exact interval at
+ * options.confidence_level (one-sided for a one-sided alternative), df NaN, n = a + b + c + d, n1 = n2 = 0, method "Fisher's exact
+ * test" (released by anofox_free_test_result).  anofox_mcnemar_test: df 1, or 0 with exact (the statistic is then NaN).
+ * False, the result zeroed and nothing to free: out_result NULL, "Invalid table data" (a NULL table or no rows), a table with
+ * fewer than 2 occupied rows or columns, an unknown alternative or a confidence level outside (0, 1) that is not NaN
+ * (ANOFOX_ERROR_INVALID_INPUT); "No valid data pairs" and an all-zero 2 x 2 table (ANOFOX_ERROR_INSUFFICIENT_DATA). */
+ANOFOX_HIP_API bool anofox_chisq_test(AnofoxDataArray row_var, AnofoxDataArray col_var, AnofoxChiSquareOptions options,
+                       AnofoxChiSquareResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_fisher_exact(size_t a, size_t b, size_t c, size_t d, AnofoxFisherExactOptions options, AnofoxTestResult *out_result,
+                         AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_cramers_v(const size_t *table, const size_t *row_lengths, size_t n_rows, double *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_g_test(const size_t *table, const size_t *row_lengths, size_t n_rows, AnofoxChiSquareResult *out_result,
+                   AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_mcnemar_test(size_t a, size_t b, size_t c, size_t d, bool correction, bool exact, AnofoxChiSquareResult *out_result,
+                         AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_phi_coefficient(size_t a, size_t b, size_t c, size_t d, double *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_contingency_coef(const size_t *table, const size_t *row_lengths, size_t n_rows, double *out_result,
+                             AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_free_chisq_result(AnofoxChiSquareResult *result);
+
 /* replaces AnofoxGlmmFamily, anofox_stats_ffi.h:2433-2440 */
 typedef enum {
 	ANOFOX_GLMM_GAUSSIAN = 0,
@@ -1740,6 +1788,57 @@ ANOFOX_HIP_API bool anofox_hip_normality_test_batch_host(AnofoxHipContext *ctx, 
                                           const double *v, AnofoxHipNormalityTestBatchOptions options, double *records,
                                           AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_hip_normality_test_hooks(int64_t small_cap);
+
+/*
+ * Grouped categorical tests (chisq_test_agg, g_test_agg, fisher_exact_agg, mcnemar_agg, cramers_v_agg, phi_coefficient_agg,
+ * contingency_coef_agg and the scalars above): the chi-square test of independence with Cramer's V, Pearson's C and phi, the
+ * G-test, Fisher's exact test of a 2 x 2 table as R's fisher.test, and McNemar's test.  The formulas: DESIGN.md §1 "Categorical
+ * tests" and csrc/categorical_tests.h.
+ * Input: row_offsets[n_groups + 1], group g owns rows [off[g], off[g + 1]) of the int32 columns a (the row variable) and b (the
+ * column variable), n_rows each.  A row is valid unless either entry is INT32_MIN, the NULL of this family; every other int32 is
+ * a label.
+ * Output: records[g * 12] = {statistic, p_value, df, estimate, ci_lower, ci_upper, n, n_row_levels, n_col_levels, aux, aux2,
+ * status}.
+ *   test 0, chi-square: X2 (Yates' form with `correction` on a 2 x 2 table, the correction clipped to |O - E|), df = (r - 1)(c - 1),
+ *     estimate = Cramer's V, aux = Pearson's C, aux2 = phi (2 x 2 tables, signed by ascending label order; else NaN), all three
+ *     from the uncorrected X2.  The table is that of the distinct labels: there are no empty margins.
+ *   test 1, G: 2 sum O ln(O/E); estimate, aux, aux2 NaN.
+ *   test 2, Fisher: only rows with both labels in {0, 1} are counted.  statistic = the sample odds ratio, p for `alternative`
+ *     (two-sided: the probabilities <= the observed one times 1 + 1e-7), estimate = the conditional maximum-likelihood odds ratio,
+ *     ci_lower / ci_upper its exact interval at confidence_level (NaN: none; one-sided for a one-sided alternative), df NaN, the
+ *     level counts 2.
+ *   test 3, McNemar: a label of 0 against every other label; b = n01, c = n10.  (|b - c| - 1)^2/(b + c) with `correction`, else
+ *     (b - c)^2/(b + c), df 1; with `exact` the binomial p min(1, 2 P(X <= min(b, c))), statistic and df NaN.  estimate = b/c,
+ *     aux = b, aux2 = c, the level counts 2.  b + c = 0: status 0, statistic and p NaN.
+ *   The interval fields are NaN but for Fisher.
+ * Status per group: 0; ANOFOX_ERROR_INSUFFICIENT_DATA 6 (no valid row; tests 0 and 1: fewer than 2 distinct labels on either
+ * side; tests 2 and 3: no counted row), which makes every field but n and the two level counts NaN.
+ * Fisher and McNemar stream each group once by one wavefront and stage nothing; the chi-square and the G-test work groups of up to
+ * 1462 rows in LDS by one wavefront each, larger ones in the context's workspace (28 bytes per row of the call) by a workgroup of
+ * 1024 threads, and give the same record to the bit on both paths.  No dense table is built: the number of labels is bounded by
+ * the rows alone.
+ * Argument errors (false before any device is touched, all "categorical test: ..."): negative counts, an unknown test or
+ * alternative, a confidence level outside (0, 1) that is not NaN, a NULL array where there are groups, and for the host form
+ * offsets that are not non-decreasing within [0, n_rows].  The device form is asynchronous on the context's stream.
+ * anofox_hip_categorical_test_hooks (for tests): small_cap lowers the rows a group may have on the small path for later calls of
+ * this family in the process (the other families keep theirs); 0 restores 1462.
+ */
+typedef struct {
+	int32_t test;        /* 0 chi-square, 1 G, 2 Fisher exact, 3 McNemar */
+	int32_t alternative; /* AnofoxAlternative; read by Fisher */
+	int32_t correction;  /* != 0: Yates (chi-square, 2 x 2) / Edwards (McNemar) */
+	int32_t exact;       /* != 0: McNemar's binomial p */
+	double confidence_level; /* Fisher's interval; NaN: none */
+} AnofoxHipCategoricalTestBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_categorical_test_record_len(void); /* 12 */
+ANOFOX_HIP_API bool anofox_hip_categorical_test_batch_device(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *d_row_offsets,
+                                              const int32_t *d_a, const int32_t *d_b, AnofoxHipCategoricalTestBatchOptions options,
+                                              double *d_records, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_categorical_test_batch_host(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *row_offsets,
+                                            const int32_t *a, const int32_t *b, AnofoxHipCategoricalTestBatchOptions options,
+                                            double *records, AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_hip_categorical_test_hooks(int64_t small_cap);
 
 /*
  * Grouped Gaussian linear mixed models with one random intercept (glmm_fit_agg): per panel  y_ij = a_ij'beta + b_j + e_ij,
