@@ -121,7 +121,7 @@ GI_DEV double st_normal_upper_quantile(double tail) {
 // t with P(T > t) = tail, 0 < tail < 1, for any df > 0.  The start is the Cornish-Fisher series around the normal quantile
 // (Abramowitz & Stegun 26.7.5), which above df = 1e5 is the answer; below, Newton steps on the tail, kept inside a bracket that
 // every evaluation narrows (a step that leaves it is replaced by the bracket's middle, or by doubling while there is no upper
-// end), until a step is below 1e-8 relative: the tail is convex, the steps converge quadratically, so the step after that one
+// end), until a Newton step is below 1e-8 relative: the tail is convex, the steps converge quadratically, so the step after that one
 // would be below 1e-15.
 RC_CALL double st_t_quantile(double tail, double df) {
 	RC_NO_CONTRACT
@@ -145,10 +145,12 @@ RC_CALL double st_t_quantile(double tail, double df) {
 		if (u > tail) lo = t;
 		else hi = t;
 		const double pdf = exp(lnc - 0.5 * (df + 1.0) * log1p(t * t / df));
-		double tn = t + (u - tail) / pdf;
-		if (!(tn > lo && tn < hi)) tn = glm::gi_finite(hi) ? 0.5 * (lo + hi) : 2.0 * t;
-		if (fabs(tn - t) <= 1e-8 * fabs(tn)) return sign * tn;
-		t = tn;
+		const double tn = t + (u - tail) / pdf;
+		// only a Newton step ends the search.  At the root the step rounds to 0 and tn is the end of the bracket that t has just
+		// become: the bracket is closed here, or the converged t would be given up for the bracket's middle, which within 2e-8
+		// of the start passed for a small step and was returned 1e-8 off.
+		if (tn >= lo && tn <= hi && fabs(tn - t) <= 1e-8 * fabs(tn)) return sign * tn;
+		t = tn > lo && tn < hi ? tn : (glm::gi_finite(hi) ? 0.5 * (lo + hi) : 2.0 * t);
 	}
 	return sign * t;
 }

@@ -77,6 +77,8 @@ def sw_coefficients(n):
 def sw_p(w, w1, n):
     """The p-value of W = 1 - w1 at n rows."""
     if n == 3:
+        if np.isnan(w):                        # (an infinity among the three rows; max() below would turn the NaN into 0)
+            return NAN
         return max(0.0, 6.0 / np.pi * (np.arcsin(np.sqrt(min(w, 1.0))) - np.arcsin(np.sqrt(0.75))))
     if not w1 > 0.0:
         return 1.0 if w1 <= 0.0 else NAN       # (W at or, by rounding, past 1: the limit of the tail)

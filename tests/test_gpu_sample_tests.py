@@ -190,6 +190,19 @@ def test_second_sub_view_on_and_off_a_wavefront_boundary(pkg, n1):
             R.check_records(test, pkg.sample_test_batch_host(call["off"], call["v"], None, s, test), ref)
 
 
+def test_interval_ends_over_many_degrees_of_freedom(pkg):
+    """Regression (found by tests/test_gpu_fuzz_stat_tests.py): the t quantile returned the middle of its bracket, up to 1e-8
+    relative off, where the Newton step at the root rounded to 0; it happened at about one df in 120.  600 Welch groups of 6 to 40
+    rows at three levels: 1800 quantiles at as many real-valued df, every interval end within the bounds."""
+    rng = np.random.default_rng(41)
+    call = _random_call(41, rng.integers(6, 41, 600), ids=(0, 0, 1, -3), rounded=True)
+    for level in (0.9, 0.95, 0.99):
+        got = pkg.sample_test_batch_host(call["off"], call["v"], None, call["sample"], R.T_TEST, pkg.SampleTestOptions(confidence_level=level))
+        ref = R.reference(R.T_TEST, call, confidence_level=level)
+        assert np.sum(ref[:, 11] == 0) >= 550
+        R.check_records(R.T_TEST, got, ref)
+
+
 def test_empty_call_and_empty_groups(pkg):
     none, ids = np.zeros(0), np.zeros(0, np.int32)
     assert pkg.sample_test_batch_host(np.zeros(1, np.int64), none, None, ids, R.ANOVA).shape == (0, 12)

@@ -162,6 +162,21 @@ def test_t_quantile_against_scipy(host_exe):
     assert worst <= 1e-10
 
 
+def test_t_quantile_ends_on_a_newton_step_only(host_exe):
+    """Regression (found by tests/test_gpu_fuzz_stat_tests.py, Yuen and Brunner-Munzel intervals 3e-9 off): at the root the Newton
+    step rounds to 0, the iterate sits on the end of its bracket, and the search took the bracket's middle instead, which it then
+    returned, up to 1e-8 relative off, when the start had been within 2e-8.  6000 quantiles on a dense grid of df: 99 of 12000
+    such points were more than 1e-10 off (worst 9.98e-9 at df = 22.653, tail 0.05); also df = 32 at 0.025, the paired t-test of 33
+    rows."""
+    dfs = np.concatenate([np.linspace(1.5, 60.0, 2000), [22.65303825956489, 32.0]])
+    pairs = [(tail, df) for df in dfs for tail in (0.05, 0.025, 0.005)]
+    got = _run(host_exe, [-1, len(pairs)] + [t for pair in pairs for t in pair], 1)[:, 0]
+    want = np.array([sps.t.isf(tail, df) for tail, df in pairs])
+    worst = np.max(np.abs(got - want) / want)
+    print("t quantile on the grid, worst relative difference %.2e" % worst)
+    assert worst <= 1e-10
+
+
 @pytest.mark.parametrize("name, content", R.CASES)
 def test_both_paths_against_the_restatement(host_sample_test, name, content):
     test = R.TESTS[name]
