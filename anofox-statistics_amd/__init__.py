@@ -61,6 +61,9 @@ from .categorical_tests import (CategoricalTestAggResult, CategoricalTestOptions
                                 categorical_test_batch_host, categorical_test_hooks, chisq_test, chisq_test_agg, contingency_coef,
                                 contingency_coef_agg, cramers_v, cramers_v_agg, fisher_exact, fisher_exact_agg, g_test, g_test_agg,
                                 mcnemar_agg, mcnemar_test, parse_categorical_test_options, phi_coefficient, phi_coefficient_agg)
+from .perm_tests import (PermTestAggResult, PermTestOptions, energy_distance, energy_distance_agg, mmd, mmd_agg,  # noqa: E402
+                         parse_perm_test_options, perm_test_batch_device, perm_test_batch_host, perm_test_hooks, permutation_t_test,
+                         permutation_t_test_agg)
 from .glmm import (GlmmFitAggResult, GlmmFitPredictAggResult, GlmmOptions, glmm_fit, glmm_fit_agg, glmm_fit_batch_device,  # noqa: E402
                    glmm_fit_batch_host, glmm_fit_predict_agg, glmm_fit_predict_batch_device, glmm_fit_predict_batch_host, glmm_test_hooks,
                    parse_glmm_options)
@@ -88,6 +91,11 @@ SQL_FUNCTIONS.update({
     "anofox_stats_pearson": pearson, "pearson": pearson, "anofox_stats_pearson_agg": pearson_agg, "pearson_agg": pearson_agg,
     "anofox_stats_spearman": spearman, "spearman": spearman, "anofox_stats_spearman_agg": spearman_agg, "spearman_agg": spearman_agg,
     "anofox_stats_kendall": kendall, "kendall": kendall, "anofox_stats_kendall_agg": kendall_agg, "kendall_agg": kendall_agg,
+    "anofox_stats_energy_distance": energy_distance, "energy_distance": energy_distance,
+    "anofox_stats_energy_distance_agg": energy_distance_agg, "energy_distance_agg": energy_distance_agg,
+    "anofox_stats_mmd": mmd, "mmd": mmd, "anofox_stats_mmd_agg": mmd_agg, "mmd_agg": mmd_agg,
+    "anofox_stats_permutation_t_test": permutation_t_test, "permutation_t_test": permutation_t_test,
+    "anofox_stats_permutation_t_test_agg": permutation_t_test_agg, "permutation_t_test_agg": permutation_t_test_agg,
     "anofox_stats_mann_whitney_u": mann_whitney_u, "mann_whitney_u": mann_whitney_u,
     "anofox_stats_mann_whitney_u_agg": mann_whitney_u_agg, "mann_whitney_u_agg": mann_whitney_u_agg,
     "anofox_stats_wilcoxon_signed_rank": wilcoxon_signed_rank, "wilcoxon_signed_rank": wilcoxon_signed_rank,
@@ -173,6 +181,8 @@ __all__ = [
     "RankTestOptions", "RankTestAggResult", "parse_rank_test_options", "mann_whitney_u", "wilcoxon_signed_rank", "kruskal_wallis",
     "mann_whitney_u_agg", "wilcoxon_signed_rank_agg", "kruskal_wallis_agg", "rank_test_batch_host", "rank_test_batch_device",
     "rank_test_hooks",
+    "PermTestOptions", "PermTestAggResult", "parse_perm_test_options", "energy_distance", "mmd", "permutation_t_test",
+    "energy_distance_agg", "mmd_agg", "permutation_t_test_agg", "perm_test_batch_host", "perm_test_batch_device", "perm_test_hooks",
     "SampleTestOptions", "SampleTestAggResult", "parse_sample_test_options", "t_test", "paired_t_test", "yuen", "one_way_anova",
     "brown_forsythe", "brunner_munzel", "t_test_agg", "paired_t_test_agg", "yuen_agg", "one_way_anova_agg", "brown_forsythe_agg",
     "brunner_munzel_agg", "sample_test_batch_host", "sample_test_batch_device", "sample_test_hooks",

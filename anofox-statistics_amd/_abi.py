@@ -310,6 +310,18 @@ class AnofoxHipSampleTestBatchOptions(C.Structure):  # the sample test batch ent
                 ("confidence_level", C.c_double)]
 
 
+class AnofoxHipPermTestBatchOptions(C.Structure):  # the permutation test batch entries' options, 32 bytes
+    _fields_ = [("test", C.c_int32), ("alternative", C.c_int32), ("n_permutations", C.c_int64), ("seed", C.c_uint64), ("sigma", C.c_double)]
+
+
+class AnofoxEnergyDistanceOptions(C.Structure):  # anofox_stats_ffi.h:1761-1768, 24 bytes
+    _fields_ = [("n_permutations", C.c_size_t), ("seed", C.c_uint64), ("has_seed", C.c_bool)]
+
+
+class AnofoxMmdOptions(C.Structure):  # anofox_stats_ffi.h:1773-1780, the same 24 bytes
+    _fields_ = AnofoxEnergyDistanceOptions._fields_
+
+
 class AnofoxHipGlmmOptions(C.Structure):  # the batch entries' options (anofox_stats_hip.h), 40 bytes
     _fields_ = [("family", C.c_int), ("fit_intercept", C.c_int), ("reml", C.c_int), ("max_iterations", C.c_uint32),
                 ("tolerance", C.c_double), ("compute_inference", C.c_int), ("confidence_level", C.c_double)]
@@ -715,6 +727,16 @@ SYMBOLS = {
                                        C.POINTER(AnofoxTestResult), _ERRP]),
     "anofox_mcnemar_test": (C.c_bool, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_bool, C.c_bool,
                                        C.POINTER(AnofoxChiSquareResult), _ERRP]),
+    "anofox_hip_perm_test_record_len": (C.c_size_t, []),
+    "anofox_hip_perm_test_batch_device": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     AnofoxHipPermTestBatchOptions, C.c_void_p, _ERRP]),
+    "anofox_hip_perm_test_batch_host": (C.c_bool, [_CTX, C.c_int64, C.c_int64, C.POINTER(C.c_int64), _DP, C.POINTER(C.c_int32),
+                                                   AnofoxHipPermTestBatchOptions, _DP, _ERRP]),
+    "anofox_hip_perm_test_hooks": (None, [C.c_int64]),
+    "anofox_energy_distance": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxEnergyDistanceOptions, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_mmd": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, AnofoxMmdOptions, C.POINTER(AnofoxTestResult), _ERRP]),
+    "anofox_permutation_t_test": (C.c_bool, [AnofoxDataArray, AnofoxDataArray, C.c_int, C.c_size_t, C.c_uint64, C.c_bool,
+                                             C.POINTER(AnofoxTestResult), _ERRP]),
     "anofox_hip_glmm_record_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_inference_len": (C.c_size_t, [C.c_size_t]),
     "anofox_hip_glmm_test_hooks": (None, [C.c_int, C.c_int]),

@@ -421,6 +421,16 @@ class Context:
         from .categorical_tests import categorical_test_batch_host
         return categorical_test_batch_host(row_offsets, a, b, test, options, ctx=self)
 
+    def perm_test_batch_device(self, row_offsets, v, sample, test: int, options=None, use_current_torch_stream: bool = True):
+        """Grouped energy distance (0), permutation t- (1) or MMD (2) tests on CUDA tensors (perm_tests.perm_test_batch_device):
+        records[n_groups, 8].  The options need a seed."""
+        from .perm_tests import perm_test_batch_device
+        return perm_test_batch_device(self, row_offsets, v, sample, test, options, use_current_torch_stream)
+
+    def perm_test_batch_host(self, row_offsets, v, sample, test: int, options=None):
+        from .perm_tests import perm_test_batch_host
+        return perm_test_batch_host(row_offsets, v, sample, test, options, ctx=self)
+
     def glmm_fit_batch_device(self, panel_level_offsets, level_row_offsets, y, x_cols: Sequence, options=None, inference: bool = False,
                               use_current_torch_stream: bool = True):
         """Grouped Gaussian random-intercept mixed models on CUDA tensors (glmm.glmm_fit_batch_device): (records, inference or None,

@@ -851,6 +851,38 @@ ANOFOX_HIP_API bool anofox_glmm_fit(AnofoxDataArray y, const AnofoxDataArray *x,
                      AnofoxGlmmResult *out_result, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_free_glmm_result(AnofoxGlmmResult *result);
 
+/* replaces AnofoxEnergyDistanceOptions, anofox_stats_ffi.h:1761-1768 — 24 bytes: n_permutations @0, seed @8, has_seed @16 */
+typedef struct {
+	size_t n_permutations;
+	uint64_t seed;
+	bool has_seed; /* false: the seed is drawn from the host's entropy */
+} AnofoxEnergyDistanceOptions;
+
+/* replaces AnofoxMmdOptions, anofox_stats_ffi.h:1773-1780 — the same 24 bytes */
+typedef struct {
+	size_t n_permutations;
+	uint64_t seed;
+	bool has_seed;
+} AnofoxMmdOptions;
+
+/* replace anofox_energy_distance / anofox_mmd / anofox_permutation_t_test, anofox_stats_ffi.h:1881, 1887 and 2179: one group
+ * (group1 as sample 1, NaN entries dropped) through anofox_hip_perm_test_batch_host (below); the result is released by
+ * anofox_free_test_result.  method: "Energy distance test (B permutations)", "MMD test (Gaussian kernel, B permutations)",
+ * "Permutation t-test (B permutations)".  effect_size is the statistic for the first two, as the reference's wrapper sets it; df is
+ * Welch's df for the t-test (the reference leaves it NaN) and NaN otherwise; the interval and its level are NaN.  The statistics and
+ * the permutation stream are this library's own: a p-value is not the reference's for the same seed.
+ * False with ANOFOX_ERROR_INVALID_INPUT, the result zeroed and nothing to free, before any device is touched: out_result NULL, an
+ * unknown alternative or n_permutations above 1000000 ("permutation test: ..."), "<test> requires at least 2 observations in group
+ * 1" / "... group 2", "<test> is not defined on infinite values", and for MMD more than 1462 observations ("mmd: group too
+ * large"). */
+ANOFOX_HIP_API bool anofox_energy_distance(AnofoxDataArray group1, AnofoxDataArray group2, AnofoxEnergyDistanceOptions options,
+                            AnofoxTestResult *out_result, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_mmd(AnofoxDataArray group1, AnofoxDataArray group2, AnofoxMmdOptions options, AnofoxTestResult *out_result,
+                AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_permutation_t_test(AnofoxDataArray group1, AnofoxDataArray group2, AnofoxAlternative alternative,
+                               size_t n_permutations, uint64_t seed, bool has_seed, AnofoxTestResult *out_result,
+                               AnofoxError *out_error);
+
 #endif /* ANOFOX_STATS_FFI_H */
 
 /* ------------------------------------------------------------------------ */
@@ -1839,6 +1871,45 @@ ANOFOX_HIP_API bool anofox_hip_categorical_test_batch_host(AnofoxHipContext *ctx
                                             const int32_t *a, const int32_t *b, AnofoxHipCategoricalTestBatchOptions options,
                                             double *records, AnofoxError *out_error);
 ANOFOX_HIP_API void anofox_hip_categorical_test_hooks(int64_t small_cap);
+
+/*
+ * Grouped permutation tests (energy_distance_agg, mmd_agg, permutation_t_test_agg and the three scalars below): the energy
+ * distance test (R's eqdist.etest, the V-statistic), the permutation Welch t-test and the biased Gaussian-kernel MMD^2, each with
+ * p = (1 + n_extreme) / (B + 1) over B random relabellings.  The statistics, the permutation stream (a function of seed,
+ * permutation and row alone) and the order of every sum: DESIGN.md §1 "Permutation tests" and csrc/perm_tests.h.
+ * Input: the layout of the rank tests: row_offsets[n_groups + 1], v (n_rows doubles) and sample (int32).  A row is valid when v is
+ * not NaN; sample 1 is sample == 0, sample 2 every other id.
+ * Output: records[g * 8] = {statistic, p_value, aux, n_extreme, n, n1, n2, status}: aux is Welch's df of the observed split
+ * (t-test), sigma (MMD) or NaN (energy distance); n_extreme the permutations at least as extreme as the observed statistic.
+ * n_permutations = 0: the statistic alone, p_value NaN.
+ * Status per group: 0; ANOFOX_ERROR_INSUFFICIENT_DATA 6 (n1 < 2, n2 < 2, or an infinity among the values); 7 ("mmd: group too
+ * large"): an MMD group of more than 1462 rows, because MMD costs O(N^2) per permutation and is built on the small path only.  A
+ * status that is not 0 makes every field but the counts NaN.  An observed t without variance, or a sigma of 0 (more than half of the
+ * pairs tied), has status 0 with statistic and p_value NaN.
+ * A group's record depends on its rows, the options and the seed alone: not on its place in the call, and, for the energy
+ * distance and the t-test, not on the size path (statistic and n_extreme are the same to the bit).
+ * Argument errors (false before any device is touched): negative counts, an unknown test or alternative, n_permutations outside
+ * [0, 1000000], an infinite sigma, a NULL array where there are groups (all "permutation test: ..."), and for the host form offsets
+ * that are not non-decreasing within [0, n_rows].  The device form is asynchronous on the context's stream.
+ * anofox_hip_perm_test_hooks (for tests): small_cap lowers the rows a group may have on the small path for later calls of the
+ * process; 0 restores 1462.
+ */
+typedef struct {
+	int32_t test;        /* 0 energy distance, 1 permutation t-test, 2 MMD */
+	int32_t alternative; /* AnofoxAlternative; read by the t-test alone */
+	int64_t n_permutations;
+	uint64_t seed;
+	double sigma;        /* MMD's kernel width; NaN or <= 0: the median heuristic */
+} AnofoxHipPermTestBatchOptions;
+
+ANOFOX_HIP_API size_t anofox_hip_perm_test_record_len(void); /* 8 */
+ANOFOX_HIP_API bool anofox_hip_perm_test_batch_device(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *d_row_offsets,
+                                       const double *d_v, const int32_t *d_sample, AnofoxHipPermTestBatchOptions options,
+                                       double *d_records, AnofoxError *out_error);
+ANOFOX_HIP_API bool anofox_hip_perm_test_batch_host(AnofoxHipContext *ctx, int64_t n_groups, int64_t n_rows, const int64_t *row_offsets,
+                                     const double *v, const int32_t *sample, AnofoxHipPermTestBatchOptions options, double *records,
+                                     AnofoxError *out_error);
+ANOFOX_HIP_API void anofox_hip_perm_test_hooks(int64_t small_cap);
 
 /*
  * Grouped Gaussian linear mixed models with one random intercept (glmm_fit_agg): per panel  y_ij = a_ij'beta + b_j + e_ij,
